@@ -25,6 +25,10 @@ One JSON line on stdout (rank 0), carrying also
                            with its own roofline block (MFMA and HBM fractions of its dominant kernel)
       seg_hrnet3           the CBAM network val.py:380 instantiates, batch 32 256x256, with its own roofline block.
 
+--dump-outputs DIR writes what the timed path returned in its last timed step, i.e. what a caller of the step
+receives: DIR/keypoints.npy, float32 [N*B, K, 3] (x, y, max heat-map value).  Inputs and weights are seeded, so
+two builds run with the same arguments can be compared output for output.
+
 Other workloads as the headline of an explicit run (never what the driver runs):
     python bench.py --workload w48-bf16        (configs[3])
     python bench.py --variant seg_hrnet3
@@ -84,7 +88,19 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of the headline CPU-baseline row")
     ap.add_argument("--sustained-steps", type=int, default=2000)
     ap.add_argument("--profile-steps", type=int, default=3, help="instrumented forwards for the roofline leg")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (keypoints) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy in float32 (the step's outputs are small: B*K*3 floats per GPU)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def host_cores() -> int:
@@ -322,6 +338,8 @@ def main():
         step = parallel.make_sharded_step(replay_or_eager, n_total) if world > 1 else replay_or_eager
         elapsed, allkp = parallel.timed_steps(step, args.steps, args.warmup, sync=torch.cuda.synchronize, device=dev)
         assert allkp.shape == (n_total, K, 3) and bool(torch.isfinite(allkp).all())
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"keypoints": allkp})
 
         roof = breakdown = None
         if rank == 0:
