@@ -921,13 +921,20 @@ void level_dims(const esahrnet_ctx& c, int h, int w, std::vector<int>& lh, std::
     for (int l = 1; l <= c.max_level; ++l) { lh[l] = (lh[l - 1] + 1) / 2; lw[l] = (lw[l - 1] + 1) / 2; }
 }
 
-int check_shape(const esahrnet_ctx& c, int n, int h, int w) {
+int check_shape(int n, int h, int w) {
     if (n <= 0) return fail("batch must be positive (got %d)", n);
     if (h < 16 || w < 16 || (h & 1) || (w & 1))
         return fail("crop %dx%d: height and width must be even and >= 16 "
                     "(UpsamplingBilinear2d(x2) output must match the crop, seg_hrnet.py:330,469)", h, w);
-    (void)c;
     return 0;
+}
+
+// Device address of tensor `t` in the workspace `ws`.  Without a workspace (the per-shape decisions, op_desc_get) launch
+// parameters are built for their shapes and flags only, and every tensor points at one non-null placeholder: the
+// *_supported() predicates and conv_kernel_name() test some pointers (res, the multi-head outputs) against nullptr.
+char* tensor_ptr(const esahrnet_ctx& c, char* ws, int t) {
+    static char placeholder;
+    return ws ? ws + c.tensors[t].off : &placeholder;
 }
 
 // does this input shape run the second-generation head (ops with alt == 2)?
@@ -952,73 +959,78 @@ bool head2_for_shape(const esahrnet_ctx& c, const std::vector<int>& lh, const st
                                       c.cfg.num_keypoints, ulo);
 }
 
-// first-fit interval allocator over op order; tensors die after their last use
-// is this multi-head group evaluated as ONE launch at this shape?  (depends on the shape only through the kernel's limits)
-bool multi_on_for(const esahrnet_ctx& c, const Multi& m, int n, const std::vector<int>& lh, const std::vector<int>& lw) {
-    esa::ConvParams q{};
+// ConvParams of the multi-head launch of group `m` (conv_s2c32.hip), from the leader's input
+esa::ConvParams multi_params(const esahrnet_ctx& c, const Multi& m, const ShapePlan& sp, char* ws) {
     const Op& o0 = c.ops[m.op[0]];
     const Tensor& ti = c.tensors[o0.in];
     const Tensor& to = c.tensors[o0.out];
-    q.N = n; q.H = lh[ti.level]; q.W = lw[ti.level]; q.OH = lh[to.level]; q.OW = lw[to.level];
-    q.Cinp = ti.Cp; q.Coutp = m.coutp; q.nheads = m.n;
+    esa::ConvParams p{};
+    p.x = tensor_ptr(c, ws, o0.in);
+    p.w = static_cast<const uint4*>(m.w); p.bias = m.bias;
+    p.N = sp.n; p.H = sp.lh[ti.level]; p.W = sp.lw[ti.level]; p.OH = sp.lh[to.level]; p.OW = sp.lw[to.level];
+    p.Cinp = ti.Cp; p.Coutp = m.coutp; p.nheads = m.n;
     for (int k = 0; k < m.n; ++k) {
-        q.hb[k + 1] = q.hb[k] + c.dconvs[c.ops[m.op[k]].dconv].coutp;
-        q.yh[k] = reinterpret_cast<char*>(const_cast<esahrnet_ctx*>(&c));      // only tested against nullptr
+        const Op& ok = c.ops[m.op[k]];
+        p.yh[k] = tensor_ptr(c, ws, ok.out);
+        p.hb[k + 1] = p.hb[k] + c.dconvs[ok.dconv].coutp;
+        p.hrelu[k] = ok.relu;
     }
-    return esa::conv_s2c32_multi_supported(q);
+    return p;
 }
 
-// ConvParams of a convolution op at a shape; `ws` == nullptr: shapes and flags only (pointers that are merely tested
-// against nullptr get a non-null dummy)
-esa::ConvParams conv_params_of(const esahrnet_ctx& c, const Op& o, int n, const std::vector<int>& lh, const std::vector<int>& lw,
-                               char* ws) {
+// ConvParams of a convolution op at a shape
+esa::ConvParams conv_params_of(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, char* ws) {
     const DevConv& d = c.dconvs[o.dconv];
     const Tensor& ti = c.tensors[o.in];
     const Tensor& to = c.tensors[o.out];
     esa::ConvParams p{};
-    char* dummy = reinterpret_cast<char*>(const_cast<esahrnet_ctx*>(&c));
-    p.x = ws ? ws + ti.off : dummy;
-    p.y = ws ? ws + to.off : dummy;
-    p.res = o.res >= 0 ? (ws ? ws + c.tensors[o.res].off : dummy) : nullptr;
+    p.x = tensor_ptr(c, ws, o.in);
+    p.y = tensor_ptr(c, ws, o.out);
+    p.res = o.res >= 0 ? tensor_ptr(c, ws, o.res) : nullptr;
     p.w = static_cast<const uint4*>(d.w); p.bias = d.bias;
-    p.N = n; p.H = lh[ti.level]; p.W = lw[ti.level]; p.OH = lh[to.level]; p.OW = lw[to.level];
+    p.N = sp.n; p.H = sp.lh[ti.level]; p.W = sp.lw[ti.level]; p.OH = sp.lh[to.level]; p.OW = sp.lw[to.level];
     p.Cinp = d.cinp; p.Coutp = d.coutp; p.relu = o.relu; p.out_f32 = d.out_f32 && !c.x6(); p.fmt = c.fmt;      // (fp32-grade: every tensor is plain f32)
     return p;
 }
 
 // is this job group evaluated as ONE launch at this shape?  Every member must be a stream-kernel launch of its own
 // there (the kernel serving a layer depends on the shape only, never on the grouping)
-bool job_on_for(const esahrnet_ctx& c, const JobGroup& g, int n, const std::vector<int>& lh, const std::vector<int>& lw) {
+bool job_on_for(const esahrnet_ctx& c, const JobGroup& g, const ShapePlan& sp) {
     if (c.ops[g.op[0]].kind != OP_CONV) return true;        // CBAM groups: the merged kernel runs every shape its members run
+    const ConvSpec& s0 = c.specs[c.dconvs[c.ops[g.op[0]].dconv].spec];
     esa::ConvParams ps[6];
-    if (c.x6()) {       // fp32-grade mode: conv_x6_jobs_kernel serves every kernel size / stride of the module
-        const ConvSpec& s0 = c.specs[c.dconvs[c.ops[g.op[0]].dconv].spec];
-        for (int k = 0; k < g.n; ++k) {
-            ps[k] = conv_params_of(c, c.ops[g.op[k]], n, lh, lw, nullptr);
-            const ConvSpec& sk = c.specs[c.dconvs[c.ops[g.op[k]].dconv].spec];
-            if (sk.k != s0.k || sk.stride != s0.stride) return false;
-        }
-        return esa::conv_x6_jobs_supported(ps, g.n, s0.k, s0.stride);
-    }
-    if (c.specs[c.dconvs[c.ops[g.op[0]].dconv].spec].k == 1) {
-        for (int k = 0; k < g.n; ++k) ps[k] = conv_params_of(c, c.ops[g.op[k]], n, lh, lw, nullptr);
-        return esa::conv1x1_jobs_supported(ps, g.n);
-    }
     for (int k = 0; k < g.n; ++k) {
-        ps[k] = conv_params_of(c, c.ops[g.op[k]], n, lh, lw, nullptr);
-        const int stride = c.specs[c.dconvs[c.ops[g.op[k]].dconv].spec].stride;
-        if (stride != c.specs[c.dconvs[c.ops[g.op[0]].dconv].spec].stride) return false;
-        if (stride == 1 && !esa::conv_is_stream_s1(ps[k])) return false;
+        ps[k] = conv_params_of(c, c.ops[g.op[k]], sp, nullptr);
+        const ConvSpec& sk = c.specs[c.dconvs[c.ops[g.op[k]].dconv].spec];
+        // fp32-grade mode: conv_x6_jobs_kernel serves every kernel size / stride of the module, but one per launch
+        if (c.x6() ? sk.k != s0.k || sk.stride != s0.stride
+                   : s0.k != 1 && (sk.stride != s0.stride || (sk.stride == 1 && !esa::conv_is_stream_s1(ps[k]))))
+            return false;
     }
-    return esa::conv_jobs_supported(ps, g.n, c.specs[c.dconvs[c.ops[g.op[0]].dconv].spec].stride);
+    if (c.x6()) return esa::conv_x6_jobs_supported(ps, g.n, s0.k, s0.stride);
+    return s0.k == 1 ? esa::conv1x1_jobs_supported(ps, g.n) : esa::conv_jobs_supported(ps, g.n, s0.stride);
 }
 
-int plan_shape(esahrnet_ctx& c, int n, int h, int w) {
-    if (c.sp.n == n && c.sp.h == h && c.sp.w == w && c.sp.keep == c.keep) return 0;
-    if (check_shape(c, n, h, w)) return 1;
+// The per-shape dispatch decisions: level sizes, the head generation, which multi-head and job groups run as one launch.
+// plan_shape adds the workspace offsets of a forward to them; op_desc_get describes the launches they make.
+ShapePlan shape_decisions(const esahrnet_ctx& c, int n, int h, int w) {
     ShapePlan sp;
     sp.n = n; sp.h = h; sp.w = w; sp.keep = c.keep;
     level_dims(c, h, w, sp.lh, sp.lw);
+    sp.head2 = head2_for_shape(c, sp.lh, sp.lw, &sp.head2_ulo);
+    sp.multi_on.assign(c.multis.size(), 0);
+    for (size_t mi = 0; mi < c.multis.size(); ++mi)       // (depends on the shape only through the kernel's limits)
+        sp.multi_on[mi] = esa::conv_s2c32_multi_supported(multi_params(c, c.multis[mi], sp, nullptr)) ? 1 : 0;
+    sp.job_on.assign(c.jobs.size(), 0);
+    for (size_t ji = 0; ji < c.jobs.size(); ++ji) sp.job_on[ji] = job_on_for(c, c.jobs[ji], sp) ? 1 : 0;
+    return sp;
+}
+
+// first-fit interval allocator over op order; tensors die after their last use
+int plan_shape(esahrnet_ctx& c, int n, int h, int w) {
+    if (c.sp.n == n && c.sp.h == h && c.sp.w == w && c.sp.keep == c.keep) return 0;
+    if (check_shape(n, h, w)) return 1;
+    ShapePlan sp = shape_decisions(c, n, h, w);
     // seg_hrnet3's head by linearity (head_gather.hip) stages the tap-product windows of two branches in LDS: a shape it
     // cannot serve is refused HERE with a message, not by a failed launch in the middle of a forward
     for (const Op& o : c.ops)
@@ -1031,12 +1043,7 @@ int plan_shape(esahrnet_ctx& c, int n, int h, int w) {
                 return fail("crop %dx%d: the interpolation windows of seg_hrnet3's last_layer[0] do not fit the gather kernel's LDS "
                             "budget (set ESAHRNET_HEAD3_DIRECT=1 before creating the net for the direct 480-channel 3x3)", h, w);
         }
-    sp.head2 = head2_for_shape(c, sp.lh, sp.lw, &sp.head2_ulo);
     const int active_alt = sp.head2 ? 2 : 1;
-    sp.multi_on.assign(c.multis.size(), 0);
-    for (size_t mi = 0; mi < c.multis.size(); ++mi) sp.multi_on[mi] = multi_on_for(c, c.multis[mi], n, sp.lh, sp.lw) ? 1 : 0;
-    sp.job_on.assign(c.jobs.size(), 0);
-    for (size_t ji = 0; ji < c.jobs.size(); ++ji) sp.job_on[ji] = job_on_for(c, c.jobs[ji], n, sp.lh, sp.lw) ? 1 : 0;
     struct Free { size_t off, len; };
     std::vector<Free> free_list;
     size_t top = 0;
@@ -1476,6 +1483,417 @@ static bool cbam_fused(const esahrnet_ctx& c, int Cp, int hh, int ww) {
     return esa::cbam_spatial_supported(Cp) && ((hh + 15) / 16) * ((ww + 31) / 32) >= 32 && !c.cbam_unfused;
 }
 
+// one CBAM launch as a job description (cbam.hip); kind < 0: nothing to launch (the maps formed inside cbam_spatial, the
+// pooling of the raw stem tensor done by the stem kernel)
+static esa::CbamJob cbam_job(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, char* ws) {
+    auto T = [&](int t) { return tensor_ptr(c, ws, t); };
+    esa::CbamJob q{};
+    q.kind = -1;
+    const Tensor& tx = c.tensors[o.kind == OP_MLP ? o.terms[0] : o.in];
+    const int hh = sp.lh[tx.level], ww = sp.lw[tx.level];
+    q.ap.N = sp.n; q.ap.H = hh; q.ap.W = ww; q.ap.Cp = tx.Cp; q.ap.C = o.nchan; q.ap.fmt = c.fmt;
+    q.HW = hh * ww; q.P = std::min(Builder::POOL_SLABS, q.HW); q.Cr = o.nchan / 16;
+    switch (o.kind) {
+        case OP_POOL:
+            if (o.out == c.stemraw_partial && stem_pools(c, sp.h, sp.w)) break;       // made by the stem kernel
+            q.kind = esa::CBAM_POOL; q.ap.x = T(o.in); q.partial = reinterpret_cast<float*>(T(o.out)); q.ap.C = tx.C;
+            break;
+        case OP_MLP:
+            q.kind = esa::CBAM_MLP; q.partial = reinterpret_cast<float*>(T(o.in)); q.ca = reinterpret_cast<float*>(T(o.out));
+            q.w0 = c.aux[o.aux[0]].dev; q.w2 = c.aux[o.aux[1]].dev;
+            if (const int slabs = o.in == c.stemraw_partial ? stem_pools(c, sp.h, sp.w) : 0) q.P = slabs;   // the stem kernel's
+            break;
+        case OP_MAPS:
+            if (cbam_fused(c, tx.Cp, hh, ww)) break;
+            q.kind = esa::CBAM_MAPS; q.ap.x = T(o.in); q.ap.ca = reinterpret_cast<const float*>(T(o.terms[1]));
+            q.maps = reinterpret_cast<float*>(T(o.out));
+            break;
+        default: {
+            const Tensor& to = c.tensors[o.out];
+            q.kind = cbam_fused(c, tx.Cp, hh, ww) ? esa::CBAM_SPATIAL : esa::CBAM_APPLY;
+            q.ap.x = T(o.in); q.ap.res = o.res >= 0 ? T(o.res) : nullptr;
+            q.ap.ca = reinterpret_cast<const float*>(T(o.terms[1])); q.ap.maps = reinterpret_cast<const float*>(T(o.terms[2]));
+            q.ap.w_sa = c.aux[o.aux[2]].dev; q.ap.y = T(o.out);
+            q.ap.y_pix_bytes = to.Cp * 4; q.ap.y_c0 = o.c0; q.ap.relu = o.relu;
+        }
+    }
+    return q;
+}
+
+// kernel and (printf-formatted) label of an op description
+__attribute__((format(printf, 3, 4)))
+static void describe(esahrnet_op_desc* d, const char* kernel, const char* label, ...) {
+    snprintf(d->kernel, sizeof d->kernel, "%s", kernel);
+    va_list ap;
+    va_start(ap, label);
+    vsnprintf(d->label, sizeof d->label, label, ap);
+    va_end(ap);
+}
+
+// the device buffers of one forward (all nullptr when an op is only described)
+struct Buffers {
+    const void* x;
+    void* heat;
+    char* ws;
+    void* part;
+};
+
+// Op `o` at the shape `sp` decided: every dispatch decision is made here, once, and the launch parameters are built once.
+// desc == nullptr: the op is launched on `stream`.  Otherwise nothing is launched and `desc` (zeroed by the caller) names
+// that launch and counts its algorithmic FLOPs and compulsory HBM bytes; kernel "" when the op launches nothing of its own.
+static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const Buffers& b, hipStream_t stream,
+                  esahrnet_op_desc* desc) {
+    const int n = sp.n, height = sp.h, width = sp.w;
+    const std::vector<int>& lh = sp.lh;
+    const std::vector<int>& lw = sp.lw;
+    if (o.alt != 0 && o.alt != (sp.head2 ? 2 : 1)) {        // the head alternative not used at this shape
+        if (desc) describe(desc, "", "(not used at this shape)");
+        return 0;
+    }
+    auto T = [&](int t) { return tensor_ptr(c, b.ws, t); };
+    auto tbytes = [&](int t) {
+        const Tensor& x = c.tensors[t];
+        const double wpix = x.tlayout ? (double)esa::head_t_xp(lw[x.level]) : (double)lw[x.level];
+        return x.flat ? (double)n * x.flat * 4.0 : (double)n * lh[x.level] * wpix * x.Cp * (double)c.eb();
+    };
+    auto plain = [&](const char* kernel) {      // the seg_hrnet3 plumbing launches: what they read and write
+        describe(desc, kernel, "seg_hrnet3");
+        desc->bytes = (o.in >= 0 ? tbytes(o.in) : 0.0) + (o.out >= 0 ? tbytes(o.out) : 0.0);
+    };
+    int rc = 0;
+    switch (o.kind) {
+        case OP_STEM: {
+            const ConvSpec& s = c.specs[c.spec_stem];
+            esa::StemParams p{static_cast<const float*>(b.x), T(o.out), c.stem_w, c.stem_b,
+                              n, height, width, c.cfg.cin, c.tensors[o.out].Cp, 1, c.fmt};
+            if (desc) {
+                describe(desc, "stem_kernel", "%s", s.name.c_str());
+                desc->flops = 2.0 * n * height * width * s.cout * s.cin * 9;
+                desc->bytes = (double)n * height * width * s.cin * 4 + tbytes(o.out);
+            } else rc = esa::launch_stem(p, stream);
+            break;
+        }
+        case OP_STEMRAW: {
+            esa::StemParams p{static_cast<const float*>(b.x), T(o.out), c.stemraw_w, c.stemraw_b,
+                              n, height, width, c.cfg.cin, c.tensors[o.out].Cp, 0, c.fmt};
+            if (desc) plain("stem_kernel(raw)");
+            else rc = stem_pools(c, height, width) ? esa::launch_stem_pool(p, reinterpret_cast<float*>(T(o.out2)), stream)
+                                                   : esa::launch_stem(p, stream);
+            break;
+        }
+        case OP_POOL: case OP_MLP: case OP_MAPS: case OP_APPLY: {
+            if (o.job >= 0 && sp.job_on[o.job]) {           // the same step of every branch of the module in one launch
+                if (o.jpos > 0 && !desc) break;             // evaluated by the group's leader
+                const JobGroup& g = c.jobs[o.job];
+                esa::CbamJob js[esa::CBAM_MAXJOBS];
+                int nj = 0;
+                double bytes = 0.0;
+                for (int k = 0; k < g.n; ++k) {
+                    const Op& ok = c.ops[g.op[k]];
+                    const esa::CbamJob q = cbam_job(c, ok, sp, b.ws);
+                    if (q.kind < 0) continue;
+                    js[nj++] = q;
+                    if (desc) bytes += (ok.in >= 0 ? tbytes(ok.in) : 0.0) + (ok.out >= 0 ? tbytes(ok.out) : 0.0);
+                }
+                if (!desc) {
+                    if (nj) rc = esa::launch_cbam_jobs(js, nj, stream);
+                } else if (o.jpos > 0 || !nj) {
+                    describe(desc, "", "seg_hrnet3 (%s)", nj ? "in the merged launch" : "inside cbam_spatial");
+                } else {
+                    static const char* names[] = {"cbam_jobs(pool)", "cbam_jobs(mlp)", "cbam_jobs(maps)", "cbam_jobs(apply)"};
+                    describe(desc, names[o.kind - OP_POOL], "seg_hrnet3: %d branches", nj);
+                    desc->bytes = bytes;
+                }
+                break;
+            }
+            const esa::CbamJob q = cbam_job(c, o, sp, b.ws);
+            if (desc) {
+                static const char* names[] = {"pool_partial", "ca_mlp", "cbam_maps", "cbam_apply", "cbam_spatial"};
+                if (q.kind >= 0) plain(names[q.kind]);
+                else describe(desc, "", "%s", o.kind == OP_POOL ? "seg_hrnet3 (inside stem_kernel(raw))" : "(inside cbam_spatial)");
+                break;
+            }
+            switch (q.kind) {
+                case esa::CBAM_POOL: rc = esa::launch_pool_partial(q.ap.x, q.partial, n, q.HW, q.ap.Cp, q.P, stream, c.fmt); break;
+                case esa::CBAM_MLP:
+                    rc = esa::launch_ca_mlp(q.partial, q.w0, q.w2, q.ca, n, q.HW, q.ap.C, q.ap.Cp, q.Cr, q.P, stream);
+                    break;
+                case esa::CBAM_MAPS: rc = esa::launch_cbam_maps(q.ap.x, q.ap.ca, q.maps, n, q.HW, q.ap.C, q.ap.Cp, stream, c.fmt); break;
+                case esa::CBAM_APPLY: rc = esa::launch_cbam_apply(q.ap, stream); break;
+                case esa::CBAM_SPATIAL: rc = esa::launch_cbam_spatial(q.ap, stream); break;
+                default: break;
+            }
+            break;
+        }
+        case OP_RESAMPLE: {
+            const Tensor& ti = c.tensors[o.in];
+            const Tensor& to = c.tensors[o.out];
+            esa::ResampleParams p{};
+            p.x = T(o.in); p.y = T(o.out); p.N = n;
+            p.h = lh[ti.level]; p.w = lw[ti.level]; p.H = lh[to.level]; p.W = lw[to.level];
+            p.C = o.nchan; p.Cp_src = ti.Cp; p.y_pix_bytes = to.Cp * 4; p.y_c0 = o.c0; p.align = o.align; p.fmt = c.fmt;
+            if (desc) plain("resample_slice");
+            else rc = esa::launch_resample_slice(p, stream);
+            break;
+        }
+        case OP_GATHER: {
+            const Tensor& to = c.tensors[o.out];
+            esa::GatherParams p{};
+            const int zt[2] = {o.in, o.terms[0]};
+            for (int k = 0; k < 2; ++k) {
+                const Tensor& tz = c.tensors[zt[k]];
+                p.z[k] = T(zt[k]); p.h[k] = lh[tz.level]; p.w[k] = lw[tz.level]; p.zpix[k] = tz.Cp * 4;
+            }
+            p.y = T(o.out); p.N = n; p.H = lh[to.level]; p.W = lw[to.level]; p.C = to.C; p.Cp = to.Cp;
+            if (desc) {
+                plain("head_gather");
+                desc->bytes += tbytes(o.terms[0]);
+            } else rc = esa::launch_head_gather(p, stream, c.fmt);
+            break;
+        }
+        case OP_ZERO: {
+            const Tensor& to = c.tensors[o.out];
+            if (desc) plain("zero_slice");
+            else rc = esa::launch_zero_slice(T(o.out), (long long)n * lh[to.level] * lw[to.level], to.Cp * 4, o.c0, o.nchan, stream);
+            break;
+        }
+        case OP_TONCHW: {
+            if (desc) plain("sb_to_nchw");
+            else rc = esa::launch_fmt_to_nchw(c.fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
+                                              static_cast<float*>(b.heat), stream);
+            break;
+        }
+        case OP_STEMF: {
+            const DevConv& d = c.dconvs[o.dconv];
+            const Tensor& to = c.tensors[o.out];
+            esa::StemFusedParams p{};
+            p.x = static_cast<const float*>(b.x); p.y = T(o.out);
+            p.w1 = c.stem_w; p.bias1 = c.stem_b;
+            p.w2 = static_cast<const uint4*>(d.w); p.bias2 = d.bias;
+            p.N = n; p.H = height; p.W = width; p.OH = lh[to.level]; p.OW = lw[to.level];
+            p.cin = c.cfg.cin; p.Cmid = d.cinp; p.Coutp = d.coutp;
+            if (desc) {
+                const ConvSpec& s1 = c.specs[c.spec_stem];
+                const ConvSpec& s2 = c.specs[d.spec];
+                describe(desc, c.x6() ? "stem_x6_kernel" : "stem_fused", "conv1 + conv2");
+                desc->flops = 2.0 * n * height * width * s1.cout * s1.cin * 9 +
+                              2.0 * n * lh[to.level] * lw[to.level] * s2.cout * s2.cin * 9;
+                desc->bytes = (double)n * height * width * s1.cin * 4 + tbytes(o.out) +
+                              (double)c.wbytes(pad32(s2.cout), pad32(s2.cin), 3);
+            } else rc = c.x6() ? esa::launch_stem_fused_x6(p, stream) : esa::launch_stem_fused(p, stream);
+            break;
+        }
+        case OP_CONV: {
+            const DevConv& d = c.dconvs[o.dconv];
+            const ConvSpec& s = c.specs[d.spec];
+            const Tensor& ti = c.tensors[o.in];
+            const Tensor& to = c.tensors[o.out];
+            if (ti.Cp != d.cinp || to.Cp != d.coutp) return fail("plan bug: channel mismatch at %s", s.name.c_str());
+            if (o.multi >= 0 && sp.multi_on[o.multi]) {
+                if (o.mpos > 0) {                           // evaluated by the group's leader
+                    if (desc) describe(desc, "", "%s (in the multi-head launch above)", s.name.c_str());
+                    break;
+                }
+                const Multi& m = c.multis[o.multi];
+                const esa::ConvParams p = multi_params(c, m, sp, b.ws);
+                if (!desc) {
+                    rc = esa::launch_conv_s2c32_multi(p, stream);
+                    break;
+                }
+                std::string lab;
+                desc->bytes = tbytes(o.in);
+                for (int k = 0; k < m.n; ++k) {
+                    const Op& ok = c.ops[m.op[k]];
+                    const DevConv& dk = c.dconvs[ok.dconv];
+                    const ConvSpec& sk = c.specs[dk.spec];
+                    const Tensor& tk = c.tensors[ok.out];
+                    lab += (k ? " + " : "") + sk.name;
+                    desc->flops += 2.0 * n * lh[tk.level] * lw[tk.level] * sk.cout * sk.cin * 9.0;
+                    desc->bytes += tbytes(ok.out) + (double)esa::packed_weight_bytes(dk.coutp, dk.cinp, 3);
+                }
+                describe(desc, m.coutp % 64 == 0 ? "conv_s2c32_kernel<2, 4, 4, true>" : "conv_s2c32_kernel<2, 4, 2, true>",
+                         "%s", lab.c_str());
+                break;
+            }
+            if (o.job >= 0 && sp.job_on[o.job]) {
+                if (o.jpos > 0) {                           // evaluated by the group's leader
+                    if (desc) describe(desc, "", "%s (in the merged launch above)", s.name.c_str());
+                    break;
+                }
+                const JobGroup& g = c.jobs[o.job];
+                esa::ConvParams ps[6];
+                for (int k = 0; k < g.n; ++k) ps[k] = conv_params_of(c, c.ops[g.op[k]], sp, b.ws);
+                if (!desc) {
+                    rc = c.x6() ? esa::launch_conv_x6_jobs(ps, g.n, s.k, s.stride, stream)
+                       : s.k == 1 ? esa::launch_conv1x1_jobs(ps, g.n, stream) : esa::launch_conv_jobs(ps, g.n, s.stride, stream);
+                    break;
+                }
+                char kernel[sizeof desc->kernel];
+                if (c.x6() && s.k == 1 && esa::conv1x1_x6_jobs_supported(ps, g.n)) snprintf(kernel, sizeof kernel, "conv1x1_x6_jobs_kernel");
+                else if (c.x6()) snprintf(kernel, sizeof kernel, "conv_x6_jobs_kernel<%d, %d>", s.k, s.stride);
+                else if (s.k == 1) snprintf(kernel, sizeof kernel, "conv1x1_jobs_kernel");
+                else snprintf(kernel, sizeof kernel, "conv_s2c32_jobs_kernel<%d, %d, %s>", s.stride, s.stride == 1 ? 8 : 4, c.bf ? "true" : "false");
+                std::string lab;
+                for (int k = 0; k < g.n; ++k) {
+                    const Op& ok = c.ops[g.op[k]];
+                    const DevConv& dk = c.dconvs[ok.dconv];
+                    const ConvSpec& sk = c.specs[dk.spec];
+                    const Tensor& tk = c.tensors[ok.out];
+                    lab += (k ? " + " : "") + sk.name;
+                    desc->flops += 2.0 * n * lh[tk.level] * lw[tk.level] * sk.cout * sk.cin * (double)(sk.k * sk.k);
+                    desc->bytes += tbytes(ok.in) + tbytes(ok.out) + (ok.res >= 0 ? tbytes(ok.res) : 0.0) +
+                                   (double)c.wbytes(dk.coutp, dk.cinp, sk.k);
+                }
+                describe(desc, kernel, "%s", lab.c_str());
+                break;
+            }
+            const esa::ConvParams p = conv_params_of(c, o, sp, b.ws);
+            if (!desc) {
+                rc = esa::launch_conv(p, s.k, s.stride, stream);
+                break;
+            }
+            if (d.c0 != 0 || d.c1 != s.cin) describe(desc, esa::conv_kernel_name(p, s.k, s.stride), "%s[:, %d:%d]", s.name.c_str(), d.c0, d.c1);
+            else describe(desc, esa::conv_kernel_name(p, s.k, s.stride), "%s", s.name.c_str());
+            desc->flops = 2.0 * n * lh[to.level] * lw[to.level] * s.cout * (d.c1 - d.c0) * s.k * s.k;
+            desc->bytes = tbytes(o.in) + tbytes(o.out) + (o.res >= 0 ? tbytes(o.res) : 0.0) +
+                          (double)c.wbytes(d.coutp, d.cinp, s.k);
+            break;
+        }
+        case OP_BLOCK: {
+            const DevConv& d1 = c.dconvs[o.dconv];
+            const DevConv& d2 = c.dconvs[o.dconv2];
+            const Tensor& ti = c.tensors[o.in];
+            const Tensor& to = c.tensors[o.out];
+            if (ti.Cp != 32 || to.Cp != 32) return fail("plan bug: bblock32 on a non-32-channel tensor");
+            esa::BlockParams p{};
+            p.x = T(o.in); p.y = T(o.out);
+            p.w1 = static_cast<const uint4*>(d1.w); p.w2 = static_cast<const uint4*>(d2.w);
+            p.bias1 = d1.bias; p.bias2 = d2.bias;
+            p.N = n; p.H = lh[ti.level]; p.W = lw[ti.level];
+            if (desc) {
+                const ConvSpec& s1 = c.specs[d1.spec];
+                const ConvSpec& s2 = c.specs[d2.spec];
+                describe(desc, "bblock32", "%s + conv2", s1.name.c_str());
+                desc->flops = 2.0 * n * lh[to.level] * lw[to.level] * 9.0 * ((double)s1.cout * s1.cin + (double)s2.cout * s2.cin);
+                desc->bytes = tbytes(o.in) + tbytes(o.out) + 2.0 * (double)esa::packed_weight_bytes(32, 32, 3);
+            } else rc = esa::launch_bblock32(p, stream);
+            break;
+        }
+        case OP_HEAD: case OP_HEADBF: {
+            const Tensor& ti = c.tensors[o.in];
+            const Tensor& to = c.tensors[o.out];
+            esa::HeadParams p{};
+            p.x0 = T(o.in); p.y = T(o.out);
+            p.w0 = static_cast<const uint4*>(c.head_w0); p.w3 = static_cast<const uint4*>(c.head_w3);
+            p.bias0 = c.head_b0; p.bias3 = c.head_b3;
+            p.N = n; p.H = lh[ti.level]; p.W = lw[ti.level];
+            for (int i = 0; i < 3; ++i) {
+                const Tensor& tt = c.tensors[o.terms[i]];
+                p.t[i] = T(o.terms[i]); p.th[i] = lh[tt.level]; p.tw[i] = lw[tt.level];
+                p.Ctp = tt.Cp;
+            }
+            p.C0p = ti.Cp; p.C3p = to.Cp; p.K = c.cfg.num_keypoints;
+            if (desc) {
+                const ConvSpec& s0 = c.specs[c.spec_l0];
+                const ConvSpec& s3 = c.specs[c.spec_l3];
+                describe(desc, o.kind == OP_HEAD ? "head_fused" : c.x6() ? "head_x6" : "head_fused_bf",
+                         "last_layer.0[:, 0:%d] + up + last_layer.3", c.head_c0);
+                desc->flops = 2.0 * n * lh[to.level] * lw[to.level] * ((double)s0.cout * c.head_c0 + (double)s3.cout * s3.cin);
+                desc->bytes = tbytes(o.in) + tbytes(o.out);
+                for (int i = 0; i < 3; ++i) desc->bytes += tbytes(o.terms[i]);
+            } else if (o.kind == OP_HEADBF) {
+                rc = c.x6() ? esa::launch_head_x6(p, stream) : esa::launch_head_bf(p, stream);
+            } else {
+                if (!esa::head_fused_supported(p.H, p.W, p.th, p.tw, p.C0p, p.K))
+                    return fail("forward: fused head does not support this shape (%dx%d)", p.H, p.W);
+                rc = esa::launch_head(p, stream);
+            }
+            break;
+        }
+        case OP_HEADT: {
+            const Tensor& ti = c.tensors[o.in];
+            const Tensor& to = c.tensors[o.out];
+            const DevConv& d = c.dconvs[o.dconv];
+            esa::HeadTParams p{};
+            p.x = T(o.in); p.t = T(o.out); p.wt = static_cast<const uint4*>(d.w);
+            p.N = n; p.h = lh[ti.level]; p.w = lw[ti.level];
+            p.Cinp = ti.Cp; p.Ctp = to.Cp; p.XP = esa::head_t_xp(p.w);
+            if (desc) {
+                const ConvSpec& s = c.specs[d.spec];
+                describe(desc, "head_t", "%s[:, %d:%d] (T layout)", s.name.c_str(), d.c0, d.c1);
+                desc->flops = 2.0 * n * lh[ti.level] * lw[ti.level] * s.cout * (d.c1 - d.c0);
+                desc->bytes = tbytes(o.in) + tbytes(o.out) + (double)esa::packed_weight_bytes(d.coutp, d.cinp, 1);
+            } else rc = esa::launch_head_t(p, stream);
+            break;
+        }
+        case OP_HEAD2: {
+            const Tensor& ti = c.tensors[o.in];
+            const Tensor& to = c.tensors[o.out];
+            const DevConv& d1 = c.dconvs[o.dconv];
+            esa::Head2Params p{};
+            p.x0 = T(o.in); p.x1 = T(o.terms[0]); p.t2 = T(o.terms[1]); p.t3 = T(o.terms[2]); p.y = T(o.out);
+            p.w0 = static_cast<const uint4*>(c.head_w0); p.w3 = static_cast<const uint4*>(c.head_w3);
+            p.w1 = static_cast<const uint4*>(d1.w);
+            p.bias0 = c.head_b0; p.bias3 = c.head_b3;
+            p.N = n; p.H = lh[ti.level]; p.W = lw[ti.level];
+            for (int i = 0; i < 3; ++i) {
+                const Tensor& tt = c.tensors[o.terms[i]];
+                p.th[i] = lh[tt.level]; p.tw[i] = lw[tt.level];
+            }
+            p.xp2 = esa::head_t_xp(p.tw[1]); p.xp3 = esa::head_t_xp(p.tw[2]);
+            p.C0p = ti.Cp; p.C1p = c.tensors[o.terms[0]].Cp; p.Ctp = c.tensors[o.terms[1]].Cp;
+            p.C3p = to.Cp; p.K = c.cfg.num_keypoints;
+            if (desc) {
+                const ConvSpec& s0 = c.specs[c.spec_l0];
+                const ConvSpec& s3 = c.specs[c.spec_l3];
+                const Tensor& t1 = c.tensors[o.terms[0]];
+                describe(desc, "head_fused2", "last_layer.0[:, 0:%d] + up (MFMA) + last_layer.3", d1.c1);
+                desc->flops = 2.0 * n * lh[to.level] * lw[to.level] * ((double)s0.cout * c.head_c0 + (double)s3.cout * s3.cin) +
+                              2.0 * n * lh[t1.level] * lw[t1.level] * (double)s0.cout * (d1.c1 - d1.c0);
+                desc->bytes = tbytes(o.in) + tbytes(o.out);
+                for (int i = 0; i < 3; ++i) desc->bytes += tbytes(o.terms[i]);
+            } else rc = esa::launch_head2(p, sp.head2_ulo, stream);
+            break;
+        }
+        case OP_FUSE: {
+            const Tensor& to = c.tensors[o.out];
+            esa::FuseParams p{};
+            p.nterms = o.nterms;
+            for (int i = 0; i < o.nterms; ++i) {
+                const Tensor& ti = c.tensors[o.terms[i]];
+                if (ti.Cp != to.Cp) return fail("plan bug: fuse channel mismatch");
+                p.x[i] = T(o.terms[i]); p.h[i] = lh[ti.level]; p.w[i] = lw[ti.level];
+            }
+            p.y = T(o.out); p.N = n; p.H = lh[to.level]; p.W = lw[to.level]; p.Cp = to.Cp;
+            p.relu = o.relu; p.fmt = c.fmt;
+            if (desc) {
+                describe(desc, "fuse_kernel", "fuse -> %s", to.tap.c_str());
+                desc->bytes = tbytes(o.out);
+                for (int i = 0; i < o.nterms; ++i) desc->bytes += tbytes(o.terms[i]);
+            } else rc = esa::launch_fuse(p, stream);
+            break;
+        }
+        case OP_FINAL: {
+            const Tensor& ti = c.tensors[o.in];
+            esa::FinalParams p{};
+            p.h3 = T(o.in); p.x0 = static_cast<const float*>(b.x); p.out = static_cast<float*>(b.heat);
+            p.w = c.final_w; p.bias = c.final_b; p.wpk = static_cast<const uint4*>(c.final_wpk);
+            p.N = n; p.H = height; p.W = width; p.h = lh[ti.level]; p.wd = lw[ti.level];
+            p.K = c.cfg.num_keypoints; p.cin = c.cfg.cin; p.Cp = ti.Cp; p.fmt = c.fmt;
+            p.part = static_cast<float2*>(b.part);
+            if (desc) {
+                const ConvSpec& s = c.specs[c.spec_final];
+                describe(desc, "final_kernel", "%s", s.name.c_str());
+                desc->flops = 2.0 * n * height * width * s.cout * s.cin * 9;
+                desc->bytes = tbytes(o.in) + (double)n * height * width * (c.cfg.cin + s.cout) * 4;
+            } else rc = esa::launch_final(p, stream);
+            break;
+        }
+    }
+    if (rc) return fail("forward: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
 static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, int width,
                        void* heat_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream_,
                        hipEvent_t* events, void* part_dev = nullptr) {
@@ -1485,9 +1903,7 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
     if (ws_bytes < h->sp.bytes) return fail("forward: workspace too small (%zu < %zu)", ws_bytes, h->sp.bytes);
     if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("forward: workspace must be 256-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    char* ws = static_cast<char*>(ws_dev);
-    const ShapePlan& sp = h->sp;
-    auto T = [&](int t) { return ws + h->tensors[t].off; };
+    const Buffers bufs{x_dev, heat_dev, static_cast<char*>(ws_dev), part_dev};
     int op_index = 0;
     if (events && hipEventRecord(events[0], stream) != hipSuccess) return fail("forward: hipEventRecord failed");
     // wave executor: lane 0 is the caller's stream; the other lanes of a wave are side streams that fork from and join
@@ -1506,39 +1922,7 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
             }
         return 0;
     };
-    const int active_alt = sp.head2 ? 2 : 1;
-    // one CBAM launch as a job description (cbam.hip); kind < 0: nothing to launch (maps formed inside cbam_spatial)
-    auto cbam_job = [&](const Op& o) {
-        esa::CbamJob q{};
-        q.kind = -1;
-        const Tensor& tx = h->tensors[o.kind == OP_MLP ? o.terms[0] : o.in];
-        const int hh = sp.lh[tx.level], ww = sp.lw[tx.level];
-        q.ap.N = n; q.ap.H = hh; q.ap.W = ww; q.ap.Cp = tx.Cp; q.ap.C = o.nchan; q.ap.fmt = h->fmt;
-        q.HW = hh * ww; q.P = std::min(Builder::POOL_SLABS, q.HW); q.Cr = o.nchan / 16;
-        switch (o.kind) {
-            case OP_POOL: q.kind = esa::CBAM_POOL; q.ap.x = T(o.in); q.partial = reinterpret_cast<float*>(T(o.out)); q.ap.C = tx.C; break;
-            case OP_MLP:
-                q.kind = esa::CBAM_MLP; q.partial = reinterpret_cast<float*>(T(o.in)); q.ca = reinterpret_cast<float*>(T(o.out));
-                q.w0 = h->aux[o.aux[0]].dev; q.w2 = h->aux[o.aux[1]].dev;
-                break;
-            case OP_MAPS:
-                if (cbam_fused(*h, tx.Cp, hh, ww)) break;
-                q.kind = esa::CBAM_MAPS; q.ap.x = T(o.in); q.ap.ca = reinterpret_cast<const float*>(T(o.terms[1]));
-                q.maps = reinterpret_cast<float*>(T(o.out));
-                break;
-            default: {
-                const Tensor& to = h->tensors[o.out];
-                q.kind = cbam_fused(*h, tx.Cp, hh, ww) ? esa::CBAM_SPATIAL : esa::CBAM_APPLY;
-                q.ap.x = T(o.in); q.ap.res = o.res >= 0 ? T(o.res) : nullptr;
-                q.ap.ca = reinterpret_cast<const float*>(T(o.terms[1])); q.ap.maps = reinterpret_cast<const float*>(T(o.terms[2]));
-                q.ap.w_sa = h->aux[o.aux[2]].dev; q.ap.y = T(o.out);
-                q.ap.y_pix_bytes = to.Cp * 4; q.ap.y_c0 = o.c0; q.ap.relu = o.relu;
-            }
-        }
-        return q;
-    };
     for (const Op& o : h->ops) {
-        int rc = 0;
         if (multi) {
             if (o.join && join((size_t)op_index, o.join)) return fail("forward: joining side lanes failed");
             if (o.wave != cur_wave) {
@@ -1550,271 +1934,7 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
             if (o.wait_entry) HIP_OK(hipStreamWaitEvent(stream, h->wave_entry[cur_wave], 0));
             if (o.wait0 >= 0) HIP_OK(hipStreamWaitEvent(stream, h->op_event[o.wait0], 0));
         }
-        if (o.alt != 0 && o.alt != active_alt) {         // the head alternative not used at this shape
-            if (multi && o.record) HIP_OK(hipEventRecord(h->op_event[op_index], caller));
-            ++op_index;
-            if (events && hipEventRecord(events[op_index], stream) != hipSuccess) return fail("forward: hipEventRecord failed");
-            continue;
-        }
-        switch (o.kind) {
-            case OP_STEM: {
-                const Tensor& t = h->tensors[o.out];
-                esa::StemParams p{static_cast<const float*>(x_dev), T(o.out), h->stem_w, h->stem_b,
-                                  n, height, width, h->cfg.cin, t.Cp, 1, h->fmt};
-                rc = esa::launch_stem(p, stream);
-                break;
-            }
-            case OP_STEMRAW: {
-                const Tensor& t = h->tensors[o.out];
-                esa::StemParams p{static_cast<const float*>(x_dev), T(o.out), h->stemraw_w, h->stemraw_b,
-                                  n, height, width, h->cfg.cin, t.Cp, 0, h->fmt};
-                rc = stem_pools(*h, height, width) ? esa::launch_stem_pool(p, reinterpret_cast<float*>(T(o.out2)), stream)
-                                                   : esa::launch_stem(p, stream);
-                break;
-            }
-            case OP_POOL: case OP_MLP: case OP_MAPS: case OP_APPLY:
-                if (o.job >= 0 && sp.job_on[o.job]) {           // the same step of every branch of the module in one launch
-                    if (o.jpos > 0) break;
-                    const JobGroup& g = h->jobs[o.job];
-                    esa::CbamJob js[esa::CBAM_MAXJOBS];
-                    int nj = 0;
-                    for (int k = 0; k < g.n; ++k) {
-                        const esa::CbamJob q = cbam_job(h->ops[g.op[k]]);
-                        if (q.kind >= 0) js[nj++] = q;
-                    }
-                    if (nj) rc = esa::launch_cbam_jobs(js, nj, stream);
-                    break;
-                }
-                switch (o.kind) {
-            case OP_POOL: {
-                const Tensor& ti = h->tensors[o.in];
-                if (o.out == h->stemraw_partial && stem_pools(*h, height, width)) break;       // made by the stem kernel
-                const int HW = sp.lh[ti.level] * sp.lw[ti.level];
-                rc = esa::launch_pool_partial(T(o.in), reinterpret_cast<float*>(T(o.out)), n, HW, ti.Cp,
-                                              std::min(Builder::POOL_SLABS, HW), stream, h->fmt);
-                break;
-            }
-            case OP_MLP: {
-                const Tensor& tx = h->tensors[o.terms[0]];
-                const int HW = sp.lh[tx.level] * sp.lw[tx.level];
-                const int slabs = o.in == h->stemraw_partial ? stem_pools(*h, height, width) : 0;
-                rc = esa::launch_ca_mlp(reinterpret_cast<const float*>(T(o.in)), h->aux[o.aux[0]].dev, h->aux[o.aux[1]].dev,
-                                        reinterpret_cast<float*>(T(o.out)), n, HW, o.nchan, tx.Cp, o.nchan / 16,
-                                        slabs ? slabs : std::min(Builder::POOL_SLABS, HW), stream);
-                break;
-            }
-            case OP_MAPS: {
-                const Tensor& ti = h->tensors[o.in];
-                if (cbam_fused(*h, ti.Cp, sp.lh[ti.level], sp.lw[ti.level])) break;      // formed inside cbam_spatial (the OP_APPLY that follows)
-                rc = esa::launch_cbam_maps(T(o.in), reinterpret_cast<const float*>(T(o.terms[1])),
-                                           reinterpret_cast<float*>(T(o.out)), n, sp.lh[ti.level] * sp.lw[ti.level],
-                                           o.nchan, ti.Cp, stream, h->fmt);
-                break;
-            }
-            case OP_APPLY: {
-                const Tensor& ti = h->tensors[o.in];
-                const Tensor& to = h->tensors[o.out];
-                esa::CbamApplyParams p{};
-                p.x = T(o.in); p.res = o.res >= 0 ? T(o.res) : nullptr;
-                p.ca = reinterpret_cast<const float*>(T(o.terms[1])); p.maps = reinterpret_cast<const float*>(T(o.terms[2]));
-                p.w_sa = h->aux[o.aux[2]].dev; p.y = T(o.out);
-                p.N = n; p.H = sp.lh[ti.level]; p.W = sp.lw[ti.level]; p.Cp = ti.Cp;
-                p.y_pix_bytes = to.Cp * 4; p.y_c0 = o.c0; p.relu = o.relu; p.C = o.nchan; p.fmt = h->fmt;
-                rc = cbam_fused(*h, ti.Cp, p.H, p.W) ? esa::launch_cbam_spatial(p, stream) : esa::launch_cbam_apply(p, stream);
-                break;
-            }
-            default: break;
-                }                   // (inner switch: the single-tensor launches)
-                break;
-            case OP_RESAMPLE: {
-                const Tensor& ti = h->tensors[o.in];
-                const Tensor& to = h->tensors[o.out];
-                esa::ResampleParams p{};
-                p.x = T(o.in); p.y = T(o.out); p.N = n;
-                p.h = sp.lh[ti.level]; p.w = sp.lw[ti.level]; p.H = sp.lh[to.level]; p.W = sp.lw[to.level];
-                p.C = o.nchan; p.Cp_src = ti.Cp; p.y_pix_bytes = to.Cp * 4; p.y_c0 = o.c0; p.align = o.align; p.fmt = h->fmt;
-                rc = esa::launch_resample_slice(p, stream);
-                break;
-            }
-            case OP_GATHER: {
-                const Tensor& to = h->tensors[o.out];
-                esa::GatherParams p{};
-                const int zt[2] = {o.in, o.terms[0]};
-                for (int b = 0; b < 2; ++b) {
-                    const Tensor& tz = h->tensors[zt[b]];
-                    p.z[b] = T(zt[b]); p.h[b] = sp.lh[tz.level]; p.w[b] = sp.lw[tz.level]; p.zpix[b] = tz.Cp * 4;
-                }
-                p.y = T(o.out); p.N = n; p.H = sp.lh[to.level]; p.W = sp.lw[to.level]; p.C = to.C; p.Cp = to.Cp;
-                rc = esa::launch_head_gather(p, stream, h->fmt);
-                break;
-            }
-            case OP_ZERO: {
-                const Tensor& to = h->tensors[o.out];
-                rc = esa::launch_zero_slice(T(o.out), (long long)n * sp.lh[to.level] * sp.lw[to.level], to.Cp * 4,
-                                            o.c0, o.nchan, stream);
-                break;
-            }
-            case OP_TONCHW: {
-                const Tensor& ti = h->tensors[o.in];
-                rc = esa::launch_fmt_to_nchw(h->fmt, T(o.in), n, h->cfg.num_keypoints, height, width, ti.Cp,
-                                             static_cast<float*>(heat_dev), stream);
-                break;
-            }
-            case OP_STEMF: {
-                const DevConv& d = h->dconvs[o.dconv];
-                const Tensor& to = h->tensors[o.out];
-                esa::StemFusedParams p{};
-                p.x = static_cast<const float*>(x_dev); p.y = T(o.out);
-                p.w1 = h->stem_w; p.bias1 = h->stem_b;
-                p.w2 = static_cast<const uint4*>(d.w); p.bias2 = d.bias;
-                p.N = n; p.H = height; p.W = width; p.OH = sp.lh[to.level]; p.OW = sp.lw[to.level];
-                p.cin = h->cfg.cin; p.Cmid = d.cinp; p.Coutp = d.coutp;
-                rc = h->x6() ? esa::launch_stem_fused_x6(p, stream) : esa::launch_stem_fused(p, stream);
-                break;
-            }
-            case OP_CONV: {
-                const DevConv& d = h->dconvs[o.dconv];
-                const ConvSpec& s = h->specs[d.spec];
-                const Tensor& ti = h->tensors[o.in];
-                const Tensor& to = h->tensors[o.out];
-                if (ti.Cp != d.cinp || to.Cp != d.coutp) return fail("plan bug: channel mismatch at %s", s.name.c_str());
-                if (o.multi >= 0 && sp.multi_on[o.multi]) {
-                    if (o.mpos > 0) break;                      // evaluated by the group's leader
-                    const Multi& m = h->multis[o.multi];
-                    esa::ConvParams p{};
-                    p.x = T(o.in);
-                    p.w = static_cast<const uint4*>(m.w); p.bias = m.bias;
-                    p.N = n; p.H = sp.lh[ti.level]; p.W = sp.lw[ti.level];
-                    p.OH = sp.lh[to.level]; p.OW = sp.lw[to.level];
-                    p.Cinp = d.cinp; p.Coutp = m.coutp; p.nheads = m.n;
-                    for (int k = 0; k < m.n; ++k) {
-                        const Op& ok = h->ops[m.op[k]];
-                        p.yh[k] = T(ok.out);
-                        p.hb[k + 1] = p.hb[k] + h->dconvs[ok.dconv].coutp;
-                        p.hrelu[k] = ok.relu;
-                    }
-                    rc = esa::launch_conv_s2c32_multi(p, stream);
-                    break;
-                }
-                if (o.job >= 0 && sp.job_on[o.job]) {
-                    if (o.jpos > 0) break;                      // evaluated by the group's leader
-                    const JobGroup& g = h->jobs[o.job];
-                    esa::ConvParams ps[6];
-                    for (int k = 0; k < g.n; ++k) ps[k] = conv_params_of(*h, h->ops[g.op[k]], n, sp.lh, sp.lw, ws);
-                    rc = h->x6() ? esa::launch_conv_x6_jobs(ps, g.n, s.k, s.stride, stream)
-                       : s.k == 1 ? esa::launch_conv1x1_jobs(ps, g.n, stream) : esa::launch_conv_jobs(ps, g.n, s.stride, stream);
-                    break;
-                }
-                const esa::ConvParams p = conv_params_of(*h, o, n, sp.lh, sp.lw, ws);
-                rc = esa::launch_conv(p, s.k, s.stride, stream);
-                break;
-            }
-            case OP_BLOCK: {
-                const DevConv& d1 = h->dconvs[o.dconv];
-                const DevConv& d2 = h->dconvs[o.dconv2];
-                const Tensor& ti = h->tensors[o.in];
-                if (ti.Cp != 32 || h->tensors[o.out].Cp != 32) return fail("plan bug: bblock32 on a non-32-channel tensor");
-                esa::BlockParams p{};
-                p.x = T(o.in); p.y = T(o.out);
-                p.w1 = static_cast<const uint4*>(d1.w); p.w2 = static_cast<const uint4*>(d2.w);
-                p.bias1 = d1.bias; p.bias2 = d2.bias;
-                p.N = n; p.H = sp.lh[ti.level]; p.W = sp.lw[ti.level];
-                rc = esa::launch_bblock32(p, stream);
-                break;
-            }
-            case OP_HEAD: {
-                const Tensor& ti = h->tensors[o.in];
-                const Tensor& to = h->tensors[o.out];
-                esa::HeadParams p{};
-                p.x0 = T(o.in); p.y = T(o.out);
-                p.w0 = static_cast<const uint4*>(h->head_w0); p.w3 = static_cast<const uint4*>(h->head_w3);
-                p.bias0 = h->head_b0; p.bias3 = h->head_b3;
-                p.N = n; p.H = sp.lh[ti.level]; p.W = sp.lw[ti.level];
-                for (int i = 0; i < 3; ++i) {
-                    const Tensor& tt = h->tensors[o.terms[i]];
-                    p.t[i] = T(o.terms[i]); p.th[i] = sp.lh[tt.level]; p.tw[i] = sp.lw[tt.level];
-                    p.Ctp = tt.Cp;
-                }
-                p.C0p = ti.Cp; p.C3p = to.Cp; p.K = h->cfg.num_keypoints;
-                if (!esa::head_fused_supported(p.H, p.W, p.th, p.tw, p.C0p, p.K))
-                    return fail("forward: fused head does not support this shape (%dx%d)", p.H, p.W);
-                rc = esa::launch_head(p, stream);
-                break;
-            }
-            case OP_HEADBF: {
-                const Tensor& ti = h->tensors[o.in];
-                const Tensor& to = h->tensors[o.out];
-                esa::HeadParams p{};
-                p.x0 = T(o.in); p.y = T(o.out);
-                p.w0 = static_cast<const uint4*>(h->head_w0); p.w3 = static_cast<const uint4*>(h->head_w3);
-                p.bias0 = h->head_b0; p.bias3 = h->head_b3;
-                p.N = n; p.H = sp.lh[ti.level]; p.W = sp.lw[ti.level];
-                for (int i = 0; i < 3; ++i) {
-                    const Tensor& tt = h->tensors[o.terms[i]];
-                    p.t[i] = T(o.terms[i]); p.th[i] = sp.lh[tt.level]; p.tw[i] = sp.lw[tt.level];
-                    p.Ctp = tt.Cp;
-                }
-                p.C0p = ti.Cp; p.C3p = to.Cp; p.K = h->cfg.num_keypoints;
-                rc = h->x6() ? esa::launch_head_x6(p, stream) : esa::launch_head_bf(p, stream);
-                break;
-            }
-            case OP_HEADT: {
-                const Tensor& ti = h->tensors[o.in];
-                const Tensor& to = h->tensors[o.out];
-                const DevConv& d = h->dconvs[o.dconv];
-                esa::HeadTParams p{};
-                p.x = T(o.in); p.t = T(o.out); p.wt = static_cast<const uint4*>(d.w);
-                p.N = n; p.h = sp.lh[ti.level]; p.w = sp.lw[ti.level];
-                p.Cinp = ti.Cp; p.Ctp = to.Cp; p.XP = esa::head_t_xp(p.w);
-                rc = esa::launch_head_t(p, stream);
-                break;
-            }
-            case OP_HEAD2: {
-                const Tensor& ti = h->tensors[o.in];
-                const Tensor& to = h->tensors[o.out];
-                esa::Head2Params p{};
-                p.x0 = T(o.in); p.x1 = T(o.terms[0]); p.t2 = T(o.terms[1]); p.t3 = T(o.terms[2]); p.y = T(o.out);
-                p.w0 = static_cast<const uint4*>(h->head_w0); p.w3 = static_cast<const uint4*>(h->head_w3);
-                p.w1 = static_cast<const uint4*>(h->dconvs[o.dconv].w);
-                p.bias0 = h->head_b0; p.bias3 = h->head_b3;
-                p.N = n; p.H = sp.lh[ti.level]; p.W = sp.lw[ti.level];
-                for (int i = 0; i < 3; ++i) {
-                    const Tensor& tt = h->tensors[o.terms[i]];
-                    p.th[i] = sp.lh[tt.level]; p.tw[i] = sp.lw[tt.level];
-                }
-                p.xp2 = esa::head_t_xp(p.tw[1]); p.xp3 = esa::head_t_xp(p.tw[2]);
-                p.C0p = ti.Cp; p.C1p = h->tensors[o.terms[0]].Cp; p.Ctp = h->tensors[o.terms[1]].Cp;
-                p.C3p = to.Cp; p.K = h->cfg.num_keypoints;
-                rc = esa::launch_head2(p, sp.head2_ulo, stream);
-                break;
-            }
-            case OP_FUSE: {
-                const Tensor& to = h->tensors[o.out];
-                esa::FuseParams p{};
-                p.nterms = o.nterms;
-                for (int i = 0; i < o.nterms; ++i) {
-                    const Tensor& ti = h->tensors[o.terms[i]];
-                    if (ti.Cp != to.Cp) return fail("plan bug: fuse channel mismatch");
-                    p.x[i] = T(o.terms[i]); p.h[i] = sp.lh[ti.level]; p.w[i] = sp.lw[ti.level];
-                }
-                p.y = T(o.out); p.N = n; p.H = sp.lh[to.level]; p.W = sp.lw[to.level]; p.Cp = to.Cp;
-                p.relu = o.relu; p.fmt = h->fmt;
-                rc = esa::launch_fuse(p, stream);
-                break;
-            }
-            case OP_FINAL: {
-                const Tensor& ti = h->tensors[o.in];
-                esa::FinalParams p{};
-                p.h3 = T(o.in); p.x0 = static_cast<const float*>(x_dev); p.out = static_cast<float*>(heat_dev);
-                p.w = h->final_w; p.bias = h->final_b; p.wpk = static_cast<const uint4*>(h->final_wpk);
-                p.N = n; p.H = height; p.W = width; p.h = sp.lh[ti.level]; p.wd = sp.lw[ti.level];
-                p.K = h->cfg.num_keypoints; p.cin = h->cfg.cin; p.Cp = ti.Cp; p.fmt = h->fmt;
-                p.part = static_cast<float2*>(part_dev);
-                rc = esa::launch_final(p, stream);
-                break;
-            }
-        }
-        if (rc) return fail("forward: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (run_op(*h, o, h->sp, bufs, stream, nullptr)) return 1;
         if (multi && o.record) HIP_OK(hipEventRecord(h->op_event[op_index], caller));
         ++op_index;
         if (events && hipEventRecord(events[op_index], stream) != hipSuccess) return fail("forward: hipEventRecord failed");
@@ -1860,227 +1980,9 @@ int esahrnet_forward_timed(esahrnet_handle h, const void* x_dev, int n, int heig
 
 int esahrnet_op_desc_get(esahrnet_handle h, int index, int n, int height, int width, esahrnet_op_desc* out) {
     if (!h || !out || index < 0 || index >= (int)h->ops.size()) return fail("op_desc_get: bad argument");
-    if (check_shape(*h, n, height, width)) return 1;
-    std::vector<int> lh, lw;
-    level_dims(*h, height, width, lh, lw);
+    if (check_shape(n, height, width)) return 1;
     memset(out, 0, sizeof *out);
-    const Op& o = h->ops[index];
-    if (o.alt != 0) {        // a head alternative: described only for the shapes that run it (else kernel = "")
-        bool ulo = false;
-        if (o.alt != (head2_for_shape(*h, lh, lw, &ulo) ? 2 : 1)) {
-            snprintf(out->label, sizeof out->label, "(not used at this shape)");
-            return 0;
-        }
-    }
-    auto tbytes = [&](int t) {
-        const Tensor& x = h->tensors[t];
-        const double wpix = x.tlayout ? (double)esa::head_t_xp(lw[x.level]) : (double)lw[x.level];
-        return x.flat ? (double)n * x.flat * 4.0 : (double)n * lh[x.level] * wpix * x.Cp * (double)h->eb();
-    };
-    switch (o.kind) {
-        case OP_STEM: {
-            const ConvSpec& s = h->specs[h->spec_stem];
-            snprintf(out->kernel, sizeof out->kernel, "stem_kernel");
-            snprintf(out->label, sizeof out->label, "%s", s.name.c_str());
-            out->flops = 2.0 * n * height * width * s.cout * s.cin * 9;
-            out->bytes = (double)n * height * width * s.cin * 4 + tbytes(o.out);
-            break;
-        }
-        case OP_STEMF: {
-            const ConvSpec& s1 = h->specs[h->spec_stem];
-            const ConvSpec& s2 = h->specs[h->dconvs[o.dconv].spec];
-            const Tensor& to = h->tensors[o.out];
-            snprintf(out->kernel, sizeof out->kernel, h->x6() ? "stem_x6_kernel" : "stem_fused");
-            snprintf(out->label, sizeof out->label, "conv1 + conv2");
-            out->flops = 2.0 * n * height * width * s1.cout * s1.cin * 9 +
-                         2.0 * n * lh[to.level] * lw[to.level] * s2.cout * s2.cin * 9;
-            out->bytes = (double)n * height * width * s1.cin * 4 + tbytes(o.out) +
-                         (double)h->wbytes(pad32(s2.cout), pad32(s2.cin), 3);
-            break;
-        }
-        case OP_CONV: {
-            const DevConv& d = h->dconvs[o.dconv];
-            const ConvSpec& s = h->specs[d.spec];
-            const Tensor& to = h->tensors[o.out];
-            if (o.multi >= 0 && multi_on_for(*h, h->multis[o.multi], n, lh, lw)) {
-                const Multi& m = h->multis[o.multi];
-                if (o.mpos > 0) {        // no launch of its own
-                    snprintf(out->label, sizeof out->label, "%s (in the multi-head launch above)", s.name.c_str());
-                    break;
-                }
-                snprintf(out->kernel, sizeof out->kernel, m.coutp % 64 == 0 ? "conv_s2c32_kernel<2, 4, 4, true>" : "conv_s2c32_kernel<2, 4, 2, true>");
-                std::string lab;
-                out->bytes = tbytes(o.in);
-                for (int k = 0; k < m.n; ++k) {
-                    const Op& ok = h->ops[m.op[k]];
-                    const DevConv& dk = h->dconvs[ok.dconv];
-                    const ConvSpec& sk = h->specs[dk.spec];
-                    const Tensor& tk = h->tensors[ok.out];
-                    lab += (k ? " + " : "") + sk.name;
-                    out->flops += 2.0 * n * lh[tk.level] * lw[tk.level] * sk.cout * sk.cin * 9.0;
-                    out->bytes += tbytes(ok.out) + (double)esa::packed_weight_bytes(dk.coutp, dk.cinp, 3);
-                }
-                snprintf(out->label, sizeof out->label, "%s", lab.c_str());
-                break;
-            }
-            if (o.job >= 0 && job_on_for(*h, h->jobs[o.job], n, lh, lw)) {
-                const JobGroup& g = h->jobs[o.job];
-                if (o.jpos > 0) {        // no launch of its own
-                    snprintf(out->label, sizeof out->label, "%s (in the merged launch above)", s.name.c_str());
-                    break;
-                }
-                if (h->x6()) {
-                    esa::ConvParams qs[6];
-                    for (int k = 0; k < g.n; ++k) qs[k] = conv_params_of(*h, h->ops[g.op[k]], n, lh, lw, nullptr);
-                    if (s.k == 1 && esa::conv1x1_x6_jobs_supported(qs, g.n)) snprintf(out->kernel, sizeof out->kernel, "conv1x1_x6_jobs_kernel");
-                    else snprintf(out->kernel, sizeof out->kernel, "conv_x6_jobs_kernel<%d, %d>", s.k, s.stride);
-                }
-                else if (s.k == 1) snprintf(out->kernel, sizeof out->kernel, "conv1x1_jobs_kernel");
-                else snprintf(out->kernel, sizeof out->kernel, "conv_s2c32_jobs_kernel<%d, %d, %s>", s.stride, s.stride == 1 ? 8 : 4, h->bf ? "true" : "false");
-                std::string lab;
-                for (int k = 0; k < g.n; ++k) {
-                    const Op& ok = h->ops[g.op[k]];
-                    const DevConv& dk = h->dconvs[ok.dconv];
-                    const ConvSpec& sk = h->specs[dk.spec];
-                    const Tensor& tk = h->tensors[ok.out];
-                    lab += (k ? " + " : "") + sk.name;
-                    out->flops += 2.0 * n * lh[tk.level] * lw[tk.level] * sk.cout * sk.cin * (double)(sk.k * sk.k);
-                    out->bytes += tbytes(ok.in) + tbytes(ok.out) + (ok.res >= 0 ? tbytes(ok.res) : 0.0) +
-                                  (double)h->wbytes(dk.coutp, dk.cinp, sk.k);
-                }
-                snprintf(out->label, sizeof out->label, "%s", lab.c_str());
-                break;
-            }
-            {
-                const Tensor& ti = h->tensors[o.in];
-                esa::ConvParams q{};
-                q.N = n; q.H = lh[ti.level]; q.W = lw[ti.level]; q.OH = lh[to.level]; q.OW = lw[to.level];
-                q.Cinp = d.cinp; q.Coutp = d.coutp; q.out_f32 = d.out_f32 && !h->x6(); q.fmt = h->fmt;
-                q.res = o.res >= 0 ? reinterpret_cast<const char*>(h) : nullptr;     // only tested against nullptr
-                snprintf(out->kernel, sizeof out->kernel, "%s", esa::conv_kernel_name(q, s.k, s.stride));
-            }
-            if (d.c0 != 0 || d.c1 != s.cin) snprintf(out->label, sizeof out->label, "%s[:, %d:%d]", s.name.c_str(), d.c0, d.c1);
-            else snprintf(out->label, sizeof out->label, "%s", s.name.c_str());
-            out->flops = 2.0 * n * lh[to.level] * lw[to.level] * s.cout * (d.c1 - d.c0) * s.k * s.k;
-            out->bytes = tbytes(o.in) + tbytes(o.out) + (o.res >= 0 ? tbytes(o.res) : 0.0) +
-                         (double)h->wbytes(d.coutp, d.cinp, s.k);
-            break;
-        }
-        case OP_BLOCK: {
-            const ConvSpec& s1 = h->specs[h->dconvs[o.dconv].spec];
-            const ConvSpec& s2 = h->specs[h->dconvs[o.dconv2].spec];
-            const Tensor& to = h->tensors[o.out];
-            snprintf(out->kernel, sizeof out->kernel, "bblock32");
-            snprintf(out->label, sizeof out->label, "%s + conv2", s1.name.c_str());
-            out->flops = 2.0 * n * lh[to.level] * lw[to.level] * 9.0 * ((double)s1.cout * s1.cin + (double)s2.cout * s2.cin);
-            out->bytes = tbytes(o.in) + tbytes(o.out) + 2.0 * (double)esa::packed_weight_bytes(32, 32, 3);
-            break;
-        }
-        case OP_HEAD: {
-            const ConvSpec& s0 = h->specs[h->spec_l0];
-            const ConvSpec& s3 = h->specs[h->spec_l3];
-            const Tensor& to = h->tensors[o.out];
-            snprintf(out->kernel, sizeof out->kernel, "head_fused");
-            snprintf(out->label, sizeof out->label, "last_layer.0[:, 0:%d] + up + last_layer.3", h->head_c0);
-            out->flops = 2.0 * n * lh[to.level] * lw[to.level] * ((double)s0.cout * h->head_c0 + (double)s3.cout * s3.cin);
-            out->bytes = tbytes(o.in) + tbytes(o.out);
-            for (int i = 0; i < 3; ++i) out->bytes += tbytes(o.terms[i]);
-            break;
-        }
-        case OP_HEADBF: {
-            const ConvSpec& s0 = h->specs[h->spec_l0];
-            const ConvSpec& s3 = h->specs[h->spec_l3];
-            const Tensor& to = h->tensors[o.out];
-            snprintf(out->kernel, sizeof out->kernel, h->x6() ? "head_x6" : "head_fused_bf");
-            snprintf(out->label, sizeof out->label, "last_layer.0[:, 0:%d] + up + last_layer.3", h->head_c0);
-            out->flops = 2.0 * n * lh[to.level] * lw[to.level] * ((double)s0.cout * h->head_c0 + (double)s3.cout * s3.cin);
-            out->bytes = tbytes(o.in) + tbytes(o.out);
-            for (int i = 0; i < 3; ++i) out->bytes += tbytes(o.terms[i]);
-            break;
-        }
-        case OP_HEADT: {
-            const DevConv& d = h->dconvs[o.dconv];
-            const ConvSpec& s = h->specs[d.spec];
-            const Tensor& ti = h->tensors[o.in];
-            snprintf(out->kernel, sizeof out->kernel, "head_t");
-            snprintf(out->label, sizeof out->label, "%s[:, %d:%d] (T layout)", s.name.c_str(), d.c0, d.c1);
-            out->flops = 2.0 * n * lh[ti.level] * lw[ti.level] * s.cout * (d.c1 - d.c0);
-            out->bytes = tbytes(o.in) + tbytes(o.out) + (double)esa::packed_weight_bytes(d.coutp, d.cinp, 1);
-            break;
-        }
-        case OP_HEAD2: {
-            const ConvSpec& s0 = h->specs[h->spec_l0];
-            const ConvSpec& s3 = h->specs[h->spec_l3];
-            const DevConv& d1 = h->dconvs[o.dconv];
-            const Tensor& to = h->tensors[o.out];
-            const Tensor& t1 = h->tensors[o.terms[0]];
-            snprintf(out->kernel, sizeof out->kernel, "head_fused2");
-            snprintf(out->label, sizeof out->label, "last_layer.0[:, 0:%d] + up (MFMA) + last_layer.3", d1.c1);
-            out->flops = 2.0 * n * lh[to.level] * lw[to.level] * ((double)s0.cout * h->head_c0 + (double)s3.cout * s3.cin) +
-                         2.0 * n * lh[t1.level] * lw[t1.level] * (double)s0.cout * (d1.c1 - d1.c0);
-            out->bytes = tbytes(o.in) + tbytes(o.out);
-            for (int i = 0; i < 3; ++i) out->bytes += tbytes(o.terms[i]);
-            break;
-        }
-        case OP_FUSE: {
-            snprintf(out->kernel, sizeof out->kernel, "fuse_kernel");
-            snprintf(out->label, sizeof out->label, "fuse -> %s", h->tensors[o.out].tap.c_str());
-            out->bytes = tbytes(o.out);
-            for (int i = 0; i < o.nterms; ++i) out->bytes += tbytes(o.terms[i]);
-            break;
-        }
-        case OP_STEMRAW: case OP_POOL: case OP_MLP: case OP_MAPS: case OP_APPLY: case OP_RESAMPLE: case OP_ZERO:
-        case OP_TONCHW: case OP_GATHER: {
-            static const char* names[] = {"stem_kernel(raw)", "pool_partial", "ca_mlp", "cbam_maps", "cbam_apply",
-                                          "resample_slice", "zero_slice", "sb_to_nchw", "head_gather"};
-            snprintf(out->kernel, sizeof out->kernel, "%s", names[o.kind - OP_STEMRAW]);
-            snprintf(out->label, sizeof out->label, "seg_hrnet3");
-            if (o.kind == OP_POOL && o.out == h->stemraw_partial && stem_pools(*h, height, width)) {
-                out->kernel[0] = 0;
-                snprintf(out->label, sizeof out->label, "seg_hrnet3 (inside stem_kernel(raw))");
-                break;
-            }
-            if (o.job >= 0 && (o.kind == OP_POOL || o.kind == OP_MLP || o.kind == OP_MAPS || o.kind == OP_APPLY)) {
-                // merged launch of the group (run_forward): issued at the first member, for every member that launches at all
-                const JobGroup& g = h->jobs[o.job];
-                auto folded = [&](const Op& ok) {
-                    return ok.kind == OP_MAPS && cbam_fused(*h, h->tensors[ok.in].Cp, lh[h->tensors[ok.in].level], lw[h->tensors[ok.in].level]);
-                };
-                int launching = 0;
-                for (int k = 0; k < g.n; ++k) launching += folded(h->ops[g.op[k]]) ? 0 : 1;
-                if (o.jpos > 0 || launching == 0) {
-                    out->kernel[0] = 0;
-                    snprintf(out->label, sizeof out->label, "seg_hrnet3 (%s)", launching ? "in the merged launch" : "inside cbam_spatial");
-                    break;
-                }
-                static const char* jn[] = {"cbam_jobs(pool)", "cbam_jobs(mlp)", "cbam_jobs(maps)", "cbam_jobs(apply)"};
-                snprintf(out->kernel, sizeof out->kernel, "%s", jn[o.kind - OP_POOL]);
-                snprintf(out->label, sizeof out->label, "seg_hrnet3: %d branches", launching);
-                for (int k = 0; k < g.n; ++k) {
-                    const Op& ok = h->ops[g.op[k]];
-                    if (!folded(ok)) out->bytes += (ok.in >= 0 ? tbytes(ok.in) : 0.0) + (ok.out >= 0 ? tbytes(ok.out) : 0.0);
-                }
-                break;
-            }
-            if ((o.kind == OP_MAPS || o.kind == OP_APPLY) &&
-                cbam_fused(*h, h->tensors[o.in].Cp, lh[h->tensors[o.in].level], lw[h->tensors[o.in].level])) {
-                if (o.kind == OP_MAPS) { out->kernel[0] = 0; snprintf(out->label, sizeof out->label, "(inside cbam_spatial)"); break; }
-                snprintf(out->kernel, sizeof out->kernel, "cbam_spatial");
-            }
-            out->bytes += (o.in >= 0 ? tbytes(o.in) : 0.0) + (o.out >= 0 ? tbytes(o.out) : 0.0);
-            if (o.kind == OP_GATHER) out->bytes += tbytes(o.terms[0]);
-            break;
-        }
-        case OP_FINAL: {
-            const ConvSpec& s = h->specs[h->spec_final];
-            snprintf(out->kernel, sizeof out->kernel, "final_kernel");
-            snprintf(out->label, sizeof out->label, "%s", s.name.c_str());
-            out->flops = 2.0 * n * height * width * s.cout * s.cin * 9;
-            out->bytes = tbytes(o.in) + (double)n * height * width * (h->cfg.cin + s.cout) * 4;
-            break;
-        }
-    }
-    return 0;
+    return run_op(*h, h->ops[index], shape_decisions(*h, n, height, width), Buffers{}, nullptr, out);
 }
 
 int esahrnet_partial_tiles(esahrnet_handle h, int height, int width, int* ntiles) {

@@ -4,6 +4,9 @@ topology (checked against the oracle's independent enumeration and the reference
 state_dict keys held in the golden fixtures), the host logic (BN folding, config checks, top-k,
 back-projection, synth determinism) and the loud failure without a GPU."""
 import ctypes as C
+import gzip
+import importlib.util
+import json
 import os
 import re
 
@@ -17,6 +20,9 @@ from esa_pose_estimation_amd import _lib, config, fold, inference, seg_hrnet, se
 from oracle import hrnet_ref, keypoints_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("make_op_descs", os.path.join(ROOT, "tests", "golden", "make_op_descs.py"))
+make_op_descs = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(make_op_descs)
 
 
 def test_library_exports_every_declared_symbol():
@@ -343,3 +349,19 @@ def test_hot_kernels_keep_their_registers():
             assert u["waves_per_simd"] >= 2, (k, u)          # two workgroups of four waves per CU
         if "head_gather_kernelILi6E" in k:
             assert u["vgprs"] <= 128 and u["waves_per_simd"] == 4, (k, u)
+
+
+@pytest.mark.parametrize("combo", make_op_descs.COMBOS, ids=lambda c: make_op_descs.combo_key(*c))
+def test_op_descriptions_match_the_fixture(combo, monkeypatch):
+    """esahrnet_op_desc_get names every launch of the plan and counts its FLOPs and bytes (bench.py's roofline leg, the GPU
+    tests' kernel checks).  tests/golden/op_descs.json.gz pins them for every variant / precision / width and four shapes:
+    strings byte for byte and the figures exactly (the same double expressions, no tolerance)."""
+    for k in [k for k in os.environ if k.startswith("ESAHRNET_")]:
+        monkeypatch.delenv(k)                   # plan switches: esahrnet_create reads them
+    want = json.load(gzip.open(make_op_descs.OUT))[make_op_descs.combo_key(*combo)]
+    got = make_op_descs.op_descs(*combo)
+    assert list(got) == list(want)
+    for shape, rows in want.items():
+        assert len(got[shape]) == len(rows), shape
+        for i, (g, w) in enumerate(zip(got[shape], rows)):
+            assert g == w, (shape, i)
