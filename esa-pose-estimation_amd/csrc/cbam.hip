@@ -1,5 +1,7 @@
 // cbam.hip — the CBAM attention of the seg_hrnet3 variant on SB tensors — and on the
-// fp32-grade mode's plain f32 NHWC tensors: 8 channels are 32 bytes in both (sb.h: load8_fmt / store8_fmt).
+// fp32-grade mode's plain f32 NHWC tensors: 8 channels are 32 bytes in both (sb.h: load8_fmt / store8_fmt) — and on the
+// bf16 mode's BF tensors (8 channels = 16 bytes): every body below takes the format as a template parameter BF, and the
+// BF code objects are kernels of their own (*_bf_kernel), so the SB / F32 ones are the code they always were.
 //
 // Replaces ChannelAttention / SpatialAttention of models/seg_hrnet3.py:32-61 and their use inside
 // BasicBlock.forward (:90-91: out = ca(out)*out; out = sa(out)*out, before the residual add) and on
@@ -20,9 +22,22 @@ namespace {
 
 __device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }
 
+// 8 channels of a pixel: 32 bytes in SB / F32 (run-time flag f32), 16 bytes in BF — read as f32, written rounded once
+template <bool BF> __device__ __forceinline__ void ld8(const char* p, float v[8], bool f32) {
+    if constexpr (BF) unpack8_bf16(*reinterpret_cast<const uint4*>(p), v);
+    else load8_fmt(p, v, f32);
+}
+template <bool BF> __device__ __forceinline__ void st8(char* p, const float v[8], bool f32) {
+    if constexpr (BF) *reinterpret_cast<uint4*>(p) = pack8_bf16(v);
+    else store8_fmt(p, v, f32);
+}
+
 // ---- pool_partial: grid (P, N), 256 threads; thread = (pixel lane pl, channel group c8) ----------
+// (BF: Cp up to 2048 — W48's 384-channel branch — so the reduction walks the channels in steps of 256)
+template <bool BF>
 __device__ __forceinline__ void pool_partial_body(const char* x, float* partial, int HW, int Cp, int P, int slab, int n,
                                                   float* ssum, float* smax, bool f32) {
+    constexpr int EB = BF ? 2 : 4, GB = 8 * EB;
     const int G = Cp >> 3, PL = 256 / G;
     const int S = (HW + P - 1) / P;
     const int p0 = slab * S, p1 = min(HW, p0 + S);
@@ -32,27 +47,37 @@ __device__ __forceinline__ void pool_partial_body(const char* x, float* partial,
     for (int i = 0; i < 8; ++i) { s[i] = 0.f; m[i] = -INFINITY; }
     if (pl < PL)
         for (int p = p0 + pl; p < p1; p += PL) {
-            const char* a = x + ((size_t)n * HW + p) * (size_t)(Cp * 4) + c8 * 32;
+            const char* a = x + ((size_t)n * HW + p) * (size_t)(Cp * EB) + c8 * GB;
             float v[8];
-            load8_fmt(a, v, f32);
+            ld8<BF>(a, v, f32);
 #pragma unroll
             for (int i = 0; i < 8; ++i) { s[i] += v[i]; m[i] = fmaxf(m[i], v[i]); }
         }
 #pragma unroll
     for (int i = 0; i < 8; ++i) { ssum[tid * 8 + i] = s[i]; smax[tid * 8 + i] = m[i]; }
     __syncthreads();
-    if (tid < Cp) {                       // channel c = tid: reduce over the pixel lanes
-        const int g = tid >> 3, i = tid & 7;
+    auto reduce = [&](int c) {                  // channel c: reduce over the pixel lanes
+        const int g = c >> 3, i = c & 7;
         float a = 0.f, b = -INFINITY;
         for (int l = 0; l < PL; ++l) { a += ssum[(l * G + g) * 8 + i]; b = fmaxf(b, smax[(l * G + g) * 8 + i]); }
-        float* o = partial + (((size_t)n * P + slab) * Cp + tid) * 2;
+        float* o = partial + (((size_t)n * P + slab) * Cp + c) * 2;
         o[0] = a; o[1] = b;
+    };
+    if constexpr (BF) {
+        for (int c = tid; c < Cp; c += 256) reduce(c);
+    } else {
+        if (tid < Cp) reduce(tid);
     }
 }
 __global__ __launch_bounds__(256) void pool_partial_kernel(const char* x, float* partial, int HW, int Cp, int P, int f32) {
     __shared__ float ssum[256 * 8];
     __shared__ float smax[256 * 8];
-    pool_partial_body(x, partial, HW, Cp, P, (int)blockIdx.x, (int)blockIdx.y, ssum, smax, f32 != 0);
+    pool_partial_body<false>(x, partial, HW, Cp, P, (int)blockIdx.x, (int)blockIdx.y, ssum, smax, f32 != 0);
+}
+__global__ __launch_bounds__(256) void pool_partial_bf_kernel(const char* x, float* partial, int HW, int Cp, int P) {
+    __shared__ float ssum[256 * 8];
+    __shared__ float smax[256 * 8];
+    pool_partial_body<true>(x, partial, HW, Cp, P, (int)blockIdx.x, (int)blockIdx.y, ssum, smax, false);
 }
 
 // ---- ca_mlp: grid N, 256 threads ----------------------------------------------------------------------
@@ -106,8 +131,10 @@ __global__ __launch_bounds__(256) void ca_mlp_kernel(const float* partial, const
 
 // ---- cbam_maps: thread = (pixel, 8-channel group), group fastest -> coalesced 32-B pieces; the G
 // partial (sum, max) of a pixel meet in LDS ------------------------------------------------------------
+template <bool BF>
 __device__ __forceinline__ void cbam_maps_body(const char* x, const float* ca, float* maps, long long npix, int HW, int C, int Cp,
                                                long long block, float* ps, float* pm, bool f32) {
+    constexpr int EB = BF ? 2 : 4, GB = 8 * EB;
     const int G = Cp >> 3, PPB = 256 / G;                 // pixels per block
     const int tid = threadIdx.x, pl = tid / G, c8 = tid - pl * G;
     const long long pix = block * PPB + pl;
@@ -115,9 +142,9 @@ __device__ __forceinline__ void cbam_maps_body(const char* x, const float* ca, f
     if (pl < PPB && pix < npix && c8 * 8 < C) {
         const int n = (int)(pix / HW);
         const float* cn = ca + (size_t)n * Cp + c8 * 8;
-        const char* a = x + (size_t)pix * (size_t)(Cp * 4) + c8 * 32;
+        const char* a = x + (size_t)pix * (size_t)(Cp * EB) + c8 * GB;
         float v[8];
-        load8_fmt(a, v, f32);
+        ld8<BF>(a, v, f32);
 #pragma unroll
         for (int i = 0; i < 8; ++i)
             if (c8 * 8 + i < C) { const float u = v[i] * cn[i]; s += u; m = fmaxf(m, u); }
@@ -134,12 +161,19 @@ __device__ __forceinline__ void cbam_maps_body(const char* x, const float* ca, f
 __global__ __launch_bounds__(256) void cbam_maps_kernel(const char* x, const float* ca, float* maps, long long npix,
                                                         int HW, int C, int Cp, int f32) {
     __shared__ float ps[256], pm[256];
-    cbam_maps_body(x, ca, maps, npix, HW, C, Cp, (long long)blockIdx.x, ps, pm, f32 != 0);
+    cbam_maps_body<false>(x, ca, maps, npix, HW, C, Cp, (long long)blockIdx.x, ps, pm, f32 != 0);
+}
+__global__ __launch_bounds__(256) void cbam_maps_bf_kernel(const char* x, const float* ca, float* maps, long long npix, int HW,
+                                                           int C, int Cp) {
+    __shared__ float ps[256], pm[256];
+    cbam_maps_body<true>(x, ca, maps, npix, HW, C, Cp, (long long)blockIdx.x, ps, pm, false);
 }
 
 // ---- cbam_apply: thread = (pixel, 8-channel group); the pixel's first thread evaluates the 7x7
 // spatial attention once and shares it through LDS ----------------------------------------------------
+template <bool BF>
 __device__ __forceinline__ void cbam_apply_body(const CbamApplyParams& p, long long npix, long long block, float* w, float* sas) {
+    constexpr int EB = BF ? 2 : 4, GB = 8 * EB;
     if (threadIdx.x < 98) w[threadIdx.x] = p.w_sa[threadIdx.x];
     __syncthreads();
     const int G = p.Cp >> 3, PPB = 256 / G;
@@ -176,15 +210,15 @@ __device__ __forceinline__ void cbam_apply_body(const CbamApplyParams& p, long l
     const float sa = sas[pl];
     const float* cn = p.ca + (size_t)n * p.Cp + c8 * 8;
     const bool f32 = p.fmt == FMT_F32;
-    const char* a = p.x + (size_t)idx * (size_t)(p.Cp * 4) + c8 * 32;
+    const char* a = p.x + (size_t)idx * (size_t)(p.Cp * EB) + c8 * GB;
     float v[8];
-    load8_fmt(a, v, f32);
+    ld8<BF>(a, v, f32);
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = (sa * cn[i]) * v[i];
     if (p.res) {
-        const char* r = p.res + (size_t)idx * (size_t)(p.Cp * 4) + c8 * 32;
+        const char* r = p.res + (size_t)idx * (size_t)(p.Cp * EB) + c8 * GB;
         float rv[8];
-        load8_fmt(r, rv, f32);
+        ld8<BF>(r, rv, f32);
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] += rv[i];
     }
@@ -192,13 +226,18 @@ __device__ __forceinline__ void cbam_apply_body(const CbamApplyParams& p, long l
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i], 0.f);
     }
-    store8_fmt(p.y + (size_t)idx * (size_t)p.y_pix_bytes + ((p.y_c0 >> 3) + c8) * 32, v, f32);
+    st8<BF>(p.y + (size_t)idx * (size_t)p.y_pix_bytes + ((p.y_c0 >> 3) + c8) * GB, v, f32);
 }
 
 __global__ __launch_bounds__(256) void cbam_apply_kernel(CbamApplyParams p, long long npix) {
     __shared__ float w[98];
     __shared__ float sas[256];
-    cbam_apply_body(p, npix, (long long)blockIdx.x, w, sas);
+    cbam_apply_body<false>(p, npix, (long long)blockIdx.x, w, sas);
+}
+__global__ __launch_bounds__(256) void cbam_apply_bf_kernel(CbamApplyParams p, long long npix) {
+    __shared__ float w[98];
+    __shared__ float sas[256];
+    cbam_apply_body<true>(p, npix, (long long)blockIdx.x, w, sas);
 }
 
 // ---- cbam_spatial: cbam_maps + cbam_apply in one pass over a 16 x 32 tile (+ 3-pixel halo for the 7x7) -------------
@@ -207,7 +246,9 @@ __global__ __launch_bounds__(256) void cbam_apply_kernel(CbamApplyParams p, long
 // attention from there and applies it.  thread = (pixel, 8-channel group), the G = Cp/8 threads of a pixel are
 // neighbouring lanes (G a power of two <= 32): channel reductions and the 49 taps are shared by xor-shuffles.
 constexpr int CS_TH = 16, CS_TW = 32, CS_HH = CS_TH + 6, CS_HW = CS_TW + 6;
+template <bool BF>
 __device__ __forceinline__ void cbam_spatial_body(const CbamApplyParams& p, int tiles_x, int tiles_y, int block, float* mp, float* w) {
+    constexpr int EB = BF ? 2 : 4, GB = 8 * EB;
     const int tid = threadIdx.x;
     int b = block;
     const int tx0 = (b % tiles_x) * CS_TW; b /= tiles_x;
@@ -234,9 +275,9 @@ __device__ __forceinline__ void cbam_spatial_body(const CbamApplyParams& p, int 
             inside[k] = q < CS_HH * CS_HW && Y >= 0 && Y < p.H && X >= 0 && X < p.W;
             h4[k] = make_uint4(0, 0, 0, 0); l4[k] = make_uint4(0, 0, 0, 0);
             if (inside[k] && lg * 8 < p.C) {
-                const char* a = p.x + (img + (size_t)Y * p.W + X) * (size_t)(p.Cp * 4) + lg * 32;
+                const char* a = p.x + (img + (size_t)Y * p.W + X) * (size_t)(p.Cp * EB) + lg * GB;
                 h4[k] = *reinterpret_cast<const uint4*>(a);
-                l4[k] = *reinterpret_cast<const uint4*>(a + 16);
+                if (!BF) l4[k] = *reinterpret_cast<const uint4*>(a + 16);
             }
         }
 #pragma unroll
@@ -245,7 +286,8 @@ __device__ __forceinline__ void cbam_spatial_body(const CbamApplyParams& p, int 
             float s = 0.f, m = -INFINITY;
             if (inside[k] && lg * 8 < p.C) {
                 float v[8];
-                join8_fmt(h4[k], l4[k], v, f32);
+                if (BF) unpack8_bf16(h4[k], v);
+                else join8_fmt(h4[k], l4[k], v, f32);
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
                     if (lg * 8 + i < p.C) { const float u = v[i] * cn[i]; s += u; m = fmaxf(m, u); }
@@ -269,15 +311,15 @@ __device__ __forceinline__ void cbam_spatial_body(const CbamApplyParams& p, int 
         if (Y >= p.H || X >= p.W) continue;
         const float sa = sigmoidf(part);
         const size_t idx = img + (size_t)Y * p.W + X;
-        const char* a = p.x + idx * (size_t)(p.Cp * 4) + lg * 32;
+        const char* a = p.x + idx * (size_t)(p.Cp * EB) + lg * GB;
         float v[8];
-        load8_fmt(a, v, f32);
+        ld8<BF>(a, v, f32);
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = (sa * cn[i]) * v[i];
         if (p.res) {
-            const char* r = p.res + idx * (size_t)(p.Cp * 4) + lg * 32;
+            const char* r = p.res + idx * (size_t)(p.Cp * EB) + lg * GB;
             float rv[8];
-            load8_fmt(r, rv, f32);
+            ld8<BF>(r, rv, f32);
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] += rv[i];
         }
@@ -285,23 +327,27 @@ __device__ __forceinline__ void cbam_spatial_body(const CbamApplyParams& p, int 
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i], 0.f);
         }
-        store8_fmt(p.y + idx * (size_t)p.y_pix_bytes + ((p.y_c0 >> 3) + lg) * 32, v, f32);
+        st8<BF>(p.y + idx * (size_t)p.y_pix_bytes + ((p.y_c0 >> 3) + lg) * GB, v, f32);
     }
 }
 
 __global__ __launch_bounds__(256) void cbam_spatial_kernel(CbamApplyParams p, int tiles_x, int tiles_y) {
     __shared__ float mp[CS_HH * CS_HW * 2];
     __shared__ float w[98];
-    cbam_spatial_body(p, tiles_x, tiles_y, (int)blockIdx.x, mp, w);
+    cbam_spatial_body<false>(p, tiles_x, tiles_y, (int)blockIdx.x, mp, w);
+}
+__global__ __launch_bounds__(256) void cbam_spatial_bf_kernel(CbamApplyParams p, int tiles_x, int tiles_y) {
+    __shared__ float mp[CS_HH * CS_HW * 2];
+    __shared__ float w[98];
+    cbam_spatial_body<true>(p, tiles_x, tiles_y, (int)blockIdx.x, mp, w);
 }
 
 // ---- the same launches for several tensors at once: the CBAM blocks of the branches of an HRModule at one depth are
 // independent (seg_hrnet3.py: every branch is its own Sequential of BasicBlocks), and on the 32x32 and 16x16 branches each of
 // these kernels is a few microseconds of pure launch latency.  Workgroups [start[j], start[j+1]) run job j exactly as its own
 // launch would. ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void cbam_jobs_kernel(CbamJobs jobs) {
-    __shared__ float sh[4096];
-    __shared__ float sw[128];
+template <bool BF>
+__device__ __forceinline__ void cbam_jobs_body(const CbamJobs& jobs, float* sh, float* sw) {
     const int b = (int)blockIdx.x;
     int j = 0;
 #pragma unroll
@@ -309,12 +355,22 @@ __global__ __launch_bounds__(256) void cbam_jobs_kernel(CbamJobs jobs) {
     const CbamJob& q = jobs.j[j];
     const int bid = b - jobs.start[j];
     switch (q.kind) {
-        case CBAM_POOL: pool_partial_body(q.ap.x, q.partial, q.HW, q.ap.Cp, q.P, bid % q.P, bid / q.P, sh, sh + 2048, q.ap.fmt == FMT_F32); break;
+        case CBAM_POOL: pool_partial_body<BF>(q.ap.x, q.partial, q.HW, q.ap.Cp, q.P, bid % q.P, bid / q.P, sh, sh + 2048, q.ap.fmt == FMT_F32); break;
         case CBAM_MLP: ca_mlp_body(q.partial, q.w0, q.w2, q.ca, q.HW, q.ap.C, q.ap.Cp, q.Cr, q.P, bid, sh, sh + 512, sh + 1024, sh + 1088); break;
-        case CBAM_MAPS: cbam_maps_body(q.ap.x, q.ap.ca, q.maps, (long long)q.ap.N * q.HW, q.HW, q.ap.C, q.ap.Cp, bid, sh, sh + 256, q.ap.fmt == FMT_F32); break;
-        case CBAM_APPLY: cbam_apply_body(q.ap, (long long)q.ap.N * q.HW, bid, sw, sh); break;
-        default: cbam_spatial_body(q.ap, q.tiles_x, q.tiles_y, bid, sh, sw); break;
+        case CBAM_MAPS: cbam_maps_body<BF>(q.ap.x, q.ap.ca, q.maps, (long long)q.ap.N * q.HW, q.HW, q.ap.C, q.ap.Cp, bid, sh, sh + 256, q.ap.fmt == FMT_F32); break;
+        case CBAM_APPLY: cbam_apply_body<BF>(q.ap, (long long)q.ap.N * q.HW, bid, sw, sh); break;
+        default: cbam_spatial_body<BF>(q.ap, q.tiles_x, q.tiles_y, bid, sh, sw); break;
     }
+}
+__global__ __launch_bounds__(256) void cbam_jobs_kernel(CbamJobs jobs) {
+    __shared__ float sh[4096];
+    __shared__ float sw[128];
+    cbam_jobs_body<false>(jobs, sh, sw);
+}
+__global__ __launch_bounds__(256) void cbam_jobs_bf_kernel(CbamJobs jobs) {
+    __shared__ float sh[4096];
+    __shared__ float sw[128];
+    cbam_jobs_body<true>(jobs, sh, sw);
 }
 
 // ---- resample_slice: thread = (dst pixel, 8-channel group of the source) ---------------------------------
@@ -337,7 +393,9 @@ __device__ __forceinline__ LerpR lerp_any(int dst, int in, int out, int align) {
     return r;
 }
 
-__global__ __launch_bounds__(256) void resample_slice_kernel(ResampleParams p, long long total) {
+template <bool BF>
+__device__ __forceinline__ void resample_slice_body(const ResampleParams& p, long long total) {
+    constexpr int EB = BF ? 2 : 4, GB = 8 * EB;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int G = (p.C + 7) >> 3;             // only the groups that hold real channels
@@ -349,7 +407,7 @@ __global__ __launch_bounds__(256) void resample_slice_kernel(ResampleParams p, l
     const int n = (int)(row / p.H);
     float v[8];
     const bool f32 = p.fmt == FMT_F32;
-    auto ld = [&](size_t sp, float* out) { load8_fmt(p.x + sp * (size_t)(p.Cp_src * 4) + c8 * 32, out, f32); };
+    auto ld = [&](size_t sp, float* out) { ld8<BF>(p.x + sp * (size_t)(p.Cp_src * EB) + c8 * GB, out, f32); };
     if (p.h == p.H && p.w == p.W) {
         ld((size_t)pix, v);
     } else {
@@ -361,8 +419,10 @@ __global__ __launch_bounds__(256) void resample_slice_kernel(ResampleParams p, l
         for (int i = 0; i < 8; ++i)
             v[i] = ly.l0 * (lx.l0 * v00[i] + lx.l1 * v01[i]) + ly.l1 * (lx.l0 * v10[i] + lx.l1 * v11[i]);
     }
-    store8_fmt(p.y + (size_t)pix * (size_t)p.y_pix_bytes + ((p.y_c0 >> 3) + c8) * 32, v, f32);
+    st8<BF>(p.y + (size_t)pix * (size_t)p.y_pix_bytes + ((p.y_c0 >> 3) + c8) * GB, v, f32);
 }
+__global__ __launch_bounds__(256) void resample_slice_kernel(ResampleParams p, long long total) { resample_slice_body<false>(p, total); }
+__global__ __launch_bounds__(256) void resample_slice_bf_kernel(ResampleParams p, long long total) { resample_slice_body<true>(p, total); }
 
 __global__ __launch_bounds__(256) void zero_slice_kernel(char* y, long long npix, int y_pix_bytes, int c0, int ngroups) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -373,12 +433,25 @@ __global__ __launch_bounds__(256) void zero_slice_kernel(char* y, long long npix
     *reinterpret_cast<uint4*>(o) = make_uint4(0, 0, 0, 0);
     *reinterpret_cast<uint4*>(o + 16) = make_uint4(0, 0, 0, 0);
 }
+// BF: a group of 8 channels is one 16-byte chunk
+__global__ __launch_bounds__(256) void zero_slice_bf_kernel(char* y, long long npix, int y_pix_bytes, int c0, int ngroups) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= npix * ngroups) return;
+    const long long pix = idx / ngroups;
+    const int g = (int)(idx - pix * ngroups);
+    *reinterpret_cast<uint4*>(y + (size_t)pix * (size_t)y_pix_bytes + ((c0 >> 3) + g) * 16) = make_uint4(0, 0, 0, 0);
+}
 
 inline int blocks(long long total) { return (int)((total + 255) / 256); }
 
 }  // namespace
 
 int launch_pool_partial(const char* x, float* partial, int N, int HW, int Cp, int P, hipStream_t s, int fmt) {
+    if (fmt == FMT_BF) {
+        if ((Cp & 7) || Cp > 2048 || Cp < 8) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(pool_partial_bf_kernel, dim3(P, N), dim3(256), 0, s, x, partial, HW, Cp, P);
+        return (int)hipGetLastError();
+    }
     if ((Cp & 7) || Cp > 256 || Cp < 8 || (fmt != FMT_SB && fmt != FMT_F32)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(pool_partial_kernel, dim3(P, N), dim3(256), 0, s, x, partial, HW, Cp, P, fmt == FMT_F32 ? 1 : 0);
     return (int)hipGetLastError();
@@ -393,16 +466,25 @@ int launch_ca_mlp(const float* partial, const float* w0, const float* w2, float*
 
 int launch_cbam_maps(const char* x, const float* ca, float* maps, int N, int HW, int C, int Cp, hipStream_t s, int fmt) {
     const long long npix = (long long)N * HW;
-    if ((Cp & 7) || Cp > 2048 || Cp < 8 || (fmt != FMT_SB && fmt != FMT_F32)) return (int)hipErrorInvalidValue;
+    if ((Cp & 7) || Cp > 2048 || Cp < 8 || (fmt != FMT_SB && fmt != FMT_F32 && fmt != FMT_BF)) return (int)hipErrorInvalidValue;
     const int ppb = 256 / (Cp >> 3);
+    if (fmt == FMT_BF) {
+        hipLaunchKernelGGL(cbam_maps_bf_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), 0, s, x, ca, maps, npix, HW, C, Cp);
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(cbam_maps_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), 0, s, x, ca, maps, npix, HW, C, Cp, fmt == FMT_F32 ? 1 : 0);
     return (int)hipGetLastError();
 }
 
 int launch_cbam_apply(const CbamApplyParams& p, hipStream_t s) {
     const long long npix = (long long)p.N * p.H * p.W;
-    if ((p.y_c0 & 7) || (p.Cp & 7) || p.Cp > 2048 || p.Cp < 8 || (p.fmt != FMT_SB && p.fmt != FMT_F32)) return (int)hipErrorInvalidValue;
+    if ((p.y_c0 & 7) || (p.Cp & 7) || p.Cp > 2048 || p.Cp < 8 || (p.fmt != FMT_SB && p.fmt != FMT_F32 && p.fmt != FMT_BF))
+        return (int)hipErrorInvalidValue;
     const int ppb = 256 / (p.Cp >> 3);
+    if (p.fmt == FMT_BF) {
+        hipLaunchKernelGGL(cbam_apply_bf_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), 0, s, p, npix);
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(cbam_apply_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), 0, s, p, npix);
     return (int)hipGetLastError();
 }
@@ -410,9 +492,9 @@ int launch_cbam_apply(const CbamApplyParams& p, hipStream_t s) {
 // workgroups job `q` needs (the grid its own launch would use); -1: invalid
 long long cbam_job_blocks(CbamJob& q) {
     const int Cp = q.ap.Cp;
-    if ((Cp & 7) || Cp < 8 || (q.ap.fmt != FMT_SB && q.ap.fmt != FMT_F32)) return -1;
+    if ((Cp & 7) || Cp < 8 || (q.ap.fmt != FMT_SB && q.ap.fmt != FMT_F32 && q.ap.fmt != FMT_BF)) return -1;
     switch (q.kind) {
-        case CBAM_POOL: return Cp > 256 ? -1 : (long long)q.P * q.ap.N;
+        case CBAM_POOL: return Cp > (q.ap.fmt == FMT_BF ? 2048 : 256) ? -1 : (long long)q.P * q.ap.N;
         case CBAM_MLP: return (Cp > 512 || q.Cr > 64 || q.Cr < 1) ? -1 : q.ap.N;
         case CBAM_MAPS: { if (Cp > 2048) return -1; const int ppb = 256 / (Cp >> 3); return ((long long)q.ap.N * q.HW + ppb - 1) / ppb; }
         case CBAM_APPLY: { if (Cp > 2048 || (q.ap.y_c0 & 7)) return -1; const int ppb = 256 / (Cp >> 3); return ((long long)q.ap.N * q.HW + ppb - 1) / ppb; }
@@ -429,6 +511,7 @@ int launch_cbam_jobs(const CbamJob* js, int n, hipStream_t s) {
     CbamJobs jobs{};
     long long at = 0;
     for (int k = 0; k < n; ++k) {
+        if ((js[k].ap.fmt == FMT_BF) != (js[0].ap.fmt == FMT_BF)) return (int)hipErrorInvalidValue;     // one code object per launch
         jobs.j[k] = js[k];
         const long long nb = cbam_job_blocks(jobs.j[k]);
         if (nb <= 0) return (int)hipErrorInvalidValue;
@@ -438,7 +521,8 @@ int launch_cbam_jobs(const CbamJob* js, int n, hipStream_t s) {
     }
     for (int k = n; k <= CBAM_MAXJOBS; ++k) jobs.start[k] = (int)at;
     jobs.n = n;
-    hipLaunchKernelGGL(cbam_jobs_kernel, dim3((unsigned)at), dim3(256), 0, s, jobs);
+    if (js[0].ap.fmt == FMT_BF) hipLaunchKernelGGL(cbam_jobs_bf_kernel, dim3((unsigned)at), dim3(256), 0, s, jobs);
+    else hipLaunchKernelGGL(cbam_jobs_kernel, dim3((unsigned)at), dim3(256), 0, s, jobs);
     return (int)hipGetLastError();
 }
 
@@ -448,24 +532,34 @@ bool cbam_spatial_supported(int Cp) {
 }
 
 int launch_cbam_spatial(const CbamApplyParams& p, hipStream_t s) {
-    if (!cbam_spatial_supported(p.Cp) || (p.y_c0 & 7) || p.C < 1 || p.C > p.Cp || (p.fmt != FMT_SB && p.fmt != FMT_F32)) return (int)hipErrorInvalidValue;
+    if (!cbam_spatial_supported(p.Cp) || (p.y_c0 & 7) || p.C < 1 || p.C > p.Cp || (p.fmt != FMT_SB && p.fmt != FMT_F32 && p.fmt != FMT_BF))
+        return (int)hipErrorInvalidValue;
     const int tiles_x = (p.W + CS_TW - 1) / CS_TW, tiles_y = (p.H + CS_TH - 1) / CS_TH;
     const long long nblk = (long long)tiles_x * tiles_y * p.N;
     if (nblk <= 0 || nblk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(cbam_spatial_kernel, dim3((unsigned)nblk), dim3(256), 0, s, p, tiles_x, tiles_y);
+    if (p.fmt == FMT_BF) hipLaunchKernelGGL(cbam_spatial_bf_kernel, dim3((unsigned)nblk), dim3(256), 0, s, p, tiles_x, tiles_y);
+    else hipLaunchKernelGGL(cbam_spatial_kernel, dim3((unsigned)nblk), dim3(256), 0, s, p, tiles_x, tiles_y);
     return (int)hipGetLastError();
 }
 
 int launch_resample_slice(const ResampleParams& p, hipStream_t s) {
-    if ((p.y_c0 & 7) || (p.Cp_src & 7) || (p.fmt != FMT_SB && p.fmt != FMT_F32)) return (int)hipErrorInvalidValue;
+    if ((p.y_c0 & 7) || (p.Cp_src & 7) || (p.fmt != FMT_SB && p.fmt != FMT_F32 && p.fmt != FMT_BF)) return (int)hipErrorInvalidValue;
     const long long total = (long long)p.N * p.H * p.W * ((p.C + 7) >> 3);
+    if (p.fmt == FMT_BF) {
+        hipLaunchKernelGGL(resample_slice_bf_kernel, dim3(blocks(total)), dim3(256), 0, s, p, total);
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(resample_slice_kernel, dim3(blocks(total)), dim3(256), 0, s, p, total);
     return (int)hipGetLastError();
 }
 
-int launch_zero_slice(char* y, long long npix, int y_pix_bytes, int c0, int nchan, hipStream_t s) {
+int launch_zero_slice(char* y, long long npix, int y_pix_bytes, int c0, int nchan, hipStream_t s, int fmt) {
     if ((c0 & 7) || (nchan & 7) || nchan <= 0) return (int)hipErrorInvalidValue;
     const long long total = npix * (nchan >> 3);
+    if (fmt == FMT_BF) {
+        hipLaunchKernelGGL(zero_slice_bf_kernel, dim3(blocks(total)), dim3(256), 0, s, y, npix, y_pix_bytes, c0, nchan >> 3);
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(zero_slice_kernel, dim3(blocks(total)), dim3(256), 0, s, y, npix, y_pix_bytes, c0, nchan >> 3);
     return (int)hipGetLastError();
 }

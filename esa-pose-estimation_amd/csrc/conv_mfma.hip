@@ -527,7 +527,7 @@ Choice choose_conv(const ConvParams& p, int k, int stride) {
     if (p.fmt == FMT_F32) return conv_x6_supported(p, k, stride) ? C_X6 : C_NONE;      // f32 tensors: bf16x6 arithmetic (conv_x6.hip)
     if ((p.fmt == FMT_BF)) {         // single-bf16 tensors: the stream kernel (every 3x3) and the register 1x1 kernel only
         if (k == 3 && stride == 1) return conv_s2c32_supported(p) ? C_STREAM_S1 : C_NONE;
-        if (k == 3 && stride == 2) return conv_s2c32_supported(p) ? C_STREAM_S2 : C_NONE;
+        if (k == 3 && stride == 2) return conv_s2c32_supported(p) && !p.out_f32 ? C_STREAM_S2 : C_NONE;
         if (k == 1 && stride == 1) return conv1x1_supported(p) ? C_1X1 : C_NONE;
         return C_NONE;
     }
@@ -581,7 +581,7 @@ const char* conv_kernel_name(const ConvParams& p, int k, int stride) {
     if (p.fmt == FMT_F32) return choose_conv(p, k, stride) == C_X6 ? conv_x6_kernel_name(p, k, stride) : "none";
     if ((p.fmt == FMT_BF)) {
         switch (choose_conv(p, k, stride)) {
-            case C_STREAM_S1: return "conv_s2c32_kernel<1, 8, 4, false, true>";
+            case C_STREAM_S1: return p.out_f32 ? "conv_s2c32_f32out_kernel<1, 8, 4, true>" : "conv_s2c32_kernel<1, 8, 4, false, true>";
             case C_STREAM_S2: return "conv_s2c32_kernel<2, 4, 4, false, true>";
             case C_1X1: return "conv1x1_kernel<bf16>";
             default: return "none";

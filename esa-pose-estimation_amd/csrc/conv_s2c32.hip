@@ -99,9 +99,11 @@ __device__ __forceinline__ int div_magic(int b, int d, uint32_t m) {
 // and retires the reads of step s at once.  (Single-buffered: barrier, write, barrier, and the LDS-read pipe starts
 // cold behind the second one.)
 // OCC: workgroups per CU the register budget is cut for (2: 256 VGPRs per wave; 1: 512 — the 16-row tile).
+// OF (BF only, conv_s2c32_f32out_kernel): the output is plain f32 NHWC [N][OH][OW][Coutp] — seg_hrnet3's output layer in
+// the bf16 mode, whose heat-maps leave unrounded; no residual.  The other kernels are instantiated with OF = false.
 // The body is shared by the one-convolution kernel and by conv_s2c32_jobs_kernel (several independent convolutions in
 // one launch): `bid` / `G` are the workgroup's index and the grid size WITHIN its convolution.
-template <int S, int TH, int MW, bool MH, bool BF, bool DB, int OCC>
+template <int S, int TH, int MW, bool MH, bool BF, bool DB, int OCC, bool OF = false>
 __device__ __forceinline__ void conv_s2c32_body(const ConvParams& p, const StreamGeo& geo, const int bid, const int G) {
     using S2C = ConvCfg<3, S, TH, 2>;
     constexpr int RG = 4 / MW;                  // row groups
@@ -122,7 +124,8 @@ __device__ __forceinline__ void conv_s2c32_body(const ConvParams& p, const Strea
     constexpr int EB = BF ? 2 : 4;             // bytes per channel
     const int nchunks = p.Cinp >> (BF ? 6 : 5);
     const int pixb = p.Cinp * EB;
-    int opix = p.Coutp * EB;                                             // (per item in a multi-head launch)
+    static_assert(!OF || (BF && !MH), "f32 output: single-head bf16 only");
+    int opix = p.Coutp * (OF ? 4 : EB);                                  // (per item in a multi-head launch)
     const int ximg = p.H * p.W * pixb;
     int yimg = p.OH * p.OW * opix;                                       // bytes per image (< 2^31, host-checked)
     int item = xcd_contiguous(bid, G);
@@ -322,7 +325,7 @@ __device__ __forceinline__ void conv_s2c32_body(const ConvParams& p, const Strea
         }
         // output rows of this wave: 32-bit offsets inside the image, OOB for pixels outside it
         const int rox = ox0 + (lane & 15), roy = oy0 + rg * NT;
-        const uint32_t o0 = rox < p.OW ? (uint32_t)((roy * p.OW + rox) * opix + (BF ? co * 2 : chunk_ofs(co, g))) : OOB;
+        const uint32_t o0 = rox < p.OW ? (uint32_t)((roy * p.OW + rox) * opix + (OF ? co * 4 : BF ? co * 2 : chunk_ofs(co, g))) : OOB;
         const int orow = p.OW * opix, yso = n * yimg;
         const int nrows = p.OH - roy;                                   // rows t < nrows exist
         // residual (last chunk only): the first half of the wave's rows is loaded at the start of the step and folded
@@ -382,6 +385,11 @@ __device__ __forceinline__ void conv_s2c32_body(const ConvParams& p, const Strea
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = relu_opt(v[i], rfl);
             const uint32_t so_ = t < nrows ? o0 + (uint32_t)(t * orow) : OOB;
+            if (OF) {       // 4 f32 channels of one pixel = 16 bytes per lane (vector offset only, see below)
+                const u32x4 fv = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+                __builtin_amdgcn_raw_buffer_store_b128(fv, ry, (int)(so_ + (uint32_t)yso), 0, 0);
+                return;
+            }
             if (BF) {       // 4 channels of one pixel = 8 bytes per lane; the four rows of 16 lanes fill 32 contiguous bytes
                 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
                 const uint2 pk = pack4_bf16(v);
@@ -508,6 +516,11 @@ template <int S, int TH, int MW, bool MH = false, bool BF = false, bool DB = fal
 __global__ __launch_bounds__(NTHREADS, OCC) void conv_s2c32_kernel(ConvParams p, StreamGeo geo) {
     conv_s2c32_body<S, TH, MW, MH, BF, DB, OCC>(p, geo, (int)blockIdx.x, (int)gridDim.x);
 }
+// the same body with the f32 epilogue (OF): single-buffered in every batch, so that a crop's bits do not depend on it
+template <int S, int TH, int MW, bool BF>
+__global__ __launch_bounds__(NTHREADS, 2) void conv_s2c32_f32out_kernel(ConvParams p, StreamGeo geo) {
+    conv_s2c32_body<S, TH, MW, false, BF, false, 2, true>(p, geo, (int)blockIdx.x, (int)gridDim.x);
+}
 
 // Several INDEPENDENT convolutions (the same-depth 3x3s of the 64/128/256-channel branches of an HRModule,
 // models/seg_hrnet.py:143-174: the branches do not talk to each other between two fuse layers) in one launch.
@@ -550,7 +563,7 @@ int images_per_launch(const ConvParams& p) {
     if (p.nheads > 1) {
         for (int h = 0; h < p.nheads; ++h) per = std::max(per, (long long)p.OH * p.OW * (p.hb[h + 1] - p.hb[h]) * eb);
     } else {
-        per = std::max(per, (long long)p.OH * p.OW * p.Coutp * eb);
+        per = std::max(per, (long long)p.OH * p.OW * p.Coutp * (p.out_f32 ? 4 : eb));
     }
     return (int)std::min<long long>(p.N, g_launch_limit.load(std::memory_order_relaxed) / std::max(per, 1LL));
 }
@@ -558,19 +571,22 @@ int images_per_launch(const ConvParams& p) {
 #ifndef S2_DB
 #define S2_DB 1          // 1: stride-1 launches with at most one workgroup per CU run the double-buffered variant
 #endif
-template <int S, int TH, int MW, bool MH, bool BF, bool DB, int OCC = 2>
+template <int S, int TH, int MW, bool MH, bool BF, bool DB, int OCC = 2, bool OF = false>
 int launch_s2c32_k(const ConvParams& p, const StreamGeo& geo, int grid, hipStream_t stream) {
     using S2C = ConvCfg<3, S, TH, 2>;
     constexpr int LDS = (DB ? 2 : 1) * S2C::XBYTES;
-    auto kern = conv_s2c32_kernel<S, TH, MW, MH, BF, DB, OCC>;
+    static_assert(!OF || (!DB && OCC == 2 && !MH), "conv_s2c32_f32out_kernel is the single-buffered body");
+    void (*kern)(ConvParams, StreamGeo);
+    if constexpr (OF) kern = conv_s2c32_f32out_kernel<S, TH, MW, BF>;
+    else kern = conv_s2c32_kernel<S, TH, MW, MH, BF, DB, OCC>;
     if (const int e_ = ensure_dyn_lds(reinterpret_cast<const void*>(kern), LDS)) return e_;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NTHREADS), LDS, stream, p, geo);
     return (int)hipGetLastError();
 }
 
-template <int S, int TH, int MW, bool MH = false, bool BF = false>
+template <int S, int TH, int MW, bool MH = false, bool BF = false, bool OF = false>
 int launch_s2c32_t(const ConvParams& p, hipStream_t stream) {
-    constexpr int EB = BF ? 2 : 4;
+    constexpr int EB = BF ? 2 : 4, OEB = OF ? 4 : EB;
     const int nmax = images_per_launch(p);
     if (nmax < 1) return (int)hipErrorInvalidValue;
     if (p.N > nmax) {
@@ -578,11 +594,11 @@ int launch_s2c32_t(const ConvParams& p, hipStream_t stream) {
             ConvParams q = p;
             q.N = std::min(nmax, p.N - n0);
             q.x = p.x + (size_t)n0 * p.H * p.W * p.Cinp * EB;
-            if (p.y) q.y = p.y + (size_t)n0 * p.OH * p.OW * p.Coutp * EB;
+            if (p.y) q.y = p.y + (size_t)n0 * p.OH * p.OW * p.Coutp * OEB;
             if (p.res) q.res = p.res + (size_t)n0 * p.OH * p.OW * p.Coutp * EB;
             for (int h = 0; h < p.nheads && h < 3; ++h)
                 if (p.yh[h]) q.yh[h] = p.yh[h] + (size_t)n0 * p.OH * p.OW * (p.hb[h + 1] - p.hb[h]) * EB;
-            if (const int e = launch_s2c32_t<S, TH, MW, MH, BF>(q, stream)) return e;
+            if (const int e = launch_s2c32_t<S, TH, MW, MH, BF, OF>(q, stream)) return e;
         }
         return 0;
     }
@@ -601,7 +617,9 @@ int launch_s2c32_t(const ConvParams& p, hipStream_t stream) {
     if (grid > geo.ctiles) grid -= grid % geo.ctiles;   // grid stride keeps the cout slice of a workgroup constant
     // All variants run the same MFMAs in the same order on every accumulator: a crop's result does not depend on which
     // one a batch size selects.
-    if constexpr (TH == 16) {
+    if constexpr (OF) {
+        return launch_s2c32_k<S, TH, MW, MH, BF, false, 2, true>(p, geo, grid, stream);
+    } else if constexpr (TH == 16) {
         return launch_s2c32_k<S, TH, MW, MH, BF, true, 1>(p, geo, grid, stream);
     } else {
         if constexpr (S2_DB && S == 1 && !MH) {
@@ -621,15 +639,16 @@ void set_stream_launch_limit(long long bytes) {
 // one IMAGE must be addressable with 31-bit byte offsets (buffer descriptors, OOB marker 2^31); a batch that is not
 // is cut into image ranges by the launcher (images_per_launch), so this predicate does not look at N
 bool conv_s2c32_supported(const ConvParams& p) {
-    if ((p.fmt == FMT_BF)) return (p.Cinp & 63) == 0 && p.Cinp >= 64 && (p.Coutp & 63) == 0 && !p.out_f32 && p.nheads <= 1 &&
-                     (long long)p.H * p.W * p.Cinp * 2 < 0x7fffffffLL && (long long)p.OH * p.OW * p.Coutp * 2 < 0x7fffffffLL;
+    // (BF with out_f32: stride 1 without residual only — conv_s2c32_f32out_kernel; launch_conv_s2c32 refuses it)
+    if ((p.fmt == FMT_BF)) return (p.Cinp & 63) == 0 && p.Cinp >= 64 && (p.Coutp & 63) == 0 && (!p.out_f32 || !p.res) && p.nheads <= 1 &&
+                     (long long)p.H * p.W * p.Cinp * 2 < 0x7fffffffLL && (long long)p.OH * p.OW * p.Coutp * (p.out_f32 ? 4 : 2) < 0x7fffffffLL;
     return (p.Cinp & 31) == 0 && p.Cinp >= 32 && (p.Coutp & 31) == 0 && !p.out_f32 &&
            (long long)p.H * p.W * p.Cinp * 4 < 0x7fffffffLL &&
            (long long)p.OH * p.OW * p.Coutp * 4 < 0x7fffffffLL;
 }
 
 int launch_conv_s2c32(const ConvParams& p, hipStream_t stream) {
-    if (!conv_s2c32_supported(p)) return (int)hipErrorInvalidValue;
+    if (!conv_s2c32_supported(p) || p.out_f32) return (int)hipErrorInvalidValue;
     if ((p.fmt == FMT_BF)) return launch_s2c32_t<2, 4, 4, false, true>(p, stream);
     return (p.Coutp % 64 == 0) ? launch_s2c32_t<2, 4, 4>(p, stream) : launch_s2c32_t<2, 4, 2>(p, stream);
 }
@@ -670,7 +689,7 @@ bool use_th16(const ConvParams& p) {
 
 int launch_conv_s1w(const ConvParams& p, hipStream_t stream) {
     if (!conv_s2c32_supported(p)) return (int)hipErrorInvalidValue;
-    if ((p.fmt == FMT_BF)) return launch_s2c32_t<1, 8, 4, false, true>(p, stream);
+    if ((p.fmt == FMT_BF)) return p.out_f32 ? launch_s2c32_t<1, 8, 4, false, true, true>(p, stream) : launch_s2c32_t<1, 8, 4, false, true>(p, stream);
 #if S2_TH16
     if (use_th16(p)) return launch_s2c32_t<1, 16, 4>(p, stream);
 #endif

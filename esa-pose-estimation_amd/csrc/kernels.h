@@ -21,7 +21,8 @@ struct ConvParams {
     int N, H, W, OH, OW;
     int Cinp, Coutp;    // multiples of 32
     int relu;
-    int out_f32;        // 0: y is SB; 1: y is plain f32 NHWC [N][OH][OW][Coutp] (head terms t_b)
+    int out_f32;        // 0: y is SB; 1: y is plain f32 NHWC [N][OH][OW][Coutp] (head terms t_b; FMT_BF: the stride-1 3x3
+                        //    without residual only, conv_s2c32_f32out_kernel — seg_hrnet3's output layer)
     int fmt;            // FMT_SB; FMT_BF: x, y, res are BF tensors (single bf16, sb.h), Cinp / Coutp multiples of 64, weights
                         //    packed by pack_conv_weights_bf, served by the stream kernel (3x3) and conv1x1 only; FMT_F32: plain
                         //    f32 NHWC tensors, weights packed by pack_conv_weights_x6, served by conv_x6.hip (bf16x6 arithmetic)
@@ -97,7 +98,8 @@ struct StemParams {
 };
 int launch_stem(const StemParams& p, hipStream_t stream);
 // the same convolution + the per-channel (sum, max) of the output over slabs of pixels, in pool_partial's layout
-// [N][slabs][cout][2] (cbam.hip); stem_pool_slabs: slabs per image, 0 = not available (needs cin 1, cout 64)
+// [N][slabs][cout][2] (cbam.hip); stem_pool_slabs: slabs per image, 0 = not available (needs cin 1, cout 64).  FMT_BF: the
+// partials are of the bf16-rounded values the tensor holds
 int stem_pool_slabs(int cin, int cout, int H, int W);
 int launch_stem_pool(const StemParams& p, float* pool, hipStream_t stream);
 
@@ -241,7 +243,7 @@ struct CbamApplyParams {
     char* y;            // SB, pixel pitch y_pix_bytes, written at channel offset y_c0 (multiple of 8)
     int N, H, W, Cp, y_pix_bytes, y_c0, relu;
     int C;              // real channels (cbam_spatial only: it forms the maps itself and ignores `maps`)
-    int fmt = FMT_SB;   // FMT_SB or FMT_F32 (x, res and y alike)
+    int fmt = FMT_SB;   // FMT_SB, FMT_F32 or FMT_BF (x, res and y alike; BF: 8 channels = 16 bytes, y_pix_bytes = Cp * 2)
 };
 int launch_cbam_apply(const CbamApplyParams& p, hipStream_t s);
 // maps + apply in one pass (no `maps` tensor); Cp / 8 must be a power of two <= 32
@@ -266,10 +268,10 @@ struct ResampleParams {
     char* y;            // SB [N][H][W][..], pixel pitch y_pix_bytes, channel offset y_c0 (multiple of 8)
     int N, h, w, H, W, C, Cp_src, y_pix_bytes, y_c0;
     int align;          // 1: align_corners=True, 0: False (irrelevant when h==H && w==W: copy)
-    int fmt = FMT_SB;   // FMT_SB or FMT_F32 (x and y alike)
+    int fmt = FMT_SB;   // FMT_SB, FMT_F32 or FMT_BF (x and y alike)
 };
 int launch_resample_slice(const ResampleParams& p, hipStream_t s);
-int launch_zero_slice(char* y, long long npix, int y_pix_bytes, int c0, int nchan, hipStream_t s);
+int launch_zero_slice(char* y, long long npix, int y_pix_bytes, int c0, int nchan, hipStream_t s, int fmt = FMT_SB);
 
 // ---- seg_hrnet3 head: low-resolution branches' share of last_layer[0] (head_gather.hip) ----
 struct GatherParams {

@@ -93,6 +93,7 @@ struct Tensor {
     int flat = 0;               // > 0: plain f32 scratch of `flat` floats per sample (no spatial extent)
     std::string tap;            // name for esahrnet_tap_read, "" if anonymous
     bool tlayout = false;       // head term in the transposed T layout (head_t.hip): row pitch head_t_xp(w)
+    bool f32 = false;           // plain f32 NHWC whatever the plan's format (the output of an out_f32 convolution)
     int alt = 0;                // 0: always; 1 / 2: only when the first / second generation head runs
     int def = -1, last = -1;    // op indices
     size_t off = 0;             // per-shape plan
@@ -261,6 +262,7 @@ struct Builder {
         if (jkey2 >= 0 && ((s.k == 3 && s.stride == 2) || s.k == 1)) o.jkey = jkey2;
         // ESAHRNET_TAP_ALL=1 (debugging): every convolution output becomes a named tap
         o.out = tensor(s.cout, s.level, tap.empty() && !out_f32 && getenv("ESAHRNET_TAP_ALL") ? "conv:" + s.name : tap);
+        c.tensors[o.out].f32 = out_f32;
         const int idx = (int)c.ops.size();
         c.tensors[o.out].def = idx;
         use(in, idx); use(res, idx);
@@ -307,7 +309,7 @@ struct Builder {
         const int a2 = aux(q + "sa.conv1.weight", 1, 2, 7, 7);
         const int level = c.tensors[x].level, Cp = c.tensors[x].Cp;
         const int partial = flat_tensor(POOL_SLABS * Cp * 2), cav = flat_tensor(Cp);
-        Tensor mt; mt.C = 2; mt.Cp = 2; mt.level = level;
+        Tensor mt; mt.C = 2; mt.Cp = 2; mt.level = level; mt.f32 = true;       // (f32 [N][H][W][2] in every format)
         c.tensors.push_back(mt);
         const int maps = (int)c.tensors.size() - 1;
         // inside an HRModule branch (jkey >= 0) the four CBAM launches take the next depth keys behind the block's two
@@ -603,7 +605,14 @@ int build_plan_ops(esahrnet_ctx& c) {
     const int spec_conv2 = B.spec("conv2", "bn2", sw, sw, 3, 2, 1, false, true);
     int x;
     int stem_raw = -1;
-    if (g.variant == 1) {   // seg_hrnet3.py:473-475: x0 = conv1(x0) is kept (pre-BN) for the CBAM skip
+    if (g.variant == 1 && c.bf) {   // bf16 mode: the raw conv1 as below; conv1 + bn1 + ReLU on the stem kernel, conv2 on the
+        c.fuse_big = false;         // stream kernel (as variant 0's bf16 plan: the fused stem kernel is built for SB only)
+        { Op o; o.kind = OP_STEMRAW; o.out = B.tensor(sw, 0, "stem_raw"); stem_raw = o.out;
+          o.aux[0] = B.aux("conv1.weight", sw, g.cin, 3, 3); B.push(o); }
+        Op o; o.kind = OP_STEM; o.out = B.tensor(sw, 0, "stem1");
+        B.push(o);
+        x = B.conv(spec_conv2, o.out, -1, true, "stem2");
+    } else if (g.variant == 1) {   // seg_hrnet3.py:473-475: x0 = conv1(x0) is kept (pre-BN) for the CBAM skip
         c.fuse_big = false;
         { Op o; o.kind = OP_STEMRAW; o.out = B.tensor(sw, 0, "stem_raw"); stem_raw = o.out;
           o.aux[0] = B.aux("conv1.weight", sw, g.cin, 3, 3); B.push(o); }
@@ -724,6 +733,8 @@ int build_plan_ops(esahrnet_ctx& c) {
         // 3x3 conv here), 3x3 480->480, 1x1 480->K, up x2 (align_corners=True), cat with CBAM(stem skip),
         // 3x3 (K+64)->K.  The second concat is laid out [skip | heat-maps] so that both slices start on
         // an 8-channel group; output_layer's input channels are permuted accordingly when packed.
+        // bf16 mode: the direct head below (no gather), and the output layer leaves its heat-maps in f32 (out_f32: the
+        // stream kernel's f32 epilogue), as variant 0's bf16 output layer does.
         const int l0 = B.spec("last_layer.0", "last_layer.1", tot, tot, 3, 1, 1, true, true);
         const int l3 = B.spec("last_layer.3", "last_layer.4", tot, K, 1, 1, 1, true, true);
         c.spec_final = B.spec("output_layer.0", "", K + sw, K, 3, 1, 0, true, false);
@@ -771,8 +782,8 @@ int build_plan_ops(esahrnet_ctx& c) {
                 B.push(o);
                 off += pre[b];
             }
-            if (pad32(tot) > ((tot + 7) & ~7)) {
-                Op o; o.kind = OP_ZERO; o.out = cat; o.terms[0] = cat; o.c0 = (tot + 7) & ~7; o.nchan = pad32(tot) - ((tot + 7) & ~7);
+            if (c.padc(tot) > ((tot + 7) & ~7)) {
+                Op o; o.kind = OP_ZERO; o.out = cat; o.terms[0] = cat; o.c0 = (tot + 7) & ~7; o.nchan = c.padc(tot) - ((tot + 7) & ~7);
                 B.push(o);
             }
             h0 = B.conv(l0, cat, -1, true, "head0");
@@ -793,11 +804,11 @@ int build_plan_ops(esahrnet_ctx& c) {
                     c.stemraw_partial = partial;
                 }
         { Op o; o.kind = OP_RESAMPLE; o.in = h3; o.out = cat2; o.terms[0] = cat2; o.c0 = sw; o.nchan = K; o.align = 1; B.push(o); }
-        if (pad32(sw + K) > sw + ((K + 7) & ~7)) {
-            Op o; o.kind = OP_ZERO; o.out = cat2; o.terms[0] = cat2; o.c0 = sw + ((K + 7) & ~7); o.nchan = pad32(sw + K) - o.c0;
+        if (c.padc(sw + K) > sw + ((K + 7) & ~7)) {
+            Op o; o.kind = OP_ZERO; o.out = cat2; o.terms[0] = cat2; o.c0 = sw + ((K + 7) & ~7); o.nchan = c.padc(sw + K) - o.c0;
             B.push(o);
         }
-        const int oc = B.conv(c.spec_final, cat2, -1, false, "out_sb");
+        const int oc = B.conv(c.spec_final, cat2, -1, false, "out_sb", 0, -1, true, c.bf);
         std::vector<int>& perm = c.dconvs[c.ops.back().dconv].perm;     // packed ci -> reference ci
         for (int i = 0; i < sw; ++i) perm.push_back(K + i);              // skip channels come second in the reference
         for (int i = 0; i < K; ++i) perm.push_back(i);
@@ -1049,7 +1060,7 @@ int plan_shape(esahrnet_ctx& c, int n, int h, int w) {
     size_t top = 0;
     auto bytes_of = [&](const Tensor& t) {
         const size_t wpix = t.tlayout ? (size_t)esa::head_t_xp(sp.lw[t.level]) : (size_t)sp.lw[t.level];
-        size_t b = t.flat ? (size_t)n * t.flat * 4 : (size_t)n * sp.lh[t.level] * wpix * t.Cp * c.eb();
+        size_t b = t.flat ? (size_t)n * t.flat * 4 : (size_t)n * sp.lh[t.level] * wpix * t.Cp * (t.f32 ? 4 : c.eb());
         return (b + 255) & ~(size_t)255;
     };
     auto alloc = [&](size_t len) {
@@ -1172,7 +1183,6 @@ int esahrnet_create(const esahrnet_cfg* cfg, int device, esahrnet_handle* out) {
     if (cfg->variant != 0 && cfg->variant != 1) return fail("variant=%d unsupported (0: seg_hrnet/2, 1: seg_hrnet3)", cfg->variant);
     if (cfg->precision < 0 || cfg->precision > 2)
         return fail("precision=%d unsupported (0: split-bf16 'bf16x3', 1: bf16, 2: fp32-grade 'bf16x6')", cfg->precision);
-    if (cfg->precision == 1 && cfg->variant != 0) return fail("precision 1 (bf16) is built for variant 0 only");
     if (cfg->variant == 1) {
         if (cfg->stem_width % 16) return fail("variant 1: stem_width must be a multiple of 16 (ChannelAttention ratio)");
         for (int b = 0; b < ESAHRNET_MAX_BRANCHES; ++b)
@@ -1393,7 +1403,7 @@ int esahrnet_commit(esahrnet_handle h) {
     for (const Op& o : h->ops)
         if (o.kind == OP_STEMRAW) {   // un-normalised conv1 in the stem kernel's [cout/8][cin][9][8] layout, zero bias
             const AuxSpec& a = h->aux[o.aux[0]];
-            const int cout = a.shape[0], cin = a.shape[1], coutp = pad32(cout);
+            const int cout = a.shape[0], cin = a.shape[1], coutp = h->padc(cout);
             std::vector<float> w((size_t)coutp * cin * 9, 0.f), b(coutp, 0.f);
             for (int co = 0; co < cout; ++co)
                 for (int ci = 0; ci < cin; ++ci)
@@ -1474,7 +1484,7 @@ int esahrnet_workspace_bytes(esahrnet_handle h, int n, int height, int width, si
 // arrangement, or a crop whose rows make more slabs than the partials tensor reserves)
 static int stem_pools(const esahrnet_ctx& c, int height, int width) {
     if (c.stemraw_partial < 0) return 0;
-    const int slabs = esa::stem_pool_slabs(c.cfg.cin, pad32(c.cfg.stem_width), height, width);
+    const int slabs = esa::stem_pool_slabs(c.cfg.cin, c.padc(c.cfg.stem_width), height, width);
     return slabs <= STEM_POOL_SLABS_MAX ? slabs : 0;
 }
 
@@ -1514,7 +1524,7 @@ static esa::CbamJob cbam_job(const esahrnet_ctx& c, const Op& o, const ShapePlan
             q.ap.x = T(o.in); q.ap.res = o.res >= 0 ? T(o.res) : nullptr;
             q.ap.ca = reinterpret_cast<const float*>(T(o.terms[1])); q.ap.maps = reinterpret_cast<const float*>(T(o.terms[2]));
             q.ap.w_sa = c.aux[o.aux[2]].dev; q.ap.y = T(o.out);
-            q.ap.y_pix_bytes = to.Cp * 4; q.ap.y_c0 = o.c0; q.ap.relu = o.relu;
+            q.ap.y_pix_bytes = to.Cp * c.eb(); q.ap.y_c0 = o.c0; q.ap.relu = o.relu;
         }
     }
     return q;
@@ -1554,7 +1564,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
     auto tbytes = [&](int t) {
         const Tensor& x = c.tensors[t];
         const double wpix = x.tlayout ? (double)esa::head_t_xp(lw[x.level]) : (double)lw[x.level];
-        return x.flat ? (double)n * x.flat * 4.0 : (double)n * lh[x.level] * wpix * x.Cp * (double)c.eb();
+        return x.flat ? (double)n * x.flat * 4.0 : (double)n * lh[x.level] * wpix * x.Cp * (double)(x.f32 ? 4 : c.eb());
     };
     auto plain = [&](const char* kernel) {      // the seg_hrnet3 plumbing launches: what they read and write
         describe(desc, kernel, "seg_hrnet3");
@@ -1631,7 +1641,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             esa::ResampleParams p{};
             p.x = T(o.in); p.y = T(o.out); p.N = n;
             p.h = lh[ti.level]; p.w = lw[ti.level]; p.H = lh[to.level]; p.W = lw[to.level];
-            p.C = o.nchan; p.Cp_src = ti.Cp; p.y_pix_bytes = to.Cp * 4; p.y_c0 = o.c0; p.align = o.align; p.fmt = c.fmt;
+            p.C = o.nchan; p.Cp_src = ti.Cp; p.y_pix_bytes = to.Cp * c.eb(); p.y_c0 = o.c0; p.align = o.align; p.fmt = c.fmt;
             if (desc) plain("resample_slice");
             else rc = esa::launch_resample_slice(p, stream);
             break;
@@ -1654,12 +1664,13 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
         case OP_ZERO: {
             const Tensor& to = c.tensors[o.out];
             if (desc) plain("zero_slice");
-            else rc = esa::launch_zero_slice(T(o.out), (long long)n * lh[to.level] * lw[to.level], to.Cp * 4, o.c0, o.nchan, stream);
+            else rc = esa::launch_zero_slice(T(o.out), (long long)n * lh[to.level] * lw[to.level], to.Cp * c.eb(), o.c0, o.nchan, stream, c.fmt);
             break;
         }
         case OP_TONCHW: {
-            if (desc) plain("sb_to_nchw");
-            else rc = esa::launch_fmt_to_nchw(c.fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
+            const bool f32 = c.tensors[o.in].f32;       // (bf16 mode: the output layer's f32 heat-maps)
+            if (desc) plain(f32 ? "f32_to_nchw" : "sb_to_nchw");
+            else rc = esa::launch_fmt_to_nchw(f32 ? esa::FMT_F32 : c.fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
                                               static_cast<float*>(b.heat), stream);
             break;
         }
@@ -2093,7 +2104,7 @@ int esahrnet_tap_read(esahrnet_handle h, const char* name, int n, int height, in
     if (plan_shape(*h, n, height, width)) return 1;
     if (t->alt != 0 && t->alt != (h->sp.head2 ? 2 : 1))
         return fail("tap_read: '%s' belongs to the head alternative that does not run at this shape", name);
-    const int rc = esa::launch_fmt_to_nchw(h->fmt,
+    const int rc = esa::launch_fmt_to_nchw(t->f32 ? esa::FMT_F32 : h->fmt,
         static_cast<const char*>(ws_dev) + t->off, n, t->C, h->sp.lh[t->level], h->sp.lw[t->level], t->Cp,
         static_cast<float*>(out_dev), static_cast<hipStream_t>(stream));
     if (rc) return fail("tap_read: %s", hipGetErrorString((hipError_t)rc));
@@ -2183,6 +2194,53 @@ int esahrnet_op_fuse_ex(const void* const* xs_dev, const int* hs, const int* ws,
     cleanup();
     if (rc) return fail("op_fuse: launch failed: %s", hipGetErrorString((hipError_t)rc));
     if (se != hipSuccess) return fail("op_fuse: %s", hipGetErrorString(se));
+    return 0;
+}
+
+int esahrnet_op_cbam(const void* x_dev, const void* res_dev, int n, int c, int height, int width, const float* w_fc0,
+                     const float* w_fc2, const float* w_sa, int relu, void* y_dev, int cy, int c0, int fused, int precision,
+                     esahrnet_stream stream_) {
+    if (!x_dev || !w_fc0 || !w_fc2 || !w_sa || !y_dev || n <= 0 || height <= 0 || width <= 0) return fail("op_cbam: bad argument");
+    if (precision < 0 || precision > 2) return fail("op_cbam: precision %d", precision);
+    if (c < 16 || (c & 7)) return fail("op_cbam: c=%d (a multiple of 8, at least 16: ChannelAttention's ratio)", c);
+    const bool bf = precision == 1;
+    const int fmt = bf ? esa::FMT_BF : precision == 2 ? esa::FMT_F32 : esa::FMT_SB;
+    const int eb = bf ? 2 : 4;
+    const int cp = bf ? pad64(c) : pad32(c), cyp = bf ? pad64(cy) : pad32(cy);
+    if (c0 < 0 || (c0 & 7) || c0 + cp > cyp) return fail("op_cbam: slice [%d, %d) outside the %d channels of y", c0, c0 + cp, cyp);
+    if (fused && !esa::cbam_spatial_supported(cp)) return fail("op_cbam: cbam_spatial does not serve %d channels", cp);
+    const int cr = c / 16, hw = height * width, P = std::min(Builder::POOL_SLABS, hw);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const std::vector<float> h0(w_fc0, w_fc0 + (size_t)cr * c), h2(w_fc2, w_fc2 + (size_t)c * cr), hs(w_sa, w_sa + 98);
+    void *xs = nullptr, *rs = nullptr, *ys = nullptr, *part = nullptr, *ca = nullptr, *maps = nullptr, *w0 = nullptr,
+         *w2 = nullptr, *wsa = nullptr;
+    auto cleanup = [&]() { for (void* p : {xs, rs, ys, part, ca, maps, w0, w2, wsa}) if (p) (void)hipFree(p); };
+    if (upload(h0, &w0) || upload(h2, &w2) || upload(hs, &wsa)) { cleanup(); return 1; }
+    const size_t npix = (size_t)n * hw;
+    if (hipMalloc(&xs, npix * cp * eb) != hipSuccess || (res_dev && hipMalloc(&rs, npix * cp * eb) != hipSuccess) ||
+        hipMalloc(&ys, npix * cyp * eb) != hipSuccess || hipMalloc(&part, (size_t)n * P * cp * 2 * sizeof(float)) != hipSuccess ||
+        hipMalloc(&ca, (size_t)n * cp * sizeof(float)) != hipSuccess || hipMalloc(&maps, npix * 2 * sizeof(float)) != hipSuccess) {
+        cleanup();
+        return fail("op_cbam: hipMalloc failed");
+    }
+    int rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(x_dev), n, c, height, width, static_cast<char*>(xs), cp, stream);
+    if (!rc && res_dev) rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(res_dev), n, c, height, width, static_cast<char*>(rs), cp, stream);
+    if (!rc) rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(y_dev), n, cy, height, width, static_cast<char*>(ys), cyp, stream);
+    if (!rc) rc = esa::launch_pool_partial(static_cast<const char*>(xs), static_cast<float*>(part), n, hw, cp, P, stream, fmt);
+    if (!rc) rc = esa::launch_ca_mlp(static_cast<const float*>(part), static_cast<const float*>(w0), static_cast<const float*>(w2),
+                                     static_cast<float*>(ca), n, hw, c, cp, cr, P, stream);
+    esa::CbamApplyParams ap{};
+    ap.x = static_cast<const char*>(xs); ap.res = static_cast<const char*>(rs); ap.ca = static_cast<const float*>(ca);
+    ap.maps = static_cast<const float*>(maps); ap.w_sa = static_cast<const float*>(wsa); ap.y = static_cast<char*>(ys);
+    ap.N = n; ap.H = height; ap.W = width; ap.Cp = cp; ap.y_pix_bytes = cyp * eb; ap.y_c0 = c0; ap.relu = relu; ap.C = c; ap.fmt = fmt;
+    if (!rc && fused) rc = esa::launch_cbam_spatial(ap, stream);
+    if (!rc && !fused) rc = esa::launch_cbam_maps(ap.x, ap.ca, static_cast<float*>(maps), n, hw, c, cp, stream, fmt);
+    if (!rc && !fused) rc = esa::launch_cbam_apply(ap, stream);
+    if (!rc) rc = esa::launch_fmt_to_nchw(fmt, static_cast<const char*>(ys), n, cy, height, width, cyp, static_cast<float*>(y_dev), stream);
+    hipError_t se = hipStreamSynchronize(stream);
+    cleanup();
+    if (rc) return fail("op_cbam: launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (se != hipSuccess) return fail("op_cbam: %s", hipGetErrorString(se));
     return 0;
 }
 

@@ -80,9 +80,10 @@ constexpr int STEM_PX = 8;
 // POOL (seg_hrnet3's raw skip tensor, whose CBAM needs the per-channel mean and maximum): grid (row pieces, n * H), and the
 // block also reduces its 8 x (256 / G) pixels per channel into slab `y * gridDim.x + blockIdx.x` of `pool` — the layout
 // pool_partial_kernel writes (cbam.hip), so that kernel's 537 MB read of the tensor just written is not needed.
-template <bool POOL>
-__global__ __launch_bounds__(256) void stem1_kernel(StemParams p, int xgroups, long long total, float* pool) {
-    __shared__ float psum[POOL ? 256 * 8 : 1], pmax[POOL ? 256 * 8 : 1];
+// BFQ (bf16 mode, stem1_pool_bf_kernel): the outputs are rounded to bf16 first, so that the partials are those of the
+// values the BF tensor holds — what pool_partial would compute from it.
+template <bool POOL, bool BFQ>
+__device__ __forceinline__ void stem1_body(const StemParams& p, int xgroups, long long total, float* pool, float* psum, float* pmax) {
     const int G = p.cout >> 3;
     int c8, xg, y, n;
     bool live = true;
@@ -142,6 +143,7 @@ __global__ __launch_bounds__(256) void stem1_kernel(StemParams p, int xgroups, l
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc[i] = relu1(acc[i]);
         }
+        if (BFQ) unpack8_bf16(pack8_bf16(acc), acc);
         if (x >= p.W || !live) continue;
         if (POOL) {
 #pragma unroll
@@ -175,6 +177,15 @@ __global__ __launch_bounds__(256) void stem1_kernel(StemParams p, int xgroups, l
         }
     }
 }
+template <bool POOL>
+__global__ __launch_bounds__(256) void stem1_kernel(StemParams p, int xgroups, long long total, float* pool) {
+    __shared__ float psum[POOL ? 256 * 8 : 1], pmax[POOL ? 256 * 8 : 1];
+    stem1_body<POOL, false>(p, xgroups, total, pool, psum, pmax);
+}
+__global__ __launch_bounds__(256) void stem1_pool_bf_kernel(StemParams p, int xgroups, float* pool) {
+    __shared__ float psum[256 * 8], pmax[256 * 8];
+    stem1_body<true, true>(p, xgroups, 0LL, pool, psum, pmax);
+}
 
 }  // namespace
 
@@ -188,9 +199,14 @@ int stem_pool_slabs(int cin, int cout, int H, int W) {
 // conv1 as launch_stem computes it + per-slab (sum, max) of every channel into pool[N][slabs][cout][2]
 int launch_stem_pool(const StemParams& p, float* pool, hipStream_t stream) {
     const int slabs = stem_pool_slabs(p.cin, p.cout, p.H, p.W);
-    if (!slabs || !pool || (p.fmt != FMT_SB && p.fmt != FMT_F32) || (long long)p.N * p.H > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    if (!slabs || !pool || (p.fmt != FMT_SB && p.fmt != FMT_F32 && p.fmt != FMT_BF) || (long long)p.N * p.H > 0x7fffffffLL)
+        return (int)hipErrorInvalidValue;
     const int xgroups = (p.W + STEM_PX - 1) / STEM_PX;
     const dim3 grid((unsigned)((xgroups * (p.cout >> 3) + 255) / 256), (unsigned)(p.N * p.H));
+    if (p.fmt == FMT_BF) {
+        hipLaunchKernelGGL(stem1_pool_bf_kernel, grid, dim3(256), 0, stream, p, xgroups, pool);
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(stem1_kernel<true>, grid, dim3(256), 0, stream, p, xgroups, 0LL, pool);
     return (int)hipGetLastError();
 }

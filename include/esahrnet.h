@@ -34,7 +34,8 @@ extern "C" {
 #endif
 
 #define ESAHRNET_MAX_BRANCHES 4
-#define ESAHRNET_ABI_VERSION 5      /* 5: esahrnet_cfg.precision 2 (fp32-grade bf16x6) */
+#define ESAHRNET_ABI_VERSION 6      /* 5: esahrnet_cfg.precision 2 (fp32-grade bf16x6); 6: precision 1 for variant 1,
+                                       esahrnet_op_cbam */
 
 typedef struct esahrnet_ctx* esahrnet_handle;
 typedef void* esahrnet_stream; /* hipStream_t */
@@ -60,7 +61,9 @@ typedef struct esahrnet_cfg {
                                        accumulate: heatmap L_inf ~1e-5 of the heat-map scale; opt-in fast mode, NOT fp32;
                                     1: bf16 activations and weights stored ONCE (half the bytes, one MFMA per
                                        product), f32 accumulate, f32 folded-BN bias epilogue — configs[3]
-                                       (heatmap L_inf ~1e-2); variant 0 only                                   */
+                                       (heatmap L_inf ~1e-2); both variants (variant 1: CBAM statistics, MLP,
+                                       maps and sigmoids in f32 from the stored bf16 values, its output rounded
+                                       once; the heat-maps leave the output layer in f32)                      */
 } esahrnet_cfg;
 
 /* A parameter tensor that is not a convolution of the main graph (variant 1: the CBAM weights). */
@@ -202,6 +205,16 @@ int esahrnet_op_conv_ex(const void* x_dev, int n, int cin, int height, int width
 int esahrnet_op_fuse_ex(const void* const* xs_dev, const int* hs, const int* ws, int nterms,
                         int n, int c, int height, int width, int relu, void* y_dev, int precision,
                         esahrnet_stream stream);
+/* One CBAM of seg_hrnet3 (ChannelAttention + SpatialAttention, models/seg_hrnet3.py:32-61, 90-91) in the format of `precision`:
+ * y[:, c0 : c0 + C'] = [relu]( sa(ca*x) * ca*x [+ res] ), C' = c padded to the mode's channel multiple (32; bf16: 64), the
+ * padding written as zeros.  x_dev / res_dev: f32 NCHW [n][c][height][width] (res_dev may be NULL); w_fc0 [c/16][c],
+ * w_fc2 [c][c/16], w_sa [2][7][7]: host f32.  y_dev: f32 NCHW [n][cy][height][width], read (converted to the internal
+ * format) and written back whole: channels outside the slice come back as they went in (exactly, if the format holds them
+ * exactly).  c0 a multiple of 8, c0 + C' <= cy padded.  fused: 1 = maps and attention in one pass (cbam_spatial; c padded / 8
+ * must be a power of two <= 32), 0 = cbam_maps + cbam_apply. */
+int esahrnet_op_cbam(const void* x_dev, const void* res_dev, int n, int c, int height, int width, const float* w_fc0,
+                     const float* w_fc2, const float* w_sa, int relu, void* y_dev, int cy, int c0, int fused, int precision,
+                     esahrnet_stream stream);
 
 /* ---- test hooks ------------------------------------------------------------------------------------ */
 /* Launch state is kept per DEVICE (dynamic-LDS limits raised per kernel and device, CU counts), never in
