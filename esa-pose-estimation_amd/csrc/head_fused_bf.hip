@@ -378,8 +378,7 @@ bool head_fused_bf_supported(int H, int W, const int th[3], const int tw[3], int
 int launch_head_bf(const HeadParams& p, hipStream_t stream) {
     if ((p.Ctp & 31) || (p.C3p & 3)) return (int)hipErrorInvalidValue;
     const int m3 = p.K <= 16 ? 1 : 2;
-    const bool valu = getenv("ESAHRNET_BF_HEAD_VALU") != nullptr;       // the first-generation (VALU interpolation) form (A/B, tests)
-    if (valu) {
+    if (p.valu) {       // the first-generation (VALU interpolation) form (A/B, tests)
         if (p.C0p == 64 && m3 == 1) return launch_head_bf_t<1, 1, false>(p, stream);
         if (p.C0p == 64 && m3 == 2) return launch_head_bf_t<1, 2, false>(p, stream);
         if (p.C0p == 128 && m3 == 1) return launch_head_bf_t<2, 1, false>(p, stream);

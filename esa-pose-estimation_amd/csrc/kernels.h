@@ -182,6 +182,7 @@ struct HeadParams {
     int N, H, W;
     int th[3], tw[3];
     int C0p, Ctp, C3p, K;
+    bool valu;          // launch_head_bf: the first-generation form (VALU interpolation) instead of the matrix-core one
 };
 int launch_head(const HeadParams& p, hipStream_t stream);
 bool head_fused_supported(int H, int W, const int th[3], const int tw[3], int C0p, int K);

@@ -152,6 +152,58 @@ struct ShapePlan {
     std::vector<char> job_on;   // per JobGroup: evaluated as one launch at this shape
 };
 
+enum StemForm { STEM_SEPARATE, STEM_FUSED, STEM_FUSED_X6 };
+enum HeadForm { HEAD_UNFUSED, HEAD_SB, HEAD_BF, HEAD_X6 };
+
+// The plan switches and what follows from them and the configuration.  plan_options() fills it once, in
+// esahrnet_create, and nothing writes it afterwards: a handle's plan and launches depend on the environment at its creation.
+struct PlanOptions {
+    // ESAHRNET_<NAME>, on unless unset, empty or "0"
+    bool unfused, head_v1, final_valu, no_multihead, no_jobs, no_bblock, no_cbam_jobs, cbam_unfused, stem_pool_separate,
+         head3_direct, head3_cout32, bf_unfused_head, bf_head_valu, x6_unfused_head, x6_unfused_stem, tap_all;
+    int nlanes;                 // 4 if ESAHRNET_STREAMS > 1 (the wave executor), else 1: everything on the caller's stream
+    int fmt;                    // tensor format: FMT_SB (precision 0), FMT_BF (1: single bf16), FMT_F32 (2: bf16x6 arithmetic)
+    StemForm stem;              // conv1 + conv2: stem_kernel + stride-2 convolution, stem_fused, or stem_x6_kernel
+    bool fused_block;           // a 32-channel BasicBlock outside the job groups is one bblock32 launch
+    HeadForm head;              // seg_hrnet / seg_hrnet2: the fused head kernel the plan carries (seg_hrnet3 has its own head)
+    bool head2;                 // the second head alternative (head_fused2, head_fused_bf, head_x6) may be chosen per shape
+    bool final_mfma;            // seg_hrnet / seg_hrnet2: output layer on the matrix cores (final_mfma_kernel)
+};
+
+PlanOptions plan_options(const esahrnet_cfg& g) {
+    auto on = [](const char* name) { const char* e = getenv(name); return e && e[0] && strcmp(e, "0") != 0; };
+    PlanOptions o;
+    o.unfused = on("ESAHRNET_UNFUSED"); o.head_v1 = on("ESAHRNET_HEAD_V1"); o.final_valu = on("ESAHRNET_FINAL_VALU");
+    o.no_multihead = on("ESAHRNET_NO_MULTIHEAD"); o.no_jobs = on("ESAHRNET_NO_JOBS"); o.no_bblock = on("ESAHRNET_NO_BBLOCK");
+    o.no_cbam_jobs = on("ESAHRNET_NO_CBAM_JOBS"); o.cbam_unfused = on("ESAHRNET_CBAM_UNFUSED");
+    o.stem_pool_separate = on("ESAHRNET_STEM_POOL_SEPARATE"); o.head3_direct = on("ESAHRNET_HEAD3_DIRECT");
+    o.head3_cout32 = on("ESAHRNET_HEAD3_COUT32"); o.bf_unfused_head = on("ESAHRNET_BF_UNFUSED_HEAD");
+    o.bf_head_valu = on("ESAHRNET_BF_HEAD_VALU"); o.x6_unfused_head = on("ESAHRNET_X6_UNFUSED_HEAD");
+    o.x6_unfused_stem = on("ESAHRNET_X6_UNFUSED_STEM"); o.tap_all = on("ESAHRNET_TAP_ALL");
+    const char* streams = getenv("ESAHRNET_STREAMS");
+    o.nlanes = streams && atoi(streams) > 1 ? 4 : 1;
+    o.fmt = g.precision == 1 ? esa::FMT_BF : g.precision == 2 ? esa::FMT_F32 : esa::FMT_SB;
+    const bool sb = o.fmt == esa::FMT_SB, v0 = g.variant == 0;
+    // the fused stem kernels: stem_fused serves every (cin, stem width) in the split format, stem_x6_kernel one; none in bf16
+    const bool x6_stem = esa::stem_fused_x6_supported(g.cin, pad32(g.stem_width), pad32(g.stem_width)) && g.stem_width == 64;
+    o.stem = sb && (!v0 || !o.unfused) ? STEM_FUSED
+           : o.fmt == esa::FMT_F32 && x6_stem && !o.x6_unfused_stem ? STEM_FUSED_X6 : STEM_SEPARATE;
+    // bblock32 is built for the split format, and seg_hrnet3's block has a CBAM inside
+    o.fused_block = sb && v0 && !o.unfused && !o.no_bblock;
+    int nb4 = 0;                // branches of stage 4
+    while (nb4 < ESAHRNET_MAX_BRANCHES && g.blocks[3][nb4] > 0) ++nb4;
+    const int c0 = pad32(g.widths[0]);
+    o.head = !v0 || nb4 != 4 ? HEAD_UNFUSED
+           : sb ? (!o.unfused && (c0 == 32 || c0 == 64) ? HEAD_SB : HEAD_UNFUSED)
+           : o.fmt == esa::FMT_BF ? (!o.bf_unfused_head && (pad64(g.widths[0]) == 64 || pad64(g.widths[0]) == 128) ? HEAD_BF : HEAD_UNFUSED)
+           : !o.x6_unfused_head && (c0 == 32 || c0 == 64) ? HEAD_X6 : HEAD_UNFUSED;
+    // head_fused2 needs head_t's channel counts on branches 2 and 3 and 64 or 96 on branch 1
+    o.head2 = !o.head_v1 && (o.head != HEAD_SB || ((pad32(g.widths[1]) == 64 || pad32(g.widths[1]) == 96) &&
+                                                   esa::head_t_supported(pad32(g.widths[2])) && esa::head_t_supported(pad32(g.widths[3]))));
+    o.final_mfma = v0 && o.fmt != esa::FMT_F32 && !o.final_valu && esa::final_mfma_supported(g.num_keypoints, g.cin);
+    return o;
+}
+
 }  // namespace
 
 int esa::set_error(const char* fmt, ...) {
@@ -180,23 +232,26 @@ struct esahrnet_ctx {
     float *head_b0 = nullptr, *head_b3 = nullptr;
     bool committed = false;
     bool keep = false;
-    bool bf = false;            // cfg.precision == 1: tensors are single bf16 (sb.h "BF"), channels padded to 64
-    int fmt = esa::FMT_SB;      // tensor format of the plan: FMT_SB (precision 0), FMT_BF (1), FMT_F32 (2: bf16x6 arithmetic)
-    bool x6() const { return fmt == esa::FMT_F32; }
-    int padc(int ch) const { return bf ? pad64(ch) : pad32(ch); }
-    int eb() const { return bf ? 2 : 4; }       // bytes per stored channel
+    PlanOptions opt;
+    bool bf() const { return opt.fmt == esa::FMT_BF; }       // tensors are single bf16 (sb.h "BF"), channels padded to 64
+    bool x6() const { return opt.fmt == esa::FMT_F32; }
+    int padc(int ch) const { return bf() ? pad64(ch) : pad32(ch); }
+    int eb() const { return bf() ? 2 : 4; }     // bytes per stored channel
     size_t wbytes(int coutp, int cinp, int k) const {
-        return bf ? esa::packed_weight_bytes_bf(coutp, cinp, k) : x6() ? esa::packed_weight_bytes_x6(coutp, cinp, k)
-                                                                       : esa::packed_weight_bytes(coutp, cinp, k);
+        return bf() ? esa::packed_weight_bytes_bf(coutp, cinp, k) : x6() ? esa::packed_weight_bytes_x6(coutp, cinp, k)
+                                                                         : esa::packed_weight_bytes(coutp, cinp, k);
     }
-    bool fuse_big = true;       // fused stem + fused head (ESAHRNET_UNFUSED=1 selects the op-by-op plan)
-    bool head2_enabled = true;  // ESAHRNET_HEAD_V1=1 keeps the first-generation fused head for every shape
-    bool x6_stemf = false;      // fp32-grade mode: conv1 inside conv2's staging (stem_x6_kernel), cin == 1
-    bool cbam_unfused = false;  // ESAHRNET_CBAM_UNFUSED=1: cbam_maps + cbam_apply instead of cbam_spatial
+    // w [cout][cin][k][k] packed for the plan's format (wbytes(coutp, cinp, k) bytes)
+    std::vector<char> pack(const float* w, int cout, int cin, int k, int coutp, int cinp) const {
+        std::vector<char> p(wbytes(coutp, cinp, k), 0);
+        if (bf()) esa::pack_conv_weights_bf(w, cout, cin, k, coutp, cinp, p.data());
+        else if (x6()) esa::pack_conv_weights_x6(w, cout, cin, k, coutp, cinp, p.data());
+        else esa::pack_conv_weights(w, cout, cin, k, coutp, cinp, p.data());
+        return p;
+    }
     int head2_op = -1;          // index of the OP_HEAD2 op, -1 if the plan has none
     // wave executor (schedule_waves): the launches of a wave that do not depend on each other run on up to four lanes
-    // (the caller's stream + three side streams), fork/join through the caller's stream at every wave boundary
-    int nlanes = 1;             // 1: everything on the caller's stream;  4: waves (ESAHRNET_STREAMS)
+    // (the caller's stream + three side streams), fork/join through the caller's stream at every wave boundary (opt.nlanes)
     int nwaves = 1;
     std::vector<int> wave_last;                       // per wave: index of its last op
     std::vector<unsigned char> wave_mask;             // per wave: bit l set = lane l has work
@@ -261,7 +316,7 @@ struct Builder {
         if (jkey >= 0 && s.k == 3 && s.stride == 1) o.jkey = jkey++;
         if (jkey2 >= 0 && ((s.k == 3 && s.stride == 2) || s.k == 1)) o.jkey = jkey2;
         // ESAHRNET_TAP_ALL=1 (debugging): every convolution output becomes a named tap
-        o.out = tensor(s.cout, s.level, tap.empty() && !out_f32 && getenv("ESAHRNET_TAP_ALL") ? "conv:" + s.name : tap);
+        o.out = tensor(s.cout, s.level, tap.empty() && !out_f32 && c.opt.tap_all ? "conv:" + s.name : tap);
         c.tensors[o.out].f32 = out_f32;
         const int idx = (int)c.ops.size();
         c.tensors[o.out].def = idx;
@@ -344,8 +399,8 @@ struct Builder {
         const int c2 = spec(p + ".conv2", p + ".bn2", cout, cout, 3, 1, level, false, true);
         // whole block in one kernel (bblock32.hip) — for layer1; inside the HRModules the block's two convolutions join the
         // same-depth convolutions of the other branches in one launch instead (group_jobs; ESAHRNET_NO_JOBS=1: fused block)
-        const bool in_job = jkey >= 0 && !getenv("ESAHRNET_NO_JOBS");
-        if (c.fuse_big && cin == cout && pad32(cin) == 32 && !getenv("ESAHRNET_NO_BBLOCK") && !in_job) {
+        const bool in_job = jkey >= 0 && !c.opt.no_jobs;
+        if (c.opt.fused_block && cin == cout && pad32(cin) == 32 && !in_job) {
             Op o;
             o.kind = OP_BLOCK; o.in = x; o.relu = true;
             for (int k = 0; k < 2; ++k) {
@@ -373,7 +428,7 @@ struct Builder {
 // Post-pass over the op list: find the stride-2 3x3 convolutions that share their input and make each such group
 // consecutive (moving a member EARLIER is always legal: its only input is defined before the group's first member).
 void group_multihead(esahrnet_ctx& c) {
-    if (getenv("ESAHRNET_NO_MULTIHEAD") || c.fmt != esa::FMT_SB) return;
+    if (c.opt.no_multihead || c.opt.fmt != esa::FMT_SB) return;
     auto eligible = [&](const Op& o) {
         if (o.kind != OP_CONV || o.res >= 0 || o.alt != 0 || o.multi >= 0) return false;
         const DevConv& d = c.dconvs[o.dconv];
@@ -432,18 +487,18 @@ void group_multihead(esahrnet_ctx& c) {
 // branch by branch; here the convolutions of a module are put in depth-major order (stable, so every branch keeps its own
 // order) and the same-depth ones of up to three branches become a JobGroup.
 void group_jobs(esahrnet_ctx& c) {
-    if (getenv("ESAHRNET_NO_JOBS")) return;
+    if (c.opt.no_jobs) return;
     std::vector<Op> ops = c.ops;
     auto eligible = [&](const Op& o) {
         // the CBAM launches of a depth (seg_hrnet3): same kind on every branch, one launch (cbam.hip: cbam_jobs_kernel)
         if ((o.kind == OP_POOL || o.kind == OP_MLP || o.kind == OP_MAPS || o.kind == OP_APPLY) && o.jkey >= 0)
-            return !getenv("ESAHRNET_NO_CBAM_JOBS");
+            return !c.opt.no_cbam_jobs;
         if (o.kind != OP_CONV || o.jkey < 0 || o.alt != 0 || o.multi >= 0) return false;
         const DevConv& d = c.dconvs[o.dconv];
         const ConvSpec& s = c.specs[d.spec];
-        if (s.k == 1) return !c.bf && o.res < 0 && !d.out_f32 && d.c0 == 0 && d.c1 == s.cin && d.perm.empty() && d.use_bias;
+        if (s.k == 1) return !c.bf() && o.res < 0 && !d.out_f32 && d.c0 == 0 && d.c1 == s.cin && d.perm.empty() && d.use_bias;
         return s.k == 3 && !d.out_f32 && d.c0 == 0 && d.c1 == s.cin && d.perm.empty() && d.use_bias &&
-               d.coutp % (c.bf ? 64 : 32) == 0;
+               d.coutp % (c.bf() ? 64 : 32) == 0;
     };
     size_t i = 0;
     while (i < ops.size()) {
@@ -508,7 +563,7 @@ void schedule_waves(esahrnet_ctx& c) {
     const size_t nops = c.ops.size();
     for (Op& o : c.ops) { o.lane = 0; o.wave = 0; o.wait0 = -1; o.wait_entry = false; o.record = false; o.join = 0; }
     c.nwaves = 1;
-    if (c.nlanes > 1) {
+    if (c.opt.nlanes > 1) {
         std::vector<std::vector<int>> readers(c.tensors.size()), writers(c.tensors.size());
         std::vector<int> unit_end(nops, 0);       // op -> last op of its launch unit
         int wave = 0, wave_start = 0, tail0 = -1;
@@ -605,40 +660,22 @@ int build_plan_ops(esahrnet_ctx& c) {
     const int spec_conv2 = B.spec("conv2", "bn2", sw, sw, 3, 2, 1, false, true);
     int x;
     int stem_raw = -1;
-    if (g.variant == 1 && c.bf) {   // bf16 mode: the raw conv1 as below; conv1 + bn1 + ReLU on the stem kernel, conv2 on the
-        c.fuse_big = false;         // stream kernel (as variant 0's bf16 plan: the fused stem kernel is built for SB only)
-        { Op o; o.kind = OP_STEMRAW; o.out = B.tensor(sw, 0, "stem_raw"); stem_raw = o.out;
-          o.aux[0] = B.aux("conv1.weight", sw, g.cin, 3, 3); B.push(o); }
+    if (g.variant == 1) {   // seg_hrnet3.py:473-475: x0 = conv1(x0) is kept (pre-BN) for the CBAM skip: conv1 a second time
+        Op o; o.kind = OP_STEMRAW; o.out = B.tensor(sw, 0, "stem_raw"); stem_raw = o.out;
+        o.aux[0] = B.aux("conv1.weight", sw, g.cin, 3, 3); B.push(o);
+    }
+    if (c.opt.stem != STEM_SEPARATE) {  // conv1 + bn1 + ReLU recomputed per tile inside the conv2 kernel (stem_fused.hip / conv_x6.hip)
+        DevConv d;
+        d.spec = spec_conv2; d.c0 = 0; d.c1 = sw; d.use_bias = true;
+        d.cinp = pad32(sw); d.coutp = pad32(sw);
+        c.dconvs.push_back(d);
+        Op o; o.kind = OP_STEMF; o.dconv = (int)c.dconvs.size() - 1; o.out = B.tensor(sw, 1, "stem2");
+        B.push(o);
+        x = o.out;
+    } else {                // conv1 + bn1 + ReLU on the stem kernel, conv2 on the stream kernel
         Op o; o.kind = OP_STEM; o.out = B.tensor(sw, 0, "stem1");
         B.push(o);
         x = B.conv(spec_conv2, o.out, -1, true, "stem2");
-    } else if (g.variant == 1) {   // seg_hrnet3.py:473-475: x0 = conv1(x0) is kept (pre-BN) for the CBAM skip
-        c.fuse_big = false;
-        { Op o; o.kind = OP_STEMRAW; o.out = B.tensor(sw, 0, "stem_raw"); stem_raw = o.out;
-          o.aux[0] = B.aux("conv1.weight", sw, g.cin, 3, 3); B.push(o); }
-        // bn1 + ReLU + conv2 + bn2 + ReLU: the fused stem kernel (conv1 is evaluated a second time inside it,
-        // with bn1 folded; the raw copy above exists only for the skip)
-        DevConv d;
-        d.spec = spec_conv2; d.c0 = 0; d.c1 = sw; d.use_bias = true;
-        d.cinp = pad32(sw); d.coutp = pad32(sw);
-        c.dconvs.push_back(d);
-        Op o; o.kind = OP_STEMF; o.dconv = (int)c.dconvs.size() - 1; o.out = B.tensor(sw, 1, "stem2");
-        B.push(o);
-        x = o.out;
-    } else if (c.fuse_big || c.x6_stemf) {       // conv1 recomputed per tile inside the conv2 kernel (stem_fused.hip / conv_x6.hip)
-        DevConv d;
-        d.spec = spec_conv2; d.c0 = 0; d.c1 = sw; d.use_bias = true;
-        d.cinp = pad32(sw); d.coutp = pad32(sw);
-        c.dconvs.push_back(d);
-        Op o; o.kind = OP_STEMF; o.dconv = (int)c.dconvs.size() - 1; o.out = B.tensor(sw, 1, "stem2");
-        c.tensors[o.out].def = 0;
-        c.ops.push_back(o);
-        x = o.out;
-    } else {
-        Op o; o.kind = OP_STEM; o.out = B.tensor(sw, 0, "stem1");
-        c.tensors[o.out].def = 0;
-        c.ops.push_back(o);
-        x = B.conv(spec_conv2, c.ops[0].out, -1, true, "stem2");
     }
     // ---- layer1 (:277, :432) ----
     int cin = sw;
@@ -739,7 +776,7 @@ int build_plan_ops(esahrnet_ctx& c) {
         const int l3 = B.spec("last_layer.3", "last_layer.4", tot, K, 1, 1, 1, true, true);
         c.spec_final = B.spec("output_layer.0", "", K + sw, K, 3, 1, 0, true, false);
         int h0, wide_h0 = 0;
-        if (ys.size() == 4 && !c.bf && !getenv("ESAHRNET_HEAD3_DIRECT")) {
+        if (ys.size() == 4 && !c.bf() && !c.opt.head3_direct) {
             // last_layer[0] by linearity (head_gather.hip): branches 2, 3 as nine 1x1 products on their own grids + a gather,
             // branch 0 and the up-sampled branch 1 as a direct 3x3 that takes the gather's result as its residual
             const int cd = pre[0] + pre[1];
@@ -767,7 +804,7 @@ int build_plan_ops(esahrnet_ctx& c) {
             // 64-cout workgroup slices for the direct convolution: the stream kernel stages an input tile once per 64 instead of
             // once per 32 couts (480 = 7.5 x 64: the output, its residual and the reader's input are padded to 512 channels,
             // the padding is exact zeros end to end: zero weights, zero bias, zero residual)
-            if (pad64(tot) != pad32(tot) && !getenv("ESAHRNET_HEAD3_COUT32")) {
+            if (pad64(tot) != pad32(tot) && !c.opt.head3_cout32) {
                 const int cp = pad64(tot);
                 c.tensors[gop.out].Cp = cp;
                 c.tensors[h0].Cp = cp;
@@ -795,7 +832,7 @@ int build_plan_ops(esahrnet_ctx& c) {
         B.cbam("", stem_raw, sw, -1, false, cat2, 0);
         // the pooling over the raw stem tensor rides in the kernel that writes it (stem.hip: launch_stem_pool): that op also
         // owns the partials, sized for the slabs that kernel makes (one per row piece) instead of pool_partial's 64
-        if (c.ops[first_cbam_op].kind == OP_POOL && c.ops[first_cbam_op].in == stem_raw && !getenv("ESAHRNET_STEM_POOL_SEPARATE"))
+        if (c.ops[first_cbam_op].kind == OP_POOL && c.ops[first_cbam_op].in == stem_raw && !c.opt.stem_pool_separate)
             for (Op& so : c.ops)
                 if (so.kind == OP_STEMRAW) {
                     const int partial = c.ops[first_cbam_op].out;
@@ -808,7 +845,7 @@ int build_plan_ops(esahrnet_ctx& c) {
             Op o; o.kind = OP_ZERO; o.out = cat2; o.terms[0] = cat2; o.c0 = sw + ((K + 7) & ~7); o.nchan = c.padc(sw + K) - o.c0;
             B.push(o);
         }
-        const int oc = B.conv(c.spec_final, cat2, -1, false, "out_sb", 0, -1, true, c.bf);
+        const int oc = B.conv(c.spec_final, cat2, -1, false, "out_sb", 0, -1, true, c.bf());
         std::vector<int>& perm = c.dconvs[c.ops.back().dconv].perm;     // packed ci -> reference ci
         for (int i = 0; i < sw; ++i) perm.push_back(K + i);              // skip channels come second in the reference
         for (int i = 0; i < K; ++i) perm.push_back(i);
@@ -819,17 +856,14 @@ int build_plan_ops(esahrnet_ctx& c) {
     const int l3 = B.spec("last_layer.3", "last_layer.4", tot, K, 1, 1, 1, true, true);
     c.spec_final = B.spec("output_layer.0", "", K + g.cin, K, 3, 1, 0, true, false);
     int h3;
-    const bool fused_head = c.fuse_big && ys.size() == 4 && (pad32(pre[0]) == 32 || pad32(pre[0]) == 64);
-    if (fused_head) {
+    if (c.opt.head == HEAD_SB) {
         // t_b = W_b x_b on branch b's grid (f32 NHWC), b = 1..3; W_0, bias, ReLU, last_layer[3..5]
         // and the up-sampling of the t_b all happen inside head_fused.hip
         c.spec_l0 = l0; c.spec_l3 = l3; c.head_c0 = pre[0];
         // Two alternatives, chosen per input shape (plan_shape): alt 2 = head_t.hip + head_fused2.hip
         // (interpolation on the matrix cores, t_1 never materialised) when its geometry checks pass,
         // alt 1 = f32 NHWC terms + head_fused.hip otherwise.  Both read the same packed W_b slices.
-        const bool have2 = c.head2_enabled && (pad32(pre[1]) == 64 || pad32(pre[1]) == 96) &&
-                           esa::head_t_supported(pad32(pre[2])) && esa::head_t_supported(pad32(pre[3]));
-        Op o; o.kind = OP_HEAD; o.in = ys[0]; o.nterms = 3; o.alt = have2 ? 1 : 0;
+        Op o; o.kind = OP_HEAD; o.in = ys[0]; o.nterms = 3; o.alt = c.opt.head2 ? 1 : 0;
         int off = pre[0];
         int dslice[4] = {-1, -1, -1, -1};
         for (int b = 1; b < 4; ++b) {
@@ -850,7 +884,7 @@ int build_plan_ops(esahrnet_ctx& c) {
         for (int i = 0; i < 3; ++i) B.use(o.terms[i], idx);
         c.ops.push_back(o);
         h3 = o.out;
-        if (have2) {
+        if (c.opt.head2) {
             int tt[4] = {-1, -1, -1, -1};
             for (int b = 2; b < 4; ++b) {
                 Op t; t.kind = OP_HEADT; t.in = ys[b]; t.dconv = dslice[b]; t.alt = 2;
@@ -870,9 +904,7 @@ int build_plan_ops(esahrnet_ctx& c) {
         // alt 2 = head_fused_bf.hip (W0, interpolation, ReLU, last_layer[3] in one kernel) where its source-region
         // geometry holds, alt 1 = slice 0 + fuse + 1x1 (the 720-channel tensors materialised) otherwise
         // (fp32-grade mode: the same arrangement with head_x6.hip; f32 NHWC slices, ESAHRNET_X6_UNFUSED_HEAD=1 keeps alt 1)
-        const bool bf_head = ys.size() == 4 &&
-                             ((c.bf && (c.padc(pre[0]) == 64 || c.padc(pre[0]) == 128) && !getenv("ESAHRNET_BF_UNFUSED_HEAD")) ||
-                              (c.x6() && (c.padc(pre[0]) == 32 || c.padc(pre[0]) == 64) && !getenv("ESAHRNET_X6_UNFUSED_HEAD")));
+        const bool bf_head = c.opt.head == HEAD_BF || c.opt.head == HEAD_X6;
         std::vector<int> hterms(ys.size(), -1);
         int off = 0;
         std::vector<int> offs;
@@ -950,7 +982,7 @@ char* tensor_ptr(const esahrnet_ctx& c, char* ws, int t) {
 
 // does this input shape run the second-generation head (ops with alt == 2)?
 bool head2_for_shape(const esahrnet_ctx& c, const std::vector<int>& lh, const std::vector<int>& lw, bool* ulo) {
-    if (c.head2_op < 0 || !c.head2_enabled) return false;
+    if (c.head2_op < 0 || !c.opt.head2) return false;
     const Op& o = c.ops[c.head2_op];
     int th[3], tw[3];
     for (int i = 0; i < 3; ++i) {
@@ -1000,7 +1032,7 @@ esa::ConvParams conv_params_of(const esahrnet_ctx& c, const Op& o, const ShapePl
     p.res = o.res >= 0 ? tensor_ptr(c, ws, o.res) : nullptr;
     p.w = static_cast<const uint4*>(d.w); p.bias = d.bias;
     p.N = sp.n; p.H = sp.lh[ti.level]; p.W = sp.lw[ti.level]; p.OH = sp.lh[to.level]; p.OW = sp.lw[to.level];
-    p.Cinp = d.cinp; p.Coutp = d.coutp; p.relu = o.relu; p.out_f32 = d.out_f32 && !c.x6(); p.fmt = c.fmt;      // (fp32-grade: every tensor is plain f32)
+    p.Cinp = d.cinp; p.Coutp = d.coutp; p.relu = o.relu; p.out_f32 = d.out_f32 && !c.x6(); p.fmt = c.opt.fmt;      // (fp32-grade: every tensor is plain f32)
     return p;
 }
 
@@ -1113,7 +1145,7 @@ int plan_shape(esahrnet_ctx& c, int n, int h, int w) {
         // (and with lanes: until the last op of the wave, whose launches run concurrently)
         auto last_of = [&](const Tensor& t) {
             if (t.last < 0) return t.last;
-            if (c.nlanes > 1) return c.wave_last[c.ops[t.last].wave];
+            if (c.opt.nlanes > 1) return c.wave_last[c.ops[t.last].wave];
             if (c.ops[t.last].job >= 0) {
                 const JobGroup& g = c.jobs[c.ops[t.last].job];
                 return g.op[g.n - 1];
@@ -1204,21 +1236,7 @@ int esahrnet_create(const esahrnet_cfg* cfg, int device, esahrnet_handle* out) {
     esahrnet_ctx* c = new esahrnet_ctx();
     c->cfg = *cfg;
     c->device = device;
-    if (const char* e = getenv("ESAHRNET_UNFUSED")) c->fuse_big = !(e[0] && e[0] != '0');
-    if (cfg->precision == 1) {      // bf16 mode: op-by-op plan on the stream / 1x1 / fuse kernels (the fused stem, block
-        c->bf = true;               // and head kernels are built for the split format only)
-        c->fuse_big = false;
-        c->fmt = esa::FMT_BF;
-    }
-    if (cfg->precision == 2) {      // fp32-grade mode: f32 NHWC tensors, bf16x6 arithmetic (conv_x6.hip); op-by-op plan
-        c->fmt = esa::FMT_F32;
-        c->fuse_big = false;
-        c->x6_stemf = esa::stem_fused_x6_supported(cfg->cin, pad32(cfg->stem_width), pad32(cfg->stem_width)) && cfg->stem_width == 64 &&
-                      !getenv("ESAHRNET_X6_UNFUSED_STEM");
-    }
-    if (const char* e = getenv("ESAHRNET_STREAMS")) c->nlanes = atoi(e) > 1 ? 4 : 1;
-    if (const char* e = getenv("ESAHRNET_HEAD_V1")) c->head2_enabled = !(e[0] && e[0] != '0');
-    c->cbam_unfused = getenv("ESAHRNET_CBAM_UNFUSED") != nullptr;
+    c->opt = plan_options(*cfg);
     if (build_plan(*c)) { delete c; return 1; }
     *out = c;
     return 0;
@@ -1332,17 +1350,7 @@ int esahrnet_commit(esahrnet_handle h) {
                     const int src_ci = d.perm.empty() ? d.c0 + ci : d.perm[ci];
                     w[((size_t)co * cin + ci) * taps + t] = s.w[((size_t)co * s.cin + src_ci) * taps + t];
                 }
-        if (h->bf) {
-            packed.assign(esa::packed_weight_bytes_bf(d.coutp, d.cinp, s.k), 0);
-            esa::pack_conv_weights_bf(w.data(), s.cout, cin, s.k, d.coutp, d.cinp, packed.data());
-        } else if (h->x6()) {
-            packed.assign(esa::packed_weight_bytes_x6(d.coutp, d.cinp, s.k), 0);
-            esa::pack_conv_weights_x6(w.data(), s.cout, cin, s.k, d.coutp, d.cinp, packed.data());
-        } else {
-            packed.assign(esa::packed_weight_bytes(d.coutp, d.cinp, s.k), 0);
-            esa::pack_conv_weights(w.data(), s.cout, cin, s.k, d.coutp, d.cinp, packed.data());
-        }
-        if (upload(packed, &d.w)) return 1;
+        if (upload(h->pack(w.data(), s.cout, cin, s.k, d.coutp, d.cinp), &d.w)) return 1;
         std::vector<float> bias(d.coutp, 0.f);
         if (d.use_bias) std::copy(s.b.begin(), s.b.end(), bias.begin());
         if (upload(bias, reinterpret_cast<void**>(&d.bias))) return 1;
@@ -1374,7 +1382,7 @@ int esahrnet_commit(esahrnet_handle h) {
                 for (int t = 0; t < 9; ++t)
                     w[(((size_t)(co >> 3) * s.cin + ci) * 9 + t) * 8 + (co & 7)] = s.w[((size_t)co * s.cin + ci) * 9 + t];
         }
-        if (h->x6_stemf) {      // stem_x6_kernel reads conv1 in its own layout (bias inside)
+        if (h->opt.stem == STEM_FUSED_X6) {      // stem_x6_kernel reads conv1 in its own layout (bias inside)
             std::vector<float> wx(2 * 4 * 10 * 8, 0.f);
             esa::pack_stem_w1_x6(s.w.data(), s.b.data(), wx.data());
             w = wx;
@@ -1385,7 +1393,7 @@ int esahrnet_commit(esahrnet_handle h) {
         const ConvSpec& s = h->specs[h->spec_final];
         const int kt = esa::final_kt(s.cout);
         std::vector<float> w((size_t)s.cin * 9 * kt, 0.f), b(std::max(kt, 32), 0.f);
-        if (esa::final_mfma_supported(s.cout, s.cin - s.cout) && !getenv("ESAHRNET_FINAL_VALU") && !h->x6()) {
+        if (h->opt.final_mfma) {
             packed.assign(esa::final_mfma_bytes(s.cout, s.cin - s.cout), 0);
             esa::pack_final_mfma(s.w.data(), s.cout, s.cin - s.cout, packed.data());
             if (upload(packed, &h->final_wpk)) return 1;
@@ -1418,25 +1426,17 @@ int esahrnet_commit(esahrnet_handle h) {
         std::vector<float> w((size_t)ct * c0);
         for (int co = 0; co < ct; ++co)
             for (int ci = 0; ci < c0; ++ci) w[(size_t)co * c0 + ci] = s0.w[(size_t)co * s0.cin + ci];
-        if (h->bf) {
-            packed.assign(esa::packed_weight_bytes_bf(ctp, c0p, 1), 0);
-            esa::pack_conv_weights_bf(w.data(), ct, c0, 1, ctp, c0p, packed.data());
-            if (upload(packed, &h->head_w0)) return 1;
+        if (upload(h->pack(w.data(), ct, c0, 1, ctp, c0p), &h->head_w0)) return 1;
+        if (h->bf()) {
             packed.assign(esa::head_w3_bf_bytes(s3.cout, ctp), 0);
             esa::pack_head_w3_bf(s3.w.data(), s3.cout, ct, ctp, packed.data());
             if (upload(packed, &h->head_w3)) return 1;
-        } else if (h->x6()) {      // head_x6.hip: both in conv_x6's three-term fragments (its K order is the h0 fragment's)
-            packed.assign(esa::packed_weight_bytes_x6(ctp, c0p, 1), 0);
-            esa::pack_conv_weights_x6(w.data(), ct, c0, 1, ctp, c0p, packed.data());
-            if (upload(packed, &h->head_w0)) return 1;
+        } else if (h->x6()) {      // head_x6.hip: W3 in conv_x6's three-term fragments (its K order is the h0 fragment's)
             const int m3p = s3.cout <= 16 ? 16 : 32;
             packed.assign(esa::packed_weight_bytes_x6(m3p, ctp, 1), 0);
             esa::pack_conv_weights_x6(s3.w.data(), s3.cout, ct, 1, m3p, ctp, packed.data());
             if (upload(packed, &h->head_w3)) return 1;
         } else {
-            packed.assign(esa::packed_weight_bytes(ctp, c0p, 1), 0);
-            esa::pack_conv_weights(w.data(), ct, c0, 1, ctp, c0p, packed.data());
-            if (upload(packed, &h->head_w0)) return 1;
             packed.assign(esa::head_w3_bytes(s3.cout, ctp), 0);
             esa::pack_head_w3(s3.w.data(), s3.cout, ct, ctp, packed.data());
             if (upload(packed, &h->head_w3)) return 1;
@@ -1446,7 +1446,7 @@ int esahrnet_commit(esahrnet_handle h) {
         std::copy(s3.b.begin(), s3.b.end(), b3.begin());
         if (upload(b0, reinterpret_cast<void**>(&h->head_b0)) || upload(b3, reinterpret_cast<void**>(&h->head_b3))) return 1;
     }
-    if (h->nlanes > 1) {     // side streams + events for the wave executor
+    if (h->opt.nlanes > 1) {     // side streams + events for the wave executor
         for (int i = 0; i < 3; ++i) HIP_OK(hipStreamCreateWithFlags(&h->side[i], hipStreamNonBlocking));
         h->wave_entry.assign(h->nwaves, nullptr);
         h->wave_end.assign((h->ops.size() + 1) * 3, nullptr);
@@ -1488,9 +1488,8 @@ static int stem_pools(const esahrnet_ctx& c, int height, int width) {
     return slabs <= STEM_POOL_SLABS_MAX ? slabs : 0;
 }
 
-// (ESAHRNET_CBAM_UNFUSED is read once, at esahrnet_create, like the other plan switches — not per launch)
 static bool cbam_fused(const esahrnet_ctx& c, int Cp, int hh, int ww) {
-    return esa::cbam_spatial_supported(Cp) && ((hh + 15) / 16) * ((ww + 31) / 32) >= 32 && !c.cbam_unfused;
+    return esa::cbam_spatial_supported(Cp) && ((hh + 15) / 16) * ((ww + 31) / 32) >= 32 && !c.opt.cbam_unfused;
 }
 
 // one CBAM launch as a job description (cbam.hip); kind < 0: nothing to launch (the maps formed inside cbam_spatial, the
@@ -1501,7 +1500,7 @@ static esa::CbamJob cbam_job(const esahrnet_ctx& c, const Op& o, const ShapePlan
     q.kind = -1;
     const Tensor& tx = c.tensors[o.kind == OP_MLP ? o.terms[0] : o.in];
     const int hh = sp.lh[tx.level], ww = sp.lw[tx.level];
-    q.ap.N = sp.n; q.ap.H = hh; q.ap.W = ww; q.ap.Cp = tx.Cp; q.ap.C = o.nchan; q.ap.fmt = c.fmt;
+    q.ap.N = sp.n; q.ap.H = hh; q.ap.W = ww; q.ap.Cp = tx.Cp; q.ap.C = o.nchan; q.ap.fmt = c.opt.fmt;
     q.HW = hh * ww; q.P = std::min(Builder::POOL_SLABS, q.HW); q.Cr = o.nchan / 16;
     switch (o.kind) {
         case OP_POOL:
@@ -1575,7 +1574,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
         case OP_STEM: {
             const ConvSpec& s = c.specs[c.spec_stem];
             esa::StemParams p{static_cast<const float*>(b.x), T(o.out), c.stem_w, c.stem_b,
-                              n, height, width, c.cfg.cin, c.tensors[o.out].Cp, 1, c.fmt};
+                              n, height, width, c.cfg.cin, c.tensors[o.out].Cp, 1, c.opt.fmt};
             if (desc) {
                 describe(desc, "stem_kernel", "%s", s.name.c_str());
                 desc->flops = 2.0 * n * height * width * s.cout * s.cin * 9;
@@ -1585,7 +1584,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
         }
         case OP_STEMRAW: {
             esa::StemParams p{static_cast<const float*>(b.x), T(o.out), c.stemraw_w, c.stemraw_b,
-                              n, height, width, c.cfg.cin, c.tensors[o.out].Cp, 0, c.fmt};
+                              n, height, width, c.cfg.cin, c.tensors[o.out].Cp, 0, c.opt.fmt};
             if (desc) plain("stem_kernel(raw)");
             else rc = stem_pools(c, height, width) ? esa::launch_stem_pool(p, reinterpret_cast<float*>(T(o.out2)), stream)
                                                    : esa::launch_stem(p, stream);
@@ -1624,11 +1623,11 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 break;
             }
             switch (q.kind) {
-                case esa::CBAM_POOL: rc = esa::launch_pool_partial(q.ap.x, q.partial, n, q.HW, q.ap.Cp, q.P, stream, c.fmt); break;
+                case esa::CBAM_POOL: rc = esa::launch_pool_partial(q.ap.x, q.partial, n, q.HW, q.ap.Cp, q.P, stream, c.opt.fmt); break;
                 case esa::CBAM_MLP:
                     rc = esa::launch_ca_mlp(q.partial, q.w0, q.w2, q.ca, n, q.HW, q.ap.C, q.ap.Cp, q.Cr, q.P, stream);
                     break;
-                case esa::CBAM_MAPS: rc = esa::launch_cbam_maps(q.ap.x, q.ap.ca, q.maps, n, q.HW, q.ap.C, q.ap.Cp, stream, c.fmt); break;
+                case esa::CBAM_MAPS: rc = esa::launch_cbam_maps(q.ap.x, q.ap.ca, q.maps, n, q.HW, q.ap.C, q.ap.Cp, stream, c.opt.fmt); break;
                 case esa::CBAM_APPLY: rc = esa::launch_cbam_apply(q.ap, stream); break;
                 case esa::CBAM_SPATIAL: rc = esa::launch_cbam_spatial(q.ap, stream); break;
                 default: break;
@@ -1641,7 +1640,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             esa::ResampleParams p{};
             p.x = T(o.in); p.y = T(o.out); p.N = n;
             p.h = lh[ti.level]; p.w = lw[ti.level]; p.H = lh[to.level]; p.W = lw[to.level];
-            p.C = o.nchan; p.Cp_src = ti.Cp; p.y_pix_bytes = to.Cp * c.eb(); p.y_c0 = o.c0; p.align = o.align; p.fmt = c.fmt;
+            p.C = o.nchan; p.Cp_src = ti.Cp; p.y_pix_bytes = to.Cp * c.eb(); p.y_c0 = o.c0; p.align = o.align; p.fmt = c.opt.fmt;
             if (desc) plain("resample_slice");
             else rc = esa::launch_resample_slice(p, stream);
             break;
@@ -1658,23 +1657,24 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             if (desc) {
                 plain("head_gather");
                 desc->bytes += tbytes(o.terms[0]);
-            } else rc = esa::launch_head_gather(p, stream, c.fmt);
+            } else rc = esa::launch_head_gather(p, stream, c.opt.fmt);
             break;
         }
         case OP_ZERO: {
             const Tensor& to = c.tensors[o.out];
             if (desc) plain("zero_slice");
-            else rc = esa::launch_zero_slice(T(o.out), (long long)n * lh[to.level] * lw[to.level], to.Cp * c.eb(), o.c0, o.nchan, stream, c.fmt);
+            else rc = esa::launch_zero_slice(T(o.out), (long long)n * lh[to.level] * lw[to.level], to.Cp * c.eb(), o.c0, o.nchan, stream, c.opt.fmt);
             break;
         }
         case OP_TONCHW: {
             const bool f32 = c.tensors[o.in].f32;       // (bf16 mode: the output layer's f32 heat-maps)
             if (desc) plain(f32 ? "f32_to_nchw" : "sb_to_nchw");
-            else rc = esa::launch_fmt_to_nchw(f32 ? esa::FMT_F32 : c.fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
+            else rc = esa::launch_fmt_to_nchw(f32 ? esa::FMT_F32 : c.opt.fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
                                               static_cast<float*>(b.heat), stream);
             break;
         }
         case OP_STEMF: {
+            const bool x6 = c.opt.stem == STEM_FUSED_X6;
             const DevConv& d = c.dconvs[o.dconv];
             const Tensor& to = c.tensors[o.out];
             esa::StemFusedParams p{};
@@ -1686,12 +1686,12 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             if (desc) {
                 const ConvSpec& s1 = c.specs[c.spec_stem];
                 const ConvSpec& s2 = c.specs[d.spec];
-                describe(desc, c.x6() ? "stem_x6_kernel" : "stem_fused", "conv1 + conv2");
+                describe(desc, x6 ? "stem_x6_kernel" : "stem_fused", "conv1 + conv2");
                 desc->flops = 2.0 * n * height * width * s1.cout * s1.cin * 9 +
                               2.0 * n * lh[to.level] * lw[to.level] * s2.cout * s2.cin * 9;
                 desc->bytes = (double)n * height * width * s1.cin * 4 + tbytes(o.out) +
                               (double)c.wbytes(pad32(s2.cout), pad32(s2.cin), 3);
-            } else rc = c.x6() ? esa::launch_stem_fused_x6(p, stream) : esa::launch_stem_fused(p, stream);
+            } else rc = x6 ? esa::launch_stem_fused_x6(p, stream) : esa::launch_stem_fused(p, stream);
             break;
         }
         case OP_CONV: {
@@ -1743,7 +1743,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 if (c.x6() && s.k == 1 && esa::conv1x1_x6_jobs_supported(ps, g.n)) snprintf(kernel, sizeof kernel, "conv1x1_x6_jobs_kernel");
                 else if (c.x6()) snprintf(kernel, sizeof kernel, "conv_x6_jobs_kernel<%d, %d>", s.k, s.stride);
                 else if (s.k == 1) snprintf(kernel, sizeof kernel, "conv1x1_jobs_kernel");
-                else snprintf(kernel, sizeof kernel, "conv_s2c32_jobs_kernel<%d, %d, %s>", s.stride, s.stride == 1 ? 8 : 4, c.bf ? "true" : "false");
+                else snprintf(kernel, sizeof kernel, "conv_s2c32_jobs_kernel<%d, %d, %s>", s.stride, s.stride == 1 ? 8 : 4, c.bf() ? "true" : "false");
                 std::string lab;
                 for (int k = 0; k < g.n; ++k) {
                     const Op& ok = c.ops[g.op[k]];
@@ -1803,7 +1803,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 p.t[i] = T(o.terms[i]); p.th[i] = lh[tt.level]; p.tw[i] = lw[tt.level];
                 p.Ctp = tt.Cp;
             }
-            p.C0p = ti.Cp; p.C3p = to.Cp; p.K = c.cfg.num_keypoints;
+            p.C0p = ti.Cp; p.C3p = to.Cp; p.K = c.cfg.num_keypoints; p.valu = c.opt.bf_head_valu;
             if (desc) {
                 const ConvSpec& s0 = c.specs[c.spec_l0];
                 const ConvSpec& s3 = c.specs[c.spec_l3];
@@ -1876,7 +1876,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 p.x[i] = T(o.terms[i]); p.h[i] = lh[ti.level]; p.w[i] = lw[ti.level];
             }
             p.y = T(o.out); p.N = n; p.H = lh[to.level]; p.W = lw[to.level]; p.Cp = to.Cp;
-            p.relu = o.relu; p.fmt = c.fmt;
+            p.relu = o.relu; p.fmt = c.opt.fmt;
             if (desc) {
                 describe(desc, "fuse_kernel", "fuse -> %s", to.tap.c_str());
                 desc->bytes = tbytes(o.out);
@@ -1890,7 +1890,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             p.h3 = T(o.in); p.x0 = static_cast<const float*>(b.x); p.out = static_cast<float*>(b.heat);
             p.w = c.final_w; p.bias = c.final_b; p.wpk = static_cast<const uint4*>(c.final_wpk);
             p.N = n; p.H = height; p.W = width; p.h = lh[ti.level]; p.wd = lw[ti.level];
-            p.K = c.cfg.num_keypoints; p.cin = c.cfg.cin; p.Cp = ti.Cp; p.fmt = c.fmt;
+            p.K = c.cfg.num_keypoints; p.cin = c.cfg.cin; p.Cp = ti.Cp; p.fmt = c.opt.fmt;
             p.part = static_cast<float2*>(b.part);
             if (desc) {
                 const ConvSpec& s = c.specs[c.spec_final];
@@ -1920,7 +1920,7 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
     // wave executor: lane 0 is the caller's stream; the other lanes of a wave are side streams that fork from and join
     // into it (also valid under stream capture: the graph gets parallel branches).  The timed and the
     // keep-intermediates modes stay on one stream.
-    const bool multi = !events && !h->keep && h->nlanes > 1 && h->side[0] != nullptr;
+    const bool multi = !events && !h->keep && h->opt.nlanes > 1 && h->side[0] != nullptr;
     const hipStream_t caller = stream;
     bool lane_used[4] = {true, false, false, false};
     int cur_wave = -1;
@@ -2104,7 +2104,7 @@ int esahrnet_tap_read(esahrnet_handle h, const char* name, int n, int height, in
     if (plan_shape(*h, n, height, width)) return 1;
     if (t->alt != 0 && t->alt != (h->sp.head2 ? 2 : 1))
         return fail("tap_read: '%s' belongs to the head alternative that does not run at this shape", name);
-    const int rc = esa::launch_fmt_to_nchw(t->f32 ? esa::FMT_F32 : h->fmt,
+    const int rc = esa::launch_fmt_to_nchw(t->f32 ? esa::FMT_F32 : h->opt.fmt,
         static_cast<const char*>(ws_dev) + t->off, n, t->C, h->sp.lh[t->level], h->sp.lw[t->level], t->Cp,
         static_cast<float*>(out_dev), static_cast<hipStream_t>(stream));
     if (rc) return fail("tap_read: %s", hipGetErrorString((hipError_t)rc));

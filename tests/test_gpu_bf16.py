@@ -211,14 +211,16 @@ def test_bf16_head_interpolation_on_matrix_cores_matches_valu_form(env, monkeypa
     """head_fused_bf.hip evaluates sum_b up(t_b) as T . U on the matrix cores (U = interpolation weights: exact in bf16 for the
     2x / 4x / 8x grids, hi + lo otherwise — 104x72 and 70x50 have branch grids that are not exact decimations).  The first
     form (four VALU taps per branch, ESAHRNET_BF_HEAD_VALU=1) computes the same sums in another order: the two must agree
-    to the rounding of h0 to bf16."""
+    to the rounding of h0 to bf16.  (The switch is read when the handle is created: the second net is built under it.)"""
+    monkeypatch.delenv("ESAHRNET_BF_HEAD_VALU", raising=False)
     net, sd = _build(env, "seg_hrnet2", (32, 64, 128, 256), 8)
     x = env["synth"].make_crops(2, 1, hw[0], hw[1], seed=8).cuda()
     with torch.no_grad():
-        monkeypatch.delenv("ESAHRNET_BF_HEAD_VALU", raising=False)
         y_mf, ops = net.forward_timed(x)
-        monkeypatch.setenv("ESAHRNET_BF_HEAD_VALU", "1")
-        y_valu = net(x)
+    monkeypatch.setenv("ESAHRNET_BF_HEAD_VALU", "1")
+    net_valu, _ = _build(env, "seg_hrnet2", (32, 64, 128, 256), 8)
+    with torch.no_grad():
+        y_valu = net_valu(x)
     if "head_fused_bf" not in {o["kernel"] for o in ops}:
         pytest.skip("this geometry runs the unfused head alternative")
     scale = max(1.0, y_valu.abs().max().item())

@@ -33,8 +33,8 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _build(env, variant, widths, seed, gain=0.5, precision="fp32"):
-    net = env[variant].get_seg_model(env["config"].make_config(widths=widths), precision=precision)
+def _build(env, variant, widths, seed, gain=0.5, precision="fp32", **kw):
+    net = env[variant].get_seg_model(env["config"].make_config(widths=widths), precision=precision, **kw)
     sd = env["synth"].make_state_dict({k: v.shape for k, v in net.state_dict().items()}, seed=seed, gain=gain)
     net.load_state_dict(sd, strict=True)
     return net.cuda().eval(), sd
@@ -466,6 +466,43 @@ def test_hrnet3_odd_shapes_and_head_forms(env, monkeypatch, hw):
     scale = max(1.0, ref.abs().max().item())
     assert (y - ref).abs().max().item() <= 2e-5 * scale
     assert (yd - ref).abs().max().item() <= 2e-5 * scale
+
+
+@pytest.mark.parametrize("stem_width, cin, unfused", [(32, 1, False), (64, 3, False), (64, 1, True)])
+def test_hrnet3_stem_where_stem_x6_does_not_serve(env, monkeypatch, stem_width, cin, unfused):
+    """stem_x6_kernel serves cin 1 and stem width 64 only: another stem width, another cin and ESAHRNET_X6_UNFUSED_STEM=1 take
+    stem_kernel + the stride-2 convolution, within fp32-grade distance of the oracle.  At (64, 1) the unfused stem is bit-identical
+    to stem_x6_kernel.  (The Python module fixes a stem width of 64: the test hands the library a configuration with another
+    width, and the module takes its convolutions from the library.)"""
+    from esa_pose_estimation_amd import hrnet
+    make = hrnet._cfg_struct
+
+    def cfg_struct(*a, **k):
+        s = make(*a, **k)
+        s.stem_width = stem_width
+        return s
+    monkeypatch.setattr(hrnet, "_cfg_struct", cfg_struct)
+    monkeypatch.delenv("ESAHRNET_X6_UNFUSED_STEM", raising=False)
+    if unfused:
+        monkeypatch.setenv("ESAHRNET_X6_UNFUSED_STEM", "1")
+    net, sd = _build(env, "seg_hrnet3", (32, 64, 128, 256), 19, cin=cin)
+    assert sd["conv1.weight"].shape == (stem_width, cin, 3, 3)
+    x = env["synth"].make_crops(2, cin, 64, 96, seed=19)
+    cfg = env["hrnet_ref"].default_cfg(cin, 30, variant=1, stem_width=stem_width)
+    with torch.no_grad():
+        ref = env["hrnet_ref"].forward(sd, cfg, x)
+        y, ops = net.forward_timed(x.cuda())
+        y = y.cpu()
+    kernels = [o["kernel"] for o in ops]
+    assert "stem_x6_kernel" not in kernels and "stem_kernel" in kernels, kernels[:3]
+    assert (y - ref).abs().max().item() <= 2e-5 * max(1.0, ref.abs().max().item())
+    if unfused:
+        monkeypatch.delenv("ESAHRNET_X6_UNFUSED_STEM")
+        net_f, _ = _build(env, "seg_hrnet3", (32, 64, 128, 256), 19, cin=cin)
+        with torch.no_grad():
+            y_f, ops_f = net_f.forward_timed(x.cuda())
+        assert "stem_x6_kernel" in {o["kernel"] for o in ops_f}
+        assert torch.equal(y_f.cpu(), y)
 
 
 def test_hrnet3_cbam_forms_agree(env, monkeypatch):

@@ -193,6 +193,30 @@ def test_unfused_plan_matches_reference_golden(env, golden_dir, tag, monkeypatch
     assert err <= GUARD, err
 
 
+def test_valu_output_layer_matches_reference_golden(env, golden_dir, monkeypatch):
+    """ESAHRNET_FINAL_VALU=1: the f32 VALU output layer instead of final_mfma_kernel.  It leaves no per-tile maxima
+    (esahrnet_partial_tiles reports 0, the matrix-core one does not) and must reproduce the reference just as well."""
+    g = np.load(os.path.join(golden_dir, "w32_hrnet2_128.npz"), allow_pickle=False)
+    hw = int(g["hw"])
+    x = env["synth"].make_crops(int(g["n"]), 1, hw, hw, seed=int(g["seed"])).cuda()
+    tiles = {}
+    for valu in (False, True):
+        if valu:
+            monkeypatch.setenv("ESAHRNET_FINAL_VALU", "1")
+        else:
+            monkeypatch.delenv("ESAHRNET_FINAL_VALU", raising=False)
+        net, sd = _build(env, "seg_hrnet2", tuple(int(v) for v in g["widths"]), int(g["seed"]))
+        with torch.no_grad():
+            y = net(x)
+        nt = C.c_int(-1)
+        env["L"].check(env["lib"].esahrnet_partial_tiles(net._rt._handle_for(net, x.device), hw, hw, C.byref(nt)))
+        tiles[valu] = nt.value
+    assert tiles[False] > 0 and tiles[True] == 0, tiles
+    s = int(g["subsample"]) if "subsample" in g.files else 1
+    err = np.abs(y.cpu().numpy()[:, :, ::s, ::s] - g["out"]).max()
+    assert err <= GUARD, err
+
+
 @pytest.mark.parametrize("v1", [False, True])
 def test_both_head_generations_match_reference_golden(env, golden_dir, monkeypatch, v1):
     """The plan carries two heads and picks per input shape: head_fused2 (+ head_t; interpolation on the

@@ -351,13 +351,18 @@ def test_hot_kernels_keep_their_registers():
             assert u["vgprs"] <= 128 and u["waves_per_simd"] == 4, (k, u)
 
 
-@pytest.mark.parametrize("combo", make_op_descs.COMBOS, ids=lambda c: make_op_descs.combo_key(*c))
-def test_op_descriptions_match_the_fixture(combo, monkeypatch):
-    """esahrnet_op_desc_get names every launch of the plan and counts its FLOPs and bytes (bench.py's roofline leg, the GPU
-    tests' kernel checks).  tests/golden/op_descs.json.gz pins them for every variant / precision / width and four shapes:
-    strings byte for byte and the figures exactly (the same double expressions, no tolerance)."""
+def _clear_switches(monkeypatch):
     for k in [k for k in os.environ if k.startswith("ESAHRNET_")]:
         monkeypatch.delenv(k)                   # plan switches: esahrnet_create reads them
+
+
+@pytest.mark.parametrize("combo", make_op_descs.COMBOS + make_op_descs.SWITCHED, ids=lambda c: make_op_descs.combo_key(*c))
+def test_op_descriptions_match_the_fixture(combo, monkeypatch):
+    """esahrnet_op_desc_get names every launch of the plan and counts its FLOPs and bytes (bench.py's roofline leg, the GPU
+    tests' kernel checks).  tests/golden/op_descs.json.gz pins them for every variant / precision / width and four shapes,
+    and for every plan switch that changes them at two shapes: strings byte for byte and the figures exactly (the same
+    double expressions, no tolerance)."""
+    _clear_switches(monkeypatch)
     want = json.load(gzip.open(make_op_descs.OUT))[make_op_descs.combo_key(*combo)]
     got = make_op_descs.op_descs(*combo)
     assert list(got) == list(want)
@@ -365,3 +370,74 @@ def test_op_descriptions_match_the_fixture(combo, monkeypatch):
         assert len(got[shape]) == len(rows), shape
         for i, (g, w) in enumerate(zip(got[shape], rows)):
             assert g == w, (shape, i)
+
+
+def test_op_schedule_matches_the_fixture(monkeypatch):
+    """ESAHRNET_STREAMS=4: the (wave, lane) schedule_waves gives every op, pinned like the descriptions."""
+    _clear_switches(monkeypatch)
+    want = json.load(gzip.open(make_op_descs.OUT))[make_op_descs.combo_key(*make_op_descs.SCHEDULE)]
+    assert make_op_descs.op_schedule(*make_op_descs.SCHEDULE) == want
+
+
+@pytest.mark.parametrize("combo", [c for c in make_op_descs.SWITCHED if c[3][0][1] == "1"],
+                         ids=lambda c: make_op_descs.combo_key(*c))
+def test_switches_set_to_zero_are_off(combo, monkeypatch):
+    """A plan switch set to 0 (or empty) is off: the plan is the default one."""
+    _clear_switches(monkeypatch)
+    variant, precision, widths, switches = combo
+    default = make_op_descs.op_descs(variant, precision, widths)
+    for value in ("0", ""):
+        got = make_op_descs.op_descs(variant, precision, widths, tuple((k, value) for k, _ in switches))
+        assert got == {s: default[s] for s in got}, value
+    sched = make_op_descs.SCHEDULE
+    assert make_op_descs.op_schedule(*sched[:3], (("STREAMS", "0"),)) == make_op_descs.op_schedule(*sched[:3])
+
+
+@pytest.mark.parametrize("stem_width, cin, switches", [(32, 1, ()), (64, 3, ()), (16, 4, ()), (48, 2, ()),
+                                                       (64, 1, (("X6_UNFUSED_STEM", "1"),))])
+def test_seg_hrnet3_fp32_stem_where_stem_x6_does_not_serve(stem_width, cin, switches, monkeypatch):
+    """seg_hrnet3 in the fp32-grade mode gets stem_x6_kernel only where that kernel serves (cin 1, stem width 64, no
+    ESAHRNET_X6_UNFUSED_STEM); otherwise the raw conv1, conv1 + bn1 + ReLU on the stem kernel and a stride-2 conv2."""
+    from esa_pose_estimation_amd import hrnet
+    _clear_switches(monkeypatch)
+    for k, v in switches:
+        monkeypatch.setenv("ESAHRNET_" + k, v)
+    lib = _lib.lib()
+    s = hrnet._cfg_struct(config.make_config(), cin, 30, 1, "fp32")
+    s.stem_width = stem_width
+    h = C.c_void_p()
+    assert lib.esahrnet_create(C.byref(s), 0, C.byref(h)) == 0, lib.esahrnet_last_error().decode()
+    try:
+        for n, hh, ww in [(2, 64, 80), (32, 256, 256)]:
+            rows = []
+            for i in range(lib.esahrnet_launch_count(h)):
+                d = _lib.OpDesc()
+                assert lib.esahrnet_op_desc_get(h, i, n, hh, ww, C.byref(d)) == 0, lib.esahrnet_last_error().decode()
+                rows.append((d.kernel.decode(), d.label.decode()))
+            kernels = [k for k, _ in rows]
+            assert kernels[:2] == ["stem_kernel(raw)", "stem_kernel"] and "stem_x6_kernel" not in kernels
+            assert rows[2][1] == "conv2" and rows[2][0].startswith("conv_x6_kernel<3, 2, "), rows[2]
+    finally:
+        lib.esahrnet_destroy(h)
+
+
+def test_switches_are_read_when_the_handle_is_created(monkeypatch):
+    """Setting a switch after esahrnet_create does not change that handle's plan."""
+    _clear_switches(monkeypatch)
+    variant, precision, widths, switches = make_op_descs.SWITCHED[0]
+    rt = make_op_descs._probe(variant, precision, widths, ())
+    n, h, w = make_op_descs.SWITCH_SHAPES[0]
+
+    def descs():
+        rows = []
+        for i in range(rt.launch_count()):
+            d = _lib.OpDesc()
+            _lib.check(rt.lib.esahrnet_op_desc_get(rt._probe, i, n, h, w, C.byref(d)))
+            rows.append((d.kernel.decode(), d.label.decode(), d.flops, d.bytes))
+        return rows
+    before = descs()
+    for k, v in switches:
+        monkeypatch.setenv("ESAHRNET_" + k, v)
+    assert descs() == before
+    switched = make_op_descs.op_descs(variant, precision, widths, switches)[f"{n},{h},{w}"]
+    assert [tuple(r[1:]) for r in switched] != before      # (a new handle does see it)
