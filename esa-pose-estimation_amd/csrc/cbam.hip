@@ -33,7 +33,8 @@ template <bool BF> __device__ __forceinline__ void st8(char* p, const float v[8]
 }
 
 // ---- pool_partial: grid (P, N), 256 threads; thread = (pixel lane pl, channel group c8) ----------
-// (BF: Cp up to 2048 — W48's 384-channel branch — so the reduction walks the channels in steps of 256)
+// Cp up to 2048 (W48's 384-channel branch: G = 48 groups, PL = 5 pixel lanes): the final reduction walks the channels in
+// steps of 256; the LDS arrays hold 8 values per thread whatever Cp is
 template <bool BF>
 __device__ __forceinline__ void pool_partial_body(const char* x, float* partial, int HW, int Cp, int P, int slab, int n,
                                                   float* ssum, float* smax, bool f32) {
@@ -63,11 +64,7 @@ __device__ __forceinline__ void pool_partial_body(const char* x, float* partial,
         float* o = partial + (((size_t)n * P + slab) * Cp + c) * 2;
         o[0] = a; o[1] = b;
     };
-    if constexpr (BF) {
-        for (int c = tid; c < Cp; c += 256) reduce(c);
-    } else {
-        if (tid < Cp) reduce(tid);
-    }
+    for (int c = tid; c < Cp; c += 256) reduce(c);
 }
 __global__ __launch_bounds__(256) void pool_partial_kernel(const char* x, float* partial, int HW, int Cp, int P, int f32) {
     __shared__ float ssum[256 * 8];
@@ -447,12 +444,11 @@ inline int blocks(long long total) { return (int)((total + 255) / 256); }
 }  // namespace
 
 int launch_pool_partial(const char* x, float* partial, int N, int HW, int Cp, int P, hipStream_t s, int fmt) {
+    if ((Cp & 7) || Cp > 2048 || Cp < 8 || (fmt != FMT_SB && fmt != FMT_F32 && fmt != FMT_BF)) return (int)hipErrorInvalidValue;
     if (fmt == FMT_BF) {
-        if ((Cp & 7) || Cp > 2048 || Cp < 8) return (int)hipErrorInvalidValue;
         hipLaunchKernelGGL(pool_partial_bf_kernel, dim3(P, N), dim3(256), 0, s, x, partial, HW, Cp, P);
         return (int)hipGetLastError();
     }
-    if ((Cp & 7) || Cp > 256 || Cp < 8 || (fmt != FMT_SB && fmt != FMT_F32)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(pool_partial_kernel, dim3(P, N), dim3(256), 0, s, x, partial, HW, Cp, P, fmt == FMT_F32 ? 1 : 0);
     return (int)hipGetLastError();
 }
@@ -494,7 +490,7 @@ long long cbam_job_blocks(CbamJob& q) {
     const int Cp = q.ap.Cp;
     if ((Cp & 7) || Cp < 8 || (q.ap.fmt != FMT_SB && q.ap.fmt != FMT_F32 && q.ap.fmt != FMT_BF)) return -1;
     switch (q.kind) {
-        case CBAM_POOL: return Cp > (q.ap.fmt == FMT_BF ? 2048 : 256) ? -1 : (long long)q.P * q.ap.N;
+        case CBAM_POOL: return Cp > 2048 ? -1 : (long long)q.P * q.ap.N;
         case CBAM_MLP: return (Cp > 512 || q.Cr > 64 || q.Cr < 1) ? -1 : q.ap.N;
         case CBAM_MAPS: { if (Cp > 2048) return -1; const int ppb = 256 / (Cp >> 3); return ((long long)q.ap.N * q.HW + ppb - 1) / ppb; }
         case CBAM_APPLY: { if (Cp > 2048 || (q.ap.y_c0 & 7)) return -1; const int ppb = 256 / (Cp >> 3); return ((long long)q.ap.N * q.HW + ppb - 1) / ppb; }

@@ -264,6 +264,9 @@ struct CbamJob {
 };
 struct CbamJobs { CbamJob j[CBAM_MAXJOBS]; int start[CBAM_MAXJOBS + 1]; int n; };
 int launch_cbam_jobs(const CbamJob* jobs, int n, hipStream_t s);
+// workgroups job `q` needs (the grid its own launch would use; fills tiles_x / tiles_y); -1: no CBAM kernel serves it.  The
+// predicates are those of every CBAM launcher, single or merged, and depend on the shape, never on the batch.
+long long cbam_job_blocks(CbamJob& q);
 struct ResampleParams {
     const char* x;      // SB [N][h][w][Cp_src]
     char* y;            // SB [N][H][W][..], pixel pitch y_pix_bytes, channel offset y_c0 (multiple of 8)
@@ -308,5 +311,9 @@ int launch_f32_to_nchw(const char* x, int N, int C, int H, int W, int Cp, float*
 // by format code
 int launch_nchw_to_fmt(int fmt, const float* x, int N, int C, int H, int W, char* y, int Cp, hipStream_t s);
 int launch_fmt_to_nchw(int fmt, const char* x, int N, int C, int H, int W, int Cp, float* y, hipStream_t s);
+// f32 / SB (fmt) NHWC heat-maps -> f32 NCHW plus each tile's first maximum, part [N*C][to_nchw_part_tiles(H, W)] (value,
+// index bits) as keypoints_finish reads it; C <= 32
+int to_nchw_part_tiles(int H, int W);
+int launch_to_nchw_part(int fmt, const char* x, int N, int C, int H, int W, int Cp, float* y, float2* part, hipStream_t s);
 
 }  // namespace esa

@@ -1,6 +1,5 @@
-// layout.hip — f32 NCHW <-> SB (split-bf16 NHWC) conversion.  Used by the per-operator test
-// entry points and by esahrnet_tap_read; the network itself enters SB through the stem kernel
-// and leaves it through the head kernel.
+// layout.hip — f32 NCHW <-> SB (split-bf16 NHWC), BF and F32 conversion.  Used by the per-operator test entry points, by
+// esahrnet_tap_read and for seg_hrnet3's heat-maps; the network itself enters its format through the stem kernel.
 #include "kernels.h"
 #include "sb.h"
 
@@ -108,7 +107,84 @@ __global__ __launch_bounds__(256) void f32_to_nchw_kernel(const float* x, int C,
         if (g * 8 + j < C) o[(size_t)j * hw] = v[j];
 }
 
+// The network output with per-tile maxima (seg_hrnet3 under esahrnet_forward_partials): f32 or SB NHWC -> f32 NCHW, the
+// same values as the two kernels above.  A workgroup owns TONCHW_TP consecutive row-major pixels of one crop (the last
+// tile of a plane is shorter).  It reads them as whole 32-byte channel groups, all loads of a thread in flight at once, turns
+// them round in LDS, writes each plane's run with consecutive lanes, and leaves the run's first maximum per plane as (value,
+// int bits of row * W + col) in part[(n * C + c) * ntiles + tile], the layout keypoints_finish_kernel reads.  Every step goes
+// through argmax_take, whose order does not depend on the order of the steps: the finish over these runs picks what the
+// full sweep picks.  Eight waves per workgroup: with 33 KB of LDS four workgroups fit a CU, and those fill it.
+constexpr int TONCHW_TP = 256, TONCHW_NT = 512;
+template <bool F32>
+__global__ __launch_bounds__(TONCHW_NT) void to_nchw_part_kernel(const char* x, int C, int hw, int Cp, float* y, float2* part,
+                                                                 int ntiles) {
+    __shared__ float s[32][TONCHW_TP + 2];         // C <= 32 planes; (+2: a wave's 8-channel groups write to different banks)
+    constexpr int IT = TONCHW_TP * 4 / TONCHW_NT;   // (pixel, 8-channel group) items per thread: G <= 4
+    const int tile = (int)(blockIdx.x % (unsigned)ntiles), n = (int)(blockIdx.x / (unsigned)ntiles);
+    const int q0 = tile * TONCHW_TP, np = min(TONCHW_TP, hw - q0);
+    const int G = (C + 7) >> 3, tid = threadIdx.x;
+    uint4 a[IT], b[IT];
+#pragma unroll
+    for (int k = 0; k < IT; ++k) {
+        const int i = tid + k * TONCHW_NT, pl = i / G, g = i - pl * G;
+        if (i < np * G) {
+            const char* p = x + ((size_t)n * hw + q0 + pl) * (size_t)(Cp * 4) + g * 32;
+            a[k] = *reinterpret_cast<const uint4*>(p);
+            b[k] = *reinterpret_cast<const uint4*>(p + 16);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < IT; ++k) {
+        const int i = tid + k * TONCHW_NT, pl = i / G, g = i - pl * G;
+        if (i < np * G) {
+            float v[8];
+            join8_fmt(a[k], b[k], v, F32);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (g * 8 + j < C) s[g * 8 + j][pl] = v[j];
+        }
+    }
+    __syncthreads();
+    const int lane = tid & 63;
+    for (int c = tid >> 6; c < C; c += TONCHW_NT / 64) {     // plane c: one wave
+        float* o = y + ((size_t)n * C + c) * hw + q0;
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int r = 0; r < TONCHW_TP / 64; ++r) {
+            const int p = lane + r * 64;
+            if (p < np) {
+                const float v = s[c][p];
+                o[p] = v;
+                argmax_take(v, q0 + p, bv, bi);
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const float ov = __shfl_xor(bv, off);
+            const int oi = __shfl_xor(bi, off);
+            argmax_take(ov, oi, bv, bi);
+        }
+        if (lane == 0) part[((size_t)n * C + c) * ntiles + tile] = make_float2(bv, __int_as_float(bi));
+    }
+}
+
 }  // namespace
+
+int to_nchw_part_tiles(int H, int W) {
+    const long long hw = (long long)H * W;
+    return H > 0 && W > 0 && hw <= 0x7fffffffLL ? (int)((hw + TONCHW_TP - 1) / TONCHW_TP) : 0;
+}
+
+int launch_to_nchw_part(int fmt, const char* x, int N, int C, int H, int W, int Cp, float* y, float2* part, hipStream_t s) {
+    const int ntiles = to_nchw_part_tiles(H, W);
+    const long long nblk = (long long)N * ntiles;
+    if (ntiles <= 0 || N <= 0 || nblk > 0x7fffffffLL || C < 1 || C > 32 || C > Cp || (Cp & 7) || (fmt != FMT_SB && fmt != FMT_F32))
+        return (int)hipErrorInvalidValue;
+    auto kern = fmt == FMT_F32 ? to_nchw_part_kernel<true> : to_nchw_part_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(TONCHW_NT), 0, s, x, C, H * W, Cp, y, part, ntiles);
+    return (int)hipGetLastError();
+}
 
 int launch_nchw_to_f32(const float* x, int N, int C, int H, int W, char* y, int Cp, hipStream_t s) {
     const long long total = (long long)N * H * W * (Cp >> 3);

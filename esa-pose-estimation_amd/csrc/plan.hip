@@ -114,7 +114,7 @@ struct Op {
     bool wait_entry = false;    // side-lane launch: waits for the wave's entry event first
     bool record = false;        // lane-0 op: an event is recorded behind it (a side lane forks from here)
     unsigned join = 0;          // lane-0 launch: side lanes (bit l) lane 0 waits for first
-    int aux[3] = {-1, -1, -1};  // CBAM ops: fc.0, fc.2, sa.conv1
+    int aux[3] = {-1, -1, -1};  // CBAM ops: fc.0 (on every step: it names the layer), fc.2, sa.conv1
     int c0 = 0;                 // channel offset inside `out` (OP_APPLY / OP_RESAMPLE / OP_ZERO)
     int nchan = 0;              // OP_ZERO: channels to clear;  OP_RESAMPLE/OP_APPLY/OP_MAPS: real channels
     int align = 0;              // OP_RESAMPLE: align_corners
@@ -370,10 +370,10 @@ struct Builder {
         // inside an HRModule branch (jkey >= 0) the four CBAM launches take the next depth keys behind the block's two
         // convolutions, so that group_jobs can put the module in depth-major order and merge the convolutions of its branches
         auto key = [&]() { return jkey >= 0 ? jkey++ : -1; };
-        { Op o; o.kind = OP_POOL; o.in = x; o.out = partial; o.jkey = key(); push(o); }
+        { Op o; o.kind = OP_POOL; o.in = x; o.out = partial; o.aux[0] = a0; o.jkey = key(); push(o); }
         { Op o; o.kind = OP_MLP; o.in = partial; o.out = cav; o.aux[0] = a0; o.aux[1] = a1; o.nchan = C; o.terms[0] = x; o.jkey = key(); push(o); }
-        { Op o; o.kind = OP_MAPS; o.in = x; o.terms[1] = cav; o.out = maps; o.nchan = C; o.jkey = key(); push(o); }
-        { Op o; o.kind = OP_APPLY; o.in = x; o.res = res; o.terms[1] = cav; o.terms[2] = maps; o.aux[2] = a2;
+        { Op o; o.kind = OP_MAPS; o.in = x; o.terms[1] = cav; o.out = maps; o.aux[0] = a0; o.nchan = C; o.jkey = key(); push(o); }
+        { Op o; o.kind = OP_APPLY; o.in = x; o.res = res; o.terms[1] = cav; o.terms[2] = maps; o.aux[0] = a0; o.aux[2] = a2;
           o.out = y; o.c0 = y_c0; o.relu = relu; o.nchan = C; o.jkey = key(); push(o); }
     }
     // BasicBlock of seg_hrnet3.py:64-103: conv-bn-relu-conv-bn, CBAM, (+res), relu
@@ -1069,6 +1069,59 @@ ShapePlan shape_decisions(const esahrnet_ctx& c, int n, int h, int w) {
     return sp;
 }
 
+// CBAM's per-pixel maps and their 7x7 attention in one kernel (cbam.hip: cbam_spatial) where the channel-group count allows
+// and the image has at least 32 of its 16 x 32 tiles (measured, batch 32: 128x128x32ch 69 -> 47 us, 256x256x64ch 448 -> 323 us,
+// but 64x64 and smaller lose: too few workgroups, each walking a halo that is mostly padding).  The batch size is
+// deliberately not part of the rule: the kernel serving a layer must not depend on it.
+// slabs per image the stem kernel pools the raw seg_hrnet3 skip tensor into; 0: pool_partial does it (plan without the
+// arrangement, or a crop whose rows make more slabs than the partials tensor reserves)
+int stem_pools(const esahrnet_ctx& c, int height, int width) {
+    if (c.stemraw_partial < 0) return 0;
+    const int slabs = esa::stem_pool_slabs(c.cfg.cin, c.padc(c.cfg.stem_width), height, width);
+    return slabs <= STEM_POOL_SLABS_MAX ? slabs : 0;
+}
+
+bool cbam_fused(const esahrnet_ctx& c, int Cp, int hh, int ww) {
+    return esa::cbam_spatial_supported(Cp) && ((hh + 15) / 16) * ((ww + 31) / 32) >= 32 && !c.opt.cbam_unfused;
+}
+
+// one CBAM launch as a job description (cbam.hip); kind < 0: nothing to launch (the maps formed inside cbam_spatial, the
+// pooling of the raw stem tensor done by the stem kernel)
+esa::CbamJob cbam_job(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, char* ws) {
+    auto T = [&](int t) { return tensor_ptr(c, ws, t); };
+    esa::CbamJob q{};
+    q.kind = -1;
+    const Tensor& tx = c.tensors[o.kind == OP_MLP ? o.terms[0] : o.in];
+    const int hh = sp.lh[tx.level], ww = sp.lw[tx.level];
+    q.ap.N = sp.n; q.ap.H = hh; q.ap.W = ww; q.ap.Cp = tx.Cp; q.ap.C = o.nchan; q.ap.fmt = c.opt.fmt;
+    q.HW = hh * ww; q.P = std::min(Builder::POOL_SLABS, q.HW); q.Cr = o.nchan / 16;
+    switch (o.kind) {
+        case OP_POOL:
+            if (o.out == c.stemraw_partial && stem_pools(c, sp.h, sp.w)) break;       // made by the stem kernel
+            q.kind = esa::CBAM_POOL; q.ap.x = T(o.in); q.partial = reinterpret_cast<float*>(T(o.out)); q.ap.C = tx.C;
+            break;
+        case OP_MLP:
+            q.kind = esa::CBAM_MLP; q.partial = reinterpret_cast<float*>(T(o.in)); q.ca = reinterpret_cast<float*>(T(o.out));
+            q.w0 = c.aux[o.aux[0]].dev; q.w2 = c.aux[o.aux[1]].dev;
+            if (const int slabs = o.in == c.stemraw_partial ? stem_pools(c, sp.h, sp.w) : 0) q.P = slabs;   // the stem kernel's
+            break;
+        case OP_MAPS:
+            if (cbam_fused(c, tx.Cp, hh, ww)) break;
+            q.kind = esa::CBAM_MAPS; q.ap.x = T(o.in); q.ap.ca = reinterpret_cast<const float*>(T(o.terms[1]));
+            q.maps = reinterpret_cast<float*>(T(o.out));
+            break;
+        default: {
+            const Tensor& to = c.tensors[o.out];
+            q.kind = cbam_fused(c, tx.Cp, hh, ww) ? esa::CBAM_SPATIAL : esa::CBAM_APPLY;
+            q.ap.x = T(o.in); q.ap.res = o.res >= 0 ? T(o.res) : nullptr;
+            q.ap.ca = reinterpret_cast<const float*>(T(o.terms[1])); q.ap.maps = reinterpret_cast<const float*>(T(o.terms[2]));
+            q.ap.w_sa = c.aux[o.aux[2]].dev; q.ap.y = T(o.out);
+            q.ap.y_pix_bytes = to.Cp * c.eb(); q.ap.y_c0 = o.c0; q.ap.relu = o.relu;
+        }
+    }
+    return q;
+}
+
 // first-fit interval allocator over op order; tensors die after their last use
 int plan_shape(esahrnet_ctx& c, int n, int h, int w) {
     if (c.sp.n == n && c.sp.h == h && c.sp.w == w && c.sp.keep == c.keep) return 0;
@@ -1085,6 +1138,17 @@ int plan_shape(esahrnet_ctx& c, int n, int h, int w) {
             if (!esa::head_gather_supported(sp.lh[to.level], sp.lw[to.level], zh, zw, to.Cp))
                 return fail("crop %dx%d: the interpolation windows of seg_hrnet3's last_layer[0] do not fit the gather kernel's LDS "
                             "budget (set ESAHRNET_HEAD3_DIRECT=1 before creating the net for the direct 480-channel 3x3)", h, w);
+        } else if (o.kind >= OP_POOL && o.kind <= OP_APPLY) {
+            // a CBAM step, alone or in a merged launch: cbam_job_blocks holds the predicates of every CBAM launcher, and
+            // none of them depends on the batch
+            esa::CbamJob q = cbam_job(c, o, sp, nullptr);
+            if (q.kind >= 0 && esa::cbam_job_blocks(q) < 1) {
+                static const char* steps[] = {"channel pooling", "channel-attention MLP", "spatial maps", "apply", "spatial attention"};
+                const std::string& a = c.aux[o.aux[0]].name;        // "<layer>.ca.fc.0.weight"; the stem skip's has no layer
+                const std::string layer = a.size() > 15 ? "'" + a.substr(0, a.size() - 15) + "'" : "the stem skip";
+                return fail("seg_hrnet3: no kernel serves the CBAM %s of %s at %d channels (%d padded)", steps[q.kind],
+                            layer.c_str(), q.ap.C, q.ap.Cp);
+            }
         }
     const int active_alt = sp.head2 ? 2 : 1;
     struct Free { size_t off, len; };
@@ -1476,59 +1540,6 @@ int esahrnet_workspace_bytes(esahrnet_handle h, int n, int height, int width, si
     return 0;
 }
 
-// CBAM's per-pixel maps and their 7x7 attention in one kernel (cbam.hip: cbam_spatial) where the channel-group count allows
-// and the image has at least 32 of its 16 x 32 tiles (measured, batch 32: 128x128x32ch 69 -> 47 us, 256x256x64ch 448 -> 323 us,
-// but 64x64 and smaller lose: too few workgroups, each walking a halo that is mostly padding).  The batch size is
-// deliberately not part of the rule: the kernel serving a layer must not depend on it.
-// slabs per image the stem kernel pools the raw seg_hrnet3 skip tensor into; 0: pool_partial does it (plan without the
-// arrangement, or a crop whose rows make more slabs than the partials tensor reserves)
-static int stem_pools(const esahrnet_ctx& c, int height, int width) {
-    if (c.stemraw_partial < 0) return 0;
-    const int slabs = esa::stem_pool_slabs(c.cfg.cin, c.padc(c.cfg.stem_width), height, width);
-    return slabs <= STEM_POOL_SLABS_MAX ? slabs : 0;
-}
-
-static bool cbam_fused(const esahrnet_ctx& c, int Cp, int hh, int ww) {
-    return esa::cbam_spatial_supported(Cp) && ((hh + 15) / 16) * ((ww + 31) / 32) >= 32 && !c.opt.cbam_unfused;
-}
-
-// one CBAM launch as a job description (cbam.hip); kind < 0: nothing to launch (the maps formed inside cbam_spatial, the
-// pooling of the raw stem tensor done by the stem kernel)
-static esa::CbamJob cbam_job(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, char* ws) {
-    auto T = [&](int t) { return tensor_ptr(c, ws, t); };
-    esa::CbamJob q{};
-    q.kind = -1;
-    const Tensor& tx = c.tensors[o.kind == OP_MLP ? o.terms[0] : o.in];
-    const int hh = sp.lh[tx.level], ww = sp.lw[tx.level];
-    q.ap.N = sp.n; q.ap.H = hh; q.ap.W = ww; q.ap.Cp = tx.Cp; q.ap.C = o.nchan; q.ap.fmt = c.opt.fmt;
-    q.HW = hh * ww; q.P = std::min(Builder::POOL_SLABS, q.HW); q.Cr = o.nchan / 16;
-    switch (o.kind) {
-        case OP_POOL:
-            if (o.out == c.stemraw_partial && stem_pools(c, sp.h, sp.w)) break;       // made by the stem kernel
-            q.kind = esa::CBAM_POOL; q.ap.x = T(o.in); q.partial = reinterpret_cast<float*>(T(o.out)); q.ap.C = tx.C;
-            break;
-        case OP_MLP:
-            q.kind = esa::CBAM_MLP; q.partial = reinterpret_cast<float*>(T(o.in)); q.ca = reinterpret_cast<float*>(T(o.out));
-            q.w0 = c.aux[o.aux[0]].dev; q.w2 = c.aux[o.aux[1]].dev;
-            if (const int slabs = o.in == c.stemraw_partial ? stem_pools(c, sp.h, sp.w) : 0) q.P = slabs;   // the stem kernel's
-            break;
-        case OP_MAPS:
-            if (cbam_fused(c, tx.Cp, hh, ww)) break;
-            q.kind = esa::CBAM_MAPS; q.ap.x = T(o.in); q.ap.ca = reinterpret_cast<const float*>(T(o.terms[1]));
-            q.maps = reinterpret_cast<float*>(T(o.out));
-            break;
-        default: {
-            const Tensor& to = c.tensors[o.out];
-            q.kind = cbam_fused(c, tx.Cp, hh, ww) ? esa::CBAM_SPATIAL : esa::CBAM_APPLY;
-            q.ap.x = T(o.in); q.ap.res = o.res >= 0 ? T(o.res) : nullptr;
-            q.ap.ca = reinterpret_cast<const float*>(T(o.terms[1])); q.ap.maps = reinterpret_cast<const float*>(T(o.terms[2]));
-            q.ap.w_sa = c.aux[o.aux[2]].dev; q.ap.y = T(o.out);
-            q.ap.y_pix_bytes = to.Cp * c.eb(); q.ap.y_c0 = o.c0; q.ap.relu = o.relu;
-        }
-    }
-    return q;
-}
-
 // kernel and (printf-formatted) label of an op description
 __attribute__((format(printf, 3, 4)))
 static void describe(esahrnet_op_desc* d, const char* kernel, const char* label, ...) {
@@ -1668,8 +1679,12 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
         }
         case OP_TONCHW: {
             const bool f32 = c.tensors[o.in].f32;       // (bf16 mode: the output layer's f32 heat-maps)
+            const int fmt = f32 ? esa::FMT_F32 : c.opt.fmt;
             if (desc) plain(f32 ? "f32_to_nchw" : "sb_to_nchw");
-            else rc = esa::launch_fmt_to_nchw(f32 ? esa::FMT_F32 : c.opt.fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
+            else if (b.part)                            // esahrnet_forward_partials: the same maps plus each tile's maximum
+                rc = esa::launch_to_nchw_part(fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
+                                              static_cast<float*>(b.heat), static_cast<float2*>(b.part), stream);
+            else rc = esa::launch_fmt_to_nchw(fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
                                               static_cast<float*>(b.heat), stream);
             break;
         }
@@ -2000,9 +2015,12 @@ int esahrnet_partial_tiles(esahrnet_handle h, int height, int width, int* ntiles
     if (!h || !ntiles) return fail("partial_tiles: null argument");
     if (!h->committed) return fail("partial_tiles: esahrnet_commit has not been called");
     *ntiles = 0;
-    // only the matrix-core output-layer kernel of the seg_hrnet / seg_hrnet2 plans reports per-tile maxima
+    // seg_hrnet / seg_hrnet2: the matrix-core output-layer kernel reports per-tile maxima, the VALU one none;
+    // seg_hrnet3: the conversion of its heat-maps to NCHW does, in every precision
     if (h->cfg.variant == 0 && h->final_wpk)
         *ntiles = esa::final_part_tiles(h->cfg.num_keypoints, h->cfg.cin, height, width);
+    else if (h->cfg.variant == 1)
+        *ntiles = esa::to_nchw_part_tiles(height, width);
     return 0;
 }
 

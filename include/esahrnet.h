@@ -128,8 +128,9 @@ int esahrnet_keypoints_ex(const void* heat_dev, int n, int k, int height, int wi
  * those instead of sweeping n*K*height*width floats; its results are bit-identical to esahrnet_keypoints_ex on the same
  * heat-maps (same ordering of ties and NaNs, same refinement).  Replaces: `net(x)` followed by get_final / the host peak
  * search (val.py:151-166, inference.py:136-152).
- * esahrnet_partial_tiles: ntiles for a crop size; 0 = this handle cannot (seg_hrnet3, a VALU output layer):
- * use esahrnet_forward + esahrnet_keypoints.  part_dev == NULL makes esahrnet_forward_partials plain esahrnet_forward. */
+ * esahrnet_partial_tiles: ntiles for a crop size; 0 = this handle cannot (seg_hrnet / seg_hrnet2 with a VALU output layer):
+ * use esahrnet_forward + esahrnet_keypoints.  seg_hrnet3 reports them in every precision (its heat-map conversion to NCHW:
+ * runs of 256 row-major pixels per tile).  part_dev == NULL makes esahrnet_forward_partials plain esahrnet_forward. */
 int esahrnet_partial_tiles(esahrnet_handle h, int height, int width, int* ntiles);
 int esahrnet_forward_partials(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* heat_dev,
                               void* part_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
