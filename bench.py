@@ -12,13 +12,16 @@ resident in HBM:  x [B,1,256,256] f32 -> HRNet forward (seg_hrnet2 topology, wid
 Arithmetic: the fp32-grade mode (precision "fp32" = bf16x6, include/esahrnet.h) — configs[1] says fp32; the faster
 split-bf16 mode is an `extras` line, never `value`.
 
-One JSON line on stdout (rank 0), carrying also
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints one JSON line on stdout (rank 0):
+the headline (`value`, `ms_per_step`, `dtype`, `config`), nothing else measured ("full": false; the four blocks below
+and config.launches_per_forward, which the roofline leg counts, are null).  With --full, and only after the timed steps, the line carries also
   "roofline":     dominant kernel (the 3x3 stride-1 bf16x6 MFMA convolution, conv_x6.hip) — algorithmic FLOPs
                   per launch / HIP-event duration per launch, against the bf16x6 ceiling 2500/6 TFLOP/s;
   "cpu_baseline": the CPU oracle (torch-CPU restatement of the reference forward + numpy
                   post-processing) timed on this box's host cores on a bounded sample: batch 1 on all
                   cores (the headline row), batch 1 on one thread and batch 32 on all cores (BASELINE.md §2);
-  "extras" (N = 1 only, all measured AFTER the timed region, none of them is `value`):
+  "kernel_breakdown": per kernel of the roofline leg's forwards: launches, ms, share of the step, TFLOP/s, GB/s;
+  "extras" (N = 1 only, none of them is `value`):
       latency_b1_us        one crop, graph-replayed and eager (the reference calls the net per image, val.py:112)
       sustained            the same step over >= 2000 back-to-back replays (clocks settle under load)
       config3_w48_384_bf16 BASELINE.json configs[3]: HRNet-W48 384x384 batch 64 in the single-pass bf16 mode,
@@ -83,8 +86,11 @@ def parse():
     ap.add_argument("--precision", default=None, choices=["fp32", "bf16x3", "bf16"],
                     help="default: fp32 (fp32-grade bf16x6, BASELINE configs[1]); w48-bf16: bf16; seg_hrnet3: bf16x3")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline leg, the per-kernel breakdown, the extras and "
+                         "the CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of the headline CPU-baseline row")
     ap.add_argument("--sustained-steps", type=int, default=2000)
     ap.add_argument("--profile-steps", type=int, default=3, help="instrumented forwards for the roofline leg")
@@ -342,11 +348,11 @@ def main():
             dump_outputs(args.dump_outputs, {"keypoints": allkp})
 
         roof = breakdown = None
-        if rank == 0:
+        if rank == 0 and args.full:
             roof, breakdown = roofline_leg(net, x, args.profile_steps, precision)
 
         extras = None
-        if rank == 0 and world == 1 and not args.no_extras and args.workload == "w32" and args.variant == "seg_hrnet2" and precision == "fp32":
+        if rank == 0 and world == 1 and args.full and not args.no_extras and args.workload == "w32" and args.variant == "seg_hrnet2" and precision == "fp32":
             extras = {}
             # ---- batch-1 latency (val.py:112 calls the net once per image) --------------------------------------
             x1 = x[:1].clone()
@@ -405,7 +411,7 @@ def main():
                     extras[key] = {"error": f"{type(e).__name__}: {e}"}
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         from oracle import hrnet_ref
         variant_id = 1 if args.variant == "seg_hrnet3" else 0
         cpu = cpu_baseline(sd, hrnet_ref.default_cfg(cin, K, widths=widths, variant=variant_id), args.variant, hw,
@@ -420,7 +426,7 @@ def main():
         line = {
             "metric": f"HRNet-{wname} {hw}x{hw} crops/sec (heatmaps + fused argmax/refine keypoints)",
             "value": round(value, 1), "unit": "crops/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "warmup": args.warmup, "full": args.full, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None,
             "dtype": DTYPES[precision],
             "data": "synthetic",
