@@ -7,9 +7,11 @@
 // (8+2)x(32+2) concat tile in LDS (bilinear taps taken straight from the half-resolution SB
 // tensor, raw input straight from the caller's NCHW crop) and runs the (K+cin)*9*K MACs per
 // pixel on the f32 VALU with wave-uniform (scalar) weights.  K*(K+cin)*9 = 1188 MACs per pixel
-// for the 11-keypoint variant: 0.5 % of the network, HBM-write-bound (K*4 B per pixel out).
+// for the 11-keypoint variant: 0.5 % of the network.  Not HBM-write-bound: without its stores (the keypoints-only form) it is
+// no faster.
 #include "devstate.h"
 #include "kernels.h"
+#include "refine.h"
 #include "sb.h"
 
 namespace esa {
@@ -45,9 +47,82 @@ __device__ __forceinline__ LerpT lerp_ac_scaled(int dst, int in, float scale) { 
     return r;
 }
 
+// ---- the per-pixel arithmetic of the output layer, shared by final_kernel and the keypoints-only finish (final_kp_finish_kernel
+// evaluates single pixels with these very functions, so that its values are the bits final_kernel stores) ------------------
+// ATen align_corners=True: scale = (in-1)/(out-1), src = scale*dst — the two divisions once per thread, not per unit
+__device__ __forceinline__ float final_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
+// concat channels c8 * 8 .. + 7 (up-sampled keypoint channels) of output pixel (gy, gx) of image n; zeros outside the crop
+__device__ __forceinline__ void final_stage8(const FinalParams& p, int n, int gy, int gx, int c8, float sc_y, float sc_x, float v[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = 0.f;
+    if (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) {
+        const LerpT ly = lerp_ac_scaled(gy, p.h, sc_y), lx = lerp_ac_scaled(gx, p.wd, sc_x);
+        const size_t r0 = ((size_t)n * p.h + ly.i0) * p.wd, r1 = ((size_t)n * p.h + ly.i1) * p.wd;
+        const size_t ps = (size_t)p.Cp * (p.fmt == FMT_BF ? 2 : 4);
+        float v00[8], v01[8], v10[8], v11[8];
+        auto ld = [&](size_t pix, float v_[8]) {
+            if (p.fmt == FMT_BF) {
+                unpack8_bf16(*reinterpret_cast<const uint4*>(p.h3 + pix * ps + c8 * 16), v_);
+            } else if (p.fmt == FMT_F32) {
+                const float* a = reinterpret_cast<const float*>(p.h3 + pix * ps) + c8 * 8;
+                const f32x4 a0 = *reinterpret_cast<const f32x4*>(a), a1 = *reinterpret_cast<const f32x4*>(a + 4);
+                v_[0] = a0[0]; v_[1] = a0[1]; v_[2] = a0[2]; v_[3] = a0[3]; v_[4] = a1[0]; v_[5] = a1[1]; v_[6] = a1[2]; v_[7] = a1[3];
+            } else {
+                const char* a = p.h3 + pix * ps + c8 * 32;
+                join8(*reinterpret_cast<const uint4*>(a), *reinterpret_cast<const uint4*>(a + 16), v_);
+            }
+        };
+        ld(r0 + lx.i0, v00);
+        ld(r0 + lx.i1, v01);
+        ld(r1 + lx.i0, v10);
+        ld(r1 + lx.i1, v11);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            v[i] = ly.l0 * (lx.l0 * v00[i] + lx.l1 * v01[i]) + ly.l1 * (lx.l0 * v10[i] + lx.l1 * v11[i]);
+    }
+}
+// raw input channel ci of output pixel (gy, gx) of image n; zero outside the crop
+__device__ __forceinline__ float final_stage_raw(const FinalParams& p, int n, int ci, int gy, int gx) {
+    float v = 0.f;
+    if (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W)
+        v = p.x0[(((size_t)n * p.cin + ci) * p.H + gy) * p.W + gx];
+    return v;
+}
+
 // RPT = 2: the two pixels of a thread share 12 of their 18 tile reads per channel and every weight, and their
 // multiply-adds pair up as v_pk_fma_f32 (same order per pixel as RPT = 1) — 102 -> ~60 us at W32 256^2.
-template <int KT, int RPT>
+// The workgroup's first maximum of every heat-map over its tile, from red[k][q] = the value of heat-map k at tile pixel q (row
+// * FTW + column; the staging tile's LDS, free once every wave has left the compute loop): one wave per heat-map, its lanes
+// over the pixels, then a wave reduction.  argmax_take does not depend on the order of its steps, so any tiling and any
+// reduction order leaves the maximum the full sweep finds.
+template <int RPT>
+__device__ __forceinline__ void final_tile_max(const FinalParams& p, const float* red, int tiles_x, int tiles_y) {
+    constexpr int NP = FTW * 8 * RPT;
+    const int lane = threadIdx.x & 63;
+    const int ntiles = tiles_x * tiles_y, tile = (int)(blockIdx.x % (unsigned)ntiles), n = (int)(blockIdx.x / (unsigned)ntiles);
+    const int oy0 = tile / tiles_x * (8 * RPT), ox0 = tile % tiles_x * FTW;
+    for (int k = threadIdx.x >> 6; k < p.K; k += 4) {
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < NP / 64; ++j) {
+            const int q = lane + 64 * j, oy = oy0 + q / FTW, ox = ox0 + q % FTW;
+            if (oy < p.H && ox < p.W) argmax_take(red[k * NP + q], oy * p.W + ox, bv, bi);
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const float ov = __shfl_xor(bv, off);
+            const int oi = __shfl_xor(bi, off);
+            argmax_take(ov, oi, bv, bi);
+        }
+        if (lane == 0) p.part[((size_t)n * p.K + k) * (size_t)ntiles + tile] = make_float2(bv, __int_as_float(bi));
+    }
+}
+
+// KP (esahrnet_forward_keypoints): nothing is stored; each heat-map's first maximum over the tile goes to
+// p.part[(n * K + k) * ntiles + tile] (final_tile_max), final_kp_finish_kernel finishes from there.  The tile's LDS holds the
+// K x 256 * RPT values: K * 256 * RPT <= (K + cin) * (8 * RPT + 2) * FROW for every K >= 1.
+template <int KT, int RPT, bool KP>
 __global__ __launch_bounds__(256) void final_kernel(FinalParams p, int tiles_x, int tiles_y) {
     constexpr int FTH = 8 * RPT, FIH = FTH + 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -61,41 +136,14 @@ __global__ __launch_bounds__(256) void final_kernel(FinalParams p, int tiles_x, 
 
     // ---- stage: up-sampled keypoint channels, 8 at a time per thread ------------------------
     constexpr int G = (KT + 7) >> 3;        // (K <= KT: groups past K hold nothing the compute loop reads)
-    // ATen align_corners=True: scale = (in-1)/(out-1), src = scale*dst — the two divisions once per thread, not per unit
-    const float sc_y = p.H > 1 ? (float)(p.h - 1) / (float)(p.H - 1) : 0.f, sc_x = p.W > 1 ? (float)(p.wd - 1) / (float)(p.W - 1) : 0.f;
+    const float sc_y = final_scale(p.h, p.H), sc_x = final_scale(p.wd, p.W);
     for (int u = threadIdx.x; u < FIH * FIW * G; u += 256) {
         const int c8 = u % G;
         const int q = u / G;
         const int py = q / FIW, px = q - py * FIW;
         const int gy = oy0 - 1 + py, gx = ox0 - 1 + px;
         float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = 0.f;
-        if (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) {
-            const LerpT ly = lerp_ac_scaled(gy, p.h, sc_y), lx = lerp_ac_scaled(gx, p.wd, sc_x);
-            const size_t r0 = ((size_t)n * p.h + ly.i0) * p.wd, r1 = ((size_t)n * p.h + ly.i1) * p.wd;
-            const size_t ps = (size_t)p.Cp * (p.fmt == FMT_BF ? 2 : 4);
-            float v00[8], v01[8], v10[8], v11[8];
-            auto ld = [&](size_t pix, float v_[8]) {
-                if (p.fmt == FMT_BF) {
-                    unpack8_bf16(*reinterpret_cast<const uint4*>(p.h3 + pix * ps + c8 * 16), v_);
-                } else if (p.fmt == FMT_F32) {
-                    const float* a = reinterpret_cast<const float*>(p.h3 + pix * ps) + c8 * 8;
-                    const f32x4 a0 = *reinterpret_cast<const f32x4*>(a), a1 = *reinterpret_cast<const f32x4*>(a + 4);
-                    v_[0] = a0[0]; v_[1] = a0[1]; v_[2] = a0[2]; v_[3] = a0[3]; v_[4] = a1[0]; v_[5] = a1[1]; v_[6] = a1[2]; v_[7] = a1[3];
-                } else {
-                    const char* a = p.h3 + pix * ps + c8 * 32;
-                    join8(*reinterpret_cast<const uint4*>(a), *reinterpret_cast<const uint4*>(a + 16), v_);
-                }
-            };
-            ld(r0 + lx.i0, v00);
-            ld(r0 + lx.i1, v01);
-            ld(r1 + lx.i0, v10);
-            ld(r1 + lx.i1, v11);
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                v[i] = ly.l0 * (lx.l0 * v00[i] + lx.l1 * v01[i]) + ly.l1 * (lx.l0 * v10[i] + lx.l1 * v11[i]);
-        }
+        final_stage8(p, n, gy, gx, c8, sc_y, sc_x, v);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int c = c8 * 8 + i;
@@ -107,11 +155,7 @@ __global__ __launch_bounds__(256) void final_kernel(FinalParams p, int tiles_x, 
         const int px = u % FIW;
         const int r = u / FIW;
         const int py = r % FIH, ci = r / FIH;
-        const int gy = oy0 - 1 + py, gx = ox0 - 1 + px;
-        float v = 0.f;
-        if (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W)
-            v = p.x0[(((size_t)n * p.cin + ci) * p.H + gy) * p.W + gx];
-        tile[((p.K + ci) * FIH + py) * FROW + px] = v;
+        tile[((p.K + ci) * FIH + py) * FROW + px] = final_stage_raw(p, n, ci, oy0 - 1 + py, ox0 - 1 + px);
     }
     __syncthreads();
 
@@ -140,6 +184,18 @@ __global__ __launch_bounds__(256) void final_kernel(FinalParams p, int tiles_x, 
             }
         }
         const int ox = ox0 + lx;
+        if constexpr (KP) {
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < KT; ++k)
+                if (k < p.K) {
+                    tile[k * (FTW * FTH) + lyy * FTW + lx] = acc[k][0];
+                    tile[k * (FTW * FTH) + (lyy + 1) * FTW + lx] = acc[k][1];
+                }
+            __syncthreads();
+            final_tile_max<RPT>(p, tile, tiles_x, tiles_y);
+            return;
+        }
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
             const int oy = oy0 + lyy + rr;
@@ -164,6 +220,15 @@ __global__ __launch_bounds__(256) void final_kernel(FinalParams p, int tiles_x, 
             }
         }
         const int oy = oy0 + lyy, ox = ox0 + lx;
+        if constexpr (KP) {
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < KT; ++k)
+                if (k < p.K) tile[k * (FTW * FTH) + lyy * FTW + lx] = acc[k];
+            __syncthreads();
+            final_tile_max<RPT>(p, tile, tiles_x, tiles_y);
+            return;
+        }
         if (oy < p.H && ox < p.W) {
 #pragma unroll
             for (int k = 0; k < KT; ++k)
@@ -171,24 +236,71 @@ __global__ __launch_bounds__(256) void final_kernel(FinalParams p, int tiles_x, 
         }
     }
 }
-template <int KT, int RPT>
+template <int KT, int RPT, bool KP = false>
 int launch_final_rt(const FinalParams& p, hipStream_t stream) {
     constexpr int FTH = 8 * RPT, FIH = FTH + 2;
     const int tiles_x = (p.W + FTW - 1) / FTW, tiles_y = (p.H + FTH - 1) / FTH;
     const long long nblk = (long long)p.N * tiles_x * tiles_y;
     if (nblk <= 0 || nblk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     const size_t lds = (size_t)(p.K + p.cin) * FIH * FROW * sizeof(float);
-    auto kern = final_kernel<KT, RPT>;
+    auto kern = final_kernel<KT, RPT, KP>;
     if (const int e_ = ensure_dyn_lds(reinterpret_cast<const void*>(kern), 64 * 1024)) return e_;
     if (lds > 64 * 1024) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, stream, p, tiles_x, tiles_y);
     return (int)hipGetLastError();
 }
-template <int KT>
+// two rows per thread where the 18-row tile fits the 64 KB the kernel may ask for (same multiply-add order either way)
+inline int final_rpt(int K, int cin, int KT) { return (size_t)(K + cin) * 18 * FROW * sizeof(float) <= 64 * 1024 && KT <= 16 ? 2 : 1; }
+template <int KT, bool KP = false>
 int launch_final_t(const FinalParams& p, hipStream_t stream) {
-    // two rows per thread where the 18-row tile fits the 64 KB the kernel may ask for (same multiply-add order either way)
-    if ((size_t)(p.K + p.cin) * 18 * FROW * sizeof(float) <= 64 * 1024 && KT <= 16) return launch_final_rt<KT, 2>(p, stream);
-    return launch_final_rt<KT, 1>(p, stream);
+    if (final_rpt(p.K, p.cin, KT) == 2) return launch_final_rt<KT, 2, KP>(p, stream);
+    return launch_final_rt<KT, 1, KP>(p, stream);
+}
+
+// ---- keypoints-only finish of the VALU output layer (esahrnet_forward_keypoints) --------------------------------------
+// One wave per heat-map: the first maximum over final_kernel<KT, RPT, true>'s tile maxima, then the heat-map values the refine reads (the
+// peak and its +-1 / +-2 neighbours in x and y, refine.h's numbering) are evaluated again, pixel by pixel, with the arithmetic
+// of final_kernel: the same staging functions (final_stage8 / final_stage_raw, zeros outside the crop), then acc = bias[k] and
+// one fma per (channel, tap) in final_kernel's order.  81 (pixel, tap) slots x (K + cin) channels of LDS.
+constexpr int FKP_MAXC = 40;        // K + cin the finish stages (K <= 32)
+__global__ __launch_bounds__(64) void final_kp_finish_kernel(FinalParams p, int kt, int ntiles, float* kp, int* idx_out) {
+    __shared__ float sv[81][FKP_MAXC];
+    __shared__ float spt[9];
+    const int plane = blockIdx.x, n = plane / p.K, k = plane - n * p.K;
+    float bv;
+    int bi;
+    reduce_tile_maxima(p.part + (size_t)plane * ntiles, ntiles, bv, bi);
+    const int b0 = bi == 0x7fffffff ? 0 : bi, px = b0 % p.W, py = b0 / p.W;
+    const int npt = 1 < px && px < p.W - 2 && 1 < py && py < p.H - 2 ? 9 : 1;     // refine_keypoint reads the 8 others only then
+    const int G = (p.K + 7) >> 3, U = G + p.cin, CT = p.K + p.cin;
+    const float sc_y = final_scale(p.h, p.H), sc_x = final_scale(p.wd, p.W);
+    for (int u = threadIdx.x; u < npt * 9 * U; u += 64) {
+        const int j = u % U, slot = u / U, pt = slot / 9, tap = slot - pt * 9;
+        const int gy = py + refine_point_dy(pt) - 1 + tap / 3, gx = px + refine_point_dx(pt) - 1 + tap % 3;
+        if (j < G) {
+            float v[8];
+            final_stage8(p, n, gy, gx, j, sc_y, sc_x, v);
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if (j * 8 + i < p.K) sv[slot][j * 8 + i] = v[i];
+        } else {
+            sv[slot][p.K + j - G] = final_stage_raw(p, n, j - G, gy, gx);
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < npt) {
+        float acc = p.bias[k];
+        for (int c = 0; c < CT; ++c) {
+            const float* wp = p.w + (size_t)c * 9 * kt;
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) acc = fmaf(sv[threadIdx.x * 9 + tap][c], wp[tap * kt + k], acc);
+        }
+        spt[threadIdx.x] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        refine_keypoint([&](int yy, int xx) { return spt[refine_point_of(yy - py, xx - px)]; }, p.H, p.W, bi,
+                        kp + (size_t)plane * 3, idx_out ? idx_out + plane : nullptr);
 }
 
 
@@ -465,6 +577,28 @@ void pack_final_mfma(const float* w, int K, int cin, void* dst) {
                     d[base + l * 8 + j] = hi;
                     d[base + 512 + l * 8 + j] = lo;
                 }
+}
+
+int final_kp_tiles(int K, int cin, int H, int W) {
+    const int kt = final_kt(K);
+    if (kt < 0 || H <= 0 || W <= 0) return 0;
+    return ((W + FTW - 1) / FTW) * ((H + 8 * final_rpt(K, cin, kt) - 1) / (8 * final_rpt(K, cin, kt)));
+}
+
+int launch_final_kp(const FinalParams& p, float* kp, int* idx_out, hipStream_t stream) {
+    const int ntiles = final_kp_tiles(p.K, p.cin, p.H, p.W), kt = final_kt(p.K);
+    const long long planes = (long long)p.N * p.K;
+    if (!p.part || !kp || ntiles <= 0 || p.K + p.cin > FKP_MAXC || planes > 0x7fffffffLL || (long long)p.H * p.W > 0x7fffffffLL)
+        return (int)hipErrorInvalidValue;
+    int rc = (int)hipErrorInvalidValue;
+    switch (kt) {
+        case 11: rc = launch_final_t<11, true>(p, stream); break;
+        case 16: rc = launch_final_t<16, true>(p, stream); break;
+        case 32: rc = launch_final_t<32, true>(p, stream); break;
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(final_kp_finish_kernel, dim3((unsigned)planes), dim3(64), 0, stream, p, kt, ntiles, kp, idx_out);
+    return (int)hipGetLastError();
 }
 
 int launch_final(const FinalParams& p, hipStream_t stream) {

@@ -155,9 +155,14 @@ struct FinalParams {
     int N, H, W, h, wd; // h,wd = resolution of h3
     int K, cin, Cp;
     int fmt;            // format of h3 (FMT_F32: VALU kernel only)
-    float2* part;       // optional (MFMA kernel only): [N*K][final_part_tiles] (value, index bits) of every tile's first maximum
+    float2* part;       // optional (MFMA kernel only): [N*K][final_part_tiles] (value, index bits) of every tile's first maximum;
+                        // launch_final_kp: [N*K][final_kp_tiles], its scratch
 };
 int launch_final(const FinalParams& p, hipStream_t stream);
+// keypoints without heat-maps, VALU output layer (final_kernel<KT, RPT, true> + final_kp_finish_kernel): kp f32 [N*K][3], idx_out int32
+// [N*K] or nullptr, bit-identical to launch_final (VALU) + launch_keypoints; p.out is not used
+int final_kp_tiles(int K, int cin, int H, int W);
+int launch_final_kp(const FinalParams& p, float* kp, int* idx_out, hipStream_t stream);
 // tiles per heat-map the MFMA output-layer kernel reports partial maxima for; 0: that kernel does not serve (K, cin)
 int final_part_tiles(int K, int cin, int H, int W);
 // (v, i) beats (bv, bi) if it is larger — NaN counting as larger than every number — or equal with a lower index
@@ -294,6 +299,10 @@ int launch_keypoints(const float* heat, int planes, int H, int W, float* kp, int
 // same result from the per-tile maxima of the output-layer kernel (FinalParams::part, `ntiles` pairs per plane)
 int launch_keypoints_finish(const float* heat, const float2* part, int ntiles, int planes, int H, int W, float* kp, int* idx_out,
                             hipStream_t stream);
+// the same finish on NHWC heat-maps x [N][H][W][Cp] (fmt FMT_SB or FMT_F32) that were never converted to NCHW; part from
+// launch_tile_max, planes = N * C
+int launch_keypoints_finish_nhwc(int fmt, const char* x, int N, int C, int H, int W, int Cp, const float2* part, int ntiles,
+                                 float* kp, int* idx_out, hipStream_t stream);
 
 // ---- crop + edge-pad + 8-bit bilinear resize + normalise: u8 frames -> f32 [N][1][S][S] (crops.hip) ----
 int launch_crops(const unsigned char* frames, const int* boxes, float* out, int N, int FH, int FW, int S,
@@ -315,5 +324,7 @@ int launch_fmt_to_nchw(int fmt, const char* x, int N, int C, int H, int W, int C
 // index bits) as keypoints_finish reads it; C <= 32
 int to_nchw_part_tiles(int H, int W);
 int launch_to_nchw_part(int fmt, const char* x, int N, int C, int H, int W, int Cp, float* y, float2* part, hipStream_t s);
+// the same per-tile maxima without the NCHW copy
+int launch_tile_max(int fmt, const char* x, int N, int C, int H, int W, int Cp, float2* part, hipStream_t s);
 
 }  // namespace esa

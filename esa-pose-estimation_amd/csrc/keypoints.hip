@@ -11,41 +11,17 @@
 // FIRST NaN's index, the reported peak is NaN, and the refinement falls through (np.maximum(hm, 1e-10) and
 // math.log propagate the NaN, `offset < 1` is then false): integer coordinates of the first NaN, peak NaN.
 #include "kernels.h"
+#include "refine.h"
+#include "sb.h"
 
 namespace esa {
 namespace {
 
 __device__ __forceinline__ void take(float v, int i, float& bv, int& bi) { argmax_take(v, i, bv, bi); }      // kernels.h
 
-// integer peak (bi) of plane `pl` -> sub-pixel keypoint: the 9-tap log-quadratic offset in f64 exactly as the
-// reference's Python floats do (inference.py:75-94, 136-152)
+// integer peak (bi) of plane `pl` -> sub-pixel keypoint (refine.h)
 __device__ __forceinline__ void refine_and_store(const float* pl, int H, int W, int bi, float* kp3, int* idx_slot) {
-    if (bi == 0x7fffffff) bi = 0;                        // all-NaN / all -inf plane
-    const int px = bi % W, py = bi / W;
-    float fx = (float)px, fy = (float)py;
-    if (1 < px && px < W - 2 && 1 < py && py < H - 2) {   // inference.py:81
-        // np.maximum(hm, 1e-10) of inference.py:141 (NaN-propagating, unlike fmaxf), then math.log in f64
-        auto lg = [&](int yy, int xx) {
-            const float v = pl[yy * W + xx];
-            return log((double)(v < 1e-10f ? 1e-10f : v));
-        };
-        const double c = lg(py, px);
-        const double hx = 0.5 * (lg(py, px + 1) - lg(py, px - 1));
-        const double hy = 0.5 * (lg(py + 1, px) - lg(py - 1, px));
-        const double hxx = 0.25 * (lg(py, px + 2) - 2 * c + lg(py, px - 2));
-        const double hyy = 0.25 * (lg(py + 2, px) - 2 * c + lg(py - 2, px));
-        if (hxx != 0 && hyy != 0) {
-            const double ox = -hx / hxx, oy = -hy / hyy;
-            if (ox < 1 && oy < 1) {                        // signed, both-or-neither (:92)
-                fx = (float)((double)fx + ox);
-                fy = (float)((double)fy + oy);
-            }
-        }
-    }
-    kp3[0] = fx;
-    kp3[1] = fy;
-    kp3[2] = pl[bi];
-    if (idx_slot) *idx_slot = bi;
+    refine_keypoint([=](int yy, int xx) { return pl[yy * W + xx]; }, H, W, bi, kp3, idx_slot);
 }
 
 constexpr int KT = 1024;        // 16 waves per plane: the sweep is latency-bound, it wants loads in flight
@@ -90,21 +66,36 @@ __global__ __launch_bounds__(KT) void keypoints_kernel(const float* heat, int H,
 // the 92 MB of heat-maps of a 32-crop batch are not read a second time.
 __global__ __launch_bounds__(64) void keypoints_finish_kernel(const float* heat, const float2* part, int ntiles, int H, int W,
                                                               float* kp, int* idx_out) {
-    const float2* pp = part + (size_t)blockIdx.x * ntiles;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int t = threadIdx.x; t < ntiles; t += 64) {
-        const float2 q = pp[t];
-        take(q.x, __float_as_int(q.y), bv, bi);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_xor(bv, off);
-        const int oi = __shfl_xor(bi, off);
-        take(ov, oi, bv, bi);
-    }
+    float bv;
+    int bi;
+    reduce_tile_maxima(part + (size_t)blockIdx.x * ntiles, ntiles, bv, bi);
     if (threadIdx.x == 0)
         refine_and_store(heat + (size_t)blockIdx.x * H * W, H, W, bi, kp + (size_t)blockIdx.x * 3, idx_out ? idx_out + blockIdx.x : nullptr);
+}
+
+// The same finish for heat-maps that never leave the workspace's NHWC layout (seg_hrnet3 under esahrnet_forward_keypoints,
+// the maxima from layout.hip's tile-maximum kernel): the refine reads its values straight from the f32 / SB tensor x
+// [N][H][W][Cp], decoded by join8_fmt exactly as the conversion to NCHW decodes them.
+template <bool F32>
+__global__ __launch_bounds__(64) void keypoints_finish_nhwc_kernel(const char* x, int C, int Cp, const float2* part, int ntiles,
+                                                                   int H, int W, float* kp, int* idx_out) {
+    float bv;
+    int bi;
+    reduce_tile_maxima(part + (size_t)blockIdx.x * ntiles, ntiles, bv, bi);
+    if (threadIdx.x == 0) {
+        const int n = (int)(blockIdx.x / (unsigned)C), c = (int)(blockIdx.x % (unsigned)C), j = c & 7;
+        const char* img = x + (size_t)n * ((size_t)H * W * Cp * 4) + (c >> 3) * 32;
+        auto at = [=](int yy, int xx) {
+            float v[8];
+            load8_fmt(img + (size_t)(yy * W + xx) * (Cp * 4), v, F32);
+            float r = v[0];
+#pragma unroll
+            for (int i = 1; i < 8; ++i)
+                if (j == i) r = v[i];          // (no run-time index into v: it would live in scratch memory)
+            return r;
+        };
+        refine_keypoint(at, H, W, bi, kp + (size_t)blockIdx.x * 3, idx_out ? idx_out + blockIdx.x : nullptr);
+    }
 }
 
 }  // namespace
@@ -113,6 +104,17 @@ int launch_keypoints_finish(const float* heat, const float2* part, int ntiles, i
                             hipStream_t stream) {
     if (planes <= 0 || ntiles <= 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(keypoints_finish_kernel, dim3((unsigned)planes), dim3(64), 0, stream, heat, part, ntiles, H, W, kp, idx_out);
+    return (int)hipGetLastError();
+}
+
+int launch_keypoints_finish_nhwc(int fmt, const char* x, int N, int C, int H, int W, int Cp, const float2* part, int ntiles,
+                                 float* kp, int* idx_out, hipStream_t stream) {
+    const long long planes = (long long)N * C;
+    if (N <= 0 || C < 1 || C > Cp || (Cp & 7) || ntiles <= 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL ||
+        planes > 0x7fffffffLL || (fmt != FMT_SB && fmt != FMT_F32))
+        return (int)hipErrorInvalidValue;
+    auto kern = fmt == FMT_F32 ? keypoints_finish_nhwc_kernel<true> : keypoints_finish_nhwc_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)planes), dim3(64), 0, stream, x, C, Cp, part, ntiles, H, W, kp, idx_out);
     return (int)hipGetLastError();
 }
 

@@ -115,7 +115,9 @@ __global__ __launch_bounds__(256) void f32_to_nchw_kernel(const float* x, int C,
 // through argmax_take, whose order does not depend on the order of the steps: the finish over these runs picks what the
 // full sweep picks.  Eight waves per workgroup: with 33 KB of LDS four workgroups fit a CU, and those fill it.
 constexpr int TONCHW_TP = 256, TONCHW_NT = 512;
-template <bool F32>
+// STORE = false (seg_hrnet3 under esahrnet_forward_keypoints): the maxima only, no NCHW copy — the heat-maps stay in the
+// workspace and keypoints_finish_nhwc_kernel refines from there; read-bound, Cp * 4 bytes per pixel
+template <bool F32, bool STORE>
 __global__ __launch_bounds__(TONCHW_NT) void to_nchw_part_kernel(const char* x, int C, int hw, int Cp, float* y, float2* part,
                                                                  int ntiles) {
     __shared__ float s[32][TONCHW_TP + 2];         // C <= 32 planes; (+2: a wave's 8-channel groups write to different banks)
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(TONCHW_NT) void to_nchw_part_kernel(const char* x, 
     __syncthreads();
     const int lane = tid & 63;
     for (int c = tid >> 6; c < C; c += TONCHW_NT / 64) {     // plane c: one wave
-        float* o = y + ((size_t)n * C + c) * hw + q0;
+        float* o = STORE ? y + ((size_t)n * C + c) * hw + q0 : nullptr;
         float bv = -INFINITY;
         int bi = 0x7fffffff;
 #pragma unroll
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(TONCHW_NT) void to_nchw_part_kernel(const char* x, 
             const int p = lane + r * 64;
             if (p < np) {
                 const float v = s[c][p];
-                o[p] = v;
+                if constexpr (STORE) o[p] = v;
                 argmax_take(v, q0 + p, bv, bi);
             }
         }
@@ -168,7 +170,6 @@ __global__ __launch_bounds__(TONCHW_NT) void to_nchw_part_kernel(const char* x, 
         if (lane == 0) part[((size_t)n * C + c) * ntiles + tile] = make_float2(bv, __int_as_float(bi));
     }
 }
-
 }  // namespace
 
 int to_nchw_part_tiles(int H, int W) {
@@ -181,8 +182,18 @@ int launch_to_nchw_part(int fmt, const char* x, int N, int C, int H, int W, int 
     const long long nblk = (long long)N * ntiles;
     if (ntiles <= 0 || N <= 0 || nblk > 0x7fffffffLL || C < 1 || C > 32 || C > Cp || (Cp & 7) || (fmt != FMT_SB && fmt != FMT_F32))
         return (int)hipErrorInvalidValue;
-    auto kern = fmt == FMT_F32 ? to_nchw_part_kernel<true> : to_nchw_part_kernel<false>;
+    auto kern = fmt == FMT_F32 ? to_nchw_part_kernel<true, true> : to_nchw_part_kernel<false, true>;
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(TONCHW_NT), 0, s, x, C, H * W, Cp, y, part, ntiles);
+    return (int)hipGetLastError();
+}
+
+int launch_tile_max(int fmt, const char* x, int N, int C, int H, int W, int Cp, float2* part, hipStream_t s) {
+    const int ntiles = to_nchw_part_tiles(H, W);
+    const long long nblk = (long long)N * ntiles;
+    if (ntiles <= 0 || N <= 0 || nblk > 0x7fffffffLL || C < 1 || C > 32 || C > Cp || (Cp & 7) || (fmt != FMT_SB && fmt != FMT_F32))
+        return (int)hipErrorInvalidValue;
+    auto kern = fmt == FMT_F32 ? to_nchw_part_kernel<true, false> : to_nchw_part_kernel<false, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(TONCHW_NT), 0, s, x, C, H * W, Cp, nullptr, part, ntiles);
     return (int)hipGetLastError();
 }
 

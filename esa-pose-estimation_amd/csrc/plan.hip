@@ -1556,7 +1556,34 @@ struct Buffers {
     void* heat;
     char* ws;
     void* part;
+    // esahrnet_forward_keypoints: the last op (OP_FINAL / OP_TONCHW) writes keypoints instead of heat-maps (heat == nullptr),
+    // through the scratch behind the forward's workspace (KpScratch)
+    float* kp = nullptr;
+    int* idx = nullptr;
+    float* kheat = nullptr;
+    float2* kpart = nullptr;
 };
+
+// What esahrnet_forward_keypoints keeps behind the forward's workspace (at ShapePlan::bytes, a multiple of 256): the per-tile
+// maxima of the output layer and, where that is the matrix-core kernel, its heat-maps (that kernel writes them in any case)
+struct KpScratch {
+    int ntiles = 0;
+    size_t heat = 0, part = 0;
+};
+static KpScratch kp_scratch(const esahrnet_ctx& c, int n, int height, int width) {
+    KpScratch s;
+    const int K = c.cfg.num_keypoints;
+    if (c.cfg.variant == 1) {
+        s.ntiles = esa::to_nchw_part_tiles(height, width);
+    } else if (c.opt.final_mfma) {
+        s.ntiles = esa::final_part_tiles(K, c.cfg.cin, height, width);
+        s.heat = ((size_t)n * K * height * width * 4 + 255) & ~(size_t)255;
+    } else {
+        s.ntiles = esa::final_kp_tiles(K, c.cfg.cin, height, width);
+    }
+    s.part = ((size_t)n * K * s.ntiles * 8 + 255) & ~(size_t)255;
+    return s;
+}
 
 // Op `o` at the shape `sp` decided: every dispatch decision is made here, once, and the launch parameters are built once.
 // desc == nullptr: the op is launched on `stream`.  Otherwise nothing is launched and `desc` (zeroed by the caller) names
@@ -1681,7 +1708,13 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             const bool f32 = c.tensors[o.in].f32;       // (bf16 mode: the output layer's f32 heat-maps)
             const int fmt = f32 ? esa::FMT_F32 : c.opt.fmt;
             if (desc) plain(f32 ? "f32_to_nchw" : "sb_to_nchw");
-            else if (b.part)                            // esahrnet_forward_partials: the same maps plus each tile's maximum
+            else if (b.kp) {                            // esahrnet_forward_keypoints: maxima and refine on the NHWC maps
+                const int K = c.cfg.num_keypoints, Cp = c.tensors[o.in].Cp;
+                rc = esa::launch_tile_max(fmt, T(o.in), n, K, height, width, Cp, b.kpart, stream);
+                if (!rc)
+                    rc = esa::launch_keypoints_finish_nhwc(fmt, T(o.in), n, K, height, width, Cp, b.kpart,
+                                                           esa::to_nchw_part_tiles(height, width), b.kp, b.idx, stream);
+            } else if (b.part)                            // esahrnet_forward_partials: the same maps plus each tile's maximum
                 rc = esa::launch_to_nchw_part(fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
                                               static_cast<float*>(b.heat), static_cast<float2*>(b.part), stream);
             else rc = esa::launch_fmt_to_nchw(fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
@@ -1912,6 +1945,17 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 describe(desc, "final_kernel", "%s", s.name.c_str());
                 desc->flops = 2.0 * n * height * width * s.cout * s.cin * 9;
                 desc->bytes = tbytes(o.in) + (double)n * height * width * (c.cfg.cin + s.cout) * 4;
+            } else if (b.kp && !c.final_wpk) {         // esahrnet_forward_keypoints, VALU output layer: no heat-maps at all
+                p.out = nullptr;
+                p.part = b.kpart;
+                rc = esa::launch_final_kp(p, b.kp, b.idx, stream);
+            } else if (b.kp) {                          // ... matrix-core output layer: heat-maps and maxima into the scratch
+                p.out = b.kheat;
+                p.part = b.kpart;
+                rc = esa::launch_final(p, stream);
+                if (!rc)
+                    rc = esa::launch_keypoints_finish(p.out, p.part, esa::final_part_tiles(p.K, p.cin, height, width), n * p.K,
+                                                      height, width, b.kp, b.idx, stream);
             } else rc = esa::launch_final(p, stream);
             break;
         }
@@ -1920,16 +1964,25 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
     return 0;
 }
 
+// kp_dev != nullptr: esahrnet_forward_keypoints (heat_dev and part_dev unused)
 static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, int width,
                        void* heat_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream_,
-                       hipEvent_t* events, void* part_dev = nullptr) {
-    if (!h || !x_dev || !heat_dev || !ws_dev) return fail("forward: null argument");
+                       hipEvent_t* events, void* part_dev = nullptr, void* kp_dev = nullptr, void* idx_dev = nullptr) {
+    if (!h || !x_dev || !(heat_dev || kp_dev) || !ws_dev) return fail("forward: null argument");
     if (!h->committed) return fail("forward: esahrnet_commit has not been called");
     if (plan_shape(*h, n, height, width)) return 1;
-    if (ws_bytes < h->sp.bytes) return fail("forward: workspace too small (%zu < %zu)", ws_bytes, h->sp.bytes);
+    const KpScratch ks = kp_dev ? kp_scratch(*h, n, height, width) : KpScratch{};
+    const size_t need = h->sp.bytes + ks.heat + ks.part;
+    if (ws_bytes < need) return fail("forward: workspace too small (%zu < %zu)", ws_bytes, need);
     if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("forward: workspace must be 256-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const Buffers bufs{x_dev, heat_dev, static_cast<char*>(ws_dev), part_dev};
+    Buffers bufs{x_dev, heat_dev, static_cast<char*>(ws_dev), part_dev};
+    if (kp_dev) {
+        bufs.kp = static_cast<float*>(kp_dev);
+        bufs.idx = static_cast<int*>(idx_dev);
+        bufs.kheat = reinterpret_cast<float*>(bufs.ws + h->sp.bytes);
+        bufs.kpart = reinterpret_cast<float2*>(bufs.ws + h->sp.bytes + ks.heat);
+    }
     int op_index = 0;
     if (events && hipEventRecord(events[0], stream) != hipSuccess) return fail("forward: hipEventRecord failed");
     // wave executor: lane 0 is the caller's stream; the other lanes of a wave are side streams that fork from and join
@@ -2032,6 +2085,20 @@ int esahrnet_forward_partials(esahrnet_handle h, const void* x_dev, int n, int h
         if (nt <= 0) return fail("forward_partials: this handle's output layer does not report per-tile maxima (esahrnet_partial_tiles = 0)");
     }
     return run_forward(h, x_dev, n, height, width, heat_dev, ws_dev, ws_bytes, stream, nullptr, part_dev);
+}
+
+int esahrnet_keypoints_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
+    if (!h || !bytes) return fail("keypoints_workspace_bytes: null argument");
+    if (plan_shape(*h, n, height, width)) return 1;
+    const KpScratch ks = kp_scratch(*h, n, height, width);
+    *bytes = h->sp.bytes + ks.heat + ks.part;
+    return 0;
+}
+
+int esahrnet_forward_keypoints(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* kp_dev, void* idx_dev,
+                               void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
+    if (!h || !kp_dev) return fail("forward_keypoints: null argument");
+    return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev);
 }
 
 int esahrnet_keypoints_finish(const void* heat_dev, const void* part_dev, int ntiles, int n, int k, int height, int width,

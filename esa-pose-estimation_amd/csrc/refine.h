@@ -1,0 +1,69 @@
+// refine.h — integer peak -> sub-pixel keypoint, the one refinement every keypoint kernel uses (keypoints.hip: the heat-map
+// sweep and the finishes over per-tile maxima, NCHW or NHWC; head.hip: the finish of the keypoints-only VALU output layer).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+
+namespace esa {
+
+// integer peak `bi` (row * W + column) of a plane whose values at(row, col) returns -> kp3 = (x, y, peak): the 9-tap
+// log-quadratic offset in f64 exactly as the reference's Python floats do (inference.py:75-94, 136-152).  `at` is called
+// for the peak and, when the peak is at least 2 px inside the plane, for its 8 neighbours at +-1 and +-2 in x and in y.
+template <class At>
+__device__ __forceinline__ void refine_keypoint(At at, int H, int W, int bi, float* kp3, int* idx_slot) {
+    if (bi == 0x7fffffff) bi = 0;                        // all-NaN / all -inf plane
+    const int px = bi % W, py = bi / W;
+    float fx = (float)px, fy = (float)py;
+    if (1 < px && px < W - 2 && 1 < py && py < H - 2) {   // inference.py:81
+        // np.maximum(hm, 1e-10) of inference.py:141 (NaN-propagating, unlike fmaxf), then math.log in f64
+        auto lg = [&](int yy, int xx) {
+            const float v = at(yy, xx);
+            return log((double)(v < 1e-10f ? 1e-10f : v));
+        };
+        const double c = lg(py, px);
+        const double hx = 0.5 * (lg(py, px + 1) - lg(py, px - 1));
+        const double hy = 0.5 * (lg(py + 1, px) - lg(py - 1, px));
+        const double hxx = 0.25 * (lg(py, px + 2) - 2 * c + lg(py, px - 2));
+        const double hyy = 0.25 * (lg(py + 2, px) - 2 * c + lg(py - 2, px));
+        if (hxx != 0 && hyy != 0) {
+            const double ox = -hx / hxx, oy = -hy / hyy;
+            if (ox < 1 && oy < 1) {                        // signed, both-or-neither (:92)
+                fx = (float)((double)fx + ox);
+                fy = (float)((double)fy + oy);
+            }
+        }
+    }
+    kp3[0] = fx;
+    kp3[1] = fy;
+    kp3[2] = at(py, px);
+    if (idx_slot) *idx_slot = bi;
+}
+
+// first maximum of a plane over its `ntiles` per-tile maxima pp[0 .. ntiles), one wave: every lane ends with the same
+// (value, index) — argmax_take's order does not depend on the order of its steps
+__device__ __forceinline__ void reduce_tile_maxima(const float2* pp, int ntiles, float& bv, int& bi) {
+    bv = -INFINITY;
+    bi = 0x7fffffff;
+    for (int t = threadIdx.x; t < ntiles; t += 64) {
+        const float2 q = pp[t];
+        argmax_take(q.x, __float_as_int(q.y), bv, bi);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        argmax_take(ov, oi, bv, bi);
+    }
+}
+
+// The nine pixels refine_keypoint reads around a peak, numbered: 0 the peak, 1 / 2 x -1 / +1, 3 / 4 x -2 / +2, 5 / 6 y -1 / +1,
+// 7 / 8 y -2 / +2.  Kernels that evaluate those pixels themselves (instead of reading a stored heat-map) use this order.
+__device__ __forceinline__ int refine_point_dx(int pt) { return pt == 0 || pt > 4 ? 0 : (pt & 1 ? -1 : 1) * ((pt + 1) >> 1); }
+__device__ __forceinline__ int refine_point_dy(int pt) { return pt <= 4 ? 0 : (pt & 1 ? -1 : 1) * ((pt - 3) >> 1); }
+__device__ __forceinline__ int refine_point_of(int dy, int dx) {
+    if (dy == 0) return dx == 0 ? 0 : dx == -1 ? 1 : dx == 1 ? 2 : dx == -2 ? 3 : 4;
+    return dy == -1 ? 5 : dy == 1 ? 6 : dy == -2 ? 7 : 8;
+}
+
+}  // namespace esa

@@ -139,11 +139,25 @@ class HighResolutionNet(nn.Module):
             model_dict.update({k: v for k, v in pretrained_dict.items() if k in model_dict})
             self.load_state_dict(model_dict)
 
-    def forward(self, x0: torch.Tensor) -> torch.Tensor:
+    OUTPUTS = ("heatmaps", "keypoints", "keypoints+index")
+
+    def forward(self, x0: torch.Tensor, output: str = "heatmaps"):
+        """output="heatmaps" (default): f32 [N,K,H,W], the reference's forward.  "keypoints": f32 cuda [N,K,3] = (x, y, peak)
+        without writing heat-maps (include/esahrnet.h esahrnet_forward_keypoints), bit-identical to
+        inference.heatmaps_to_keypoints(net(x)); "keypoints+index": (kp, idx int32 [N,K] = row * W + column)."""
         if self.training:
             raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
                                "(the reference callers do, val.py:95 / demo.py:80)")
-        return self._rt.forward(self, x0)
+        if output == "heatmaps":
+            return self._rt.forward(self, x0)
+        if output not in self.OUTPUTS:
+            raise ValueError(f"output must be one of {self.OUTPUTS}, got {output!r}")
+        kp, idx = self._rt.forward_keypoints(self, x0, output == "keypoints+index")
+        return (kp, idx) if output == "keypoints+index" else kp
+
+    def keypoints(self, x0: torch.Tensor) -> torch.Tensor:
+        """net(x, output="keypoints"): f32 cuda [N,K,3] keypoints straight from the crops."""
+        return self(x0, output="keypoints")
 
     # ---- extras of the MI355X path ---------------------------------------------------------------
     @property
@@ -243,6 +257,7 @@ class _Runtime:
         self.handles = {}        # device index -> (handle, weight-version key)
         self.dev_locks = {}      # device index -> lock serialising the enqueues of that device's handle
         self.ws = {}             # (device, stream, n, h, w, keep) -> uint8 tensor, insertion order = LRU order
+        self.kp_ws = {}          # the same for esahrnet_forward_keypoints (its own size: esahrnet_keypoints_workspace_bytes)
         self.part_tiles = {}     # (handle, h, w) -> tiles per heat-map with partial maxima (0: none)
         self._probe = self._create(-1)
 
@@ -326,27 +341,33 @@ class _Runtime:
     def release_workspaces(self):
         with self.lock:
             self.ws.clear()
+            self.kp_ws.clear()
 
-    def _workspace(self, h, device, stream, n, hh, ww, keep):
+    def _workspace(self, h, device, stream, n, hh, ww, keep, kind="forward"):
         """Scratch for one forward.  Contract: while the stream is being CAPTURED into a HIP
         graph the scratch is a fresh tensor allocated inside the capture (the graph's private pool owns it, like
         any temporary of a captured torch op) and is never cached, so no graph ever holds a pointer into the
         eager cache; eager forwards share a small per-device LRU of scratch tensors, keyed by stream and shape
         (two streams never share scratch) and protected by record_stream."""
         nbytes = C.c_size_t()
-        _lib.check(self.lib.esahrnet_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
+        if kind == "keypoints":
+            _lib.check(self.lib.esahrnet_keypoints_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
+            cache = self.kp_ws
+        else:
+            _lib.check(self.lib.esahrnet_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
+            cache = self.ws
         if torch.cuda.is_current_stream_capturing():
             ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=device)
         else:
             key = (device.index, stream.cuda_stream, n, hh, ww, keep)
             with self.lock:
-                ws = self.ws.pop(key, None)
+                ws = cache.pop(key, None)
                 if ws is None or ws.numel() < nbytes.value + 256:
                     ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=device)
-                self.ws[key] = ws                                    # most recently used last
-                mine = [k for k in self.ws if k[0] == device.index]
+                cache[key] = ws                                      # most recently used last
+                mine = [k for k in cache if k[0] == device.index]
                 for k in mine[: max(0, len(mine) - self.WS_SHAPES_PER_DEVICE)]:
-                    del self.ws[k]
+                    del cache[k]
         off = (-ws.data_ptr()) % 256
         return ws, ws.data_ptr() + off, nbytes.value
 
@@ -389,6 +410,31 @@ class _Runtime:
             except RuntimeError:            # torch.inference_mode(): no version counter, so no way to tell a later edit
                 pass
         return heat
+
+    def forward_keypoints(self, module, x0, want_index):
+        """esahrnet_forward_keypoints: (kp f32 [N,K,3], idx int32 [N,K] or None), no heat-map in caller memory.  Same device
+        lock, workspace contract (graph capture included) and record_stream handling as forward()."""
+        x = self._check_input(module, x0)
+        n, _, hh, ww = x.shape
+        dev = x.device
+        ts = torch.cuda.current_stream(dev)
+        with self._device_lock(dev.index):
+            h = self._handle_for(module, dev)
+            _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
+            ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, n, hh, ww, False, kind="keypoints")
+            kp = torch.empty((n, module._k, 3), dtype=torch.float32, device=dev)
+            idx = torch.empty((n, module._k), dtype=torch.int32, device=dev) if want_index else None
+            args = (h, x.data_ptr(), n, hh, ww, kp.data_ptr(), idx.data_ptr() if want_index else None, ws_ptr, ws_bytes,
+                    C.c_void_p(ts.cuda_stream))
+            if torch.cuda.current_device() == dev.index:
+                rc = self.lib.esahrnet_forward_keypoints(*args)
+            else:
+                with torch.cuda.device(dev):
+                    rc = self.lib.esahrnet_forward_keypoints(*args)
+            _lib.check(rc)
+        ws.record_stream(ts)
+        x.record_stream(ts)
+        return kp, idx
 
     def _partial_tiles(self, h, hh, ww):
         if os.environ.get("ESAHRNET_NO_PARTIALS"):

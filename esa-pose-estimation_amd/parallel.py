@@ -46,10 +46,11 @@ def gather_keypoints(local_kp: torch.Tensor, n_total: int, group=None) -> torch.
     return torch.cat(parts, 0)
 
 
-def sharded_keypoints(net, crops: torch.Tensor, group=None, keypoints_fn=None) -> torch.Tensor:
+def sharded_keypoints(net, crops: torch.Tensor, group=None, keypoints_fn=None, keypoints_only: bool = False) -> torch.Tensor:
     """Every rank holds (or can index) the full batch `crops` [N,Cin,H,W]; each runs its slice
     through `net` + the fused keypoint kernel and all ranks return the full [N,K,3].
-    `keypoints_fn` (default: inference.heatmaps_to_keypoints, GPU only) maps the rank's heat-maps to [n,K,3]."""
+    `keypoints_fn` (default: inference.heatmaps_to_keypoints, GPU only) maps the rank's heat-maps to [n,K,3].
+    keypoints_only=True: the rank's slice goes through net(x, output="keypoints") (no heat-maps; keypoints_fn unused)."""
     if keypoints_fn is None:
         from .inference import heatmaps_to_keypoints as keypoints_fn
     heatmaps_to_keypoints = keypoints_fn
@@ -59,7 +60,9 @@ def sharded_keypoints(net, crops: torch.Tensor, group=None, keypoints_fn=None) -
     else:
         lo, hi = 0, n_total
     k = net.num_keypoints
-    if hi > lo:
+    if hi > lo and keypoints_only:
+        kp = net(crops[lo:hi], output="keypoints")
+    elif hi > lo:
         kp = heatmaps_to_keypoints(net(crops[lo:hi]))
     else:
         kp = crops.new_zeros((0, k, 3))

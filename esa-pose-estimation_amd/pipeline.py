@@ -109,16 +109,19 @@ class PoseFailure(ValueError):
 
 def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256, thresh: float = 0.8,
                    min_k: int = 24, distributed: bool = False, pool=None, native: bool = True,
-                   on_fail: str = "raise"):
+                   on_fail: str = "raise", keypoints_only: bool = False):
     """One batch of the val.py:136-233 loop.  frames uint8 cuda [N,H,W]; bboxes N x (x, y, x2, y2);
     kp3d [K3, 3] model keypoints; K camera matrix.  -> list of (q [w,x,y,z], t) per image.
     An image without a solution (the native solver reports it as a NaN row; the reference would die inside
     cv2.solvePnPRansac) raises PoseFailure, or with on_fail="nan" is returned as the NaN row for the caller to
-    deal with — it is never passed on silently."""
+    deal with — it is never passed on silently.  keypoints_only=True: the net goes straight to keypoints
+    (net(x, output="keypoints"): the same bits, no heat-maps written)."""
     x, boxes, rates = crops.crop_batch(frames, bboxes, scale)
     with torch.no_grad():
         if distributed:
-            kp = parallel.sharded_keypoints(net, x)
+            kp = parallel.sharded_keypoints(net, x, keypoints_only=keypoints_only)
+        elif keypoints_only:
+            kp = net(x, output="keypoints")
         else:
             kp = inference.heatmaps_to_keypoints(net(x))
     kp = kp.cpu().numpy()                                   # the only device->host copy: N*K*3 floats

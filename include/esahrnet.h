@@ -137,6 +137,23 @@ int esahrnet_forward_partials(esahrnet_handle h, const void* x_dev, int n, int h
 int esahrnet_keypoints_finish(const void* heat_dev, const void* part_dev, int ntiles, int n, int k, int height, int width,
                               void* kp_dev, void* idx_dev, esahrnet_stream stream);
 
+/* ---- forward straight to keypoints, without heat-maps ------------------------------------------------------
+ * esahrnet_forward_keypoints runs the forward of esahrnet_forward with its last launch (the output layer, or seg_hrnet3's
+ * conversion of its heat-maps to NCHW) replaced, so that no heat-map reaches caller memory: kp_dev f32 [n][K][3] = (x, y,
+ * peak) and idx_dev int32 [n][K] (NULL: not written) are bit-identical to esahrnet_forward followed by esahrnet_keypoints_ex
+ * on the same input and weights (same ties, NaN rule and refinement).  Replaces `net(x)` + get_final and the host peak search
+ * (val.py:151-180, inference.py:136-152).  ws_dev: esahrnet_keypoints_workspace_bytes bytes (at least esahrnet_workspace_bytes
+ * for the same shape), 256-byte aligned.  Like esahrnet_forward it allocates nothing, does not synchronise, may be captured
+ * into a graph, and follows esahrnet_set_debug_keep and the multi-lane schedule.
+ *   seg_hrnet / seg_hrnet2, VALU output layer: each tile's first maximum per heat-map, nothing stored; the finish evaluates
+ *     the output layer again at the <= 9 pixels the refinement reads.
+ *   seg_hrnet / seg_hrnet2, matrix-core output layer: the heat-maps go to the workspace instead of caller memory, then
+ *     esahrnet_keypoints_finish's kernel (no new arithmetic: the gain is caller memory).
+ *   seg_hrnet3: the tile maxima of the NHWC heat-maps already in the workspace; the refinement reads them there. */
+int esahrnet_keypoints_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes);
+int esahrnet_forward_keypoints(esahrnet_handle h, const void* x_dev, int n, int height, int width,
+                               void* kp_dev, void* idx_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+
 /* Loader stage in front of the path (data_load_val.py:139-187): for each of n 8-bit frames
  * [frame_h][frame_w] take the clamped box boxes[i] = (x0, y0, x1, y1) (int32, device), edge-pad it the
  * way the reference does, resize to scale x scale (OpenCV 8-bit INTER_LINEAR arithmetic) and write
