@@ -304,6 +304,14 @@ int launch_keypoints_finish(const float* heat, const float2* part, int ntiles, i
 int launch_keypoints_finish_nhwc(int fmt, const char* x, int N, int C, int H, int W, int Cp, const float2* part, int ntiles,
                                  float* kp, int* idx_out, hipStream_t stream);
 
+// ---- get_final2: 11x11 Gaussian blur, rescale, log, full-Hessian Newton step (keypoints_final2.hip) -------------------
+// Same kp / idx_out layout, arg-max and peak as launch_keypoints.  ws: final2_workspace_bytes, 256-byte aligned (per-tile
+// maxima of the raw and of the blurred planes; the blurred planes themselves are never stored).
+int final2_tiles(int H, int W);
+size_t final2_workspace_bytes(long long planes, int H, int W);
+int launch_keypoints_final2(const float* heat, int planes, int H, int W, float* kp, int* idx_out, void* ws, size_t ws_bytes,
+                            hipStream_t stream);
+
 // ---- crop + edge-pad + 8-bit bilinear resize + normalise: u8 frames -> f32 [N][1][S][S] (crops.hip) ----
 int launch_crops(const unsigned char* frames, const int* boxes, float* out, int N, int FH, int FW, int S,
                  float mean, float std_, hipStream_t s);

@@ -2121,6 +2121,29 @@ int esahrnet_keypoints_ex(const void* heat_dev, int n, int k, int height, int wi
     return 0;
 }
 
+int esahrnet_keypoints_final2_workspace_bytes(int n, int k, int height, int width, size_t* bytes) {
+    if (!bytes) return fail("keypoints_final2_workspace_bytes: null argument");
+    if (n <= 0 || k <= 0 || height <= 0 || width <= 0 || (long long)height * width > 0x7fffffffLL)
+        return fail("keypoints_final2_workspace_bytes: bad shape %d x %d x %d x %d", n, k, height, width);
+    *bytes = esa::final2_workspace_bytes((long long)n * k, height, width);
+    return 0;
+}
+
+int esahrnet_keypoints_final2(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev, void* ws_dev,
+                              size_t ws_bytes, esahrnet_stream stream) {
+    if (!heat_dev || !kp_dev || !ws_dev) return fail("keypoints_final2: null argument");
+    size_t need = 0;
+    if (esahrnet_keypoints_final2_workspace_bytes(n, k, height, width, &need)) return 1;
+    if ((long long)n * k * esa::final2_tiles(height, width) > 0x7fffffLL)
+        return fail("keypoints_final2: %d x %d planes of %d x %d: too many tiles for one launch", n, k, height, width);
+    if (ws_bytes < need) return fail("keypoints_final2: workspace too small (%zu < %zu)", ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("keypoints_final2: workspace must be 256-byte aligned");
+    const int rc = esa::launch_keypoints_final2(static_cast<const float*>(heat_dev), n * k, height, width, static_cast<float*>(kp_dev),
+                                                static_cast<int*>(idx_dev), ws_dev, ws_bytes, static_cast<hipStream_t>(stream));
+    if (rc) return fail("keypoints_final2: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
 int esahrnet_keypoints(const void* heat_dev, int n, int k, int height, int width, void* kp_dev,
                        esahrnet_stream stream) {
     return esahrnet_keypoints_ex(heat_dev, n, k, height, width, kp_dev, nullptr, stream);

@@ -1,5 +1,6 @@
 // refine.h — integer peak -> sub-pixel keypoint, the one refinement every keypoint kernel uses (keypoints.hip: the heat-map
-// sweep and the finishes over per-tile maxima, NCHW or NHWC; head.hip: the finish of the keypoints-only VALU output layer).
+// sweep and the finishes over per-tile maxima, NCHW or NHWC; head.hip: the finish of the keypoints-only VALU output layer),
+// and the Newton step of the second decoder, get_final2 (keypoints_final2.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,6 +65,49 @@ __device__ __forceinline__ int refine_point_dy(int pt) { return pt <= 4 ? 0 : (p
 __device__ __forceinline__ int refine_point_of(int dy, int dx) {
     if (dy == 0) return dx == 0 ? 0 : dx == -1 ? 1 : dx == 1 ? 2 : dx == -2 ? 3 : 4;
     return dy == -1 ? 5 : dy == 1 ? 6 : dy == -2 ? 7 : 8;
+}
+
+// ---- get_final2 (inference.py:154-169): blur, rescale, log, full-Hessian Newton step ------------------------------------
+// The 11 taps of cv2.GaussianBlur(., (11, 11), 0) (getGaussianKernel: sigma 0.3 * ((11 - 1) * 0.5 - 1) + 0.8 = 2,
+// t_i = exp(-(i - 5)^2 / 8), each times 1 / sum_i t_i, in f64), written out so that host and device agree on every bit.
+constexpr double kFinal2Gauss[11] = {0x1.20c2564ee6770p-7, 0x1.bcb86a082c301p-6, 0x1.0ab50979aaf94p-4, 0x1.f2464c62edaf4p-4,
+                                     0x1.6a7e1d504a91ep-3, 0x1.9ac20a36ea596p-3, 0x1.6a7e1d504a91ep-3, 0x1.f2464c62edaf4p-4,
+                                     0x1.0ab50979aaf94p-4, 0x1.bcb86a082c301p-6, 0x1.20c2564ee6770p-7};
+
+// The 13 blurred points the Newton step reads: 0..8 as refine_point_dx / _dy, then 9 / 10 / 11 / 12 at (y-1, x-1),
+// (y-1, x+1), (y+1, x-1), (y+1, x+1).
+__device__ __forceinline__ int final2_point_dx(int pt) { return pt < 9 ? refine_point_dx(pt) : pt & 1 ? -1 : 1; }
+__device__ __forceinline__ int final2_point_dy(int pt) { return pt < 9 ? refine_point_dy(pt) : pt < 11 ? -1 : 1; }
+
+// blurred f32 value b -> the value the Newton step reads: b * s in f32 (the rescale, inference.py:110), np.maximum(., 1e-10)
+// (NaN-propagating), then log, taken as f32(log(f64(.))) on host and device alike (NumPy's f32 log may differ by one ulp)
+__device__ __forceinline__ float final2_log(float b, float s) {
+#pragma clang fp contract(off)
+    float v = (float)((double)b * (double)s);              // exact product, one rounding: the f32 product
+    v = v < 1e-10f ? 1e-10f : v;
+    return (float)log((double)v);
+}
+
+// taylor (inference.py:54-73) on the 13 log values h[]: the differences of two f32 values are f32 (NumPy scalars), the first
+// product with a Python number and everything after it f64 (NumPy 1.x promotion); the inverse in closed form.  The step is
+// taken when det != 0 and the offset is finite; then (fx, fy) = f32(f64(p) + offset).
+__device__ __forceinline__ void final2_newton(const float* h, int px, int py, float& fx, float& fy) {
+#pragma clang fp contract(off)                             // the host restatement has no fma
+    const double dx = 0.5 * (double)(h[2] - h[1]);
+    const double dy = 0.5 * (double)(h[6] - h[5]);
+    const double c2 = 2 * (double)h[0];
+    const double dxx = 0.25 * (((double)h[4] - c2) + (double)h[3]);
+    const double dyy = 0.25 * (((double)h[8] - c2) + (double)h[7]);
+    const double dxy = 0.25 * (double)(((h[12] - h[10]) - h[11]) + h[9]);
+    const double det = dxx * dyy - dxy * dxy;
+    if (det != 0) {
+        const double i00 = dyy / det, i01 = -dxy / det, i11 = dxx / det;
+        const double ox = -(i00 * dx + i01 * dy), oy = -(i01 * dx + i11 * dy);
+        if (isfinite(ox) && isfinite(oy)) {
+            fx = (float)((double)px + ox);
+            fy = (float)((double)py + oy);
+        }
+    }
 }
 
 }  // namespace esa

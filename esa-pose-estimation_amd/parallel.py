@@ -46,11 +46,16 @@ def gather_keypoints(local_kp: torch.Tensor, n_total: int, group=None) -> torch.
     return torch.cat(parts, 0)
 
 
-def sharded_keypoints(net, crops: torch.Tensor, group=None, keypoints_fn=None, keypoints_only: bool = False) -> torch.Tensor:
+def sharded_keypoints(net, crops: torch.Tensor, group=None, keypoints_fn=None, keypoints_only: bool = False,
+                      refine: str = "get_final") -> torch.Tensor:
     """Every rank holds (or can index) the full batch `crops` [N,Cin,H,W]; each runs its slice
     through `net` + the fused keypoint kernel and all ranks return the full [N,K,3].
     `keypoints_fn` (default: inference.heatmaps_to_keypoints, GPU only) maps the rank's heat-maps to [n,K,3].
-    keypoints_only=True: the rank's slice goes through net(x, output="keypoints") (no heat-maps; keypoints_fn unused)."""
+    keypoints_only=True: the rank's slice goes through net(x, output="keypoints") (no heat-maps; keypoints_fn unused).
+    refine="get_final2": the second decoder (inference.get_final2), passed on as refine= to the net or to keypoints_fn."""
+    from .inference import check_refine
+    check_refine(refine)
+    rk = {} if refine == "get_final" else {"refine": refine}
     if keypoints_fn is None:
         from .inference import heatmaps_to_keypoints as keypoints_fn
     heatmaps_to_keypoints = keypoints_fn
@@ -61,9 +66,9 @@ def sharded_keypoints(net, crops: torch.Tensor, group=None, keypoints_fn=None, k
         lo, hi = 0, n_total
     k = net.num_keypoints
     if hi > lo and keypoints_only:
-        kp = net(crops[lo:hi], output="keypoints")
+        kp = net(crops[lo:hi], output="keypoints", **rk)
     elif hi > lo:
-        kp = heatmaps_to_keypoints(net(crops[lo:hi]))
+        kp = heatmaps_to_keypoints(net(crops[lo:hi]), **rk)
     else:
         kp = crops.new_zeros((0, k, 3))
     return gather_keypoints(kp, n_total, group)

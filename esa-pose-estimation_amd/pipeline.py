@@ -109,21 +109,24 @@ class PoseFailure(ValueError):
 
 def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256, thresh: float = 0.8,
                    min_k: int = 24, distributed: bool = False, pool=None, native: bool = True,
-                   on_fail: str = "raise", keypoints_only: bool = False):
+                   on_fail: str = "raise", keypoints_only: bool = False, refine: str = "get_final"):
     """One batch of the val.py:136-233 loop.  frames uint8 cuda [N,H,W]; bboxes N x (x, y, x2, y2);
     kp3d [K3, 3] model keypoints; K camera matrix.  -> list of (q [w,x,y,z], t) per image.
     An image without a solution (the native solver reports it as a NaN row; the reference would die inside
     cv2.solvePnPRansac) raises PoseFailure, or with on_fail="nan" is returned as the NaN row for the caller to
     deal with — it is never passed on silently.  keypoints_only=True: the net goes straight to keypoints
-    (net(x, output="keypoints"): the same bits, no heat-maps written)."""
+    (net(x, output="keypoints"): the same bits, no heat-maps written).  refine="get_final2": the reference's second
+    decoder (inference.get_final2: blur + full-Hessian step) instead of get_final."""
+    inference.check_refine(refine)
+    rk = {} if refine == "get_final" else {"refine": refine}
     x, boxes, rates = crops.crop_batch(frames, bboxes, scale)
     with torch.no_grad():
         if distributed:
-            kp = parallel.sharded_keypoints(net, x, keypoints_only=keypoints_only)
+            kp = parallel.sharded_keypoints(net, x, keypoints_only=keypoints_only, **rk)
         elif keypoints_only:
-            kp = net(x, output="keypoints")
+            kp = net(x, output="keypoints", **rk)
         else:
-            kp = inference.heatmaps_to_keypoints(net(x))
+            kp = inference.heatmaps_to_keypoints(net(x), **rk)
     kp = kp.cpu().numpy()                                   # the only device->host copy: N*K*3 floats
     poses = poses_from_keypoints(kp, boxes, rates, kp3d, K, thresh, min_k, pool, native)
     if on_fail == "raise":
@@ -137,7 +140,8 @@ def run_submission(net, batches, kp3d, K, writer, real: bool = False, on_fail: s
     """`batches` yields (names, frames_u8_cuda, bboxes); appends every pose to `writer` (ours or the reference's
     SubmissionWriter: anything with append_test / append_real_test).  A submission needs a finite row for every
     image, so an image without a solution gets FALLBACK_POSE and is logged and listed in `writer.failed`
-    (on_fail="fallback"), or stops the run (on_fail="raise")."""
+    (on_fail="fallback"), or stops the run (on_fail="raise").  `kw` goes to estimate_poses (keypoints_only=,
+    refine="get_final2", ...)."""
     failed = []
     for names, frames, bboxes in batches:
         poses = estimate_poses(net, frames, bboxes, kp3d, K, on_fail="nan", **kw)

@@ -122,6 +122,19 @@ int esahrnet_keypoints(const void* heat_dev, int n, int k, int height, int width
 int esahrnet_keypoints_ex(const void* heat_dev, int n, int k, int height, int width,
                           void* kp_dev, void* idx_dev, esahrnet_stream stream);
 
+/* ---- the second decoder: get_final2 (inference.py:154-169) ---------------------------------------------------------
+ * Same arg-max, peak and idx_dev as esahrnet_keypoints_ex (bit-identical), but the sub-pixel step of get_final2: each plane
+ * blurred by the 11x11 Gaussian of cv2.GaussianBlur(., (11, 11), 0) (sigma 2, zero padding, f64 sums, rounded to f32),
+ * rescaled to the plane's raw maximum, clamped at 1e-10 and logged (inference.py:96-111), then one Newton step with the
+ * full 2x2 Hessian, dxy included (taylor, :54-73).  The step is applied when the peak is at least 2 px inside the plane,
+ * the Hessian's determinant is non-zero, and the raw maximum, the blurred maximum, the rescale factor and the offset are
+ * all finite; otherwise the keypoint keeps its integer coordinates (the reference would write NaN or raise).  The blurred
+ * planes are never stored: ws_dev (esahrnet_keypoints_final2_workspace_bytes bytes, 256-byte aligned) holds per-tile
+ * maxima only.  The heat-maps are read once.  Allocates nothing, does not synchronise, may be captured into a graph. */
+int esahrnet_keypoints_final2_workspace_bytes(int n, int k, int height, int width, size_t* bytes);
+int esahrnet_keypoints_final2(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev,
+                              void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+
 /* ---- forward + keypoints without re-reading the heat-maps -------------------------------------------------
  * The output-layer kernel can leave, beside the heat-maps, the first row-major maximum of each of its tiles:
  * part_dev = 8 bytes x [n * K][ntiles] (f32 value, int32 index row * width + column).  esahrnet_keypoints_finish reduces
