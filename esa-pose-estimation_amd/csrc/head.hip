@@ -303,6 +303,186 @@ __global__ __launch_bounds__(64) void final_kp_finish_kernel(FinalParams p, int 
                         kp + (size_t)plane * 3, idx_out ? idx_out + plane : nullptr);
 }
 
+// ---- get_final2 without heat-maps, VALU output layer (esahrnet_forward_keypoints_final2) ------------------------------
+// final2_valu_kernel: one workgroup per (image, 22 x 22 output tile).  It evaluates the output layer over the tile and the
+// blur's 5-pixel halo, 32 x 32 pixels, with final_kernel's arithmetic: the same staging functions, acc = bias[k], then one fma
+// per (channel, tap) in final_kernel's order (a pair of pixels per v_pk_fma_f32, as final_kernel's RPT = 2).  The input is
+// staged 8 concat channels at a time (34 x 34 each), so the LDS does not grow with K + cin.  Values outside the plane are
+// zero, as keypoints_final2.hip's tile pass stages them.  Then, four heat-maps at a time, one wave each: the row and the
+// column pass in f64 in blur_taps' order, the tile's first raw maximum -> p.part and its blurred maximum -> bmax, both
+// [N * K][final2_valu_tiles].  Nothing else is stored.
+// final2_valu_finish_kernel: one wave per heat-map.  The maxima as keypoints_final2.hip's finish reduces them, then the
+// output layer again at the 15 x 15 pixels around the peak (the 13 blurred values read +-7 rows and columns), the same
+// arithmetic, and the 13 blurred values from those with blur_at's sums.  kp / idx bit-identical to launch_final (VALU)
+// followed by launch_keypoints_final2.
+constexpr int F2V_T = 22, F2V_V = F2V_T + 10, F2V_S = F2V_V + 2;     // output tile, value region, staged input region
+constexpr int F2V_LDS = 4 * F2V_V * F2V_V * 4 + 4 * F2V_V * F2V_T * 8;  // >= 8 * F2V_S * F2V_S * 4, the staging it overlays
+static_assert(F2V_LDS >= 8 * F2V_S * F2V_S * 4, "staging overlay");
+
+// concat channels 8g .. 8g+7 (g < G: up-sampled) or the raw channels (g == G) of image n over the S x S pixels from (sy0, sx0)
+// -> stg[channel - first][S * S]
+template <int S, int NT>
+__device__ __forceinline__ void final2_stage_chunk(const FinalParams& p, int n, int g, int G, int sy0, int sx0, float sc_y,
+                                                   float sc_x, float* stg, int tid) {
+    if (g < G) {
+        for (int q = tid; q < S * S; q += NT) {
+            float v[8];
+            final_stage8(p, n, sy0 + q / S, sx0 + q % S, g, sc_y, sc_x, v);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) stg[i * S * S + q] = v[i];
+        }
+    } else {
+        for (int u = tid; u < S * S * p.cin; u += NT) {
+            const int q = u % (S * S), ci = u / (S * S);
+            stg[ci * S * S + q] = final_stage_raw(p, n, ci, sy0 + q / S, sx0 + q % S);
+        }
+    }
+}
+
+template <int KT>
+__global__ __launch_bounds__(256) void final2_valu_kernel(FinalParams p, int tiles_x, int ntiles, float* bmax) {
+    constexpr int V = F2V_V, T = F2V_T, S = F2V_S;
+    __shared__ __attribute__((aligned(16))) char smem[F2V_LDS];
+    float* stg = reinterpret_cast<float*>(smem);                          // [8][S * S] while the output layer runs
+    float* val = reinterpret_cast<float*>(smem);                          // [4][V * V] then
+    double* srow = reinterpret_cast<double*>(smem + 4 * V * V * 4);       // [4][V][T]
+    const int tid = threadIdx.x, tile = (int)(blockIdx.x % (unsigned)ntiles), n = (int)(blockIdx.x / (unsigned)ntiles);
+    const int oy0 = tile / tiles_x * T, ox0 = tile % tiles_x * T, vy0 = oy0 - 5, vx0 = ox0 - 5;
+    const float sc_y = final_scale(p.h, p.H), sc_x = final_scale(p.wd, p.W);
+    const int G = (p.K + 7) >> 3;
+    // pixel pair m of this thread: value-region pixels tid + 512 m (element 0) and tid + 512 m + 256 (element 1)
+    f32x2 acc[2][KT];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int k = 0; k < KT; ++k) acc[m][k] = f32x2{p.bias[k], p.bias[k]};
+    for (int g = 0; g <= G; ++g) {
+        const int c0 = g < G ? 8 * g : p.K, nc = g < G ? min(8, p.K - 8 * g) : p.cin;
+        __syncthreads();                                                  // the previous chunk is read
+        final2_stage_chunk<S, 256>(p, n, g, G, vy0 - 1, vx0 - 1, sc_y, sc_x, stg, tid);
+        __syncthreads();
+        for (int i = 0; i < nc; ++i) {
+            const float* sp = stg + i * S * S;
+            const float* wp = p.w + (size_t)(c0 + i) * 9 * KT;
+#pragma unroll 1
+            for (int tap = 0; tap < 9; ++tap) {                            // (one tap's KT weights in SGPRs at a time)
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    const int q0 = tid + 512 * m, q1 = q0 + 256, o = (tap / 3) * S + tap % 3;
+                    const f32x2 v = {sp[(q0 / V) * S + q0 % V + o], sp[(q1 / V) * S + q1 % V + o]};
+#pragma unroll
+                    for (int k = 0; k < KT; ++k) {
+                        const float w = wp[tap * KT + k];
+                        acc[m][k] = __builtin_elementwise_fma(v, f32x2{w, w}, acc[m][k]);
+                    }
+                }
+            }
+        }
+    }
+    const int wv = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int k0 = 0; k0 < KT; k0 += 4) {
+        __syncthreads();                                                  // staging / the previous planes are read
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+            if (k0 + d < KT)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int q = tid + 256 * e, gy = vy0 + q / V, gx = vx0 + q % V;
+                    const bool in = gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
+                    val[d * V * V + q] = in ? acc[e >> 1][k0 + d][e & 1] : 0.f;
+                }
+        __syncthreads();
+        const int k = k0 + wv;
+        const float* pv = val + wv * V * V;
+        double* pr = srow + wv * V * T;
+        float bv = -INFINITY, bm = -INFINITY;
+        int bi = 0x7fffffff;
+        if (k < p.K) {
+            for (int i = lane; i < T * T; i += 64) {
+                const int r = i / T, c = i % T, y = oy0 + r, x = ox0 + c;
+                if (y < p.H && x < p.W) argmax_take(pv[(r + 5) * V + c + 5], y * p.W + x, bv, bi);
+            }
+            for (int i = lane; i < V * T; i += 64) {                      // row pass: every value row, the tile's columns
+                const int r = i / T, c = i % T;
+                pr[r * T + c] = blur_taps([&](int t) { return pv[r * V + c + t]; });
+            }
+        }
+        __syncthreads();
+        if (k < p.K) {
+            for (int i = lane; i < T * T; i += 64) {                      // column pass
+                const int r = i / T, c = i % T;
+                const float b = (float)blur_taps([&](int t) { return pr[(r + t) * T + c]; });
+                if (oy0 + r < p.H && ox0 + c < p.W) bm = max_nan(bm, b);
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const float ov = __shfl_xor(bv, off);
+                const int oi = __shfl_xor(bi, off);
+                argmax_take(ov, oi, bv, bi);
+                bm = max_nan(bm, __shfl_xor(bm, off));
+            }
+            if (lane == 0) {
+                const size_t rec = ((size_t)n * p.K + k) * ntiles + tile;
+                p.part[rec] = make_float2(bv, __int_as_float(bi));
+                bmax[rec] = bm;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void final2_valu_finish_kernel(FinalParams p, int kt, int ntiles, const float* bmax, float* kp,
+                                                                int* idx_out) {
+    constexpr int R = 15, S = R + 2;
+    __shared__ float stg[8 * S * S];
+    __shared__ float win[R * R];
+    const int plane = blockIdx.x, n = plane / p.K, k = plane - n * p.K, lane = threadIdx.x;
+    float bv;
+    int bi;
+    reduce_tile_maxima(p.part + (size_t)plane * ntiles, ntiles, bv, bi);
+    float bm = -INFINITY;
+    for (int t = lane; t < ntiles; t += 64) bm = max_nan(bm, bmax[(size_t)plane * ntiles + t]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) bm = max_nan(bm, __shfl_xor(bm, off));
+    if (bi == 0x7fffffff) bi = 0;                          // all -inf plane
+    const int px = bi % p.W, py = bi / p.W, wy0 = py - R / 2, wx0 = px - R / 2;
+    const float sc_y = final_scale(p.h, p.H), sc_x = final_scale(p.wd, p.W);
+    const int G = (p.K + 7) >> 3;
+    float acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = p.bias[k];
+    for (int g = 0; g <= G; ++g) {
+        const int c0 = g < G ? 8 * g : p.K, nc = g < G ? min(8, p.K - 8 * g) : p.cin;
+        __syncthreads();
+        final2_stage_chunk<S, 64>(p, n, g, G, wy0 - 1, wx0 - 1, sc_y, sc_x, stg, lane);
+        __syncthreads();
+        for (int i = 0; i < nc; ++i) {
+            const float* sp = stg + i * S * S;
+            const float* wp = p.w + (size_t)(c0 + i) * 9 * kt;
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int q = min(lane + 64 * j, R * R - 1);
+                    acc[j] = fmaf(sp[(q / R + tap / 3) * S + q % R + tap % 3], wp[tap * kt + k], acc[j]);
+                }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int q = lane + 64 * j, gy = wy0 + q / R, gx = wx0 + q % R;
+        if (q < R * R) win[q] = gy >= 0 && gy < p.H && gx >= 0 && gx < p.W ? acc[j] : 0.f;
+    }
+    __syncthreads();
+    final2_finish(
+        bv, bi, bm, p.H, p.W,
+        [&](int j) {
+            const int cy = R / 2 + final2_point_dy(j), cx = R / 2 + final2_point_dx(j);
+            return (float)blur_taps([&](int r) { return blur_taps([&](int t) { return win[(cy - 5 + r) * R + cx - 5 + t]; }); });
+        },
+        [&] { return win[(R / 2) * R + R / 2]; }, kp, idx_out, plane);
+}
+
 
 // ---------------------------------------------------------------------------------------------------
 // Matrix-core version of the same op.  The contraction index is (tap, channel) with the K+cin concat
@@ -598,6 +778,29 @@ int launch_final_kp(const FinalParams& p, float* kp, int* idx_out, hipStream_t s
     }
     if (rc) return rc;
     hipLaunchKernelGGL(final_kp_finish_kernel, dim3((unsigned)planes), dim3(64), 0, stream, p, kt, ntiles, kp, idx_out);
+    return (int)hipGetLastError();
+}
+
+int final2_valu_tiles(int H, int W) {
+    if (H <= 0 || W <= 0) return 0;
+    return ((H + F2V_T - 1) / F2V_T) * ((W + F2V_T - 1) / F2V_T);
+}
+
+int launch_final2_kp(const FinalParams& p, float* bmax, float* kp, int* idx_out, hipStream_t stream) {
+    const int ntiles = final2_valu_tiles(p.H, p.W), kt = final_kt(p.K);
+    const long long planes = (long long)p.N * p.K, nblk = (long long)p.N * ntiles;
+    if (!p.part || !bmax || !kp || ntiles <= 0 || kt < 0 || p.cin < 0 || p.cin > 8 || planes > 0x7fffffffLL ||
+        nblk > 0x7fffffffLL || (long long)p.H * p.W > 0x7fffffffLL)
+        return (int)hipErrorInvalidValue;
+    const int tiles_x = (p.W + F2V_T - 1) / F2V_T;
+    switch (kt) {
+        case 11: hipLaunchKernelGGL(final2_valu_kernel<11>, dim3((unsigned)nblk), dim3(256), 0, stream, p, tiles_x, ntiles, bmax); break;
+        case 16: hipLaunchKernelGGL(final2_valu_kernel<16>, dim3((unsigned)nblk), dim3(256), 0, stream, p, tiles_x, ntiles, bmax); break;
+        case 32: hipLaunchKernelGGL(final2_valu_kernel<32>, dim3((unsigned)nblk), dim3(256), 0, stream, p, tiles_x, ntiles, bmax); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(final2_valu_finish_kernel, dim3((unsigned)planes), dim3(64), 0, stream, p, kt, ntiles, bmax, kp, idx_out);
     return (int)hipGetLastError();
 }
 

@@ -163,6 +163,11 @@ int launch_final(const FinalParams& p, hipStream_t stream);
 // [N*K] or nullptr, bit-identical to launch_final (VALU) + launch_keypoints; p.out is not used
 int final_kp_tiles(int K, int cin, int H, int W);
 int launch_final_kp(const FinalParams& p, float* kp, int* idx_out, hipStream_t stream);
+// get_final2 keypoints without heat-maps, VALU output layer (final2_valu_kernel + final2_valu_finish_kernel): kp / idx_out
+// bit-identical to launch_final (VALU) + launch_keypoints_final2; p.part and bmax: [N*K][final2_valu_tiles] records, p.out
+// not used; cin <= 8
+int final2_valu_tiles(int H, int W);
+int launch_final2_kp(const FinalParams& p, float* bmax, float* kp, int* idx_out, hipStream_t stream);
 // tiles per heat-map the MFMA output-layer kernel reports partial maxima for; 0: that kernel does not serve (K, cin)
 int final_part_tiles(int K, int cin, int H, int W);
 // (v, i) beats (bv, bi) if it is larger — NaN counting as larger than every number — or equal with a lower index
@@ -311,6 +316,10 @@ int final2_tiles(int H, int W);
 size_t final2_workspace_bytes(long long planes, int H, int W);
 int launch_keypoints_final2(const float* heat, int planes, int H, int W, float* kp, int* idx_out, void* ws, size_t ws_bytes,
                             hipStream_t stream);
+// the same decoder on NHWC heat-maps x [N][H][W][Cp] (fmt FMT_SB or FMT_F32) that were never converted to NCHW: seg_hrnet3
+// under esahrnet_forward_keypoints_final2; planes = N * C, ws as above
+int launch_keypoints_final2_nhwc(int fmt, const char* x, int N, int C, int H, int W, int Cp, float* kp, int* idx_out, void* ws,
+                                 size_t ws_bytes, hipStream_t stream);
 
 // ---- crop + edge-pad + 8-bit bilinear resize + normalise: u8 frames -> f32 [N][1][S][S] (crops.hip) ----
 int launch_crops(const unsigned char* frames, const int* boxes, float* out, int N, int FH, int FW, int S,

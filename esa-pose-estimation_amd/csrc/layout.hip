@@ -1,5 +1,6 @@
 // layout.hip — f32 NCHW <-> SB (split-bf16 NHWC), BF and F32 conversion.  Used by the per-operator test entry points, by
 // esahrnet_tap_read and for seg_hrnet3's heat-maps; the network itself enters its format through the stem kernel.
+#include "final2.h"
 #include "kernels.h"
 #include "sb.h"
 
@@ -185,6 +186,16 @@ int launch_to_nchw_part(int fmt, const char* x, int N, int C, int H, int W, int 
     auto kern = fmt == FMT_F32 ? to_nchw_part_kernel<true, true> : to_nchw_part_kernel<false, true>;
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(TONCHW_NT), 0, s, x, C, H * W, Cp, y, part, ntiles);
     return (int)hipGetLastError();
+}
+
+// get_final2 straight from seg_hrnet3's NHWC heat-maps (final2.h's kernels with the NHWC plane accessor)
+int launch_keypoints_final2_nhwc(int fmt, const char* x, int N, int C, int H, int W, int Cp, float* kp, int* idx_out, void* ws,
+                                 size_t ws_bytes, hipStream_t stream) {
+    if (N <= 0 || C < 1 || C > Cp || (Cp & 7) || (long long)N * C > 0x7fffffffLL || (fmt != FMT_SB && fmt != FMT_F32))
+        return (int)hipErrorInvalidValue;
+    const int planes = N * C;
+    if (fmt == FMT_F32) return launch_final2(F2Nhwc<true>{x, C, Cp}, planes, H, W, kp, idx_out, ws, ws_bytes, stream);
+    return launch_final2(F2Nhwc<false>{x, C, Cp}, planes, H, W, kp, idx_out, ws, ws_bytes, stream);
 }
 
 int launch_tile_max(int fmt, const char* x, int N, int C, int H, int W, int Cp, float2* part, hipStream_t s) {

@@ -1562,17 +1562,38 @@ struct Buffers {
     int* idx = nullptr;
     float* kheat = nullptr;
     float2* kpart = nullptr;
+    // esahrnet_forward_keypoints_final2: the same, decoded with get_final2.  kbmax: the VALU output layer's blurred tile maxima;
+    // kws: the bytes at kpart that launch_keypoints_final2(_nhwc) may use
+    bool final2 = false;
+    float* kbmax = nullptr;
+    size_t kws = 0;
 };
 
 // What esahrnet_forward_keypoints keeps behind the forward's workspace (at ShapePlan::bytes, a multiple of 256): the per-tile
 // maxima of the output layer and, where that is the matrix-core kernel, its heat-maps (that kernel writes them in any case)
+// esahrnet_forward_keypoints_final2 keeps: seg_hrnet3, get_final2's per-tile raw and blurred maxima of the NHWC heat-maps
+// (part: esa::final2_workspace_bytes); the matrix-core output layer, its heat-maps and the same; the VALU output layer, the
+// raw (part) and blurred (bmax) maxima of its 22 x 22 tiles.  No N*K*H*W term but the matrix-core one.
 struct KpScratch {
     int ntiles = 0;
-    size_t heat = 0, part = 0;
+    size_t heat = 0, part = 0, bmax = 0;
 };
-static KpScratch kp_scratch(const esahrnet_ctx& c, int n, int height, int width) {
+static KpScratch kp_scratch(const esahrnet_ctx& c, int n, int height, int width, bool final2 = false) {
     KpScratch s;
     const int K = c.cfg.num_keypoints;
+    const long long planes = (long long)n * K;
+    if (final2) {
+        if (c.cfg.variant != 1 && c.opt.final_mfma) s.heat = ((size_t)planes * height * width * 4 + 255) & ~(size_t)255;
+        if (c.cfg.variant == 1 || c.opt.final_mfma) {
+            s.ntiles = esa::final2_tiles(height, width);
+            s.part = esa::final2_workspace_bytes(planes, height, width);
+        } else {
+            s.ntiles = esa::final2_valu_tiles(height, width);
+            s.part = ((size_t)planes * s.ntiles * 8 + 255) & ~(size_t)255;
+            s.bmax = ((size_t)planes * s.ntiles * 4 + 255) & ~(size_t)255;
+        }
+        return s;
+    }
     if (c.cfg.variant == 1) {
         s.ntiles = esa::to_nchw_part_tiles(height, width);
     } else if (c.opt.final_mfma) {
@@ -1708,6 +1729,9 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             const bool f32 = c.tensors[o.in].f32;       // (bf16 mode: the output layer's f32 heat-maps)
             const int fmt = f32 ? esa::FMT_F32 : c.opt.fmt;
             if (desc) plain(f32 ? "f32_to_nchw" : "sb_to_nchw");
+            else if (b.kp && b.final2)                  // esahrnet_forward_keypoints_final2: get_final2 on the NHWC maps
+                rc = esa::launch_keypoints_final2_nhwc(fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
+                                                       b.kp, b.idx, b.kpart, b.kws, stream);
             else if (b.kp) {                            // esahrnet_forward_keypoints: maxima and refine on the NHWC maps
                 const int K = c.cfg.num_keypoints, Cp = c.tensors[o.in].Cp;
                 rc = esa::launch_tile_max(fmt, T(o.in), n, K, height, width, Cp, b.kpart, stream);
@@ -1945,6 +1969,15 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 describe(desc, "final_kernel", "%s", s.name.c_str());
                 desc->flops = 2.0 * n * height * width * s.cout * s.cin * 9;
                 desc->bytes = tbytes(o.in) + (double)n * height * width * (c.cfg.cin + s.cout) * 4;
+            } else if (b.kp && b.final2 && !c.final_wpk) {   // esahrnet_forward_keypoints_final2, VALU: the blurring output layer
+                p.out = nullptr;
+                p.part = b.kpart;
+                rc = esa::launch_final2_kp(p, b.kbmax, b.kp, b.idx, stream);
+            } else if (b.kp && b.final2) {              // ... matrix-core: heat-maps into the scratch, then get_final2 on them
+                p.out = b.kheat;
+                p.part = nullptr;
+                rc = esa::launch_final(p, stream);
+                if (!rc) rc = esa::launch_keypoints_final2(p.out, n * p.K, height, width, b.kp, b.idx, b.kpart, b.kws, stream);
             } else if (b.kp && !c.final_wpk) {         // esahrnet_forward_keypoints, VALU output layer: no heat-maps at all
                 p.out = nullptr;
                 p.part = b.kpart;
@@ -1964,15 +1997,16 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
     return 0;
 }
 
-// kp_dev != nullptr: esahrnet_forward_keypoints (heat_dev and part_dev unused)
+// kp_dev != nullptr: esahrnet_forward_keypoints, or with final2 esahrnet_forward_keypoints_final2 (heat_dev and part_dev unused)
 static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, int width,
                        void* heat_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream_,
-                       hipEvent_t* events, void* part_dev = nullptr, void* kp_dev = nullptr, void* idx_dev = nullptr) {
+                       hipEvent_t* events, void* part_dev = nullptr, void* kp_dev = nullptr, void* idx_dev = nullptr,
+                       bool final2 = false) {
     if (!h || !x_dev || !(heat_dev || kp_dev) || !ws_dev) return fail("forward: null argument");
     if (!h->committed) return fail("forward: esahrnet_commit has not been called");
     if (plan_shape(*h, n, height, width)) return 1;
-    const KpScratch ks = kp_dev ? kp_scratch(*h, n, height, width) : KpScratch{};
-    const size_t need = h->sp.bytes + ks.heat + ks.part;
+    const KpScratch ks = kp_dev ? kp_scratch(*h, n, height, width, final2) : KpScratch{};
+    const size_t need = h->sp.bytes + ks.heat + ks.part + ks.bmax;
     if (ws_bytes < need) return fail("forward: workspace too small (%zu < %zu)", ws_bytes, need);
     if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("forward: workspace must be 256-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -1982,6 +2016,9 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
         bufs.idx = static_cast<int*>(idx_dev);
         bufs.kheat = reinterpret_cast<float*>(bufs.ws + h->sp.bytes);
         bufs.kpart = reinterpret_cast<float2*>(bufs.ws + h->sp.bytes + ks.heat);
+        bufs.final2 = final2;
+        bufs.kbmax = reinterpret_cast<float*>(bufs.ws + h->sp.bytes + ks.heat + ks.part);
+        bufs.kws = ks.part;
     }
     int op_index = 0;
     if (events && hipEventRecord(events[0], stream) != hipSuccess) return fail("forward: hipEventRecord failed");
@@ -2099,6 +2136,20 @@ int esahrnet_forward_keypoints(esahrnet_handle h, const void* x_dev, int n, int 
                                void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
     if (!h || !kp_dev) return fail("forward_keypoints: null argument");
     return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev);
+}
+
+int esahrnet_keypoints_final2_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
+    if (!h || !bytes) return fail("keypoints_final2_forward_workspace_bytes: null argument");
+    if (plan_shape(*h, n, height, width)) return 1;
+    const KpScratch ks = kp_scratch(*h, n, height, width, true);
+    *bytes = h->sp.bytes + ks.heat + ks.part + ks.bmax;
+    return 0;
+}
+
+int esahrnet_forward_keypoints_final2(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* kp_dev,
+                                      void* idx_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
+    if (!h || !kp_dev) return fail("forward_keypoints_final2: null argument");
+    return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev, true);
 }
 
 int esahrnet_keypoints_finish(const void* heat_dev, const void* part_dev, int ntiles, int n, int k, int height, int width,

@@ -1,6 +1,7 @@
 // refine.h — integer peak -> sub-pixel keypoint, the one refinement every keypoint kernel uses (keypoints.hip: the heat-map
 // sweep and the finishes over per-tile maxima, NCHW or NHWC; head.hip: the finish of the keypoints-only VALU output layer),
-// and the Newton step of the second decoder, get_final2 (keypoints_final2.hip).
+// and the pieces every get_final2 kernel shares (keypoints_final2.hip's tile pass and finish over NCHW or NHWC heat-maps; head.hip's
+// blurring output layer and its finish): the f64 blur taps, the Newton step and the end of the finish.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -74,6 +75,19 @@ constexpr double kFinal2Gauss[11] = {0x1.20c2564ee6770p-7, 0x1.bcb86a082c301p-6,
                                      0x1.6a7e1d504a91ep-3, 0x1.9ac20a36ea596p-3, 0x1.6a7e1d504a91ep-3, 0x1.f2464c62edaf4p-4,
                                      0x1.0ab50979aaf94p-4, 0x1.bcb86a082c301p-6, 0x1.20c2564ee6770p-7};
 
+__device__ __forceinline__ float max_nan(float m, float v) { return (v > m || v != v) ? v : m; }   // np.max: NaN wins
+
+// sum_t G[t] * p[t * stride], t = 0..10 in this order, in f64 without fma: the one summation of the blur's row and column
+// passes, in every get_final2 kernel (the tile passes, the finishes) and in the host restatement
+template <class V>
+__device__ __forceinline__ double blur_taps(V p) {
+#pragma clang fp contract(off)
+    double a = kFinal2Gauss[0] * (double)p(0);
+#pragma unroll
+    for (int t = 1; t < 11; ++t) a = a + kFinal2Gauss[t] * (double)p(t);
+    return a;
+}
+
 // The 13 blurred points the Newton step reads: 0..8 as refine_point_dx / _dy, then 9 / 10 / 11 / 12 at (y-1, x-1),
 // (y-1, x+1), (y+1, x-1), (y+1, x+1).
 __device__ __forceinline__ int final2_point_dx(int pt) { return pt < 9 ? refine_point_dx(pt) : pt & 1 ? -1 : 1; }
@@ -107,6 +121,37 @@ __device__ __forceinline__ void final2_newton(const float* h, int px, int py, fl
             fx = (float)((double)px + ox);
             fy = (float)((double)py + oy);
         }
+    }
+}
+
+// The end of get_final2's finish for one plane, one wave: bv / bm the plane's first raw maximum and its blurred maximum, bi
+// the raw maximum's index (0 for an all -inf / all-NaN plane).  blurred(pt) is the f32 blurred value at final2 point pt; lanes
+// 0..12 call it, and only when the step is taken.  peak() is the raw value at bi (lane 0).  Lane 0 writes kp[plane] (x, y,
+// peak) and, when idx_out is not null, idx_out[plane] = bi.
+template <class Blurred, class Peak>
+__device__ __forceinline__ void final2_finish(float bv, int bi, float bm, int H, int W, Blurred blurred, Peak peak, float* kp,
+                                              int* idx_out, int plane) {
+#pragma clang fp contract(off)
+    const int px = bi % W, py = bi / W;
+    // gaussian_blur's rescale factor origin_max / max(blurred), f32 (inference.py:110)
+    const float s = (float)((double)bv / (double)bm);
+    const bool go = 1 < px && px < W - 2 && 1 < py && py < H - 2 && isfinite(bv) && isfinite(bm) && isfinite(s);
+    float lv = 0.f;                                        // lane j < 13: log of the rescaled, clamped blurred value at point j
+    if (go && threadIdx.x < 13) {
+        const int j = threadIdx.x;
+        lv = final2_log(blurred(j), s);
+    }
+    float h[13];
+#pragma unroll
+    for (int j = 0; j < 13; ++j) h[j] = __shfl(lv, j);
+    if (threadIdx.x == 0) {
+        float fx = (float)px, fy = (float)py;
+        if (go) final2_newton(h, px, py, fx, fy);
+        float* kp3 = kp + (size_t)plane * 3;
+        kp3[0] = fx;
+        kp3[1] = fy;
+        kp3[2] = peak();
+        if (idx_out) idx_out[plane] = bi;
     }
 }
 

@@ -134,6 +134,12 @@ __device__ __forceinline__ void join8_fmt(uint4 a, uint4 b, float v[8], bool f32
 __device__ __forceinline__ void load8_fmt(const char* p, float v[8], bool f32) {
     join8_fmt(*reinterpret_cast<const uint4*>(p), *reinterpret_cast<const uint4*>(p + 16), v, f32);
 }
+// channel j (0..7) of such a group alone, the bits join8_fmt gives it
+__device__ __forceinline__ float load1_fmt(const char* p, int j, bool f32) {
+    if (f32) return *reinterpret_cast<const float*>(p + 4 * j);
+    const uint16_t* h = reinterpret_cast<const uint16_t*>(p);
+    return bf16_bits_to_f32(h[j]) + bf16_bits_to_f32(h[8 + j]);
+}
 __device__ __forceinline__ void store8_fmt(char* p, const float v[8], bool f32) {
     uint4 a, b;
     if (f32) {

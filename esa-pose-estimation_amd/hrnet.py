@@ -147,7 +147,8 @@ class HighResolutionNet(nn.Module):
         without writing heat-maps (include/esahrnet.h esahrnet_forward_keypoints), bit-identical to
         inference.heatmaps_to_keypoints(net(x)); "keypoints+index": (kp, idx int32 [N,K] = row * W + column).
         refine="get_final2" (keypoint outputs only): the second decoder, bit-identical to
-        inference.heatmaps_to_keypoints(net(x), refine="get_final2"); the heat-maps go to workspace scratch."""
+        inference.heatmaps_to_keypoints(net(x), refine="get_final2"), without writing heat-maps either
+        (include/esahrnet.h esahrnet_forward_keypoints_final2)."""
         if self.training:
             raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
                                "(the reference callers do, val.py:95 / demo.py:80)")
@@ -267,7 +268,7 @@ class _Runtime:
         self.dev_locks = {}      # device index -> lock serialising the enqueues of that device's handle
         self.ws = {}             # (device, stream, n, h, w, keep) -> uint8 tensor, insertion order = LRU order
         self.kp_ws = {}          # the same for esahrnet_forward_keypoints (its own size: esahrnet_keypoints_workspace_bytes)
-        self.f2_ws = {}          # the same for forward_final2: forward scratch + heat-maps + esahrnet_keypoints_final2's maxima
+        self.f2_ws = {}          # the same for forward_final2 (esahrnet_keypoints_final2_forward_workspace_bytes)
         self.part_tiles = {}     # (handle, h, w) -> tiles per heat-map with partial maxima (0: none)
         self._probe = self._create(-1)
 
@@ -354,15 +355,6 @@ class _Runtime:
             self.kp_ws.clear()
             self.f2_ws.clear()
 
-    def _final2_layout(self, h, n, hh, ww):
-        """forward_final2's scratch: (forward workspace bytes, heat-map bytes, keypoints_final2 bytes), each 256-aligned."""
-        fw, f2 = C.c_size_t(), C.c_size_t()
-        k = self.cfg.num_keypoints
-        _lib.check(self.lib.esahrnet_workspace_bytes(h, n, hh, ww, C.byref(fw)))
-        _lib.check(self.lib.esahrnet_keypoints_final2_workspace_bytes(n, k, hh, ww, C.byref(f2)))
-        a = lambda b: (b + 255) & ~255
-        return a(fw.value), a(n * k * hh * ww * 4), f2.value
-
     def _workspace(self, h, device, stream, n, hh, ww, keep, kind="forward"):
         """Scratch for one forward.  Contract: while the stream is being CAPTURED into a HIP
         graph the scratch is a fresh tensor allocated inside the capture (the graph's private pool owns it, like
@@ -374,7 +366,7 @@ class _Runtime:
             _lib.check(self.lib.esahrnet_keypoints_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
             cache = self.kp_ws
         elif kind == "final2":
-            nbytes.value = sum(self._final2_layout(h, n, hh, ww))
+            _lib.check(self.lib.esahrnet_keypoints_final2_forward_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
             cache = self.f2_ws
         else:
             _lib.check(self.lib.esahrnet_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
@@ -460,9 +452,9 @@ class _Runtime:
         return kp, idx
 
     def forward_final2(self, module, x0, want_index):
-        """net(x, output="keypoints", refine="get_final2"): esahrnet_forward writes the heat-maps into workspace scratch, then
-        esahrnet_keypoints_final2 decodes them; nothing but (kp, idx) reaches caller memory.  Same device lock, workspace
-        contract (graph capture included) and record_stream handling as forward()."""
+        """net(x, output="keypoints", refine="get_final2"): esahrnet_forward_keypoints_final2, the forward with get_final2 in
+        place of its last launch; nothing but (kp, idx) reaches caller memory.  Same device lock, workspace contract (graph
+        capture included) and record_stream handling as forward()."""
         x = self._check_input(module, x0)
         n, _, hh, ww = x.shape
         dev = x.device
@@ -471,15 +463,13 @@ class _Runtime:
         with self._device_lock(dev.index):
             h = self._handle_for(module, dev)
             _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
-            fw, hb, f2 = self._final2_layout(h, n, hh, ww)
-            ws, ws_ptr, _ = self._workspace(h, dev, ts, n, hh, ww, False, kind="final2")
+            ws, ws_ptr, nbytes = self._workspace(h, dev, ts, n, hh, ww, False, kind="final2")
             kp = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
             idx = torch.empty((n, k), dtype=torch.int32, device=dev) if want_index else None
             with torch.cuda.device(dev):
-                _lib.check(self.lib.esahrnet_forward(h, x.data_ptr(), n, hh, ww, ws_ptr + fw, ws_ptr, fw, C.c_void_p(ts.cuda_stream)))
-                _lib.check(self.lib.esahrnet_keypoints_final2(ws_ptr + fw, n, k, hh, ww, kp.data_ptr(),
-                                                              idx.data_ptr() if want_index else None, ws_ptr + fw + hb, f2,
-                                                              C.c_void_p(ts.cuda_stream)))
+                _lib.check(self.lib.esahrnet_forward_keypoints_final2(h, x.data_ptr(), n, hh, ww, kp.data_ptr(),
+                                                                      idx.data_ptr() if want_index else None, ws_ptr, nbytes,
+                                                                      C.c_void_p(ts.cuda_stream)))
         ws.record_stream(ts)
         x.record_stream(ts)
         return kp, idx

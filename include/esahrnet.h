@@ -167,6 +167,22 @@ int esahrnet_keypoints_workspace_bytes(esahrnet_handle h, int n, int height, int
 int esahrnet_forward_keypoints(esahrnet_handle h, const void* x_dev, int n, int height, int width,
                                void* kp_dev, void* idx_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
 
+/* ---- forward straight to get_final2 keypoints ----------------------------------------------------------------
+ * esahrnet_forward_keypoints_final2 is esahrnet_forward_keypoints with the second decoder: kp_dev and idx_dev are
+ * bit-identical to esahrnet_forward followed by esahrnet_keypoints_final2 (same arg-max, peak, step rule, NaN, ties and
+ * non-finite handling).  ws_dev: esahrnet_keypoints_final2_forward_workspace_bytes bytes, 256-byte aligned.  Same contract:
+ * no allocation, no synchronisation, graph-capturable, esahrnet_set_debug_keep and the multi-lane schedule apply.
+ *   seg_hrnet / seg_hrnet2, VALU output layer: the output layer is evaluated over each 22 x 22 tile and the blur's 5-pixel
+ *     halo, blurred in LDS, and only the tile's raw and blurred maxima are kept (12 bytes per tile and heat-map); the finish
+ *     evaluates the output layer again at the 15 x 15 pixels around the peak that the 13 blurred values read.
+ *   seg_hrnet / seg_hrnet2, matrix-core output layer: the heat-maps go to the workspace instead of caller memory, then
+ *     esahrnet_keypoints_final2's kernels (no new arithmetic: the gain is one call and no caller buffer).
+ *   seg_hrnet3: esahrnet_keypoints_final2's kernels read the NHWC heat-maps already in the workspace; no NCHW copy is made.
+ * Except for the matrix-core form, the workspace has no n * K * height * width term beyond esahrnet_workspace_bytes'. */
+int esahrnet_keypoints_final2_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes);
+int esahrnet_forward_keypoints_final2(esahrnet_handle h, const void* x_dev, int n, int height, int width,
+                                      void* kp_dev, void* idx_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+
 /* Loader stage in front of the path (data_load_val.py:139-187): for each of n 8-bit frames
  * [frame_h][frame_w] take the clamped box boxes[i] = (x0, y0, x1, y1) (int32, device), edge-pad it the
  * way the reference does, resize to scale x scale (OpenCV 8-bit INTER_LINEAR arithmetic) and write
