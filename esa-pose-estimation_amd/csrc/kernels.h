@@ -325,6 +325,20 @@ int launch_keypoints_final2_nhwc(int fmt, const char* x, int N, int C, int H, in
 int launch_crops(const unsigned char* frames, const int* boxes, float* out, int N, int FH, int FW, int S,
                  float mean, float std_, hipStream_t s);
 
+// ---- the loader on the device (frontend.hip) ------------------------------------------------------------------------
+// det int32 [m][4] detector boxes (x, y, x2, y2) -> crop int32 [m][4] (x_new, y_new, w_new, h_new), rates f64 [m], valid
+// int32 [m]; rule 0: data_load_val.py:127-158, 1: data_load4.py:112-141.  frame_idx (may be null): a crop whose frame index
+// is outside [0, nframes) is invalid too.
+int launch_boxes(const int* det, const int* frame_idx, int nframes, int m, int FH, int FW, int S, int rule, int* crop,
+                 double* rates, int* valid, hipStream_t s);
+// launch_crops with a frame index per crop (null: identity), rgb = 1: RGB8 interleaved frames reduced by PIL's convert('L'),
+// and zeros for crops with valid[i] == 0 (valid may be null), a frame index out of range or a box outside the frame.
+// m * S <= 2^24 - 1 (one block per output row)
+int launch_crops_ex(const unsigned char* frames, int nframes, int FH, int FW, int rgb, const int* frame_idx, const int* boxes,
+                    const int* valid, float* out, int m, int S, float mean, float std_, hipStream_t s);
+// kp f32 [m][K][3] -> NaN and idx int32 [m][K] (may be null) -> -1 in the rows with valid[i] == 0
+int launch_mark_invalid(const int* valid, int m, int K, float* kp, int* idx, hipStream_t s);
+
 // ---- layout conversion f32 NCHW <-> SB (layout.hip) ----------------------------------------
 int launch_nchw_to_sb(const float* x, int N, int C, int H, int W, char* y, int Cp, hipStream_t s);
 int launch_sb_to_nchw(const char* x, int N, int C, int H, int W, int Cp, float* y, hipStream_t s);

@@ -2210,6 +2210,105 @@ int esahrnet_crops(const void* frames_dev, int n, int frame_h, int frame_w, cons
     return 0;
 }
 
+// ---- the loader on the device: detector boxes + frames -> crops -> keypoints (frontend.hip) ----------------------------
+static const int kFrontendMaxRows = 0xffffff;       // launch_crops_ex: one block per output row, m * scale of them
+
+static int check_boxes_args(const char* who, int m, int frame_h, int frame_w, int scale, int rule) {
+    if (m <= 0) return fail("%s: the number of boxes must be positive (got %d)", who, m);
+    if (frame_h <= 0 || frame_w <= 0) return fail("%s: bad frame size %d x %d", who, frame_h, frame_w);
+    if (scale <= 0 || (long long)m * scale > kFrontendMaxRows)
+        return fail("%s: scale %d with %d boxes (scale positive, boxes * scale at most %d)", who, scale, m, kFrontendMaxRows);
+    if (rule != 0 && rule != 1) return fail("%s: rule=%d unknown (0: val, data_load_val.py; 1: train / demo, data_load4.py)", who, rule);
+    return 0;
+}
+
+static int check_crops_args(const char* who, int nframes, int pixel_format, float stdv) {
+    if (nframes <= 0) return fail("%s: the number of frames must be positive (got %d)", who, nframes);
+    if (pixel_format != 0 && pixel_format != 1) return fail("%s: pixel_format=%d unknown (0: gray8, 1: RGB8 interleaved)", who, pixel_format);
+    if (!(stdv > 0.f)) return fail("%s: stdv must be positive", who);
+    return 0;
+}
+
+int esahrnet_boxes(const void* det_boxes_dev, int m, int frame_h, int frame_w, int scale, int rule, void* crop_boxes_dev,
+                   void* rates_dev, void* valid_dev, esahrnet_stream stream) {
+    if (!det_boxes_dev || !crop_boxes_dev || !rates_dev || !valid_dev) return fail("boxes: null argument");
+    if (check_boxes_args("boxes", m, frame_h, frame_w, scale, rule)) return 1;
+    const int rc = esa::launch_boxes(static_cast<const int*>(det_boxes_dev), nullptr, 0, m, frame_h, frame_w, scale, rule,
+                                     static_cast<int*>(crop_boxes_dev), static_cast<double*>(rates_dev),
+                                     static_cast<int*>(valid_dev), static_cast<hipStream_t>(stream));
+    if (rc) return fail("boxes: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
+int esahrnet_crops_ex(const void* frames_dev, int nframes, int frame_h, int frame_w, int pixel_format, const void* frame_idx_dev,
+                      const void* crop_boxes_dev, const void* valid_dev, int m, int scale, float mean, float stdv, void* out_dev,
+                      esahrnet_stream stream) {
+    if (!frames_dev || !crop_boxes_dev || !out_dev) return fail("crops_ex: null argument");
+    if (check_boxes_args("crops_ex", m, frame_h, frame_w, scale, 0) || check_crops_args("crops_ex", nframes, pixel_format, stdv)) return 1;
+    if (!frame_idx_dev && m != nframes)
+        return fail("crops_ex: %d crops of %d frames need a frame index (NULL is the identity: crop i reads frame i)", m, nframes);
+    const int rc = esa::launch_crops_ex(static_cast<const unsigned char*>(frames_dev), nframes, frame_h, frame_w, pixel_format,
+                                        static_cast<const int*>(frame_idx_dev), static_cast<const int*>(crop_boxes_dev),
+                                        static_cast<const int*>(valid_dev), static_cast<float*>(out_dev), m, scale, mean, stdv,
+                                        static_cast<hipStream_t>(stream));
+    if (rc) return fail("crops_ex: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
+static size_t frontend_crop_bytes(int m, int scale) { return ((size_t)m * scale * scale * sizeof(float) + 255) & ~(size_t)255; }
+
+int esahrnet_frames_keypoints_workspace_bytes(esahrnet_handle h, int m, int scale, int decoder, size_t* bytes) {
+    if (!h || !bytes) return fail("frames_keypoints_workspace_bytes: null argument");
+    if (decoder != 0 && decoder != 1) return fail("frames_keypoints: decoder=%d unknown (0: get_final, 1: get_final2)", decoder);
+    if (h->cfg.cin != 1)
+        return fail("frames_keypoints: the loader makes 1-channel crops (data_load_val.py / data_load4.py); this handle takes %d channels",
+                    h->cfg.cin);
+    if (m <= 0 || scale <= 0 || (long long)m * scale > kFrontendMaxRows)
+        return fail("frames_keypoints: scale %d with %d boxes (both positive, boxes * scale at most %d)", scale, m, kFrontendMaxRows);
+    size_t fw = 0;
+    if (decoder ? esahrnet_keypoints_final2_forward_workspace_bytes(h, m, scale, scale, &fw)
+                : esahrnet_keypoints_workspace_bytes(h, m, scale, scale, &fw))
+        return 1;
+    *bytes = frontend_crop_bytes(m, scale) + fw;
+    return 0;
+}
+
+int esahrnet_frames_keypoints(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w, int pixel_format,
+                              const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale, int rule, float mean,
+                              float stdv, int decoder, void* kp_dev, void* idx_dev, void* crop_boxes_dev, void* rates_dev,
+                              void* valid_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
+    if (!h || !frames_dev || !det_boxes_dev || !kp_dev || !crop_boxes_dev || !rates_dev || !valid_dev || !ws_dev)
+        return fail("frames_keypoints: null argument");
+    // everything that can be refused is refused here, before the first launch
+    if (check_boxes_args("frames_keypoints", m, frame_h, frame_w, scale, rule) ||
+        check_crops_args("frames_keypoints", nframes, pixel_format, stdv))
+        return 1;
+    if (!frame_idx_dev && m != nframes)
+        return fail("frames_keypoints: %d boxes on %d frames need a frame index (NULL is the identity: box i lies on frame i)", m, nframes);
+    if (!h->committed) return fail("frames_keypoints: esahrnet_commit has not been called");
+    size_t need = 0;
+    if (esahrnet_frames_keypoints_workspace_bytes(h, m, scale, decoder, &need)) return 1;
+    if (ws_bytes < need) return fail("frames_keypoints: workspace too small (%zu < %zu)", ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("frames_keypoints: workspace must be 256-byte aligned");
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc = esa::launch_boxes(static_cast<const int*>(det_boxes_dev), static_cast<const int*>(frame_idx_dev), nframes, m, frame_h,
+                               frame_w, scale, rule, static_cast<int*>(crop_boxes_dev), static_cast<double*>(rates_dev),
+                               static_cast<int*>(valid_dev), st);
+    if (!rc)
+        rc = esa::launch_crops_ex(static_cast<const unsigned char*>(frames_dev), nframes, frame_h, frame_w, pixel_format,
+                                  static_cast<const int*>(frame_idx_dev), static_cast<const int*>(crop_boxes_dev),
+                                  static_cast<const int*>(valid_dev), static_cast<float*>(ws_dev), m, scale, mean, stdv, st);
+    if (rc) return fail("frames_keypoints: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    const size_t head = frontend_crop_bytes(m, scale);
+    if (run_forward(h, ws_dev, m, scale, scale, nullptr, static_cast<char*>(ws_dev) + head, ws_bytes - head, stream, nullptr, nullptr,
+                    kp_dev, idx_dev, decoder == 1))
+        return 1;
+    rc = esa::launch_mark_invalid(static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints, static_cast<float*>(kp_dev),
+                                  static_cast<int*>(idx_dev), st);
+    if (rc) return fail("frames_keypoints: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
 int esahrnet_flops_per_crop(esahrnet_handle h, int height, int width, double* flops) {
     if (!h || !flops) return fail("flops_per_crop: null argument");
     std::vector<int> lh, lw;

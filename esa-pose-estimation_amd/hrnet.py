@@ -25,7 +25,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, crops
 from .fold import fold_conv
 from .inference import check_refine
 
@@ -169,6 +169,29 @@ class HighResolutionNet(nn.Module):
         """net(x, output="keypoints"): f32 cuda [N,K,3] keypoints straight from the crops."""
         return self(x0, output="keypoints")
 
+    def frames_to_keypoints(self, frames: torch.Tensor, det_boxes, frame_idx=None, scale: int = 256, rule: str = "val",
+                            refine: str = "get_final", mean=None, std: float = crops.STD, pixel_format=None):
+        """Camera frames and raw detector boxes to keypoints in one library call (include/esahrnet.h
+        esahrnet_frames_keypoints): box rule, crops, forward and decoder on the device, nothing allocated or synchronised in
+        between, capturable into a graph.  Arguments as crops.crop_batch_device; mean defaults to the rule's loader
+        (crops.MEAN_VAL / crops.MEAN_TRAIN).  -> (kp f32 [m,K,3], crop_boxes int32 [m,4], rates f64 [m], valid int32 [m]),
+        all on the device; kp equals crops.crop_batch -> net(x, output="keypoints", refine=refine) bit for bit, except that
+        the rows of an invalid crop (empty box, frame index out of range: valid == 0) are NaN."""
+        return self._frames_to_keypoints(frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format)[:4]
+
+    def _frames_to_keypoints(self, frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format):
+        """frames_to_keypoints, plus (idx int32 [m,K], packed): every output is a view of `packed` (one uint8 buffer), so a
+        caller that needs them on the host fetches them with one copy (pipeline.estimate_poses)."""
+        if self.training:
+            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
+                               "(the reference callers do, val.py:95 / demo.py:80)")
+        check_refine(refine)
+        rule_n, fmt, m = crops.check_device_loader_args(frames, det_boxes, frame_idx, rule, pixel_format)
+        if mean is None:
+            mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
+        return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
+                                         1 if refine == "get_final2" else 0)
+
     # ---- extras of the MI355X path ---------------------------------------------------------------
     @property
     def num_keypoints(self):
@@ -269,6 +292,7 @@ class _Runtime:
         self.ws = {}             # (device, stream, n, h, w, keep) -> uint8 tensor, insertion order = LRU order
         self.kp_ws = {}          # the same for esahrnet_forward_keypoints (its own size: esahrnet_keypoints_workspace_bytes)
         self.f2_ws = {}          # the same for forward_final2 (esahrnet_keypoints_final2_forward_workspace_bytes)
+        self.fr_ws = {}          # the same for frames_keypoints (esahrnet_frames_keypoints_workspace_bytes), both decoders
         self.part_tiles = {}     # (handle, h, w) -> tiles per heat-map with partial maxima (0: none)
         self._probe = self._create(-1)
 
@@ -354,6 +378,7 @@ class _Runtime:
             self.ws.clear()
             self.kp_ws.clear()
             self.f2_ws.clear()
+            self.fr_ws.clear()
 
     def _workspace(self, h, device, stream, n, hh, ww, keep, kind="forward"):
         """Scratch for one forward.  Contract: while the stream is being CAPTURED into a HIP
@@ -368,6 +393,9 @@ class _Runtime:
         elif kind == "final2":
             _lib.check(self.lib.esahrnet_keypoints_final2_forward_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
             cache = self.f2_ws
+        elif kind in ("frames", "frames_final2"):       # n crops of hh x hh; `keep` tells the two decoders' entries apart
+            _lib.check(self.lib.esahrnet_frames_keypoints_workspace_bytes(h, n, hh, int(kind == "frames_final2"), C.byref(nbytes)))
+            cache = self.fr_ws
         else:
             _lib.check(self.lib.esahrnet_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
             cache = self.ws
@@ -473,6 +501,49 @@ class _Runtime:
         ws.record_stream(ts)
         x.record_stream(ts)
         return kp, idx
+
+    def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder):
+        """esahrnet_frames_keypoints (arguments already checked by crops.check_device_loader_args).  The outputs are views
+        of one packed buffer: rates f64 [m] | kp f32 [m,K,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,K].
+        Same device lock, weight-staleness key, workspace contract (graph capture included) and record_stream handling as
+        forward()."""
+        if module._cin != 1:
+            raise ValueError(f"the loader makes 1-channel crops; this network takes {module._cin} channels")
+        if "_master" not in module.__dict__:
+            p = module._weight_tensors()[0]
+            if p.device != frames.device:
+                raise RuntimeError(f"frames on {frames.device} but parameters on {p.device}")
+        frames = frames.contiguous()
+        dev = frames.device
+        nframes, fh, fw = frames.shape[:3]
+        k = module._k
+        ts = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            det = crops.to_device_int32(det_boxes, dev)
+            fidx = None if frame_idx is None else crops.to_device_int32(frame_idx, dev)
+            sizes = (8 * m, 12 * m * k, 16 * m, 4 * m, 4 * m * k)
+            offs = [0]
+            for b in sizes:
+                offs.append(offs[-1] + b)
+            packed = torch.empty(offs[-1], dtype=torch.uint8, device=dev)
+            rates = packed[offs[0]:offs[1]].view(torch.float64)
+            kp = packed[offs[1]:offs[2]].view(torch.float32).view(m, k, 3)
+            boxes = packed[offs[2]:offs[3]].view(torch.int32).view(m, 4)
+            valid = packed[offs[3]:offs[4]].view(torch.int32)
+            idx = packed[offs[4]:offs[5]].view(torch.int32).view(m, k)
+            with self._device_lock(dev.index):
+                h = self._handle_for(module, dev)
+                _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
+                ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, bool(decoder),
+                                                       kind="frames_final2" if decoder else "frames")
+                _lib.check(self.lib.esahrnet_frames_keypoints(
+                    h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m,
+                    scale, rule, mean, std, decoder, kp.data_ptr(), idx.data_ptr(), boxes.data_ptr(), rates.data_ptr(),
+                    valid.data_ptr(), ws_ptr, ws_bytes, C.c_void_p(ts.cuda_stream)))
+        for t in (ws, frames, det, fidx):
+            if t is not None:
+                t.record_stream(ts)
+        return kp, boxes, rates, valid, idx, packed
 
     def _partial_tiles(self, h, hh, ww):
         if os.environ.get("ESAHRNET_NO_PARTIALS"):

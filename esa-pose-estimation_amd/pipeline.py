@@ -109,15 +109,41 @@ class PoseFailure(ValueError):
 
 def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256, thresh: float = 0.8,
                    min_k: int = 24, distributed: bool = False, pool=None, native: bool = True,
-                   on_fail: str = "raise", keypoints_only: bool = False, refine: str = "get_final"):
+                   on_fail: str = "raise", keypoints_only: bool = False, refine: str = "get_final",
+                   device_loader: bool = False, frame_idx=None, rule: str = "val"):
     """One batch of the val.py:136-233 loop.  frames uint8 cuda [N,H,W]; bboxes N x (x, y, x2, y2);
     kp3d [K3, 3] model keypoints; K camera matrix.  -> list of (q [w,x,y,z], t) per image.
     An image without a solution (the native solver reports it as a NaN row; the reference would die inside
     cv2.solvePnPRansac) raises PoseFailure, or with on_fail="nan" is returned as the NaN row for the caller to
     deal with — it is never passed on silently.  keypoints_only=True: the net goes straight to keypoints
     (net(x, output="keypoints"): the same bits, no heat-maps written).  refine="get_final2": the reference's second
-    decoder (inference.get_final2: blur + full-Hessian step) instead of get_final."""
+    decoder (inference.get_final2: blur + full-Hessian step) instead of get_final.
+    device_loader=True: net.frames_to_keypoints does the box rule (`rule`: "val" / "train"), the crops, the forward and the
+    decoder in one library call; keypoints, crop boxes, rates and valid flags come back in ONE device->host copy of one
+    packed buffer.  bboxes are integers then, several may lie on one frame (frame_idx[i] = frame of box i; frames may be RGB
+    [N,H,W,3]), and a crop the loader could not make (empty box, frame index out of range) has no pose: on_fail applies."""
     inference.check_refine(refine)
+    if device_loader:
+        if distributed:
+            raise ValueError("device_loader=True runs on one device (distributed=True shards crops that exist on the host side)")
+        with torch.no_grad():
+            out = net._frames_to_keypoints(frames, bboxes, frame_idx, scale, rule, refine, None, crops.STD, None)
+        m, k = out[0].shape[:2]
+        host = out[5].cpu().numpy()                         # the only device->host copy
+        offs = np.cumsum([0, 8 * m, 12 * m * k, 16 * m, 4 * m])
+        rates = host[offs[0]:offs[1]].view(np.float64)
+        kp = host[offs[1]:offs[2]].view(np.float32).reshape(m, k, 3)
+        boxes = host[offs[2]:offs[3]].view(np.int32).reshape(m, 4).tolist()
+        valid = host[offs[3]:offs[4]].view(np.int32)
+        # an invalid crop (NaN keypoint rows) is kept away from the solver and reported as the NaN row that "no solution" is
+        bad = valid == 0
+        rates = [1.0 if b else float(r) for r, b in zip(rates, bad)]
+        poses = poses_from_keypoints(np.where(bad[:, None, None], np.float32(0), kp), boxes, rates, kp3d, K, thresh, min_k,
+                                     pool, native)
+        poses = [(np.full(4, np.nan), np.full(3, np.nan)) if b else p for p, b in zip(poses, bad)]
+        return _checked_poses(poses, on_fail)
+    if frame_idx is not None or rule != "val":
+        raise ValueError("frame_idx and rule belong to device_loader=True (crops.crop_batch: one val box per frame)")
     rk = {} if refine == "get_final" else {"refine": refine}
     x, boxes, rates = crops.crop_batch(frames, bboxes, scale)
     with torch.no_grad():
@@ -128,7 +154,10 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
         else:
             kp = inference.heatmaps_to_keypoints(net(x), **rk)
     kp = kp.cpu().numpy()                                   # the only device->host copy: N*K*3 floats
-    poses = poses_from_keypoints(kp, boxes, rates, kp3d, K, thresh, min_k, pool, native)
+    return _checked_poses(poses_from_keypoints(kp, boxes, rates, kp3d, K, thresh, min_k, pool, native), on_fail)
+
+
+def _checked_poses(poses, on_fail):
     if on_fail == "raise":
         bad = [i for i, (q, t) in enumerate(poses) if not (np.all(np.isfinite(q)) and np.all(np.isfinite(t)))]
         if bad:

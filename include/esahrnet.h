@@ -190,6 +190,42 @@ int esahrnet_forward_keypoints_final2(esahrnet_handle h, const void* x_dev, int 
 int esahrnet_crops(const void* frames_dev, int n, int frame_h, int frame_w, const void* boxes_dev, int scale,
                    float mean, float stdv, void* out_dev, esahrnet_stream stream);
 
+/* ---- the loader on the device: detector boxes and frames to keypoints ------------------------------------------------
+ * The box rule, the crops and the forward in one call, so that nothing between the camera frame and the keypoints passes
+ * through the host (data_load_val.py:103-195 / data_load4.py:103-165 + val.py:146-180).  All four allocate nothing, do not
+ * synchronise and may be captured into a graph; every argument error is reported before anything is enqueued.
+ *
+ * esahrnet_boxes: det_boxes_dev int32 [m][4] detector boxes (x, y, x2, y2) -> crop_boxes_dev int32 [m][4] = (x_new, y_new,
+ *   w_new, h_new) ((w_new, h_new) the far corner), rates_dev f64 [m] (1.0 when the crop's size equals scale, else scale /
+ *   size; size = max(w_new - x_new, h_new - y_new), IEEE division: inf for size 0), valid_dev int32 [m] (0: w_new <= x_new
+ *   or h_new <= y_new, the empty crop).  rule 0: ESAValDataSet (data_load_val.py:127-158); rule 1: ESADataSet
+ *   (data_load4.py:112-141: the box is forced square before the clamps).  Python's arithmetic: centre and half size by true
+ *   division in f64, 1.05 * size rounded before it is added, int() truncating toward zero.
+ * esahrnet_crops_ex: esahrnet_crops with (a) frame_idx_dev int32 [m] (NULL: identity, m == nframes): crop i reads frame
+ *   frame_idx[i]; (b) pixel_format 0: gray8 [nframes][frame_h][frame_w], 1: RGB8 interleaved [nframes][frame_h][frame_w][3],
+ *   each source pixel reduced as PIL's convert('L') does (data_load_val.py:110-117): L = (R*19595 + G*38470 + B*7471 +
+ *   0x8000) >> 16, before the resize; (c) valid_dev int32 [m] (NULL: all valid).  A crop with valid[i] == 0, a frame index
+ *   outside [0, nframes) or a box that is empty or leaves the frame is written as zeros.  crop_boxes_dev as esahrnet_boxes
+ *   wrote it.  On gray frames with the identity index out_dev f32 [m][1][scale][scale] is bit-identical to esahrnet_crops'.
+ * esahrnet_frames_keypoints: esahrnet_boxes -> esahrnet_crops_ex into the head of the workspace -> esahrnet_forward_keypoints
+ *   (decoder 0) or esahrnet_forward_keypoints_final2 (decoder 1) on the rest -> the rows of kp_dev f32 [m][K][3] (and of
+ *   idx_dev int32 [m][K], NULL: not written) whose crop is invalid become NaN (-1); valid rows are bit-identical to the calls it
+ *   is built from.  valid_dev here also is 0 for a frame index out of range.  crop_boxes_dev, rates_dev, valid_dev are outputs
+ *   the host pose stage needs (esahrnet_pnp_batch: boxes_xy, rates).  ws_dev: esahrnet_frames_keypoints_workspace_bytes bytes
+ *   (the chosen decoder's query for m crops of scale x scale plus the crop tensor), 256-byte aligned.  Handles with cin != 1
+ *   are refused: the reference has no loader for 3-channel crops. */
+int esahrnet_boxes(const void* det_boxes_dev, int m, int frame_h, int frame_w, int scale, int rule,
+                   void* crop_boxes_dev, void* rates_dev, void* valid_dev, esahrnet_stream stream);
+int esahrnet_crops_ex(const void* frames_dev, int nframes, int frame_h, int frame_w, int pixel_format,
+                      const void* frame_idx_dev, const void* crop_boxes_dev, const void* valid_dev, int m,
+                      int scale, float mean, float stdv, void* out_dev, esahrnet_stream stream);
+int esahrnet_frames_keypoints_workspace_bytes(esahrnet_handle h, int m, int scale, int decoder, size_t* bytes);
+int esahrnet_frames_keypoints(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                              int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m,
+                              int scale, int rule, float mean, float stdv, int decoder,
+                              void* kp_dev, void* idx_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev,
+                              void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+
 /* Host pose solve behind the path, for a batch (pnp.py:46-90 + cpnp.cpnp_m of val.py:194-209 + val.py:172-180,
  * 221-224): kp = host f32 [n][k][3] keypoint rows (x, y, peak) in crop coordinates as esahrnet_keypoints wrote
  * them; kp3d = f64 [k][3] model points; K9 = f64 row-major camera matrix; boxes_xy = int32 [n][2] crop origins;

@@ -1,0 +1,328 @@
+"""The loader on the device (include/esahrnet.h: esahrnet_boxes, esahrnet_crops_ex, esahrnet_frames_keypoints): box rules
+exactly as crops.val_box / crops.train_box, crops bit-identical to esahrnet_crops (with a frame index per crop and RGB frames
+reduced as PIL's convert('L')), the one-call form bit-identical to crop_batch -> net(x, output="keypoints"), invalid crops as
+NaN rows, the call captured into a graph, and pipeline.estimate_poses(device_loader=True)."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import test_crops_pipeline as TCP  # noqa: E402  (its scene: BOXES and the frames' recipe)
+import test_frontend_host as TFH  # noqa: E402  (the deterministic box sweep)
+
+pytestmark = pytest.mark.gpu
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@pytest.fixture(scope="module")
+def env():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a GPU (torch.cuda.is_available() is False)")
+    from esa_pose_estimation_amd import _lib, config, crops, pipeline, seg_hrnet2, seg_hrnet3, synth
+    return dict(lib=_lib.lib(), L=_lib, config=config, crops=crops, pipeline=pipeline, synth=synth, seg_hrnet2=seg_hrnet2,
+                seg_hrnet3=seg_hrnet3)
+
+
+@pytest.fixture(autouse=True)
+def _clean_env(monkeypatch):
+    for k in [k for k in os.environ if k.startswith("ESAHRNET_")]:
+        monkeypatch.delenv(k)
+
+
+def _frames(env, name, n, seed=3):
+    return torch.from_numpy(env["synth"].uniform(name, seed, (n, 1200, 1920), 0, 255.99).astype(np.uint8)).cuda()
+
+
+def _net(env, name):
+    if name == "seg_hrnet2":
+        net = env["seg_hrnet2"].get_seg_model(env["config"].make_config(), precision="fp32")           # W32
+    else:
+        net = env["seg_hrnet3"].get_seg_model(env["config"].make_config(widths=(16, 16, 32, 64)), precision="fp32")
+    sd = env["synth"].make_state_dict({k: v.shape for k, v in net.state_dict().items()}, seed=53)
+    net.load_state_dict(sd, strict=True)
+    return net.cuda().eval()
+
+
+@pytest.fixture(scope="module")
+def nets(env):
+    return {name: _net(env, name) for name in ("seg_hrnet2", "seg_hrnet3")}
+
+
+def _bits(a, b):
+    """Bit-identical tensors (NaN included)."""
+    a, b = a.contiguous(), b.contiguous()
+    it = {4: torch.int32, 8: torch.int64}[a.element_size()]
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.view(it), b.view(it))
+
+
+# ---- 4. boxes ---------------------------------------------------------------------------------------------------------------
+def det_boxes(scale=256):
+    boxes = list(TFH.sweep_boxes())                                             # 700: every border clamp, double clamps
+    rng = np.random.default_rng(11)
+    for _ in range(1400):                                                       # interior and border boxes, odd / even sizes
+        cx, cy = int(rng.integers(-100, 2020)), int(rng.integers(-100, 1300))
+        hw, hh = int(rng.integers(1, 700)), int(rng.integers(1, 700))
+        boxes.append((cx - hw, cy - hh, cx + hw + int(rng.integers(0, 2)), cy + hh + int(rng.integers(0, 2))))
+    for s in (1, 2, 3, 5, 30):                                                  # larger than the frame
+        boxes += [(-s * 100, -s * 70, 1920 + s * 90, 1200 + s * 60), (-s * 1000, 100, 1920 + s * 1000, 300),
+                  (500, -s * 900, 700, 1200 + s * 900)]
+    # crop size == scale (rate exactly 1.0): int() truncates toward zero, so a span that straddles 0 is 2 * int(1.05 * size)
+    # wide: 256 for size 122, 128 for size 61 (a span on one side of 0 is odd)
+    for c in range(0, 60, 7):
+        boxes += [(c - 122, c - 122, c + 122, c + 122), (c - 61, c - 61, c + 61, c + 61), (c - 122, c - 100, c + 122, c + 100)]
+    for cx, cy in ((0, 0), (500, 500), (1920, 1200), (-300, 600), (2500, 600), (900, -400), (900, 1700)):
+        boxes += [(cx, cy, cx, cy), (cx + 10, cy, cx - 10, cy + 50), (cx, cy + 9, cx + 50, cy - 9), (cx, cy, cx + 1, cy + 1),
+                  (cx, cy, cx + 2, cy), (cx + 40, cy + 40, cx - 40, cy - 40)]    # degenerate (empty or reversed)
+    boxes += [(-3000, 500, -2500, 900), (4000, 100, 4400, 500), (100, -2000, 400, -1500), (100, 3000, 500, 3400)]   # off-frame
+    return boxes
+
+
+def test_boxes_equal_the_python_rules_exactly(env):
+    lib, L, crops = env["lib"], env["L"], env["crops"]
+    boxes = det_boxes()
+    m = len(boxes)
+    assert m >= 2000
+    det = torch.tensor(boxes, dtype=torch.int32, device="cuda")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    seen = dict(valid=0, invalid=0, rate_one=0, rules_differ=0)
+    for rule, fn in ((0, crops.val_box), (1, crops.train_box)):
+        for scale, (fw, fh) in ((256, (1920, 1200)), (128, (1920, 1200)), (256, (640, 480))):
+            out = torch.full((m, 4), -7, dtype=torch.int32, device="cuda")
+            rates = torch.full((m,), -7.0, dtype=torch.float64, device="cuda")
+            valid = torch.full((m,), -7, dtype=torch.int32, device="cuda")
+            L.check(lib.esahrnet_boxes(det.data_ptr(), m, fh, fw, scale, rule, out.data_ptr(), rates.data_ptr(), valid.data_ptr(),
+                                       stream))
+            torch.cuda.synchronize()
+            exp_b, exp_r, exp_v = [], [], []
+            for b in boxes:
+                box, size = fn(b, fw, fh)
+                exp_b.append(box)
+                exp_r.append(1.0 if size == scale else (scale / size if size else float("inf")))
+                exp_v.append(int(box[2] > box[0] and box[3] > box[1]))
+                seen["rules_differ"] += box != crops.val_box(b, fw, fh)[0]
+            bad = [i for i in range(m) if out[i].tolist() != exp_b[i]][:5]
+            assert not bad, [(boxes[i], out[i].tolist(), exp_b[i]) for i in bad]
+            assert np.array_equal(rates.cpu().numpy().view(np.int64), np.array(exp_r, np.float64).view(np.int64))
+            assert valid.cpu().tolist() == exp_v
+            seen["valid"] += sum(exp_v)
+            seen["invalid"] += m - sum(exp_v)
+            seen["rate_one"] += sum(r == 1.0 for r in exp_r)
+    assert all(v > 0 for v in seen.values()), seen
+
+
+# ---- 5. crops -----------------------------------------------------------------------------------------------------------------
+def test_gray_identity_is_bit_identical_to_esahrnet_crops(env):
+    crops = env["crops"]
+    frames = _frames(env, "frames", len(TCP.BOXES))
+    for scale in (256, 128, 90):
+        ref, rboxes, rrates = crops.crop_batch(frames, TCP.BOXES, scale)
+        out, boxes, rates, valid = crops.crop_batch_device(frames, TCP.BOXES, scale=scale)
+        torch.cuda.synchronize()
+        assert boxes.tolist() == rboxes and rates.tolist() == rrates and valid.tolist() == [1] * len(TCP.BOXES)
+        assert _bits(out, ref), scale
+        det = torch.tensor(TCP.BOXES, dtype=torch.int32, device="cuda")         # a device tensor is used as it is
+        out2 = crops.crop_batch_device(frames, det, scale=scale, pixel_format="gray")[0]
+        assert _bits(out2, ref)
+
+
+def test_frame_index_several_boxes_on_one_frame(env):
+    crops = env["crops"]
+    frames = _frames(env, "frames", 3)
+    fidx = [2, 0, 0, 1, 2, 0, 2]
+    ref, rboxes, rrates = crops.crop_batch(frames[fidx], TCP.BOXES, 128)
+    out, boxes, rates, valid = crops.crop_batch_device(frames, TCP.BOXES, frame_idx=fidx, scale=128)
+    assert _bits(out, ref) and boxes.tolist() == rboxes and rates.tolist() == rrates and valid.tolist() == [1] * 7
+    # an index out of range: that crop is invalid and zero, the others are untouched
+    bad = [2, 0, 3, 1, -1, 0, 2]
+    out, boxes, rates, valid = crops.crop_batch_device(frames, TCP.BOXES, frame_idx=torch.tensor(bad, dtype=torch.int32).cuda(),
+                                                       scale=128)
+    assert valid.tolist() == [1, 1, 0, 1, 0, 1, 1]
+    keep = [0, 1, 3, 5, 6]
+    assert _bits(out[keep], ref[keep]) and bool((out[[2, 4]] == 0).all())
+    assert boxes.tolist() == rboxes
+
+
+def test_rgb_equals_pil_luma_plane(env):
+    crops = env["crops"]
+    d = np.load(os.path.join(GOLDEN, "frontend_rgb_l.npz"))
+    rgb, lum = d["rgb"], d["l"]
+    h, w = lum.shape
+    assert rgb.shape == (h, w, 3) and rgb.dtype == np.uint8 and (rgb != rgb[..., :1]).any()
+    frames_rgb = torch.from_numpy(np.stack([rgb, rgb[::-1].copy()])).cuda()
+    frames_l = torch.from_numpy(np.stack([lum, lum[::-1].copy()])).cuda()
+    boxes = [(0, 0, w, h), (10, 5, 90, 70), (-20, 30, 100, 190), (150, 120, 260, 230), (0, 0, 40, 12), (60, 60, 64, 64)]
+    fidx = [0, 1, 1, 0, 0, 1]
+    for scale in (64, 256):
+        a = crops.crop_batch_device(frames_rgb, boxes, frame_idx=fidx, scale=scale)
+        b = crops.crop_batch_device(frames_l, boxes, frame_idx=fidx, scale=scale)
+        assert a[3].tolist() == [1] * 6
+        for x, y in zip(a, b):
+            assert _bits(x, y)
+
+
+# ---- 6. / 7. one call -------------------------------------------------------------------------------------------------------
+SCALE = {"seg_hrnet2": 256, "seg_hrnet3": 64}
+
+
+def _reference(env, net, frames, boxes, fidx, scale, refine):
+    x, rboxes, rrates = env["crops"].crop_batch(frames if fidx is None else frames[fidx], boxes, scale)
+    with torch.no_grad():
+        kp, idx = net(x, output="keypoints+index", refine=refine)
+    return kp, idx, rboxes, rrates
+
+
+@pytest.mark.parametrize("refine", ["get_final", "get_final2"])
+@pytest.mark.parametrize("name", ["seg_hrnet2", "seg_hrnet3"])
+def test_one_call_equals_crop_batch_then_keypoints(env, nets, name, refine):
+    net, scale = nets[name], SCALE[name]
+    frames = _frames(env, "frames", 4)
+    cases = [([TCP.BOXES[0]], None, frames[:1]),                                                       # batch 1
+             (TCP.BOXES + [TCP.BOXES[4]], [0, 0, 1, 1, 2, 2, 3, 3], frames)]                          # two boxes per frame
+    for boxes, fidx, fr in cases:
+        rkp, ridx, rboxes, rrates = _reference(env, net, fr, boxes, fidx, scale, refine)
+        with torch.no_grad():
+            kp, cboxes, rates, valid, idx, _ = net._frames_to_keypoints(fr, boxes, fidx, scale, "val", refine, None, 0.229, None)
+            kp2, cboxes2, rates2, valid2 = net.frames_to_keypoints(fr, boxes, frame_idx=fidx, scale=scale, refine=refine)
+        torch.cuda.synchronize()
+        assert kp.shape == (len(boxes), net.num_keypoints, 3) and idx.dtype == torch.int32 and rates.dtype == torch.float64
+        assert _bits(kp, rkp) and torch.equal(idx, ridx) and _bits(kp2, rkp)
+        assert cboxes.tolist() == rboxes == cboxes2.tolist() and rates.tolist() == rrates == rates2.tolist()
+        assert valid.tolist() == [1] * len(boxes) == valid2.tolist()
+
+
+def test_rule_train_uses_train_box_and_its_mean(env, nets):
+    crops, net = env["crops"], nets["seg_hrnet3"]
+    frames = _frames(env, "frames", 2)
+    boxes = [(-91, 400, 111, 600), (859, -91, 1061, 111)]                      # the two rules differ on both
+    kp, cboxes, rates, valid = net.frames_to_keypoints(frames, boxes, scale=64, rule="train")
+    exp = [crops.train_box(b) for b in boxes]
+    assert cboxes.tolist() == [e[0] for e in exp] != [crops.val_box(b)[0] for b in boxes]
+    assert rates.tolist() == [64 / e[1] for e in exp] and valid.tolist() == [1, 1]
+    x = crops.crop_batch_device(frames, boxes, scale=64, rule="train", mean=crops.MEAN_TRAIN)[0]
+    with torch.no_grad():
+        assert _bits(kp, net(x, output="keypoints"))
+
+
+@pytest.mark.parametrize("refine", ["get_final", "get_final2"])
+def test_invalid_crops_are_nan_rows(env, nets, refine):
+    net, scale = nets["seg_hrnet3"], 64
+    frames = _frames(env, "frames", 3)
+    good = list(TCP.BOXES[:5])
+    fidx = [0, 1, 2, 2, 1]
+    kp0, b0, r0, v0, idx0, _ = net._frames_to_keypoints(frames, good, fidx, scale, "val", refine, None, 0.229, None)
+    boxes = good[:2] + [(500, 500, 500, 500)] + good[2:] + [TCP.BOXES[5]]       # position 2: an empty box
+    fidx2 = fidx[:2] + [0] + fidx[2:] + [3]                                      # position 6: no such frame
+    kp, b, r, v, idx, _ = net._frames_to_keypoints(frames, boxes, fidx2, scale, "val", refine, None, 0.229, None)
+    torch.cuda.synchronize()
+    assert v.tolist() == [1, 1, 0, 1, 1, 1, 0] and v0.tolist() == [1] * 5
+    assert bool(torch.isnan(kp[[2, 6]]).all()) and bool((idx[[2, 6]] == -1).all())
+    keep = [0, 1, 3, 4, 5]
+    assert _bits(kp[keep], kp0) and torch.equal(idx[keep], idx0) and _bits(r[keep], r0) and torch.equal(b[keep], b0)
+    assert bool(torch.isfinite(kp0).all())
+
+
+# ---- 8. capture -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["seg_hrnet2", "seg_hrnet3"])
+def test_captured_once_replayed_on_a_second_scene(env, nets, name):
+    net, scale = nets[name], SCALE[name]
+    f1, f2 = _frames(env, "frames", 2), _frames(env, "frames_b", 2, seed=9)
+    fidx = torch.tensor([0, 1, 1], dtype=torch.int32, device="cuda")
+    d1 = torch.tensor(TCP.BOXES[:3], dtype=torch.int32, device="cuda")
+    d2 = torch.tensor(TCP.BOXES[3:6], dtype=torch.int32, device="cuda")
+    frames, det = f1.clone(), d1.clone()
+    with torch.no_grad():
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            net.frames_to_keypoints(frames, det, frame_idx=fidx, scale=scale)
+        torch.cuda.current_stream().wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            out = net.frames_to_keypoints(frames, det, frame_idx=fidx, scale=scale)
+        frames.copy_(f2)
+        det.copy_(d2)
+        other = net(env["synth"].make_crops(2, 1, 48, 80, seed=1).cuda(), output="keypoints")      # eager, another shape
+        eager_other = net.frames_to_keypoints(f1, d1, frame_idx=fidx, scale=scale)                  # eager, the same shape
+        g.replay()
+        torch.cuda.synchronize()
+        got = [t.clone() for t in out]
+        ref2 = net.frames_to_keypoints(f2, d2, frame_idx=fidx, scale=scale)
+        ref1 = net.frames_to_keypoints(f1, d1, frame_idx=fidx, scale=scale)
+        torch.cuda.synchronize()
+    assert all(_bits(a, b) for a, b in zip(got, ref2))
+    assert all(_bits(a, b) for a, b in zip(eager_other, ref1)) and not _bits(ref1[0], ref2[0])
+    assert bool(torch.isfinite(other).all())
+
+
+# ---- 9. pipeline ------------------------------------------------------------------------------------------------------------
+def _same_poses(a, b):
+    return len(a) == len(b) and all(np.array_equal(np.asarray(qa), np.asarray(qb), equal_nan=True) and
+                                    np.array_equal(np.asarray(ta), np.asarray(tb), equal_nan=True)
+                                    for (qa, ta), (qb, tb) in zip(a, b))
+
+
+def test_estimate_poses_with_the_device_loader(env, nets):
+    """The scaled-down configs[4] scene (synth.make_scene, ESA camera, random frames): the same poses from both loaders."""
+    pipeline, synth = env["pipeline"], env["synth"]
+    net = nets["seg_hrnet2"]
+    n = 16
+    scene = synth.make_scene(n, net.num_keypoints, seed=0)
+    frames = torch.from_numpy(np.random.default_rng(0).integers(0, 256, size=(n, 1200, 1920), dtype=np.uint8)).cuda()
+    kw = dict(scale=128, thresh=0.0, min_k=8)
+    for refine in ("get_final", "get_final2"):
+        ref = pipeline.estimate_poses(net, frames, scene["bboxes"], scene["kp3d"], synth.ESA_CAMERA, on_fail="nan", refine=refine, **kw)
+        got = pipeline.estimate_poses(net, frames, scene["bboxes"], scene["kp3d"], synth.ESA_CAMERA, on_fail="nan", refine=refine,
+                                      device_loader=True, **kw)
+        assert _same_poses(got, ref)
+    # two boxes on one frame + an invalid crop: the NaN row (on_fail="nan"), PoseFailure (on_fail="raise"), the fallback
+    # pose in run_submission
+    boxes = scene["bboxes"][:3] + [[700, 700, 700, 700]]
+    fidx = [0, 1, 1, 2]
+    boxes[2] = scene["bboxes"][1]
+    got = pipeline.estimate_poses(net, frames[:3], boxes, scene["kp3d"], synth.ESA_CAMERA, on_fail="nan", device_loader=True,
+                                  frame_idx=fidx, **kw)
+    ref = pipeline.estimate_poses(net, frames[[0, 1, 1]], boxes[:3], scene["kp3d"], synth.ESA_CAMERA, on_fail="nan", **kw)
+    assert _same_poses(got[:3], ref) and np.isnan(got[3][0]).all() and np.isnan(got[3][1]).all()
+    with pytest.raises(pipeline.PoseFailure, match=r"\b3\b"):
+        pipeline.estimate_poses(net, frames[:3], boxes, scene["kp3d"], synth.ESA_CAMERA, device_loader=True, frame_idx=fidx, **kw)
+    with pytest.raises(ValueError, match="empty crop box"):                  # the host loader's answer to the same box
+        pipeline.estimate_poses(net, frames[:1], boxes[3:], scene["kp3d"], synth.ESA_CAMERA, **kw)
+    w = pipeline.run_submission(net, [(["a", "b", "c", "d"], frames[:3], boxes)], scene["kp3d"], synth.ESA_CAMERA,
+                                pipeline.SubmissionWriter(), device_loader=True, frame_idx=fidx, **kw)
+    assert "d" in w.failed
+    row = [r for r in w.test_results if r["filename"] == "d"][0]
+    assert (tuple(row["q"]), tuple(row["r"])) == pipeline.FALLBACK_POSE
+
+
+# ---- the C entry point's own refusals, with a committed handle ----------------------------------------------------------
+def test_entry_errors_then_a_good_call(env, nets):
+    lib, L, net = env["lib"], env["L"], nets["seg_hrnet3"]
+    frames = _frames(env, "frames", 1)
+    ref = net.frames_to_keypoints(frames, [TCP.BOXES[0]], scale=64)
+    h = net._rt._handle_for(net, frames.device)
+    need = C.c_size_t()
+    L.check(lib.esahrnet_frames_keypoints_workspace_bytes(h, 1, 64, 0, C.byref(need)))
+    ws = torch.empty(need.value + 512, dtype=torch.uint8, device="cuda")
+    wp = ws.data_ptr() + (-ws.data_ptr()) % 256
+    k = net.num_keypoints
+    kp = torch.zeros((1, k, 3), device="cuda")
+    det = torch.tensor([TCP.BOXES[0]], dtype=torch.int32, device="cuda")
+    cb = torch.zeros((1, 4), dtype=torch.int32, device="cuda")
+    rt = torch.zeros((1,), dtype=torch.float64, device="cuda")
+    va = torch.zeros((1,), dtype=torch.int32, device="cuda")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def call(wsp=wp, wsb=need.value, m=1):
+        return lib.esahrnet_frames_keypoints(h, frames.data_ptr(), 1, 1200, 1920, 0, det.data_ptr(), None, m, 64, 0, 0.485, 0.229, 0,
+                                             kp.data_ptr(), None, cb.data_ptr(), rt.data_ptr(), va.data_ptr(), wsp, wsb, stream)
+    assert call(wsb=need.value - 256) != 0 and b"too small" in lib.esahrnet_last_error()
+    assert call(wsp=wp + 8) != 0 and b"aligned" in lib.esahrnet_last_error()
+    torch.cuda.synchronize()
+    assert va.tolist() == [0] and bool((kp == 0).all())                       # nothing was enqueued by the refused calls
+    L.check(call())
+    torch.cuda.synchronize()
+    assert _bits(kp, ref[0]) and cb.tolist() == ref[1].tolist() and va.tolist() == [1]
