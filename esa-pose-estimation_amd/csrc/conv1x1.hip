@@ -22,9 +22,12 @@ namespace {
 // two K-steps of a block (sb.h), 2 MFMAs instead of 3, and the epilogue packs 4 channels into 8 bytes.
 // PG: 16-pixel groups per wave.  With 2 the wave reads every weight fragment once for 32 pixels — twice the MFMAs per barrier
 // and per LDS byte; used for the big bf16 launches, whose chunks are only 4 .. 8 MFMAs deep per group.
-template <int NCH, bool BF, int PG = 1>
+// EL (sb.h): the element type, EL_SB / EL_BF / EL_HF (fp16: the BF scheme on v_mfma_f32_16x16x32_f16, saturating stores);
+// BF below = 2 bytes per channel, either of the two.
+template <int NCH, int EL, int PG = 1>
 __device__ __forceinline__ void conv1x1_body(const ConvParams& p, const long long ntiles, const int tiles_per_row,
                                              const int bid, const int G, const int split = 0, const int nsplit = 1) {
+    constexpr bool BF = el_half(EL);
     constexpr int WFR = 4 * NCH;                   // 1-KB weight fragments per 32-cout chunk
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -104,8 +107,8 @@ __device__ __forceinline__ void conv1x1_body(const ConvParams& p, const long lon
 #pragma unroll
                 for (int pg = 0; pg < PG; ++pg) {
                     if (BF) {
-                        d[pg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh[pg][c], d[pg], 0, 0, 0);
-                        d[pg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xl[pg][c], d[pg], 0, 0, 0);
+                        d[pg] = mfma_el<EL>(wh, xh[pg][c], d[pg]);
+                        d[pg] = mfma_el<EL>(wl, xl[pg][c], d[pg]);
                     } else {
                         d[pg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh[pg][c], d[pg], 0, 0, 0);
                         d[pg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[pg][c], d[pg], 0, 0, 0);
@@ -122,7 +125,7 @@ __device__ __forceinline__ void conv1x1_body(const ConvParams& p, const long lon
                     for (int r = 0; r < 4; ++r) v[r] = relu_opt(v[r], rfl);
                 }
                 if (BF) {
-                    pk[pg][m] = pack4_bf16(v);
+                    pk[pg][m] = pack4_el<EL>(v);
                 } else if (p.out_f32) {     // plain f32 NHWC (same pixel pitch): the nine-tap products read by head_gather.hip
                     if (valid[pg]) *reinterpret_cast<float4*>(orow[pg] + co * 4) = make_float4(v[0], v[1], v[2], v[3]);
                 } else {
@@ -154,9 +157,9 @@ __device__ __forceinline__ void conv1x1_body(const ConvParams& p, const long lon
 #undef C1_COMMIT
 }
 
-template <int NCH, bool BF = false, int PG = 1>
+template <int NCH, int EL = EL_SB, int PG = 1>
 __global__ __launch_bounds__(256, 2) void conv1x1_kernel(ConvParams p, long long ntiles, int tiles_per_row) {
-    conv1x1_body<NCH, BF, PG>(p, ntiles, tiles_per_row, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y, (int)gridDim.y);
+    conv1x1_body<NCH, EL, PG>(p, ntiles, tiles_per_row, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y, (int)gridDim.y);
 }
 
 // Several independent 1x1 convolutions in one launch (the fuse-up convolutions of an HRModule, models/seg_hrnet.py:
@@ -178,22 +181,22 @@ __global__ __launch_bounds__(256, 2) void conv1x1_jobs_kernel(C1Jobs jobs) {
     const int bid = b - jobs.start[j], G = jobs.start[j + 1] - jobs.start[j];
     const ConvParams& p = jobs.p[j];
     switch (p.Cinp >> 5) {
-        case 2: conv1x1_body<2, false>(p, jobs.ntiles[j], jobs.tiles_per_row[j], bid, G); break;
-        case 4: conv1x1_body<4, false>(p, jobs.ntiles[j], jobs.tiles_per_row[j], bid, G); break;
-        default: conv1x1_body<8, false>(p, jobs.ntiles[j], jobs.tiles_per_row[j], bid, G); break;
+        case 2: conv1x1_body<2, EL_SB>(p, jobs.ntiles[j], jobs.tiles_per_row[j], bid, G); break;
+        case 4: conv1x1_body<4, EL_SB>(p, jobs.ntiles[j], jobs.tiles_per_row[j], bid, G); break;
+        default: conv1x1_body<8, EL_SB>(p, jobs.ntiles[j], jobs.tiles_per_row[j], bid, G); break;
     }
 }
 
-template <int NCH, bool BF = false>
+template <int NCH, int EL = EL_SB>
 int launch_conv1x1_n(const ConvParams& p, hipStream_t stream) {
     const int lds = 2 * 4 * NCH * 1024 + p.Coutp * 4;        // two weight buffers + the bias
     const int tiles_per_row = (p.W + 15) / 16;
     const long long ntiles = (long long)p.N * p.H * tiles_per_row;
     // two 16-pixel groups per wave for the big bf16 launches (same MFMAs in the same order on every accumulator: the result
     // does not depend on the choice)
-    if constexpr (BF && NCH <= 4) {
+    if constexpr (el_half(EL) && NCH <= 4) {
         if (ntiles >= 32LL * device_cus()) {
-            auto kern2 = conv1x1_kernel<NCH, BF, 2>;
+            auto kern2 = conv1x1_kernel<NCH, EL, 2>;
             if (const int e_ = ensure_dyn_lds(reinterpret_cast<const void*>(kern2), lds)) return e_;
             const long long nblk2 = (ntiles + 7) / 8;
             if (nblk2 > 0x7fffffffLL) return (int)hipErrorInvalidValue;
@@ -201,7 +204,7 @@ int launch_conv1x1_n(const ConvParams& p, hipStream_t stream) {
             return (int)hipGetLastError();
         }
     }
-    auto kern = conv1x1_kernel<NCH, BF>;
+    auto kern = conv1x1_kernel<NCH, EL>;
     if (const int e_ = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds)) return e_;
     const long long nblk = (ntiles + 3) / 4;
     if (nblk <= 0 || nblk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
@@ -216,7 +219,7 @@ int launch_conv1x1_n(const ConvParams& p, hipStream_t stream) {
 // weights must be packed with pack_conv_weights(k = 1): [Coutp/16][Cinp/32][hi|lo][64] fragments — the
 // 4*NCH fragments of a 32-cout chunk are contiguous, which is what the staging above relies on
 bool conv1x1_supported(const ConvParams& p) {
-    if ((p.fmt == FMT_BF)) {         // blocks of 64 input channels; every width of the BF plans (64 .. 768 channels)
+    if (fmt_half(p.fmt)) {         // blocks of 64 input channels; every width of the BF plans (64 .. 768 channels)
         const int n = p.Cinp / 64;
         return (p.Cinp % 64) == 0 && (p.Coutp % 64) == 0 && !p.res && !p.out_f32 && p.H == p.OH && p.W == p.OW &&
                (n == 1 || n == 2 || n == 3 || n == 4 || n == 6 || n == 8 || n == 12);
@@ -228,15 +231,27 @@ bool conv1x1_supported(const ConvParams& p) {
 
 int launch_conv1x1(const ConvParams& p, hipStream_t stream) {
     if (!conv1x1_supported(p)) return (int)hipErrorInvalidValue;
-    if ((p.fmt == FMT_BF)) {
+    if (p.fmt == FMT_BF) {
         switch (p.Cinp / 64) {
-            case 1: return launch_conv1x1_n<1, true>(p, stream);
-            case 2: return launch_conv1x1_n<2, true>(p, stream);
-            case 3: return launch_conv1x1_n<3, true>(p, stream);
-            case 4: return launch_conv1x1_n<4, true>(p, stream);
-            case 6: return launch_conv1x1_n<6, true>(p, stream);
-            case 8: return launch_conv1x1_n<8, true>(p, stream);
-            case 12: return launch_conv1x1_n<12, true>(p, stream);
+            case 1: return launch_conv1x1_n<1, EL_BF>(p, stream);
+            case 2: return launch_conv1x1_n<2, EL_BF>(p, stream);
+            case 3: return launch_conv1x1_n<3, EL_BF>(p, stream);
+            case 4: return launch_conv1x1_n<4, EL_BF>(p, stream);
+            case 6: return launch_conv1x1_n<6, EL_BF>(p, stream);
+            case 8: return launch_conv1x1_n<8, EL_BF>(p, stream);
+            case 12: return launch_conv1x1_n<12, EL_BF>(p, stream);
+        }
+        return (int)hipErrorInvalidValue;
+    }
+    if (p.fmt == FMT_HF) {
+        switch (p.Cinp / 64) {
+            case 1: return launch_conv1x1_n<1, EL_HF>(p, stream);
+            case 2: return launch_conv1x1_n<2, EL_HF>(p, stream);
+            case 3: return launch_conv1x1_n<3, EL_HF>(p, stream);
+            case 4: return launch_conv1x1_n<4, EL_HF>(p, stream);
+            case 6: return launch_conv1x1_n<6, EL_HF>(p, stream);
+            case 8: return launch_conv1x1_n<8, EL_HF>(p, stream);
+            case 12: return launch_conv1x1_n<12, EL_HF>(p, stream);
         }
         return (int)hipErrorInvalidValue;
     }

@@ -525,7 +525,7 @@ namespace {
 enum Choice { C_NONE, C_STREAM_S1, C_TILE_S1_8, C_TILE_S1_16, C_STREAM_S2, C_TILE_S2, C_1X1, C_TILE_1X1, C_X6 };
 Choice choose_conv(const ConvParams& p, int k, int stride) {
     if (p.fmt == FMT_F32) return conv_x6_supported(p, k, stride) ? C_X6 : C_NONE;      // f32 tensors: bf16x6 arithmetic (conv_x6.hip)
-    if ((p.fmt == FMT_BF)) {         // single-bf16 tensors: the stream kernel (every 3x3) and the register 1x1 kernel only
+    if (fmt_half(p.fmt)) {         // single-bf16 / single-fp16 tensors: the stream kernel (every 3x3) and the register 1x1 kernel only
         if (k == 3 && stride == 1) return conv_s2c32_supported(p) ? C_STREAM_S1 : C_NONE;
         if (k == 3 && stride == 2) return conv_s2c32_supported(p) && !p.out_f32 ? C_STREAM_S2 : C_NONE;
         if (k == 1 && stride == 1) return conv1x1_supported(p) ? C_1X1 : C_NONE;
@@ -579,6 +579,14 @@ const char* conv_kernel_name(const ConvParams& p, int k, int stride) {
     const bool ring = ESA_CONV_RING && p.Cinp > 32;
     const bool persist = p.Cinp == 32;
     if (p.fmt == FMT_F32) return choose_conv(p, k, stride) == C_X6 ? conv_x6_kernel_name(p, k, stride) : "none";
+    if (p.fmt == FMT_HF) {      // the fp16 instantiations of the bf16 mode's kernels
+        switch (choose_conv(p, k, stride)) {
+            case C_STREAM_S1: return "conv_s2c32_kernel<1, 8, 4, false, fp16>";
+            case C_STREAM_S2: return "conv_s2c32_kernel<2, 4, 4, false, fp16>";
+            case C_1X1: return "conv1x1_kernel<fp16>";
+            default: return "none";
+        }
+    }
     if ((p.fmt == FMT_BF)) {
         switch (choose_conv(p, k, stride)) {
             case C_STREAM_S1: return p.out_f32 ? "conv_s2c32_f32out_kernel<1, 8, 4, true>" : "conv_s2c32_kernel<1, 8, 4, false, true>";
@@ -641,8 +649,30 @@ size_t packed_weight_bytes_bf(int coutp, int cinp, int k) {
     return (size_t)(coutp / 16) * (cinp / 64) * k * k * 2048;
 }
 
-// BF mode (kernels.h): [cout16 tile][cin64 block][tap][K-step][lane 0..63][8 x bf16]; one rounding per weight
-void pack_conv_weights_bf(const float* w, int cout, int cin, int k, int coutp, int cinp, void* dst) {
+// f32 -> IEEE binary16 bits, round to nearest even, subnormals kept; beyond the largest finite half: +-inf (the callers
+// refuse such weights, host_f16_finite)
+uint16_t host_f16(float f) {
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    const uint32_t sign = (u >> 16) & 0x8000u;
+    u &= 0x7fffffffu;
+    if (u >= 0x7f800000u) return (uint16_t)(sign | (u > 0x7f800000u ? 0x7e00u : 0x7c00u));      // NaN / inf
+    if (u >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);          // >= 65520 rounds to inf
+    if (u < 0x38800000u) {                                            // below 2^-14: subnormal half (or zero)
+        if (u < 0x33000000u) return (uint16_t)sign;                   // < 2^-25 rounds to zero (2^-25 itself: tie to even = 0)
+        const int shift = 126 - (int)(u >> 23);                       // 14 .. 24 bits dropped from the 24-bit significand
+        const uint32_t m = (u & 0x7fffffu) | 0x800000u;
+        const uint32_t q = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+        return (uint16_t)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));
+    }
+    u += 0xc8000000u + 0xfffu + ((u >> 13) & 1u);                     // rebias 127 -> 15, round to nearest even
+    return (uint16_t)(sign | (u >> 13));
+}
+bool host_f16_finite(float f) { return (host_f16(f) & 0x7c00u) != 0x7c00u; }
+
+// BF mode (kernels.h): [cout16 tile][cin64 block][tap][K-step][lane 0..63][8 x bf16]; one rounding per weight.  half = true:
+// the same image with fp16 elements (HF mode)
+void pack_conv_weights_bf(const float* w, int cout, int cin, int k, int coutp, int cinp, void* dst, bool half) {
     uint16_t* d = static_cast<uint16_t*>(dst);
     const int taps = k * k, nblk = cinp / 64;
     for (int t16 = 0; t16 < coutp / 16; ++t16)
@@ -654,7 +684,7 @@ void pack_conv_weights_bf(const float* w, int cout, int cin, int k, int coutp, i
                             const int co = t16 * 16 + (l & 15), ci = c * 64 + step * 32 + 8 * (l >> 4) + j;
                             float v = 0.f;
                             if (co < cout && ci < cin) v = w[((size_t)co * cin + ci) * taps + tap];
-                            d[(((((size_t)t16 * nblk + c) * taps + tap) * 2) + step) * 512 + l * 8 + j] = host_bf16(v);
+                            d[(((((size_t)t16 * nblk + c) * taps + tap) * 2) + step) * 512 + l * 8 + j] = half ? host_f16(v) : host_bf16(v);
                         }
 }
 

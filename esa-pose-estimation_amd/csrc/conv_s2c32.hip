@@ -98,14 +98,18 @@ __device__ __forceinline__ int div_magic(int b, int d, uint32_t m) {
 // flight, and the loads of step s+2 are issued behind it; the barrier that opens step s+1 then publishes that tile
 // and retires the reads of step s at once.  (Single-buffered: barrier, write, barrier, and the LDS-read pipe starts
 // cold behind the second one.)
+// EL (sb.h): the element type — EL_SB the split format, EL_BF what "BF" says above, EL_HF the same with fp16 elements
+// (esahrnet_cfg.precision 3: v_mfma_f32_16x16x32_f16, stores rounded to nearest even and saturated at +-65504); BF below
+// stands for "2 bytes per channel", i.e. either of the two.
 // OCC: workgroups per CU the register budget is cut for (2: 256 VGPRs per wave; 1: 512 — the 16-row tile).
 // OF (BF only, conv_s2c32_f32out_kernel): the output is plain f32 NHWC [N][OH][OW][Coutp] — seg_hrnet3's output layer in
 // the bf16 mode, whose heat-maps leave unrounded; no residual.  The other kernels are instantiated with OF = false.
 // The body is shared by the one-convolution kernel and by conv_s2c32_jobs_kernel (several independent convolutions in
 // one launch): `bid` / `G` are the workgroup's index and the grid size WITHIN its convolution.
-template <int S, int TH, int MW, bool MH, bool BF, bool DB, int OCC, bool OF = false>
+template <int S, int TH, int MW, bool MH, int EL, bool DB, int OCC, bool OF = false>
 __device__ __forceinline__ void conv_s2c32_body(const ConvParams& p, const StreamGeo& geo, const int bid, const int G) {
     using S2C = ConvCfg<3, S, TH, 2>;
+    constexpr bool BF = el_half(EL);
     constexpr int RG = 4 / MW;                  // row groups
     constexpr int NT = TH / RG;                 // output rows per wave
     constexpr int ROWS = (NT - 1) * S + 3;      // input rows a wave touches
@@ -361,7 +365,7 @@ __device__ __forceinline__ void conv_s2c32_body(const ConvParams& p, const Strea
         if (BF && do_res) {
             int jj = (lane & 15) - 8 * g;
             asm volatile("" : "+v"(jj));
-            const uint32_t one = (jj & 1) ? 0x3f800000u : 0x00003f80u;
+            const uint32_t one = (jj & 1) ? one_hi_el<EL>() : one_lo_el<EL>();
             const bool on = jj >= 0 && jj < 8 && g < 2;
 #pragma unroll
             for (int k = 0; k < 4; ++k) idw[k] = (on && (jj >> 1) == k) ? one : 0u;
@@ -369,7 +373,7 @@ __device__ __forceinline__ void conv_s2c32_body(const ConvParams& p, const Strea
         const bf16x8 idA = __builtin_bit_cast(bf16x8, idw);
         auto res_fold = [&](int t) __attribute__((always_inline)) {          // acc[t] += residual row t (its chunk in rc[t % NH])
             if (BF) {
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(idA, __builtin_bit_cast(bf16x8, rc[t % NH]), acc[t], 0, 0, 0);
+                acc[t] = mfma_el<EL>(idA, __builtin_bit_cast(bf16x8, rc[t % NH]), acc[t]);
             } else {
                 uint2 rh_, rl_;
                 chunk_to_quad(make_uint4(rc[t % NH][0], rc[t % NH][1], rc[t % NH][2], rc[t % NH][3]), rh_, rl_);
@@ -392,7 +396,7 @@ __device__ __forceinline__ void conv_s2c32_body(const ConvParams& p, const Strea
             }
             if (BF) {       // 4 channels of one pixel = 8 bytes per lane; the four rows of 16 lanes fill 32 contiguous bytes
                 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-                const uint2 pk = pack4_bf16(v);
+                const uint2 pk = pack4_el<EL>(v);
                 __builtin_amdgcn_raw_buffer_store_b64(u32x2{pk.x, pk.y}, ry, (int)(so_ + (uint32_t)yso), 0, 0);
                 return;
             }
@@ -432,8 +436,8 @@ __device__ __forceinline__ void conv_s2c32_body(const ConvParams& p, const Strea
                     if (!(S2_ABL & 8) && d >= 0 && d % S == 0 && d / S < NT) {
                         const int t = d / S;
                         if (BF) {
-                            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ky * 3 + kx], xh, acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[ky * 3 + kx], xo, acc[t], 0, 0, 0);
+                            acc[t] = mfma_el<EL>(wh[ky * 3 + kx], xh, acc[t]);
+                            acc[t] = mfma_el<EL>(wl[ky * 3 + kx], xo, acc[t]);
                         } else {
                             acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[ky * 3 + kx], xh, acc[t], 0, 0, 0);
                             acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ky * 3 + kx], xo, acc[t], 0, 0, 0);
@@ -512,14 +516,14 @@ __device__ __forceinline__ void conv_s2c32_body(const ConvParams& p, const Strea
 #undef S2_LOAD_W
 }
 
-template <int S, int TH, int MW, bool MH = false, bool BF = false, bool DB = false, int OCC = 2>
+template <int S, int TH, int MW, bool MH = false, int EL = EL_SB, bool DB = false, int OCC = 2>
 __global__ __launch_bounds__(NTHREADS, OCC) void conv_s2c32_kernel(ConvParams p, StreamGeo geo) {
-    conv_s2c32_body<S, TH, MW, MH, BF, DB, OCC>(p, geo, (int)blockIdx.x, (int)gridDim.x);
+    conv_s2c32_body<S, TH, MW, MH, EL, DB, OCC>(p, geo, (int)blockIdx.x, (int)gridDim.x);
 }
 // the same body with the f32 epilogue (OF): single-buffered in every batch, so that a crop's bits do not depend on it
-template <int S, int TH, int MW, bool BF>
+template <int S, int TH, int MW, int EL>
 __global__ __launch_bounds__(NTHREADS, 2) void conv_s2c32_f32out_kernel(ConvParams p, StreamGeo geo) {
-    conv_s2c32_body<S, TH, MW, false, BF, false, 2, true>(p, geo, (int)blockIdx.x, (int)gridDim.x);
+    conv_s2c32_body<S, TH, MW, false, EL, false, 2, true>(p, geo, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // Several INDEPENDENT convolutions (the same-depth 3x3s of the 64/128/256-channel branches of an HRModule,
@@ -540,15 +544,15 @@ struct StreamJobs {
     int mw[MAXJOBS];
     int njobs;
 };
-template <int S, int TH, bool BF>
+template <int S, int TH, int EL>
 __global__ __launch_bounds__(NTHREADS, 2) void conv_s2c32_jobs_kernel(StreamJobs jobs) {
     const int b = (int)blockIdx.x;
     int j = 0;
 #pragma unroll
     for (int k = 1; k < MAXJOBS; ++k) j += (k < jobs.njobs && b >= jobs.start[k]) ? 1 : 0;
     const int bid = b - jobs.start[j], G = jobs.start[j + 1] - jobs.start[j];
-    if (!BF && jobs.mw[j] == 2) conv_s2c32_body<S, TH, 2, false, BF, false, 2>(jobs.p[j], jobs.geo[j], bid, G);
-    else conv_s2c32_body<S, TH, 4, false, BF, false, 2>(jobs.p[j], jobs.geo[j], bid, G);
+    if (EL == EL_SB && jobs.mw[j] == 2) conv_s2c32_body<S, TH, 2, false, EL, false, 2>(jobs.p[j], jobs.geo[j], bid, G);
+    else conv_s2c32_body<S, TH, 4, false, EL, false, 2>(jobs.p[j], jobs.geo[j], bid, G);
 }
 
 uint32_t magic_of(int d) { return (uint32_t)(0xffffffffull / (uint64_t)d); }
@@ -558,7 +562,7 @@ uint32_t magic_of(int d) { return (uint32_t)(0xffffffffull / (uint64_t)d); }
 // layer — and with it every bit of a crop's result — never depends on the batch size.
 std::atomic<long long> g_launch_limit{0x7fffffffLL};      // bytes; lowered only by tests (esahrnet_debug_set_launch_limit)
 int images_per_launch(const ConvParams& p) {
-    const int eb = (p.fmt == FMT_BF) ? 2 : 4;
+    const int eb = fmt_half(p.fmt) ? 2 : 4;
     long long per = (long long)p.H * p.W * p.Cinp * eb;
     if (p.nheads > 1) {
         for (int h = 0; h < p.nheads; ++h) per = std::max(per, (long long)p.OH * p.OW * (p.hb[h + 1] - p.hb[h]) * eb);
@@ -571,22 +575,22 @@ int images_per_launch(const ConvParams& p) {
 #ifndef S2_DB
 #define S2_DB 1          // 1: stride-1 launches with at most one workgroup per CU run the double-buffered variant
 #endif
-template <int S, int TH, int MW, bool MH, bool BF, bool DB, int OCC = 2, bool OF = false>
+template <int S, int TH, int MW, bool MH, int EL, bool DB, int OCC = 2, bool OF = false>
 int launch_s2c32_k(const ConvParams& p, const StreamGeo& geo, int grid, hipStream_t stream) {
     using S2C = ConvCfg<3, S, TH, 2>;
     constexpr int LDS = (DB ? 2 : 1) * S2C::XBYTES;
     static_assert(!OF || (!DB && OCC == 2 && !MH), "conv_s2c32_f32out_kernel is the single-buffered body");
     void (*kern)(ConvParams, StreamGeo);
-    if constexpr (OF) kern = conv_s2c32_f32out_kernel<S, TH, MW, BF>;
-    else kern = conv_s2c32_kernel<S, TH, MW, MH, BF, DB, OCC>;
+    if constexpr (OF) kern = conv_s2c32_f32out_kernel<S, TH, MW, EL>;
+    else kern = conv_s2c32_kernel<S, TH, MW, MH, EL, DB, OCC>;
     if (const int e_ = ensure_dyn_lds(reinterpret_cast<const void*>(kern), LDS)) return e_;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NTHREADS), LDS, stream, p, geo);
     return (int)hipGetLastError();
 }
 
-template <int S, int TH, int MW, bool MH = false, bool BF = false, bool OF = false>
+template <int S, int TH, int MW, bool MH = false, int EL = EL_SB, bool OF = false>
 int launch_s2c32_t(const ConvParams& p, hipStream_t stream) {
-    constexpr int EB = BF ? 2 : 4, OEB = OF ? 4 : EB;
+    constexpr int EB = el_half(EL) ? 2 : 4, OEB = OF ? 4 : EB;
     const int nmax = images_per_launch(p);
     if (nmax < 1) return (int)hipErrorInvalidValue;
     if (p.N > nmax) {
@@ -598,7 +602,7 @@ int launch_s2c32_t(const ConvParams& p, hipStream_t stream) {
             if (p.res) q.res = p.res + (size_t)n0 * p.OH * p.OW * p.Coutp * EB;
             for (int h = 0; h < p.nheads && h < 3; ++h)
                 if (p.yh[h]) q.yh[h] = p.yh[h] + (size_t)n0 * p.OH * p.OW * (p.hb[h + 1] - p.hb[h]) * EB;
-            if (const int e = launch_s2c32_t<S, TH, MW, MH, BF, OF>(q, stream)) return e;
+            if (const int e = launch_s2c32_t<S, TH, MW, MH, EL, OF>(q, stream)) return e;
         }
         return 0;
     }
@@ -618,14 +622,14 @@ int launch_s2c32_t(const ConvParams& p, hipStream_t stream) {
     // All variants run the same MFMAs in the same order on every accumulator: a crop's result does not depend on which
     // one a batch size selects.
     if constexpr (OF) {
-        return launch_s2c32_k<S, TH, MW, MH, BF, false, 2, true>(p, geo, grid, stream);
+        return launch_s2c32_k<S, TH, MW, MH, EL, false, 2, true>(p, geo, grid, stream);
     } else if constexpr (TH == 16) {
-        return launch_s2c32_k<S, TH, MW, MH, BF, true, 1>(p, geo, grid, stream);
+        return launch_s2c32_k<S, TH, MW, MH, EL, true, 1>(p, geo, grid, stream);
     } else {
         if constexpr (S2_DB && S == 1 && !MH) {
-            if (nitems <= cus) return launch_s2c32_k<S, TH, MW, MH, BF, true>(p, geo, grid, stream);
+            if (nitems <= cus) return launch_s2c32_k<S, TH, MW, MH, EL, true>(p, geo, grid, stream);
         }
-        return launch_s2c32_k<S, TH, MW, MH, BF, false>(p, geo, grid, stream);
+        return launch_s2c32_k<S, TH, MW, MH, EL, false>(p, geo, grid, stream);
     }
 }
 
@@ -639,8 +643,10 @@ void set_stream_launch_limit(long long bytes) {
 // one IMAGE must be addressable with 31-bit byte offsets (buffer descriptors, OOB marker 2^31); a batch that is not
 // is cut into image ranges by the launcher (images_per_launch), so this predicate does not look at N
 bool conv_s2c32_supported(const ConvParams& p) {
-    // (BF with out_f32: stride 1 without residual only — conv_s2c32_f32out_kernel; launch_conv_s2c32 refuses it)
-    if ((p.fmt == FMT_BF)) return (p.Cinp & 63) == 0 && p.Cinp >= 64 && (p.Coutp & 63) == 0 && (!p.out_f32 || !p.res) && p.nheads <= 1 &&
+    // (BF with out_f32: stride 1 without residual only — conv_s2c32_f32out_kernel; launch_conv_s2c32 refuses it.  HF has
+    // no f32-output form: it exists for seg_hrnet3's output layer, which has no fp16 mode)
+    if (p.fmt == FMT_HF && p.out_f32) return false;
+    if (fmt_half(p.fmt)) return (p.Cinp & 63) == 0 && p.Cinp >= 64 && (p.Coutp & 63) == 0 && (!p.out_f32 || !p.res) && p.nheads <= 1 &&
                      (long long)p.H * p.W * p.Cinp * 2 < 0x7fffffffLL && (long long)p.OH * p.OW * p.Coutp * (p.out_f32 ? 4 : 2) < 0x7fffffffLL;
     return (p.Cinp & 31) == 0 && p.Cinp >= 32 && (p.Coutp & 31) == 0 && !p.out_f32 &&
            (long long)p.H * p.W * p.Cinp * 4 < 0x7fffffffLL &&
@@ -649,12 +655,13 @@ bool conv_s2c32_supported(const ConvParams& p) {
 
 int launch_conv_s2c32(const ConvParams& p, hipStream_t stream) {
     if (!conv_s2c32_supported(p) || p.out_f32) return (int)hipErrorInvalidValue;
-    if ((p.fmt == FMT_BF)) return launch_s2c32_t<2, 4, 4, false, true>(p, stream);
+    if (p.fmt == FMT_HF) return launch_s2c32_t<2, 4, 4, false, EL_HF>(p, stream);
+    if (p.fmt == FMT_BF) return launch_s2c32_t<2, 4, 4, false, EL_BF>(p, stream);
     return (p.Coutp % 64 == 0) ? launch_s2c32_t<2, 4, 4>(p, stream) : launch_s2c32_t<2, 4, 2>(p, stream);
 }
 
 bool conv_s2c32_multi_supported(const ConvParams& p) {
-    if ((p.fmt == FMT_BF)) return false;
+    if (fmt_half(p.fmt)) return false;
     if (p.nheads < 2 || p.nheads > 3 || p.res || p.out_f32 || p.hb[0] != 0 || p.hb[p.nheads] != p.Coutp) return false;
     if ((p.Cinp & 31) || p.Cinp < 32 || (long long)p.H * p.W * p.Cinp * 4 >= 0x7fffffffLL) return false;
     for (int h = 0; h < p.nheads; ++h) {
@@ -682,14 +689,15 @@ int launch_conv_s2c32_multi(const ConvParams& p, hipStream_t stream) {
 // loses more to its own stalls than the longer step wins back — and the residual is folded at another point of the
 // accumulation, so results are not bit-identical to the 8-row tile.  Not used.
 bool use_th16(const ConvParams& p) {
-    if (!S2_TH16 || (p.fmt == FMT_BF) || p.Coutp % 64 != 0 || p.OH < 16) return false;
+    if (!S2_TH16 || fmt_half(p.fmt) || p.Coutp % 64 != 0 || p.OH < 16) return false;
     const long long items16 = (long long)p.N * ((p.OH + 15) / 16) * ((p.OW + 15) / 16) * (p.Coutp / 64);
     return items16 >= device_cus();
 }
 
 int launch_conv_s1w(const ConvParams& p, hipStream_t stream) {
     if (!conv_s2c32_supported(p)) return (int)hipErrorInvalidValue;
-    if ((p.fmt == FMT_BF)) return p.out_f32 ? launch_s2c32_t<1, 8, 4, false, true, true>(p, stream) : launch_s2c32_t<1, 8, 4, false, true>(p, stream);
+    if (p.fmt == FMT_HF) return launch_s2c32_t<1, 8, 4, false, EL_HF>(p, stream);
+    if (p.fmt == FMT_BF) return p.out_f32 ? launch_s2c32_t<1, 8, 4, false, EL_BF, true>(p, stream) : launch_s2c32_t<1, 8, 4, false, EL_BF>(p, stream);
 #if S2_TH16
     if (use_th16(p)) return launch_s2c32_t<1, 16, 4>(p, stream);
 #endif
@@ -702,14 +710,14 @@ bool conv_jobs_supported(const ConvParams* ps, int n, int stride) {
     if (n < 2 || n > MAXJOBS || (stride != 1 && stride != 2)) return false;
     for (int j = 0; j < n; ++j) {
         const ConvParams& p = ps[j];
-        if (p.fmt != ps[0].fmt || p.nheads > 1 || p.out_f32 || p.Coutp % ((p.fmt == FMT_BF) ? 64 : 32) != 0 || !conv_s2c32_supported(p)) return false;
+        if (p.fmt != ps[0].fmt || p.nheads > 1 || p.out_f32 || p.Coutp % (fmt_half(p.fmt) ? 64 : 32) != 0 || !conv_s2c32_supported(p)) return false;
         if (images_per_launch(p) < p.N || (stride == 1 && (p.H != p.OH || p.W != p.OW || use_th16(p)))) return false;
         if (stride == 2 && (p.OH != (p.H + 1) / 2 || p.OW != (p.W + 1) / 2 || p.res)) return false;
     }
     return true;
 }
 
-template <int S, int TH, bool BF>
+template <int S, int TH, int EL>
 static int launch_jobs_t(const ConvParams* ps, int n, hipStream_t stream) {
     using S2C = ConvCfg<3, S, TH, 2>;
     StreamJobs jobs{};
@@ -734,7 +742,7 @@ static int launch_jobs_t(const ConvParams* ps, int n, hipStream_t stream) {
         geo.m_ty = magic_of(geo.tiles_y);
         int grid = (int)(nitems < slots ? nitems : slots);
         if (grid > geo.ctiles) grid -= grid % geo.ctiles;
-        order[j] = {j, grid, ((nitems + grid - 1) / grid) * (p.Cinp >> (BF ? 6 : 5))};
+        order[j] = {j, grid, ((nitems + grid - 1) / grid) * (p.Cinp >> (el_half(EL) ? 6 : 5))};
     }
     std::sort(order, order + n, [](const J& a, const J& b) { return a.steps > b.steps; });   // longest workgroups first
     jobs.njobs = n;
@@ -747,7 +755,7 @@ static int launch_jobs_t(const ConvParams* ps, int n, hipStream_t stream) {
         at += order[k].grid;
     }
     for (int k = n; k <= MAXJOBS; ++k) jobs.start[k] = at;
-    auto kern = conv_s2c32_jobs_kernel<S, TH, BF>;
+    auto kern = conv_s2c32_jobs_kernel<S, TH, EL>;
     if (const int e_ = ensure_dyn_lds(reinterpret_cast<const void*>(kern), S2C::XBYTES)) return e_;
     hipLaunchKernelGGL(kern, dim3((unsigned)at), dim3(NTHREADS), S2C::XBYTES, stream, jobs);
     return (int)hipGetLastError();
@@ -755,8 +763,11 @@ static int launch_jobs_t(const ConvParams* ps, int n, hipStream_t stream) {
 
 int launch_conv_jobs(const ConvParams* ps, int n, int stride, hipStream_t stream) {
     if (!conv_jobs_supported(ps, n, stride)) return (int)hipErrorInvalidValue;
-    if (stride == 1) return (ps[0].fmt == FMT_BF) ? launch_jobs_t<1, 8, true>(ps, n, stream) : launch_jobs_t<1, 8, false>(ps, n, stream);
-    return (ps[0].fmt == FMT_BF) ? launch_jobs_t<2, 4, true>(ps, n, stream) : launch_jobs_t<2, 4, false>(ps, n, stream);
+    const int fmt = ps[0].fmt;
+    if (stride == 1) return fmt == FMT_HF ? launch_jobs_t<1, 8, EL_HF>(ps, n, stream) : fmt == FMT_BF ? launch_jobs_t<1, 8, EL_BF>(ps, n, stream)
+                                                                                                     : launch_jobs_t<1, 8, EL_SB>(ps, n, stream);
+    return fmt == FMT_HF ? launch_jobs_t<2, 4, EL_HF>(ps, n, stream) : fmt == FMT_BF ? launch_jobs_t<2, 4, EL_BF>(ps, n, stream)
+                                                                                    : launch_jobs_t<2, 4, EL_SB>(ps, n, stream);
 }
 
 }  // namespace esa

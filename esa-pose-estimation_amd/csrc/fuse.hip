@@ -15,6 +15,8 @@
 namespace esa {
 namespace {
 
+static_assert(FMT_BF == EL_BF && FMT_HF == EL_HF && FMT_SB == EL_SB, "format codes double as element types");
+
 struct Lerp {
     int i0, i1;
     float l0, l1;
@@ -61,8 +63,8 @@ struct FuseScales {
 // one 8-channel group of a pixel -> 8 floats (SB: hi + lo chunks, 32 bytes; BF: one 16-byte chunk)
 template <int FMT>
 __device__ __forceinline__ void load8(const char* pix, int c8, float v[8]) {
-    if (FMT == FMT_BF) {
-        unpack8_bf16(*reinterpret_cast<const uint4*>(pix + c8 * 16), v);
+    if (FMT == FMT_BF || FMT == FMT_HF) {
+        unpack8_el<FMT>(*reinterpret_cast<const uint4*>(pix + c8 * 16), v);       // (FMT_BF / FMT_HF are sb.h's EL_BF / EL_HF)
     } else if (FMT == FMT_F32) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(pix + c8 * 32), b = *reinterpret_cast<const f32x4*>(pix + c8 * 32 + 16);
         v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
@@ -73,7 +75,7 @@ __device__ __forceinline__ void load8(const char* pix, int c8, float v[8]) {
 
 template <int NS, int NU, int FMT = FMT_SB>
 __global__ __launch_bounds__(256) void fuse_kernel(FuseParams p, FuseScales fs) {
-    constexpr bool BF = FMT == FMT_BF;
+    constexpr bool BF = FMT == FMT_BF || FMT == FMT_HF;        // 2 bytes per channel; HF: f32 sum, one saturating fp16 rounding
     const int G = p.Cp >> 3;
     const unsigned u = blockIdx.x * 256u + threadIdx.x;
     if (u >= (unsigned)(p.W * G)) return;
@@ -119,7 +121,7 @@ __global__ __launch_bounds__(256) void fuse_kernel(FuseParams p, FuseScales fs) 
         for (int i = 0; i < 8; ++i) acc[i] = relu1(acc[i]);
     }
     if (BF) {
-        *reinterpret_cast<uint4*>(p.y + ((size_t)row * p.W + x) * (size_t)pixb + c8 * 16) = pack8_bf16(acc);
+        *reinterpret_cast<uint4*>(p.y + ((size_t)row * p.W + x) * (size_t)pixb + c8 * 16) = pack8_el<FMT>(acc);
         return;
     }
     if (FMT == FMT_F32) {
@@ -267,6 +269,7 @@ int launch_fuse_t(const FuseParams& p, const FuseScales& fs, hipStream_t stream)
     if (per_row <= 0 || rows <= 0 || rows > 0x7fffffffLL || per_row > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((per_row + 255) / 256), (unsigned)rows);
     if (p.fmt == FMT_BF) hipLaunchKernelGGL((fuse_kernel<NS, NU, FMT_BF>), grid, dim3(256), 0, stream, p, fs);
+    else if (p.fmt == FMT_HF) hipLaunchKernelGGL((fuse_kernel<NS, NU, FMT_HF>), grid, dim3(256), 0, stream, p, fs);
     else if (p.fmt == FMT_F32) hipLaunchKernelGGL((fuse_kernel<NS, NU, FMT_F32>), grid, dim3(256), 0, stream, p, fs);
     else hipLaunchKernelGGL((fuse_kernel<NS, NU, FMT_SB>), grid, dim3(256), 0, stream, p, fs);
     return (int)hipGetLastError();

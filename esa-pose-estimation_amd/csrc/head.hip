@@ -498,7 +498,11 @@ constexpr int MPLANE = ((MIH * MIW * 16 + 255) / 256) * 256;       // 5376 B, mu
 constexpr int MSRC = 12;                           // source window of a tile (rows and columns), see the staging
 __host__ __device__ constexpr bool final_wreg(int cg, int m) { return m == 1 && (9 * cg + 3) / 4 <= 7; }
 
-template <int CG, int M>
+// HF: h3 is an HF tensor (fp16 mode, esahrnet_cfg.precision 3).  The layer itself stays split-bf16: a half widens to f32
+// exactly, the four taps are interpolated in f32 as in every mode, and the interpolated value is split into hi + lo bf16
+// as the other modes' values are.  Where a tap weight is 1 (the crop's corners, every source-aligned pixel) the value IS
+// a stored half, and hi + lo carries it exactly: 11 significand bits fit in 8 + 8.
+template <int CG, int M, bool HF = false>
 __global__ __launch_bounds__(256, 2) void final_mfma_kernel(FinalParams p, const uint4* __restrict__ wpk, int tiles_x,
                                                            int tiles_y) {
     constexpr int NG = 9 * CG;                    // K-slot groups carrying weights
@@ -540,7 +544,10 @@ __global__ __launch_bounds__(256, 2) void final_mfma_kernel(FinalParams p, const
         const int q = u / NKG;
         const int sy = q / scols, sx = q - sy * scols;
         float v[8];
-        if (p.fmt == FMT_BF) {         // single-bf16 tensor (precision = 1): 2 bytes per channel
+        if (HF) {                      // single-fp16 tensor (precision = 3)
+            const char* a = p.h3 + (((size_t)n * p.h + sy0 + sy) * p.wd + sx0 + sx) * ((size_t)p.Cp * 2) + kg * 16;
+            unpack8_f16(*reinterpret_cast<const uint4*>(a), v);
+        } else if (p.fmt == FMT_BF) {         // single-bf16 tensor (precision = 1): 2 bytes per channel
             const char* a = p.h3 + (((size_t)n * p.h + sy0 + sy) * p.wd + sx0 + sx) * ((size_t)p.Cp * 2) + kg * 16;
             unpack8_bf16(*reinterpret_cast<const uint4*>(a), v);
         } else {
@@ -693,14 +700,14 @@ __global__ __launch_bounds__(256, 2) void final_mfma_kernel(FinalParams p, const
     }
 }
 
-template <int CG, int M>
+template <int CG, int M, bool HF = false>
 int launch_final_mfma_t(const FinalParams& p, hipStream_t stream) {
     constexpr int NCH = (9 * CG + 3) / 4;
     const int tiles_x = (p.W + MTW - 1) / MTW, tiles_y = (p.H + MTH - 1) / MTH;
     const long long nblk = (long long)p.N * tiles_x * tiles_y;
     if (nblk <= 0 || nblk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     const int lds = 2 * CG * MPLANE + (final_wreg(CG, M) ? 0 : M * NCH * 2048) + MSRC * MSRC * CG * 32 + 4 * M * 16 * 8;
-    auto kern = final_mfma_kernel<CG, M>;
+    auto kern = final_mfma_kernel<CG, M, HF>;
     if (const int e_ = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds)) return e_;
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, stream, p, p.wpk, tiles_x, tiles_y);
     return (int)hipGetLastError();
@@ -807,6 +814,15 @@ int launch_final2_kp(const FinalParams& p, float* bmax, float* kp, int* idx_out,
 int launch_final(const FinalParams& p, hipStream_t stream) {
     if (p.wpk && final_mfma_supported(p.K, p.cin)) {
         const int cg = (p.K + p.cin + 7) / 8, m = (p.K + 15) / 16;
+        if (p.fmt == FMT_HF) {
+            switch (cg * 10 + m) {
+                case 21: return launch_final_mfma_t<2, 1, true>(p, stream);
+                case 31: return launch_final_mfma_t<3, 1, true>(p, stream);
+                case 32: return launch_final_mfma_t<3, 2, true>(p, stream);
+                case 42: return launch_final_mfma_t<4, 2, true>(p, stream);
+                case 52: return launch_final_mfma_t<5, 2, true>(p, stream);
+            }
+        }
         switch (cg * 10 + m) {
             case 21: return launch_final_mfma_t<2, 1>(p, stream);
             case 31: return launch_final_mfma_t<3, 1>(p, stream);
@@ -815,6 +831,7 @@ int launch_final(const FinalParams& p, hipStream_t stream) {
             case 52: return launch_final_mfma_t<5, 2>(p, stream);
         }
     }
+    if (p.fmt == FMT_HF) return (int)hipErrorInvalidValue;      // fp16 tensors: the matrix-core kernel only (esahrnet_create checks)
     switch (final_kt(p.K)) {
         case 11: return launch_final_t<11>(p, stream);
         case 16: return launch_final_t<16>(p, stream);

@@ -70,7 +70,10 @@ __device__ __forceinline__ uint32_t lane_xor4(uint32_t v, bool hi) {
 // output row and column only: built once per wave, kept in registers, exact in bf16 for the 2x / 4x / 8x grids (numerators
 // < 256); other ratios carry a lo part (`ulo`: two more MFMAs).  The accumulator is the one W0·x0 already uses.  Replaces 96
 // multiply-adds + 96 bf16 widenings per lane and chunk (the kernel was VALU-bound: 2.65 ms at W48 384x384 batch 64).
-template <int NB0, int M3, bool MF>
+// EL (sb.h): EL_BF, or EL_HF for the fp16 mode (esahrnet_cfg.precision = 3) — the same kernel on v_mfma_f32_16x16x32_f16 with
+// fp16 tensors, weights and U.  The interpolation weights of the 2x / 4x / 8x grids are exact in fp16 as they are in bf16
+// (numerators < 256 over a power of two); h0 and h3 are rounded to nearest even and saturated (sb.h pack2_f16).
+template <int NB0, int M3, bool MF, int EL = EL_BF>
 __global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(HeadParams p, int tiles_x, int tiles_y, int ulo) {
     constexpr int WFR = 2 * NB0 * 2 + M3;               // 1-KB weight fragments per chunk: W0 [m][block][step], W3 [m]
     constexpr int WBYTES = WFR * 1024;
@@ -222,16 +225,16 @@ __global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(Hea
             }
             toff1 = (b == 1 ? T2OFF : T3OFF) + ((row * 32 + ch) * 8) * 2;
         }
-        const uint4 ha = pack8_bf16(wa), hb = pack8_bf16(wb_);
+        const uint4 ha = pack8_el<EL>(wa), hb = pack8_el<EL>(wb_);
         u0 = __builtin_bit_cast(bf16x8, ha);
         u1 = __builtin_bit_cast(bf16x8, hb);
         float ra[8], rb[8];
-        unpack8_bf16(ha, ra);
-        unpack8_bf16(hb, rb);
+        unpack8_el<EL>(ha, ra);
+        unpack8_el<EL>(hb, rb);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { ra[j] = wa[j] - ra[j]; rb[j] = wb_[j] - rb[j]; }
-        u0l = __builtin_bit_cast(bf16x8, pack8_bf16(ra));
-        u1l = __builtin_bit_cast(bf16x8, pack8_bf16(rb));
+        u0l = __builtin_bit_cast(bf16x8, pack8_el<EL>(ra));
+        u1l = __builtin_bit_cast(bf16x8, pack8_el<EL>(rb));
     }
     int o00[3], o01[3], o10[3], o11[3];     // (VALU form) LDS byte offsets of the 4 taps (incl. region base, q*8)
     float w00[3], w01[3], w10[3], w11[3];
@@ -265,8 +268,8 @@ __global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(Hea
             for (int c = 0; c < NB0; ++c) {
                 const bf16x8 w0 = *reinterpret_cast<const bf16x8*>(wb + ((m * NB0 + c) * 2 + 0) * 1024);
                 const bf16x8 w1 = *reinterpret_cast<const bf16x8*>(wb + ((m * NB0 + c) * 2 + 1) * 1024);
-                a[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, x0[c], a[m], 0, 0, 0);
-                a[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x1[c], a[m], 0, 0, 0);
+                a[m] = mfma_el<EL>(w0, x0[c], a[m]);
+                a[m] = mfma_el<EL>(w1, x1[c], a[m]);
             }
         f32x4 s[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
         if (MF) {
@@ -274,11 +277,11 @@ __global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(Hea
             for (int m = 0; m < 2; ++m) {
                 const bf16x8 t0 = *reinterpret_cast<const bf16x8*>(tb + toff0 + m * (16 * 16 * 2));
                 const bf16x8 t1 = *reinterpret_cast<const bf16x8*>(tb + toff1 + m * (16 * 8 * 2));
-                a[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t0, u0, a[m], 0, 0, 0);
-                a[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t1, u1, a[m], 0, 0, 0);
+                a[m] = mfma_el<EL>(t0, u0, a[m]);
+                a[m] = mfma_el<EL>(t1, u1, a[m]);
                 if (ulo) {
-                    a[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t0, u0l, a[m], 0, 0, 0);
-                    a[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t1, u1l, a[m], 0, 0, 0);
+                    a[m] = mfma_el<EL>(t0, u0l, a[m]);
+                    a[m] = mfma_el<EL>(t1, u1l, a[m]);
                 }
             }
         }
@@ -287,10 +290,10 @@ __global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(Hea
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 float v00[4], v01[4], v10[4], v11[4];
-                unpack4_bf16(*reinterpret_cast<const uint2*>(tb + o00[b] + m * 32), v00);
-                unpack4_bf16(*reinterpret_cast<const uint2*>(tb + o01[b] + m * 32), v01);
-                unpack4_bf16(*reinterpret_cast<const uint2*>(tb + o10[b] + m * 32), v10);
-                unpack4_bf16(*reinterpret_cast<const uint2*>(tb + o11[b] + m * 32), v11);
+                unpack4_el<EL>(*reinterpret_cast<const uint2*>(tb + o00[b] + m * 32), v00);
+                unpack4_el<EL>(*reinterpret_cast<const uint2*>(tb + o01[b] + m * 32), v01);
+                unpack4_el<EL>(*reinterpret_cast<const uint2*>(tb + o10[b] + m * 32), v10);
+                unpack4_el<EL>(*reinterpret_cast<const uint2*>(tb + o11[b] + m * 32), v11);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     s[m][i] += w00[b] * v00[i] + w01[b] * v01[i] + w10[b] * v10[i] + w11[b] * v11[i];
@@ -303,11 +306,11 @@ __global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(Hea
             v[i] = relu1(a[0][i] + s[0][i]);
             v[4 + i] = relu1(a[1][i] + s[1][i]);
         }
-        const bf16x8 hh = __builtin_bit_cast(bf16x8, pack8_bf16(v));
+        const bf16x8 hh = __builtin_bit_cast(bf16x8, pack8_el<EL>(v));
 #pragma unroll
         for (int m = 0; m < M3; ++m) {
             const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(wb + (4 * NB0 + m) * 1024);
-            acc3[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, hh, acc3[m], 0, 0, 0);
+            acc3[m] = mfma_el<EL>(a3, hh, acc3[m]);
         }
         if (cc + 1 < nchunks) {
             HB_COMMIT(buf ^ 1)          // nobody reads buffer buf^1 during this iteration
@@ -327,15 +330,15 @@ __global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(Hea
             float v[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = relu1(acc3[m][i] + bv[i]);
-            *reinterpret_cast<uint2*>(o + co * 2) = pack4_bf16(v);
+            *reinterpret_cast<uint2*>(o + co * 2) = pack4_el<EL>(v);
         }
         for (int c = M3 * 16 + q * 4; c < p.C3p; c += 16) *reinterpret_cast<uint2*>(o + c * 2) = make_uint2(0, 0);
     }
 }
 
-template <int NB0, int M3, bool MF>
+template <int NB0, int M3, bool MF, int EL = EL_BF>
 int launch_head_bf_t(const HeadParams& p, hipStream_t stream) {
-    auto kern = head_fused_bf_kernel<NB0, M3, MF>;
+    auto kern = head_fused_bf_kernel<NB0, M3, MF, EL>;
     const int lds = 2 * ((MF ? TBYTES : BBUF) + (2 * NB0 * 2 + M3) * 1024);
     // exact bf16 interpolation weights: every branch grid is the 2x / 4x / 8x decimation of branch 0's
     int ulo = 0;
@@ -378,6 +381,14 @@ bool head_fused_bf_supported(int H, int W, const int th[3], const int tw[3], int
 int launch_head_bf(const HeadParams& p, hipStream_t stream) {
     if ((p.Ctp & 31) || (p.C3p & 3)) return (int)hipErrorInvalidValue;
     const int m3 = p.K <= 16 ? 1 : 2;
+    if (p.hf) {         // fp16 tensors: the matrix-core form only
+        if (p.valu) return (int)hipErrorInvalidValue;
+        if (p.C0p == 64 && m3 == 1) return launch_head_bf_t<1, 1, true, EL_HF>(p, stream);
+        if (p.C0p == 64 && m3 == 2) return launch_head_bf_t<1, 2, true, EL_HF>(p, stream);
+        if (p.C0p == 128 && m3 == 1) return launch_head_bf_t<2, 1, true, EL_HF>(p, stream);
+        if (p.C0p == 128 && m3 == 2) return launch_head_bf_t<2, 2, true, EL_HF>(p, stream);
+        return (int)hipErrorInvalidValue;
+    }
     if (p.valu) {       // the first-generation (VALU interpolation) form (A/B, tests)
         if (p.C0p == 64 && m3 == 1) return launch_head_bf_t<1, 1, false>(p, stream);
         if (p.C0p == 64 && m3 == 2) return launch_head_bf_t<1, 2, false>(p, stream);
@@ -395,7 +406,7 @@ int launch_head_bf(const HeadParams& p, hipStream_t stream) {
 // W3 [K][Ct] (1x1) -> [M3][Ctp/32][lane][8] bf16 with the permuted K order of the h0 fragment (head_fused.hip):
 // lane (r = l&15, g = l>>4), element j  <->  channel chunk*32 + (j < 4 ? 4g + j : 16 + 4g + j - 4)
 size_t head_w3_bf_bytes(int K, int Ctp) { return (size_t)(K <= 16 ? 1 : 2) * (Ctp / 32) * 1024; }
-void pack_head_w3_bf(const float* w, int K, int Ct, int Ctp, void* dst) {
+void pack_head_w3_bf(const float* w, int K, int Ct, int Ctp, void* dst, bool half) {
     uint16_t* d = static_cast<uint16_t*>(dst);
     const int m3 = K <= 16 ? 1 : 2, nch = Ctp / 32;
     for (int m = 0; m < m3; ++m)
@@ -406,7 +417,7 @@ void pack_head_w3_bf(const float* w, int K, int Ct, int Ctp, void* dst) {
                     const int ch = c * 32 + (j < 4 ? 4 * g + j : 16 + 4 * g + j - 4);
                     float v = 0.f;
                     if (r < K && ch < Ct) v = w[(size_t)r * Ct + ch];
-                    d[(((size_t)m * nch + c) * 64 + l) * 8 + j] = hbf16(v);
+                    d[(((size_t)m * nch + c) * 64 + l) * 8 + j] = half ? host_f16(v) : hbf16(v);
                 }
 }
 

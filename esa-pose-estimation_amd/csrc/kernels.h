@@ -5,8 +5,11 @@
 
 namespace esa {
 
-// tensor formats of the internal activations (sb.h): split-bf16 NHWC, single bf16 NHWC, plain f32 NHWC
-enum { FMT_SB = 0, FMT_BF = 1, FMT_F32 = 2 };
+// tensor formats of the internal activations (sb.h): split-bf16 NHWC, single bf16 NHWC, plain f32 NHWC, single fp16 NHWC
+// (HF: the BF layout with IEEE binary16 elements — wherever a comment says "BF tensors" of a launcher that takes a
+// format, HF tensors are served the same way by the fp16 instantiation of the same kernel)
+enum { FMT_SB = 0, FMT_BF = 1, FMT_F32 = 2, FMT_HF = 3 };
+inline bool fmt_half(int fmt) { return fmt == FMT_BF || fmt == FMT_HF; }       // 2 bytes per channel, channels padded to 64
 
 // thread-local error text behind esahrnet_last_error() (plan.hip); returns 1 so that `return set_error(...)` reads well
 int set_error(const char* fmt, ...);
@@ -66,7 +69,12 @@ void pack_conv_weights(const float* w, int cout, int cin, int k, int coutp, int 
 // W[tile*16 + (l&15)][block*64 + step*32 + 8*(l>>4) + j] rounded to bf16 — same fragment count and order as the
 // split format has for twice the channels per block
 size_t packed_weight_bytes_bf(int coutp, int cinp, int k);
-void pack_conv_weights_bf(const float* w, int cout, int cin, int k, int coutp, int cinp, void* dst);
+// half = true: fp16 elements (FMT_HF) in the same order
+void pack_conv_weights_bf(const float* w, int cout, int cin, int k, int coutp, int cinp, void* dst, bool half = false);
+// f32 -> IEEE binary16 bits on the host (round to nearest even, subnormals kept, inf beyond 65504 + half an ulp); is the
+// rounded value finite?
+uint16_t host_f16(float f);
+bool host_f16_finite(float f);
 
 // bf16x6 mode (conv_x6.hip): [cout16 tile][cin32 chunk][tap][term 0..2][lane][8 x bf16], every weight split exactly into
 // three bf16 terms, K order inside a chunk as the staging threads load it (x6_chan_of_k)
@@ -193,6 +201,7 @@ struct HeadParams {
     int th[3], tw[3];
     int C0p, Ctp, C3p, K;
     bool valu;          // launch_head_bf: the first-generation form (VALU interpolation) instead of the matrix-core one
+    bool hf;            // launch_head_bf: x0, t[b] and y are HF tensors, w0 / w3 packed with half = true (matrix-core form only)
 };
 int launch_head(const HeadParams& p, hipStream_t stream);
 bool head_fused_supported(int H, int W, const int th[3], const int tw[3], int C0p, int K);
@@ -203,7 +212,7 @@ void pack_head_w3(const float* w, int K, int Ct, int Ctp, void* dst);
 int launch_head_bf(const HeadParams& p, hipStream_t stream);
 bool head_fused_bf_supported(int H, int W, const int th[3], const int tw[3], int C0p, int K);
 size_t head_w3_bf_bytes(int K, int Ctp);
-void pack_head_w3_bf(const float* w, int K, int Ct, int Ctp, void* dst);
+void pack_head_w3_bf(const float* w, int K, int Ct, int Ctp, void* dst, bool half = false);     // half: fp16 elements (FMT_HF)
 
 // fp32-grade mode (head_x6.hip): x0, t[b] and y are f32 NHWC tensors; w0 / w3 = pack_conv_weights_x6(k = 1) of the branch-0
 // slice of last_layer[0] and of last_layer[3] (cout padded to 16 or 32)
@@ -345,6 +354,9 @@ int launch_sb_to_nchw(const char* x, int N, int C, int H, int W, int Cp, float* 
 // the same for BF tensors (single bf16 NHWC, sb.h)
 int launch_nchw_to_bf(const float* x, int N, int C, int H, int W, char* y, int Cp, hipStream_t s);
 int launch_bf_to_nchw(const char* x, int N, int C, int H, int W, int Cp, float* y, hipStream_t s);
+// for HF tensors (single fp16 NHWC: rounded to nearest even and saturated on the way in, exact on the way out)
+int launch_nchw_to_hf(const float* x, int N, int C, int H, int W, char* y, int Cp, hipStream_t s);
+int launch_hf_to_nchw(const char* x, int N, int C, int H, int W, int Cp, float* y, hipStream_t s);
 // and for F32 tensors (plain f32 NHWC)
 int launch_nchw_to_f32(const float* x, int N, int C, int H, int W, char* y, int Cp, hipStream_t s);
 int launch_f32_to_nchw(const char* x, int N, int C, int H, int W, int Cp, float* y, hipStream_t s);

@@ -7,7 +7,8 @@
 namespace esa {
 namespace {
 
-template <bool BF>
+// EL (sb.h): EL_SB, EL_BF or EL_HF (fp16: rounded to nearest even, saturated)
+template <int EL>
 __global__ __launch_bounds__(256) void nchw_to_sb_kernel(const float* x, int N, int C, int H, int W,
                                                          char* y, int Cp, long long total) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -24,8 +25,8 @@ __global__ __launch_bounds__(256) void nchw_to_sb_kernel(const float* x, int N, 
         const int c = c8 * 8 + i;
         v[i] = c < C ? x[((size_t)n * C + c) * hw + s] : 0.f;
     }
-    if (BF) {
-        *reinterpret_cast<uint4*>(y + (size_t)pix * (size_t)(Cp * 2) + c8 * 16) = pack8_bf16(v);
+    if (el_half(EL)) {
+        *reinterpret_cast<uint4*>(y + (size_t)pix * (size_t)(Cp * 2) + c8 * 16) = pack8_el<EL>(v);
         return;
     }
     uint4 hi, lo;
@@ -35,7 +36,7 @@ __global__ __launch_bounds__(256) void nchw_to_sb_kernel(const float* x, int N, 
     *reinterpret_cast<uint4*>(o + 16) = lo;
 }
 
-template <bool BF>
+template <int EL>
 __global__ __launch_bounds__(256) void sb_to_nchw_kernel(const char* x, int N, int C, int H, int W,
                                                          int Cp, float* y, long long total) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;   // over (n, c, s), s fastest
@@ -45,8 +46,9 @@ __global__ __launch_bounds__(256) void sb_to_nchw_kernel(const char* x, int N, i
     const long long nc = idx / hw;
     const int c = (int)(nc % C);
     const int n = (int)(nc / C);
-    if (BF) {
-        y[idx] = bf16_bits_to_f32(*reinterpret_cast<const unsigned short*>(x + ((size_t)n * hw + s) * (size_t)(Cp * 2) + c * 2));
+    if (el_half(EL)) {
+        const uint32_t b = *reinterpret_cast<const unsigned short*>(x + ((size_t)n * hw + s) * (size_t)(Cp * 2) + c * 2);
+        y[idx] = EL == EL_HF ? f16_bits_to_f32(b) : bf16_bits_to_f32(b);
         return;
     }
     const char* a = x + ((size_t)n * hw + s) * (size_t)(Cp * 4) + (c >> 3) * 32 + (c & 7) * 2;
@@ -225,11 +227,11 @@ int launch_f32_to_nchw(const char* x, int N, int C, int H, int W, int Cp, float*
 }
 
 int launch_nchw_to_fmt(int fmt, const float* x, int N, int C, int H, int W, char* y, int Cp, hipStream_t s) {
-    return fmt == FMT_BF ? launch_nchw_to_bf(x, N, C, H, W, y, Cp, s) : fmt == FMT_F32 ? launch_nchw_to_f32(x, N, C, H, W, y, Cp, s)
+    return fmt == FMT_BF ? launch_nchw_to_bf(x, N, C, H, W, y, Cp, s) : fmt == FMT_HF ? launch_nchw_to_hf(x, N, C, H, W, y, Cp, s) : fmt == FMT_F32 ? launch_nchw_to_f32(x, N, C, H, W, y, Cp, s)
                                                                                           : launch_nchw_to_sb(x, N, C, H, W, y, Cp, s);
 }
 int launch_fmt_to_nchw(int fmt, const char* x, int N, int C, int H, int W, int Cp, float* y, hipStream_t s) {
-    return fmt == FMT_BF ? launch_bf_to_nchw(x, N, C, H, W, Cp, y, s) : fmt == FMT_F32 ? launch_f32_to_nchw(x, N, C, H, W, Cp, y, s)
+    return fmt == FMT_BF ? launch_bf_to_nchw(x, N, C, H, W, Cp, y, s) : fmt == FMT_HF ? launch_hf_to_nchw(x, N, C, H, W, Cp, y, s) : fmt == FMT_F32 ? launch_f32_to_nchw(x, N, C, H, W, Cp, y, s)
                                                                                           : launch_sb_to_nchw(x, N, C, H, W, Cp, y, s);
 }
 
@@ -237,7 +239,7 @@ int launch_nchw_to_sb(const float* x, int N, int C, int H, int W, char* y, int C
     const long long total = (long long)N * H * W * (Cp >> 3);
     const long long nblk = (total + 255) / 256;
     if (nblk <= 0 || nblk > 0x7fffffffLL || (Cp & 7) || C > Cp) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(nchw_to_sb_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, s, x, N, C, H, W, y, Cp, total);
+    hipLaunchKernelGGL(nchw_to_sb_kernel<EL_SB>, dim3((unsigned)nblk), dim3(256), 0, s, x, N, C, H, W, y, Cp, total);
     return (int)hipGetLastError();
 }
 
@@ -245,7 +247,23 @@ int launch_nchw_to_bf(const float* x, int N, int C, int H, int W, char* y, int C
     const long long total = (long long)N * H * W * (Cp >> 3);
     const long long nblk = (total + 255) / 256;
     if (nblk <= 0 || nblk > 0x7fffffffLL || (Cp & 7) || C > Cp) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(nchw_to_sb_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, s, x, N, C, H, W, y, Cp, total);
+    hipLaunchKernelGGL(nchw_to_sb_kernel<EL_BF>, dim3((unsigned)nblk), dim3(256), 0, s, x, N, C, H, W, y, Cp, total);
+    return (int)hipGetLastError();
+}
+
+int launch_nchw_to_hf(const float* x, int N, int C, int H, int W, char* y, int Cp, hipStream_t s) {
+    const long long total = (long long)N * H * W * (Cp >> 3);
+    const long long nblk = (total + 255) / 256;
+    if (nblk <= 0 || nblk > 0x7fffffffLL || (Cp & 7) || C > Cp) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(nchw_to_sb_kernel<EL_HF>, dim3((unsigned)nblk), dim3(256), 0, s, x, N, C, H, W, y, Cp, total);
+    return (int)hipGetLastError();
+}
+
+int launch_hf_to_nchw(const char* x, int N, int C, int H, int W, int Cp, float* y, hipStream_t s) {
+    const long long total = (long long)N * C * H * W;
+    const long long nblk = (total + 255) / 256;
+    if (nblk <= 0 || nblk > 0x7fffffffLL || C > Cp) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sb_to_nchw_kernel<EL_HF>, dim3((unsigned)nblk), dim3(256), 0, s, x, N, C, H, W, Cp, y, total);
     return (int)hipGetLastError();
 }
 
@@ -261,7 +279,7 @@ int launch_bf_to_nchw(const char* x, int N, int C, int H, int W, int Cp, float* 
     const long long total = (long long)N * C * H * W;
     const long long nblk = (total + 255) / 256;
     if (nblk <= 0 || nblk > 0x7fffffffLL || C > Cp) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(sb_to_nchw_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, s, x, N, C, H, W, Cp, y, total);
+    hipLaunchKernelGGL(sb_to_nchw_kernel<EL_BF>, dim3((unsigned)nblk), dim3(256), 0, s, x, N, C, H, W, Cp, y, total);
     return (int)hipGetLastError();
 }
 

@@ -162,7 +162,8 @@ struct PlanOptions {
     bool unfused, head_v1, final_valu, no_multihead, no_jobs, no_bblock, no_cbam_jobs, cbam_unfused, stem_pool_separate,
          head3_direct, head3_cout32, bf_unfused_head, bf_head_valu, x6_unfused_head, x6_unfused_stem, tap_all;
     int nlanes;                 // 4 if ESAHRNET_STREAMS > 1 (the wave executor), else 1: everything on the caller's stream
-    int fmt;                    // tensor format: FMT_SB (precision 0), FMT_BF (1: single bf16), FMT_F32 (2: bf16x6 arithmetic)
+    int fmt;                    // tensor format: FMT_SB (precision 0), FMT_BF (1: single bf16), FMT_F32 (2: bf16x6 arithmetic),
+                                // FMT_HF (3: single fp16 — the bf16 mode's plan op for op, fp16 elements)
     StemForm stem;              // conv1 + conv2: stem_kernel + stride-2 convolution, stem_fused, or stem_x6_kernel
     bool fused_block;           // a 32-channel BasicBlock outside the job groups is one bblock32 launch
     HeadForm head;              // seg_hrnet / seg_hrnet2: the fused head kernel the plan carries (seg_hrnet3 has its own head)
@@ -182,7 +183,7 @@ PlanOptions plan_options(const esahrnet_cfg& g) {
     o.x6_unfused_stem = on("ESAHRNET_X6_UNFUSED_STEM"); o.tap_all = on("ESAHRNET_TAP_ALL");
     const char* streams = getenv("ESAHRNET_STREAMS");
     o.nlanes = streams && atoi(streams) > 1 ? 4 : 1;
-    o.fmt = g.precision == 1 ? esa::FMT_BF : g.precision == 2 ? esa::FMT_F32 : esa::FMT_SB;
+    o.fmt = g.precision == 1 ? esa::FMT_BF : g.precision == 2 ? esa::FMT_F32 : g.precision == 3 ? esa::FMT_HF : esa::FMT_SB;
     const bool sb = o.fmt == esa::FMT_SB, v0 = g.variant == 0;
     // the fused stem kernels: stem_fused serves every (cin, stem width) in the split format, stem_x6_kernel one; none in bf16
     const bool x6_stem = esa::stem_fused_x6_supported(g.cin, pad32(g.stem_width), pad32(g.stem_width)) && g.stem_width == 64;
@@ -195,7 +196,7 @@ PlanOptions plan_options(const esahrnet_cfg& g) {
     const int c0 = pad32(g.widths[0]);
     o.head = !v0 || nb4 != 4 ? HEAD_UNFUSED
            : sb ? (!o.unfused && (c0 == 32 || c0 == 64) ? HEAD_SB : HEAD_UNFUSED)
-           : o.fmt == esa::FMT_BF ? (!o.bf_unfused_head && (pad64(g.widths[0]) == 64 || pad64(g.widths[0]) == 128) ? HEAD_BF : HEAD_UNFUSED)
+           : esa::fmt_half(o.fmt) ? (!o.bf_unfused_head && (pad64(g.widths[0]) == 64 || pad64(g.widths[0]) == 128) ? HEAD_BF : HEAD_UNFUSED)
            : !o.x6_unfused_head && (c0 == 32 || c0 == 64) ? HEAD_X6 : HEAD_UNFUSED;
     // head_fused2 needs head_t's channel counts on branches 2 and 3 and 64 or 96 on branch 1
     o.head2 = !o.head_v1 && (o.head != HEAD_SB || ((pad32(g.widths[1]) == 64 || pad32(g.widths[1]) == 96) &&
@@ -233,18 +234,21 @@ struct esahrnet_ctx {
     bool committed = false;
     bool keep = false;
     PlanOptions opt;
-    bool bf() const { return opt.fmt == esa::FMT_BF; }       // tensors are single bf16 (sb.h "BF"), channels padded to 64
+    // half-width format: the tensors are single bf16 (sb.h "BF") or single fp16 ("HF"), 2 bytes per channel, channels padded
+    // to 64; hf(): the element type is fp16
+    bool h16() const { return esa::fmt_half(opt.fmt); }
+    bool hf() const { return opt.fmt == esa::FMT_HF; }
     bool x6() const { return opt.fmt == esa::FMT_F32; }
-    int padc(int ch) const { return bf() ? pad64(ch) : pad32(ch); }
-    int eb() const { return bf() ? 2 : 4; }     // bytes per stored channel
+    int padc(int ch) const { return h16() ? pad64(ch) : pad32(ch); }
+    int eb() const { return h16() ? 2 : 4; }     // bytes per stored channel
     size_t wbytes(int coutp, int cinp, int k) const {
-        return bf() ? esa::packed_weight_bytes_bf(coutp, cinp, k) : x6() ? esa::packed_weight_bytes_x6(coutp, cinp, k)
+        return h16() ? esa::packed_weight_bytes_bf(coutp, cinp, k) : x6() ? esa::packed_weight_bytes_x6(coutp, cinp, k)
                                                                          : esa::packed_weight_bytes(coutp, cinp, k);
     }
     // w [cout][cin][k][k] packed for the plan's format (wbytes(coutp, cinp, k) bytes)
     std::vector<char> pack(const float* w, int cout, int cin, int k, int coutp, int cinp) const {
         std::vector<char> p(wbytes(coutp, cinp, k), 0);
-        if (bf()) esa::pack_conv_weights_bf(w, cout, cin, k, coutp, cinp, p.data());
+        if (h16()) esa::pack_conv_weights_bf(w, cout, cin, k, coutp, cinp, p.data(), hf());
         else if (x6()) esa::pack_conv_weights_x6(w, cout, cin, k, coutp, cinp, p.data());
         else esa::pack_conv_weights(w, cout, cin, k, coutp, cinp, p.data());
         return p;
@@ -496,9 +500,9 @@ void group_jobs(esahrnet_ctx& c) {
         if (o.kind != OP_CONV || o.jkey < 0 || o.alt != 0 || o.multi >= 0) return false;
         const DevConv& d = c.dconvs[o.dconv];
         const ConvSpec& s = c.specs[d.spec];
-        if (s.k == 1) return !c.bf() && o.res < 0 && !d.out_f32 && d.c0 == 0 && d.c1 == s.cin && d.perm.empty() && d.use_bias;
+        if (s.k == 1) return !c.h16() && o.res < 0 && !d.out_f32 && d.c0 == 0 && d.c1 == s.cin && d.perm.empty() && d.use_bias;
         return s.k == 3 && !d.out_f32 && d.c0 == 0 && d.c1 == s.cin && d.perm.empty() && d.use_bias &&
-               d.coutp % (c.bf() ? 64 : 32) == 0;
+               d.coutp % (c.h16() ? 64 : 32) == 0;
     };
     size_t i = 0;
     while (i < ops.size()) {
@@ -776,7 +780,7 @@ int build_plan_ops(esahrnet_ctx& c) {
         const int l3 = B.spec("last_layer.3", "last_layer.4", tot, K, 1, 1, 1, true, true);
         c.spec_final = B.spec("output_layer.0", "", K + sw, K, 3, 1, 0, true, false);
         int h0, wide_h0 = 0;
-        if (ys.size() == 4 && !c.bf() && !c.opt.head3_direct) {
+        if (ys.size() == 4 && !c.h16() && !c.opt.head3_direct) {
             // last_layer[0] by linearity (head_gather.hip): branches 2, 3 as nine 1x1 products on their own grids + a gather,
             // branch 0 and the up-sampled branch 1 as a direct 3x3 that takes the gather's result as its residual
             const int cd = pre[0] + pre[1];
@@ -845,7 +849,7 @@ int build_plan_ops(esahrnet_ctx& c) {
             Op o; o.kind = OP_ZERO; o.out = cat2; o.terms[0] = cat2; o.c0 = sw + ((K + 7) & ~7); o.nchan = c.padc(sw + K) - o.c0;
             B.push(o);
         }
-        const int oc = B.conv(c.spec_final, cat2, -1, false, "out_sb", 0, -1, true, c.bf());
+        const int oc = B.conv(c.spec_final, cat2, -1, false, "out_sb", 0, -1, true, c.h16());
         std::vector<int>& perm = c.dconvs[c.ops.back().dconv].perm;     // packed ci -> reference ci
         for (int i = 0; i < sw; ++i) perm.push_back(K + i);              // skip channels come second in the reference
         for (int i = 0; i < K; ++i) perm.push_back(i);
@@ -1277,8 +1281,11 @@ int esahrnet_create(const esahrnet_cfg* cfg, int device, esahrnet_handle* out) {
     if (cfg->num_keypoints < 1 || esa::final_kt(cfg->num_keypoints) < 0) return fail("num_keypoints=%d unsupported (1..32)", cfg->num_keypoints);
     if (cfg->stem_width < 1 || cfg->blocks[0][0] < 1) return fail("bad stem_width/blocks");
     if (cfg->variant != 0 && cfg->variant != 1) return fail("variant=%d unsupported (0: seg_hrnet/2, 1: seg_hrnet3)", cfg->variant);
-    if (cfg->precision < 0 || cfg->precision > 2)
-        return fail("precision=%d unsupported (0: split-bf16 'bf16x3', 1: bf16, 2: fp32-grade 'bf16x6')", cfg->precision);
+    if (cfg->precision < 0 || cfg->precision > 3)
+        return fail("precision=%d unsupported (0..3 — 0: split-bf16 'bf16x3', 1: bf16, 2: fp32-grade 'bf16x6', 3: fp16)", cfg->precision);
+    if (cfg->precision == 3 && cfg->variant == 1)
+        return fail("precision=3 (fp16) is not built for variant 1 (seg_hrnet3): its CBAM kernels have no fp16 form; "
+                    "seg_hrnet / seg_hrnet2 take it, seg_hrnet3 takes 0, 1 or 2");
     if (cfg->variant == 1) {
         if (cfg->stem_width % 16) return fail("variant 1: stem_width must be a multiple of 16 (ChannelAttention ratio)");
         for (int b = 0; b < ESAHRNET_MAX_BRANCHES; ++b)
@@ -1301,6 +1308,12 @@ int esahrnet_create(const esahrnet_cfg* cfg, int device, esahrnet_handle* out) {
     c->cfg = *cfg;
     c->device = device;
     c->opt = plan_options(*cfg);
+    // fp16 tensors reach the output layer through the matrix-core kernel only (head.hip final_mfma_kernel<.., HF>)
+    if (c->hf() && !c->opt.final_mfma) {
+        delete c;
+        return fail("precision=3 (fp16) needs the matrix-core output layer: unset ESAHRNET_FINAL_VALU (num_keypoints=%d, cin=%d)",
+                    cfg->num_keypoints, cfg->cin);
+    }
     if (build_plan(*c)) { delete c; return 1; }
     *out = c;
     return 0;
@@ -1398,6 +1411,16 @@ int esahrnet_commit(esahrnet_handle h) {
         if (!s.set) return fail("commit: weights of '%s' were never set", s.name.c_str());
     for (const AuxSpec& a : h->aux)
         if (!a.set) return fail("commit: tensor '%s' was never set", a.name.c_str());
+    if (h->hf()) {      // a folded weight that rounds to +-inf in fp16 is refused, not saturated (conv1 and the output layer stay f32 / split bf16)
+        for (size_t i = 0; i < h->specs.size(); ++i) {
+            const ConvSpec& s = h->specs[i];
+            if ((int)i == h->spec_stem || (int)i == h->spec_final) continue;
+            for (float v : s.w)
+                if (!esa::host_f16_finite(v))
+                    return fail("commit: weight %g of '%s' is not finite in fp16 (|w| must stay below 65520): precision 'fp16' cannot hold "
+                                "this network, use 'bf16'", (double)v, s.name.c_str());
+        }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail("commit: no HIP device visible — the MI355X kernels cannot run (no CPU fallback exists)");
@@ -1491,9 +1514,9 @@ int esahrnet_commit(esahrnet_handle h) {
         for (int co = 0; co < ct; ++co)
             for (int ci = 0; ci < c0; ++ci) w[(size_t)co * c0 + ci] = s0.w[(size_t)co * s0.cin + ci];
         if (upload(h->pack(w.data(), ct, c0, 1, ctp, c0p), &h->head_w0)) return 1;
-        if (h->bf()) {
+        if (h->h16()) {
             packed.assign(esa::head_w3_bf_bytes(s3.cout, ctp), 0);
-            esa::pack_head_w3_bf(s3.w.data(), s3.cout, ct, ctp, packed.data());
+            esa::pack_head_w3_bf(s3.w.data(), s3.cout, ct, ctp, packed.data(), h->hf());
             if (upload(packed, &h->head_w3)) return 1;
         } else if (h->x6()) {      // head_x6.hip: W3 in conv_x6's three-term fragments (its K order is the h0 fragment's)
             const int m3p = s3.cout <= 16 ? 16 : 32;
@@ -1635,7 +1658,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             esa::StemParams p{static_cast<const float*>(b.x), T(o.out), c.stem_w, c.stem_b,
                               n, height, width, c.cfg.cin, c.tensors[o.out].Cp, 1, c.opt.fmt};
             if (desc) {
-                describe(desc, "stem_kernel", "%s", s.name.c_str());
+                describe(desc, c.hf() ? "stem_kernel<fp16>" : "stem_kernel", "%s", s.name.c_str());
                 desc->flops = 2.0 * n * height * width * s.cout * s.cin * 9;
                 desc->bytes = (double)n * height * width * s.cin * 4 + tbytes(o.out);
             } else rc = esa::launch_stem(p, stream);
@@ -1815,7 +1838,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 if (c.x6() && s.k == 1 && esa::conv1x1_x6_jobs_supported(ps, g.n)) snprintf(kernel, sizeof kernel, "conv1x1_x6_jobs_kernel");
                 else if (c.x6()) snprintf(kernel, sizeof kernel, "conv_x6_jobs_kernel<%d, %d>", s.k, s.stride);
                 else if (s.k == 1) snprintf(kernel, sizeof kernel, "conv1x1_jobs_kernel");
-                else snprintf(kernel, sizeof kernel, "conv_s2c32_jobs_kernel<%d, %d, %s>", s.stride, s.stride == 1 ? 8 : 4, c.bf() ? "true" : "false");
+                else snprintf(kernel, sizeof kernel, "conv_s2c32_jobs_kernel<%d, %d, %s>", s.stride, s.stride == 1 ? 8 : 4, c.hf() ? "fp16" : c.h16() ? "true" : "false");
                 std::string lab;
                 for (int k = 0; k < g.n; ++k) {
                     const Op& ok = c.ops[g.op[k]];
@@ -1875,11 +1898,11 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 p.t[i] = T(o.terms[i]); p.th[i] = lh[tt.level]; p.tw[i] = lw[tt.level];
                 p.Ctp = tt.Cp;
             }
-            p.C0p = ti.Cp; p.C3p = to.Cp; p.K = c.cfg.num_keypoints; p.valu = c.opt.bf_head_valu;
+            p.C0p = ti.Cp; p.C3p = to.Cp; p.K = c.cfg.num_keypoints; p.valu = c.opt.bf_head_valu && !c.hf(); p.hf = c.hf();
             if (desc) {
                 const ConvSpec& s0 = c.specs[c.spec_l0];
                 const ConvSpec& s3 = c.specs[c.spec_l3];
-                describe(desc, o.kind == OP_HEAD ? "head_fused" : c.x6() ? "head_x6" : "head_fused_bf",
+                describe(desc, o.kind == OP_HEAD ? "head_fused" : c.x6() ? "head_x6" : c.hf() ? "head_fused_bf<fp16>" : "head_fused_bf",
                          "last_layer.0[:, 0:%d] + up + last_layer.3", c.head_c0);
                 desc->flops = 2.0 * n * lh[to.level] * lw[to.level] * ((double)s0.cout * c.head_c0 + (double)s3.cout * s3.cin);
                 desc->bytes = tbytes(o.in) + tbytes(o.out);
@@ -1950,7 +1973,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             p.y = T(o.out); p.N = n; p.H = lh[to.level]; p.W = lw[to.level]; p.Cp = to.Cp;
             p.relu = o.relu; p.fmt = c.opt.fmt;
             if (desc) {
-                describe(desc, "fuse_kernel", "fuse -> %s", to.tap.c_str());
+                describe(desc, c.hf() ? "fuse_kernel<fp16>" : "fuse_kernel", "fuse -> %s", to.tap.c_str());
                 desc->bytes = tbytes(o.out);
                 for (int i = 0; i < o.nterms; ++i) desc->bytes += tbytes(o.terms[i]);
             } else rc = esa::launch_fuse(p, stream);
@@ -1966,7 +1989,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             p.part = static_cast<float2*>(b.part);
             if (desc) {
                 const ConvSpec& s = c.specs[c.spec_final];
-                describe(desc, "final_kernel", "%s", s.name.c_str());
+                describe(desc, c.hf() ? "final_kernel<fp16>" : "final_kernel", "%s", s.name.c_str());
                 desc->flops = 2.0 * n * height * width * s.cout * s.cin * 9;
                 desc->bytes = tbytes(o.in) + (double)n * height * width * (c.cfg.cin + s.cout) * 4;
             } else if (b.kp && b.final2 && !c.final_wpk) {   // esahrnet_forward_keypoints_final2, VALU: the blurring output layer
@@ -2380,9 +2403,9 @@ int esahrnet_op_conv_ex(const void* x_dev, int n, int cin, int height, int width
                         const float* b, int cout, int k, int stride, int relu, const void* res_dev,
                         void* y_dev, int precision, esahrnet_stream stream_) {
     if (!x_dev || !w || !b || !y_dev) return fail("op_conv: null argument");
-    if (precision < 0 || precision > 2) return fail("op_conv: precision %d", precision);
-    const bool bf = precision == 1, x6 = precision == 2;
-    const int fmt = bf ? esa::FMT_BF : x6 ? esa::FMT_F32 : esa::FMT_SB;
+    if (precision < 0 || precision > 3) return fail("op_conv: precision %d", precision);
+    const bool hf = precision == 3, bf = precision == 1 || hf, x6 = precision == 2;       // bf: half-width format (bf16 or fp16)
+    const int fmt = hf ? esa::FMT_HF : bf ? esa::FMT_BF : x6 ? esa::FMT_F32 : esa::FMT_SB;
     const int eb = bf ? 2 : 4;
     if (!((k == 1 && stride == 1) || (k == 3 && (stride == 1 || stride == 2)))) return fail("op_conv: k=%d stride=%d unsupported", k, stride);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -2390,7 +2413,7 @@ int esahrnet_op_conv_ex(const void* x_dev, int n, int cin, int height, int width
     const int oh = stride == 2 ? (height + 1) / 2 : height, ow = stride == 2 ? (width + 1) / 2 : width;
     std::vector<char> packed(bf ? esa::packed_weight_bytes_bf(coutp, cinp, k) : x6 ? esa::packed_weight_bytes_x6(coutp, cinp, k)
                                                                                     : esa::packed_weight_bytes(coutp, cinp, k), 0);
-    if (bf) esa::pack_conv_weights_bf(w, cout, cin, k, coutp, cinp, packed.data());
+    if (bf) esa::pack_conv_weights_bf(w, cout, cin, k, coutp, cinp, packed.data(), hf);
     else if (x6) esa::pack_conv_weights_x6(w, cout, cin, k, coutp, cinp, packed.data());
     else esa::pack_conv_weights(w, cout, cin, k, coutp, cinp, packed.data());
     std::vector<float> bias(coutp, 0.f);
@@ -2428,9 +2451,9 @@ int esahrnet_op_fuse(const void* const* xs_dev, const int* hs, const int* ws, in
 int esahrnet_op_fuse_ex(const void* const* xs_dev, const int* hs, const int* ws, int nterms, int n, int c,
                         int height, int width, int relu, void* y_dev, int precision, esahrnet_stream stream_) {
     if (!xs_dev || !hs || !ws || !y_dev || nterms < 1 || nterms > 4) return fail("op_fuse: bad argument");
-    if (precision < 0 || precision > 2) return fail("op_fuse: precision %d", precision);
-    const bool bf = precision == 1;
-    const int fmt = bf ? esa::FMT_BF : precision == 2 ? esa::FMT_F32 : esa::FMT_SB;
+    if (precision < 0 || precision > 3) return fail("op_fuse: precision %d", precision);
+    const bool bf = precision == 1 || precision == 3;      // half-width format (bf16 or fp16)
+    const int fmt = precision == 3 ? esa::FMT_HF : bf ? esa::FMT_BF : precision == 2 ? esa::FMT_F32 : esa::FMT_SB;
     const int eb = bf ? 2 : 4;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int cp = bf ? pad64(c) : pad32(c);

@@ -181,3 +181,72 @@ __device__ __forceinline__ void unpack8_bf16(uint4 c, float v[8]) {
     unpack4_bf16(make_uint2(c.x, c.y), v);
     unpack4_bf16(make_uint2(c.z, c.w), v + 4);
 }
+
+// ---- "HF" = single fp16 NHWC (esahrnet_cfg.precision == 3) -------------------------------------------------------
+// The BF layout element for element (channels padded to 64, 2 bytes per channel, the same chunks, planes and fragment
+// order), every element an IEEE binary16 instead of a bf16: 11 significand bits for 8, at the matrix rate of bf16
+// (v_mfma_f32_16x16x32_f16).  The kernels that serve both take the element type as a template parameter EL; the
+// fragments travel as bf16x8 bit patterns in either case (a bit cast is free).
+constexpr int EL_SB = 0, EL_BF = 1, EL_HF = 3;       // split bf16 (hi, lo) / bf16 / fp16: the FMT_* codes of kernels.h
+__host__ __device__ __forceinline__ constexpr bool el_half(int el) { return el == EL_BF || el == EL_HF; }   // 2 bytes per channel
+
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+
+// one 16x16x32 product of the element type (A, B as bit patterns)
+template <int EL>
+__device__ __forceinline__ f32x4 mfma_el(bf16x8 a, bf16x8 b, f32x4 c) {
+    if constexpr (EL == EL_HF)
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
+// Two floats -> two fp16 in one dword, round to nearest even (v_cvt_pk_f16_f32 on gfx950 — NOT v_cvt_pkrtz_f16_f32,
+// which truncates), then SATURATED on the packed halves: |v| beyond 65504 — the conversion's +-inf — becomes +-65504
+// (v_pk_min_f16 / v_pk_max_f16, one VALU op each per pair).  An inf would meet a zero interpolation weight in the
+// next fuse (inf * 0 = NaN) and the decoder takes a NaN for the arg-max.  Subnormal results are kept.
+#ifndef ESA_HF_NOCLAMP
+#define ESA_HF_NOCLAMP 0      // timing experiment only: 1 compiles the saturation out.  0 in the product build.
+#endif
+__device__ __forceinline__ uint32_t pack2_f16(float a, float b) {
+    const f32x2 v = {a, b};
+    f16x2 h = __builtin_convertvector(v, f16x2);
+    const f16x2 top = {(_Float16)65504.f, (_Float16)65504.f};
+    if (!ESA_HF_NOCLAMP) h = __builtin_elementwise_max(__builtin_elementwise_min(h, top), -top);
+    return __builtin_bit_cast(uint32_t, h);
+}
+__device__ __forceinline__ uint2 pack4_f16(const float v[4]) { return make_uint2(pack2_f16(v[0], v[1]), pack2_f16(v[2], v[3])); }
+__device__ __forceinline__ void unpack4_f16(uint2 c, float v[4]) {       // exact
+    const f32x2 a = __builtin_convertvector(__builtin_bit_cast(f16x2, c.x), f32x2);
+    const f32x2 b = __builtin_convertvector(__builtin_bit_cast(f16x2, c.y), f32x2);
+    v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
+}
+__device__ __forceinline__ uint4 pack8_f16(const float v[8]) {
+    const uint2 a = pack4_f16(v), b = pack4_f16(v + 4);
+    return make_uint4(a.x, a.y, b.x, b.y);
+}
+__device__ __forceinline__ void unpack8_f16(uint4 c, float v[8]) {
+    unpack4_f16(make_uint2(c.x, c.y), v);
+    unpack4_f16(make_uint2(c.z, c.w), v + 4);
+}
+__device__ __forceinline__ float f16_bits_to_f32(uint32_t b) {
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)b);
+}
+
+// by element type (EL_BF or EL_HF)
+template <int EL> __device__ __forceinline__ uint2 pack4_el(const float v[4]) {
+    if constexpr (EL == EL_HF) return pack4_f16(v); else return pack4_bf16(v);
+}
+template <int EL> __device__ __forceinline__ void unpack4_el(uint2 c, float v[4]) {
+    if constexpr (EL == EL_HF) unpack4_f16(c, v); else unpack4_bf16(c, v);
+}
+template <int EL> __device__ __forceinline__ uint4 pack8_el(const float v[8]) {
+    if constexpr (EL == EL_HF) return pack8_f16(v); else return pack8_bf16(v);
+}
+template <int EL> __device__ __forceinline__ void unpack8_el(uint4 c, float v[8]) {
+    if constexpr (EL == EL_HF) unpack8_f16(c, v); else unpack8_bf16(c, v);
+}
+// bits of 1.0 in the low / high half of a dword
+template <int EL> __device__ __forceinline__ constexpr uint32_t one_lo_el() { return EL == EL_HF ? 0x00003c00u : 0x00003f80u; }
+template <int EL> __device__ __forceinline__ constexpr uint32_t one_hi_el() { return EL == EL_HF ? 0x3c000000u : 0x3f800000u; }

@@ -11,6 +11,8 @@
 namespace esa {
 namespace {
 
+// HF: y is an HF tensor (fp16 mode) — an instantiation of its own, so that the other formats' kernel stays as it is
+template <bool HF>
 __global__ __launch_bounds__(256) void stem_kernel(StemParams p, long long total) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* wsm = reinterpret_cast<float*>(smem);
@@ -56,6 +58,10 @@ __global__ __launch_bounds__(256) void stem_kernel(StemParams p, long long total
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] = relu1(acc[i]);
     }
+    if (HF) {       // f32 VALU result, rounded once to fp16 (nearest even, saturating: sb.h)
+        *reinterpret_cast<uint4*>(p.y + (((size_t)(n * p.H + y) * p.W + x) * p.cout) * 2 + c8 * 16) = pack8_f16(acc);
+        return;
+    }
     if (p.fmt == FMT_BF) {
         *reinterpret_cast<uint4*>(p.y + (((size_t)(n * p.H + y) * p.W + x) * p.cout) * 2 + c8 * 16) = pack8_bf16(acc);
         return;
@@ -82,7 +88,8 @@ constexpr int STEM_PX = 8;
 // pool_partial_kernel writes (cbam.hip), so that kernel's 537 MB read of the tensor just written is not needed.
 // BFQ (bf16 mode, stem1_pool_bf_kernel): the outputs are rounded to bf16 first, so that the partials are those of the
 // values the BF tensor holds — what pool_partial would compute from it.
-template <bool POOL, bool BFQ>
+// HF: y is an HF tensor (fp16 mode), see stem_kernel
+template <bool POOL, bool BFQ, bool HF = false>
 __device__ __forceinline__ void stem1_body(const StemParams& p, int xgroups, long long total, float* pool, float* psum, float* pmax) {
     const int G = p.cout >> 3;
     int c8, xg, y, n;
@@ -149,7 +156,9 @@ __device__ __forceinline__ void stem1_body(const StemParams& p, int xgroups, lon
 #pragma unroll
             for (int i = 0; i < 8; ++i) { ps[i] += acc[i]; pm[i] = fmaxf(pm[i], acc[i]); }
         }
-        if (p.fmt == FMT_BF) {
+        if (HF) {
+            *reinterpret_cast<uint4*>(p.y + (((size_t)(n * p.H + y) * p.W + x) * p.cout) * 2 + c8 * 16) = pack8_f16(acc);
+        } else if (p.fmt == FMT_BF) {
             *reinterpret_cast<uint4*>(p.y + (((size_t)(n * p.H + y) * p.W + x) * p.cout) * 2 + c8 * 16) = pack8_bf16(acc);
         } else if (p.fmt == FMT_F32) {
             float* o = reinterpret_cast<float*>(p.y) + ((size_t)(n * p.H + y) * p.W + x) * p.cout + c8 * 8;
@@ -182,6 +191,9 @@ __global__ __launch_bounds__(256) void stem1_kernel(StemParams p, int xgroups, l
     __shared__ float psum[POOL ? 256 * 8 : 1], pmax[POOL ? 256 * 8 : 1];
     stem1_body<POOL, false>(p, xgroups, total, pool, psum, pmax);
 }
+__global__ __launch_bounds__(256) void stem1_hf_kernel(StemParams p, int xgroups, long long total) {
+    stem1_body<false, false, true>(p, xgroups, total, nullptr, nullptr, nullptr);
+}
 __global__ __launch_bounds__(256) void stem1_pool_bf_kernel(StemParams p, int xgroups, float* pool) {
     __shared__ float psum[256 * 8], pmax[256 * 8];
     stem1_body<true, true>(p, xgroups, 0LL, pool, psum, pmax);
@@ -212,20 +224,22 @@ int launch_stem_pool(const StemParams& p, float* pool, hipStream_t stream) {
 }
 
 int launch_stem(const StemParams& p, hipStream_t stream) {
-    if ((p.cout & 31) || p.cin < 1 || p.cin > 4) return (int)hipErrorInvalidValue;
+    if ((p.cout & 31) || p.cin < 1 || p.cin > 4 || (p.fmt == FMT_HF && (p.cout & 63))) return (int)hipErrorInvalidValue;
     if (p.cin == 1) {
         const int xgroups = (p.W + STEM_PX - 1) / STEM_PX;
         const long long total1 = (long long)p.N * p.H * xgroups * (p.cout >> 3);
         const long long nblk1 = (total1 + 255) / 256;
         if (nblk1 <= 0 || nblk1 > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(stem1_kernel<false>, dim3((unsigned)nblk1), dim3(256), 0, stream, p, xgroups, total1, nullptr);
+        if (p.fmt == FMT_HF) hipLaunchKernelGGL(stem1_hf_kernel, dim3((unsigned)nblk1), dim3(256), 0, stream, p, xgroups, total1);
+        else hipLaunchKernelGGL(stem1_kernel<false>, dim3((unsigned)nblk1), dim3(256), 0, stream, p, xgroups, total1, nullptr);
         return (int)hipGetLastError();
     }
     const long long total = (long long)p.N * p.H * p.W * (p.cout >> 3);
     const long long nblk = (total + 255) / 256;
     if (nblk <= 0 || nblk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     const size_t lds = (size_t)(p.cout >> 3) * p.cin * 72 * sizeof(float);
-    hipLaunchKernelGGL(stem_kernel, dim3((unsigned)nblk), dim3(256), lds, stream, p, total);
+    if (p.fmt == FMT_HF) hipLaunchKernelGGL(stem_kernel<true>, dim3((unsigned)nblk), dim3(256), lds, stream, p, total);
+    else hipLaunchKernelGGL(stem_kernel<false>, dim3((unsigned)nblk), dim3(256), lds, stream, p, total);
     return (int)hipGetLastError();
 }
 

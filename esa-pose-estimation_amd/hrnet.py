@@ -35,7 +35,9 @@ BN_MOMENTUM = 0.01           # models/seg_hrnet.py:23 (irrelevant at inference, 
 
 # "fp32" is the fp32-grade bf16x6 mode (the reference's arithmetic class, BASELINE configs[1]); "bf16x3" (split-bf16,
 # ~16 significand bits) is an explicitly named opt-in and NOT an alias of fp32
-PRECISIONS = {"fp32": 2, "bf16x6": 2, "bf16x3": 0, "split-bf16": 0, "bf16": 1, 0: 0, 1: 1, 2: 2}
+# "fp16" is the single-pass mode with fp16 storage: bf16's cost, 11 significand bits, range +-65504 (saturating); seg_hrnet /
+# seg_hrnet2 only
+PRECISIONS = {"fp32": 2, "bf16x6": 2, "bf16x3": 0, "split-bf16": 0, "bf16": 1, "fp16": 3, 0: 0, 1: 1, 2: 2, 3: 3}
 
 
 def _cfg_struct(config, cin: int, num_keypoints: int, variant: int = 0, precision=0) -> _lib.Cfg:
@@ -102,7 +104,8 @@ class HighResolutionNet(nn.Module):
         self._cin, self._k = cin, k
         # precision (include/esahrnet.h esahrnet_cfg.precision): "fp32" = "bf16x6" (default: fp32-grade, BASELINE
         # configs[1] / [2]), "bf16x3" (split-bf16, ~16 significand bits: explicit opt-in, ~1.7x faster), "bf16"
-        # (single-pass bf16 storage / fp32 accumulate, BASELINE configs[3])
+        # (single-pass bf16 storage / fp32 accumulate, BASELINE configs[3]), "fp16" (the same with fp16 storage, seg_hrnet /
+        # seg_hrnet2 only: seg_hrnet3 raises the library's message)
         self._cfg_struct = _cfg_struct(config, cin, k, int(kwargs.pop("variant", self.VARIANT)),
                                        kwargs.pop("precision", self.DEFAULT_PRECISION))
         object.__setattr__(self, "_rt", _Runtime(self._cfg_struct))

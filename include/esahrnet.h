@@ -63,7 +63,14 @@ typedef struct esahrnet_cfg {
                                        product), f32 accumulate, f32 folded-BN bias epilogue — configs[3]
                                        (heatmap L_inf ~1e-2); both variants (variant 1: CBAM statistics, MLP,
                                        maps and sigmoids in f32 from the stored bf16 values, its output rounded
-                                       once; the heat-maps leave the output layer in f32)                      */
+                                       once; the heat-maps leave the output layer in f32);
+                                    3: "fp16" — the plan, layout and cost of mode 1 with IEEE binary16 elements (11
+                                       significand bits for 8, v_mfma_f32_16x16x32_f16): activations and weights stored
+                                       once as fp16, rounded to nearest even, stores SATURATED at +-65504 (never inf),
+                                       f32 accumulate and bias, f32 heat-maps; heatmap L_inf ~7e-4, nine times closer to
+                                       the reference than mode 1 inside fp16's range; variant 0 only (esahrnet_create
+                                       refuses variant 1); esahrnet_commit refuses a folded weight that is not finite in
+                                       fp16.  A value of this field, not a new field or symbol: the ABI version stays */
 } esahrnet_cfg;
 
 /* A parameter tensor that is not a convolution of the main graph (variant 1: the CBAM weights). */
@@ -280,7 +287,7 @@ int esahrnet_op_conv(const void* x_dev, int n, int cin, int height, int width,
 int esahrnet_op_fuse(const void* const* xs_dev, const int* hs, const int* ws, int nterms,
                      int n, int c, int height, int width, int relu, void* y_dev,
                      esahrnet_stream stream);
-/* The same two operators in the arithmetic of esahrnet_cfg.precision (0: split-bf16, 1: single bf16, 2: bf16x6): inputs are
+/* The same two operators in the arithmetic of esahrnet_cfg.precision (0: split-bf16, 1: single bf16, 2: bf16x6, 3: fp16): inputs are
  * converted to the internal format, the kernel of that mode runs, the result is converted back to f32. */
 int esahrnet_op_conv_ex(const void* x_dev, int n, int cin, int height, int width,
                         const float* w, const float* b, int cout, int k, int stride, int relu,
