@@ -88,6 +88,21 @@ _SIGS = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "esahrnet_pnp_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "esahrnet_keypoints_final2_hess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_size_t, C.c_void_p]),
+    "esahrnet_forward_keypoints_final2_hess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "esahrnet_correspondences": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esahrnet_frames_correspondences_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                                  C.POINTER(C.c_size_t)]),
+    "esahrnet_frames_correspondences": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                  C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_double,
+                                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p]),
+    "esahrnet_pnp_batch_w": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_void_p, C.c_void_p]),
     "esahrnet_flops_per_crop": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "esahrnet_launch_count": (C.c_int, [C.c_void_p]),
     "esahrnet_op_desc_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OpDesc)]),
@@ -140,6 +155,18 @@ def lib():
         raise EsaHrnetError("libesahrnet.so ABI version mismatch — rebuild it")
     _lib = l
     return l
+
+
+def load_other(path: str):
+    """Another build of the library (a measurement against an older libesahrnet.so), bound like lib() with the entries it has.
+    For hrnet._Runtime.use_library only; errors of calls through it are read from it, not from lib()."""
+    import torch  # noqa: F401
+    other = C.CDLL(os.path.abspath(path))
+    for name, (res, args) in _SIGS.items():
+        if hasattr(other, name):
+            fn = getattr(other, name)
+            fn.restype, fn.argtypes = res, args
+    return other
 
 
 def check(rc: int):

@@ -125,9 +125,10 @@ __device__ __forceinline__ double blur_at(Plane pl, int H, int W, int y, int x) 
     return blur_taps([&](int r) { return row(r); });
 }
 
-template <class Src>
+// HESS: also hess[plane] = (dxx, dxy, dyy) (refine.h final2_finish); the false instantiation never reads `hess`
+template <class Src, bool HESS>
 __global__ __launch_bounds__(64) void final2_finish_kernel(Src src, const float2* part, const float* bmax, int ntiles, int H,
-                                                           int W, float* kp, int* idx_out) {
+                                                           int W, float* kp, int* idx_out, double* hess) {
 #pragma clang fp contract(off)
     const int plane = blockIdx.x;
     float bv;
@@ -140,14 +141,18 @@ __global__ __launch_bounds__(64) void final2_finish_kernel(Src src, const float2
     if (bi == 0x7fffffff) bi = 0;                          // all -inf plane
     const int px = bi % W, py = bi / W;
     const auto pl = src.plane(plane, H, W);
-    final2_finish(
+    final2_finish<HESS>(
         bv, bi, bm, H, W,
         [&](int j) { return (float)blur_at(pl, H, W, py + final2_point_dy(j), px + final2_point_dx(j)); },
-        [&] { return pl[bi]; }, kp, idx_out, plane);
+        [&] { return pl[bi]; }, kp, idx_out, plane, hess);
 }
 
-template <class Src>
-int launch_final2(Src src, int planes, int H, int W, float* kp, int* idx_out, void* ws, size_t ws_bytes, hipStream_t stream) {
+// HESS: the finish also writes hess f64 [planes][3] (not null).  A template flag, so that a file which never asks for the
+// Hessian instantiates the two kernels it always had.
+template <class Src, bool HESS = false>
+int launch_final2(Src src, int planes, int H, int W, float* kp, int* idx_out, void* ws, size_t ws_bytes, hipStream_t stream,
+                  double* hess = nullptr) {
+    if (HESS != (hess != nullptr)) return (int)hipErrorInvalidValue;
     if (planes <= 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     const int ntiles = final2_tiles(H, W);
     if ((long long)planes * ntiles > 0x7fffffLL || ws_bytes < final2_workspace_bytes(planes, H, W) ||
@@ -160,8 +165,8 @@ int launch_final2(Src src, int planes, int H, int W, float* kp, int* idx_out, vo
                        ntiles, part, bmax);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(final2_finish_kernel<Src>, dim3((unsigned)planes), dim3(64), 0, stream, src, part, bmax, ntiles, H, W, kp,
-                       idx_out);
+    hipLaunchKernelGGL((final2_finish_kernel<Src, HESS>), dim3((unsigned)planes), dim3(64), 0, stream, src, part, bmax, ntiles, H,
+                       W, kp, idx_out, hess);
     return (int)hipGetLastError();
 }
 

@@ -431,8 +431,9 @@ __global__ __launch_bounds__(256) void final2_valu_kernel(FinalParams p, int til
     }
 }
 
+template <bool HESS>
 __global__ __launch_bounds__(64) void final2_valu_finish_kernel(FinalParams p, int kt, int ntiles, const float* bmax, float* kp,
-                                                                int* idx_out) {
+                                                                int* idx_out, double* hess) {
     constexpr int R = 15, S = R + 2;
     __shared__ float stg[8 * S * S];
     __shared__ float win[R * R];
@@ -474,13 +475,13 @@ __global__ __launch_bounds__(64) void final2_valu_finish_kernel(FinalParams p, i
         if (q < R * R) win[q] = gy >= 0 && gy < p.H && gx >= 0 && gx < p.W ? acc[j] : 0.f;
     }
     __syncthreads();
-    final2_finish(
+    final2_finish<HESS>(
         bv, bi, bm, p.H, p.W,
         [&](int j) {
             const int cy = R / 2 + final2_point_dy(j), cx = R / 2 + final2_point_dx(j);
             return (float)blur_taps([&](int r) { return blur_taps([&](int t) { return win[(cy - 5 + r) * R + cx - 5 + t]; }); });
         },
-        [&] { return win[(R / 2) * R + R / 2]; }, kp, idx_out, plane);
+        [&] { return win[(R / 2) * R + R / 2]; }, kp, idx_out, plane, hess);
 }
 
 
@@ -793,7 +794,7 @@ int final2_valu_tiles(int H, int W) {
     return ((H + F2V_T - 1) / F2V_T) * ((W + F2V_T - 1) / F2V_T);
 }
 
-int launch_final2_kp(const FinalParams& p, float* bmax, float* kp, int* idx_out, hipStream_t stream) {
+int launch_final2_kp(const FinalParams& p, float* bmax, float* kp, int* idx_out, hipStream_t stream, double* hess) {
     const int ntiles = final2_valu_tiles(p.H, p.W), kt = final_kt(p.K);
     const long long planes = (long long)p.N * p.K, nblk = (long long)p.N * ntiles;
     if (!p.part || !bmax || !kp || ntiles <= 0 || kt < 0 || p.cin < 0 || p.cin > 8 || planes > 0x7fffffffLL ||
@@ -807,7 +808,12 @@ int launch_final2_kp(const FinalParams& p, float* bmax, float* kp, int* idx_out,
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(final2_valu_finish_kernel, dim3((unsigned)planes), dim3(64), 0, stream, p, kt, ntiles, bmax, kp, idx_out);
+    if (hess)
+        hipLaunchKernelGGL(final2_valu_finish_kernel<true>, dim3((unsigned)planes), dim3(64), 0, stream, p, kt, ntiles, bmax, kp,
+                           idx_out, hess);
+    else
+        hipLaunchKernelGGL(final2_valu_finish_kernel<false>, dim3((unsigned)planes), dim3(64), 0, stream, p, kt, ntiles, bmax, kp,
+                           idx_out, hess);
     return (int)hipGetLastError();
 }
 

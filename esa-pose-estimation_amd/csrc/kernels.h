@@ -175,7 +175,8 @@ int launch_final_kp(const FinalParams& p, float* kp, int* idx_out, hipStream_t s
 // bit-identical to launch_final (VALU) + launch_keypoints_final2; p.part and bmax: [N*K][final2_valu_tiles] records, p.out
 // not used; cin <= 8
 int final2_valu_tiles(int H, int W);
-int launch_final2_kp(const FinalParams& p, float* bmax, float* kp, int* idx_out, hipStream_t stream);
+// hess (may be null): f64 [N*K][3] = (dxx, dxy, dyy), the Hessian each step used, NaN x 3 where no step is taken
+int launch_final2_kp(const FinalParams& p, float* bmax, float* kp, int* idx_out, hipStream_t stream, double* hess = nullptr);
 // tiles per heat-map the MFMA output-layer kernel reports partial maxima for; 0: that kernel does not serve (K, cin)
 int final_part_tiles(int K, int cin, int H, int W);
 // (v, i) beats (bv, bi) if it is larger — NaN counting as larger than every number — or equal with a lower index
@@ -323,11 +324,18 @@ int launch_keypoints_finish_nhwc(int fmt, const char* x, int N, int C, int H, in
 // maxima of the raw and of the blurred planes; the blurred planes themselves are never stored).
 int final2_tiles(int H, int W);
 size_t final2_workspace_bytes(long long planes, int H, int W);
+// hess (may be null): f64 [planes][3] = (dxx, dxy, dyy) of the blurred log heat-map, the values the step uses; NaN x 3 where no
+// step is taken.  A template flag of the finish: with hess == nullptr the kernels launched are the ones without it.
 int launch_keypoints_final2(const float* heat, int planes, int H, int W, float* kp, int* idx_out, void* ws, size_t ws_bytes,
-                            hipStream_t stream);
+                            hipStream_t stream, double* hess = nullptr);
 // the same decoder on NHWC heat-maps x [N][H][W][Cp] (fmt FMT_SB or FMT_F32) that were never converted to NCHW: seg_hrnet3
 // under esahrnet_forward_keypoints_final2; planes = N * C, ws as above
 int launch_keypoints_final2_nhwc(int fmt, const char* x, int N, int C, int H, int W, int Cp, float* kp, int* idx_out, void* ws,
+                                 size_t ws_bytes, hipStream_t stream, double* hess = nullptr);
+
+// launch_keypoints_final2 with hess (not null), keypoints_final2_hess.hip: the same tile pass, the finish instantiated with
+// the Hessian output
+int launch_keypoints_final2_hess(const float* heat, int planes, int H, int W, float* kp, int* idx_out, double* hess, void* ws,
                                  size_t ws_bytes, hipStream_t stream);
 
 // ---- crop + edge-pad + 8-bit bilinear resize + normalise: u8 frames -> f32 [N][1][S][S] (crops.hip) ----
@@ -347,6 +355,12 @@ int launch_crops_ex(const unsigned char* frames, int nframes, int FH, int FW, in
                     const int* valid, float* out, int m, int S, float mean, float std_, hipStream_t s);
 // kp f32 [m][K][3] -> NaN and idx int32 [m][K] (may be null) -> -1 in the rows with valid[i] == 0
 int launch_mark_invalid(const int* valid, int m, int K, float* kp, int* idx, hipStream_t s);
+
+// ---- keypoints -> the record the pose solver consumes (correspond.hip, correspond.h) ----------------------------------
+// kp f32 [m][K][3], hess f64 [m][K][3] (mode 1; may be null in mode 0), crop / rates / valid as launch_boxes wrote them ->
+// count int32 [m], order int32 [m][K], pts f64 [m][K][2], w f64 [m][K][3].  K <= 32 (one wave per crop).
+int launch_correspond(const float* kp, const double* hess, const int* crop, const double* rates, const int* valid, int m, int K,
+                      double thresh, int min_k, int mode, int* count, int* order, double* pts, double* w, hipStream_t s);
 
 // ---- layout conversion f32 NCHW <-> SB (layout.hip) ----------------------------------------
 int launch_nchw_to_sb(const float* x, int N, int C, int H, int W, char* y, int Cp, hipStream_t s);

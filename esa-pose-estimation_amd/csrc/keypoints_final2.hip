@@ -15,6 +15,7 @@
 // layout.hip for seg_hrnet3's NHWC heat-maps.
 // Numerics (refine.h final2_newton): the restatement in tests/final2_ref.py.  No fma anywhere in this file: the host
 // restatement sums in plain IEEE f64.
+// With the Hessian as a third output the finish is another instantiation: keypoints_final2_hess.hip.
 #include "final2.h"
 
 namespace esa {
@@ -27,7 +28,8 @@ size_t final2_workspace_bytes(long long planes, int H, int W) {
 }
 
 int launch_keypoints_final2(const float* heat, int planes, int H, int W, float* kp, int* idx_out, void* ws, size_t ws_bytes,
-                            hipStream_t stream) {
+                            hipStream_t stream, double* hess) {
+    if (hess) return launch_keypoints_final2_hess(heat, planes, H, W, kp, idx_out, hess, ws, ws_bytes, stream);
     return launch_final2(F2Nchw{heat}, planes, H, W, kp, idx_out, ws, ws_bytes, stream);
 }
 

@@ -192,10 +192,15 @@ int launch_to_nchw_part(int fmt, const char* x, int N, int C, int H, int W, int 
 
 // get_final2 straight from seg_hrnet3's NHWC heat-maps (final2.h's kernels with the NHWC plane accessor)
 int launch_keypoints_final2_nhwc(int fmt, const char* x, int N, int C, int H, int W, int Cp, float* kp, int* idx_out, void* ws,
-                                 size_t ws_bytes, hipStream_t stream) {
+                                 size_t ws_bytes, hipStream_t stream, double* hess) {
     if (N <= 0 || C < 1 || C > Cp || (Cp & 7) || (long long)N * C > 0x7fffffffLL || (fmt != FMT_SB && fmt != FMT_F32))
         return (int)hipErrorInvalidValue;
     const int planes = N * C;
+    if (hess) {
+        if (fmt == FMT_F32)
+            return launch_final2<F2Nhwc<true>, true>(F2Nhwc<true>{x, C, Cp}, planes, H, W, kp, idx_out, ws, ws_bytes, stream, hess);
+        return launch_final2<F2Nhwc<false>, true>(F2Nhwc<false>{x, C, Cp}, planes, H, W, kp, idx_out, ws, ws_bytes, stream, hess);
+    }
     if (fmt == FMT_F32) return launch_final2(F2Nhwc<true>{x, C, Cp}, planes, H, W, kp, idx_out, ws, ws_bytes, stream);
     return launch_final2(F2Nhwc<false>{x, C, Cp}, planes, H, W, kp, idx_out, ws, ws_bytes, stream);
 }

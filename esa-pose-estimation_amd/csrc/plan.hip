@@ -1590,6 +1590,8 @@ struct Buffers {
     bool final2 = false;
     float* kbmax = nullptr;
     size_t kws = 0;
+    // esahrnet_forward_keypoints_final2_hess: f64 [n * K][3], the Hessian each get_final2 step used (nullptr: not asked for)
+    double* hess = nullptr;
 };
 
 // What esahrnet_forward_keypoints keeps behind the forward's workspace (at ShapePlan::bytes, a multiple of 256): the per-tile
@@ -1754,7 +1756,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             if (desc) plain(f32 ? "f32_to_nchw" : "sb_to_nchw");
             else if (b.kp && b.final2)                  // esahrnet_forward_keypoints_final2: get_final2 on the NHWC maps
                 rc = esa::launch_keypoints_final2_nhwc(fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
-                                                       b.kp, b.idx, b.kpart, b.kws, stream);
+                                                       b.kp, b.idx, b.kpart, b.kws, stream, b.hess);
             else if (b.kp) {                            // esahrnet_forward_keypoints: maxima and refine on the NHWC maps
                 const int K = c.cfg.num_keypoints, Cp = c.tensors[o.in].Cp;
                 rc = esa::launch_tile_max(fmt, T(o.in), n, K, height, width, Cp, b.kpart, stream);
@@ -1995,12 +1997,13 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             } else if (b.kp && b.final2 && !c.final_wpk) {   // esahrnet_forward_keypoints_final2, VALU: the blurring output layer
                 p.out = nullptr;
                 p.part = b.kpart;
-                rc = esa::launch_final2_kp(p, b.kbmax, b.kp, b.idx, stream);
+                rc = esa::launch_final2_kp(p, b.kbmax, b.kp, b.idx, stream, b.hess);
             } else if (b.kp && b.final2) {              // ... matrix-core: heat-maps into the scratch, then get_final2 on them
                 p.out = b.kheat;
                 p.part = nullptr;
                 rc = esa::launch_final(p, stream);
-                if (!rc) rc = esa::launch_keypoints_final2(p.out, n * p.K, height, width, b.kp, b.idx, b.kpart, b.kws, stream);
+                if (!rc)
+                    rc = esa::launch_keypoints_final2(p.out, n * p.K, height, width, b.kp, b.idx, b.kpart, b.kws, stream, b.hess);
             } else if (b.kp && !c.final_wpk) {         // esahrnet_forward_keypoints, VALU output layer: no heat-maps at all
                 p.out = nullptr;
                 p.part = b.kpart;
@@ -2024,7 +2027,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
 static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, int width,
                        void* heat_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream_,
                        hipEvent_t* events, void* part_dev = nullptr, void* kp_dev = nullptr, void* idx_dev = nullptr,
-                       bool final2 = false) {
+                       bool final2 = false, void* hess_dev = nullptr) {
     if (!h || !x_dev || !(heat_dev || kp_dev) || !ws_dev) return fail("forward: null argument");
     if (!h->committed) return fail("forward: esahrnet_commit has not been called");
     if (plan_shape(*h, n, height, width)) return 1;
@@ -2042,6 +2045,7 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
         bufs.final2 = final2;
         bufs.kbmax = reinterpret_cast<float*>(bufs.ws + h->sp.bytes + ks.heat + ks.part);
         bufs.kws = ks.part;
+        bufs.hess = final2 ? static_cast<double*>(hess_dev) : nullptr;
     }
     int op_index = 0;
     if (events && hipEventRecord(events[0], stream) != hipSuccess) return fail("forward: hipEventRecord failed");
@@ -2175,6 +2179,13 @@ int esahrnet_forward_keypoints_final2(esahrnet_handle h, const void* x_dev, int 
     return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev, true);
 }
 
+int esahrnet_forward_keypoints_final2_hess(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* kp_dev,
+                                           void* idx_dev, void* hess_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
+    if (!h || !kp_dev) return fail("forward_keypoints_final2_hess: null argument");
+    return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev, true,
+                       hess_dev);
+}
+
 int esahrnet_keypoints_finish(const void* heat_dev, const void* part_dev, int ntiles, int n, int k, int height, int width,
                               void* kp_dev, void* idx_dev, esahrnet_stream stream) {
     if (!heat_dev || !part_dev || !kp_dev || n <= 0 || k <= 0 || ntiles <= 0) return fail("keypoints_finish: bad argument");
@@ -2205,6 +2216,11 @@ int esahrnet_keypoints_final2_workspace_bytes(int n, int k, int height, int widt
 
 int esahrnet_keypoints_final2(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev, void* ws_dev,
                               size_t ws_bytes, esahrnet_stream stream) {
+    return esahrnet_keypoints_final2_hess(heat_dev, n, k, height, width, kp_dev, idx_dev, nullptr, ws_dev, ws_bytes, stream);
+}
+
+int esahrnet_keypoints_final2_hess(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev,
+                                   void* hess_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
     if (!heat_dev || !kp_dev || !ws_dev) return fail("keypoints_final2: null argument");
     size_t need = 0;
     if (esahrnet_keypoints_final2_workspace_bytes(n, k, height, width, &need)) return 1;
@@ -2213,7 +2229,8 @@ int esahrnet_keypoints_final2(const void* heat_dev, int n, int k, int height, in
     if (ws_bytes < need) return fail("keypoints_final2: workspace too small (%zu < %zu)", ws_bytes, need);
     if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("keypoints_final2: workspace must be 256-byte aligned");
     const int rc = esa::launch_keypoints_final2(static_cast<const float*>(heat_dev), n * k, height, width, static_cast<float*>(kp_dev),
-                                                static_cast<int*>(idx_dev), ws_dev, ws_bytes, static_cast<hipStream_t>(stream));
+                                                static_cast<int*>(idx_dev), ws_dev, ws_bytes, static_cast<hipStream_t>(stream),
+                                                static_cast<double*>(hess_dev));
     if (rc) return fail("keypoints_final2: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return 0;
 }
@@ -2296,6 +2313,31 @@ int esahrnet_frames_keypoints_workspace_bytes(esahrnet_handle h, int m, int scal
     return 0;
 }
 
+// esahrnet_frames_keypoints / esahrnet_frames_correspondences after their argument checks (`who` names the caller in the
+// messages): boxes -> crops -> forward + decoder -> NaN rows for invalid crops.  hess_dev: decoder 1 only, may be null.
+static int frames_run(const char* who, esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                      int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale, int rule, float mean,
+                      float stdv, int decoder, void* kp_dev, void* idx_dev, void* hess_dev, void* crop_boxes_dev, void* rates_dev,
+                      void* valid_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc = esa::launch_boxes(static_cast<const int*>(det_boxes_dev), static_cast<const int*>(frame_idx_dev), nframes, m, frame_h,
+                               frame_w, scale, rule, static_cast<int*>(crop_boxes_dev), static_cast<double*>(rates_dev),
+                               static_cast<int*>(valid_dev), st);
+    if (!rc)
+        rc = esa::launch_crops_ex(static_cast<const unsigned char*>(frames_dev), nframes, frame_h, frame_w, pixel_format,
+                                  static_cast<const int*>(frame_idx_dev), static_cast<const int*>(crop_boxes_dev),
+                                  static_cast<const int*>(valid_dev), static_cast<float*>(ws_dev), m, scale, mean, stdv, st);
+    if (rc) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+    const size_t head = frontend_crop_bytes(m, scale);
+    if (run_forward(h, ws_dev, m, scale, scale, nullptr, static_cast<char*>(ws_dev) + head, ws_bytes - head, stream, nullptr, nullptr,
+                    kp_dev, idx_dev, decoder == 1, hess_dev))
+        return 1;
+    rc = esa::launch_mark_invalid(static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints, static_cast<float*>(kp_dev),
+                                  static_cast<int*>(idx_dev), st);
+    if (rc) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
 int esahrnet_frames_keypoints(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w, int pixel_format,
                               const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale, int rule, float mean,
                               float stdv, int decoder, void* kp_dev, void* idx_dev, void* crop_boxes_dev, void* rates_dev,
@@ -2313,22 +2355,82 @@ int esahrnet_frames_keypoints(esahrnet_handle h, const void* frames_dev, int nfr
     if (esahrnet_frames_keypoints_workspace_bytes(h, m, scale, decoder, &need)) return 1;
     if (ws_bytes < need) return fail("frames_keypoints: workspace too small (%zu < %zu)", ws_bytes, need);
     if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("frames_keypoints: workspace must be 256-byte aligned");
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc = esa::launch_boxes(static_cast<const int*>(det_boxes_dev), static_cast<const int*>(frame_idx_dev), nframes, m, frame_h,
-                               frame_w, scale, rule, static_cast<int*>(crop_boxes_dev), static_cast<double*>(rates_dev),
-                               static_cast<int*>(valid_dev), st);
-    if (!rc)
-        rc = esa::launch_crops_ex(static_cast<const unsigned char*>(frames_dev), nframes, frame_h, frame_w, pixel_format,
-                                  static_cast<const int*>(frame_idx_dev), static_cast<const int*>(crop_boxes_dev),
-                                  static_cast<const int*>(valid_dev), static_cast<float*>(ws_dev), m, scale, mean, stdv, st);
-    if (rc) return fail("frames_keypoints: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    const size_t head = frontend_crop_bytes(m, scale);
-    if (run_forward(h, ws_dev, m, scale, scale, nullptr, static_cast<char*>(ws_dev) + head, ws_bytes - head, stream, nullptr, nullptr,
-                    kp_dev, idx_dev, decoder == 1))
+    return frames_run("frames_keypoints", h, frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m,
+                      scale, rule, mean, stdv, decoder, kp_dev, idx_dev, nullptr, crop_boxes_dev, rates_dev, valid_dev, ws_dev,
+                      ws_bytes, stream);
+}
+
+// ---- keypoints -> correspondences for the pose solver (correspond.hip) --------------------------------------------------
+static int check_corr_args(const char* who, int m, int k, int mode) {
+    if (m <= 0) return fail("%s: the number of crops must be positive (got %d)", who, m);
+    if (k < 1 || k > 32) return fail("%s: %d keypoints per crop unsupported (1..32: one wave per crop)", who, k);
+    if (mode != 0 && mode != 1) return fail("%s: mode=%d unknown (0: peak weights, 1: get_final2 Hessian weights)", who, mode);
+    return 0;
+}
+
+int esahrnet_correspondences(const void* kp_dev, const void* hess_dev, const void* crop_boxes_dev, const void* rates_dev,
+                             const void* valid_dev, int m, int k, double thresh, int min_k, int mode, void* count_dev,
+                             void* order_dev, void* pts_dev, void* w_dev, esahrnet_stream stream) {
+    if (!kp_dev || !crop_boxes_dev || !rates_dev || !valid_dev || !count_dev || !order_dev || !pts_dev || !w_dev)
+        return fail("correspondences: null argument");
+    if (check_corr_args("correspondences", m, k, mode)) return 1;
+    if (mode == 1 && !hess_dev) return fail("correspondences: mode 1 (Hessian weights) needs hess_dev (esahrnet_keypoints_final2_hess)");
+    const int rc = esa::launch_correspond(static_cast<const float*>(kp_dev), static_cast<const double*>(hess_dev),
+                                          static_cast<const int*>(crop_boxes_dev), static_cast<const double*>(rates_dev),
+                                          static_cast<const int*>(valid_dev), m, k, thresh, min_k, mode, static_cast<int*>(count_dev),
+                                          static_cast<int*>(order_dev), static_cast<double*>(pts_dev), static_cast<double*>(w_dev),
+                                          static_cast<hipStream_t>(stream));
+    if (rc) return fail("correspondences: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
+static size_t frontend_hess_bytes(int m, int k) { return ((size_t)m * k * 3 * sizeof(double) + 255) & ~(size_t)255; }
+
+int esahrnet_frames_correspondences_workspace_bytes(esahrnet_handle h, int m, int scale, int decoder, int mode, size_t* bytes) {
+    if (!h || !bytes) return fail("frames_correspondences_workspace_bytes: null argument");
+    if (check_corr_args("frames_correspondences", m, h->cfg.num_keypoints, mode)) return 1;
+    if (mode == 1 && decoder == 0)
+        return fail("frames_correspondences: mode 1 (Hessian weights) needs decoder 1: get_final (decoder 0) computes no Hessian");
+    size_t fk = 0;
+    if (esahrnet_frames_keypoints_workspace_bytes(h, m, scale, decoder, &fk)) return 1;
+    *bytes = ((fk + 255) & ~(size_t)255) + (mode == 1 ? frontend_hess_bytes(m, h->cfg.num_keypoints) : 0);
+    return 0;
+}
+
+int esahrnet_frames_correspondences(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                                    int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale,
+                                    int rule, float mean, float stdv, int decoder, double thresh, int min_k, int mode, void* kp_dev,
+                                    void* idx_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev, void* count_dev,
+                                    void* order_dev, void* pts_dev, void* w_dev, void* ws_dev, size_t ws_bytes,
+                                    esahrnet_stream stream) {
+    if (!h || !frames_dev || !det_boxes_dev || !kp_dev || !crop_boxes_dev || !rates_dev || !valid_dev || !count_dev || !order_dev ||
+        !pts_dev || !w_dev || !ws_dev)
+        return fail("frames_correspondences: null argument");
+    // everything that can be refused is refused here, before the first launch
+    if (check_boxes_args("frames_correspondences", m, frame_h, frame_w, scale, rule) ||
+        check_crops_args("frames_correspondences", nframes, pixel_format, stdv))
         return 1;
-    rc = esa::launch_mark_invalid(static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints, static_cast<float*>(kp_dev),
-                                  static_cast<int*>(idx_dev), st);
-    if (rc) return fail("frames_keypoints: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (!frame_idx_dev && m != nframes)
+        return fail("frames_correspondences: %d boxes on %d frames need a frame index (NULL is the identity: box i lies on frame i)", m,
+                    nframes);
+    if (!h->committed) return fail("frames_correspondences: esahrnet_commit has not been called");
+    size_t need = 0, fk = 0;
+    if (esahrnet_frames_correspondences_workspace_bytes(h, m, scale, decoder, mode, &need) ||
+        esahrnet_frames_keypoints_workspace_bytes(h, m, scale, decoder, &fk))
+        return 1;
+    if (ws_bytes < need) return fail("frames_correspondences: workspace too small (%zu < %zu)", ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("frames_correspondences: workspace must be 256-byte aligned");
+    const size_t fk_al = (fk + 255) & ~(size_t)255;
+    void* hess = mode == 1 ? static_cast<char*>(ws_dev) + fk_al : nullptr;
+    if (frames_run("frames_correspondences", h, frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m,
+                   scale, rule, mean, stdv, decoder, kp_dev, idx_dev, hess, crop_boxes_dev, rates_dev, valid_dev, ws_dev, fk_al, stream))
+        return 1;
+    const int rc = esa::launch_correspond(static_cast<const float*>(kp_dev), static_cast<const double*>(hess),
+                                          static_cast<const int*>(crop_boxes_dev), static_cast<const double*>(rates_dev),
+                                          static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints, thresh, min_k, mode,
+                                          static_cast<int*>(count_dev), static_cast<int*>(order_dev), static_cast<double*>(pts_dev),
+                                          static_cast<double*>(w_dev), static_cast<hipStream_t>(stream));
+    if (rc) return fail("frames_correspondences: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return 0;
 }
 

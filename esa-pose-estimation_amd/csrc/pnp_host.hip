@@ -3,7 +3,9 @@
 // Replaces (reference): pnp.py:46-90 (cv2.solvePnPRansac, SOLVEPNP_EPNP, reprojectionError 5 px, + Rodrigues),
 // cpnp.cpnp_m (val.py:194-209; Ceres refinement with peak-weighted residuals, model:
 // lib/utils/extend_utils/src/uncertainty_pnp.cpp:7-92), the top-k selection and crop -> image mapping of
-// val.py:172-180 and the [w,x,y,z] quaternion of val.py:221-224 — for a whole batch of keypoint rows.
+// val.py:172-180 (correspond.h: the statement of it shared with the device stage, correspond.hip) and the [w,x,y,z]
+// quaternion of val.py:221-224 — for a whole batch of keypoint rows (esahrnet_pnp_batch), or of correspondence records
+// that the device stage already selected, back-projected and weighted (esahrnet_pnp_batch_w).
 //
 // It is a line-by-line native restatement of esa-pose-estimation_amd/pnp.py (which is the oracle for it:
 // tests/test_pnp_native.py compares poses and inlier sets); like that module it restates the PUBLISHED
@@ -20,6 +22,7 @@
 #include <vector>
 
 #include "../../include/esahrnet.h"
+#include "correspond.h"
 #include "kernels.h"
 
 namespace {
@@ -482,6 +485,8 @@ bool ransac(const double* p3d, const double* p2d, int n, const Cam& K, Mat3 R, d
 }
 
 // ---- weighted LM refinement (pnp.py: cpnp_m) ------------------------------------------------------------------
+// wts [n][3] = (wxx, wxy, wyy), the symmetric 2x2 weight of uncertainty_pnp.cpp:30-31: r = [wxx dx + wxy dy, wxy dx + wyy dy];
+// the scalar weight of val.py:194-209 is (peak, 0, peak), whose zero terms change no value
 void cpnp(const double* p3d, const double* p2d, const double* wts, int n, const Cam& K, double x[6]) {
     std::vector<double> r(2 * n), rn(2 * n), J(2 * n * 6);
     auto residual = [&](const double* xx, std::vector<double>& out, Mat3 R) {
@@ -489,8 +494,9 @@ void cpnp(const double* p3d, const double* p2d, const double* wts, int n, const 
         for (int i = 0; i < n; ++i) {
             double p[2];
             project1(p3d + i * 3, R, xx + 3, K, p);
-            out[2 * i] = wts[i] * (p[0] - p2d[i * 2]);
-            out[2 * i + 1] = wts[i] * (p[1] - p2d[i * 2 + 1]);
+            const double dx = p[0] - p2d[i * 2], dy = p[1] - p2d[i * 2 + 1];
+            out[2 * i] = wts[i * 3] * dx + wts[i * 3 + 1] * dy;
+            out[2 * i + 1] = wts[i * 3 + 1] * dx + wts[i * 3 + 2] * dy;
         }
     };
     auto sq = [&](const std::vector<double>& v) { double s = 0.0; for (double e : v) s += e * e; return s; };
@@ -507,11 +513,14 @@ void cpnp(const double* p3d, const double* p2d, const double* wts, int n, const 
             const double X = pc[0], Y = pc[1], Z = pc[2];
             const double dpx[3] = {K.fx / Z, 0.0, -K.fx * X / (Z * Z)}, dpy[3] = {0.0, K.fy / Z, -K.fy * Y / (Z * Z)};
             const double S[3][3] = {{0, rp[2], -rp[1]}, {-rp[2], 0, rp[0]}, {rp[1], -rp[0], 0}};      // -[rp]x
+            const double wxx = wts[i * 3], wxy = wts[i * 3 + 1], wyy = wts[i * 3 + 2];
             for (int c = 0; c < 3; ++c) {
-                J[(2 * i) * 6 + c] = wts[i] * (dpx[0] * S[0][c] + dpx[1] * S[1][c] + dpx[2] * S[2][c]);
-                J[(2 * i + 1) * 6 + c] = wts[i] * (dpy[0] * S[0][c] + dpy[1] * S[1][c] + dpy[2] * S[2][c]);
-                J[(2 * i) * 6 + 3 + c] = wts[i] * dpx[c];
-                J[(2 * i + 1) * 6 + 3 + c] = wts[i] * dpy[c];
+                const double jx = dpx[0] * S[0][c] + dpx[1] * S[1][c] + dpx[2] * S[2][c];
+                const double jy = dpy[0] * S[0][c] + dpy[1] * S[1][c] + dpy[2] * S[2][c];
+                J[(2 * i) * 6 + c] = wxx * jx + wxy * jy;
+                J[(2 * i + 1) * 6 + c] = wxy * jx + wyy * jy;
+                J[(2 * i) * 6 + 3 + c] = wxx * dpx[c] + wxy * dpy[c];
+                J[(2 * i + 1) * 6 + 3 + c] = wxy * dpx[c] + wyy * dpy[c];
             }
         }
         double H[36], gvec[6];
@@ -556,37 +565,53 @@ void cpnp(const double* p3d, const double* p2d, const double* wts, int n, const 
     }
 }
 
-// ---- one image: val.py:172-224 --------------------------------------------------------------------------------
-void pose_one(const float* kp, int k, const double* kp3d, const Cam& K, double x0, double y0, double rate, double thresh,
-              int min_k, double q[4], double t[3]) {
-    // top-k by peak (heapq.nlargest: descending, ties keep index order)
-    int large = 0;
-    for (int i = 0; i < k; ++i) large += (double)kp[i * 3 + 2] > thresh;
-    large = std::min(k, std::max(large, min_k));
-    std::vector<int> order(k);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return kp[a * 3 + 2] > kp[b * 3 + 2]; });
-    std::vector<double> p3(3 * large), p2(2 * large), wv(large);
-    const double inv = 1.0 / rate;
-    for (int i = 0; i < large; ++i) {
-        const int j = order[i];
-        for (int d = 0; d < 3; ++d) p3[i * 3 + d] = kp3d[j * 3 + d];
-        p2[i * 2 + 0] = (double)kp[j * 3 + 0] * inv + x0;
-        p2[i * 2 + 1] = (double)kp[j * 3 + 1] * inv + y0;
-        wv[i] = (double)kp[j * 3 + 2];
-    }
+// ---- one image: val.py:194-224 on n correspondences (model points, image pixels, 2x2 weights) --------------------------
+void pose_solve(const double* p3, const double* p2, const double* w3, int n, const Cam& K, double q[4], double t[3]) {
     Mat3 R;
     double tt[3], cam[6];
-    if (large < 4 || !ransac(p3.data(), p2.data(), large, K, R, tt, nullptr)) {
+    if (n < 4 || !ransac(p3, p2, n, K, R, tt, nullptr)) {
         q[0] = q[1] = q[2] = q[3] = t[0] = t[1] = t[2] = NAN;
         return;
     }
     rodrigues_inv(R, cam);
     for (int d = 0; d < 3; ++d) cam[3 + d] = tt[d];
-    cpnp(p3.data(), p2.data(), wv.data(), large, K, cam);
+    cpnp(p3, p2, w3, n, K, cam);
     rodrigues(cam, R);
     quat_wxyz(R, q);
     for (int d = 0; d < 3; ++d) t[d] = cam[3 + d];
+}
+
+// ---- one image from its keypoint rows: val.py:172-180 (correspond.h), then the solve ---------------------------------
+void pose_one(const float* kp, int k, const double* kp3d, const Cam& K, int x0, int y0, double rate, double thresh,
+              int min_k, double q[4], double t[3]) {
+    // top-k by peak (heapq.nlargest: descending, ties keep index order)
+    int above = 0;
+    for (int i = 0; i < k; ++i) above += (double)kp[i * 3 + 2] > thresh;
+    const int large = esa::corr_count(above, min_k, k);
+    std::vector<int> order(k);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return esa::corr_before(kp[a * 3 + 2], a, kp[b * 3 + 2], b); });
+    std::vector<double> p3(3 * large), p2(2 * large), wv(3 * large);
+    const double inv = esa::corr_inv_rate(rate);
+    for (int i = 0; i < large; ++i) {
+        const int j = order[i];
+        for (int d = 0; d < 3; ++d) p3[i * 3 + d] = kp3d[j * 3 + d];
+        p2[i * 2 + 0] = esa::corr_to_image(kp[j * 3 + 0], inv, x0);
+        p2[i * 2 + 1] = esa::corr_to_image(kp[j * 3 + 1], inv, y0);
+        wv[i * 3 + 0] = wv[i * 3 + 2] = (double)kp[j * 3 + 2];
+        wv[i * 3 + 1] = 0.0;
+    }
+    pose_solve(p3.data(), p2.data(), wv.data(), large, K, q, t);
+}
+
+// `work(lo, hi)` over [0, n) on up to `threads` threads
+template <class Work>
+void run_batch(int n, int threads, Work work) {
+    const int nt = std::max(1, std::min(threads, n));
+    if (nt == 1) { work(0, n); return; }
+    std::vector<std::thread> pool;
+    for (int w = 0; w < nt; ++w) pool.emplace_back(work, (int)((long long)n * w / nt), (int)((long long)n * (w + 1) / nt));
+    for (std::thread& th : pool) th.join();
 }
 
 }  // namespace
@@ -598,15 +623,34 @@ extern "C" int esahrnet_pnp_batch(const float* kp, int n, int k, const double* k
     if (n < 0) return esa::set_error("pnp_batch: negative image count %d", n);
     if (k < 1 || k > 64) return esa::set_error("pnp_batch: %d keypoints per image unsupported (1..64)", k);
     const Cam K{K9[0], K9[4], K9[2], K9[5]};
-    auto work = [&](int lo, int hi) {
+    run_batch(n, threads, [&](int lo, int hi) {
         for (int i = lo; i < hi; ++i)
-            pose_one(kp + (size_t)i * k * 3, k, kp3d, K, (double)boxes_xy[i * 2], (double)boxes_xy[i * 2 + 1], rates[i],
-                     thresh, min_k, q_out + (size_t)i * 4, t_out + (size_t)i * 3);
-    };
-    const int nt = std::max(1, std::min(threads, n));
-    if (nt == 1) { work(0, n); return 0; }
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; ++w) pool.emplace_back(work, (int)((long long)n * w / nt), (int)((long long)n * (w + 1) / nt));
-    for (std::thread& th : pool) th.join();
+            pose_one(kp + (size_t)i * k * 3, k, kp3d, K, boxes_xy[i * 2], boxes_xy[i * 2 + 1], rates[i], thresh, min_k,
+                     q_out + (size_t)i * 4, t_out + (size_t)i * 3);
+    });
+    return 0;
+}
+
+extern "C" int esahrnet_pnp_batch_w(const double* pts, const double* w, const int* count, int m, int k, const double* kp3d,
+                                    const int* order, const double* K9, int threads, double* q_out, double* t_out) {
+    if (!pts || !w || !count || !kp3d || !order || !K9 || !q_out || !t_out) return esa::set_error("pnp_batch_w: null argument");
+    if (m < 0) return esa::set_error("pnp_batch_w: negative image count %d", m);
+    if (k < 1 || k > 64) return esa::set_error("pnp_batch_w: %d keypoints per image unsupported (1..64)", k);
+    for (int i = 0; i < m; ++i) {
+        if (count[i] < 0 || count[i] > k) return esa::set_error("pnp_batch_w: count[%d] = %d outside 0..%d", i, count[i], k);
+        for (int j = 0; j < count[i]; ++j)
+            if (order[(size_t)i * k + j] < 0 || order[(size_t)i * k + j] >= k)
+                return esa::set_error("pnp_batch_w: order[%d][%d] = %d is no keypoint index (0..%d)", i, j, order[(size_t)i * k + j], k - 1);
+    }
+    const Cam K{K9[0], K9[4], K9[2], K9[5]};
+    run_batch(m, threads, [&](int lo, int hi) {
+        std::vector<double> p3(3 * (size_t)k);
+        for (int i = lo; i < hi; ++i) {
+            const int n = count[i];
+            for (int j = 0; j < n; ++j)
+                for (int d = 0; d < 3; ++d) p3[j * 3 + d] = kp3d[order[(size_t)i * k + j] * 3 + d];
+            pose_solve(p3.data(), pts + (size_t)i * k * 2, w + (size_t)i * k * 3, n, K, q_out + (size_t)i * 4, t_out + (size_t)i * 3);
+        }
+    });
     return 0;
 }

@@ -104,8 +104,10 @@ __device__ __forceinline__ float final2_log(float b, float s) {
 
 // taylor (inference.py:54-73) on the 13 log values h[]: the differences of two f32 values are f32 (NumPy scalars), the first
 // product with a Python number and everything after it f64 (NumPy 1.x promotion); the inverse in closed form.  The step is
-// taken when det != 0 and the offset is finite; then (fx, fy) = f32(f64(p) + offset).
-__device__ __forceinline__ void final2_newton(const float* h, int px, int py, float& fx, float& fy) {
+// taken when det != 0 and the offset is finite; then (fx, fy) = f32(f64(p) + offset).  HESS: a step that is taken also leaves
+// the Hessian it used in hess3 = (dxx, dxy, dyy) (otherwise hess3 is not touched); the false instantiation is the code it was.
+template <bool HESS = false>
+__device__ __forceinline__ void final2_newton(const float* h, int px, int py, float& fx, float& fy, double* hess3 = nullptr) {
 #pragma clang fp contract(off)                             // the host restatement has no fma
     const double dx = 0.5 * (double)(h[2] - h[1]);
     const double dy = 0.5 * (double)(h[6] - h[5]);
@@ -120,6 +122,11 @@ __device__ __forceinline__ void final2_newton(const float* h, int px, int py, fl
         if (isfinite(ox) && isfinite(oy)) {
             fx = (float)((double)px + ox);
             fy = (float)((double)py + oy);
+            if constexpr (HESS) {
+                hess3[0] = dxx;
+                hess3[1] = dxy;
+                hess3[2] = dyy;
+            }
         }
     }
 }
@@ -127,10 +134,11 @@ __device__ __forceinline__ void final2_newton(const float* h, int px, int py, fl
 // The end of get_final2's finish for one plane, one wave: bv / bm the plane's first raw maximum and its blurred maximum, bi
 // the raw maximum's index (0 for an all -inf / all-NaN plane).  blurred(pt) is the f32 blurred value at final2 point pt; lanes
 // 0..12 call it, and only when the step is taken.  peak() is the raw value at bi (lane 0).  Lane 0 writes kp[plane] (x, y,
-// peak) and, when idx_out is not null, idx_out[plane] = bi.
-template <class Blurred, class Peak>
+// peak) and, when idx_out is not null, idx_out[plane] = bi.  HESS: lane 0 also writes hess[plane] = (dxx, dxy, dyy), f64, the
+// Hessian of the blurred log heat-map that the step used, or NaN x 3 when no step is taken (border, det == 0, non-finite).
+template <bool HESS = false, class Blurred, class Peak>
 __device__ __forceinline__ void final2_finish(float bv, int bi, float bm, int H, int W, Blurred blurred, Peak peak, float* kp,
-                                              int* idx_out, int plane) {
+                                              int* idx_out, int plane, double* hess = nullptr) {
 #pragma clang fp contract(off)
     const int px = bi % W, py = bi / W;
     // gaussian_blur's rescale factor origin_max / max(blurred), f32 (inference.py:110)
@@ -146,7 +154,17 @@ __device__ __forceinline__ void final2_finish(float bv, int bi, float bm, int H,
     for (int j = 0; j < 13; ++j) h[j] = __shfl(lv, j);
     if (threadIdx.x == 0) {
         float fx = (float)px, fy = (float)py;
-        if (go) final2_newton(h, px, py, fx, fy);
+        if constexpr (HESS) {
+            const double nan = __longlong_as_double(0x7ff8000000000000LL);
+            double hs[3] = {nan, nan, nan};
+            if (go) final2_newton<true>(h, px, py, fx, fy, hs);
+            double* h3 = hess + (size_t)plane * 3;
+            h3[0] = hs[0];
+            h3[1] = hs[1];
+            h3[2] = hs[2];
+        } else {
+            if (go) final2_newton(h, px, py, fx, fy);
+        }
         float* kp3 = kp + (size_t)plane * 3;
         kp3[0] = fx;
         kp3[1] = fy;

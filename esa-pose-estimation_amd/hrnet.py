@@ -27,7 +27,7 @@ import torch.nn as nn
 
 from . import _lib, crops
 from .fold import fold_conv
-from .inference import check_refine
+from .inference import check_refine, check_weights, pack_correspondences
 
 logger = logging.getLogger(__name__)
 BN_MOMENTUM = 0.01           # models/seg_hrnet.py:23 (irrelevant at inference, kept for parity)
@@ -182,6 +182,44 @@ class HighResolutionNet(nn.Module):
         the rows of an invalid crop (empty box, frame index out of range: valid == 0) are NaN."""
         return self._frames_to_keypoints(frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format)[:4]
 
+    def frames_to_correspondences(self, frames: torch.Tensor, det_boxes, frame_idx=None, scale: int = 256, rule: str = "val",
+                                  refine: str = "get_final", thresh: float = 0.8, min_k: int = 24, weights: str = "peak",
+                                  mean=None, std: float = crops.STD, pixel_format=None):
+        """frames_to_keypoints and val.py:172-180 behind it in one library call (include/esahrnet.h
+        esahrnet_frames_correspondences): -> (count int32 [m], order int32 [m,K], pts f64 [m,K,2], w f64 [m,K,3], kp, crop_boxes,
+        rates, valid), all on the device.  The first four are the record the host pose solver consumes
+        (pnp.correspondences_to_pose_batch): the keypoints handed to PnP, largest peak first, in image pixels, each with its
+        2x2 weight (wxx, wxy, wyy) — weights="peak": (peak, 0, peak); "hessian" (refine="get_final2" only): the get_final2
+        Hessian as an information matrix, rate * (-H)^(1/2).  Equal, bit for bit, to frames_to_keypoints followed by
+        inference.keypoints_to_correspondences; capturable into a graph."""
+        return self._frames_to_correspondences(frames, det_boxes, frame_idx, scale, rule, refine, thresh, min_k, weights, mean, std,
+                                               pixel_format)[:8]
+
+    def _frames_to_correspondences(self, frames, det_boxes, frame_idx, scale, rule, refine, thresh, min_k, weights, mean, std,
+                                   pixel_format):
+        """frames_to_correspondences, plus (packed,): count, order, pts and w are views of `packed` (one uint8 buffer,
+        inference.pack_correspondences), which a caller that needs them on the host fetches with one copy."""
+        if self.training:
+            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
+                               "(the reference callers do, val.py:95 / demo.py:80)")
+        check_refine(refine)
+        mode = check_weights(weights, refine)
+        rule_n, fmt, m = crops.check_device_loader_args(frames, det_boxes, frame_idx, rule, pixel_format)
+        if mean is None:
+            mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
+        return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
+                                         1 if refine == "get_final2" else 0, corr=(float(thresh), int(min_k), mode))
+
+    def keypoints_hessian(self, x0: torch.Tensor):
+        """net(x, output="keypoints+index", refine="get_final2") with the Hessian of each step: -> (kp f32 [N,K,3], idx int32
+        [N,K], hess f64 [N,K,3] = (dxx, dxy, dyy), NaN where no step was taken), bit-identical to
+        inference.heatmaps_to_keypoints(net(x), refine="get_final2", return_hessian=True), without heat-maps in caller memory
+        (include/esahrnet.h esahrnet_forward_keypoints_final2_hess)."""
+        if self.training:
+            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
+                               "(the reference callers do, val.py:95 / demo.py:80)")
+        return self._rt.forward_final2(self, x0, True, want_hessian=True)
+
     def _frames_to_keypoints(self, frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format):
         """frames_to_keypoints, plus (idx int32 [m,K], packed): every output is a view of `packed` (one uint8 buffer), so a
         caller that needs them on the host fetches them with one copy (pipeline.estimate_poses)."""
@@ -299,6 +337,15 @@ class _Runtime:
         self.part_tiles = {}     # (handle, h, w) -> tiles per heat-map with partial maxima (0: none)
         self._probe = self._create(-1)
 
+    def use_library(self, other):
+        """Run this runtime through another build of the library (_lib.load_other), for A/B timing of the entries both have.
+        Only before the first forward: no handle of the first library may exist yet."""
+        if self.handles:
+            raise RuntimeError("use_library: this runtime already holds handles of its library")
+        self.lib.esahrnet_destroy(self._probe)
+        self.lib = other
+        self._probe = self._create(-1)
+
     def _create(self, device):
         h = C.c_void_p()
         _lib.check(self.lib.esahrnet_create(C.byref(self.cfg), max(device, 0), C.byref(h)))
@@ -396,6 +443,9 @@ class _Runtime:
         elif kind == "final2":
             _lib.check(self.lib.esahrnet_keypoints_final2_forward_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
             cache = self.f2_ws
+        elif kind == "corr":                            # n crops of hh x hh; keep = (decoder, mode)
+            _lib.check(self.lib.esahrnet_frames_correspondences_workspace_bytes(h, n, hh, keep[0], keep[1], C.byref(nbytes)))
+            cache = self.fr_ws
         elif kind in ("frames", "frames_final2"):       # n crops of hh x hh; `keep` tells the two decoders' entries apart
             _lib.check(self.lib.esahrnet_frames_keypoints_workspace_bytes(h, n, hh, int(kind == "frames_final2"), C.byref(nbytes)))
             cache = self.fr_ws
@@ -482,7 +532,7 @@ class _Runtime:
         x.record_stream(ts)
         return kp, idx
 
-    def forward_final2(self, module, x0, want_index):
+    def forward_final2(self, module, x0, want_index, want_hessian=False):
         """net(x, output="keypoints", refine="get_final2"): esahrnet_forward_keypoints_final2, the forward with get_final2 in
         place of its last launch; nothing but (kp, idx) reaches caller memory.  Same device lock, workspace contract (graph
         capture included) and record_stream handling as forward()."""
@@ -497,19 +547,26 @@ class _Runtime:
             ws, ws_ptr, nbytes = self._workspace(h, dev, ts, n, hh, ww, False, kind="final2")
             kp = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
             idx = torch.empty((n, k), dtype=torch.int32, device=dev) if want_index else None
+            hess = torch.empty((n, k, 3), dtype=torch.float64, device=dev) if want_hessian else None
             with torch.cuda.device(dev):
-                _lib.check(self.lib.esahrnet_forward_keypoints_final2(h, x.data_ptr(), n, hh, ww, kp.data_ptr(),
-                                                                      idx.data_ptr() if want_index else None, ws_ptr, nbytes,
-                                                                      C.c_void_p(ts.cuda_stream)))
+                if want_hessian:
+                    _lib.check(self.lib.esahrnet_forward_keypoints_final2_hess(
+                        h, x.data_ptr(), n, hh, ww, kp.data_ptr(), idx.data_ptr() if want_index else None, hess.data_ptr(), ws_ptr,
+                        nbytes, C.c_void_p(ts.cuda_stream)))
+                else:
+                    _lib.check(self.lib.esahrnet_forward_keypoints_final2(h, x.data_ptr(), n, hh, ww, kp.data_ptr(),
+                                                                          idx.data_ptr() if want_index else None, ws_ptr, nbytes,
+                                                                          C.c_void_p(ts.cuda_stream)))
         ws.record_stream(ts)
         x.record_stream(ts)
-        return kp, idx
+        return (kp, idx, hess) if want_hessian else (kp, idx)
 
-    def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder):
+    def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None):
         """esahrnet_frames_keypoints (arguments already checked by crops.check_device_loader_args).  The outputs are views
         of one packed buffer: rates f64 [m] | kp f32 [m,K,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,K].
         Same device lock, weight-staleness key, workspace contract (graph capture included) and record_stream handling as
-        forward()."""
+        forward().  corr = (thresh, min_k, mode): esahrnet_frames_correspondences instead -> (count, order, pts, w, kp, boxes,
+        rates, valid, packed), the first four views of `packed` (inference.pack_correspondences)."""
         if module._cin != 1:
             raise ValueError(f"the loader makes 1-channel crops; this network takes {module._cin} channels")
         if "_master" not in module.__dict__:
@@ -537,6 +594,19 @@ class _Runtime:
             with self._device_lock(dev.index):
                 h = self._handle_for(module, dev)
                 _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
+                if corr is not None:
+                    thresh, min_k, mode = corr
+                    count, order, pts, w, cpacked = pack_correspondences(m, k, dev)
+                    ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, (decoder, mode), kind="corr")
+                    _lib.check(self.lib.esahrnet_frames_correspondences(
+                        h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m,
+                        scale, rule, mean, std, decoder, thresh, min_k, mode, kp.data_ptr(), idx.data_ptr(), boxes.data_ptr(),
+                        rates.data_ptr(), valid.data_ptr(), count.data_ptr(), order.data_ptr(), pts.data_ptr(), w.data_ptr(),
+                        ws_ptr, ws_bytes, C.c_void_p(ts.cuda_stream)))
+                    for t in (ws, frames, det, fidx):
+                        if t is not None:
+                            t.record_stream(ts)
+                    return count, order, pts, w, kp, boxes, rates, valid, cpacked
                 ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, bool(decoder),
                                                        kind="frames_final2" if decoder else "frames")
                 _lib.check(self.lib.esahrnet_frames_keypoints(

@@ -40,7 +40,7 @@ def final2_workspace(n: int, k: int, h: int, w: int, device):
     return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, nbytes.value
 
 
-def _keypoints_final2(heat: torch.Tensor, want_index: bool):
+def _keypoints_final2(heat: torch.Tensor, want_index: bool, want_hessian: bool = False):
     heat = heat.contiguous()
     n, k, h, w = heat.shape
     kp = torch.empty((n, k, 3), dtype=torch.float32, device=heat.device)
@@ -48,14 +48,22 @@ def _keypoints_final2(heat: torch.Tensor, want_index: bool):
     stream = torch.cuda.current_stream(heat.device).cuda_stream
     with torch.cuda.device(heat.device):
         ws, ws_ptr, ws_bytes = final2_workspace(n, k, h, w, heat.device)
+        if want_hessian:
+            hess = torch.empty((n, k, 3), dtype=torch.float64, device=heat.device)
+            _lib.check(_lib.lib().esahrnet_keypoints_final2_hess(heat.data_ptr(), n, k, h, w, kp.data_ptr(),
+                                                                 idx.data_ptr() if want_index else None, hess.data_ptr(),
+                                                                 ws_ptr, ws_bytes, C.c_void_p(stream)))
+            return kp, idx, hess
         _lib.check(_lib.lib().esahrnet_keypoints_final2(heat.data_ptr(), n, k, h, w, kp.data_ptr(),
                                                         idx.data_ptr() if want_index else None, ws_ptr, ws_bytes,
                                                         C.c_void_p(stream)))
     return kp, idx
 
 
-def _keypoints(heat: torch.Tensor, want_index: bool, refine: str = "get_final"):
+def _keypoints(heat: torch.Tensor, want_index: bool, refine: str = "get_final", want_hessian: bool = False):
     check_refine(refine)
+    if want_hessian and refine != "get_final2":
+        raise ValueError("return_hessian=True needs refine='get_final2': get_final computes no Hessian")
     if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
         raise ValueError("expected a 4-D tensor [N, K, H, W]")
     if not heat.is_cuda:
@@ -63,7 +71,7 @@ def _keypoints(heat: torch.Tensor, want_index: bool, refine: str = "get_final"):
     if heat.dtype != torch.float32:
         raise TypeError(f"expected float32 heatmaps, got {heat.dtype}")
     if refine == "get_final2":
-        return _keypoints_final2(heat, want_index)
+        return _keypoints_final2(heat, want_index, want_hessian)
     # heat-maps that come straight out of a forward carry the per-tile maxima their output-layer kernel found
     # (hrnet._Runtime.forward): finishing over those gives the same bits without reading the maps again.  The note is
     # honoured only for this very tensor object, unmodified since (views, clones and in-place edits take the full sweep).
@@ -91,12 +99,80 @@ def _keypoints(heat: torch.Tensor, want_index: bool, refine: str = "get_final"):
     return kp, idx
 
 
-def heatmaps_to_keypoints(heat: torch.Tensor, refine: str = "get_final") -> torch.Tensor:
+def heatmaps_to_keypoints(heat: torch.Tensor, refine: str = "get_final", return_hessian: bool = False):
     """f32 cuda [N,K,H,W] -> f32 cuda [N,K,3] = (x, y, peak); x=col, y=row, 0-based; peak is the raw maximum.
     refine="get_final" (default): sub-pixel refined exactly as inference.my_taylor does.  refine="get_final2": as
     get_final2 does (11x11 Gaussian blur rescaled to the raw peak, log, full-Hessian Newton step; include/esahrnet.h
-    esahrnet_keypoints_final2), same arg-max and peak; the blurred maps are never stored and `heat` is not modified."""
-    return _keypoints(heat, False, refine)[0]
+    esahrnet_keypoints_final2), same arg-max and peak; the blurred maps are never stored and `heat` is not modified.
+    return_hessian=True (get_final2 only): -> (kp, hess f64 cuda [N,K,3] = (dxx, dxy, dyy)), the Hessian of the blurred
+    log heat-map each step used, NaN where no step was taken (esahrnet_keypoints_final2_hess); kp has the same bits."""
+    out = _keypoints(heat, False, refine, return_hessian)
+    return (out[0], out[2]) if return_hessian else out[0]
+
+
+WEIGHTS = ("peak", "hessian")
+
+
+def check_weights(weights, refine="get_final2"):
+    """The weight of the pose refinement: "peak" (default; val.py:194-209) or "hessian" (the get_final2 Hessian as the 2x2
+    weight uncertainty_pnp.cpp takes; needs refine="get_final2").  -> the mode of esahrnet_correspondences."""
+    if not isinstance(weights, str) or weights not in WEIGHTS:
+        raise ValueError(f"weights must be one of {WEIGHTS}, got {weights!r}")
+    if weights == "hessian" and refine != "get_final2":
+        raise ValueError("weights='hessian' needs refine='get_final2': get_final computes no Hessian")
+    return WEIGHTS.index(weights)
+
+
+def pack_correspondences(m: int, k: int, device):
+    """One uint8 buffer and its views count int32 [m] | order int32 [m,k] | pts f64 [m,k,2] | w f64 [m,k,3] (pts first in
+    memory: 8-byte aligned), so that a caller fetches the whole record with one copy.  -> (count, order, pts, w, packed)."""
+    sizes = (16 * m * k, 24 * m * k, 4 * m, 4 * m * k)
+    offs = [0]
+    for b in sizes:
+        offs.append(offs[-1] + b)
+    packed = torch.empty(offs[-1], dtype=torch.uint8, device=device)
+    pts = packed[offs[0]:offs[1]].view(torch.float64).view(m, k, 2)
+    w = packed[offs[1]:offs[2]].view(torch.float64).view(m, k, 3)
+    count = packed[offs[2]:offs[3]].view(torch.int32)
+    order = packed[offs[3]:offs[4]].view(torch.int32).view(m, k)
+    return count, order, pts, w, packed
+
+
+def unpack_correspondences(host: np.ndarray, m: int, k: int):
+    """pack_correspondences' buffer, copied to the host -> (count, order, pts, w) as numpy views."""
+    offs = np.cumsum([0, 16 * m * k, 24 * m * k, 4 * m, 4 * m * k])
+    pts = host[offs[0]:offs[1]].view(np.float64).reshape(m, k, 2)
+    w = host[offs[1]:offs[2]].view(np.float64).reshape(m, k, 3)
+    count = host[offs[2]:offs[3]].view(np.int32)
+    order = host[offs[3]:offs[4]].view(np.int32).reshape(m, k)
+    return count, order, pts, w
+
+
+def keypoints_to_correspondences(kp: torch.Tensor, crop_boxes: torch.Tensor, rates: torch.Tensor, valid: torch.Tensor,
+                                 hess: torch.Tensor = None, thresh: float = 0.8, min_k: int = 24, weights: str = "peak"):
+    """val.py:172-180 on the device (include/esahrnet.h esahrnet_correspondences): kp f32 cuda [m,K,3] and the crop boxes
+    int32 [m,4], rates f64 [m] and valid int32 [m] of net.frames_to_keypoints / crops.crop_batch_device -> (count int32 [m],
+    order int32 [m,K], pts f64 [m,K,2], w f64 [m,K,3]) on the device: what select_keypoints + crop_to_image give, bit for bit,
+    and the weight of each point.  weights="hessian" takes hess f64 [m,K,3] (heatmaps_to_keypoints(..., return_hessian=True))."""
+    mode = check_weights(weights)
+    if not (isinstance(kp, torch.Tensor) and kp.is_cuda and kp.dtype == torch.float32 and kp.dim() == 3 and kp.shape[2] == 3):
+        raise ValueError("kp must be a float32 cuda tensor [m, K, 3]")
+    m, k = kp.shape[:2]
+    dev = kp.device
+    for name, t, dt, shape in (("crop_boxes", crop_boxes, torch.int32, (m, 4)), ("rates", rates, torch.float64, (m,)),
+                               ("valid", valid, torch.int32, (m,))) + ((("hess", hess, torch.float64, (m, k, 3)),) if mode else ()):
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt and tuple(t.shape) == shape):
+            raise ValueError(f"{name} must be a {dt} tensor {list(shape)} on {dev}")
+    kp, crop_boxes, rates, valid = kp.contiguous(), crop_boxes.contiguous(), rates.contiguous(), valid.contiguous()
+    hess = hess.contiguous() if mode else None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        count, order, pts, w, _ = pack_correspondences(m, k, dev)
+        _lib.check(_lib.lib().esahrnet_correspondences(kp.data_ptr(), hess.data_ptr() if mode else None, crop_boxes.data_ptr(),
+                                                       rates.data_ptr(), valid.data_ptr(), m, k, float(thresh), int(min_k), mode,
+                                                       count.data_ptr(), order.data_ptr(), pts.data_ptr(), w.data_ptr(),
+                                                       C.c_void_p(stream)))
+    return count, order, pts, w
 
 
 def _to_device(hm):

@@ -110,7 +110,8 @@ class PoseFailure(ValueError):
 def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256, thresh: float = 0.8,
                    min_k: int = 24, distributed: bool = False, pool=None, native: bool = True,
                    on_fail: str = "raise", keypoints_only: bool = False, refine: str = "get_final",
-                   device_loader: bool = False, frame_idx=None, rule: str = "val"):
+                   device_loader: bool = False, frame_idx=None, rule: str = "val", device_select: bool = False,
+                   weights: str = "peak", threads: int = 0):
     """One batch of the val.py:136-233 loop.  frames uint8 cuda [N,H,W]; bboxes N x (x, y, x2, y2);
     kp3d [K3, 3] model keypoints; K camera matrix.  -> list of (q [w,x,y,z], t) per image.
     An image without a solution (the native solver reports it as a NaN row; the reference would die inside
@@ -121,8 +122,30 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
     device_loader=True: net.frames_to_keypoints does the box rule (`rule`: "val" / "train"), the crops, the forward and the
     decoder in one library call; keypoints, crop boxes, rates and valid flags come back in ONE device->host copy of one
     packed buffer.  bboxes are integers then, several may lie on one frame (frame_idx[i] = frame of box i; frames may be RGB
-    [N,H,W,3]), and a crop the loader could not make (empty box, frame index out of range) has no pose: on_fail applies."""
+    [N,H,W,3]), and a crop the loader could not make (empty box, frame index out of range) has no pose: on_fail applies.
+    device_select=True (implies the device loader): net.frames_to_correspondences also does the top-k rule, the ordering and
+    the back-projection of val.py:172-180 on the device; ONE device->host copy of the correspondence record (count, order,
+    image points, 2x2 weights), then the native solver on it (pnp.correspondences_to_pose_batch).  `threads`: worker threads of
+    the native solver on every path (0: one per available CPU, at most 16).
+    weights="peak" (default): the poses of device_loader=True, bit for bit.  weights="hessian" (device_select=True and
+    refine="get_final2" only): the refinement weighs each point by the get_final2 Hessian, rate * (-H)^(1/2), the anisotropic
+    weight uncertainty_pnp.cpp:30-31 takes, instead of the scalar peak."""
     inference.check_refine(refine)
+    inference.check_weights(weights, refine)
+    if weights != "peak" and not device_select:
+        raise ValueError("weights='hessian' belongs to device_select=True (the host selection weighs by the peak)")
+    if device_select:
+        if distributed:
+            raise ValueError("device_select=True runs on one device (distributed=True shards crops that exist on the host side)")
+        if not native:
+            raise ValueError("device_select=True hands its record to the native solver (native=False has no entry for it)")
+        with torch.no_grad():
+            out = net._frames_to_correspondences(frames, bboxes, frame_idx, scale, rule, refine, thresh, min_k, weights, None,
+                                                 crops.STD, None)
+        m, k = out[4].shape[:2]
+        count, order, pts, w = inference.unpack_correspondences(out[8].cpu().numpy(), m, k)     # the only device->host copy
+        q, t = pnp.correspondences_to_pose_batch(pts, w, count, order, kp3d, np.asarray(K, np.float64), threads)
+        return _checked_poses([(q[i], t[i]) for i in range(m)], on_fail)
     if device_loader:
         if distributed:
             raise ValueError("device_loader=True runs on one device (distributed=True shards crops that exist on the host side)")
@@ -139,7 +162,7 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
         bad = valid == 0
         rates = [1.0 if b else float(r) for r, b in zip(rates, bad)]
         poses = poses_from_keypoints(np.where(bad[:, None, None], np.float32(0), kp), boxes, rates, kp3d, K, thresh, min_k,
-                                     pool, native)
+                                     pool, native, threads)
         poses = [(np.full(4, np.nan), np.full(3, np.nan)) if b else p for p, b in zip(poses, bad)]
         return _checked_poses(poses, on_fail)
     if frame_idx is not None or rule != "val":
@@ -154,7 +177,7 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
         else:
             kp = inference.heatmaps_to_keypoints(net(x), **rk)
     kp = kp.cpu().numpy()                                   # the only device->host copy: N*K*3 floats
-    return _checked_poses(poses_from_keypoints(kp, boxes, rates, kp3d, K, thresh, min_k, pool, native), on_fail)
+    return _checked_poses(poses_from_keypoints(kp, boxes, rates, kp3d, K, thresh, min_k, pool, native, threads), on_fail)
 
 
 def _checked_poses(poses, on_fail):

@@ -279,19 +279,35 @@ def pnp(points_3d, points_2d, camera_matrix, method=SOLVEPNP_EPNP):
 
 # ------------------------------------------------------------------------ weighted refinement (cpnp_m)
 def cpnp_m(p3d, p2d, weights, K, camera, iters=50):
-    """Peak-weighted reprojection refinement: camera = [angle-axis(3), t(3)] -> refined camera.
-    Residual per point = w * (proj - obs)  (uncertainty_pnp.cpp:7-33 with wxx = wyy = w, wxy = 0),
-    minimised by Levenberg-Marquardt with a numerical-free analytic Jacobian in the pose increment."""
+    """Weighted reprojection refinement: camera = [angle-axis(3), t(3)] -> refined camera.
+    weights [n]: residual per point = w * (proj - obs)  (uncertainty_pnp.cpp:7-33 with wxx = wyy = w, wxy = 0).
+    weights [n, 3] = (wxx, wxy, wyy): the symmetric 2x2 weight of uncertainty_pnp.cpp:30-31,
+    r = [wxx dx + wxy dy, wxy dx + wyy dy]; rows (w, 0, w) give the scalar form's result bit for bit.
+    Minimised by Levenberg-Marquardt with a numerical-free analytic Jacobian in the pose increment."""
     p3d = np.asarray(p3d, np.float64)
     p2d = np.asarray(p2d, np.float64)
-    w = np.asarray(weights, np.float64).reshape(-1, 1)
+    w = np.asarray(weights, np.float64)
+    full = w.ndim == 2
+    if full:
+        if w.shape != (len(p3d), 3):
+            raise ValueError(f"weights must be [n] or [n, 3] = (wxx, wxy, wyy), got {w.shape}")
+        W = np.stack([w[:, [0, 1]], w[:, [1, 2]]], 1)          # [n, 2, 2]
+    else:
+        w = w.reshape(-1, 1)
     K = np.asarray(K, np.float64)
     fx, fy = K[0, 0], K[1, 1]
     x = np.asarray(camera, np.float64).reshape(6).copy()
 
+    def weigh(d):
+        """d [n, 2, ...]: reprojection differences, or their Jacobian rows -> W d per point."""
+        if not full:
+            return d * w.reshape((-1, 1) + (1,) * (d.ndim - 2))
+        return W[:, :, 0].reshape(W.shape[:2] + (1,) * (d.ndim - 2)) * d[:, :1] + \
+            W[:, :, 1].reshape(W.shape[:2] + (1,) * (d.ndim - 2)) * d[:, 1:]
+
     def residual(x):
         R = rodrigues(x[:3])
-        return (w * (project(p3d, R, x[3:], K) - p2d)).ravel(), R
+        return weigh(project(p3d, R, x[3:], K) - p2d).ravel(), R
 
     r, R = residual(x)
     cost = r @ r
@@ -310,7 +326,7 @@ def cpnp_m(p3d, p2d, weights, K, camera, iters=50):
             J[i, 1, :3] = dpy[i] @ S
             J[i, 0, 3:] = dpx[i]
             J[i, 1, 3:] = dpy[i]
-        J = (J * w[:, :, None]).reshape(-1, 6)
+        J = weigh(J).reshape(-1, 6)
         H = J.T @ J
         g = J.T @ r
         improved = False
@@ -368,6 +384,32 @@ def keypoints_to_pose_batch(kp, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=24, 
                                              K9.ctypes.data_as(C.c_void_p), bxy.ctypes.data_as(C.c_void_p),
                                              rt.ctypes.data_as(C.c_void_p), float(thresh), int(min_k), int(threads),
                                              q.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p)))
+    return q, t
+
+
+def correspondences_to_pose_batch(pts, w, count, order, kp3d, K, threads=0):
+    """The host stage on records the device stage wrote (include/esahrnet.h esahrnet_correspondences ->
+    `esahrnet_pnp_batch_w`): pts [N,K,2] f64 image pixels, w [N,K,3] f64 = (wxx, wxy, wyy), count [N], order [N,K] int32
+    -> (q [N,4] = [w,x,y,z], t [N,3]); rows without a solution (fewer than 4 points among them) are NaN.  EPnP + RANSAC on
+    pts, LM with the full 2x2 weights: with (peak, 0, peak) rows the poses of keypoints_to_pose_batch, bit for bit."""
+    import ctypes as C
+    import os
+    from . import _lib
+    pts = np.ascontiguousarray(pts, np.float64)
+    n, k = pts.shape[0], pts.shape[1]
+    w = np.ascontiguousarray(w, np.float64)
+    count = np.ascontiguousarray(count, np.int32)
+    order = np.ascontiguousarray(order, np.int32)
+    kp3d = np.ascontiguousarray(kp3d, np.float64)
+    K9 = np.ascontiguousarray(K, np.float64).reshape(9)
+    assert pts.shape == (n, k, 2) and w.shape == (n, k, 3) and count.shape == (n,) and order.shape == (n, k)
+    assert kp3d.shape == (k, 3)
+    q = np.empty((n, 4), np.float64)
+    t = np.empty((n, 3), np.float64)
+    if threads <= 0:
+        threads = min(16, len(os.sched_getaffinity(0))) if hasattr(os, "sched_getaffinity") else 4
+    p = lambda a: a.ctypes.data_as(C.c_void_p)                       # noqa: E731
+    _lib.check(_lib.lib().esahrnet_pnp_batch_w(p(pts), p(w), p(count), n, k, p(kp3d), p(order), p(K9), int(threads), p(q), p(t)))
     return q, t
 
 

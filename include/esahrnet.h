@@ -142,6 +142,15 @@ int esahrnet_keypoints_final2_workspace_bytes(int n, int k, int height, int widt
 int esahrnet_keypoints_final2(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev,
                               void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
 
+/* esahrnet_keypoints_final2 with one more output: hess_dev f64 [n][k][3] = (dxx, dxy, dyy), the Hessian of the blurred log
+ * heat-map at the peak — the very values the Newton step used (central differences of the 13 f32 log values, in f64) — or
+ * NaN x 3 for a keypoint whose step was not taken (peak within 2 px of the border, det = 0, anything non-finite).  For a
+ * Gaussian blob -H is the keypoint's information matrix in crop pixels (esahrnet_correspondences, mode 1).  The finish kernel
+ * is instantiated with and without the output: hess_dev == NULL launches the kernels of esahrnet_keypoints_final2, and
+ * kp_dev / idx_dev are bit-identical to its in either case. */
+int esahrnet_keypoints_final2_hess(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev,
+                                   void* hess_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+
 /* ---- forward + keypoints without re-reading the heat-maps -------------------------------------------------
  * The output-layer kernel can leave, beside the heat-maps, the first row-major maximum of each of its tiles:
  * part_dev = 8 bytes x [n * K][ntiles] (f32 value, int32 index row * width + column).  esahrnet_keypoints_finish reduces
@@ -190,6 +199,13 @@ int esahrnet_keypoints_final2_forward_workspace_bytes(esahrnet_handle h, int n, 
 int esahrnet_forward_keypoints_final2(esahrnet_handle h, const void* x_dev, int n, int height, int width,
                                       void* kp_dev, void* idx_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
 
+/* The same with hess_dev f64 [n][K][3] as esahrnet_keypoints_final2_hess writes it, in all three forms (VALU re-evaluation,
+ * matrix-core, seg_hrnet3 NHWC): bit-identical to esahrnet_forward + esahrnet_keypoints_final2_hess.  hess_dev == NULL is
+ * esahrnet_forward_keypoints_final2; same workspace query. */
+int esahrnet_forward_keypoints_final2_hess(esahrnet_handle h, const void* x_dev, int n, int height, int width,
+                                           void* kp_dev, void* idx_dev, void* hess_dev, void* ws_dev, size_t ws_bytes,
+                                           esahrnet_stream stream);
+
 /* Loader stage in front of the path (data_load_val.py:139-187): for each of n 8-bit frames
  * [frame_h][frame_w] take the clamped box boxes[i] = (x0, y0, x1, y1) (int32, device), edge-pad it the
  * way the reference does, resize to scale x scale (OpenCV 8-bit INTER_LINEAR arithmetic) and write
@@ -233,15 +249,56 @@ int esahrnet_frames_keypoints(esahrnet_handle h, const void* frames_dev, int nfr
                               void* kp_dev, void* idx_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev,
                               void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
 
+/* ---- keypoints to the record the pose solver consumes, on the device (val.py:172-180) -------------------------------------
+ * esahrnet_correspondences (correspond_kernel, one wave per crop, k <= 32): kp_dev f32 [m][k][3] keypoint rows, crop_boxes_dev /
+ *   rates_dev / valid_dev as esahrnet_boxes wrote them ->
+ *     count_dev int32 [m]       keypoints handed to the solver: max(#(peak > thresh), min_k), at most k;
+ *     order_dev int32 [m][k]    their indices, largest peak first, equal peaks by lower index (heapq.nlargest); -1 beyond count;
+ *     pts_dev   f64 [m][k][2]   image pixels in that order: p * (1 / rate) + (x_new, y_new), bit-identical to what
+ *                               esahrnet_pnp_batch computes for its image points (one shared header, csrc/correspond.h);
+ *     w_dev     f64 [m][k][3]   (wxx, wxy, wyy), the symmetric 2x2 weight of uncertainty_pnp.cpp:30-31, in that order.
+ *   pts and w are zero beyond count.  mode 0 "peak": w = (peak, 0, peak), the scalar weight of val.py:194-209; hess_dev unused
+ *   (may be NULL).  mode 1 "hessian": w = rate * (-H)^(1/2), H = hess_dev f64 [m][k][3] from the get_final2 decoder
+ *   (esahrnet_keypoints_final2_hess): the closed-form symmetric square root of the 2x2 information matrix, scaled to image
+ *   pixels (d_img = d_crop / rate); w = 0 when -H is not positive definite, H is NaN or the weight is not finite — the point
+ *   still reaches EPnP / RANSAC but carries no weight in the refinement.  An invalid crop (valid == 0) has count 0.  A NaN
+ *   peak in a valid crop is never selected (count is at most the number of peaks that are numbers).
+ * esahrnet_frames_correspondences: esahrnet_frames_keypoints (same arguments, same kp_dev / idx_dev / crop_boxes_dev /
+ *   rates_dev / valid_dev outputs, bit-identical) followed by esahrnet_correspondences on its outputs, the Hessian passing
+ *   through the workspace.  decoder 0 with mode 1 is refused: get_final computes no Hessian.  ws_dev:
+ *   esahrnet_frames_correspondences_workspace_bytes bytes, 256-byte aligned.
+ * All three allocate nothing, do not synchronise and may be captured into a graph.  Argument errors are reported before
+ * anything is enqueued (esahrnet_frames_correspondences: as far as esahrnet_frames_keypoints does — its checks and its
+ * workspace query, which plans the shape, run first; a failure inside the forward after that would come behind the box
+ * and crop launches). */
+int esahrnet_correspondences(const void* kp_dev, const void* hess_dev, const void* crop_boxes_dev, const void* rates_dev,
+                             const void* valid_dev, int m, int k, double thresh, int min_k, int mode, void* count_dev,
+                             void* order_dev, void* pts_dev, void* w_dev, esahrnet_stream stream);
+int esahrnet_frames_correspondences_workspace_bytes(esahrnet_handle h, int m, int scale, int decoder, int mode, size_t* bytes);
+int esahrnet_frames_correspondences(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                                    int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale,
+                                    int rule, float mean, float stdv, int decoder, double thresh, int min_k, int mode,
+                                    void* kp_dev, void* idx_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev,
+                                    void* count_dev, void* order_dev, void* pts_dev, void* w_dev, void* ws_dev, size_t ws_bytes,
+                                    esahrnet_stream stream);
+
 /* Host pose solve behind the path, for a batch (pnp.py:46-90 + cpnp.cpnp_m of val.py:194-209 + val.py:172-180,
  * 221-224): kp = host f32 [n][k][3] keypoint rows (x, y, peak) in crop coordinates as esahrnet_keypoints wrote
  * them; kp3d = f64 [k][3] model points; K9 = f64 row-major camera matrix; boxes_xy = int32 [n][2] crop origins;
  * rates = f64 [n] crop scale factors.  Per image: keypoints with peak > thresh (at least min_k, largest first),
- * mapped back to image pixels, EPnP + RANSAC (5 px, 100 iterations, 0.99), peak-weighted LM refinement,
+ * mapped back to image pixels — selection and back-projection are the functions of csrc/correspond.h, the header the device
+ * stage esahrnet_correspondences shares —, EPnP + RANSAC (5 px, 100 iterations, 0.99), peak-weighted LM refinement,
  * -> q_out f64 [n][4] = [w, x, y, z], t_out f64 [n][3] (NaN when fewer than 4 keypoints or no solution).
  * Pure host code, `threads` worker threads; needs no GPU.  Returns 0, or 1 on a bad argument. */
 int esahrnet_pnp_batch(const float* kp, int n, int k, const double* kp3d, const double* K9, const int* boxes_xy,
                        const double* rates, double thresh, int min_k, int threads, double* q_out, double* t_out);
+/* The same solver on records esahrnet_correspondences wrote (host copies): pts f64 [m][k][2], w f64 [m][k][3], count int32
+ * [m], order int32 [m][k]; image i solves on its first count[i] points, model point kp3d[order[i][j]] for point j: EPnP +
+ * RANSAC on pts, then the LM refinement with the full 2x2 weight, r = [wxx dx + wxy dy, wxy dx + wyy dy]
+ * (uncertainty_pnp.cpp:30-31).  With w = (peak, 0, peak) the poses are bit-identical to esahrnet_pnp_batch's (which runs
+ * this code with those weights).  count outside 0..k or an order entry outside 0..k-1 is refused. */
+int esahrnet_pnp_batch_w(const double* pts, const double* w, const int* count, int m, int k, const double* kp3d,
+                         const int* order, const double* K9, int threads, double* q_out, double* t_out);
 
 /* ---- introspection / per-operator entry points (used by the parity tests) ------------- */
 
