@@ -33,6 +33,16 @@ class OpDesc(C.Structure):
                 ("bytes", C.c_double)]
 
 
+class DebugRegion(C.Structure):
+    _fields_ = [("tensor", C.c_int32), ("role", C.c_int32), ("write", C.c_int32), ("slice", C.c_int32),
+                ("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class DebugOp(C.Structure):
+    _fields_ = [("index", C.c_int32), ("wave", C.c_int32), ("lane", C.c_int32), ("job", C.c_int32), ("multi", C.c_int32),
+                ("nregions", C.c_int32), ("regions", DebugRegion * 8)]
+
+
 class EsaHrnetError(RuntimeError):
     pass
 
@@ -48,6 +58,8 @@ _SIGS = {
     "esahrnet_debug_devstate": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "esahrnet_debug_set_launch_limit": (C.c_int, [C.c_longlong]),
     "esahrnet_debug_op_schedule": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "esahrnet_debug_op_count": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "esahrnet_debug_op_regions": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DebugOp)]),
     "esahrnet_conv_count": (C.c_int, [C.c_void_p]),
     "esahrnet_conv_desc_get": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ConvDesc)]),
     "esahrnet_set_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -1126,6 +1126,13 @@ esa::CbamJob cbam_job(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, c
     return q;
 }
 
+// bytes the planner reserves for tensor `t` at a shape (a multiple of 256)
+size_t tensor_bytes(const esahrnet_ctx& c, const ShapePlan& sp, const Tensor& t) {
+    const size_t wpix = t.tlayout ? (size_t)esa::head_t_xp(sp.lw[t.level]) : (size_t)sp.lw[t.level];
+    size_t b = t.flat ? (size_t)sp.n * t.flat * 4 : (size_t)sp.n * sp.lh[t.level] * wpix * t.Cp * (t.f32 ? 4 : c.eb());
+    return (b + 255) & ~(size_t)255;
+}
+
 // first-fit interval allocator over op order; tensors die after their last use
 int plan_shape(esahrnet_ctx& c, int n, int h, int w) {
     if (c.sp.n == n && c.sp.h == h && c.sp.w == w && c.sp.keep == c.keep) return 0;
@@ -1158,11 +1165,7 @@ int plan_shape(esahrnet_ctx& c, int n, int h, int w) {
     struct Free { size_t off, len; };
     std::vector<Free> free_list;
     size_t top = 0;
-    auto bytes_of = [&](const Tensor& t) {
-        const size_t wpix = t.tlayout ? (size_t)esa::head_t_xp(sp.lw[t.level]) : (size_t)sp.lw[t.level];
-        size_t b = t.flat ? (size_t)n * t.flat * 4 : (size_t)n * sp.lh[t.level] * wpix * t.Cp * (t.f32 ? 4 : c.eb());
-        return (b + 255) & ~(size_t)255;
-    };
+    auto bytes_of = [&](const Tensor& t) { return tensor_bytes(c, sp, t); };
     auto alloc = [&](size_t len) {
         for (size_t i = 0; i < free_list.size(); ++i)
             if (free_list[i].len >= len) {
@@ -1343,6 +1346,51 @@ int esahrnet_debug_op_schedule(esahrnet_handle h, int index, int* wave, int* lan
     if (!h || !wave || !lane || index < 0 || index >= (int)h->ops.size()) return fail("debug_op_schedule: bad argument");
     *wave = h->ops[index].wave;
     *lane = h->ops[index].lane;
+    return 0;
+}
+
+// the plan ops that run at the planned shape: the head alternative the shape does not take is left out
+static std::vector<int> active_ops(const esahrnet_ctx& c) {
+    std::vector<int> idx;
+    for (size_t k = 0; k < c.ops.size(); ++k)
+        if (c.ops[k].alt == 0 || c.ops[k].alt == (c.sp.head2 ? 2 : 1)) idx.push_back((int)k);
+    return idx;
+}
+
+int esahrnet_debug_op_count(esahrnet_handle h, int n, int height, int width, int* count) {
+    if (!h || !count) return fail("debug_op_count: null argument");
+    if (plan_shape(*h, n, height, width)) return 1;
+    *count = (int)active_ops(*h).size();
+    return 0;
+}
+
+int esahrnet_debug_op_regions(esahrnet_handle h, int n, int height, int width, int k, esahrnet_debug_op* out) {
+    if (!h || !out) return fail("debug_op_regions: null argument");
+    if (plan_shape(*h, n, height, width)) return 1;
+    const std::vector<int> idx = active_ops(*h);
+    if (k < 0 || k >= (int)idx.size()) return fail("debug_op_regions: op %d out of range (%zu run at this shape)", k, idx.size());
+    const Op& o = h->ops[idx[k]];
+    memset(out, 0, sizeof *out);
+    out->index = idx[k]; out->wave = o.wave; out->lane = o.lane;
+    out->job = o.job >= 0 && h->sp.job_on[o.job] ? o.job : -1;
+    out->multi = o.multi >= 0 && h->sp.multi_on[o.multi] ? o.multi : -1;
+    // slice: by the op's KIND — resample_slice, zero_slice and the CBAM apply write at a channel offset into `out`; the apply of
+    // a BasicBlock fills its tensor alone (c0 = 0) and is flagged all the same.  The report is the PLAN, which is what the
+    // allocator sees, not the launches: an op that launches nothing at this shape (the CBAM maps inside cbam_spatial, a
+    // group member evaluated by its leader) is listed with the tensors the plan gives it.
+    const bool slice = o.kind == OP_APPLY || o.kind == OP_RESAMPLE || o.kind == OP_ZERO;
+    const int ts[ESAHRNET_DEBUG_MAX_REGIONS] = {o.in, o.res, o.terms[0], o.terms[1], o.terms[2], o.terms[3], o.out, o.out2};
+    // the pooled partials of the raw stem tensor have one writer per shape: the stem kernel, or the pooling step
+    const bool stem_pooled = stem_pools(*h, height, width) > 0;
+    for (int role = 0; role < ESAHRNET_DEBUG_MAX_REGIONS; ++role) {
+        if (ts[role] < 0) continue;
+        if (role == 7 && o.kind == OP_STEMRAW && !stem_pooled) continue;
+        if (role == 6 && o.kind == OP_POOL && o.out == h->stemraw_partial && stem_pooled) continue;
+        const Tensor& t = h->tensors[ts[role]];
+        esahrnet_debug_region& r = out->regions[out->nregions++];
+        r.tensor = ts[role]; r.role = role; r.write = role >= 6; r.slice = role == 6 && slice;
+        r.offset = t.off; r.bytes = tensor_bytes(*h, h->sp, t);
+    }
     return 0;
 }
 

@@ -115,7 +115,10 @@ int esahrnet_commit(esahrnet_handle h);
 int esahrnet_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes);
 
 /* x_dev: f32 [n][cin][height][width] NCHW contiguous (already normalised, data_load_val.py:86).
- * heat_dev: f32 [n][K][height][width] NCHW, fully overwritten.  x_dev is not modified. */
+ * heat_dev: f32 [n][K][height][width] NCHW, fully overwritten.  x_dev is not modified.
+ * ws_dev (here and in every entry point below that takes one): what it holds on entry is irrelevant — zeros, NaN bit patterns
+ * and the leftovers of another call give the same bits; what it holds on exit is unspecified; nothing outside
+ * [ws_dev, ws_dev + ws_bytes) and the documented outputs is written; inputs are not modified. */
 int esahrnet_forward(esahrnet_handle h, const void* x_dev, int n, int height, int width,
                      void* heat_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
 
@@ -373,6 +376,27 @@ int esahrnet_debug_set_launch_limit(long long bytes);
 /* Where launch `index` (0 .. esahrnet_launch_count-1) sits in the wave schedule: launches of one wave on different
  * lanes run concurrently (lane 0 = the caller's stream), waves one after another.  All zero on a one-lane handle. */
 int esahrnet_debug_op_schedule(esahrnet_handle h, int index, int* wave, int* lane);
+/* The workspace plan of a forward of (n, height, width), op by op, for a host check of the recycling (no device call: the
+ * plan is made on the host, as for esahrnet_workspace_bytes; follows esahrnet_set_debug_keep).  esahrnet_debug_op_count:
+ * the plan ops that run at that shape (the head alternative the shape does not take is left out), in launch order.
+ * esahrnet_debug_op_regions: op `k` of those — its index in the plan (esahrnet_debug_op_schedule's), wave and lane, the job
+ * group and multi-head group it is launched with AT THIS SHAPE (-1: a launch of its own; the members of a group are one
+ * launch, made at its first member), and every workspace tensor it touches: tensor id, role (0 in, 1 res, 2..5 terms[0..3],
+ * 6 out, 7 out2), write (roles 6, 7), slice (the output of an op kind that writes at a channel offset into an allocation
+ * other ops may fill too: resample_slice, zero_slice, every CBAM apply), byte offset in the workspace and byte length as the
+ * planner reserved it.  This is the plan as the allocator sees it: an op that launches nothing of its own at the shape (the
+ * CBAM maps formed inside cbam_spatial, a group member) is reported with the tensors the plan gives it. */
+#define ESAHRNET_DEBUG_MAX_REGIONS 8
+typedef struct esahrnet_debug_region {
+    int32_t tensor, role, write, slice;
+    uint64_t offset, bytes;
+} esahrnet_debug_region;
+typedef struct esahrnet_debug_op {
+    int32_t index, wave, lane, job, multi, nregions;
+    esahrnet_debug_region regions[ESAHRNET_DEBUG_MAX_REGIONS];
+} esahrnet_debug_op;
+int esahrnet_debug_op_count(esahrnet_handle h, int n, int height, int width, int* count);
+int esahrnet_debug_op_regions(esahrnet_handle h, int n, int height, int width, int k, esahrnet_debug_op* out);
 
 #ifdef __cplusplus
 }
