@@ -104,6 +104,8 @@ _SIGS = {
                                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "esahrnet_forward_keypoints_final2_hess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "esahrnet_keypoints_gaussfit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "esahrnet_correspondences": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
                                            C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "esahrnet_frames_correspondences_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -338,6 +338,13 @@ int launch_keypoints_final2_nhwc(int fmt, const char* x, int N, int C, int H, in
 int launch_keypoints_final2_hess(const float* heat, int planes, int H, int W, float* kp, int* idx_out, double* hess, void* ws,
                                  size_t ws_bytes, hipStream_t stream);
 
+// ---- the third decoder: a 2-D Gaussian fitted to the 13 x 13 window around the arg-max (keypoints_gaussfit.hip) -----------
+// launch_keypoints (unchanged: kp rows and the arg-max index), then gaussfit_kernel, one wave per plane: fit f64 [planes][8] =
+// (A, x0, y0, a, b, c, off, cost), status int32 [planes] (0 accepted, 1 / 2 / 3 rejected), hess f64 [planes][3] = (-2a, -2b,
+// -2c); fit, hess and idx_out may be null (without idx_out the index passes through status).  An accepted fit replaces x, y.
+int launch_keypoints_gaussfit(const float* heat, int planes, int H, int W, float* kp, int* idx_out, double* fit, int* status,
+                              double* hess, hipStream_t stream);
+
 // ---- crop + edge-pad + 8-bit bilinear resize + normalise: u8 frames -> f32 [N][1][S][S] (crops.hip) ----
 int launch_crops(const unsigned char* frames, const int* boxes, float* out, int N, int FH, int FW, int S,
                  float mean, float std_, hipStream_t s);

@@ -2283,6 +2283,25 @@ int esahrnet_keypoints_final2_hess(const void* heat_dev, int n, int k, int heigh
     return 0;
 }
 
+int esahrnet_keypoints_gaussfit(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev,
+                                void* fit_dev, void* status_dev, void* hess_dev, esahrnet_stream stream) {
+    if (!heat_dev || !kp_dev || !status_dev) return fail("keypoints_gaussfit: null argument");
+    if (n <= 0 || k <= 0 || height <= 0 || width <= 0 || (long long)height * width > 0x7fffffffLL ||
+        (long long)n * k > 0x7fffffffLL)
+        return fail("keypoints_gaussfit: bad shape %d x %d x %d x %d", n, k, height, width);
+    if ((reinterpret_cast<uintptr_t>(heat_dev) | reinterpret_cast<uintptr_t>(kp_dev) | reinterpret_cast<uintptr_t>(idx_dev) |
+         reinterpret_cast<uintptr_t>(status_dev)) & 3)
+        return fail("keypoints_gaussfit: heat_dev, kp_dev, idx_dev and status_dev must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(fit_dev) | reinterpret_cast<uintptr_t>(hess_dev)) & 7)
+        return fail("keypoints_gaussfit: fit_dev and hess_dev must be 8-byte aligned");
+    const int rc = esa::launch_keypoints_gaussfit(static_cast<const float*>(heat_dev), n * k, height, width,
+                                                  static_cast<float*>(kp_dev), static_cast<int*>(idx_dev),
+                                                  static_cast<double*>(fit_dev), static_cast<int*>(status_dev),
+                                                  static_cast<double*>(hess_dev), static_cast<hipStream_t>(stream));
+    if (rc) return fail("keypoints_gaussfit: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
 int esahrnet_keypoints(const void* heat_dev, int n, int k, int height, int width, void* kp_dev,
                        esahrnet_stream stream) {
     return esahrnet_keypoints_ex(heat_dev, n, k, height, width, kp_dev, nullptr, stream);

@@ -27,7 +27,7 @@ import torch.nn as nn
 
 from . import _lib, crops
 from .fold import fold_conv
-from .inference import check_refine, check_weights, pack_correspondences
+from .inference import check_refine, check_weights, gaussfit_keypoints, pack_correspondences
 
 logger = logging.getLogger(__name__)
 BN_MOMENTUM = 0.01           # models/seg_hrnet.py:23 (irrelevant at inference, kept for parity)
@@ -219,6 +219,16 @@ class HighResolutionNet(nn.Module):
             raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
                                "(the reference callers do, val.py:95 / demo.py:80)")
         return self._rt.forward_final2(self, x0, True, want_hessian=True)
+
+    def keypoints_gaussfit(self, x0: torch.Tensor, return_fit: bool = False):
+        """The forward, then the Gaussian-fit decoder on its heat-maps (inference.gaussfit_keypoints; include/esahrnet.h
+        esahrnet_keypoints_gaussfit): -> (kp f32 [N,K,3], status int32 [N,K], hess f64 [N,K,3] = (-2a, -2b, -2c)), or with
+        return_fit=True (kp, fit f64 [N,K,8], status, hess); bit-identical to inference.gaussfit_keypoints(net(x)).  The
+        heat-maps live in a temporary tensor of the forward's stream (the decoder is not fused into the forward)."""
+        if self.training:
+            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
+                               "(the reference callers do, val.py:95 / demo.py:80)")
+        return self._rt.forward_gaussfit(self, x0, bool(return_fit))
 
     def _frames_to_keypoints(self, frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format):
         """frames_to_keypoints, plus (idx int32 [m,K], packed): every output is a view of `packed` (one uint8 buffer), so a
@@ -560,6 +570,16 @@ class _Runtime:
         ws.record_stream(ts)
         x.record_stream(ts)
         return (kp, idx, hess) if want_hessian else (kp, idx)
+
+    def forward_gaussfit(self, module, x0, want_fit):
+        """forward(), then esahrnet_keypoints_gaussfit on the heat-maps, enqueued behind it on the caller's current stream of
+        the input's device.  forward() brings the device lock, the workspace and the record_stream handling; the heat-map
+        tensor is a temporary allocated under that same stream, so it needs no record_stream of its own.  forward() also
+        leaves the per-tile maxima beside the heat-maps, which this decoder does not read (its entry point sweeps the planes
+        with the arg-max kernel): work a fused form would save, and that form is not built."""
+        heat = self.forward(module, x0)
+        kp, fit, status, hess = gaussfit_keypoints(heat)
+        return (kp, fit, status, hess) if want_fit else (kp, status, hess)
 
     def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None):
         """esahrnet_frames_keypoints (arguments already checked by crops.check_device_loader_args).  The outputs are views

@@ -110,6 +110,52 @@ def heatmaps_to_keypoints(heat: torch.Tensor, refine: str = "get_final", return_
     return (out[0], out[2]) if return_hessian else out[0]
 
 
+def gaussfit_keypoints(heat: torch.Tensor):
+    """The third decoder (include/esahrnet.h esahrnet_keypoints_gaussfit): offset + A exp(-(a dx^2 + 2 b dx dy + c dy^2)) fitted
+    on the device to the 13 x 13 window around each plane's arg-max, the fit the reference's test.py makes with curve_fit.
+    f32 cuda [N,K,H,W] -> (kp f32 [N,K,3] = (x0, y0, raw peak); fit f64 [N,K,8] = (A, x0, y0, a, b, c, off, cost); status int32
+    [N,K], 0 = accepted; hess f64 [N,K,3] = (-2a, -2b, -2c)).  A rejected keypoint (status 1, 2, 3) keeps the get_final row of
+    heatmaps_to_keypoints, its fit and hess are NaN.  hess is what keypoints_to_correspondences(weights="hessian") takes."""
+    if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
+        raise ValueError("expected a 4-D tensor [N, K, H, W]")
+    if not heat.is_cuda:
+        raise RuntimeError("gaussfit_keypoints runs on the GPU only (no CPU fallback)")
+    if heat.dtype != torch.float32:
+        raise TypeError(f"expected float32 heatmaps, got {heat.dtype}")
+    heat = heat.contiguous()
+    n, k, h, w = heat.shape
+    dev = heat.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        kp = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
+        fit = torch.empty((n, k, 8), dtype=torch.float64, device=dev)
+        status = torch.empty((n, k), dtype=torch.int32, device=dev)
+        hess = torch.empty((n, k, 3), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().esahrnet_keypoints_gaussfit(heat.data_ptr(), n, k, h, w, kp.data_ptr(), None, fit.data_ptr(),
+                                                          status.data_ptr(), hess.data_ptr(), C.c_void_p(stream)))
+    return kp, fit, status, hess
+
+
+def gaussfit_sigma_theta(fit):
+    """fit [..., 8] (tensor or array) of gaussfit_keypoints -> (sigma_x, sigma_y, theta) as numpy f64 arrays: the parameters of
+    the reference's test.py twoD_Gaussian, which reproduce the fitted function when put into it with (A, x0, y0, off):
+        a = cos^2 th / (2 sx^2) + sin^2 th / (2 sy^2),  b = -sin 2th / (4 sx^2) + sin 2th / (4 sy^2),  c = sin^2 th / (2 sx^2) + ...
+    Of the equivalent triples the one with sigma_x >= sigma_y and theta in (-pi/2, pi/2] is returned.  test.py's sign of b makes
+    its theta the NEGATIVE of the counter-clockwise angle (x right, y down the rows) of the sigma_x axis: the long axis points
+    along (cos theta, -sin theta).  theta is undetermined when the two sigmas are equal (0 or pi/2 is returned).  NaN for a
+    rejected fit."""
+    f = fit.detach().cpu().numpy() if isinstance(fit, torch.Tensor) else np.asarray(fit)
+    a, b, c = f[..., 3].astype(np.float64), f[..., 4].astype(np.float64), f[..., 5].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        half, rad = 0.5 * (a + c), np.hypot(0.5 * (a - c), b)
+        sx, sy = np.sqrt(0.5 / (half - rad)), np.sqrt(0.5 / (half + rad))
+        # eigenvector of the SMALLER eigenvalue (the long axis): (b, l - a) or (l - c, b), whichever is better conditioned
+        l = half - rad
+        th = -np.where(a > c, np.arctan2(l - a, b), np.arctan2(b, l - c))      # test.py's sign
+        th = np.where(th > np.pi / 2, th - np.pi, np.where(th <= -np.pi / 2, th + np.pi, th))
+    return sx, sy, th
+
+
 WEIGHTS = ("peak", "hessian")
 
 

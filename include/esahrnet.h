@@ -154,6 +154,34 @@ int esahrnet_keypoints_final2(const void* heat_dev, int n, int k, int height, in
 int esahrnet_keypoints_final2_hess(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev,
                                    void* hess_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
 
+/* ---- the third decoder: a 2-D Gaussian fitted around each peak ----------------------------------------------------------
+ * The decoder the reference's test.py sketches with scipy.optimize.curve_fit: g = off + A exp(-(a dx^2 + 2 b dx dy + c dy^2)),
+ * test.py's family parametrised by (a, b, c) instead of (sigma_x, sigma_y, theta), fitted to the pixels within 6 px of the
+ * integer arg-max in x and in y (at most 13 x 13, clipped to the plane), one wave per plane (csrc/keypoints_gaussfit.hip).
+ * esahrnet_keypoints_ex's kernel is enqueued first, unchanged; then the fit: start off = window minimum, A = peak - off,
+ * centre = arg-max, a = c = 1/8, b = 0; Levenberg-Marquardt in f64 (lambda 1e-3, x 4 on a rejected step, / 3 with floor 1e-9
+ * on an accepted one, at most 10 tries per iteration and 50 iterations, stop at a relative cost decrease below 1e-14); sums
+ * in a fixed order, so that a plane's result does not depend on its batch.
+ *   status_dev int32 [n][k]  0: accepted — every parameter and the cost finite, A > 0, a > 0, a c - b^2 > 0, and the centre
+ *                            inside the window (its first to its last pixel centre, in x and in y); 1: the solver ended on a
+ *                            parameter or a cost that is not finite; 2: finite, but one of the other rules fails (a constant
+ *                            plane: A = 0); 3: a value in the window that is not finite (a NaN peak included).
+ *   kp_dev f32 [n][k][3]     accepted: (x0, y0, raw peak); rejected: the row of esahrnet_keypoints_ex, bit for bit.  The peak
+ *                            is the raw maximum either way, so the selection of keypoints does not change.
+ *   idx_dev int32 [n][k]     as esahrnet_keypoints_ex writes it (NULL: not written; the fit needs the index, which then passes
+ *                            through status_dev: the first kernel leaves it there, the fit reads it and stores the status).
+ *   fit_dev f64 [n][k][8]    (A, x0, y0, a, b, c, off, cost), cost the sum of squared residuals; NaN x 8 when rejected (NULL:
+ *                            not written).
+ *   hess_dev f64 [n][k][3]   (-2a, -2b, -2c), NaN x 3 when rejected (NULL: not written).  For this model the inverse
+ *                            covariance of the blob is 2 [[a, b], [b, c]], so hess_dev is, as it stands, the hess_dev of
+ *                            esahrnet_correspondences(mode 1): w = rate (-H)^(1/2).
+ * No workspace.  Allocates nothing, does not synchronise, may be captured into a graph; argument errors (NULL heat_dev, kp_dev
+ * or status_dev, a shape that is not positive, a pointer that is not aligned to its element) are reported before anything is
+ * enqueued. */
+int esahrnet_keypoints_gaussfit(const void* heat_dev, int n, int k, int height, int width,
+                                void* kp_dev, void* idx_dev, void* fit_dev, void* status_dev,
+                                void* hess_dev, esahrnet_stream stream);
+
 /* ---- forward + keypoints without re-reading the heat-maps -------------------------------------------------
  * The output-layer kernel can leave, beside the heat-maps, the first row-major maximum of each of its tiles:
  * part_dev = 8 bytes x [n * K][ntiles] (f32 value, int32 index row * width + column).  esahrnet_keypoints_finish reduces
