@@ -2694,4 +2694,58 @@ int esahrnet_op_cbam(const void* x_dev, const void* res_dev, int n, int c, int h
     return 0;
 }
 
+// the slice kernels' formats (precisions 0, 1, 2): format code, and a channel count padded as that format pads it
+static int slice_fmt(int precision) { return precision == 1 ? esa::FMT_BF : precision == 2 ? esa::FMT_F32 : esa::FMT_SB; }
+static int slice_pad(int precision, int c) { return precision == 1 ? pad64(c) : pad32(c); }
+
+int esahrnet_op_resample(const void* x_dev, int n, int c, int h, int w, void* y_dev, int cy, int c0, int height, int width,
+                         int align, int precision, esahrnet_stream stream_) {
+    if (!x_dev || !y_dev || n <= 0 || c <= 0 || cy <= 0 || h <= 0 || w <= 0 || height <= 0 || width <= 0) return fail("op_resample: bad argument");
+    if (precision < 0 || precision > 2) return fail("op_resample: precision %d (resample_slice serves 0, 1 and 2)", precision);
+    const int fmt = slice_fmt(precision), eb = precision == 1 ? 2 : 4, cp = slice_pad(precision, c), cyp = slice_pad(precision, cy);
+    const int cw = (c + 7) & ~7;        // the kernel writes whole 8-channel groups
+    if (c0 < 0 || (c0 & 7)) return fail("op_resample: c0=%d is not a multiple of 8", c0);
+    if (c0 + cw > cyp) return fail("op_resample: slice [%d, %d) outside the %d channels of y", c0, c0 + cw, cyp);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    void *xs = nullptr, *ys = nullptr;
+    auto cleanup = [&]() { for (void* p : {xs, ys}) if (p) (void)hipFree(p); };
+    if (hipMalloc(&xs, (size_t)n * h * w * cp * eb) != hipSuccess || hipMalloc(&ys, (size_t)n * height * width * cyp * eb) != hipSuccess) {
+        cleanup();
+        return fail("op_resample: hipMalloc failed");
+    }
+    int rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(x_dev), n, c, h, w, static_cast<char*>(xs), cp, stream);
+    if (!rc) rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(y_dev), n, cy, height, width, static_cast<char*>(ys), cyp, stream);
+    esa::ResampleParams p{};
+    p.x = static_cast<const char*>(xs); p.y = static_cast<char*>(ys); p.N = n; p.h = h; p.w = w; p.H = height; p.W = width;
+    p.C = c; p.Cp_src = cp; p.y_pix_bytes = cyp * eb; p.y_c0 = c0; p.align = align ? 1 : 0; p.fmt = fmt;
+    if (!rc) rc = esa::launch_resample_slice(p, stream);
+    if (!rc) rc = esa::launch_fmt_to_nchw(fmt, static_cast<const char*>(ys), n, cy, height, width, cyp, static_cast<float*>(y_dev), stream);
+    hipError_t se = hipStreamSynchronize(stream);
+    cleanup();
+    if (rc) return fail("op_resample: launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (se != hipSuccess) return fail("op_resample: %s", hipGetErrorString(se));
+    return 0;
+}
+
+int esahrnet_op_zero_slice(void* y_dev, int n, int cy, int height, int width, int c0, int nchan, int precision,
+                           esahrnet_stream stream_) {
+    if (!y_dev || n <= 0 || cy <= 0 || height <= 0 || width <= 0) return fail("op_zero_slice: bad argument");
+    if (precision < 0 || precision > 2) return fail("op_zero_slice: precision %d (zero_slice serves 0, 1 and 2)", precision);
+    const int fmt = slice_fmt(precision), eb = precision == 1 ? 2 : 4, cyp = slice_pad(precision, cy);
+    if (c0 < 0 || (c0 & 7) || nchan <= 0 || (nchan & 7)) return fail("op_zero_slice: c0=%d, nchan=%d must be multiples of 8", c0, nchan);
+    if (nchan > cyp - c0) return fail("op_zero_slice: slice [%d, %d) outside the %d channels of y", c0, c0 + nchan, cyp);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    void* ys = nullptr;
+    const long long npix = (long long)n * height * width;
+    if (hipMalloc(&ys, (size_t)npix * cyp * eb) != hipSuccess) return fail("op_zero_slice: hipMalloc failed");
+    int rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(y_dev), n, cy, height, width, static_cast<char*>(ys), cyp, stream);
+    if (!rc) rc = esa::launch_zero_slice(static_cast<char*>(ys), npix, cyp * eb, c0, nchan, stream, fmt);
+    if (!rc) rc = esa::launch_fmt_to_nchw(fmt, static_cast<const char*>(ys), n, cy, height, width, cyp, static_cast<float*>(y_dev), stream);
+    hipError_t se = hipStreamSynchronize(stream);
+    (void)hipFree(ys);
+    if (rc) return fail("op_zero_slice: launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (se != hipSuccess) return fail("op_zero_slice: %s", hipGetErrorString(se));
+    return 0;
+}
+
 }  // extern "C"

@@ -393,6 +393,19 @@ int esahrnet_op_fuse_ex(const void* const* xs_dev, const int* hs, const int* ws,
 int esahrnet_op_cbam(const void* x_dev, const void* res_dev, int n, int c, int height, int width, const float* w_fc0,
                      const float* w_fc2, const float* w_sa, int relu, void* y_dev, int cy, int c0, int fused, int precision,
                      esahrnet_stream stream);
+/* resample_slice on its own, in the format of `precision` (0, 1 or 2; 3 is refused: the kernel does not serve fp16):
+ * y[:, c0 : c0 + c] = bilinear(x -> (height, width)) under F.interpolate's rule for align (0: align_corners=False, 1: True);
+ * h == height and w == width is the copy path.  x_dev: f32 NCHW [n][c][h][w]; y_dev: f32 NCHW [n][cy][height][width], read
+ * and written back whole as esahrnet_op_cbam does: channels outside the slice come back as they went in.  The kernel writes
+ * whole 8-channel groups: with c not a multiple of 8 the channels c0 + c .. c0 + 8*ceil(c/8) - 1 of y receive the source's
+ * channel padding (zeros).  c0 a multiple of 8, c0 + 8*ceil(c/8) <= cy padded (32; bf16: 64); checked before anything is
+ * enqueued.  Synchronous; test use only. */
+int esahrnet_op_resample(const void* x_dev, int n, int c, int h, int w, void* y_dev, int cy, int c0, int height, int width,
+                         int align, int precision, esahrnet_stream stream);
+/* zero_slice on its own, the same round trip of y_dev (f32 NCHW [n][cy][height][width]): y[:, c0 : c0 + nchan] = +0, the
+ * rest comes back as it went in.  c0 and nchan multiples of 8, c0 + nchan <= cy padded; precision 0, 1 or 2. */
+int esahrnet_op_zero_slice(void* y_dev, int n, int cy, int height, int width, int c0, int nchan, int precision,
+                           esahrnet_stream stream);
 
 /* ---- test hooks ------------------------------------------------------------------------------------ */
 /* Launch state is kept per DEVICE (dynamic-LDS limits raised per kernel and device, CU counts), never in
