@@ -19,7 +19,7 @@ SOURCES = ["conv_mfma.hip", "conv_s2c32.hip", "conv_x6.hip", "conv1x1.hip", "cor
 PER_FILE_FLAGS = {"conv_x6.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                   # frontend.hip restates Python's box arithmetic: int(c0 - 1.05 * size) must see the rounded product
                   "frontend.hip": ["-ffp-contract=off"]}
-HEADERS = ["kernels.h", "correspond.h", "final2.h", "refine.h", "sb.h", "conv_cfg.h", "devstate.h", os.path.join("..", "..", "include", "esahrnet.h")]
+HEADERS = ["kernels.h", "correspond.h", "final2.h", "gaussfit.h", "refine.h", "sb.h", "conv_cfg.h", "devstate.h", os.path.join("..", "..", "include", "esahrnet.h")]
 
 
 def _hipcc() -> str:

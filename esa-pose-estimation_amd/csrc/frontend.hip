@@ -123,6 +123,25 @@ __global__ __launch_bounds__(256) void mark_invalid_kernel(const int* valid, int
     if (idx) idx[t] = -1;
 }
 
+// mark_invalid_kernel for esahrnet_frames_keypoints_gaussfit: the decoder's other outputs too
+__global__ __launch_bounds__(256) void mark_invalid_gaussfit_kernel(const int* valid, int m, int K, float* kp, int* idx, double* fit,
+                                                                    int* status, double* hess) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m * K) return;
+    if (valid[t / K]) return;
+    const float nan = __int_as_float(0x7fc00000);
+    const double dnan = __longlong_as_double(0x7ff8000000000000LL);
+    kp[(size_t)t * 3 + 0] = nan;
+    kp[(size_t)t * 3 + 1] = nan;
+    kp[(size_t)t * 3 + 2] = nan;
+    if (idx) idx[t] = -1;
+    if (fit)
+        for (int i = 0; i < 8; ++i) fit[(size_t)t * 8 + i] = dnan;
+    if (hess)
+        for (int i = 0; i < 3; ++i) hess[(size_t)t * 3 + i] = dnan;
+    status[t] = -1;
+}
+
 }  // namespace
 
 int launch_boxes(const int* det, const int* frame_idx, int nframes, int m, int FH, int FW, int S, int rule, int* crop,
@@ -150,6 +169,14 @@ int launch_mark_invalid(const int* valid, int m, int K, float* kp, int* idx, hip
     if (m <= 0 || K <= 0 || (long long)m * K > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(mark_invalid_kernel, dim3((unsigned)(((long long)m * K + 255) / 256)), dim3(256), 0, s, valid, m, K, kp,
                        idx);
+    return (int)hipGetLastError();
+}
+
+int launch_mark_invalid_gaussfit(const int* valid, int m, int K, float* kp, int* idx, double* fit, int* status, double* hess,
+                                 hipStream_t s) {
+    if (m <= 0 || K <= 0 || (long long)m * K > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(mark_invalid_gaussfit_kernel, dim3((unsigned)(((long long)m * K + 255) / 256)), dim3(256), 0, s, valid, m, K,
+                       kp, idx, fit, status, hess);
     return (int)hipGetLastError();
 }
 

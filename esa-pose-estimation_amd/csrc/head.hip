@@ -10,6 +10,7 @@
 // for the 11-keypoint variant: 0.5 % of the network.  Not HBM-write-bound: without its stores (the keypoints-only form) it is
 // no faster.
 #include "devstate.h"
+#include "gaussfit.h"
 #include "kernels.h"
 #include "refine.h"
 #include "sb.h"
@@ -484,6 +485,57 @@ __global__ __launch_bounds__(64) void final2_valu_finish_kernel(FinalParams p, i
         [&] { return win[(R / 2) * R + R / 2]; }, kp, idx_out, plane, hess);
 }
 
+// ---- the Gaussian-fit decoder without heat-maps, VALU output layer (esahrnet_forward_keypoints_gaussfit) ------------------
+// final_gf_finish_kernel: one wave per heat-map, behind final_kernel<KT, RPT, true>.  The first maximum over the tile maxima,
+// then the output layer again at the 13 x 13 pixels around it (the fit's window before it is clipped to the plane; 15 x 15
+// staged inputs, 8 concat channels at a time as final2_valu_finish_kernel stages them) with final_kp_finish_kernel's
+// arithmetic: the same staging functions, zeros outside the crop, acc = bias[k], one fma per (channel, tap), channel-major.  The
+// values stay in LDS: lane 0 writes the get_final row from them (refine_keypoint reads +-2 around the peak), then
+// gaussfit.h's solver reads its window from them.  Values at positions outside the plane are computed and never read.  kp /
+// idx / fit / status / hess bit-identical to launch_final (VALU) followed by launch_keypoints_gaussfit.
+__global__ __launch_bounds__(64) void final_gf_finish_kernel(FinalParams p, int kt, int ntiles, float* kp, int* idx_out, double* fit,
+                                                             int* status, double* hess) {
+    constexpr int R = 2 * GF_R + 1, S = R + 2;
+    __shared__ float stg[8 * S * S];
+    __shared__ float win[R * R];
+    const int plane = blockIdx.x, n = plane / p.K, k = plane - n * p.K, lane = threadIdx.x;
+    float bv;
+    int bi;
+    reduce_tile_maxima(p.part + (size_t)plane * ntiles, ntiles, bv, bi);
+    if (bi == 0x7fffffff) bi = 0;                          // all -inf plane
+    const int px = bi % p.W, py = bi / p.W, wy0 = py - GF_R, wx0 = px - GF_R;
+    const float sc_y = final_scale(p.h, p.H), sc_x = final_scale(p.wd, p.W);
+    const int G = (p.K + 7) >> 3;
+    float acc[GF_SLOTS];
+#pragma unroll
+    for (int j = 0; j < GF_SLOTS; ++j) acc[j] = p.bias[k];
+    for (int g = 0; g <= G; ++g) {
+        const int c0 = g < G ? 8 * g : p.K, nc = g < G ? min(8, p.K - 8 * g) : p.cin;
+        __syncthreads();
+        final2_stage_chunk<S, 64>(p, n, g, G, wy0 - 1, wx0 - 1, sc_y, sc_x, stg, lane);
+        __syncthreads();
+        for (int i = 0; i < nc; ++i) {
+            const float* sp = stg + i * S * S;
+            const float* wp = p.w + (size_t)(c0 + i) * 9 * kt;
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+                for (int j = 0; j < GF_SLOTS; ++j) {
+                    const int q = min(lane + 64 * j, R * R - 1);
+                    acc[j] = fmaf(sp[(q / R + tap / 3) * S + q % R + tap % 3], wp[tap * kt + k], acc[j]);
+                }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < GF_SLOTS; ++j) {
+        const int q = lane + 64 * j;
+        if (q < R * R) win[q] = acc[j];
+    }
+    __syncthreads();
+    auto at = [&](int yy, int xx) { return win[(yy - wy0) * R + (xx - wx0)]; };
+    if (lane == 0) refine_keypoint(at, p.H, p.W, bi, kp + (size_t)plane * 3, idx_out ? idx_out + plane : nullptr);
+    gaussfit_plane(at, (size_t)plane, p.H, p.W, bi, kp, fit, status, hess);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // Matrix-core version of the same op.  The contraction index is (tap, channel) with the K+cin concat
@@ -786,6 +838,24 @@ int launch_final_kp(const FinalParams& p, float* kp, int* idx_out, hipStream_t s
     }
     if (rc) return rc;
     hipLaunchKernelGGL(final_kp_finish_kernel, dim3((unsigned)planes), dim3(64), 0, stream, p, kt, ntiles, kp, idx_out);
+    return (int)hipGetLastError();
+}
+
+int launch_final_gf(const FinalParams& p, float* kp, int* idx_out, double* fit, int* status, double* hess, hipStream_t stream) {
+    const int ntiles = final_kp_tiles(p.K, p.cin, p.H, p.W), kt = final_kt(p.K);
+    const long long planes = (long long)p.N * p.K;
+    if (!p.part || !kp || !status || ntiles <= 0 || kt < 0 || p.cin < 0 || p.cin > 8 || planes > 0x7fffffffLL ||
+        (long long)p.H * p.W > 0x7fffffffLL)
+        return (int)hipErrorInvalidValue;
+    int rc = (int)hipErrorInvalidValue;
+    switch (kt) {
+        case 11: rc = launch_final_t<11, true>(p, stream); break;
+        case 16: rc = launch_final_t<16, true>(p, stream); break;
+        case 32: rc = launch_final_t<32, true>(p, stream); break;
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(final_gf_finish_kernel, dim3((unsigned)planes), dim3(64), 0, stream, p, kt, ntiles, kp, idx_out, fit, status,
+                       hess);
     return (int)hipGetLastError();
 }
 

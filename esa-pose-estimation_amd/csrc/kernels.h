@@ -171,6 +171,10 @@ int launch_final(const FinalParams& p, hipStream_t stream);
 // [N*K] or nullptr, bit-identical to launch_final (VALU) + launch_keypoints; p.out is not used
 int final_kp_tiles(int K, int cin, int H, int W);
 int launch_final_kp(const FinalParams& p, float* kp, int* idx_out, hipStream_t stream);
+// the Gaussian-fit decoder without heat-maps, VALU output layer (final_kernel<KT, RPT, true> + final_gf_finish_kernel): kp, idx_out
+// (may be null), fit f64 [N*K][8] (may be null), status int32 [N*K], hess f64 [N*K][3] (may be null) bit-identical to launch_final
+// (VALU) + launch_keypoints_gaussfit; p.part: [N*K][final_kp_tiles], p.out not used; cin <= 8
+int launch_final_gf(const FinalParams& p, float* kp, int* idx_out, double* fit, int* status, double* hess, hipStream_t stream);
 // get_final2 keypoints without heat-maps, VALU output layer (final2_valu_kernel + final2_valu_finish_kernel): kp / idx_out
 // bit-identical to launch_final (VALU) + launch_keypoints_final2; p.part and bmax: [N*K][final2_valu_tiles] records, p.out
 // not used; cin <= 8
@@ -344,6 +348,12 @@ int launch_keypoints_final2_hess(const float* heat, int planes, int H, int W, fl
 // -2c); fit, hess and idx_out may be null (without idx_out the index passes through status).  An accepted fit replaces x, y.
 int launch_keypoints_gaussfit(const float* heat, int planes, int H, int W, float* kp, int* idx_out, double* fit, int* status,
                               double* hess, hipStream_t stream);
+// the fit alone (gaussfit_kernel): idx_in int32 [planes] and the kp rows as launch_keypoints / launch_keypoints_finish left them
+int launch_gaussfit_fit(const float* heat, const int* idx_in, int planes, int H, int W, float* kp, double* fit, int* status,
+                        double* hess, hipStream_t stream);
+// the fit alone on NHWC heat-maps x [N][H][W][Cp] (fmt FMT_SB or FMT_F32) behind launch_keypoints_finish_nhwc; planes = N * C
+int launch_gaussfit_fit_nhwc(int fmt, const char* x, int N, int C, int H, int W, int Cp, const int* idx_in, float* kp, double* fit,
+                             int* status, double* hess, hipStream_t stream);
 
 // ---- crop + edge-pad + 8-bit bilinear resize + normalise: u8 frames -> f32 [N][1][S][S] (crops.hip) ----
 int launch_crops(const unsigned char* frames, const int* boxes, float* out, int N, int FH, int FW, int S,
@@ -362,6 +372,10 @@ int launch_crops_ex(const unsigned char* frames, int nframes, int FH, int FW, in
                     const int* valid, float* out, int m, int S, float mean, float std_, hipStream_t s);
 // kp f32 [m][K][3] -> NaN and idx int32 [m][K] (may be null) -> -1 in the rows with valid[i] == 0
 int launch_mark_invalid(const int* valid, int m, int K, float* kp, int* idx, hipStream_t s);
+// the same for the Gaussian-fit decoder's outputs: also fit f64 [m][K][8] and hess f64 [m][K][3] (may be null) -> NaN, status
+// int32 [m][K] -> -1
+int launch_mark_invalid_gaussfit(const int* valid, int m, int K, float* kp, int* idx, double* fit, int* status, double* hess,
+                                 hipStream_t s);
 
 // ---- keypoints -> the record the pose solver consumes (correspond.hip, correspond.h) ----------------------------------
 // kp f32 [m][K][3], hess f64 [m][K][3] (mode 1; may be null in mode 0), crop / rates / valid as launch_boxes wrote them ->

@@ -1640,6 +1640,12 @@ struct Buffers {
     size_t kws = 0;
     // esahrnet_forward_keypoints_final2_hess: f64 [n * K][3], the Hessian each get_final2 step used (nullptr: not asked for)
     double* hess = nullptr;
+    // esahrnet_forward_keypoints_gaussfit: the same scratch as esahrnet_forward_keypoints, decoded with the Gaussian fit.  status
+    // int32 [n * K] (never null then), fit f64 [n * K][8] and hess f64 [n * K][3] (may be null); without idx the arg-max index
+    // passes through status
+    bool gaussfit = false;
+    double* fit = nullptr;
+    int* status = nullptr;
 };
 
 // What esahrnet_forward_keypoints keeps behind the forward's workspace (at ShapePlan::bytes, a multiple of 256): the per-tile
@@ -1802,7 +1808,17 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             const bool f32 = c.tensors[o.in].f32;       // (bf16 mode: the output layer's f32 heat-maps)
             const int fmt = f32 ? esa::FMT_F32 : c.opt.fmt;
             if (desc) plain(f32 ? "f32_to_nchw" : "sb_to_nchw");
-            else if (b.kp && b.final2)                  // esahrnet_forward_keypoints_final2: get_final2 on the NHWC maps
+            else if (b.kp && b.gaussfit) {              // esahrnet_forward_keypoints_gaussfit: maxima, refine and fit on the NHWC maps
+                const int K = c.cfg.num_keypoints, Cp = c.tensors[o.in].Cp;
+                int* const idx = b.idx ? b.idx : b.status;
+                rc = esa::launch_tile_max(fmt, T(o.in), n, K, height, width, Cp, b.kpart, stream);
+                if (!rc)
+                    rc = esa::launch_keypoints_finish_nhwc(fmt, T(o.in), n, K, height, width, Cp, b.kpart,
+                                                           esa::to_nchw_part_tiles(height, width), b.kp, idx, stream);
+                if (!rc)
+                    rc = esa::launch_gaussfit_fit_nhwc(fmt, T(o.in), n, K, height, width, Cp, idx, b.kp, b.fit, b.status, b.hess,
+                                                       stream);
+            } else if (b.kp && b.final2)                // esahrnet_forward_keypoints_final2: get_final2 on the NHWC maps
                 rc = esa::launch_keypoints_final2_nhwc(fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
                                                        b.kp, b.idx, b.kpart, b.kws, stream, b.hess);
             else if (b.kp) {                            // esahrnet_forward_keypoints: maxima and refine on the NHWC maps
@@ -2042,6 +2058,19 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 describe(desc, c.hf() ? "final_kernel<fp16>" : "final_kernel", "%s", s.name.c_str());
                 desc->flops = 2.0 * n * height * width * s.cout * s.cin * 9;
                 desc->bytes = tbytes(o.in) + (double)n * height * width * (c.cfg.cin + s.cout) * 4;
+            } else if (b.kp && b.gaussfit && !c.final_wpk) { // esahrnet_forward_keypoints_gaussfit, VALU: no heat-maps at all
+                p.out = nullptr;
+                p.part = b.kpart;
+                rc = esa::launch_final_gf(p, b.kp, b.idx, b.fit, b.status, b.hess, stream);
+            } else if (b.kp && b.gaussfit) {            // ... matrix-core: heat-maps and maxima into the scratch, then the fit on them
+                int* const idx = b.idx ? b.idx : b.status;
+                p.out = b.kheat;
+                p.part = b.kpart;
+                rc = esa::launch_final(p, stream);
+                if (!rc)
+                    rc = esa::launch_keypoints_finish(p.out, p.part, esa::final_part_tiles(p.K, p.cin, height, width), n * p.K,
+                                                      height, width, b.kp, idx, stream);
+                if (!rc) rc = esa::launch_gaussfit_fit(p.out, idx, n * p.K, height, width, b.kp, b.fit, b.status, b.hess, stream);
             } else if (b.kp && b.final2 && !c.final_wpk) {   // esahrnet_forward_keypoints_final2, VALU: the blurring output layer
                 p.out = nullptr;
                 p.part = b.kpart;
@@ -2071,11 +2100,12 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
     return 0;
 }
 
-// kp_dev != nullptr: esahrnet_forward_keypoints, or with final2 esahrnet_forward_keypoints_final2 (heat_dev and part_dev unused)
+// kp_dev != nullptr: esahrnet_forward_keypoints, or with final2 esahrnet_forward_keypoints_final2, or with status_dev
+// esahrnet_forward_keypoints_gaussfit (heat_dev and part_dev unused)
 static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, int width,
                        void* heat_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream_,
                        hipEvent_t* events, void* part_dev = nullptr, void* kp_dev = nullptr, void* idx_dev = nullptr,
-                       bool final2 = false, void* hess_dev = nullptr) {
+                       bool final2 = false, void* hess_dev = nullptr, void* fit_dev = nullptr, void* status_dev = nullptr) {
     if (!h || !x_dev || !(heat_dev || kp_dev) || !ws_dev) return fail("forward: null argument");
     if (!h->committed) return fail("forward: esahrnet_commit has not been called");
     if (plan_shape(*h, n, height, width)) return 1;
@@ -2093,7 +2123,10 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
         bufs.final2 = final2;
         bufs.kbmax = reinterpret_cast<float*>(bufs.ws + h->sp.bytes + ks.heat + ks.part);
         bufs.kws = ks.part;
-        bufs.hess = final2 ? static_cast<double*>(hess_dev) : nullptr;
+        bufs.gaussfit = status_dev != nullptr;
+        bufs.fit = static_cast<double*>(fit_dev);
+        bufs.status = static_cast<int*>(status_dev);
+        bufs.hess = final2 || status_dev ? static_cast<double*>(hess_dev) : nullptr;
     }
     int op_index = 0;
     if (events && hipEventRecord(events[0], stream) != hipSuccess) return fail("forward: hipEventRecord failed");
@@ -2232,6 +2265,32 @@ int esahrnet_forward_keypoints_final2_hess(esahrnet_handle h, const void* x_dev,
     if (!h || !kp_dev) return fail("forward_keypoints_final2_hess: null argument");
     return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev, true,
                        hess_dev);
+}
+
+int esahrnet_keypoints_gaussfit_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
+    if (!h || !bytes) return fail("keypoints_gaussfit_forward_workspace_bytes: null argument");
+    return esahrnet_keypoints_workspace_bytes(h, n, height, width, bytes);      // the scratch of esahrnet_forward_keypoints
+}
+
+// what esahrnet_forward_keypoints_gaussfit and the loader in front of it refuse about the decoder's outputs
+static int check_gaussfit_outputs(const char* who, const esahrnet_ctx& c, const void* kp_dev, const void* idx_dev, const void* fit_dev,
+                                  const void* status_dev, const void* hess_dev) {
+    if ((reinterpret_cast<uintptr_t>(kp_dev) | reinterpret_cast<uintptr_t>(idx_dev) | reinterpret_cast<uintptr_t>(status_dev)) & 3)
+        return fail("%s: kp_dev, idx_dev and status_dev must be 4-byte aligned", who);
+    if ((reinterpret_cast<uintptr_t>(fit_dev) | reinterpret_cast<uintptr_t>(hess_dev)) & 7)
+        return fail("%s: fit_dev and hess_dev must be 8-byte aligned", who);
+    if (c.cfg.variant != 1 && !c.opt.final_mfma && c.cfg.cin > 8)
+        return fail("%s: the VALU output layer's fit stages at most 8 input channels (this handle takes %d)", who, c.cfg.cin);
+    return 0;
+}
+
+int esahrnet_forward_keypoints_gaussfit(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* kp_dev,
+                                        void* idx_dev, void* fit_dev, void* status_dev, void* hess_dev, void* ws_dev,
+                                        size_t ws_bytes, esahrnet_stream stream) {
+    if (!h || !x_dev || !kp_dev || !status_dev || !ws_dev) return fail("forward_keypoints_gaussfit: null argument");
+    if (check_gaussfit_outputs("forward_keypoints_gaussfit", *h, kp_dev, idx_dev, fit_dev, status_dev, hess_dev)) return 1;
+    return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev, false,
+                       hess_dev, fit_dev, status_dev);
 }
 
 int esahrnet_keypoints_finish(const void* heat_dev, const void* part_dev, int ntiles, int n, int k, int height, int width,
@@ -2382,10 +2441,12 @@ int esahrnet_frames_keypoints_workspace_bytes(esahrnet_handle h, int m, int scal
 
 // esahrnet_frames_keypoints / esahrnet_frames_correspondences after their argument checks (`who` names the caller in the
 // messages): boxes -> crops -> forward + decoder -> NaN rows for invalid crops.  hess_dev: decoder 1 only, may be null.
+// decoder 2 (esahrnet_frames_keypoints_gaussfit only): the Gaussian fit, with fit_dev / hess_dev (may be null) and status_dev.
 static int frames_run(const char* who, esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
                       int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale, int rule, float mean,
                       float stdv, int decoder, void* kp_dev, void* idx_dev, void* hess_dev, void* crop_boxes_dev, void* rates_dev,
-                      void* valid_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
+                      void* valid_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream, void* fit_dev = nullptr,
+                      void* status_dev = nullptr) {
     const hipStream_t st = static_cast<hipStream_t>(stream);
     int rc = esa::launch_boxes(static_cast<const int*>(det_boxes_dev), static_cast<const int*>(frame_idx_dev), nframes, m, frame_h,
                                frame_w, scale, rule, static_cast<int*>(crop_boxes_dev), static_cast<double*>(rates_dev),
@@ -2397,10 +2458,15 @@ static int frames_run(const char* who, esahrnet_handle h, const void* frames_dev
     if (rc) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)rc));
     const size_t head = frontend_crop_bytes(m, scale);
     if (run_forward(h, ws_dev, m, scale, scale, nullptr, static_cast<char*>(ws_dev) + head, ws_bytes - head, stream, nullptr, nullptr,
-                    kp_dev, idx_dev, decoder == 1, hess_dev))
+                    kp_dev, idx_dev, decoder == 1, hess_dev, fit_dev, decoder == 2 ? status_dev : nullptr))
         return 1;
-    rc = esa::launch_mark_invalid(static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints, static_cast<float*>(kp_dev),
-                                  static_cast<int*>(idx_dev), st);
+    if (decoder == 2)
+        rc = esa::launch_mark_invalid_gaussfit(static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints,
+                                               static_cast<float*>(kp_dev), static_cast<int*>(idx_dev), static_cast<double*>(fit_dev),
+                                               static_cast<int*>(status_dev), static_cast<double*>(hess_dev), st);
+    else
+        rc = esa::launch_mark_invalid(static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints, static_cast<float*>(kp_dev),
+                                      static_cast<int*>(idx_dev), st);
     if (rc) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)rc));
     return 0;
 }
@@ -2425,6 +2491,45 @@ int esahrnet_frames_keypoints(esahrnet_handle h, const void* frames_dev, int nfr
     return frames_run("frames_keypoints", h, frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m,
                       scale, rule, mean, stdv, decoder, kp_dev, idx_dev, nullptr, crop_boxes_dev, rates_dev, valid_dev, ws_dev,
                       ws_bytes, stream);
+}
+
+int esahrnet_frames_keypoints_gaussfit_workspace_bytes(esahrnet_handle h, int m, int scale, size_t* bytes) {
+    if (!h || !bytes) return fail("frames_keypoints_gaussfit_workspace_bytes: null argument");
+    if (h->cfg.cin != 1)
+        return fail("frames_keypoints_gaussfit: the loader makes 1-channel crops (data_load_val.py / data_load4.py); this handle takes %d channels",
+                    h->cfg.cin);
+    if (m <= 0 || scale <= 0 || (long long)m * scale > kFrontendMaxRows)
+        return fail("frames_keypoints_gaussfit: scale %d with %d boxes (both positive, boxes * scale at most %d)", scale, m,
+                    kFrontendMaxRows);
+    size_t fw = 0;
+    if (esahrnet_keypoints_gaussfit_forward_workspace_bytes(h, m, scale, scale, &fw)) return 1;
+    *bytes = frontend_crop_bytes(m, scale) + fw;
+    return 0;
+}
+
+int esahrnet_frames_keypoints_gaussfit(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                                       int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale,
+                                       int rule, float mean, float stdv, void* kp_dev, void* idx_dev, void* fit_dev, void* status_dev,
+                                       void* hess_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev, void* ws_dev,
+                                       size_t ws_bytes, esahrnet_stream stream) {
+    if (!h || !frames_dev || !det_boxes_dev || !kp_dev || !status_dev || !crop_boxes_dev || !rates_dev || !valid_dev || !ws_dev)
+        return fail("frames_keypoints_gaussfit: null argument");
+    // everything that can be refused is refused here, before the first launch
+    if (check_boxes_args("frames_keypoints_gaussfit", m, frame_h, frame_w, scale, rule) ||
+        check_crops_args("frames_keypoints_gaussfit", nframes, pixel_format, stdv))
+        return 1;
+    if (!frame_idx_dev && m != nframes)
+        return fail("frames_keypoints_gaussfit: %d boxes on %d frames need a frame index (NULL is the identity: box i lies on frame i)",
+                    m, nframes);
+    if (!h->committed) return fail("frames_keypoints_gaussfit: esahrnet_commit has not been called");
+    if (check_gaussfit_outputs("frames_keypoints_gaussfit", *h, kp_dev, idx_dev, fit_dev, status_dev, hess_dev)) return 1;
+    size_t need = 0;
+    if (esahrnet_frames_keypoints_gaussfit_workspace_bytes(h, m, scale, &need)) return 1;
+    if (ws_bytes < need) return fail("frames_keypoints_gaussfit: workspace too small (%zu < %zu)", ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("frames_keypoints_gaussfit: workspace must be 256-byte aligned");
+    return frames_run("frames_keypoints_gaussfit", h, frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev,
+                      frame_idx_dev, m, scale, rule, mean, stdv, 2, kp_dev, idx_dev, hess_dev, crop_boxes_dev, rates_dev, valid_dev,
+                      ws_dev, ws_bytes, stream, fit_dev, status_dev);
 }
 
 // ---- keypoints -> correspondences for the pose solver (correspond.hip) --------------------------------------------------

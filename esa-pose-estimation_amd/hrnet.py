@@ -27,7 +27,7 @@ import torch.nn as nn
 
 from . import _lib, crops
 from .fold import fold_conv
-from .inference import check_refine, check_weights, gaussfit_keypoints, pack_correspondences
+from .inference import check_refine, check_weights, pack_correspondences, packed_layout
 
 logger = logging.getLogger(__name__)
 BN_MOMENTUM = 0.01           # models/seg_hrnet.py:23 (irrelevant at inference, kept for parity)
@@ -73,6 +73,10 @@ def _cfg_struct(config, cin: int, num_keypoints: int, variant: int = 0, precisio
             elif int(st["NUM_CHANNELS"][b]) != int(extra["STAGE4"]["NUM_CHANNELS"][b]):
                 raise ValueError("branch widths must agree across stages")
     return s
+
+
+# refine -> the decoder of esahrnet_frames_keypoints; 2 has an entry point of its own (esahrnet_frames_keypoints_gaussfit)
+REFINE_DECODER = {"get_final": 0, "get_final2": 1, "gaussfit": 2}
 
 
 class _Node(nn.Module):
@@ -151,7 +155,8 @@ class HighResolutionNet(nn.Module):
         inference.heatmaps_to_keypoints(net(x)); "keypoints+index": (kp, idx int32 [N,K] = row * W + column).
         refine="get_final2" (keypoint outputs only): the second decoder, bit-identical to
         inference.heatmaps_to_keypoints(net(x), refine="get_final2"), without writing heat-maps either
-        (include/esahrnet.h esahrnet_forward_keypoints_final2)."""
+        (include/esahrnet.h esahrnet_forward_keypoints_final2).  refine="gaussfit": the Gaussian-fit decoder fused into the
+        forward (esahrnet_forward_keypoints_gaussfit), the kp of keypoints_gaussfit."""
         if self.training:
             raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
                                "(the reference callers do, val.py:95 / demo.py:80)")
@@ -162,7 +167,9 @@ class HighResolutionNet(nn.Module):
             return self._rt.forward(self, x0)
         if output not in self.OUTPUTS:
             raise ValueError(f"output must be one of {self.OUTPUTS}, got {output!r}")
-        if refine == "get_final2":
+        if refine == "gaussfit":
+            kp, _, _, _, idx = self._rt.forward_gaussfit(self, x0, False, output == "keypoints+index", want_hessian=False)
+        elif refine == "get_final2":
             kp, idx = self._rt.forward_final2(self, x0, output == "keypoints+index")
         else:
             kp, idx = self._rt.forward_keypoints(self, x0, output == "keypoints+index")
@@ -189,9 +196,10 @@ class HighResolutionNet(nn.Module):
         esahrnet_frames_correspondences): -> (count int32 [m], order int32 [m,K], pts f64 [m,K,2], w f64 [m,K,3], kp, crop_boxes,
         rates, valid), all on the device.  The first four are the record the host pose solver consumes
         (pnp.correspondences_to_pose_batch): the keypoints handed to PnP, largest peak first, in image pixels, each with its
-        2x2 weight (wxx, wxy, wyy) — weights="peak": (peak, 0, peak); "hessian" (refine="get_final2" only): the get_final2
-        Hessian as an information matrix, rate * (-H)^(1/2).  Equal, bit for bit, to frames_to_keypoints followed by
-        inference.keypoints_to_correspondences; capturable into a graph."""
+        2x2 weight (wxx, wxy, wyy) — weights="peak": (peak, 0, peak); "hessian" (refine="get_final2" or "gaussfit"): the
+        decoder's Hessian as an information matrix, rate * (-H)^(1/2).  Equal, bit for bit, to frames_to_keypoints followed by
+        inference.keypoints_to_correspondences; capturable into a graph.  refine="gaussfit": two library calls on one stream
+        (esahrnet_frames_keypoints_gaussfit, then esahrnet_correspondences on its outputs)."""
         return self._frames_to_correspondences(frames, det_boxes, frame_idx, scale, rule, refine, thresh, min_k, weights, mean, std,
                                                pixel_format)[:8]
 
@@ -208,7 +216,7 @@ class HighResolutionNet(nn.Module):
         if mean is None:
             mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
         return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
-                                         1 if refine == "get_final2" else 0, corr=(float(thresh), int(min_k), mode))
+                                         REFINE_DECODER[refine], corr=(float(thresh), int(min_k), mode))
 
     def keypoints_hessian(self, x0: torch.Tensor):
         """net(x, output="keypoints+index", refine="get_final2") with the Hessian of each step: -> (kp f32 [N,K,3], idx int32
@@ -221,18 +229,20 @@ class HighResolutionNet(nn.Module):
         return self._rt.forward_final2(self, x0, True, want_hessian=True)
 
     def keypoints_gaussfit(self, x0: torch.Tensor, return_fit: bool = False):
-        """The forward, then the Gaussian-fit decoder on its heat-maps (inference.gaussfit_keypoints; include/esahrnet.h
-        esahrnet_keypoints_gaussfit): -> (kp f32 [N,K,3], status int32 [N,K], hess f64 [N,K,3] = (-2a, -2b, -2c)), or with
-        return_fit=True (kp, fit f64 [N,K,8], status, hess); bit-identical to inference.gaussfit_keypoints(net(x)).  The
-        heat-maps live in a temporary tensor of the forward's stream (the decoder is not fused into the forward)."""
+        """The forward with the Gaussian-fit decoder in place of its last launch (include/esahrnet.h
+        esahrnet_forward_keypoints_gaussfit): -> (kp f32 [N,K,3], status int32 [N,K], hess f64 [N,K,3] = (-2a, -2b, -2c)), or
+        with return_fit=True (kp, fit f64 [N,K,8], status, hess); bit-identical to inference.gaussfit_keypoints(net(x)), without
+        heat-maps in caller memory."""
         if self.training:
             raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
                                "(the reference callers do, val.py:95 / demo.py:80)")
-        return self._rt.forward_gaussfit(self, x0, bool(return_fit))
+        kp, fit, status, hess, _ = self._rt.forward_gaussfit(self, x0, bool(return_fit), False)
+        return (kp, fit, status, hess) if return_fit else (kp, status, hess)
 
     def _frames_to_keypoints(self, frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format):
         """frames_to_keypoints, plus (idx int32 [m,K], packed): every output is a view of `packed` (one uint8 buffer), so a
-        caller that needs them on the host fetches them with one copy (pipeline.estimate_poses)."""
+        caller that needs them on the host fetches them with one copy (pipeline.estimate_poses).  refine="gaussfit": plus (fit
+        f64 [m,K,8], status int32 [m,K], hess f64 [m,K,3]), views of `packed` too (inference.packed_layout)."""
         if self.training:
             raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
                                "(the reference callers do, val.py:95 / demo.py:80)")
@@ -241,7 +251,7 @@ class HighResolutionNet(nn.Module):
         if mean is None:
             mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
         return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
-                                         1 if refine == "get_final2" else 0)
+                                         REFINE_DECODER[refine])
 
     # ---- extras of the MI355X path ---------------------------------------------------------------
     @property
@@ -343,7 +353,8 @@ class _Runtime:
         self.ws = {}             # (device, stream, n, h, w, keep) -> uint8 tensor, insertion order = LRU order
         self.kp_ws = {}          # the same for esahrnet_forward_keypoints (its own size: esahrnet_keypoints_workspace_bytes)
         self.f2_ws = {}          # the same for forward_final2 (esahrnet_keypoints_final2_forward_workspace_bytes)
-        self.fr_ws = {}          # the same for frames_keypoints (esahrnet_frames_keypoints_workspace_bytes), both decoders
+        self.fr_ws = {}          # the same for frames_keypoints (esahrnet_frames_keypoints_workspace_bytes), every decoder
+        self.gf_ws = {}          # the same for forward_gaussfit (esahrnet_keypoints_gaussfit_forward_workspace_bytes)
         self.part_tiles = {}     # (handle, h, w) -> tiles per heat-map with partial maxima (0: none)
         self._probe = self._create(-1)
 
@@ -439,6 +450,7 @@ class _Runtime:
             self.kp_ws.clear()
             self.f2_ws.clear()
             self.fr_ws.clear()
+            self.gf_ws.clear()
 
     def _workspace(self, h, device, stream, n, hh, ww, keep, kind="forward"):
         """Scratch for one forward.  Contract: while the stream is being CAPTURED into a HIP
@@ -453,6 +465,12 @@ class _Runtime:
         elif kind == "final2":
             _lib.check(self.lib.esahrnet_keypoints_final2_forward_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
             cache = self.f2_ws
+        elif kind == "gaussfit":
+            _lib.check(self.lib.esahrnet_keypoints_gaussfit_forward_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
+            cache = self.gf_ws
+        elif kind == "frames_gaussfit":                 # n crops of hh x hh; keep = "gaussfit" keeps its entries apart
+            _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit_workspace_bytes(h, n, hh, C.byref(nbytes)))
+            cache = self.fr_ws
         elif kind == "corr":                            # n crops of hh x hh; keep = (decoder, mode)
             _lib.check(self.lib.esahrnet_frames_correspondences_workspace_bytes(h, n, hh, keep[0], keep[1], C.byref(nbytes)))
             cache = self.fr_ws
@@ -571,19 +589,37 @@ class _Runtime:
         x.record_stream(ts)
         return (kp, idx, hess) if want_hessian else (kp, idx)
 
-    def forward_gaussfit(self, module, x0, want_fit):
-        """forward(), then esahrnet_keypoints_gaussfit on the heat-maps, enqueued behind it on the caller's current stream of
-        the input's device.  forward() brings the device lock, the workspace and the record_stream handling; the heat-map
-        tensor is a temporary allocated under that same stream, so it needs no record_stream of its own.  forward() also
-        leaves the per-tile maxima beside the heat-maps, which this decoder does not read (its entry point sweeps the planes
-        with the arg-max kernel): work a fused form would save, and that form is not built."""
-        heat = self.forward(module, x0)
-        kp, fit, status, hess = gaussfit_keypoints(heat)
-        return (kp, fit, status, hess) if want_fit else (kp, status, hess)
+    def forward_gaussfit(self, module, x0, want_fit, want_index, want_hessian=True):
+        """esahrnet_forward_keypoints_gaussfit: -> (kp f32 [N,K,3], fit f64 [N,K,8] or None, status int32 [N,K], hess f64 [N,K,3]
+        or None, idx int32 [N,K] or None); nothing else reaches caller memory.  Same device lock, weight-staleness key,
+        workspace contract (graph capture included) and record_stream handling as forward_final2()."""
+        x = self._check_input(module, x0)
+        n, _, hh, ww = x.shape
+        dev = x.device
+        ts = torch.cuda.current_stream(dev)
+        k = module._k
+        with self._device_lock(dev.index):
+            h = self._handle_for(module, dev)
+            _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
+            ws, ws_ptr, nbytes = self._workspace(h, dev, ts, n, hh, ww, False, kind="gaussfit")
+            with torch.cuda.device(dev):
+                kp = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
+                idx = torch.empty((n, k), dtype=torch.int32, device=dev) if want_index else None
+                fit = torch.empty((n, k, 8), dtype=torch.float64, device=dev) if want_fit else None
+                status = torch.empty((n, k), dtype=torch.int32, device=dev)
+                hess = torch.empty((n, k, 3), dtype=torch.float64, device=dev) if want_hessian else None
+                _lib.check(self.lib.esahrnet_forward_keypoints_gaussfit(
+                    h, x.data_ptr(), n, hh, ww, kp.data_ptr(), idx.data_ptr() if want_index else None,
+                    fit.data_ptr() if want_fit else None, status.data_ptr(), hess.data_ptr() if want_hessian else None, ws_ptr,
+                    nbytes, C.c_void_p(ts.cuda_stream)))
+        ws.record_stream(ts)
+        x.record_stream(ts)
+        return kp, fit, status, hess, idx
 
     def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None):
         """esahrnet_frames_keypoints (arguments already checked by crops.check_device_loader_args).  The outputs are views
-        of one packed buffer: rates f64 [m] | kp f32 [m,K,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,K].
+        of one packed buffer: rates f64 [m] | kp f32 [m,K,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,K]
+        (inference.packed_layout; decoder 2, the Gaussian fit, also fit, hess and status, returned behind `packed`).
         Same device lock, weight-staleness key, workspace contract (graph capture included) and record_stream handling as
         forward().  corr = (thresh, min_k, mode): esahrnet_frames_correspondences instead -> (count, order, pts, w, kp, boxes,
         rates, valid, packed), the first four views of `packed` (inference.pack_correspondences)."""
@@ -601,19 +637,43 @@ class _Runtime:
         with torch.cuda.device(dev):
             det = crops.to_device_int32(det_boxes, dev)
             fidx = None if frame_idx is None else crops.to_device_int32(frame_idx, dev)
-            sizes = (8 * m, 12 * m * k, 16 * m, 4 * m, 4 * m * k)
-            offs = [0]
-            for b in sizes:
-                offs.append(offs[-1] + b)
-            packed = torch.empty(offs[-1], dtype=torch.uint8, device=dev)
-            rates = packed[offs[0]:offs[1]].view(torch.float64)
-            kp = packed[offs[1]:offs[2]].view(torch.float32).view(m, k, 3)
-            boxes = packed[offs[2]:offs[3]].view(torch.int32).view(m, 4)
-            valid = packed[offs[3]:offs[4]].view(torch.int32)
-            idx = packed[offs[4]:offs[5]].view(torch.int32).view(m, k)
+            lay = packed_layout(m, k, decoder == 2)
+            packed = torch.empty(lay["total"][1], dtype=torch.uint8, device=dev)
+
+            def part(name, dtype, *shape):
+                o, b = lay[name]
+                return packed[o:o + b].view(dtype).view(*shape)
+
+            rates = part("rates", torch.float64, m)
+            kp = part("kp", torch.float32, m, k, 3)
+            boxes = part("boxes", torch.int32, m, 4)
+            valid = part("valid", torch.int32, m)
+            idx = part("idx", torch.int32, m, k)
+            if decoder == 2:
+                fit, status, hess = part("fit", torch.float64, m, k, 8), part("status", torch.int32, m, k), \
+                    part("hess", torch.float64, m, k, 3)
             with self._device_lock(dev.index):
                 h = self._handle_for(module, dev)
                 _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
+                if decoder == 2:                    # its own entry point; the correspondences, if asked for, behind it
+                    ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, "gaussfit", kind="frames_gaussfit")
+                    _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit(
+                        h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m,
+                        scale, rule, mean, std, kp.data_ptr(), idx.data_ptr(), fit.data_ptr(), status.data_ptr(), hess.data_ptr(),
+                        boxes.data_ptr(), rates.data_ptr(), valid.data_ptr(), ws_ptr, ws_bytes, C.c_void_p(ts.cuda_stream)))
+                    if corr is not None:
+                        thresh, min_k, mode = corr
+                        count, order, pts, w, cpacked = pack_correspondences(m, k, dev)
+                        _lib.check(self.lib.esahrnet_correspondences(
+                            kp.data_ptr(), hess.data_ptr() if mode else None, boxes.data_ptr(), rates.data_ptr(), valid.data_ptr(),
+                            m, k, thresh, min_k, mode, count.data_ptr(), order.data_ptr(), pts.data_ptr(), w.data_ptr(),
+                            C.c_void_p(ts.cuda_stream)))
+                    for t in (ws, frames, det, fidx):
+                        if t is not None:
+                            t.record_stream(ts)
+                    if corr is not None:
+                        return count, order, pts, w, kp, boxes, rates, valid, cpacked
+                    return kp, boxes, rates, valid, idx, packed, fit, status, hess
                 if corr is not None:
                     thresh, min_k, mode = corr
                     count, order, pts, w, cpacked = pack_correspondences(m, k, dev)

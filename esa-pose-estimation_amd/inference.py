@@ -22,11 +22,12 @@ import torch
 from . import _lib
 
 
-REFINES = ("get_final", "get_final2")
+REFINES = ("get_final", "get_final2", "gaussfit")
 
 
 def check_refine(refine):
-    """The sub-pixel step: "get_final" (default, inference.py:136-152) or "get_final2" (inference.py:154-169)."""
+    """The sub-pixel step: "get_final" (default, inference.py:136-152), "get_final2" (inference.py:154-169) or "gaussfit" (the
+    2-D Gaussian fit of the reference's test.py, gaussfit_keypoints)."""
     if not isinstance(refine, str) or refine not in REFINES:
         raise ValueError(f"refine must be one of {REFINES}, got {refine!r}")
     return refine
@@ -62,8 +63,8 @@ def _keypoints_final2(heat: torch.Tensor, want_index: bool, want_hessian: bool =
 
 def _keypoints(heat: torch.Tensor, want_index: bool, refine: str = "get_final", want_hessian: bool = False):
     check_refine(refine)
-    if want_hessian and refine != "get_final2":
-        raise ValueError("return_hessian=True needs refine='get_final2': get_final computes no Hessian")
+    if want_hessian and refine == "get_final":
+        raise ValueError("return_hessian=True needs refine='get_final2' or 'gaussfit': get_final computes no Hessian")
     if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
         raise ValueError("expected a 4-D tensor [N, K, H, W]")
     if not heat.is_cuda:
@@ -72,6 +73,9 @@ def _keypoints(heat: torch.Tensor, want_index: bool, refine: str = "get_final", 
         raise TypeError(f"expected float32 heatmaps, got {heat.dtype}")
     if refine == "get_final2":
         return _keypoints_final2(heat, want_index, want_hessian)
+    if refine == "gaussfit":
+        kp, _, _, hess, idx = _gaussfit(heat, want_index)
+        return (kp, idx, hess) if want_hessian else (kp, idx)
     # heat-maps that come straight out of a forward carry the per-tile maxima their output-layer kernel found
     # (hrnet._Runtime.forward): finishing over those gives the same bits without reading the maps again.  The note is
     # honoured only for this very tensor object, unmodified since (views, clones and in-place edits take the full sweep).
@@ -105,7 +109,9 @@ def heatmaps_to_keypoints(heat: torch.Tensor, refine: str = "get_final", return_
     get_final2 does (11x11 Gaussian blur rescaled to the raw peak, log, full-Hessian Newton step; include/esahrnet.h
     esahrnet_keypoints_final2), same arg-max and peak; the blurred maps are never stored and `heat` is not modified.
     return_hessian=True (get_final2 only): -> (kp, hess f64 cuda [N,K,3] = (dxx, dxy, dyy)), the Hessian of the blurred
-    log heat-map each step used, NaN where no step was taken (esahrnet_keypoints_final2_hess); kp has the same bits."""
+    log heat-map each step used, NaN where no step was taken (esahrnet_keypoints_final2_hess); kp has the same bits.
+    refine="gaussfit": the kp of gaussfit_keypoints (an accepted fit's centre, else the get_final row); with
+    return_hessian=True (kp, hess = (-2a, -2b, -2c) of the fit, NaN where it was rejected)."""
     out = _keypoints(heat, False, refine, return_hessian)
     return (out[0], out[2]) if return_hessian else out[0]
 
@@ -116,6 +122,11 @@ def gaussfit_keypoints(heat: torch.Tensor):
     f32 cuda [N,K,H,W] -> (kp f32 [N,K,3] = (x0, y0, raw peak); fit f64 [N,K,8] = (A, x0, y0, a, b, c, off, cost); status int32
     [N,K], 0 = accepted; hess f64 [N,K,3] = (-2a, -2b, -2c)).  A rejected keypoint (status 1, 2, 3) keeps the get_final row of
     heatmaps_to_keypoints, its fit and hess are NaN.  hess is what keypoints_to_correspondences(weights="hessian") takes."""
+    return _gaussfit(heat, False)[:4]
+
+
+def _gaussfit(heat: torch.Tensor, want_index: bool):
+    """gaussfit_keypoints, plus idx int32 [N,K] (None unless asked for): -> (kp, fit, status, hess, idx)."""
     if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
         raise ValueError("expected a 4-D tensor [N, K, H, W]")
     if not heat.is_cuda:
@@ -131,9 +142,11 @@ def gaussfit_keypoints(heat: torch.Tensor):
         fit = torch.empty((n, k, 8), dtype=torch.float64, device=dev)
         status = torch.empty((n, k), dtype=torch.int32, device=dev)
         hess = torch.empty((n, k, 3), dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().esahrnet_keypoints_gaussfit(heat.data_ptr(), n, k, h, w, kp.data_ptr(), None, fit.data_ptr(),
+        idx = torch.empty((n, k), dtype=torch.int32, device=dev) if want_index else None
+        _lib.check(_lib.lib().esahrnet_keypoints_gaussfit(heat.data_ptr(), n, k, h, w, kp.data_ptr(),
+                                                          idx.data_ptr() if want_index else None, fit.data_ptr(),
                                                           status.data_ptr(), hess.data_ptr(), C.c_void_p(stream)))
-    return kp, fit, status, hess
+    return kp, fit, status, hess, idx
 
 
 def gaussfit_sigma_theta(fit):
@@ -160,13 +173,29 @@ WEIGHTS = ("peak", "hessian")
 
 
 def check_weights(weights, refine="get_final2"):
-    """The weight of the pose refinement: "peak" (default; val.py:194-209) or "hessian" (the get_final2 Hessian as the 2x2
-    weight uncertainty_pnp.cpp takes; needs refine="get_final2").  -> the mode of esahrnet_correspondences."""
+    """The weight of the pose refinement: "peak" (default; val.py:194-209) or "hessian" (the decoder's Hessian as the 2x2
+    weight uncertainty_pnp.cpp takes; needs refine="get_final2" or "gaussfit").  -> the mode of esahrnet_correspondences."""
     if not isinstance(weights, str) or weights not in WEIGHTS:
         raise ValueError(f"weights must be one of {WEIGHTS}, got {weights!r}")
-    if weights == "hessian" and refine != "get_final2":
-        raise ValueError("weights='hessian' needs refine='get_final2': get_final computes no Hessian")
+    if weights == "hessian" and refine not in ("get_final2", "gaussfit"):
+        raise ValueError("weights='hessian' needs refine='get_final2' or 'gaussfit': get_final computes no Hessian")
     return WEIGHTS.index(weights)
+
+
+def packed_layout(m: int, k: int, gaussfit: bool = False):
+    """The packed buffer of net.frames_to_keypoints' outputs: name -> (offset, bytes).  rates f64 [m] | kp f32 [m,k,3] |
+    crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,k]; with gaussfit the decoder's f64 outputs come right behind
+    rates (8-byte aligned) and its status last: rates | fit f64 [m,k,8] | hess f64 [m,k,3] | kp | crop_boxes | valid | idx |
+    status int32 [m,k].  "total" -> (0, bytes of the buffer)."""
+    parts = [("rates", 8 * m)] + ([("fit", 64 * m * k), ("hess", 24 * m * k)] if gaussfit else [])
+    parts += [("kp", 12 * m * k), ("boxes", 16 * m), ("valid", 4 * m), ("idx", 4 * m * k)]
+    parts += [("status", 4 * m * k)] if gaussfit else []
+    out, off = {}, 0
+    for name, b in parts:
+        out[name] = (off, b)
+        off += b
+    out["total"] = (0, off)
+    return out
 
 
 def pack_correspondences(m: int, k: int, device):

@@ -52,7 +52,8 @@ def sharded_keypoints(net, crops: torch.Tensor, group=None, keypoints_fn=None, k
     through `net` + the fused keypoint kernel and all ranks return the full [N,K,3].
     `keypoints_fn` (default: inference.heatmaps_to_keypoints, GPU only) maps the rank's heat-maps to [n,K,3].
     keypoints_only=True: the rank's slice goes through net(x, output="keypoints") (no heat-maps; keypoints_fn unused).
-    refine="get_final2": the second decoder (inference.get_final2), passed on as refine= to the net or to keypoints_fn."""
+    refine="get_final2": the second decoder (inference.get_final2), passed on as refine= to the net or to keypoints_fn;
+    refine="gaussfit": the Gaussian-fit decoder, passed on the same way."""
     from .inference import check_refine
     check_refine(refine)
     rk = {} if refine == "get_final" else {"refine": refine}

@@ -128,8 +128,10 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
     image points, 2x2 weights), then the native solver on it (pnp.correspondences_to_pose_batch).  `threads`: worker threads of
     the native solver on every path (0: one per available CPU, at most 16).
     weights="peak" (default): the poses of device_loader=True, bit for bit.  weights="hessian" (device_select=True and
-    refine="get_final2" only): the refinement weighs each point by the get_final2 Hessian, rate * (-H)^(1/2), the anisotropic
-    weight uncertainty_pnp.cpp:30-31 takes, instead of the scalar peak."""
+    refine="get_final2" or "gaussfit"): the refinement weighs each point by the decoder's Hessian, rate * (-H)^(1/2), the
+    anisotropic weight uncertainty_pnp.cpp:30-31 takes, instead of the scalar peak.  refine="gaussfit": the Gaussian-fit decoder
+    (inference.gaussfit_keypoints) on every path; device_loader=True still fetches one packed buffer (the decoder's fit, Hessian
+    and status ride in it, inference.packed_layout)."""
     inference.check_refine(refine)
     inference.check_weights(weights, refine)
     if weights != "peak" and not device_select:
@@ -153,11 +155,12 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
             out = net._frames_to_keypoints(frames, bboxes, frame_idx, scale, rule, refine, None, crops.STD, None)
         m, k = out[0].shape[:2]
         host = out[5].cpu().numpy()                         # the only device->host copy
-        offs = np.cumsum([0, 8 * m, 12 * m * k, 16 * m, 4 * m])
-        rates = host[offs[0]:offs[1]].view(np.float64)
-        kp = host[offs[1]:offs[2]].view(np.float32).reshape(m, k, 3)
-        boxes = host[offs[2]:offs[3]].view(np.int32).reshape(m, 4).tolist()
-        valid = host[offs[3]:offs[4]].view(np.int32)
+        lay = inference.packed_layout(m, k, refine == "gaussfit")
+        rates, kp, boxes, valid = (host[lay[name][0]:lay[name][0] + lay[name][1]] for name in ("rates", "kp", "boxes", "valid"))
+        rates = rates.view(np.float64)
+        kp = kp.view(np.float32).reshape(m, k, 3)
+        boxes = boxes.view(np.int32).reshape(m, 4).tolist()
+        valid = valid.view(np.int32)
         # an invalid crop (NaN keypoint rows) is kept away from the solver and reported as the NaN row that "no solution" is
         bad = valid == 0
         rates = [1.0 if b else float(r) for r, b in zip(rates, bad)]

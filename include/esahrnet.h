@@ -237,6 +237,31 @@ int esahrnet_forward_keypoints_final2_hess(esahrnet_handle h, const void* x_dev,
                                            void* kp_dev, void* idx_dev, void* hess_dev, void* ws_dev, size_t ws_bytes,
                                            esahrnet_stream stream);
 
+/* ---- forward straight to Gaussian-fit keypoints -------------------------------------------------------------------
+ * esahrnet_forward_keypoints_gaussfit is esahrnet_forward_keypoints with the third decoder: kp_dev, idx_dev, fit_dev, status_dev
+ * and hess_dev have the shapes and types of esahrnet_keypoints_gaussfit (k = K) and are bit-identical to esahrnet_forward
+ * followed by esahrnet_keypoints_gaussfit on the same input and weights: the same arg-max, ties and NaN rule, the same
+ * get_final row for a rejected fit, the same statuses, the same fit to the last bit.  idx_dev, fit_dev and hess_dev may be NULL.
+ * No heat-map reaches caller memory.  ws_dev: esahrnet_keypoints_gaussfit_forward_workspace_bytes bytes (what
+ * esahrnet_keypoints_workspace_bytes reports), 256-byte aligned; its contents on entry do not matter.  Same contract as
+ * esahrnet_forward_keypoints_final2: no allocation, no synchronisation, graph-capturable, esahrnet_set_debug_keep and the
+ * multi-lane schedule apply.  Argument errors (a NULL handle, x_dev, kp_dev, status_dev or ws_dev, a handle that is not
+ * committed, a shape that is not positive, a workspace that is too small or not 256-byte aligned, an output pointer that is not
+ * aligned to its element) are reported before anything is enqueued.
+ *   seg_hrnet / seg_hrnet2, VALU output layer: each tile's first maximum per heat-map, nothing stored; the finish, one wave
+ *     per heat-map, evaluates the output layer again at the <= 13 x 13 pixels of the fit's window (15 x 15 staged inputs, the
+ *     arithmetic of the output layer, fma for fma), keeps them in LDS, writes the get_final row from them and runs the fit on
+ *     them.  Input channels: at most 8.
+ *   seg_hrnet / seg_hrnet2, matrix-core output layer: the heat-maps go to the workspace instead of caller memory, then
+ *     esahrnet_keypoints_finish's kernel and the fit kernel of esahrnet_keypoints_gaussfit (no new arithmetic).
+ *   seg_hrnet3: the tile maxima and the refinement of esahrnet_forward_keypoints on the NHWC heat-maps in the workspace, then
+ *     the fit with its window read from them; no NCHW copy is made.
+ * Except for the matrix-core form, the workspace has no n * K * height * width term beyond esahrnet_workspace_bytes'. */
+int esahrnet_keypoints_gaussfit_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes);
+int esahrnet_forward_keypoints_gaussfit(esahrnet_handle h, const void* x_dev, int n, int height, int width,
+                                        void* kp_dev, void* idx_dev, void* fit_dev, void* status_dev, void* hess_dev,
+                                        void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+
 /* Loader stage in front of the path (data_load_val.py:139-187): for each of n 8-bit frames
  * [frame_h][frame_w] take the clamped box boxes[i] = (x0, y0, x1, y1) (int32, device), edge-pad it the
  * way the reference does, resize to scale x scale (OpenCV 8-bit INTER_LINEAR arithmetic) and write
@@ -279,6 +304,22 @@ int esahrnet_frames_keypoints(esahrnet_handle h, const void* frames_dev, int nfr
                               int scale, int rule, float mean, float stdv, int decoder,
                               void* kp_dev, void* idx_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev,
                               void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+
+/* esahrnet_frames_keypoints_gaussfit: esahrnet_frames_keypoints with the third decoder, a symbol of its own (decoder = 2 is not
+ * a value of esahrnet_frames_keypoints): esahrnet_boxes -> esahrnet_crops_ex into the head of the workspace ->
+ * esahrnet_forward_keypoints_gaussfit on the rest -> the rows of an invalid crop (valid == 0) become kp NaN, idx -1, fit and hess
+ * NaN, status -1; valid rows are bit-identical to the calls it is built from.  idx_dev, fit_dev and hess_dev may be NULL.  ws_dev:
+ * esahrnet_frames_keypoints_gaussfit_workspace_bytes bytes, 256-byte aligned.  The refusals (cin != 1 among them) and the
+ * graph-capture contract are esahrnet_frames_keypoints', with the alignment rules of esahrnet_keypoints_gaussfit.  hess_dev is, as
+ * it stands, the hess_dev of esahrnet_correspondences(mode 1): enqueue that call behind this one on the same stream for
+ * Hessian-weighted correspondences. */
+int esahrnet_frames_keypoints_gaussfit_workspace_bytes(esahrnet_handle h, int m, int scale, size_t* bytes);
+int esahrnet_frames_keypoints_gaussfit(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                                       int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m,
+                                       int scale, int rule, float mean, float stdv,
+                                       void* kp_dev, void* idx_dev, void* fit_dev, void* status_dev, void* hess_dev,
+                                       void* crop_boxes_dev, void* rates_dev, void* valid_dev,
+                                       void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
 
 /* ---- keypoints to the record the pose solver consumes, on the device (val.py:172-180) -------------------------------------
  * esahrnet_correspondences (correspond_kernel, one wave per crop, k <= 32): kp_dev f32 [m][k][3] keypoint rows, crop_boxes_dev /
