@@ -142,6 +142,29 @@ __global__ __launch_bounds__(256) void mark_invalid_gaussfit_kernel(const int* v
     status[t] = -1;
 }
 
+// mark_invalid_gaussfit_kernel for esahrnet_frames_keypoints_gaussfit_cov: cov and info too
+__global__ __launch_bounds__(256) void mark_invalid_gfcov_kernel(const int* valid, int m, int K, float* kp, int* idx, double* fit,
+                                                                 int* status, double* hess, double* cov, double* info) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m * K) return;
+    if (valid[t / K]) return;
+    const float nan = __int_as_float(0x7fc00000);
+    const double dnan = __longlong_as_double(0x7ff8000000000000LL);
+    kp[(size_t)t * 3 + 0] = nan;
+    kp[(size_t)t * 3 + 1] = nan;
+    kp[(size_t)t * 3 + 2] = nan;
+    if (idx) idx[t] = -1;
+    if (fit)
+        for (int i = 0; i < 8; ++i) fit[(size_t)t * 8 + i] = dnan;
+    if (hess)
+        for (int i = 0; i < 3; ++i) hess[(size_t)t * 3 + i] = dnan;
+    if (cov)
+        for (int i = 0; i < 3; ++i) cov[(size_t)t * 3 + i] = dnan;
+    if (info)
+        for (int i = 0; i < 3; ++i) info[(size_t)t * 3 + i] = dnan;
+    status[t] = -1;
+}
+
 }  // namespace
 
 int launch_boxes(const int* det, const int* frame_idx, int nframes, int m, int FH, int FW, int S, int rule, int* crop,
@@ -177,6 +200,15 @@ int launch_mark_invalid_gaussfit(const int* valid, int m, int K, float* kp, int*
     if (m <= 0 || K <= 0 || (long long)m * K > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(mark_invalid_gaussfit_kernel, dim3((unsigned)(((long long)m * K + 255) / 256)), dim3(256), 0, s, valid, m, K,
                        kp, idx, fit, status, hess);
+    return (int)hipGetLastError();
+}
+
+int launch_mark_invalid_gaussfit_cov(const int* valid, int m, int K, float* kp, int* idx, double* fit, int* status, double* hess,
+                                     double* cov, double* info, hipStream_t s) {
+    if (!cov && !info) return launch_mark_invalid_gaussfit(valid, m, K, kp, idx, fit, status, hess, s);
+    if (m <= 0 || K <= 0 || (long long)m * K > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(mark_invalid_gfcov_kernel, dim3((unsigned)(((long long)m * K + 255) / 256)), dim3(256), 0, s, valid, m, K, kp,
+                       idx, fit, status, hess, cov, info);
     return (int)hipGetLastError();
 }
 

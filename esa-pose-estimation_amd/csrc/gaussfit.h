@@ -15,6 +15,11 @@
 //            a plane's result does not depend on its batch.  tests/gaussfit_ref.py restates it in numpy step for step.
 //   solve    the damped 7 x 7 system by a fully unrolled Cholesky, every lane the same; arrays are indexed by constants only,
 //            so that they stay in registers (build/resource_usage.json: no scratch).
+//   COV      gaussfit_plane<true> (the _cov entries; keypoints_gaussfit_cov.hip, head.hip final_gfcov_finish_kernel): behind the
+//            fit, the covariance of the fitted centre as curve_fit reports it, s^2 (J^T J)^-1 with s^2 = cost / (n - 7): one
+//            more Jacobian pass at the returned parameters (the same slot order and butterfly), the same Cholesky with lambda
+//            0, the x0 and y0 columns of the inverse.  gaussfit_plane<false> is the code it was: every addition sits behind
+//            if constexpr.  tests/gaussfit_cov_ref.py restates it.
 // Contraction is off inside every function body here (the restatement has no fma) and nowhere else: a file that includes this
 // header keeps its own setting for its own code, the loading functor included.  No LDS, no barrier.
 #pragma once
@@ -103,12 +108,47 @@ __device__ __forceinline__ bool gf_solve_damped(const double* Hm, const double* 
     return ok;
 }
 
+// J^T J of the model at p, lower triangle packed, the sums as the iteration forms them: every lane its slots in slot order, then
+// the butterfly.  For the covariance pass only (the iteration keeps its own loop, which also forms the gradient).
+__device__ __forceinline__ void gf_normal_matrix(const GfWindow& w, const double* p, double* N) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int s = 0; s < GF_SLOTS; ++s) {
+        double du, dv, e;
+        (void)gf_residual(w, s, p, du, dv, e);
+        const double ae = p[0] * e;
+        double J[GF_P];
+        J[0] = e;
+        J[1] = ae * ((2.0 * p[3]) * du + (2.0 * p[4]) * dv);
+        J[2] = ae * ((2.0 * p[4]) * du + (2.0 * p[5]) * dv);
+        J[3] = -(ae * (du * du));
+        J[4] = -(ae * ((2.0 * du) * dv));
+        J[5] = -(ae * (dv * dv));
+        J[6] = 1.0;
+#pragma unroll
+        for (int i = 0; i < GF_P; ++i) J[i] = w.m[s] ? J[i] : 0.0;
+#pragma unroll
+        for (int i = 0; i < GF_P; ++i)
+#pragma unroll
+            for (int k = 0; k <= i; ++k) {
+                const double t = J[i] * J[k];
+                N[gf_tri(i, k)] = s == 0 ? t : N[gf_tri(i, k)] + t;
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < GF_T; ++i) N[i] = gf_wave_sum(N[i]);
+}
+
 // One wave fits one plane.  load(row, column): the plane's value there as f32, called for window pixels only (inside the
 // plane).  bi: the plane's arg-max, row * W + column, the same in every lane.  kp[plane] arrives holding the get_final row (x,
 // y, peak); an accepted fit replaces x and y.  fit and hess may be null.  Lane 0 stores.
-template <class Load>
+// COV: also cov f64 [planes][3] = s^2 (Ninv[1][1], Ninv[1][2], Ninv[2][2]) in crop px^2, N = J^T J at the returned parameters, s^2
+// = cost / (n - 7), and info f64 [planes][3] = -cov^-1 = (-(cyy / det), cxy / det, -(cxx / det)), det = cxx cyy - cxy cxy (either
+// may be null).  cov is NaN x 3 for a rejected fit, n <= 7, a pivot that is not positive or a value that is not finite; info
+// where cov is, where det is not positive and where cxx < cov_floor.  The status describes the fit alone.
+template <bool COV = false, class Load>
 __device__ __forceinline__ void gaussfit_plane(Load load, size_t plane, int H, int W, int bi, float* kp, double* fit, int* status,
-                                               double* hess) {
+                                               double* hess, double* cov = nullptr, double* info = nullptr, double cov_floor = 0.0) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x;
     if ((unsigned)bi >= (unsigned)(H * W)) bi = 0;               // never: the arg-max kernels write an index inside the plane
@@ -203,6 +243,20 @@ __device__ __forceinline__ void gaussfit_plane(Load load, size_t plane, int H, i
         }
     }
 
+    // the x0 and y0 columns of (J^T J)^-1 at the solution: N d = e1 and N d = e2 through the iteration's solver, undamped
+    double c1[GF_P], c2[GF_P];
+    bool cov_ok = false;
+    if constexpr (COV) {
+        if (!bad) {
+            double N[GF_T];
+            gf_normal_matrix(w, p, N);
+            const double g1[GF_P] = {-0.0, -1.0, -0.0, -0.0, -0.0, -0.0, -0.0}, g2[GF_P] = {-0.0, -0.0, -1.0, -0.0, -0.0, -0.0, -0.0};
+            const bool ok1 = gf_solve_damped(N, g1, 0.0, c1);
+            const bool ok2 = gf_solve_damped(N, g2, 0.0, c2);
+            cov_ok = ok1 && ok2;
+        }
+    }
+
     if (lane == 0) {
         int st;
         if (bad) {
@@ -239,6 +293,31 @@ __device__ __forceinline__ void gaussfit_plane(Load load, size_t plane, int H, i
             h3[2] = st ? nan : -2.0 * p[5];
         }
         status[plane] = st;
+        if constexpr (COV) {
+            const int dof = npx - GF_P;
+            double cxx = nan, cxy = nan, cyy = nan;
+            if (st == 0 && cov_ok && dof > 0) {
+                const double s2 = cost / (double)dof;
+                cxx = s2 * c1[1];
+                cxy = s2 * c1[2];
+                cyy = s2 * c2[2];
+                if (!(isfinite(cxx) && isfinite(cxy) && isfinite(cyy))) cxx = cxy = cyy = nan;
+            }
+            if (cov) {
+                double* c3 = cov + plane * 3;
+                c3[0] = cxx;
+                c3[1] = cxy;
+                c3[2] = cyy;
+            }
+            if (info) {
+                const double det = cxx * cyy - cxy * cxy;
+                const bool keep = det > 0.0 && !(cxx < cov_floor);       // NaN cov: det is NaN
+                double* i3 = info + plane * 3;
+                i3[0] = keep ? -(cyy / det) : nan;
+                i3[1] = keep ? cxy / det : nan;
+                i3[2] = keep ? -(cxx / det) : nan;
+            }
+        }
     }
 }
 

@@ -493,8 +493,10 @@ __global__ __launch_bounds__(64) void final2_valu_finish_kernel(FinalParams p, i
 // values stay in LDS: lane 0 writes the get_final row from them (refine_keypoint reads +-2 around the peak), then
 // gaussfit.h's solver reads its window from them.  Values at positions outside the plane are computed and never read.  kp /
 // idx / fit / status / hess bit-identical to launch_final (VALU) followed by launch_keypoints_gaussfit.
-__global__ __launch_bounds__(64) void final_gf_finish_kernel(FinalParams p, int kt, int ntiles, float* kp, int* idx_out, double* fit,
-                                                             int* status, double* hess) {
+// The body is shared with final_gfcov_finish_kernel (COV: gaussfit.h's covariance pass behind the fit, cov / info / cov_floor).
+template <bool COV>
+__device__ __forceinline__ void final_gf_finish_body(const FinalParams& p, int kt, int ntiles, float* kp, int* idx_out, double* fit,
+                                                     int* status, double* hess, double* cov, double* info, double cov_floor) {
     constexpr int R = 2 * GF_R + 1, S = R + 2;
     __shared__ float stg[8 * S * S];
     __shared__ float win[R * R];
@@ -534,7 +536,21 @@ __global__ __launch_bounds__(64) void final_gf_finish_kernel(FinalParams p, int 
     __syncthreads();
     auto at = [&](int yy, int xx) { return win[(yy - wy0) * R + (xx - wx0)]; };
     if (lane == 0) refine_keypoint(at, p.H, p.W, bi, kp + (size_t)plane * 3, idx_out ? idx_out + plane : nullptr);
-    gaussfit_plane(at, (size_t)plane, p.H, p.W, bi, kp, fit, status, hess);
+    if constexpr (COV) gaussfit_plane<true>(at, (size_t)plane, p.H, p.W, bi, kp, fit, status, hess, cov, info, cov_floor);
+    else gaussfit_plane(at, (size_t)plane, p.H, p.W, bi, kp, fit, status, hess);
+}
+
+__global__ __launch_bounds__(64) void final_gf_finish_kernel(FinalParams p, int kt, int ntiles, float* kp, int* idx_out, double* fit,
+                                                             int* status, double* hess) {
+    final_gf_finish_body<false>(p, kt, ntiles, kp, idx_out, fit, status, hess, nullptr, nullptr, 0.0);
+}
+
+// final_gf_finish_kernel with the covariance of the fitted centre (esahrnet_forward_keypoints_gaussfit_cov): the same values in
+// LDS, the same get_final row and fit; cov / info as launch_keypoints_gaussfit_cov writes them
+__global__ __launch_bounds__(64) void final_gfcov_finish_kernel(FinalParams p, int kt, int ntiles, float* kp, int* idx_out,
+                                                                double* fit, int* status, double* hess, double* cov, double* info,
+                                                                double cov_floor) {
+    final_gf_finish_body<true>(p, kt, ntiles, kp, idx_out, fit, status, hess, cov, info, cov_floor);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -842,10 +858,15 @@ int launch_final_kp(const FinalParams& p, float* kp, int* idx_out, hipStream_t s
 }
 
 int launch_final_gf(const FinalParams& p, float* kp, int* idx_out, double* fit, int* status, double* hess, hipStream_t stream) {
+    return launch_final_gf_cov(p, kp, idx_out, fit, status, hess, nullptr, nullptr, 0.0, stream);
+}
+
+int launch_final_gf_cov(const FinalParams& p, float* kp, int* idx_out, double* fit, int* status, double* hess, double* cov,
+                        double* info, double cov_floor, hipStream_t stream) {
     const int ntiles = final_kp_tiles(p.K, p.cin, p.H, p.W), kt = final_kt(p.K);
     const long long planes = (long long)p.N * p.K;
     if (!p.part || !kp || !status || ntiles <= 0 || kt < 0 || p.cin < 0 || p.cin > 8 || planes > 0x7fffffffLL ||
-        (long long)p.H * p.W > 0x7fffffffLL)
+        (long long)p.H * p.W > 0x7fffffffLL || !(cov_floor >= 0.0))
         return (int)hipErrorInvalidValue;
     int rc = (int)hipErrorInvalidValue;
     switch (kt) {
@@ -854,8 +875,12 @@ int launch_final_gf(const FinalParams& p, float* kp, int* idx_out, double* fit, 
         case 32: rc = launch_final_t<32, true>(p, stream); break;
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(final_gf_finish_kernel, dim3((unsigned)planes), dim3(64), 0, stream, p, kt, ntiles, kp, idx_out, fit, status,
-                       hess);
+    if (cov || info)
+        hipLaunchKernelGGL(final_gfcov_finish_kernel, dim3((unsigned)planes), dim3(64), 0, stream, p, kt, ntiles, kp, idx_out, fit,
+                           status, hess, cov, info, cov_floor);
+    else
+        hipLaunchKernelGGL(final_gf_finish_kernel, dim3((unsigned)planes), dim3(64), 0, stream, p, kt, ntiles, kp, idx_out, fit,
+                           status, hess);
     return (int)hipGetLastError();
 }
 

@@ -175,6 +175,9 @@ int launch_final_kp(const FinalParams& p, float* kp, int* idx_out, hipStream_t s
 // (may be null), fit f64 [N*K][8] (may be null), status int32 [N*K], hess f64 [N*K][3] (may be null) bit-identical to launch_final
 // (VALU) + launch_keypoints_gaussfit; p.part: [N*K][final_kp_tiles], p.out not used; cin <= 8
 int launch_final_gf(const FinalParams& p, float* kp, int* idx_out, double* fit, int* status, double* hess, hipStream_t stream);
+// the same with cov / info f64 [N*K][3] (gaussfit.h COV; final_gfcov_finish_kernel); both null: launch_final_gf's kernels
+int launch_final_gf_cov(const FinalParams& p, float* kp, int* idx_out, double* fit, int* status, double* hess, double* cov,
+                        double* info, double cov_floor, hipStream_t stream);
 // get_final2 keypoints without heat-maps, VALU output layer (final2_valu_kernel + final2_valu_finish_kernel): kp / idx_out
 // bit-identical to launch_final (VALU) + launch_keypoints_final2; p.part and bmax: [N*K][final2_valu_tiles] records, p.out
 // not used; cin <= 8
@@ -354,6 +357,16 @@ int launch_gaussfit_fit(const float* heat, const int* idx_in, int planes, int H,
 // the fit alone on NHWC heat-maps x [N][H][W][Cp] (fmt FMT_SB or FMT_F32) behind launch_keypoints_finish_nhwc; planes = N * C
 int launch_gaussfit_fit_nhwc(int fmt, const char* x, int N, int C, int H, int W, int Cp, const int* idx_in, float* kp, double* fit,
                              int* status, double* hess, hipStream_t stream);
+// the three with the covariance of the fitted centre (keypoints_gaussfit_cov.hip; gaussfit.h COV): cov f64 [planes][3] = s^2 (J^T
+// J)^-1's (x0, y0) block, crop px^2, and info f64 [planes][3] = -cov^-1, NaN x 3 also where cov[0] < cov_floor (either may be null;
+// both null: the launches above, nothing else).  kp, idx, fit, status, hess: the bits of the launches above.  cov_floor >= 0.
+int launch_keypoints_gaussfit_cov(const float* heat, int planes, int H, int W, float* kp, int* idx_out, double* fit, int* status,
+                                  double* hess, double* cov, double* info, double cov_floor, hipStream_t stream);
+int launch_gaussfit_fit_cov(const float* heat, const int* idx_in, int planes, int H, int W, float* kp, double* fit, int* status,
+                            double* hess, double* cov, double* info, double cov_floor, hipStream_t stream);
+int launch_gaussfit_fit_nhwc_cov(int fmt, const char* x, int N, int C, int H, int W, int Cp, const int* idx_in, float* kp,
+                                 double* fit, int* status, double* hess, double* cov, double* info, double cov_floor,
+                                 hipStream_t stream);
 
 // ---- crop + edge-pad + 8-bit bilinear resize + normalise: u8 frames -> f32 [N][1][S][S] (crops.hip) ----
 int launch_crops(const unsigned char* frames, const int* boxes, float* out, int N, int FH, int FW, int S,
@@ -376,6 +389,9 @@ int launch_mark_invalid(const int* valid, int m, int K, float* kp, int* idx, hip
 // int32 [m][K] -> -1
 int launch_mark_invalid_gaussfit(const int* valid, int m, int K, float* kp, int* idx, double* fit, int* status, double* hess,
                                  hipStream_t s);
+// the same plus cov and info f64 [m][K][3] (may be null) -> NaN (mark_invalid_gfcov_kernel)
+int launch_mark_invalid_gaussfit_cov(const int* valid, int m, int K, float* kp, int* idx, double* fit, int* status, double* hess,
+                                     double* cov, double* info, hipStream_t s);
 
 // ---- keypoints -> the record the pose solver consumes (correspond.hip, correspond.h) ----------------------------------
 // kp f32 [m][K][3], hess f64 [m][K][3] (mode 1; may be null in mode 0), crop / rates / valid as launch_boxes wrote them ->

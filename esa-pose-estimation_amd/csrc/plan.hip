@@ -1646,6 +1646,11 @@ struct Buffers {
     bool gaussfit = false;
     double* fit = nullptr;
     int* status = nullptr;
+    // esahrnet_forward_keypoints_gaussfit_cov: f64 [n * K][3] each, the covariance of the fitted centre and -cov^-1 (both nullptr:
+    // not asked for, the kernels of esahrnet_forward_keypoints_gaussfit)
+    double* cov = nullptr;
+    double* info = nullptr;
+    double cov_floor = 0.0;
 };
 
 // What esahrnet_forward_keypoints keeps behind the forward's workspace (at ShapePlan::bytes, a multiple of 256): the per-tile
@@ -1816,8 +1821,8 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                     rc = esa::launch_keypoints_finish_nhwc(fmt, T(o.in), n, K, height, width, Cp, b.kpart,
                                                            esa::to_nchw_part_tiles(height, width), b.kp, idx, stream);
                 if (!rc)
-                    rc = esa::launch_gaussfit_fit_nhwc(fmt, T(o.in), n, K, height, width, Cp, idx, b.kp, b.fit, b.status, b.hess,
-                                                       stream);
+                    rc = esa::launch_gaussfit_fit_nhwc_cov(fmt, T(o.in), n, K, height, width, Cp, idx, b.kp, b.fit, b.status, b.hess,
+                                                           b.cov, b.info, b.cov_floor, stream);
             } else if (b.kp && b.final2)                // esahrnet_forward_keypoints_final2: get_final2 on the NHWC maps
                 rc = esa::launch_keypoints_final2_nhwc(fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
                                                        b.kp, b.idx, b.kpart, b.kws, stream, b.hess);
@@ -2061,7 +2066,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             } else if (b.kp && b.gaussfit && !c.final_wpk) { // esahrnet_forward_keypoints_gaussfit, VALU: no heat-maps at all
                 p.out = nullptr;
                 p.part = b.kpart;
-                rc = esa::launch_final_gf(p, b.kp, b.idx, b.fit, b.status, b.hess, stream);
+                rc = esa::launch_final_gf_cov(p, b.kp, b.idx, b.fit, b.status, b.hess, b.cov, b.info, b.cov_floor, stream);
             } else if (b.kp && b.gaussfit) {            // ... matrix-core: heat-maps and maxima into the scratch, then the fit on them
                 int* const idx = b.idx ? b.idx : b.status;
                 p.out = b.kheat;
@@ -2070,7 +2075,9 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 if (!rc)
                     rc = esa::launch_keypoints_finish(p.out, p.part, esa::final_part_tiles(p.K, p.cin, height, width), n * p.K,
                                                       height, width, b.kp, idx, stream);
-                if (!rc) rc = esa::launch_gaussfit_fit(p.out, idx, n * p.K, height, width, b.kp, b.fit, b.status, b.hess, stream);
+                if (!rc)
+                    rc = esa::launch_gaussfit_fit_cov(p.out, idx, n * p.K, height, width, b.kp, b.fit, b.status, b.hess, b.cov, b.info,
+                                                      b.cov_floor, stream);
             } else if (b.kp && b.final2 && !c.final_wpk) {   // esahrnet_forward_keypoints_final2, VALU: the blurring output layer
                 p.out = nullptr;
                 p.part = b.kpart;
@@ -2105,7 +2112,8 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
 static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, int width,
                        void* heat_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream_,
                        hipEvent_t* events, void* part_dev = nullptr, void* kp_dev = nullptr, void* idx_dev = nullptr,
-                       bool final2 = false, void* hess_dev = nullptr, void* fit_dev = nullptr, void* status_dev = nullptr) {
+                       bool final2 = false, void* hess_dev = nullptr, void* fit_dev = nullptr, void* status_dev = nullptr,
+                       void* cov_dev = nullptr, void* info_dev = nullptr, double cov_floor = 0.0) {
     if (!h || !x_dev || !(heat_dev || kp_dev) || !ws_dev) return fail("forward: null argument");
     if (!h->committed) return fail("forward: esahrnet_commit has not been called");
     if (plan_shape(*h, n, height, width)) return 1;
@@ -2127,6 +2135,9 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
         bufs.fit = static_cast<double*>(fit_dev);
         bufs.status = static_cast<int*>(status_dev);
         bufs.hess = final2 || status_dev ? static_cast<double*>(hess_dev) : nullptr;
+        bufs.cov = status_dev ? static_cast<double*>(cov_dev) : nullptr;
+        bufs.info = status_dev ? static_cast<double*>(info_dev) : nullptr;
+        bufs.cov_floor = cov_floor;
     }
     int op_index = 0;
     if (events && hipEventRecord(events[0], stream) != hipSuccess) return fail("forward: hipEventRecord failed");
@@ -2293,6 +2304,25 @@ int esahrnet_forward_keypoints_gaussfit(esahrnet_handle h, const void* x_dev, in
                        hess_dev, fit_dev, status_dev);
 }
 
+// what the _cov entries refuse about their three additions
+static int check_cov_args(const char* who, const void* cov_dev, const void* info_dev, double cov_floor) {
+    if ((reinterpret_cast<uintptr_t>(cov_dev) | reinterpret_cast<uintptr_t>(info_dev)) & 7)
+        return fail("%s: cov_dev and info_dev must be 8-byte aligned", who);
+    if (!(cov_floor >= 0.0)) return fail("%s: cov_floor must be a number >= 0 (got %g)", who, cov_floor);
+    return 0;
+}
+
+int esahrnet_forward_keypoints_gaussfit_cov(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* kp_dev,
+                                            void* idx_dev, void* fit_dev, void* status_dev, void* hess_dev, void* cov_dev,
+                                            void* info_dev, double cov_floor, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
+    if (!h || !x_dev || !kp_dev || !status_dev || !ws_dev) return fail("forward_keypoints_gaussfit_cov: null argument");
+    if (check_gaussfit_outputs("forward_keypoints_gaussfit_cov", *h, kp_dev, idx_dev, fit_dev, status_dev, hess_dev) ||
+        check_cov_args("forward_keypoints_gaussfit_cov", cov_dev, info_dev, cov_floor))
+        return 1;
+    return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev, false,
+                       hess_dev, fit_dev, status_dev, cov_dev, info_dev, cov_floor);
+}
+
 int esahrnet_keypoints_finish(const void* heat_dev, const void* part_dev, int ntiles, int n, int k, int height, int width,
                               void* kp_dev, void* idx_dev, esahrnet_stream stream) {
     if (!heat_dev || !part_dev || !kp_dev || n <= 0 || k <= 0 || ntiles <= 0) return fail("keypoints_finish: bad argument");
@@ -2358,6 +2388,28 @@ int esahrnet_keypoints_gaussfit(const void* heat_dev, int n, int k, int height, 
                                                   static_cast<double*>(fit_dev), static_cast<int*>(status_dev),
                                                   static_cast<double*>(hess_dev), static_cast<hipStream_t>(stream));
     if (rc) return fail("keypoints_gaussfit: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
+int esahrnet_keypoints_gaussfit_cov(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev,
+                                    void* fit_dev, void* status_dev, void* hess_dev, void* cov_dev, void* info_dev, double cov_floor,
+                                    esahrnet_stream stream) {
+    if (!heat_dev || !kp_dev || !status_dev) return fail("keypoints_gaussfit_cov: null argument");
+    if (n <= 0 || k <= 0 || height <= 0 || width <= 0 || (long long)height * width > 0x7fffffffLL ||
+        (long long)n * k > 0x7fffffffLL)
+        return fail("keypoints_gaussfit_cov: bad shape %d x %d x %d x %d", n, k, height, width);
+    if ((reinterpret_cast<uintptr_t>(heat_dev) | reinterpret_cast<uintptr_t>(kp_dev) | reinterpret_cast<uintptr_t>(idx_dev) |
+         reinterpret_cast<uintptr_t>(status_dev)) & 3)
+        return fail("keypoints_gaussfit_cov: heat_dev, kp_dev, idx_dev and status_dev must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(fit_dev) | reinterpret_cast<uintptr_t>(hess_dev)) & 7)
+        return fail("keypoints_gaussfit_cov: fit_dev and hess_dev must be 8-byte aligned");
+    if (check_cov_args("keypoints_gaussfit_cov", cov_dev, info_dev, cov_floor)) return 1;
+    const int rc = esa::launch_keypoints_gaussfit_cov(static_cast<const float*>(heat_dev), n * k, height, width,
+                                                      static_cast<float*>(kp_dev), static_cast<int*>(idx_dev),
+                                                      static_cast<double*>(fit_dev), static_cast<int*>(status_dev),
+                                                      static_cast<double*>(hess_dev), static_cast<double*>(cov_dev),
+                                                      static_cast<double*>(info_dev), cov_floor, static_cast<hipStream_t>(stream));
+    if (rc) return fail("keypoints_gaussfit_cov: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return 0;
 }
 
@@ -2446,7 +2498,7 @@ static int frames_run(const char* who, esahrnet_handle h, const void* frames_dev
                       int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale, int rule, float mean,
                       float stdv, int decoder, void* kp_dev, void* idx_dev, void* hess_dev, void* crop_boxes_dev, void* rates_dev,
                       void* valid_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream, void* fit_dev = nullptr,
-                      void* status_dev = nullptr) {
+                      void* status_dev = nullptr, void* cov_dev = nullptr, void* info_dev = nullptr, double cov_floor = 0.0) {
     const hipStream_t st = static_cast<hipStream_t>(stream);
     int rc = esa::launch_boxes(static_cast<const int*>(det_boxes_dev), static_cast<const int*>(frame_idx_dev), nframes, m, frame_h,
                                frame_w, scale, rule, static_cast<int*>(crop_boxes_dev), static_cast<double*>(rates_dev),
@@ -2458,12 +2510,14 @@ static int frames_run(const char* who, esahrnet_handle h, const void* frames_dev
     if (rc) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)rc));
     const size_t head = frontend_crop_bytes(m, scale);
     if (run_forward(h, ws_dev, m, scale, scale, nullptr, static_cast<char*>(ws_dev) + head, ws_bytes - head, stream, nullptr, nullptr,
-                    kp_dev, idx_dev, decoder == 1, hess_dev, fit_dev, decoder == 2 ? status_dev : nullptr))
+                    kp_dev, idx_dev, decoder == 1, hess_dev, fit_dev, decoder == 2 ? status_dev : nullptr, cov_dev, info_dev, cov_floor))
         return 1;
     if (decoder == 2)
-        rc = esa::launch_mark_invalid_gaussfit(static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints,
-                                               static_cast<float*>(kp_dev), static_cast<int*>(idx_dev), static_cast<double*>(fit_dev),
-                                               static_cast<int*>(status_dev), static_cast<double*>(hess_dev), st);
+        rc = esa::launch_mark_invalid_gaussfit_cov(static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints,
+                                                   static_cast<float*>(kp_dev), static_cast<int*>(idx_dev),
+                                                   static_cast<double*>(fit_dev), static_cast<int*>(status_dev),
+                                                   static_cast<double*>(hess_dev), static_cast<double*>(cov_dev),
+                                                   static_cast<double*>(info_dev), st);
     else
         rc = esa::launch_mark_invalid(static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints, static_cast<float*>(kp_dev),
                                       static_cast<int*>(idx_dev), st);
@@ -2505,6 +2559,31 @@ int esahrnet_frames_keypoints_gaussfit_workspace_bytes(esahrnet_handle h, int m,
     if (esahrnet_keypoints_gaussfit_forward_workspace_bytes(h, m, scale, scale, &fw)) return 1;
     *bytes = frontend_crop_bytes(m, scale) + fw;
     return 0;
+}
+
+int esahrnet_frames_keypoints_gaussfit_cov(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                                           int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale,
+                                           int rule, float mean, float stdv, void* kp_dev, void* idx_dev, void* fit_dev,
+                                           void* status_dev, void* hess_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev,
+                                           void* cov_dev, void* info_dev, double cov_floor, void* ws_dev, size_t ws_bytes,
+                                           esahrnet_stream stream) {
+    const char* who = "frames_keypoints_gaussfit_cov";
+    if (!h || !frames_dev || !det_boxes_dev || !kp_dev || !status_dev || !crop_boxes_dev || !rates_dev || !valid_dev || !ws_dev)
+        return fail("%s: null argument", who);
+    // everything that can be refused is refused here, before the first launch; the order of esahrnet_frames_keypoints_gaussfit
+    if (check_boxes_args(who, m, frame_h, frame_w, scale, rule) || check_crops_args(who, nframes, pixel_format, stdv)) return 1;
+    if (!frame_idx_dev && m != nframes)
+        return fail("%s: %d boxes on %d frames need a frame index (NULL is the identity: box i lies on frame i)", who, m, nframes);
+    if (check_cov_args(who, cov_dev, info_dev, cov_floor)) return 1;
+    if (!h->committed) return fail("%s: esahrnet_commit has not been called", who);
+    if (check_gaussfit_outputs(who, *h, kp_dev, idx_dev, fit_dev, status_dev, hess_dev)) return 1;
+    size_t need = 0;
+    if (esahrnet_frames_keypoints_gaussfit_workspace_bytes(h, m, scale, &need)) return 1;
+    if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("%s: workspace must be 256-byte aligned", who);
+    return frames_run(who, h, frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m, scale, rule,
+                      mean, stdv, 2, kp_dev, idx_dev, hess_dev, crop_boxes_dev, rates_dev, valid_dev, ws_dev, ws_bytes, stream,
+                      fit_dev, status_dev, cov_dev, info_dev, cov_floor);
 }
 
 int esahrnet_frames_keypoints_gaussfit(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,

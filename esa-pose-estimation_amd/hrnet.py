@@ -27,7 +27,7 @@ import torch.nn as nn
 
 from . import _lib, crops
 from .fold import fold_conv
-from .inference import check_refine, check_weights, pack_correspondences, packed_layout
+from .inference import check_cov_floor, check_refine, check_weights, pack_correspondences, packed_layout
 
 logger = logging.getLogger(__name__)
 BN_MOMENTUM = 0.01           # models/seg_hrnet.py:23 (irrelevant at inference, kept for parity)
@@ -191,7 +191,7 @@ class HighResolutionNet(nn.Module):
 
     def frames_to_correspondences(self, frames: torch.Tensor, det_boxes, frame_idx=None, scale: int = 256, rule: str = "val",
                                   refine: str = "get_final", thresh: float = 0.8, min_k: int = 24, weights: str = "peak",
-                                  mean=None, std: float = crops.STD, pixel_format=None):
+                                  mean=None, std: float = crops.STD, pixel_format=None, cov_floor: float = 1e-6):
         """frames_to_keypoints and val.py:172-180 behind it in one library call (include/esahrnet.h
         esahrnet_frames_correspondences): -> (count int32 [m], order int32 [m,K], pts f64 [m,K,2], w f64 [m,K,3], kp, crop_boxes,
         rates, valid), all on the device.  The first four are the record the host pose solver consumes
@@ -199,12 +199,15 @@ class HighResolutionNet(nn.Module):
         2x2 weight (wxx, wxy, wyy) — weights="peak": (peak, 0, peak); "hessian" (refine="get_final2" or "gaussfit"): the
         decoder's Hessian as an information matrix, rate * (-H)^(1/2).  Equal, bit for bit, to frames_to_keypoints followed by
         inference.keypoints_to_correspondences; capturable into a graph.  refine="gaussfit": two library calls on one stream
-        (esahrnet_frames_keypoints_gaussfit, then esahrnet_correspondences on its outputs)."""
+        (esahrnet_frames_keypoints_gaussfit, then esahrnet_correspondences on its outputs).  weights="covariance"
+        (refine="gaussfit" only): esahrnet_frames_keypoints_gaussfit_cov, then esahrnet_correspondences(mode 1) with its info
+        output: w = rate cov^(-1/2), the covariance of the fitted centre (inference.gaussfit_keypoints return_cov=True), zero
+        where cov[0] < cov_floor."""
         return self._frames_to_correspondences(frames, det_boxes, frame_idx, scale, rule, refine, thresh, min_k, weights, mean, std,
-                                               pixel_format)[:8]
+                                               pixel_format, cov_floor)[:8]
 
     def _frames_to_correspondences(self, frames, det_boxes, frame_idx, scale, rule, refine, thresh, min_k, weights, mean, std,
-                                   pixel_format):
+                                   pixel_format, cov_floor=1e-6):
         """frames_to_correspondences, plus (packed,): count, order, pts and w are views of `packed` (one uint8 buffer,
         inference.pack_correspondences), which a caller that needs them on the host fetches with one copy."""
         if self.training:
@@ -212,11 +215,12 @@ class HighResolutionNet(nn.Module):
                                "(the reference callers do, val.py:95 / demo.py:80)")
         check_refine(refine)
         mode = check_weights(weights, refine)
+        cov = check_cov_floor(cov_floor) if weights == "covariance" else None
         rule_n, fmt, m = crops.check_device_loader_args(frames, det_boxes, frame_idx, rule, pixel_format)
         if mean is None:
             mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
         return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
-                                         REFINE_DECODER[refine], corr=(float(thresh), int(min_k), mode))
+                                         REFINE_DECODER[refine], corr=(float(thresh), int(min_k), mode), cov=cov)
 
     def keypoints_hessian(self, x0: torch.Tensor):
         """net(x, output="keypoints+index", refine="get_final2") with the Hessian of each step: -> (kp f32 [N,K,3], idx int32
@@ -228,14 +232,20 @@ class HighResolutionNet(nn.Module):
                                "(the reference callers do, val.py:95 / demo.py:80)")
         return self._rt.forward_final2(self, x0, True, want_hessian=True)
 
-    def keypoints_gaussfit(self, x0: torch.Tensor, return_fit: bool = False):
+    def keypoints_gaussfit(self, x0: torch.Tensor, return_fit: bool = False, return_cov: bool = False, cov_floor: float = 1e-6):
         """The forward with the Gaussian-fit decoder in place of its last launch (include/esahrnet.h
         esahrnet_forward_keypoints_gaussfit): -> (kp f32 [N,K,3], status int32 [N,K], hess f64 [N,K,3] = (-2a, -2b, -2c)), or
         with return_fit=True (kp, fit f64 [N,K,8], status, hess); bit-identical to inference.gaussfit_keypoints(net(x)), without
-        heat-maps in caller memory."""
+        heat-maps in caller memory.  return_cov=True (esahrnet_forward_keypoints_gaussfit_cov) appends (cov, info) f64 [N,K,3]
+        each, the covariance of the fitted centre and -cov^-1 as inference.gaussfit_keypoints(net(x), return_cov=True,
+        cov_floor=cov_floor) gives them, bit for bit; the other outputs keep their bits."""
         if self.training:
             raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
                                "(the reference callers do, val.py:95 / demo.py:80)")
+        if return_cov:
+            kp, fit, status, hess, _, cov, info = self._rt.forward_gaussfit(self, x0, bool(return_fit), False,
+                                                                            cov=check_cov_floor(cov_floor))
+            return (kp, fit, status, hess, cov, info) if return_fit else (kp, status, hess, cov, info)
         kp, fit, status, hess, _ = self._rt.forward_gaussfit(self, x0, bool(return_fit), False)
         return (kp, fit, status, hess) if return_fit else (kp, status, hess)
 
@@ -589,10 +599,11 @@ class _Runtime:
         x.record_stream(ts)
         return (kp, idx, hess) if want_hessian else (kp, idx)
 
-    def forward_gaussfit(self, module, x0, want_fit, want_index, want_hessian=True):
+    def forward_gaussfit(self, module, x0, want_fit, want_index, want_hessian=True, cov=None):
         """esahrnet_forward_keypoints_gaussfit: -> (kp f32 [N,K,3], fit f64 [N,K,8] or None, status int32 [N,K], hess f64 [N,K,3]
         or None, idx int32 [N,K] or None); nothing else reaches caller memory.  Same device lock, weight-staleness key,
-        workspace contract (graph capture included) and record_stream handling as forward_final2()."""
+        workspace contract (graph capture included) and record_stream handling as forward_final2().  cov = cov_floor (not
+        None): esahrnet_forward_keypoints_gaussfit_cov, -> (..., cov f64 [N,K,3], info f64 [N,K,3]) appended."""
         x = self._check_input(module, x0)
         n, _, hh, ww = x.shape
         dev = x.device
@@ -608,21 +619,35 @@ class _Runtime:
                 fit = torch.empty((n, k, 8), dtype=torch.float64, device=dev) if want_fit else None
                 status = torch.empty((n, k), dtype=torch.int32, device=dev)
                 hess = torch.empty((n, k, 3), dtype=torch.float64, device=dev) if want_hessian else None
-                _lib.check(self.lib.esahrnet_forward_keypoints_gaussfit(
-                    h, x.data_ptr(), n, hh, ww, kp.data_ptr(), idx.data_ptr() if want_index else None,
-                    fit.data_ptr() if want_fit else None, status.data_ptr(), hess.data_ptr() if want_hessian else None, ws_ptr,
-                    nbytes, C.c_void_p(ts.cuda_stream)))
+                if cov is not None:
+                    cv = torch.empty((n, k, 3), dtype=torch.float64, device=dev)
+                    info = torch.empty((n, k, 3), dtype=torch.float64, device=dev)
+                    _lib.check(self.lib.esahrnet_forward_keypoints_gaussfit_cov(
+                        h, x.data_ptr(), n, hh, ww, kp.data_ptr(), idx.data_ptr() if want_index else None,
+                        fit.data_ptr() if want_fit else None, status.data_ptr(), hess.data_ptr() if want_hessian else None,
+                        cv.data_ptr(), info.data_ptr(), float(cov), ws_ptr, nbytes, C.c_void_p(ts.cuda_stream)))
+                else:
+                    _lib.check(self.lib.esahrnet_forward_keypoints_gaussfit(
+                        h, x.data_ptr(), n, hh, ww, kp.data_ptr(), idx.data_ptr() if want_index else None,
+                        fit.data_ptr() if want_fit else None, status.data_ptr(), hess.data_ptr() if want_hessian else None, ws_ptr,
+                        nbytes, C.c_void_p(ts.cuda_stream)))
         ws.record_stream(ts)
         x.record_stream(ts)
+        if cov is not None:
+            return kp, fit, status, hess, idx, cv, info
         return kp, fit, status, hess, idx
 
-    def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None):
+    def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None, cov=None):
         """esahrnet_frames_keypoints (arguments already checked by crops.check_device_loader_args).  The outputs are views
         of one packed buffer: rates f64 [m] | kp f32 [m,K,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,K]
         (inference.packed_layout; decoder 2, the Gaussian fit, also fit, hess and status, returned behind `packed`).
         Same device lock, weight-staleness key, workspace contract (graph capture included) and record_stream handling as
         forward().  corr = (thresh, min_k, mode): esahrnet_frames_correspondences instead -> (count, order, pts, w, kp, boxes,
-        rates, valid, packed), the first four views of `packed` (inference.pack_correspondences)."""
+        rates, valid, packed), the first four views of `packed` (inference.pack_correspondences).  cov = cov_floor (decoder 2
+        only): esahrnet_frames_keypoints_gaussfit_cov; cov and info ride in `packed` behind hess and are returned last, and the
+        correspondences, if asked for with mode 1, take info in hess' place."""
+        if cov is not None and decoder != 2:
+            raise ValueError("the covariance of the fitted centre belongs to the Gaussian-fit decoder")
         if module._cin != 1:
             raise ValueError(f"the loader makes 1-channel crops; this network takes {module._cin} channels")
         if "_master" not in module.__dict__:
@@ -637,7 +662,7 @@ class _Runtime:
         with torch.cuda.device(dev):
             det = crops.to_device_int32(det_boxes, dev)
             fidx = None if frame_idx is None else crops.to_device_int32(frame_idx, dev)
-            lay = packed_layout(m, k, decoder == 2)
+            lay = packed_layout(m, k, decoder == 2, cov is not None)
             packed = torch.empty(lay["total"][1], dtype=torch.uint8, device=dev)
 
             def part(name, dtype, *shape):
@@ -652,20 +677,31 @@ class _Runtime:
             if decoder == 2:
                 fit, status, hess = part("fit", torch.float64, m, k, 8), part("status", torch.int32, m, k), \
                     part("hess", torch.float64, m, k, 3)
+            if cov is not None:
+                cv, info = part("cov", torch.float64, m, k, 3), part("info", torch.float64, m, k, 3)
             with self._device_lock(dev.index):
                 h = self._handle_for(module, dev)
                 _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
                 if decoder == 2:                    # its own entry point; the correspondences, if asked for, behind it
                     ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, "gaussfit", kind="frames_gaussfit")
-                    _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit(
-                        h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m,
-                        scale, rule, mean, std, kp.data_ptr(), idx.data_ptr(), fit.data_ptr(), status.data_ptr(), hess.data_ptr(),
-                        boxes.data_ptr(), rates.data_ptr(), valid.data_ptr(), ws_ptr, ws_bytes, C.c_void_p(ts.cuda_stream)))
+                    if cov is not None:
+                        _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit_cov(
+                            h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(),
+                            m, scale, rule, mean, std, kp.data_ptr(), idx.data_ptr(), fit.data_ptr(), status.data_ptr(),
+                            hess.data_ptr(), boxes.data_ptr(), rates.data_ptr(), valid.data_ptr(), cv.data_ptr(), info.data_ptr(),
+                            float(cov), ws_ptr, ws_bytes, C.c_void_p(ts.cuda_stream)))
+                    else:
+                        _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit(
+                            h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(),
+                            m, scale, rule, mean, std, kp.data_ptr(), idx.data_ptr(), fit.data_ptr(), status.data_ptr(),
+                            hess.data_ptr(), boxes.data_ptr(), rates.data_ptr(), valid.data_ptr(), ws_ptr, ws_bytes,
+                            C.c_void_p(ts.cuda_stream)))
                     if corr is not None:
                         thresh, min_k, mode = corr
                         count, order, pts, w, cpacked = pack_correspondences(m, k, dev)
+                        wsrc = info if cov is not None else hess         # weights="covariance": -cov^-1 in the Hessian's place
                         _lib.check(self.lib.esahrnet_correspondences(
-                            kp.data_ptr(), hess.data_ptr() if mode else None, boxes.data_ptr(), rates.data_ptr(), valid.data_ptr(),
+                            kp.data_ptr(), wsrc.data_ptr() if mode else None, boxes.data_ptr(), rates.data_ptr(), valid.data_ptr(),
                             m, k, thresh, min_k, mode, count.data_ptr(), order.data_ptr(), pts.data_ptr(), w.data_ptr(),
                             C.c_void_p(ts.cuda_stream)))
                     for t in (ws, frames, det, fidx):
@@ -673,6 +709,8 @@ class _Runtime:
                             t.record_stream(ts)
                     if corr is not None:
                         return count, order, pts, w, kp, boxes, rates, valid, cpacked
+                    if cov is not None:
+                        return kp, boxes, rates, valid, idx, packed, fit, status, hess, cv, info
                     return kp, boxes, rates, valid, idx, packed, fit, status, hess
                 if corr is not None:
                     thresh, min_k, mode = corr

@@ -116,19 +116,40 @@ def heatmaps_to_keypoints(heat: torch.Tensor, refine: str = "get_final", return_
     return (out[0], out[2]) if return_hessian else out[0]
 
 
-def gaussfit_keypoints(heat: torch.Tensor):
+def check_cov_floor(cov_floor) -> float:
+    """cov_floor of the covariance outputs: a number >= 0 (the reference's evaluation.py:479 uses 1e-6)."""
+    try:
+        f = float(cov_floor)
+    except (TypeError, ValueError):
+        raise ValueError(f"cov_floor must be a number >= 0, got {cov_floor!r}") from None
+    if not f >= 0.0:
+        raise ValueError(f"cov_floor must be a number >= 0, got {cov_floor!r}")
+    return f
+
+
+def gaussfit_keypoints(heat: torch.Tensor, return_cov: bool = False, cov_floor: float = 1e-6):
     """The third decoder (include/esahrnet.h esahrnet_keypoints_gaussfit): offset + A exp(-(a dx^2 + 2 b dx dy + c dy^2)) fitted
     on the device to the 13 x 13 window around each plane's arg-max, the fit the reference's test.py makes with curve_fit.
     f32 cuda [N,K,H,W] -> (kp f32 [N,K,3] = (x0, y0, raw peak); fit f64 [N,K,8] = (A, x0, y0, a, b, c, off, cost); status int32
     [N,K], 0 = accepted; hess f64 [N,K,3] = (-2a, -2b, -2c)).  A rejected keypoint (status 1, 2, 3) keeps the get_final row of
-    heatmaps_to_keypoints, its fit and hess are NaN.  hess is what keypoints_to_correspondences(weights="hessian") takes."""
-    return _gaussfit(heat, False)[:4]
+    heatmaps_to_keypoints, its fit and hess are NaN.  hess is what keypoints_to_correspondences(weights="hessian") takes.
+    return_cov=True (esahrnet_keypoints_gaussfit_cov): -> (kp, fit, status, hess, cov, info), the same bits in the first four; cov
+    f64 [N,K,3] = (cxx, cxy, cyy), the (x0, y0) block of curve_fit's pcov = cost / (n - 7) (J^T J)^-1 in crop px^2, NaN for a
+    rejected fit or a window of at most 7 pixels; info f64 [N,K,3] = -cov^-1, NaN also where cxx < cov_floor (the reference's
+    guard, evaluation.py:479): what keypoints_to_correspondences(weights="covariance") takes in hess' place."""
+    if not return_cov:
+        return _gaussfit(heat, False)[:4]
+    out = _gaussfit(heat, False, True, cov_floor)
+    return out[:4] + out[5:]
 
 
-def _gaussfit(heat: torch.Tensor, want_index: bool):
-    """gaussfit_keypoints, plus idx int32 [N,K] (None unless asked for): -> (kp, fit, status, hess, idx)."""
+def _gaussfit(heat: torch.Tensor, want_index: bool, want_cov: bool = False, cov_floor: float = 1e-6):
+    """gaussfit_keypoints, plus idx int32 [N,K] (None unless asked for): -> (kp, fit, status, hess, idx), with want_cov (kp, fit,
+    status, hess, idx, cov, info)."""
     if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
         raise ValueError("expected a 4-D tensor [N, K, H, W]")
+    if want_cov:
+        cov_floor = check_cov_floor(cov_floor)
     if not heat.is_cuda:
         raise RuntimeError("gaussfit_keypoints runs on the GPU only (no CPU fallback)")
     if heat.dtype != torch.float32:
@@ -143,6 +164,14 @@ def _gaussfit(heat: torch.Tensor, want_index: bool):
         status = torch.empty((n, k), dtype=torch.int32, device=dev)
         hess = torch.empty((n, k, 3), dtype=torch.float64, device=dev)
         idx = torch.empty((n, k), dtype=torch.int32, device=dev) if want_index else None
+        if want_cov:
+            cov = torch.empty((n, k, 3), dtype=torch.float64, device=dev)
+            info = torch.empty((n, k, 3), dtype=torch.float64, device=dev)
+            _lib.check(_lib.lib().esahrnet_keypoints_gaussfit_cov(heat.data_ptr(), n, k, h, w, kp.data_ptr(),
+                                                                  idx.data_ptr() if want_index else None, fit.data_ptr(),
+                                                                  status.data_ptr(), hess.data_ptr(), cov.data_ptr(),
+                                                                  info.data_ptr(), cov_floor, C.c_void_p(stream)))
+            return kp, fit, status, hess, idx, cov, info
         _lib.check(_lib.lib().esahrnet_keypoints_gaussfit(heat.data_ptr(), n, k, h, w, kp.data_ptr(),
                                                           idx.data_ptr() if want_index else None, fit.data_ptr(),
                                                           status.data_ptr(), hess.data_ptr(), C.c_void_p(stream)))
@@ -169,25 +198,33 @@ def gaussfit_sigma_theta(fit):
     return sx, sy, th
 
 
-WEIGHTS = ("peak", "hessian")
+WEIGHTS = ("peak", "hessian", "covariance")
 
 
 def check_weights(weights, refine="get_final2"):
-    """The weight of the pose refinement: "peak" (default; val.py:194-209) or "hessian" (the decoder's Hessian as the 2x2
-    weight uncertainty_pnp.cpp takes; needs refine="get_final2" or "gaussfit").  -> the mode of esahrnet_correspondences."""
+    """The weight of the pose refinement: "peak" (default; val.py:194-209), "hessian" (the decoder's Hessian as the 2x2
+    weight uncertainty_pnp.cpp takes; needs refine="get_final2" or "gaussfit") or "covariance" (refine="gaussfit" only: the
+    covariance of the fitted centre, inv(sqrtm(covar)) as evaluation.py:471-487 forms it; its info output goes where the Hessian
+    goes).  -> the mode of esahrnet_correspondences."""
     if not isinstance(weights, str) or weights not in WEIGHTS:
         raise ValueError(f"weights must be one of {WEIGHTS}, got {weights!r}")
     if weights == "hessian" and refine not in ("get_final2", "gaussfit"):
         raise ValueError("weights='hessian' needs refine='get_final2' or 'gaussfit': get_final computes no Hessian")
-    return WEIGHTS.index(weights)
+    if weights == "covariance" and refine != "gaussfit":
+        raise ValueError("weights='covariance' needs refine='gaussfit': only the Gaussian fit has a parameter covariance")
+    return int(weights != "peak")
 
 
-def packed_layout(m: int, k: int, gaussfit: bool = False):
+def packed_layout(m: int, k: int, gaussfit: bool = False, cov: bool = False):
     """The packed buffer of net.frames_to_keypoints' outputs: name -> (offset, bytes).  rates f64 [m] | kp f32 [m,k,3] |
     crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,k]; with gaussfit the decoder's f64 outputs come right behind
     rates (8-byte aligned) and its status last: rates | fit f64 [m,k,8] | hess f64 [m,k,3] | kp | crop_boxes | valid | idx |
-    status int32 [m,k].  "total" -> (0, bytes of the buffer)."""
+    status int32 [m,k]; with cov (gaussfit only) cov f64 [m,k,3] | info f64 [m,k,3] follow hess.  "total" -> (0, bytes of the
+    buffer)."""
+    if cov and not gaussfit:
+        raise ValueError("cov=True belongs to gaussfit=True")
     parts = [("rates", 8 * m)] + ([("fit", 64 * m * k), ("hess", 24 * m * k)] if gaussfit else [])
+    parts += [("cov", 24 * m * k), ("info", 24 * m * k)] if cov else []
     parts += [("kp", 12 * m * k), ("boxes", 16 * m), ("valid", 4 * m), ("idx", 4 * m * k)]
     parts += [("status", 4 * m * k)] if gaussfit else []
     out, off = {}, 0
@@ -228,8 +265,9 @@ def keypoints_to_correspondences(kp: torch.Tensor, crop_boxes: torch.Tensor, rat
     """val.py:172-180 on the device (include/esahrnet.h esahrnet_correspondences): kp f32 cuda [m,K,3] and the crop boxes
     int32 [m,4], rates f64 [m] and valid int32 [m] of net.frames_to_keypoints / crops.crop_batch_device -> (count int32 [m],
     order int32 [m,K], pts f64 [m,K,2], w f64 [m,K,3]) on the device: what select_keypoints + crop_to_image give, bit for bit,
-    and the weight of each point.  weights="hessian" takes hess f64 [m,K,3] (heatmaps_to_keypoints(..., return_hessian=True))."""
-    mode = check_weights(weights)
+    and the weight of each point.  weights="hessian" takes hess f64 [m,K,3] (heatmaps_to_keypoints(..., return_hessian=True));
+    weights="covariance" takes, as hess, the info f64 [m,K,3] of gaussfit_keypoints(..., return_cov=True): w = rate cov^(-1/2)."""
+    mode = check_weights(weights, "gaussfit" if weights == "covariance" else "get_final2")
     if not (isinstance(kp, torch.Tensor) and kp.is_cuda and kp.dtype == torch.float32 and kp.dim() == 3 and kp.shape[2] == 3):
         raise ValueError("kp must be a float32 cuda tensor [m, K, 3]")
     m, k = kp.shape[:2]

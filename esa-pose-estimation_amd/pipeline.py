@@ -111,7 +111,7 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
                    min_k: int = 24, distributed: bool = False, pool=None, native: bool = True,
                    on_fail: str = "raise", keypoints_only: bool = False, refine: str = "get_final",
                    device_loader: bool = False, frame_idx=None, rule: str = "val", device_select: bool = False,
-                   weights: str = "peak", threads: int = 0):
+                   weights: str = "peak", threads: int = 0, cov_floor: float = 1e-6):
     """One batch of the val.py:136-233 loop.  frames uint8 cuda [N,H,W]; bboxes N x (x, y, x2, y2);
     kp3d [K3, 3] model keypoints; K camera matrix.  -> list of (q [w,x,y,z], t) per image.
     An image without a solution (the native solver reports it as a NaN row; the reference would die inside
@@ -131,19 +131,26 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
     refine="get_final2" or "gaussfit"): the refinement weighs each point by the decoder's Hessian, rate * (-H)^(1/2), the
     anisotropic weight uncertainty_pnp.cpp:30-31 takes, instead of the scalar peak.  refine="gaussfit": the Gaussian-fit decoder
     (inference.gaussfit_keypoints) on every path; device_loader=True still fetches one packed buffer (the decoder's fit, Hessian
-    and status ride in it, inference.packed_layout)."""
+    and status ride in it, inference.packed_layout).  weights="covariance" (device_select=True and refine="gaussfit"): each point
+    is weighed by the covariance of its fitted centre, rate * cov^(-1/2) (inv(sqrtm(covar)) of the reference's
+    evaluation.py:471-487), which grows with the residual noise of the fit and not only with the blob's width; a point with
+    cov[0] < cov_floor or without a covariance gets weight zero."""
     inference.check_refine(refine)
     inference.check_weights(weights, refine)
     if weights != "peak" and not device_select:
-        raise ValueError("weights='hessian' belongs to device_select=True (the host selection weighs by the peak)")
+        raise ValueError(f"weights='{weights}' belongs to device_select=True (the host selection weighs by the peak)")
     if device_select:
         if distributed:
             raise ValueError("device_select=True runs on one device (distributed=True shards crops that exist on the host side)")
         if not native:
             raise ValueError("device_select=True hands its record to the native solver (native=False has no entry for it)")
         with torch.no_grad():
-            out = net._frames_to_correspondences(frames, bboxes, frame_idx, scale, rule, refine, thresh, min_k, weights, None,
-                                                 crops.STD, None)
+            if weights == "covariance":
+                out = net._frames_to_correspondences(frames, bboxes, frame_idx, scale, rule, refine, thresh, min_k, weights, None,
+                                                     crops.STD, None, cov_floor)
+            else:
+                out = net._frames_to_correspondences(frames, bboxes, frame_idx, scale, rule, refine, thresh, min_k, weights, None,
+                                                     crops.STD, None)
         m, k = out[4].shape[:2]
         count, order, pts, w = inference.unpack_correspondences(out[8].cpu().numpy(), m, k)     # the only device->host copy
         q, t = pnp.correspondences_to_pose_batch(pts, w, count, order, kp3d, np.asarray(K, np.float64), threads)

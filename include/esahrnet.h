@@ -321,6 +321,48 @@ int esahrnet_frames_keypoints_gaussfit(esahrnet_handle h, const void* frames_dev
                                        void* crop_boxes_dev, void* rates_dev, void* valid_dev,
                                        void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
 
+/* ---- the Gaussian fit with the covariance of the fitted centre ------------------------------------------------------------------
+ * What scipy's curve_fit returns beside the parameters (the reference's test.py:43 `popt, pcov`), for the centre: the (x0, y0)
+ * block of pcov = s^2 (J^T J)^-1, s^2 = cost / (n - 7).  Unlike hess_dev, which describes the shape of the blob, it grows with the
+ * residual noise and shrinks with the amplitude; evaluation.py:471-487 turns such a covariance into the PnP weight inv(sqrtm(covar))
+ * and gives weight zero where covar[0, 0] < 1e-6 or NaN.  Each of the three entries below is its sibling without _cov with three
+ * more arguments; an accepted fit (status 0) goes on as follows, every lane the same, contraction off, sums in the fit's order:
+ *   1. residuals and the analytic Jacobian once more, at the returned parameters; N = J^T J (7 x 7) with the per-lane slot order
+ *      and the butterfly of the iteration, so that a plane's result does not depend on its batch;
+ *   2. dof = n - 7, n the number of window pixels; s^2 = cost / dof, cost the value in fit_dev[7];
+ *   3. N factored by the iteration's Cholesky with lambda = 0 (no damping); the x0 and the y0 column of N^-1 by its two
+ *      triangular solves;
+ *   4. cov = s^2 (N^-1[1][1], N^-1[2][1], N^-1[2][2]) = (cxx, cxy, cyy), in crop px^2;
+ *   5. det = cxx cyy - cxy cxy;  info = (-(cyy / det), cxy / det, -(cxx / det)) = -cov^-1, plain IEEE operations in this order.
+ *   cov_dev  f64 [n][k][3]   NaN x 3 when the fit is rejected, dof <= 0, a pivot is not positive or a value of cov is not finite
+ *                            (NULL: not written).
+ *   info_dev f64 [n][k][3]   NaN x 3 where cov is NaN, det is not positive, or cxx < cov_floor (the reference's guard looks at
+ *                            covar[0, 0] only) (NULL: not written).  It is, as it stands, a hess_dev of
+ *                            esahrnet_correspondences(mode 1): w = rate (-info)^(1/2) = rate cov^(-1/2), inv(sqrtm(covar)) in image
+ *                            pixels, and weight zero where it is NaN, as for a rejected fit.
+ *   cov_floor                a number >= 0 (the reference: 1e-6); NaN or a negative value is an argument error.
+ * The status is not changed by any of this: it describes the fit only.  With both pointers NULL a call launches exactly the
+ * kernels of its sibling; with either given, kp_dev, idx_dev, fit_dev, status_dev and hess_dev are bit-identical to the sibling's
+ * (the fit kernel is instantiated with the covariance pass behind the same code).  cov_dev and info_dev must be 8-byte aligned.
+ * Every argument error, the sibling's included, is reported before anything is enqueued; the calls allocate nothing, do not
+ * synchronise and may be captured into a graph.  esahrnet_forward_keypoints_gaussfit_cov takes the workspace of
+ * esahrnet_keypoints_gaussfit_forward_workspace_bytes, esahrnet_frames_keypoints_gaussfit_cov that of
+ * esahrnet_frames_keypoints_gaussfit_workspace_bytes; in the latter the rows of an invalid crop are NaN in cov_dev and info_dev too. */
+int esahrnet_keypoints_gaussfit_cov(const void* heat_dev, int n, int k, int height, int width,
+                                    void* kp_dev, void* idx_dev, void* fit_dev, void* status_dev, void* hess_dev,
+                                    void* cov_dev, void* info_dev, double cov_floor, esahrnet_stream stream);
+int esahrnet_forward_keypoints_gaussfit_cov(esahrnet_handle h, const void* x_dev, int n, int height, int width,
+                                            void* kp_dev, void* idx_dev, void* fit_dev, void* status_dev, void* hess_dev,
+                                            void* cov_dev, void* info_dev, double cov_floor,
+                                            void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+int esahrnet_frames_keypoints_gaussfit_cov(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                                           int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m,
+                                           int scale, int rule, float mean, float stdv,
+                                           void* kp_dev, void* idx_dev, void* fit_dev, void* status_dev, void* hess_dev,
+                                           void* crop_boxes_dev, void* rates_dev, void* valid_dev,
+                                           void* cov_dev, void* info_dev, double cov_floor,
+                                           void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+
 /* ---- keypoints to the record the pose solver consumes, on the device (val.py:172-180) -------------------------------------
  * esahrnet_correspondences (correspond_kernel, one wave per crop, k <= 32): kp_dev f32 [m][k][3] keypoint rows, crop_boxes_dev /
  *   rates_dev / valid_dev as esahrnet_boxes wrote them ->
