@@ -136,6 +136,7 @@ _SIGS = {
                                                   C.c_void_p]),
     "esahrnet_pnp_batch_w": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_void_p, C.c_void_p]),
+    "esahrnet_gather_records": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p]),
     "esahrnet_flops_per_crop": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "esahrnet_launch_count": (C.c_int, [C.c_void_p]),
     "esahrnet_op_desc_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OpDesc)]),

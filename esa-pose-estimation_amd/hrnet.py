@@ -208,8 +208,9 @@ class HighResolutionNet(nn.Module):
 
     def _frames_to_correspondences(self, frames, det_boxes, frame_idx, scale, rule, refine, thresh, min_k, weights, mean, std,
                                    pixel_format, cov_floor=1e-6):
-        """frames_to_correspondences, plus (packed,): count, order, pts and w are views of `packed` (one uint8 buffer,
-        inference.pack_correspondences), which a caller that needs them on the host fetches with one copy."""
+        """frames_to_correspondences, plus (cpacked, packed): count, order, pts and w are views of `cpacked` (one uint8 buffer,
+        inference.pack_correspondences), which a caller that needs them on the host fetches with one copy; kp, crop_boxes, rates
+        and valid are views of `packed`, the keypoint record (inference.packed_layout), as _frames_to_keypoints returns it."""
         if self.training:
             raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
                                "(the reference callers do, val.py:95 / demo.py:80)")
@@ -249,10 +250,11 @@ class HighResolutionNet(nn.Module):
         kp, fit, status, hess, _ = self._rt.forward_gaussfit(self, x0, bool(return_fit), False)
         return (kp, fit, status, hess) if return_fit else (kp, status, hess)
 
-    def _frames_to_keypoints(self, frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format):
+    def _frames_to_keypoints(self, frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format, cov_floor=None):
         """frames_to_keypoints, plus (idx int32 [m,K], packed): every output is a view of `packed` (one uint8 buffer), so a
         caller that needs them on the host fetches them with one copy (pipeline.estimate_poses).  refine="gaussfit": plus (fit
-        f64 [m,K,8], status int32 [m,K], hess f64 [m,K,3]), views of `packed` too (inference.packed_layout)."""
+        f64 [m,K,8], status int32 [m,K], hess f64 [m,K,3]), views of `packed` too (inference.packed_layout); with cov_floor
+        (refine="gaussfit" only) plus (cov, info) f64 [m,K,3] behind them (esahrnet_frames_keypoints_gaussfit_cov)."""
         if self.training:
             raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
                                "(the reference callers do, val.py:95 / demo.py:80)")
@@ -260,8 +262,9 @@ class HighResolutionNet(nn.Module):
         rule_n, fmt, m = crops.check_device_loader_args(frames, det_boxes, frame_idx, rule, pixel_format)
         if mean is None:
             mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
+        cov = None if cov_floor is None else check_cov_floor(cov_floor)
         return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
-                                         REFINE_DECODER[refine])
+                                         REFINE_DECODER[refine], cov=cov)
 
     # ---- extras of the MI355X path ---------------------------------------------------------------
     @property
@@ -643,7 +646,7 @@ class _Runtime:
         (inference.packed_layout; decoder 2, the Gaussian fit, also fit, hess and status, returned behind `packed`).
         Same device lock, weight-staleness key, workspace contract (graph capture included) and record_stream handling as
         forward().  corr = (thresh, min_k, mode): esahrnet_frames_correspondences instead -> (count, order, pts, w, kp, boxes,
-        rates, valid, packed), the first four views of `packed` (inference.pack_correspondences).  cov = cov_floor (decoder 2
+        rates, valid, cpacked, packed), the first four views of `cpacked` (inference.pack_correspondences), the next four of `packed`.  cov = cov_floor (decoder 2
         only): esahrnet_frames_keypoints_gaussfit_cov; cov and info ride in `packed` behind hess and are returned last, and the
         correspondences, if asked for with mode 1, take info in hess' place."""
         if cov is not None and decoder != 2:
@@ -708,7 +711,7 @@ class _Runtime:
                         if t is not None:
                             t.record_stream(ts)
                     if corr is not None:
-                        return count, order, pts, w, kp, boxes, rates, valid, cpacked
+                        return count, order, pts, w, kp, boxes, rates, valid, cpacked, packed
                     if cov is not None:
                         return kp, boxes, rates, valid, idx, packed, fit, status, hess, cv, info
                     return kp, boxes, rates, valid, idx, packed, fit, status, hess
@@ -724,7 +727,7 @@ class _Runtime:
                     for t in (ws, frames, det, fidx):
                         if t is not None:
                             t.record_stream(ts)
-                    return count, order, pts, w, kp, boxes, rates, valid, cpacked
+                    return count, order, pts, w, kp, boxes, rates, valid, cpacked, packed
                 ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, bool(decoder),
                                                        kind="frames_final2" if decoder else "frames")
                 _lib.check(self.lib.esahrnet_frames_keypoints(

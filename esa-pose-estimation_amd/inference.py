@@ -250,6 +250,51 @@ def pack_correspondences(m: int, k: int, device):
     return count, order, pts, w, packed
 
 
+RECORD_KINDS = ("keypoints", "correspondences")
+# element type and trailing shape of every field of the two packed records (k = keypoints per crop)
+_RECORD_TYPES = {"rates": (torch.float64, ()), "fit": (torch.float64, ("k", 8)), "hess": (torch.float64, ("k", 3)),
+                 "cov": (torch.float64, ("k", 3)), "info": (torch.float64, ("k", 3)), "kp": (torch.float32, ("k", 3)),
+                 "boxes": (torch.int32, (4,)), "valid": (torch.int32, ()), "idx": (torch.int32, ("k",)),
+                 "status": (torch.int32, ("k",)), "pts": (torch.float64, ("k", 2)), "w": (torch.float64, ("k", 3)),
+                 "count": (torch.int32, ()), "order": (torch.int32, ("k",))}
+
+
+def record_fields(k: int, kind: str, gaussfit: bool = False, cov: bool = False):
+    """The fields of a packed record in memory order, as ((name, bytes per crop), ...): kind="keypoints" the buffer of
+    packed_layout(m, k, gaussfit, cov), kind="correspondences" the buffer of pack_correspondences.  A record is field-major, so
+    field f of m crops takes m * bytes and starts at m * (the bytes of the fields in front of it); every size is a multiple of 4.
+    This is the description the exchange of a sharded batch works from (parallel.gather_records, esahrnet_gather_records)."""
+    if kind not in RECORD_KINDS:
+        raise ValueError(f"kind must be one of {RECORD_KINDS}, got {kind!r}")
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k = {k}: a record has at least one keypoint per crop")
+    if kind == "correspondences":
+        if gaussfit or cov:
+            raise ValueError("gaussfit and cov belong to kind='keypoints'")
+        return (("pts", 16 * k), ("w", 24 * k), ("count", 4), ("order", 4 * k))
+    if cov and not gaussfit:
+        raise ValueError("cov=True belongs to gaussfit=True")
+    parts = [("rates", 8)] + ([("fit", 64 * k), ("hess", 24 * k)] if gaussfit else [])
+    parts += [("cov", 24 * k), ("info", 24 * k)] if cov else []
+    parts += [("kp", 12 * k), ("boxes", 16), ("valid", 4), ("idx", 4 * k)]
+    parts += [("status", 4 * k)] if gaussfit else []
+    return tuple(parts)
+
+
+def record_views(packed: torch.Tensor, m: int, k: int, fields):
+    """The typed views of a packed record of m crops (uint8 [m * bytes per crop], laid out as `fields` = record_fields(...)
+    says): name -> tensor, e.g. kp f32 [m,k,3], rates f64 [m], order int32 [m,k]."""
+    out, off = {}, 0
+    for name, b in fields:
+        dtype, tail = _RECORD_TYPES[name]
+        out[name] = packed[off:off + m * b].view(dtype).view(m, *(k if d == "k" else d for d in tail))
+        off += m * b
+    if off != packed.numel():
+        raise ValueError(f"a record of {m} crops has {off} bytes, the buffer {packed.numel()}")
+    return out
+
+
 def unpack_correspondences(host: np.ndarray, m: int, k: int):
     """pack_correspondences' buffer, copied to the host -> (count, order, pts, w) as numpy views."""
     offs = np.cumsum([0, 16 * m * k, 24 * m * k, 4 * m, 4 * m * k])

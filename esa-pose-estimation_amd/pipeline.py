@@ -134,18 +134,22 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
     and status ride in it, inference.packed_layout).  weights="covariance" (device_select=True and refine="gaussfit"): each point
     is weighed by the covariance of its fitted centre, rate * cov^(-1/2) (inv(sqrtm(covar)) of the reference's
     evaluation.py:471-487), which grows with the residual noise of the fit and not only with the blob's width; a point with
-    cov[0] < cov_floor or without a covariance gets weight zero."""
+    cov[0] < cov_floor or without a covariance gets weight zero.
+    distributed=True with device_loader=True or device_select=True: every rank passes the whole batch (frames, bboxes,
+    frame_idx), runs its contiguous shard of the boxes through the same library call and the packed records are all-gathered
+    (parallel.sharded_frames_to_keypoints / sharded_frames_to_correspondences); every rank returns all poses."""
     inference.check_refine(refine)
     inference.check_weights(weights, refine)
     if weights != "peak" and not device_select:
         raise ValueError(f"weights='{weights}' belongs to device_select=True (the host selection weighs by the peak)")
     if device_select:
-        if distributed:
-            raise ValueError("device_select=True runs on one device (distributed=True shards crops that exist on the host side)")
         if not native:
             raise ValueError("device_select=True hands its record to the native solver (native=False has no entry for it)")
         with torch.no_grad():
-            if weights == "covariance":
+            if distributed:                 # every rank its shard of the boxes, then the two records gathered: all poses on all ranks
+                out = parallel._sharded_frames_to_correspondences(net, frames, bboxes, frame_idx, None, 0, scale, rule, refine,
+                                                                  thresh, min_k, weights, None, crops.STD, None, cov_floor)
+            elif weights == "covariance":
                 out = net._frames_to_correspondences(frames, bboxes, frame_idx, scale, rule, refine, thresh, min_k, weights, None,
                                                      crops.STD, None, cov_floor)
             else:
@@ -156,10 +160,12 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
         q, t = pnp.correspondences_to_pose_batch(pts, w, count, order, kp3d, np.asarray(K, np.float64), threads)
         return _checked_poses([(q[i], t[i]) for i in range(m)], on_fail)
     if device_loader:
-        if distributed:
-            raise ValueError("device_loader=True runs on one device (distributed=True shards crops that exist on the host side)")
         with torch.no_grad():
-            out = net._frames_to_keypoints(frames, bboxes, frame_idx, scale, rule, refine, None, crops.STD, None)
+            if distributed:
+                out = parallel._sharded_frames_to_keypoints(net, frames, bboxes, frame_idx, None, 0, scale, rule, refine, None,
+                                                            crops.STD, None)
+            else:
+                out = net._frames_to_keypoints(frames, bboxes, frame_idx, scale, rule, refine, None, crops.STD, None)
         m, k = out[0].shape[:2]
         host = out[5].cpu().numpy()                         # the only device->host copy
         lay = inference.packed_layout(m, k, refine == "gaussfit")

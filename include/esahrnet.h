@@ -414,6 +414,23 @@ int esahrnet_pnp_batch(const float* kp, int n, int k, const double* kp3d, const 
 int esahrnet_pnp_batch_w(const double* pts, const double* w, const int* count, int m, int k, const double* kp3d,
                          const int* order, const double* K9, int threads, double* q_out, double* t_out);
 
+/* The packed records of the device path after the all-gather of a sharded batch (csrc/records.hip).  A packed record is
+ * field-major: field f holds field_bytes[f] bytes per crop, all crops of field 0 first, then field 1, ..., so field f of a
+ * record laid out for m crops starts at off_f(m) = m * (field_bytes[0] + ... + field_bytes[f-1]).  gathered_dev: `world`
+ * blocks, as all_gather_into_tensor leaves them, each a record laid out for n_max = ceil(n_total / world) crops; rank r's
+ * block holds its shard in the first hi_r - lo_r crop slots of every field.  Shard rule: a contiguous split in which the
+ * first n_total % world ranks get one crop more — with base = n_total / world and extra = n_total % world,
+ * lo_r = r * base + min(r, extra) and hi_r = lo_r + base + (r < extra ? 1 : 0); it is recomputed on the device from world
+ * and n_total.  out_dev: the record laid out for n_total crops,
+ *     out[off_f(n_total) + i * b_f ... + b_f] = block_r[off_f(n_max) + (i - lo_r) * b_f ... + b_f]   for lo_r <= i < hi_r.
+ * One launch of a copy kernel (dword loads and stores), nothing allocated, nothing synchronised, capturable into a graph.
+ * Every byte of out_dev is written exactly once; the padding slots of a block and the whole block of a rank without crops
+ * are never read (they may be uninitialised).  field_bytes is a HOST array, passed on by value.  Refused before anything is
+ * enqueued: world < 1, n_total < 1, nfields outside 1..16, a field that is no positive multiple of 4, a null pointer,
+ * gathered_dev or out_dev not 8-byte aligned, a block of more than 2^31 - 1 bytes. */
+int esahrnet_gather_records(const void* gathered_dev, int world, int n_total, const int* field_bytes, int nfields,
+                            void* out_dev, esahrnet_stream stream);
+
 /* ---- introspection / per-operator entry points (used by the parity tests) ------------- */
 
 /* Algorithmic (direct-convolution) FLOPs of one forward of one crop: 2 * MACs of every conv. */
