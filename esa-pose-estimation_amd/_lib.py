@@ -9,6 +9,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libesahrnet.so")
 MAX_BRANCHES = 4
 ABI_VERSION = 6
+# a report row of esahrnet_pnp_batch_ex / esahrnet_pnp_batch_w_ex (include/esahrnet.h: enum esahrnet_pose_report)
+POSE_REPORT_FIELDS = ("status", "flags", "n", "inliers", "ransac_iters", "lm_iters", "cost", "rms_px", "max_px", "argmax",
+                      "min_depth", "s2")
+POSE_REPORT_COV = 12
+POSE_REPORT_DOUBLES = 33
 
 
 class Cfg(C.Structure):
@@ -136,6 +141,10 @@ _SIGS = {
                                                   C.c_void_p]),
     "esahrnet_pnp_batch_w": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_void_p, C.c_void_p]),
+    "esahrnet_pnp_batch_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esahrnet_pnp_batch_w_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "esahrnet_gather_records": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p]),
     "esahrnet_flops_per_crop": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "esahrnet_launch_count": (C.c_int, [C.c_void_p]),

@@ -5,7 +5,9 @@
 // lib/utils/extend_utils/src/uncertainty_pnp.cpp:7-92), the top-k selection and crop -> image mapping of
 // val.py:172-180 (correspond.h: the statement of it shared with the device stage, correspond.hip) and the [w,x,y,z]
 // quaternion of val.py:221-224 — for a whole batch of keypoint rows (esahrnet_pnp_batch), or of correspondence records
-// that the device stage already selected, back-projected and weighted (esahrnet_pnp_batch_w).
+// that the device stage already selected, back-projected and weighted (esahrnet_pnp_batch_w).  The _ex forms of both also
+// fill a report row per image from the finished pose (status, RANSAC consensus, residuals, the 6x6 covariance (J^T J)^-1;
+// enum esahrnet_pose_report), which takes no part in the solve.
 //
 // It is a line-by-line native restatement of esa-pose-estimation_amd/pnp.py (which is the oracle for it:
 // tests/test_pnp_native.py compares poses and inlier sets); like that module it restates the PUBLISHED
@@ -439,7 +441,13 @@ bool epnp(const double* pw, const double* uv, int n, const Cam& K, Mat3 Rb, doub
 }
 
 // ---- RANSAC (pnp.py: solve_pnp_ransac) ------------------------------------------------------------------------
-bool ransac(const double* p3d, const double* p2d, int n, const Cam& K, Mat3 R, double t[3], unsigned char* mask) {
+// what a solve did on its way to the pose (the integer fields of a report row, include/esahrnet.h)
+struct Fit {
+    int inliers = 0, ransac_iters = 0, lm_iters = 0;
+    bool fallback = false;
+};
+
+bool ransac(const double* p3d, const double* p2d, int n, const Cam& K, Mat3 R, double t[3], unsigned char* mask, Fit& fit) {
     const double reproj = 5.0, confidence = 0.99;
     const int iters = 100, m = std::min(5, n);
     SplitMix g{0};
@@ -473,7 +481,10 @@ bool ransac(const double* p3d, const double* p2d, int n, const Cam& K, Mat3 R, d
             niter = denom < 0 ? std::min(iters, (int)std::ceil(std::log(1.0 - confidence) / denom)) : iters;
         }
     }
-    if (best_cnt < 4) std::fill(bestm.begin(), bestm.end(), 1);
+    fit.ransac_iters = it;
+    fit.fallback = best_cnt < 4;
+    fit.inliers = fit.fallback ? n : best_cnt;
+    if (fit.fallback) std::fill(bestm.begin(), bestm.end(), 1);
     std::vector<double> iw, iu;
     for (int i = 0; i < n; ++i)
         if (bestm[i]) {
@@ -484,10 +495,45 @@ bool ransac(const double* p3d, const double* p2d, int n, const Cam& K, Mat3 R, d
     return epnp(iw.data(), iu.data(), (int)(iw.size() / 3), K, R, t);
 }
 
+// the weighted Jacobian of cpnp's residuals at (R, t), J [2n][6]: d(proj)/d(pc), then the left-multiplicative rotation
+// increment R <- exp([dw]x) R, d(pc)/d(dw) = -[R p]x, d(pc)/dt = I; columns (dw_x, dw_y, dw_z, dt_x, dt_y, dt_z)
+void weighted_jacobian(const double* p3d, const double* wts, int n, const Cam& K, const Mat3 R, const double t[3], double* J) {
+    for (int i = 0; i < n; ++i) {
+        double rp[3], pc[3];
+        for (int d = 0; d < 3; ++d) {
+            rp[d] = R[d][0] * p3d[i * 3] + R[d][1] * p3d[i * 3 + 1] + R[d][2] * p3d[i * 3 + 2];
+            pc[d] = rp[d] + t[d];
+        }
+        const double X = pc[0], Y = pc[1], Z = pc[2];
+        const double dpx[3] = {K.fx / Z, 0.0, -K.fx * X / (Z * Z)}, dpy[3] = {0.0, K.fy / Z, -K.fy * Y / (Z * Z)};
+        const double S[3][3] = {{0, rp[2], -rp[1]}, {-rp[2], 0, rp[0]}, {rp[1], -rp[0], 0}};      // -[rp]x
+        const double wxx = wts[i * 3], wxy = wts[i * 3 + 1], wyy = wts[i * 3 + 2];
+        for (int c = 0; c < 3; ++c) {
+            const double jx = dpx[0] * S[0][c] + dpx[1] * S[1][c] + dpx[2] * S[2][c];
+            const double jy = dpy[0] * S[0][c] + dpy[1] * S[1][c] + dpy[2] * S[2][c];
+            J[(2 * i) * 6 + c] = wxx * jx + wxy * jy;
+            J[(2 * i + 1) * 6 + c] = wxy * jx + wyy * jy;
+            J[(2 * i) * 6 + 3 + c] = wxx * dpx[c] + wxy * dpy[c];
+            J[(2 * i + 1) * 6 + 3 + c] = wxy * dpx[c] + wyy * dpy[c];
+        }
+    }
+}
+
+// H = J^T J (6 x 6) of a [rows][6] Jacobian
+void normal_matrix(const double* J, int rows, double H[36]) {
+    for (int a = 0; a < 6; ++a)
+        for (int c = 0; c < 6; ++c) {
+            double s = 0.0;
+            for (int k = 0; k < rows; ++k) s += J[k * 6 + a] * J[k * 6 + c];
+            H[a * 6 + c] = s;
+        }
+}
+
 // ---- weighted LM refinement (pnp.py: cpnp_m) ------------------------------------------------------------------
 // wts [n][3] = (wxx, wxy, wyy), the symmetric 2x2 weight of uncertainty_pnp.cpp:30-31: r = [wxx dx + wxy dy, wxy dx + wyy dy];
 // the scalar weight of val.py:194-209 is (peak, 0, peak), whose zero terms change no value
-void cpnp(const double* p3d, const double* p2d, const double* wts, int n, const Cam& K, double x[6]) {
+// returns the outer iterations run (each forms one Jacobian)
+int cpnp(const double* p3d, const double* p2d, const double* wts, int n, const Cam& K, double x[6]) {
     std::vector<double> r(2 * n), rn(2 * n), J(2 * n * 6);
     auto residual = [&](const double* xx, std::vector<double>& out, Mat3 R) {
         rodrigues(xx, R);
@@ -503,35 +549,15 @@ void cpnp(const double* p3d, const double* p2d, const double* wts, int n, const 
     Mat3 R;
     residual(x, r, R);
     double cost = sq(r), lam = 1e-3;
+    int iters = 0;
     for (int it = 0; it < 50; ++it) {
-        for (int i = 0; i < n; ++i) {
-            double rp[3], pc[3];
-            for (int d = 0; d < 3; ++d) {
-                rp[d] = R[d][0] * p3d[i * 3] + R[d][1] * p3d[i * 3 + 1] + R[d][2] * p3d[i * 3 + 2];
-                pc[d] = rp[d] + x[3 + d];
-            }
-            const double X = pc[0], Y = pc[1], Z = pc[2];
-            const double dpx[3] = {K.fx / Z, 0.0, -K.fx * X / (Z * Z)}, dpy[3] = {0.0, K.fy / Z, -K.fy * Y / (Z * Z)};
-            const double S[3][3] = {{0, rp[2], -rp[1]}, {-rp[2], 0, rp[0]}, {rp[1], -rp[0], 0}};      // -[rp]x
-            const double wxx = wts[i * 3], wxy = wts[i * 3 + 1], wyy = wts[i * 3 + 2];
-            for (int c = 0; c < 3; ++c) {
-                const double jx = dpx[0] * S[0][c] + dpx[1] * S[1][c] + dpx[2] * S[2][c];
-                const double jy = dpy[0] * S[0][c] + dpy[1] * S[1][c] + dpy[2] * S[2][c];
-                J[(2 * i) * 6 + c] = wxx * jx + wxy * jy;
-                J[(2 * i + 1) * 6 + c] = wxy * jx + wyy * jy;
-                J[(2 * i) * 6 + 3 + c] = wxx * dpx[c] + wxy * dpy[c];
-                J[(2 * i + 1) * 6 + 3 + c] = wxy * dpx[c] + wyy * dpy[c];
-            }
-        }
+        ++iters;
+        weighted_jacobian(p3d, wts, n, K, R, x + 3, J.data());
         double H[36], gvec[6];
+        normal_matrix(J.data(), 2 * n, H);
         for (int a = 0; a < 6; ++a) {
             gvec[a] = 0.0;
             for (int k = 0; k < 2 * n; ++k) gvec[a] += J[k * 6 + a] * r[k];
-            for (int c = 0; c < 6; ++c) {
-                double s = 0.0;
-                for (int k = 0; k < 2 * n; ++k) s += J[k * 6 + a] * J[k * 6 + c];
-                H[a * 6 + c] = s;
-            }
         }
         bool improved = false, done = false;
         for (int tr = 0; tr < 10; ++tr) {
@@ -563,27 +589,114 @@ void cpnp(const double* p3d, const double* p2d, const double* wts, int n, const 
         }
         if (!improved || done) break;
     }
+    return iters;
+}
+
+// ---- what the solve reports (include/esahrnet.h: enum esahrnet_pose_report; pnp.py: pose_report is the oracle) ------------
+// inverse of the symmetric 6 x 6 H by Cholesky, H = L L^T, inv = L^-T L^-1.  false when H is not positive definite to working
+// precision: a pivot at or below 1e-12 of its diagonal entry (the parameter is then determined by the ones before it to 12
+// digits, and rounding alone decides the pivot's sign) or a non-finite one
+bool cholesky_inverse(const double H[36], double inv[36]) {
+    double L[36] = {0}, Li[36] = {0};
+    for (int j = 0; j < 6; ++j) {
+        double d = H[j * 6 + j];
+        for (int k = 0; k < j; ++k) d -= L[j * 6 + k] * L[j * 6 + k];
+        if (!(d > 1e-12 * H[j * 6 + j]) || !std::isfinite(d)) return false;
+        L[j * 6 + j] = std::sqrt(d);
+        for (int i = j + 1; i < 6; ++i) {
+            double s = H[i * 6 + j];
+            for (int k = 0; k < j; ++k) s -= L[i * 6 + k] * L[j * 6 + k];
+            L[i * 6 + j] = s / L[j * 6 + j];
+        }
+    }
+    for (int j = 0; j < 6; ++j) {                 // Li = L^-1, column by column (forward substitution on e_j)
+        Li[j * 6 + j] = 1.0 / L[j * 6 + j];
+        for (int i = j + 1; i < 6; ++i) {
+            double s = 0.0;
+            for (int k = j; k < i; ++k) s -= L[i * 6 + k] * Li[k * 6 + j];
+            Li[i * 6 + j] = s / L[i * 6 + i];
+        }
+    }
+    for (int a = 0; a < 6; ++a)
+        for (int c = a; c < 6; ++c) {
+            double s = 0.0;
+            for (int k = c; k < 6; ++k) s += Li[k * 6 + a] * Li[k * 6 + c];
+            inv[a * 6 + c] = inv[c * 6 + a] = s;
+            if (!std::isfinite(s)) return false;
+        }
+    return true;
+}
+
+// a report row without a pose: everything NaN but the status and the number of correspondences
+void report_no_pose(double* rep, int status, int n) {
+    for (int i = 0; i < ESAHRNET_POSE_REPORT_DOUBLES; ++i) rep[i] = NAN;
+    rep[ESAHRNET_REPORT_STATUS] = status;
+    rep[ESAHRNET_REPORT_N] = n;
+}
+
+// the report row of a solved image, at the returned pose (R = rodrigues(cam[0..2]), t = cam[3..5]): one more residual and
+// Jacobian evaluation and one 6 x 6 factorisation
+void report_pose(const double* p3d, const double* p2d, const double* wts, int n, const Cam& K, const Mat3 R, const double t[3],
+                 const Fit& fit, double* rep) {
+    double cost = 0.0, sum2 = 0.0, max2 = -1.0, zmin = INFINITY;
+    int argmax = 0;
+    for (int i = 0; i < n; ++i) {
+        double p[2];
+        project1(p3d + i * 3, R, t, K, p);
+        const double dx = p[0] - p2d[i * 2], dy = p[1] - p2d[i * 2 + 1];
+        const double rx = wts[i * 3] * dx + wts[i * 3 + 1] * dy, ry = wts[i * 3 + 1] * dx + wts[i * 3 + 2] * dy;
+        cost += rx * rx;
+        cost += ry * ry;
+        const double e2 = dx * dx + dy * dy;
+        sum2 += e2;
+        if (e2 > max2) { max2 = e2; argmax = i; }
+        zmin = std::min(zmin, R[2][0] * p3d[i * 3] + R[2][1] * p3d[i * 3 + 1] + R[2][2] * p3d[i * 3 + 2] + t[2]);
+    }
+    std::vector<double> J(2 * (size_t)n * 6);
+    weighted_jacobian(p3d, wts, n, K, R, t, J.data());
+    double H[36], cov[36];
+    normal_matrix(J.data(), 2 * n, H);
+    const bool have_cov = cholesky_inverse(H, cov);
+    rep[ESAHRNET_REPORT_STATUS] = 0;
+    rep[ESAHRNET_REPORT_FLAGS] = (fit.fallback ? 1 : 0) | (have_cov ? 0 : 2);
+    rep[ESAHRNET_REPORT_N] = n;
+    rep[ESAHRNET_REPORT_INLIERS] = fit.inliers;
+    rep[ESAHRNET_REPORT_RANSAC_ITERS] = fit.ransac_iters;
+    rep[ESAHRNET_REPORT_LM_ITERS] = fit.lm_iters;
+    rep[ESAHRNET_REPORT_COST] = cost;
+    rep[ESAHRNET_REPORT_RMS_PX] = std::sqrt(sum2 / n);
+    rep[ESAHRNET_REPORT_MAX_PX] = std::sqrt(max2);
+    rep[ESAHRNET_REPORT_ARGMAX] = argmax;
+    rep[ESAHRNET_REPORT_MIN_DEPTH] = zmin;
+    rep[ESAHRNET_REPORT_S2] = cost / (2 * n - 6);
+    int o = ESAHRNET_REPORT_COV;
+    for (int a = 0; a < 6; ++a)
+        for (int c = a; c < 6; ++c) rep[o++] = have_cov ? cov[a * 6 + c] : NAN;
 }
 
 // ---- one image: val.py:194-224 on n correspondences (model points, image pixels, 2x2 weights) --------------------------
-void pose_solve(const double* p3, const double* p2, const double* w3, int n, const Cam& K, double q[4], double t[3]) {
+// rep: the image's report row, or null; it is filled from the finished pose and takes no part in the solve
+void pose_solve(const double* p3, const double* p2, const double* w3, int n, const Cam& K, double q[4], double t[3], double* rep) {
     Mat3 R;
     double tt[3], cam[6];
-    if (n < 4 || !ransac(p3, p2, n, K, R, tt, nullptr)) {
+    Fit fit;
+    if (n < 4 || !ransac(p3, p2, n, K, R, tt, nullptr, fit)) {
         q[0] = q[1] = q[2] = q[3] = t[0] = t[1] = t[2] = NAN;
+        if (rep) report_no_pose(rep, n < 4 ? 1 : 2, n);
         return;
     }
     rodrigues_inv(R, cam);
     for (int d = 0; d < 3; ++d) cam[3 + d] = tt[d];
-    cpnp(p3, p2, w3, n, K, cam);
+    fit.lm_iters = cpnp(p3, p2, w3, n, K, cam);
     rodrigues(cam, R);
     quat_wxyz(R, q);
     for (int d = 0; d < 3; ++d) t[d] = cam[3 + d];
+    if (rep) report_pose(p3, p2, w3, n, K, R, t, fit, rep);
 }
 
 // ---- one image from its keypoint rows: val.py:172-180 (correspond.h), then the solve ---------------------------------
 void pose_one(const float* kp, int k, const double* kp3d, const Cam& K, int x0, int y0, double rate, double thresh,
-              int min_k, double q[4], double t[3]) {
+              int min_k, double q[4], double t[3], double* rep) {
     // top-k by peak (heapq.nlargest: descending, ties keep index order)
     int above = 0;
     for (int i = 0; i < k; ++i) above += (double)kp[i * 3 + 2] > thresh;
@@ -601,7 +714,7 @@ void pose_one(const float* kp, int k, const double* kp3d, const Cam& K, int x0, 
         wv[i * 3 + 0] = wv[i * 3 + 2] = (double)kp[j * 3 + 2];
         wv[i * 3 + 1] = 0.0;
     }
-    pose_solve(p3.data(), p2.data(), wv.data(), large, K, q, t);
+    pose_solve(p3.data(), p2.data(), wv.data(), large, K, q, t, rep);
 }
 
 // `work(lo, hi)` over [0, n) on up to `threads` threads
@@ -616,9 +729,9 @@ void run_batch(int n, int threads, Work work) {
 
 }  // namespace
 
-extern "C" int esahrnet_pnp_batch(const float* kp, int n, int k, const double* kp3d, const double* K9, const int* boxes_xy,
-                                  const double* rates, double thresh, int min_k, int threads, double* q_out,
-                                  double* t_out) {
+extern "C" int esahrnet_pnp_batch_ex(const float* kp, int n, int k, const double* kp3d, const double* K9, const int* boxes_xy,
+                                     const double* rates, double thresh, int min_k, int threads, double* q_out,
+                                     double* t_out, double* report) {
     if (!kp || !kp3d || !K9 || !boxes_xy || !rates || !q_out || !t_out) return esa::set_error("pnp_batch: null argument");
     if (n < 0) return esa::set_error("pnp_batch: negative image count %d", n);
     if (k < 1 || k > 64) return esa::set_error("pnp_batch: %d keypoints per image unsupported (1..64)", k);
@@ -626,13 +739,20 @@ extern "C" int esahrnet_pnp_batch(const float* kp, int n, int k, const double* k
     run_batch(n, threads, [&](int lo, int hi) {
         for (int i = lo; i < hi; ++i)
             pose_one(kp + (size_t)i * k * 3, k, kp3d, K, boxes_xy[i * 2], boxes_xy[i * 2 + 1], rates[i], thresh, min_k,
-                     q_out + (size_t)i * 4, t_out + (size_t)i * 3);
+                     q_out + (size_t)i * 4, t_out + (size_t)i * 3, report ? report + (size_t)i * ESAHRNET_POSE_REPORT_DOUBLES : nullptr);
     });
     return 0;
 }
 
-extern "C" int esahrnet_pnp_batch_w(const double* pts, const double* w, const int* count, int m, int k, const double* kp3d,
-                                    const int* order, const double* K9, int threads, double* q_out, double* t_out) {
+extern "C" int esahrnet_pnp_batch(const float* kp, int n, int k, const double* kp3d, const double* K9, const int* boxes_xy,
+                                  const double* rates, double thresh, int min_k, int threads, double* q_out,
+                                  double* t_out) {
+    return esahrnet_pnp_batch_ex(kp, n, k, kp3d, K9, boxes_xy, rates, thresh, min_k, threads, q_out, t_out, nullptr);
+}
+
+extern "C" int esahrnet_pnp_batch_w_ex(const double* pts, const double* w, const int* count, int m, int k, const double* kp3d,
+                                       const int* order, const double* K9, int threads, double* q_out, double* t_out,
+                                       double* report) {
     if (!pts || !w || !count || !kp3d || !order || !K9 || !q_out || !t_out) return esa::set_error("pnp_batch_w: null argument");
     if (m < 0) return esa::set_error("pnp_batch_w: negative image count %d", m);
     if (k < 1 || k > 64) return esa::set_error("pnp_batch_w: %d keypoints per image unsupported (1..64)", k);
@@ -649,8 +769,14 @@ extern "C" int esahrnet_pnp_batch_w(const double* pts, const double* w, const in
             const int n = count[i];
             for (int j = 0; j < n; ++j)
                 for (int d = 0; d < 3; ++d) p3[j * 3 + d] = kp3d[order[(size_t)i * k + j] * 3 + d];
-            pose_solve(p3.data(), pts + (size_t)i * k * 2, w + (size_t)i * k * 3, n, K, q_out + (size_t)i * 4, t_out + (size_t)i * 3);
+            pose_solve(p3.data(), pts + (size_t)i * k * 2, w + (size_t)i * k * 3, n, K, q_out + (size_t)i * 4, t_out + (size_t)i * 3,
+                       report ? report + (size_t)i * ESAHRNET_POSE_REPORT_DOUBLES : nullptr);
         }
     });
     return 0;
+}
+
+extern "C" int esahrnet_pnp_batch_w(const double* pts, const double* w, const int* count, int m, int k, const double* kp3d,
+                                    const int* order, const double* K9, int threads, double* q_out, double* t_out) {
+    return esahrnet_pnp_batch_w_ex(pts, w, count, m, k, kp3d, order, K9, threads, q_out, t_out, nullptr);
 }

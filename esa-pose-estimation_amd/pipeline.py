@@ -81,11 +81,17 @@ def _pose_job(args):
 
 
 def poses_from_keypoints(kp, boxes, rates, kp3d, K, thresh: float = 0.8, min_k: int = 24, pool=None,
-                         native: bool = True, threads: int = 0):
+                         native: bool = True, threads: int = 0, report: bool = False):
     """Host stage of val.py:172-224 for a batch: kp [N,K,3] (numpy) -> list of (q [w,x,y,z], t).
     native=True: the C++ solver of the library (`esahrnet_pnp_batch`, `threads` worker threads, ~100 us per image
-    and thread); native=False: the numpy restatement it is tested against (optionally over a process `pool`)."""
+    and thread); native=False: the numpy restatement it is tested against (optionally over a process `pool`).
+    report=True (native only): -> (poses, pnp.PoseReport)."""
     K = np.asarray(K, np.float64)
+    if report:
+        if not native:
+            raise ValueError("the pose report comes from the native solver (native=False has none)")
+        q, t, rep = pnp.keypoints_to_pose_batch(kp, kp3d, K, [(b[0], b[1]) for b in boxes], rates, thresh, min_k, threads, report=True)
+        return [(q[i], t[i]) for i in range(len(boxes))], rep
     if native:
         q, t = pnp.keypoints_to_pose_batch(kp, kp3d, K, [(b[0], b[1]) for b in boxes], rates, thresh, min_k, threads)
         return [(q[i], t[i]) for i in range(len(boxes))]
@@ -104,14 +110,15 @@ FALLBACK_POSE = ((1.0, 0.0, 0.0, 0.0), (0.0, 0.0, 10.0))   # identity attitude, 
 
 
 class PoseFailure(ValueError):
-    """No pose for an image (fewer than 4 usable keypoints, or RANSAC found no consensus)."""
+    """No pose for an image (fewer than 4 usable keypoints, RANSAC found no consensus, or a gate of estimate_poses withdrew it)."""
 
 
 def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256, thresh: float = 0.8,
                    min_k: int = 24, distributed: bool = False, pool=None, native: bool = True,
                    on_fail: str = "raise", keypoints_only: bool = False, refine: str = "get_final",
                    device_loader: bool = False, frame_idx=None, rule: str = "val", device_select: bool = False,
-                   weights: str = "peak", threads: int = 0, cov_floor: float = 1e-6):
+                   weights: str = "peak", threads: int = 0, cov_floor: float = 1e-6, return_report: bool = False,
+                   max_rms_px=None, min_inliers=None):
     """One batch of the val.py:136-233 loop.  frames uint8 cuda [N,H,W]; bboxes N x (x, y, x2, y2);
     kp3d [K3, 3] model keypoints; K camera matrix.  -> list of (q [w,x,y,z], t) per image.
     An image without a solution (the native solver reports it as a NaN row; the reference would die inside
@@ -137,9 +144,25 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
     cov[0] < cov_floor or without a covariance gets weight zero.
     distributed=True with device_loader=True or device_select=True: every rank passes the whole batch (frames, bboxes,
     frame_idx), runs its contiguous shard of the boxes through the same library call and the packed records are all-gathered
-    (parallel.sharded_frames_to_keypoints / sharded_frames_to_correspondences); every rank returns all poses."""
+    (parallel.sharded_frames_to_keypoints / sharded_frames_to_correspondences); every rank returns all poses.
+    return_report=True (native paths): -> (poses, report), report a pnp.PoseReport with one entry per image: status, inliers,
+    RANSAC and LM iterations, final cost, rms / max reprojection error in pixels, minimal depth and the 6x6 covariance of the
+    pose (report.covariance()); the poses are the ones of the call without it, bit for bit.  Gates: a solved pose whose rms_px
+    exceeds max_rms_px or whose inliers are fewer than min_inliers is treated exactly like "no pose" — a NaN row, on_fail
+    applies — while its report row keeps the real numbers and report.gated marks it; both default to None (no gate).  With
+    device_loader=True a crop the loader could not make has a report row of status 1 with n = 0."""
     inference.check_refine(refine)
     inference.check_weights(weights, refine)
+    want = return_report or max_rms_px is not None or min_inliers is not None
+    if want and not native:
+        raise ValueError("return_report and the max_rms_px / min_inliers gates read the native solver's report (native=False has none)")
+
+    def finish(poses, rep):
+        if want:
+            poses = _gated_poses(poses, rep, max_rms_px, min_inliers)
+        poses = _checked_poses(poses, on_fail)
+        return (poses, rep) if return_report else poses
+
     if weights != "peak" and not device_select:
         raise ValueError(f"weights='{weights}' belongs to device_select=True (the host selection weighs by the peak)")
     if device_select:
@@ -157,8 +180,8 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
                                                      crops.STD, None)
         m, k = out[4].shape[:2]
         count, order, pts, w = inference.unpack_correspondences(out[8].cpu().numpy(), m, k)     # the only device->host copy
-        q, t = pnp.correspondences_to_pose_batch(pts, w, count, order, kp3d, np.asarray(K, np.float64), threads)
-        return _checked_poses([(q[i], t[i]) for i in range(m)], on_fail)
+        q, t, *rep = pnp.correspondences_to_pose_batch(pts, w, count, order, kp3d, np.asarray(K, np.float64), threads, report=want)
+        return finish([(q[i], t[i]) for i in range(m)], rep[0] if want else None)
     if device_loader:
         with torch.no_grad():
             if distributed:
@@ -178,9 +201,17 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
         bad = valid == 0
         rates = [1.0 if b else float(r) for r, b in zip(rates, bad)]
         poses = poses_from_keypoints(np.where(bad[:, None, None], np.float32(0), kp), boxes, rates, kp3d, K, thresh, min_k,
-                                     pool, native, threads)
+                                     pool, native, threads, report=want)
+        rep = None
+        if want:
+            poses, rep = poses
+            if bad.any():                                   # no crop, no correspondences: the row of "fewer than 4", with n = 0
+                raw = rep.raw.copy()
+                raw[bad] = np.nan
+                raw[bad, 0], raw[bad, 2] = 1.0, 0.0
+                rep = pnp.PoseReport(raw)
         poses = [(np.full(4, np.nan), np.full(3, np.nan)) if b else p for p, b in zip(poses, bad)]
-        return _checked_poses(poses, on_fail)
+        return finish(poses, rep)
     if frame_idx is not None or rule != "val":
         raise ValueError("frame_idx and rule belong to device_loader=True (crops.crop_batch: one val box per frame)")
     rk = {} if refine == "get_final" else {"refine": refine}
@@ -193,7 +224,19 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
         else:
             kp = inference.heatmaps_to_keypoints(net(x), **rk)
     kp = kp.cpu().numpy()                                   # the only device->host copy: N*K*3 floats
-    return _checked_poses(poses_from_keypoints(kp, boxes, rates, kp3d, K, thresh, min_k, pool, native, threads), on_fail)
+    poses = poses_from_keypoints(kp, boxes, rates, kp3d, K, thresh, min_k, pool, native, threads, report=want)
+    return finish(*poses) if want else finish(poses, None)
+
+
+def _gated_poses(poses, rep, max_rms_px, min_inliers):
+    """Solved poses that miss a gate become the NaN row of "no pose"; rep.gated marks them, their report rows stay."""
+    gated = np.zeros(len(poses), bool)
+    if max_rms_px is not None:
+        gated |= (rep.status == 0) & (rep.rms_px > max_rms_px)
+    if min_inliers is not None:
+        gated |= (rep.status == 0) & (rep.inliers < min_inliers)
+    rep.gated = gated
+    return [(np.full(4, np.nan), np.full(3, np.nan)) if g else p for p, g in zip(poses, gated)]
 
 
 def _checked_poses(poses, on_fail):
@@ -209,10 +252,13 @@ def run_submission(net, batches, kp3d, K, writer, real: bool = False, on_fail: s
     SubmissionWriter: anything with append_test / append_real_test).  A submission needs a finite row for every
     image, so an image without a solution gets FALLBACK_POSE and is logged and listed in `writer.failed`
     (on_fail="fallback"), or stops the run (on_fail="raise").  `kw` goes to estimate_poses (keypoints_only=,
-    refine="get_final2", ...)."""
+    refine="get_final2", ...).  With a gate in `kw` (max_rms_px=, min_inliers=) a solved pose that misses it is such a failure:
+    it gets FALLBACK_POSE and is listed in `writer.failed`."""
     failed = []
     for names, frames, bboxes in batches:
         poses = estimate_poses(net, frames, bboxes, kp3d, K, on_fail="nan", **kw)
+        if kw.get("return_report"):
+            poses = poses[0]
         for name, (q, t) in zip(names, poses):
             if not (np.all(np.isfinite(q)) and np.all(np.isfinite(t))):
                 if on_fail == "raise":

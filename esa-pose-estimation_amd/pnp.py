@@ -235,9 +235,11 @@ class _SplitMix:
         return perm[:m]
 
 
-def solve_pnp_ransac(p3d, p2d, K, reproj_err=5.0, iters=100, confidence=0.99, seed=0):
+def solve_pnp_ransac(p3d, p2d, K, reproj_err=5.0, iters=100, confidence=0.99, seed=0, return_stats=False):
     """RANSAC over 5-point EPnP models, inliers = reprojection error < reproj_err px, final EPnP on
-    the inliers (cv2.solvePnPRansac(flags=SOLVEPNP_EPNP) semantics).  -> (R, t, inlier_mask)."""
+    the inliers (cv2.solvePnPRansac(flags=SOLVEPNP_EPNP) semantics).  -> (R, t, inlier_mask).
+    return_stats=True: -> (R, t, inlier_mask, (inliers, iterations, fallback)): the size of the consensus set the final EPnP ran
+    on, the minimal sets drawn, and whether no consensus of >= 4 was found and all points were used (inliers == n then)."""
     p3d = np.asarray(p3d, np.float64)
     p2d = np.asarray(p2d, np.float64)
     n = len(p3d)
@@ -263,9 +265,12 @@ def solve_pnp_ransac(p3d, p2d, K, reproj_err=5.0, iters=100, confidence=0.99, se
             w = max(cnt / n, 1e-9)
             denom = np.log(max(1.0 - w ** m, 1e-12))
             niter = min(iters, int(np.ceil(np.log(1.0 - confidence) / denom))) if denom < 0 else iters
-    if best_mask is None or best_cnt < 4:
+    fallback = best_mask is None or best_cnt < 4
+    if fallback:
         best_mask = np.ones(n, bool)
     R, t = epnp(p3d[best_mask], p2d[best_mask], K)
+    if return_stats:
+        return R, t, best_mask, (int(best_mask.sum()), it, fallback)
     return R, t, best_mask
 
 
@@ -278,6 +283,45 @@ def pnp(points_3d, points_2d, camera_matrix, method=SOLVEPNP_EPNP):
 
 
 # ------------------------------------------------------------------------ weighted refinement (cpnp_m)
+def _weigher(weights, n):
+    """weights [n] or [n, 3] = (wxx, wxy, wyy) -> weigh(d): d [n, 2, ...], reprojection differences or their Jacobian rows
+    -> W d per point (cpnp_m and pose_report weigh with the same function)."""
+    w = np.asarray(weights, np.float64)
+    full = w.ndim == 2
+    if full:
+        if w.shape != (n, 3):
+            raise ValueError(f"weights must be [n] or [n, 3] = (wxx, wxy, wyy), got {w.shape}")
+        W = np.stack([w[:, [0, 1]], w[:, [1, 2]]], 1)          # [n, 2, 2]
+    else:
+        w = w.reshape(-1, 1)
+
+    def weigh(d):
+        if not full:
+            return d * w.reshape((-1, 1) + (1,) * (d.ndim - 2))
+        return W[:, :, 0].reshape(W.shape[:2] + (1,) * (d.ndim - 2)) * d[:, :1] + \
+            W[:, :, 1].reshape(W.shape[:2] + (1,) * (d.ndim - 2)) * d[:, 1:]
+
+    return weigh
+
+
+def _pose_jacobian(p3d, R, t, fx, fy):
+    """Unweighted d(proj)/d(dw, dt) [n, 2, 6] at (R, t): d(proj)/d(pc), then the left-multiplicative rotation increment
+    R <- exp([dw]x) R: d(pc)/d(dw) = -[R p]x, d(pc)/dt = I."""
+    pc = p3d @ R.T + t
+    X, Y, Z = pc[:, 0], pc[:, 1], pc[:, 2]
+    J = np.zeros((len(p3d), 2, 6))
+    dpx = np.stack([fx / Z, np.zeros_like(Z), -fx * X / Z ** 2], 1)
+    dpy = np.stack([np.zeros_like(Z), fy / Z, -fy * Y / Z ** 2], 1)
+    rp = p3d @ R.T
+    for i in range(len(p3d)):
+        S = -_skew(rp[i])
+        J[i, 0, :3] = dpx[i] @ S
+        J[i, 1, :3] = dpy[i] @ S
+        J[i, 0, 3:] = dpx[i]
+        J[i, 1, 3:] = dpy[i]
+    return J
+
+
 def cpnp_m(p3d, p2d, weights, K, camera, iters=50):
     """Weighted reprojection refinement: camera = [angle-axis(3), t(3)] -> refined camera.
     weights [n]: residual per point = w * (proj - obs)  (uncertainty_pnp.cpp:7-33 with wxx = wyy = w, wxy = 0).
@@ -286,24 +330,10 @@ def cpnp_m(p3d, p2d, weights, K, camera, iters=50):
     Minimised by Levenberg-Marquardt with a numerical-free analytic Jacobian in the pose increment."""
     p3d = np.asarray(p3d, np.float64)
     p2d = np.asarray(p2d, np.float64)
-    w = np.asarray(weights, np.float64)
-    full = w.ndim == 2
-    if full:
-        if w.shape != (len(p3d), 3):
-            raise ValueError(f"weights must be [n] or [n, 3] = (wxx, wxy, wyy), got {w.shape}")
-        W = np.stack([w[:, [0, 1]], w[:, [1, 2]]], 1)          # [n, 2, 2]
-    else:
-        w = w.reshape(-1, 1)
+    weigh = _weigher(weights, len(p3d))
     K = np.asarray(K, np.float64)
     fx, fy = K[0, 0], K[1, 1]
     x = np.asarray(camera, np.float64).reshape(6).copy()
-
-    def weigh(d):
-        """d [n, 2, ...]: reprojection differences, or their Jacobian rows -> W d per point."""
-        if not full:
-            return d * w.reshape((-1, 1) + (1,) * (d.ndim - 2))
-        return W[:, :, 0].reshape(W.shape[:2] + (1,) * (d.ndim - 2)) * d[:, :1] + \
-            W[:, :, 1].reshape(W.shape[:2] + (1,) * (d.ndim - 2)) * d[:, 1:]
 
     def residual(x):
         R = rodrigues(x[:3])
@@ -313,19 +343,7 @@ def cpnp_m(p3d, p2d, weights, K, camera, iters=50):
     cost = r @ r
     lam = 1e-3
     for _ in range(iters):
-        pc = p3d @ R.T + x[3:]
-        X, Y, Z = pc[:, 0], pc[:, 1], pc[:, 2]
-        # d(proj)/d(pc), then left-multiplicative rotation increment: d(pc)/d(dw) = -[R p]x, d(pc)/dt = I
-        J = np.zeros((len(p3d), 2, 6))
-        dpx = np.stack([fx / Z, np.zeros_like(Z), -fx * X / Z ** 2], 1)
-        dpy = np.stack([np.zeros_like(Z), fy / Z, -fy * Y / Z ** 2], 1)
-        rp = p3d @ R.T
-        for i in range(len(p3d)):
-            S = -_skew(rp[i])
-            J[i, 0, :3] = dpx[i] @ S
-            J[i, 1, :3] = dpy[i] @ S
-            J[i, 0, 3:] = dpx[i]
-            J[i, 1, 3:] = dpy[i]
+        J = _pose_jacobian(p3d, R, x[3:], fx, fy)
         J = weigh(J).reshape(-1, 6)
         H = J.T @ J
         g = J.T @ r
@@ -352,6 +370,69 @@ def cpnp_m(p3d, p2d, weights, K, camera, iters=50):
     return x
 
 
+# ------------------------------------------------------------------------------- what a solve reports
+def pose_report(p3d, p2d, weights, K, camera) -> dict:
+    """The numpy statement of fields 6..32 of a native report row (include/esahrnet.h: enum esahrnet_pose_report) at a given
+    pose: camera = [angle-axis(3), t(3)], weights [n] or [n, 3] as cpnp_m takes them, the same analytic Jacobian.  It is the
+    oracle of the native fields.  -> {"cost", "rms_px", "max_px", "argmax", "min_depth", "s2", "JtJ" [6, 6],
+    "cov" [6, 6] = inv(JtJ), NaN where JtJ is not positive definite}.  Parameter order of JtJ and cov:
+    (dw_x, dw_y, dw_z, dt_x, dt_y, dt_z), dw the left-multiplicative increment R <- exp([dw]x) R in radians (camera frame),
+    dt in the units of p3d."""
+    p3d = np.asarray(p3d, np.float64)
+    p2d = np.asarray(p2d, np.float64)
+    n = len(p3d)
+    weigh = _weigher(weights, n)
+    K = np.asarray(K, np.float64)
+    x = np.asarray(camera, np.float64).reshape(6)
+    R = rodrigues(x[:3])
+    d = project(p3d, R, x[3:], K) - p2d
+    r = weigh(d).ravel()
+    cost = float(r @ r)
+    e = np.linalg.norm(d, axis=1)
+    J = weigh(_pose_jacobian(p3d, R, x[3:], K[0, 0], K[1, 1])).reshape(-1, 6)
+    H = J.T @ J
+    try:
+        np.linalg.cholesky(H)
+        cov = np.linalg.inv(H)
+    except np.linalg.LinAlgError:
+        cov = np.full((6, 6), np.nan)
+    return {"cost": cost, "rms_px": float(np.sqrt(np.mean(e ** 2))), "max_px": float(e.max()), "argmax": int(np.argmax(e)),
+            "min_depth": float((p3d @ R[2] + x[5]).min()), "s2": cost / (2 * n - 6), "JtJ": H, "cov": cov}
+
+
+class PoseReport:
+    """What the native solver reports for a batch of m poses (`report=True`), one numpy array [m] per field of
+    include/esahrnet.h's enum esahrnet_pose_report: status, flags, n, inliers, ransac_iters, lm_iters, argmax (integer arrays;
+    -1 where the row has no pose and the field is NaN), cost, rms_px, max_px, min_depth, s2 (f64), and cov [m, 6, 6], the full
+    symmetric inverse of J^T J.  `raw` is the [m, 33] f64 array as the library wrote it.  `gated` [m] bool: poses that
+    pipeline.estimate_poses withdrew through max_rms_px / min_inliers (all False elsewhere)."""
+
+    INTEGER = ("status", "flags", "n", "inliers", "ransac_iters", "lm_iters", "argmax")
+
+    def __init__(self, raw):
+        from . import _lib
+        raw = np.asarray(raw, np.float64)
+        assert raw.ndim == 2 and raw.shape[1] == _lib.POSE_REPORT_DOUBLES, raw.shape
+        self.raw = raw
+        for i, name in enumerate(_lib.POSE_REPORT_FIELDS):
+            col = raw[:, i]
+            setattr(self, name, np.where(np.isnan(col), -1, col).astype(np.int64) if name in self.INTEGER else col.copy())
+        iu = np.triu_indices(6)
+        self.cov = np.empty((len(raw), 6, 6), np.float64)
+        self.cov[:, iu[0], iu[1]] = raw[:, _lib.POSE_REPORT_COV:]
+        self.cov[:, iu[1], iu[0]] = raw[:, _lib.POSE_REPORT_COV:]
+        self.gated = np.zeros(len(raw), bool)
+
+    def __len__(self):
+        return len(self.raw)
+
+    def covariance(self, absolute_sigma=False):
+        """The 6x6 covariance of (dw, dt) per pose, [m, 6, 6].  absolute_sigma=False: s2 * cov, what scipy's curve_fit returns —
+        the reading for "peak" and "hessian" weights, whose scale is arbitrary.  absolute_sigma=True: cov as is — for weights
+        that are inverse square roots of true pixel covariances (weights="covariance")."""
+        return self.cov.copy() if absolute_sigma else self.s2[:, None, None] * self.cov
+
+
 # ------------------------------------------------------------------------------------- caller glue
 def speed_score(q_pred, t_pred, q_gt, t_gt):
     """demo.py:297, 308: translation score + rotation score (radians)."""
@@ -362,10 +443,11 @@ def speed_score(q_pred, t_pred, q_gt, t_gt):
     return st + sr, st, sr
 
 
-def keypoints_to_pose_batch(kp, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=24, threads=0):
+def keypoints_to_pose_batch(kp, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=24, threads=0, report=False):
     """The host stage for a whole batch in native code (csrc/pnp_host.hip, `esahrnet_pnp_batch`): kp [N,K,3]
     f32 as the GPU path wrote it -> (q [N,4] = [w,x,y,z], t [N,3]); rows without a solution are NaN.
-    The same algorithm, step for step, as `keypoints_to_pose` below (which is its oracle)."""
+    The same algorithm, step for step, as `keypoints_to_pose` below (which is its oracle).
+    report=True (`esahrnet_pnp_batch_ex`): -> (q, t, rep), the same q and t bit for bit and a PoseReport of the solves."""
     import ctypes as C
     import os
     from . import _lib
@@ -380,6 +462,14 @@ def keypoints_to_pose_batch(kp, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=24, 
     t = np.empty((n, 3), np.float64)
     if threads <= 0:
         threads = min(16, len(os.sched_getaffinity(0))) if hasattr(os, "sched_getaffinity") else 4
+    if report:
+        rep = np.empty((n, _lib.POSE_REPORT_DOUBLES), np.float64)
+        _lib.check(_lib.lib().esahrnet_pnp_batch_ex(kp.ctypes.data_as(C.c_void_p), n, k, kp3d.ctypes.data_as(C.c_void_p),
+                                                    K9.ctypes.data_as(C.c_void_p), bxy.ctypes.data_as(C.c_void_p),
+                                                    rt.ctypes.data_as(C.c_void_p), float(thresh), int(min_k), int(threads),
+                                                    q.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                                    rep.ctypes.data_as(C.c_void_p)))
+        return q, t, PoseReport(rep)
     _lib.check(_lib.lib().esahrnet_pnp_batch(kp.ctypes.data_as(C.c_void_p), n, k, kp3d.ctypes.data_as(C.c_void_p),
                                              K9.ctypes.data_as(C.c_void_p), bxy.ctypes.data_as(C.c_void_p),
                                              rt.ctypes.data_as(C.c_void_p), float(thresh), int(min_k), int(threads),
@@ -387,11 +477,12 @@ def keypoints_to_pose_batch(kp, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=24, 
     return q, t
 
 
-def correspondences_to_pose_batch(pts, w, count, order, kp3d, K, threads=0):
+def correspondences_to_pose_batch(pts, w, count, order, kp3d, K, threads=0, report=False):
     """The host stage on records the device stage wrote (include/esahrnet.h esahrnet_correspondences ->
     `esahrnet_pnp_batch_w`): pts [N,K,2] f64 image pixels, w [N,K,3] f64 = (wxx, wxy, wyy), count [N], order [N,K] int32
     -> (q [N,4] = [w,x,y,z], t [N,3]); rows without a solution (fewer than 4 points among them) are NaN.  EPnP + RANSAC on
-    pts, LM with the full 2x2 weights: with (peak, 0, peak) rows the poses of keypoints_to_pose_batch, bit for bit."""
+    pts, LM with the full 2x2 weights: with (peak, 0, peak) rows the poses of keypoints_to_pose_batch, bit for bit.
+    report=True (`esahrnet_pnp_batch_w_ex`): -> (q, t, rep), the same q and t bit for bit and a PoseReport of the solves."""
     import ctypes as C
     import os
     from . import _lib
@@ -409,6 +500,11 @@ def correspondences_to_pose_batch(pts, w, count, order, kp3d, K, threads=0):
     if threads <= 0:
         threads = min(16, len(os.sched_getaffinity(0))) if hasattr(os, "sched_getaffinity") else 4
     p = lambda a: a.ctypes.data_as(C.c_void_p)                       # noqa: E731
+    if report:
+        rep = np.empty((n, _lib.POSE_REPORT_DOUBLES), np.float64)
+        _lib.check(_lib.lib().esahrnet_pnp_batch_w_ex(p(pts), p(w), p(count), n, k, p(kp3d), p(order), p(K9), int(threads), p(q), p(t),
+                                                      p(rep)))
+        return q, t, PoseReport(rep)
     _lib.check(_lib.lib().esahrnet_pnp_batch_w(p(pts), p(w), p(count), n, k, p(kp3d), p(order), p(K9), int(threads), p(q), p(t)))
     return q, t
 

@@ -414,6 +414,41 @@ int esahrnet_pnp_batch(const float* kp, int n, int k, const double* kp3d, const 
 int esahrnet_pnp_batch_w(const double* pts, const double* w, const int* count, int m, int k, const double* kp3d,
                          const int* order, const double* K9, int threads, double* q_out, double* t_out);
 
+/* What a solve reports about its pose: one row of ESAHRNET_POSE_REPORT_DOUBLES f64 per image, integer-valued fields stored
+ * as exact doubles.  Without a pose (status 1 or 2; q and t are NaN) every field but STATUS and N is NaN. */
+enum esahrnet_pose_report {
+    ESAHRNET_REPORT_STATUS = 0,        /* 0 = solved; 1 = no pose, fewer than 4 correspondences; 2 = no pose, EPnP found no model
+                                          on the consensus set */
+    ESAHRNET_REPORT_FLAGS = 1,         /* bit 0: RANSAC found no consensus of >= 4 points and all points were used; bit 1: no
+                                          covariance, J^T J is not positive definite (a Cholesky pivot at or below 1e-12 of its
+                                          diagonal entry); COV is NaN then and the pose is still returned */
+    ESAHRNET_REPORT_N = 2,             /* correspondences given */
+    ESAHRNET_REPORT_INLIERS = 3,       /* size of the best consensus set (5 px); N when flag bit 0 is set */
+    ESAHRNET_REPORT_RANSAC_ITERS = 4,  /* minimal sets drawn, 1..100 */
+    ESAHRNET_REPORT_LM_ITERS = 5,      /* outer Levenberg-Marquardt iterations run (one Jacobian each), 1..50 */
+    ESAHRNET_REPORT_COST = 6,          /* final sum r^2 of the weighted residuals r = [wxx dx + wxy dy, wxy dx + wyy dy] */
+    ESAHRNET_REPORT_RMS_PX = 7,        /* sqrt(mean_i |proj_i - obs_i|^2) over the N points, unweighted, image pixels */
+    ESAHRNET_REPORT_MAX_PX = 8,        /* largest unweighted reprojection distance */
+    ESAHRNET_REPORT_ARGMAX = 9,        /* position of that point in the record's rank order (0..N-1; the first of equals) */
+    ESAHRNET_REPORT_MIN_DEPTH = 10,    /* smallest camera-frame Z over the N model points at the pose; <= 0: a point lies behind
+                                          the camera */
+    ESAHRNET_REPORT_S2 = 11,           /* COST / (2 N - 6): the residual variance per degree of freedom */
+    ESAHRNET_REPORT_COV = 12,          /* 21 doubles: upper triangle, row-major, of the 6x6 inverse of J^T J (by Cholesky), J the
+                                          weighted Jacobian of r at the returned pose.  NOT scaled by S2.  Parameter order
+                                          (dw_x, dw_y, dw_z, dt_x, dt_y, dt_z): dw the left-multiplicative rotation increment
+                                          R <- exp([dw]x) R in radians, camera frame; dt in the units of kp3d */
+    ESAHRNET_POSE_REPORT_DOUBLES = 33
+};
+/* esahrnet_pnp_batch / esahrnet_pnp_batch_w with a report: report = f64 [n or m][ESAHRNET_POSE_REPORT_DOUBLES], or null.  The
+ * same solve: q_out and t_out are bit-identical to the entries above for every input and thread count (those entries are
+ * these with report = null), and a report row depends on its image alone, so it has the same bits for any `threads`.  The
+ * row is computed from the finished pose — one more Jacobian evaluation and one 6x6 factorisation per image. */
+int esahrnet_pnp_batch_ex(const float* kp, int n, int k, const double* kp3d, const double* K9, const int* boxes_xy,
+                          const double* rates, double thresh, int min_k, int threads, double* q_out, double* t_out,
+                          double* report);
+int esahrnet_pnp_batch_w_ex(const double* pts, const double* w, const int* count, int m, int k, const double* kp3d,
+                            const int* order, const double* K9, int threads, double* q_out, double* t_out, double* report);
+
 /* The packed records of the device path after the all-gather of a sharded batch (csrc/records.hip).  A packed record is
  * field-major: field f holds field_bytes[f] bytes per crop, all crops of field 0 first, then field 1, ..., so field f of a
  * record laid out for m crops starts at off_f(m) = m * (field_bytes[0] + ... + field_bytes[f-1]).  gathered_dev: `world`

@@ -1,0 +1,59 @@
+#!/usr/bin/env python
+"""Build tools/pnp_host_check.cpp with the host solver under host sanitizers and run it on the batches of
+tests/test_pose_report_host.py (the 64-image batch of its tests 1 and 2, as a correspondence record and as keypoint rows; the
+same record with all but two weights zero; the six random points without a consensus).  CPU only; nothing is loaded into
+Python.  --sanitize "" builds it plain."""
+import argparse
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+
+def record(f, pts, w, count, order, kp3d, K, kp=None, boxes=None, rates=None, thresh=0.5, min_k=0):
+    m, k = pts.shape[:2]
+    np.array([m, k, kp is not None], np.int32).tofile(f)
+    for a, dt in ((pts, np.float64), (w, np.float64), (count, np.int32), (order, np.int32), (kp3d, np.float64), (K, np.float64)):
+        np.ascontiguousarray(a, dt).tofile(f)
+    if kp is not None:
+        for a, dt in ((kp, np.float32), (boxes, np.int32), (rates, np.float64), ([thresh, min_k], np.float64)):
+            np.ascontiguousarray(a, dt).tofile(f)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sanitize", default="address,undefined")
+    ap.add_argument("--keep", default=None, help="directory for the program and the record file (default: a temporary one)")
+    a = ap.parse_args()
+    import test_pose_report_host as T
+    from esa_pose_estimation_amd.build import _hipcc
+    out = a.keep or tempfile.mkdtemp(prefix="pnp_host_check_")
+    os.makedirs(out, exist_ok=True)
+    b = T._batch()
+    with open(os.path.join(out, "records.bin"), "wb") as f:
+        record(f, b["pts"], b["w"], b["count"], b["order"], b["kp3d"], T.K, b["kp"], b["boxes_xy"], b["rates"])
+        w2 = b["w"].copy()
+        w2[:, 2:] = 0.0
+        record(f, b["pts"], w2, b["count"], b["order"], b["kp3d"], T.K)
+        rng = np.random.default_rng(T.FALLBACK_SEED)
+        kp3d = rng.uniform(-0.5, 0.5, (6, 3))
+        pts = rng.uniform([200, 100], [1700, 1100], (6, 2))
+        record(f, pts[None], np.tile([1.0, 0.0, 1.0], (1, 6, 1)), [6], np.arange(6)[None], kp3d, T.K)
+    san = [x for s in ([f"-fsanitize={a.sanitize}", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"] if a.sanitize else [])
+           for x in ("-Xarch_host", s)]
+    exe = os.path.join(out, "pnp_host_check")
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", *san, os.path.join(ROOT, "tools", "pnp_host_check.cpp"),
+           os.path.join(ROOT, "esa-pose-estimation_amd", "csrc", "pnp_host.hip"), *([f"-fsanitize={a.sanitize}"] if a.sanitize else []),
+           "-o", exe]
+    print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return subprocess.run([exe, os.path.join(out, "records.bin")]).returncode
+
+
+if __name__ == "__main__":
+    sys.exit(main())
