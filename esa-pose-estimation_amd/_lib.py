@@ -14,6 +14,7 @@ POSE_REPORT_FIELDS = ("status", "flags", "n", "inliers", "ransac_iters", "lm_ite
                       "min_depth", "s2")
 POSE_REPORT_COV = 12
 POSE_REPORT_DOUBLES = 33
+MAX_CANDIDATES = 4                # ESAHRNET_MAX_CANDIDATES: peaks per heat-map esahrnet_keypoints_candidates keeps at most
 
 
 class Cfg(C.Structure):
@@ -145,6 +146,11 @@ _SIGS = {
                                         C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "esahrnet_pnp_batch_w_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esahrnet_keypoints_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
+    "esahrnet_pnp_batch_cand": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "esahrnet_gather_records": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p]),
     "esahrnet_flops_per_crop": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "esahrnet_launch_count": (C.c_int, [C.c_void_p]),

@@ -318,6 +318,10 @@ int launch_head_gather(GatherParams p, hipStream_t stream, int fmt = FMT_SB);   
 // ---- arg-max + log-quadratic refine (keypoints.hip) ----------------------------------------
 // idx_out: optional int32 [planes], the flat index (row * W + column) of the arg-max
 int launch_keypoints(const float* heat, int planes, int H, int W, float* kp, int* idx_out, hipStream_t stream);
+// the M best peaks per plane (keypoints_candidates.hip): cand f32 [planes][M][3], cidx int32 [planes][M] or nullptr; row 0 is
+// launch_keypoints' row, rows m >= 1 the best local maxima at Chebyshev distance > r from every earlier one (NaN x 3, -1: none)
+int launch_keypoints_candidates(const float* heat, int planes, int H, int W, int M, int r, float* cand, int* cidx,
+                                hipStream_t stream);
 // same result from the per-tile maxima of the output-layer kernel (FinalParams::part, `ntiles` pairs per plane)
 int launch_keypoints_finish(const float* heat, const float2* part, int ntiles, int planes, int H, int W, float* kp, int* idx_out,
                             hipStream_t stream);

@@ -8,6 +8,8 @@
 // that the device stage already selected, back-projected and weighted (esahrnet_pnp_batch_w).  The _ex forms of both also
 // fill a report row per image from the finished pose (status, RANSAC consensus, residuals, the 6x6 covariance (J^T J)^-1;
 // enum esahrnet_pose_report), which takes no part in the solve.
+// esahrnet_pnp_batch_cand solves on the candidate rows of esahrnet_keypoints_candidates: the same flow on candidate 0, then one
+// repair step judged by the RANSAC consensus pose (pose_one_cand; pnp.py: candidates_to_pose is its oracle).
 //
 // It is a line-by-line native restatement of esa-pose-estimation_amd/pnp.py (which is the oracle for it:
 // tests/test_pnp_native.py compares poses and inlier sets); like that module it restates the PUBLISHED
@@ -676,7 +678,9 @@ void report_pose(const double* p3d, const double* p2d, const double* wts, int n,
 
 // ---- one image: val.py:194-224 on n correspondences (model points, image pixels, 2x2 weights) --------------------------
 // rep: the image's report row, or null; it is filled from the finished pose and takes no part in the solve
-void pose_solve(const double* p3, const double* p2, const double* w3, int n, const Cam& K, double q[4], double t[3], double* rep) {
+// judgeR / judget: null, or where a solved image leaves the RANSAC consensus pose (EPnP on the best consensus set, before the LM)
+void pose_solve(const double* p3, const double* p2, const double* w3, int n, const Cam& K, double q[4], double t[3], double* rep,
+                Mat3* judgeR = nullptr, double* judget = nullptr) {
     Mat3 R;
     double tt[3], cam[6];
     Fit fit;
@@ -684,6 +688,10 @@ void pose_solve(const double* p3, const double* p2, const double* w3, int n, con
         q[0] = q[1] = q[2] = q[3] = t[0] = t[1] = t[2] = NAN;
         if (rep) report_no_pose(rep, n < 4 ? 1 : 2, n);
         return;
+    }
+    if (judgeR) {
+        std::memcpy(*judgeR, R, sizeof(Mat3));
+        std::memcpy(judget, tt, 3 * sizeof(double));
     }
     rodrigues_inv(R, cam);
     for (int d = 0; d < 3; ++d) cam[3 + d] = tt[d];
@@ -694,27 +702,90 @@ void pose_solve(const double* p3, const double* p2, const double* w3, int n, con
     if (rep) report_pose(p3, p2, w3, n, K, R, t, fit, rep);
 }
 
-// ---- one image from its keypoint rows: val.py:172-180 (correspond.h), then the solve ---------------------------------
-void pose_one(const float* kp, int k, const double* kp3d, const Cam& K, int x0, int y0, double rate, double thresh,
-              int min_k, double q[4], double t[3], double* rep) {
-    // top-k by peak (heapq.nlargest: descending, ties keep index order)
+// ---- one image's keypoint rows -> its correspondences: val.py:172-180 (correspond.h) ------------------------------------
+// kp rows are `stride` floats apart.  -> the number selected; order[0 .. k): all keypoints, selected ones first (top-k by peak,
+// heapq.nlargest: descending, ties keep index order); p3 / p2 / wv: the selected points in that order, wv = (peak, 0, peak)
+int correspond_rows(const float* kp, int stride, int k, const double* kp3d, int x0, int y0, double rate, double thresh, int min_k,
+                    std::vector<int>& order, std::vector<double>& p3, std::vector<double>& p2, std::vector<double>& wv) {
     int above = 0;
-    for (int i = 0; i < k; ++i) above += (double)kp[i * 3 + 2] > thresh;
+    for (int i = 0; i < k; ++i) above += (double)kp[i * stride + 2] > thresh;
     const int large = esa::corr_count(above, min_k, k);
-    std::vector<int> order(k);
+    order.resize(k);
     std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return esa::corr_before(kp[a * 3 + 2], a, kp[b * 3 + 2], b); });
-    std::vector<double> p3(3 * large), p2(2 * large), wv(3 * large);
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int a, int b) { return esa::corr_before(kp[a * stride + 2], a, kp[b * stride + 2], b); });
+    p3.resize(3 * large);
+    p2.resize(2 * large);
+    wv.resize(3 * large);
     const double inv = esa::corr_inv_rate(rate);
     for (int i = 0; i < large; ++i) {
         const int j = order[i];
         for (int d = 0; d < 3; ++d) p3[i * 3 + d] = kp3d[j * 3 + d];
-        p2[i * 2 + 0] = esa::corr_to_image(kp[j * 3 + 0], inv, x0);
-        p2[i * 2 + 1] = esa::corr_to_image(kp[j * 3 + 1], inv, y0);
-        wv[i * 3 + 0] = wv[i * 3 + 2] = (double)kp[j * 3 + 2];
+        p2[i * 2 + 0] = esa::corr_to_image(kp[j * stride + 0], inv, x0);
+        p2[i * 2 + 1] = esa::corr_to_image(kp[j * stride + 1], inv, y0);
+        wv[i * 3 + 0] = wv[i * 3 + 2] = (double)kp[j * stride + 2];
         wv[i * 3 + 1] = 0.0;
     }
+    return large;
+}
+
+// ---- one image from its keypoint rows: the selection, then the solve -------------------------------------------------
+void pose_one(const float* kp, int k, const double* kp3d, const Cam& K, int x0, int y0, double rate, double thresh,
+              int min_k, double q[4], double t[3], double* rep) {
+    std::vector<int> order;
+    std::vector<double> p3, p2, wv;
+    const int large = correspond_rows(kp, 3, k, kp3d, x0, y0, rate, thresh, min_k, order, p3, p2, wv);
     pose_solve(p3.data(), p2.data(), wv.data(), large, K, q, t, rep);
+}
+
+// ---- one image from its candidate rows cand [k][M][3]: pose_one on candidate 0, then the repair step (include/esahrnet.h:
+// esahrnet_pnp_batch_cand; pnp.py: candidates_to_pose is the oracle) -------------------------------------------------------
+void pose_one_cand(const float* cand, int k, int M, const double* kp3d, const Cam& K, int x0, int y0, double rate, double thresh,
+                   int min_k, double min_ratio, double q[4], double t[3], double* rep, int* used) {
+    const double reproj = 5.0;                             // ransac()'s threshold
+    std::vector<int> order;
+    std::vector<double> p3, p2, wv;
+    const int large = correspond_rows(cand, 3 * M, k, kp3d, x0, y0, rate, thresh, min_k, order, p3, p2, wv);
+    for (int j = 0; j < k; ++j) used[j] = -1;
+    for (int i = 0; i < large; ++i) used[order[i]] = 0;
+    double r1[ESAHRNET_POSE_REPORT_DOUBLES];
+    Mat3 Rj;
+    double tj[3];
+    pose_solve(p3.data(), p2.data(), wv.data(), large, K, q, t, r1, &Rj, tj);
+    if (rep) std::memcpy(rep, r1, sizeof r1);
+    if (M == 1 || r1[ESAHRNET_REPORT_STATUS] != 0 || ((int)r1[ESAHRNET_REPORT_FLAGS] & 1)) return;
+    const double inv = esa::corr_inv_rate(rate);
+    std::vector<int> pick(large, 0);
+    bool swapped = false;
+    for (int i = 0; i < large; ++i) {
+        double pj[2];
+        project1(&p3[i * 3], Rj, tj, K, pj);
+        const double dx0 = pj[0] - p2[i * 2], dy0 = pj[1] - p2[i * 2 + 1];
+        if (!(std::sqrt(dx0 * dx0 + dy0 * dy0) >= reproj)) continue;
+        const float* c = cand + (size_t)order[i] * M * 3;
+        double best = reproj, bx = 0.0, by = 0.0;
+        for (int m = 1; m < M; ++m) {
+            if (!std::isfinite(c[m * 3]) || !std::isfinite(c[m * 3 + 1])) continue;
+            if (!((double)c[m * 3 + 2] >= min_ratio * (double)c[2])) continue;
+            const double x = esa::corr_to_image(c[m * 3 + 0], inv, x0), y = esa::corr_to_image(c[m * 3 + 1], inv, y0);
+            const double d = std::sqrt((pj[0] - x) * (pj[0] - x) + (pj[1] - y) * (pj[1] - y));
+            if (d < best) { best = d; bx = x; by = y; pick[i] = m; }
+        }
+        if (pick[i]) {
+            p2[i * 2] = bx;
+            p2[i * 2 + 1] = by;
+            wv[i * 3] = wv[i * 3 + 2] = (double)c[pick[i] * 3 + 2];
+            swapped = true;
+        }
+    }
+    if (!swapped) return;
+    double q2[4], t2[3], r2[ESAHRNET_POSE_REPORT_DOUBLES];
+    pose_solve(p3.data(), p2.data(), wv.data(), large, K, q2, t2, r2);
+    if (r2[ESAHRNET_REPORT_STATUS] != 0 || !(r2[ESAHRNET_REPORT_INLIERS] > r1[ESAHRNET_REPORT_INLIERS])) return;
+    std::memcpy(q, q2, sizeof q2);
+    std::memcpy(t, t2, sizeof t2);
+    if (rep) std::memcpy(rep, r2, sizeof r2);
+    for (int i = 0; i < large; ++i) used[order[i]] = pick[i];
 }
 
 // `work(lo, hi)` over [0, n) on up to `threads` threads
@@ -779,4 +850,23 @@ extern "C" int esahrnet_pnp_batch_w_ex(const double* pts, const double* w, const
 extern "C" int esahrnet_pnp_batch_w(const double* pts, const double* w, const int* count, int m, int k, const double* kp3d,
                                     const int* order, const double* K9, int threads, double* q_out, double* t_out) {
     return esahrnet_pnp_batch_w_ex(pts, w, count, m, k, kp3d, order, K9, threads, q_out, t_out, nullptr);
+}
+
+extern "C" int esahrnet_pnp_batch_cand(const float* cand, int n, int k, int candidates, const double* kp3d, const double* K9,
+                                       const int* boxes_xy, const double* rates, double thresh, int min_k, double min_ratio,
+                                       int threads, double* q_out, double* t_out, double* report, int* used) {
+    if (!cand || !kp3d || !K9 || !boxes_xy || !rates || !q_out || !t_out || !used) return esa::set_error("pnp_batch_cand: null argument");
+    if (n < 0) return esa::set_error("pnp_batch_cand: negative image count %d", n);
+    if (k < 1 || k > 64) return esa::set_error("pnp_batch_cand: %d keypoints per image unsupported (1..64)", k);
+    if (candidates < 1 || candidates > ESAHRNET_MAX_CANDIDATES)
+        return esa::set_error("pnp_batch_cand: %d candidates per keypoint unsupported (1..%d)", candidates, ESAHRNET_MAX_CANDIDATES);
+    if (!(min_ratio >= 0.0)) return esa::set_error("pnp_batch_cand: min_ratio %g must be a number >= 0", min_ratio);
+    const Cam K{K9[0], K9[4], K9[2], K9[5]};
+    run_batch(n, threads, [&](int lo, int hi) {
+        for (int i = lo; i < hi; ++i)
+            pose_one_cand(cand + (size_t)i * k * candidates * 3, k, candidates, kp3d, K, boxes_xy[i * 2], boxes_xy[i * 2 + 1], rates[i],
+                          thresh, min_k, min_ratio, q_out + (size_t)i * 4, t_out + (size_t)i * 3,
+                          report ? report + (size_t)i * ESAHRNET_POSE_REPORT_DOUBLES : nullptr, used + (size_t)i * k);
+    });
+    return 0;
 }

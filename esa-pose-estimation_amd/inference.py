@@ -116,6 +116,32 @@ def heatmaps_to_keypoints(heat: torch.Tensor, refine: str = "get_final", return_
     return (out[0], out[2]) if return_hessian else out[0]
 
 
+def heatmaps_to_candidates(heat: torch.Tensor, candidates: int = 3, nms_radius: int = 6, return_index: bool = False):
+    """f32 cuda [N,K,H,W] -> f32 cuda [N,K,M,3] = (x, y, peak), the M = `candidates` (1..4) best peaks of every heat-map, best
+    first (include/esahrnet.h esahrnet_keypoints_candidates, one kernel, no host sync).  Candidate 0 is the row of
+    heatmaps_to_keypoints, bit for bit; candidate m >= 1 is the largest local maximum (>= its 8 neighbours, neither NaN nor
+    -inf, no NaN neighbour) at Chebyshev distance > nms_radius from every earlier candidate, ties to the lower index, refined
+    by the same get_final step at its own pixel; rows without a qualifying pixel are NaN.  return_index=True: -> (cand, idx int32
+    cuda [N,K,M] = row * W + column of each candidate, -1 where there is none).  pnp.candidates_to_pose_batch solves on them."""
+    if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
+        raise ValueError("expected a 4-D tensor [N, K, H, W]")
+    if not heat.is_cuda:
+        raise RuntimeError("heatmaps_to_candidates runs on the GPU only (no CPU fallback)")
+    if heat.dtype != torch.float32:
+        raise TypeError(f"expected float32 heatmaps, got {heat.dtype}")
+    heat = heat.contiguous()
+    n, k, h, w = heat.shape
+    m = int(candidates)
+    # (the library refuses M outside 1..4 and a negative radius with its own text; nothing is allocated by M before that)
+    cand = torch.empty((n, k, min(max(m, 1), _lib.MAX_CANDIDATES), 3), dtype=torch.float32, device=heat.device)
+    idx = torch.empty(cand.shape[:3], dtype=torch.int32, device=heat.device) if return_index else None
+    stream = torch.cuda.current_stream(heat.device).cuda_stream
+    with torch.cuda.device(heat.device):
+        _lib.check(_lib.lib().esahrnet_keypoints_candidates(heat.data_ptr(), n, k, h, w, m, int(nms_radius), cand.data_ptr(),
+                                                            idx.data_ptr() if return_index else None, C.c_void_p(stream)))
+    return (cand, idx) if return_index else cand
+
+
 def check_cov_floor(cov_floor) -> float:
     """cov_floor of the covariance outputs: a number >= 0 (the reference's evaluation.py:479 uses 1e-6)."""
     try:

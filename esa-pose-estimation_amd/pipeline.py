@@ -118,7 +118,7 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
                    on_fail: str = "raise", keypoints_only: bool = False, refine: str = "get_final",
                    device_loader: bool = False, frame_idx=None, rule: str = "val", device_select: bool = False,
                    weights: str = "peak", threads: int = 0, cov_floor: float = 1e-6, return_report: bool = False,
-                   max_rms_px=None, min_inliers=None):
+                   max_rms_px=None, min_inliers=None, candidates: int = 1, nms_radius: int = 6, min_ratio: float = 0.3):
     """One batch of the val.py:136-233 loop.  frames uint8 cuda [N,H,W]; bboxes N x (x, y, x2, y2);
     kp3d [K3, 3] model keypoints; K camera matrix.  -> list of (q [w,x,y,z], t) per image.
     An image without a solution (the native solver reports it as a NaN row; the reference would die inside
@@ -150,10 +150,21 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
     pose (report.covariance()); the poses are the ones of the call without it, bit for bit.  Gates: a solved pose whose rms_px
     exceeds max_rms_px or whose inliers are fewer than min_inliers is treated exactly like "no pose" — a NaN row, on_fail
     applies — while its report row keeps the real numbers and report.gated marks it; both default to None (no gate).  With
-    device_loader=True a crop the loader could not make has a report row of status 1 with n = 0."""
+    device_loader=True a crop the loader could not make has a report row of status 1 with n = 0.
+    candidates=M > 1 (heat-map path, native solver, refine="get_final"): the decoder keeps the M best peaks of every heat-map
+    (inference.heatmaps_to_candidates, `nms_radius` pixels apart), ONE device->host copy of them, and the native solve swaps a
+    runner-up with at least `min_ratio` of the primary's peak in where the RANSAC consensus pose says the primary is wrong
+    (pnp.candidates_to_pose_batch; the report then carries .used and .rescued).  It is refused together with keypoints_only,
+    device_loader, device_select, distributed, native=False and any other refine; candidates=1 leaves every path as it is."""
     inference.check_refine(refine)
     inference.check_weights(weights, refine)
     want = return_report or max_rms_px is not None or min_inliers is not None
+    if candidates != 1:
+        for name, on in (("keypoints_only", keypoints_only), ("device_loader", device_loader), ("device_select", device_select),
+                         ("distributed", distributed), ("native=False", not native), (f"refine='{refine}'", refine != "get_final")):
+            if on:
+                raise ValueError(f"candidates={candidates} is not available with {name}: runner-up peaks are decoded on the "
+                                 "heat-map path (get_final) and solved by the native entry")
     if want and not native:
         raise ValueError("return_report and the max_rms_px / min_inliers gates read the native solver's report (native=False has none)")
 
@@ -216,6 +227,13 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
         raise ValueError("frame_idx and rule belong to device_loader=True (crops.crop_batch: one val box per frame)")
     rk = {} if refine == "get_final" else {"refine": refine}
     x, boxes, rates = crops.crop_batch(frames, bboxes, scale)
+    if candidates != 1:
+        with torch.no_grad():
+            cand = inference.heatmaps_to_candidates(net(x), candidates, nms_radius)
+        cand = cand.cpu().numpy()                           # the only device->host copy: N*K*M*3 floats
+        q, t, _, *rep = pnp.candidates_to_pose_batch(cand, kp3d, np.asarray(K, np.float64), [(b[0], b[1]) for b in boxes], rates,
+                                                     thresh, min_k, min_ratio, threads, report=want)
+        return finish([(q[i], t[i]) for i in range(len(boxes))], rep[0] if want else None)
     with torch.no_grad():
         if distributed:
             kp = parallel.sharded_keypoints(net, x, keypoints_only=keypoints_only, **rk)

@@ -405,7 +405,9 @@ class PoseReport:
     include/esahrnet.h's enum esahrnet_pose_report: status, flags, n, inliers, ransac_iters, lm_iters, argmax (integer arrays;
     -1 where the row has no pose and the field is NaN), cost, rms_px, max_px, min_depth, s2 (f64), and cov [m, 6, 6], the full
     symmetric inverse of J^T J.  `raw` is the [m, 33] f64 array as the library wrote it.  `gated` [m] bool: poses that
-    pipeline.estimate_poses withdrew through max_rms_px / min_inliers (all False elsewhere)."""
+    pipeline.estimate_poses withdrew through max_rms_px / min_inliers (all False elsewhere).  A report of
+    candidates_to_pose_batch also carries `used` [m, K] int32, the candidate rank each keypoint entered the returned pose's solve
+    with (-1: not selected), and `rescued` [m] bool: poses in which a runner-up replaced a primary; both are None elsewhere."""
 
     INTEGER = ("status", "flags", "n", "inliers", "ransac_iters", "lm_iters", "argmax")
 
@@ -422,6 +424,7 @@ class PoseReport:
         self.cov[:, iu[0], iu[1]] = raw[:, _lib.POSE_REPORT_COV:]
         self.cov[:, iu[1], iu[0]] = raw[:, _lib.POSE_REPORT_COV:]
         self.gated = np.zeros(len(raw), bool)
+        self.used = self.rescued = None
 
     def __len__(self):
         return len(self.raw)
@@ -507,6 +510,97 @@ def correspondences_to_pose_batch(pts, w, count, order, kp3d, K, threads=0, repo
         return q, t, PoseReport(rep)
     _lib.check(_lib.lib().esahrnet_pnp_batch_w(p(pts), p(w), p(count), n, k, p(kp3d), p(order), p(K9), int(threads), p(q), p(t)))
     return q, t
+
+
+def candidates_to_pose_batch(cand, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=24, min_ratio=0.3, threads=0, report=False):
+    """keypoints_to_pose_batch on the candidates of inference.heatmaps_to_candidates, with the repair step of
+    `esahrnet_pnp_batch_cand` (include/esahrnet.h): cand [N,K,M,3] f32 = (x, y, peak), best first.  Per image the solve on
+    candidate 0; where that pose has a RANSAC consensus, every selected keypoint whose primary lies >= 5 px from its projection
+    under the consensus pose (EPnP on the consensus set, before the LM) takes its closest runner-up with peak >= min_ratio *
+    primary peak that lies < 5 px from it; the repaired set is solved again and taken iff it has more inliers.
+    -> (q [N,4], t [N,3], used [N,K] int32: the candidate rank each keypoint entered the returned solve with, -1 = not selected).
+    With M = 1, and for images in which nothing is replaced, the bits of keypoints_to_pose_batch on cand[:, :, 0].
+    `candidates_to_pose` below is its oracle.  report=True: -> (q, t, used, rep), rep a PoseReport of the returned poses with
+    rep.used and rep.rescued."""
+    import ctypes as C
+    import os
+    from . import _lib
+    cand = np.ascontiguousarray(cand, np.float32)
+    if cand.ndim != 4 or cand.shape[3] != 3:
+        raise ValueError(f"expected candidates [N, K, M, 3], got {cand.shape}")
+    n, k, m = cand.shape[:3]
+    kp3d = np.ascontiguousarray(kp3d, np.float64)
+    K9 = np.ascontiguousarray(K, np.float64).reshape(9)
+    bxy = np.ascontiguousarray(np.asarray(boxes_xy)[:, :2], np.int32)
+    rt = np.ascontiguousarray(rates, np.float64)
+    assert kp3d.shape == (k, 3) and bxy.shape == (n, 2) and rt.shape == (n,)
+    q = np.empty((n, 4), np.float64)
+    t = np.empty((n, 3), np.float64)
+    used = np.empty((n, k), np.int32)
+    rep = np.empty((n, _lib.POSE_REPORT_DOUBLES), np.float64) if report else None
+    if threads <= 0:
+        threads = min(16, len(os.sched_getaffinity(0))) if hasattr(os, "sched_getaffinity") else 4
+    p = lambda a: a.ctypes.data_as(C.c_void_p)                       # noqa: E731
+    _lib.check(_lib.lib().esahrnet_pnp_batch_cand(p(cand), n, k, m, p(kp3d), p(K9), p(bxy), p(rt), float(thresh), int(min_k),
+                                                  float(min_ratio), int(threads), p(q), p(t), p(rep) if report else None, p(used)))
+    if not report:
+        return q, t, used
+    rep = PoseReport(rep)
+    rep.used = used
+    rep.rescued = (used > 0).any(1)
+    return q, t, used, rep
+
+
+def candidates_to_pose(cand, kp3d, K, bbox_xy, rate, thresh=0.8, min_k=24, min_ratio=0.3, reproj_err=5.0):
+    """The numpy statement of one image of candidates_to_pose_batch (its oracle): cand [K,M,3] -> (q [w,x,y,z], t, used [K]).
+    keypoints_to_pose's steps on candidate 0, the judge = solve_pnp_ransac's pose (EPnP on the consensus set), the swap rule,
+    then the same steps on the repaired points; taken iff the consensus grew."""
+    from .inference import crop_to_image, select_keypoints
+    cand = np.asarray(cand, np.float32)
+    assert cand.ndim == 3 and cand.shape[2] == 3, cand.shape
+    nk, M = cand.shape[:2]
+    K = np.asarray(K, np.float64)
+    c64 = cand.astype(np.float64)
+    idxs = list(select_keypoints(c64[:, 0, 2], thresh, min_k))
+    p3d = np.asarray(kp3d, np.float64)[idxs]
+
+    def solve(p2d, w):
+        R, t, _, (inliers, _, fallback) = solve_pnp_ransac(p3d, p2d, K, reproj_err=reproj_err, return_stats=True)
+        cam = cpnp_m(p3d, p2d, w, K, np.concatenate([rodrigues_inv(R), t]))
+        return rotation_to_quat_wxyz(rodrigues(cam[:3])), cam[3:], (R, t), inliers, fallback
+
+    p2d = crop_to_image(c64[:, 0, :2], rate, bbox_xy[0], bbox_xy[1])[idxs]
+    w = c64[idxs, 0, 2]
+    used = np.full(nk, -1, np.int32)
+    used[idxs] = 0
+    q1, t1, judge, inl1, fallback = solve(p2d, w)
+    if M == 1 or fallback:
+        return q1, t1, used
+    proj = project(p3d, judge[0], judge[1], K)
+    with np.errstate(all="ignore"):
+        d0 = np.linalg.norm(proj - p2d, axis=1)
+    p2d, w, pick = p2d.copy(), w.copy(), np.zeros(len(idxs), np.int32)
+    for i, j in enumerate(idxs):
+        if not d0[i] >= reproj_err:
+            continue
+        best = reproj_err
+        for m in range(1, M):
+            if not np.isfinite(c64[j, m, :2]).all() or not c64[j, m, 2] >= min_ratio * c64[j, 0, 2]:
+                continue
+            xy = crop_to_image(c64[j, m, :2], rate, bbox_xy[0], bbox_xy[1])
+            d = float(np.linalg.norm(proj[i] - xy))
+            if d < best:
+                best, pick[i], p2d[i], w[i] = d, m, xy, c64[j, m, 2]
+    if not pick.any():
+        return q1, t1, used
+    try:
+        q2, t2, _, inl2, _ = solve(p2d, w)
+    except np.linalg.LinAlgError:
+        return q1, t1, used
+    if not inl2 > inl1:
+        return q1, t1, used
+    used[idxs] = pick
+    return q2, t2, used
 
 
 def keypoints_to_pose(kp, kp3d, K, bbox_xy, rate, thresh=0.8, min_k=24):

@@ -132,6 +132,24 @@ int esahrnet_keypoints(const void* heat_dev, int n, int k, int height, int width
 int esahrnet_keypoints_ex(const void* heat_dev, int n, int k, int height, int width,
                           void* kp_dev, void* idx_dev, esahrnet_stream stream);
 
+/* ---- runner-up peaks: the M best local maxima of every heat-map (csrc/keypoints_candidates.hip) -------------------------------
+ * heat_dev f32 [n][k][height][width], candidates = M in 1..ESAHRNET_MAX_CANDIDATES, nms_radius = r >= 0 ->
+ *   cand_dev f32 [n][k][M][3]  (x, y, peak) per candidate, best first.
+ *   cidx_dev int32 [n][k][M]   row * width + column of each candidate's pixel, -1 where there is none (NULL: not written).
+ * Candidate 0 is the row and the index of esahrnet_keypoints_ex, bit for bit (first row-major arg-max, NaN counts as the
+ * maximum, all-NaN and all -inf planes give index 0).  Candidate m >= 1 is the largest value among the pixels that (a) are
+ * neither NaN nor -inf, (b) are local maxima: at least as large as each of their 8 neighbours — neighbours outside the plane
+ * are ignored, a NaN neighbour disqualifies —, and (c) lie at Chebyshev distance greater than r from every candidate 0..m-1;
+ * ties go to the lower index.  Each candidate gets the sub-pixel step of esahrnet_keypoints at its own pixel; its peak is the
+ * raw value there.  When no pixel qualifies, that row and all later rows are NaN x 3 with index -1.
+ * One launch, one workgroup per plane, the M sweeps of a plane back to back (the later ones read it from L2); a plane's result
+ * does not depend on its batch.  No workspace.  Allocates nothing, does not synchronise, may be captured into a graph; argument
+ * errors (NULL heat_dev or cand_dev, a shape that is not positive, M outside 1..4, r < 0, a pointer that is not 4-byte aligned)
+ * are reported before anything is enqueued. */
+#define ESAHRNET_MAX_CANDIDATES 4
+int esahrnet_keypoints_candidates(const void* heat_dev, int n, int k, int height, int width, int candidates, int nms_radius,
+                                  void* cand_dev, void* cidx_dev, esahrnet_stream stream);
+
 /* ---- the second decoder: get_final2 (inference.py:154-169) ---------------------------------------------------------
  * Same arg-max, peak and idx_dev as esahrnet_keypoints_ex (bit-identical), but the sub-pixel step of get_final2: each plane
  * blurred by the 11x11 Gaussian of cv2.GaussianBlur(., (11, 11), 0) (sigma 2, zero padding, f64 sums, rounded to f32),
@@ -448,6 +466,30 @@ int esahrnet_pnp_batch_ex(const float* kp, int n, int k, const double* kp3d, con
                           double* report);
 int esahrnet_pnp_batch_w_ex(const double* pts, const double* w, const int* count, int m, int k, const double* kp3d,
                             const int* order, const double* K9, int threads, double* q_out, double* t_out, double* report);
+
+/* esahrnet_pnp_batch_ex on the candidates esahrnet_keypoints_candidates wrote (a host copy), with one repair step: cand = f32
+ * [n][k][M][3], M = candidates in 1..ESAHRNET_MAX_CANDIDATES; kp3d, K9, boxes_xy, rates, thresh, min_k as above; min_ratio a
+ * number >= 0.  Per image:
+ *   1. the solve of esahrnet_pnp_batch_ex on candidate 0 of every keypoint: pose P1, report row R1;
+ *   2. done, with P1, when M = 1, R1's status is not 0 or its flag bit 0 is set (no consensus of at least 4);
+ *   3. the judge is the RANSAC consensus pose — EPnP on the best consensus set, BEFORE the LM refinement, which an outlier has
+ *      already pulled;
+ *   4. for every selected keypoint whose candidate 0 lies >= 5 px (the RANSAC threshold) from its projection under the judge:
+ *      a candidate m >= 1 of that keypoint qualifies when its coordinates are finite, peak_m >= min_ratio * peak_0 and its own
+ *      distance to the projection is < 5 px; the qualifying candidate with the smallest distance (ties: the lower m) replaces
+ *      candidate 0, as point and as weight;
+ *   5. done, with P1, when nothing was replaced;
+ *   6. otherwise the same solve (same selection order, same seed) on the repaired points: P2, R2, taken iff R2's status is 0
+ *      and R2.INLIERS > R1.INLIERS; else P1 and R1.
+ * used = int32 [n][k]: the candidate each keypoint entered the returned pose's solve with, -1 for a keypoint that was not
+ * selected (all of them in an image without a pose keep what the selection gave them: 0 or -1).  report: f64
+ * [n][ESAHRNET_POSE_REPORT_DOUBLES] of the returned pose, or null.  With M = 1, and for every image in which nothing is
+ * replaced or P2 is not taken, q_out, t_out and the report row are bit-identical to esahrnet_pnp_batch_ex on candidate 0.  A row
+ * depends on its image alone: the same bits for any `threads`.  Refused: a null pointer but report, n < 0, k outside 1..64, M
+ * outside 1..4, a min_ratio that is negative or NaN. */
+int esahrnet_pnp_batch_cand(const float* cand, int n, int k, int candidates, const double* kp3d, const double* K9,
+                            const int* boxes_xy, const double* rates, double thresh, int min_k, double min_ratio, int threads,
+                            double* q_out, double* t_out, double* report, int* used);
 
 /* The packed records of the device path after the all-gather of a sharded batch (csrc/records.hip).  A packed record is
  * field-major: field f holds field_bytes[f] bytes per crop, all crops of field 0 first, then field 1, ..., so field f of a

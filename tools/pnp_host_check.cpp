@@ -4,12 +4,14 @@
 // tools/pnp_host_check.py wrote through esahrnet_pnp_batch_w_ex (and esahrnet_pnp_batch_ex where the record has keypoint
 // rows), with 1 and 4 threads, with and without a report buffer.  It checks what tests/test_pose_report_host.py checks at the
 // C level: the poses do not depend on the report or the thread count, nor do the report's bits, and the old entries are the
-// new ones with a null report.  Exit status 0 and "ok" when all of it holds.  Pure host code: no GPU is touched.
+// new ones with a null report.  A second file holds candidate records for esahrnet_pnp_batch_cand: the same bits at 1 and 4
+// threads, with and without a report, and with one candidate the bits of esahrnet_pnp_batch_ex.  Exit status 0 and "ok" when
+// all of it holds.  Pure host code: no GPU is touched.
 //
 // Build and run (tools/pnp_host_check.py does both):
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         tools/pnp_host_check.cpp esa-pose-estimation_amd/csrc/pnp_host.hip -fsanitize=address,undefined -o pnp_host_check
-//   ./pnp_host_check records.bin
+//   ./pnp_host_check records.bin candidates.bin
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -39,8 +41,88 @@ static bool same(const std::vector<double>& a, const std::vector<double>& b) {
     return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0;
 }
 
+// candidate records: int32 (m, k, M), cand f32 [m][k][M][3], kp3d f64 [k][3], K9, boxes int32 [m][2], rates f64 [m],
+// (thresh, min_k, min_ratio) f64.  Every buffer handed to the library has its exact size.
+static int check_candidates(const char* path) {
+    FILE* f = std::fopen(path, "rb");
+    if (!f) { std::perror(path); return 2; }
+    int32_t head[3];
+    int nrec = 0;
+    const size_t R = ESAHRNET_POSE_REPORT_DOUBLES;
+    while (std::fread(head, sizeof(int32_t), 3, f) == 3) {
+        const int m = head[0], k = head[1], M = head[2];
+        std::vector<float> cand;
+        std::vector<double> kp3d, K9, rates, sel;
+        std::vector<int32_t> boxes;
+        if (!(read_vec(f, cand, (size_t)m * k * M * 3) && read_vec(f, kp3d, (size_t)k * 3) && read_vec(f, K9, 9) &&
+              read_vec(f, boxes, (size_t)m * 2) && read_vec(f, rates, m) && read_vec(f, sel, 3))) {
+            std::fprintf(stderr, "candidate record %d is cut short\n", nrec);
+            return 2;
+        }
+        std::vector<double> q0, t0, rep0;
+        std::vector<int32_t> used0;
+        for (int threads : {1, 4})
+            for (int with_report = 0; with_report < 2; ++with_report) {
+                std::vector<double> q((size_t)m * 4), t((size_t)m * 3), rep(with_report ? m * R : 0);
+                std::vector<int32_t> used((size_t)m * k);
+                if (esahrnet_pnp_batch_cand(cand.data(), m, k, M, kp3d.data(), K9.data(), boxes.data(), rates.data(), sel[0], (int)sel[1],
+                                            sel[2], threads, q.data(), t.data(), with_report ? rep.data() : nullptr, used.data())) {
+                    std::fprintf(stderr, "candidate record %d: %s\n", nrec, esa::g_err);
+                    return 1;
+                }
+                if (q0.empty()) { q0 = q; t0 = t; used0 = used; }
+                if (with_report && rep0.empty()) rep0 = rep;
+                if (!same(q, q0) || !same(t, t0) || used != used0 || (with_report && !same(rep, rep0))) {
+                    std::fprintf(stderr, "candidate record %d: results differ (threads %d, report %d)\n", nrec, threads, with_report);
+                    return 1;
+                }
+            }
+        // candidate 0 alone, through both entries
+        std::vector<float> first((size_t)m * k * 3);
+        for (size_t i = 0; i < (size_t)m * k; ++i) std::memcpy(&first[i * 3], &cand[i * M * 3], 3 * sizeof(float));
+        std::vector<double> q1((size_t)m * 4), t1((size_t)m * 3), rep1(m * R), q2((size_t)m * 4), t2((size_t)m * 3), rep2(m * R);
+        std::vector<int32_t> used1((size_t)m * k);
+        if (esahrnet_pnp_batch_cand(first.data(), m, k, 1, kp3d.data(), K9.data(), boxes.data(), rates.data(), sel[0], (int)sel[1], sel[2],
+                                    4, q1.data(), t1.data(), rep1.data(), used1.data()) ||
+            esahrnet_pnp_batch_ex(first.data(), m, k, kp3d.data(), K9.data(), boxes.data(), rates.data(), sel[0], (int)sel[1], 4,
+                                  q2.data(), t2.data(), rep2.data())) {
+            std::fprintf(stderr, "candidate record %d: %s\n", nrec, esa::g_err);
+            return 1;
+        }
+        if (!same(q1, q2) || !same(t1, t2) || !same(rep1, rep2)) {
+            std::fprintf(stderr, "candidate record %d: one candidate is not esahrnet_pnp_batch_ex\n", nrec);
+            return 1;
+        }
+        int rescued = 0, swaps = 0, solved = 0;
+        for (int i = 0; i < m; ++i) {
+            int s = 0;
+            for (int j = 0; j < k; ++j) s += used0[(size_t)i * k + j] > 0;
+            rescued += s > 0;
+            swaps += s;
+            solved += rep0[i * R + ESAHRNET_REPORT_STATUS] == 0;
+        }
+        std::printf("candidate record %d: %d images of %d keypoints x %d candidates, %d solved, %d rescued with %d swaps\n", nrec, m, k,
+                    M, solved, rescued, swaps);
+        ++nrec;
+    }
+    std::fclose(f);
+    double q[4], t[3];
+    int used[11];
+    float c[11 * 3] = {0};
+    double z[33] = {0};
+    int b[2] = {0, 0};
+    if (esahrnet_pnp_batch_cand(c, 1, 11, 5, z, z, b, z, 0.5, 0, 0.3, 1, q, t, nullptr, used) != 1 || !std::strstr(esa::g_err, "candidates") ||
+        esahrnet_pnp_batch_cand(c, 1, 11, 1, z, z, b, z, 0.5, 0, -1.0, 1, q, t, nullptr, used) != 1 || !std::strstr(esa::g_err, "min_ratio") ||
+        esahrnet_pnp_batch_cand(c, 1, 11, 1, z, z, b, z, 0.5, 0, 0.3, 1, q, t, nullptr, nullptr) != 1 || !std::strstr(esa::g_err, "null")) {
+        std::fprintf(stderr, "a bad argument of esahrnet_pnp_batch_cand was not refused\n");
+        return 1;
+    }
+    std::printf("ok: %d candidate records\n", nrec);
+    return nrec ? 0 : 2;
+}
+
 int main(int argc, char** argv) {
-    if (argc != 2) { std::fprintf(stderr, "usage: %s records.bin\n", argv[0]); return 2; }
+    if (argc != 2 && argc != 3) { std::fprintf(stderr, "usage: %s records.bin [candidates.bin]\n", argv[0]); return 2; }
     FILE* f = std::fopen(argv[1], "rb");
     if (!f) { std::perror(argv[1]); return 2; }
     int32_t head[3];
@@ -108,5 +190,6 @@ int main(int argc, char** argv) {
         return 1;
     }
     std::printf("ok: %d records\n", nrec);
-    return nrec ? 0 : 2;
+    if (!nrec) return 2;
+    return argc == 3 ? check_candidates(argv[2]) : 0;
 }

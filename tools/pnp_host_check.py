@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Build tools/pnp_host_check.cpp with the host solver under host sanitizers and run it on the batches of
 tests/test_pose_report_host.py (the 64-image batch of its tests 1 and 2, as a correspondence record and as keypoint rows; the
-same record with all but two weights zero; the six random points without a consensus).  CPU only; nothing is loaded into
-Python.  --sanitize "" builds it plain."""
+same record with all but two weights zero; the six random points without a consensus) and, for esahrnet_pnp_batch_cand, on the
+scenes of tests/test_candidates_host.py (its three cases at their seeds, with 3 and with 4 candidate rows, and three-keypoint
+images without a pose).  CPU only; nothing is loaded into Python.  --sanitize "" builds it plain."""
 import argparse
 import os
 import subprocess
@@ -25,6 +26,14 @@ def record(f, pts, w, count, order, kp3d, K, kp=None, boxes=None, rates=None, th
             np.ascontiguousarray(a, dt).tofile(f)
 
 
+def candidate_record(f, cand, kp3d, K, boxes, rates, thresh, min_k, min_ratio=0.3):
+    m, k, M = cand.shape[:3]
+    np.array([m, k, M], np.int32).tofile(f)
+    for a, dt in ((cand, np.float32), (kp3d, np.float64), (K, np.float64), (boxes, np.int32), (rates, np.float64),
+                  ([thresh, min_k, min_ratio], np.float64)):
+        np.ascontiguousarray(a, dt).tofile(f)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sanitize", default="address,undefined")
@@ -44,6 +53,14 @@ def main():
         kp3d = rng.uniform(-0.5, 0.5, (6, 3))
         pts = rng.uniform([200, 100], [1700, 1100], (6, 2))
         record(f, pts[None], np.tile([1.0, 0.0, 1.0], (1, 6, 1)), [6], np.arange(6)[None], kp3d, T.K)
+    import test_candidates_host as TC
+    with open(os.path.join(out, "candidates.bin"), "wb") as f:
+        for k, nbad in TC.CASES:
+            for M in (3, 4):
+                kp3d, cand, boxes, rates, _, _ = TC.scene(np.random.default_rng(TC.seed_of(k, nbad)), TC.N, k, nbad, M=M)
+                candidate_record(f, cand, kp3d, TC.K, boxes, rates, 0.0, k)
+        kp3d, cand, boxes, rates, _, _ = TC.scene(np.random.default_rng(15), 3, 3, 1)
+        candidate_record(f, cand, kp3d, TC.K, boxes, rates, 0.0, 3)
     san = [x for s in ([f"-fsanitize={a.sanitize}", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"] if a.sanitize else [])
            for x in ("-Xarch_host", s)]
     exe = os.path.join(out, "pnp_host_check")
@@ -52,7 +69,7 @@ def main():
            "-o", exe]
     print(" ".join(cmd))
     subprocess.run(cmd, check=True)
-    return subprocess.run([exe, os.path.join(out, "records.bin")]).returncode
+    return subprocess.run([exe, os.path.join(out, "records.bin"), os.path.join(out, "candidates.bin")]).returncode
 
 
 if __name__ == "__main__":
