@@ -30,6 +30,12 @@
 
 namespace esa {
 int final_kt(int K);
+// abi_decode.hip: the argument checks its handle-free entries share with the loader entries here (`who` names the entry)
+extern const int kFrontendMaxRows;
+int check_boxes_args(const char* who, int m, int frame_h, int frame_w, int scale, int rule);
+int check_crops_args(const char* who, int nframes, int pixel_format, float stdv);
+int check_cov_args(const char* who, const void* cov_dev, const void* info_dev, double cov_floor);
+int check_corr_args(const char* who, int m, int k, int mode);
 }
 
 namespace {
@@ -1604,13 +1610,6 @@ int esahrnet_set_debug_keep(esahrnet_handle h, int keep) {
     return 0;
 }
 
-int esahrnet_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
-    if (!h || !bytes) return fail("workspace_bytes: null argument");
-    if (plan_shape(*h, n, height, width)) return 1;
-    *bytes = h->sp.bytes;
-    return 0;
-}
-
 // kernel and (printf-formatted) label of an op description
 __attribute__((format(printf, 3, 4)))
 static void describe(esahrnet_op_desc* d, const char* kernel, const char* label, ...) {
@@ -1621,73 +1620,137 @@ static void describe(esahrnet_op_desc* d, const char* kernel, const char* label,
     va_end(ap);
 }
 
+// What a forward leaves in caller memory in place of heat-maps: the decoder and where its results go.
+enum Decoder { DEC_NONE, DEC_FINAL, DEC_FINAL2, DEC_GAUSSFIT };     // none (heat-maps), get_final, get_final2, the Gaussian fit
+struct Request {
+    Decoder decoder = DEC_NONE;
+    float* kp = nullptr;        // f32 [n * K][3], never null
+    int* idx = nullptr;         // int32 [n * K] (nullptr: not asked for)
+    double* hess = nullptr;     // f64 [n * K][3], the Hessian each get_final2 step / the fit used (nullptr: not asked for)
+    double* fit = nullptr;      // the Gaussian fit: f64 [n * K][8] (may be null) and int32 [n * K] (never null)
+    int* status = nullptr;
+    double* cov = nullptr;      // ... f64 [n * K][3] each, the covariance of the fitted centre and -cov^-1 (both nullptr: not
+    double* info = nullptr;     // asked for, the kernels then compute what esahrnet_forward_keypoints_gaussfit computes)
+    double cov_floor = 0.0;
+};
+
+// The one place a request is built, for the four forms the entries come in: (kp, idx), + hess, + fit and status, + cov, info and
+// cov_floor.  Two rules are stated here and nowhere else: get_final computes no Hessian, so hess is ignored by it; cov and
+// info belong to the Gaussian fit, and are ignored without it.
+static Request make_request(Decoder d, void* kp, void* idx, void* hess = nullptr, void* fit = nullptr, void* status = nullptr,
+                            void* cov = nullptr, void* info = nullptr, double cov_floor = 0.0) {
+    Request r;
+    r.decoder = d;
+    r.kp = static_cast<float*>(kp);
+    r.idx = static_cast<int*>(idx);
+    r.hess = d == DEC_FINAL ? nullptr : static_cast<double*>(hess);
+    r.fit = static_cast<double*>(fit);
+    r.status = static_cast<int*>(status);
+    r.cov = d == DEC_GAUSSFIT ? static_cast<double*>(cov) : nullptr;
+    r.info = d == DEC_GAUSSFIT ? static_cast<double*>(info) : nullptr;
+    r.cov_floor = cov_floor;
+    return r;
+}
+
 // the device buffers of one forward (all nullptr when an op is only described)
 struct Buffers {
     const void* x;
     void* heat;
     char* ws;
     void* part;
-    // esahrnet_forward_keypoints: the last op (OP_FINAL / OP_TONCHW) writes keypoints instead of heat-maps (heat == nullptr),
-    // through the scratch behind the forward's workspace (KpScratch)
-    float* kp = nullptr;
-    int* idx = nullptr;
+    // with a request the last op (OP_FINAL / OP_TONCHW) writes keypoints instead of heat-maps (heat == nullptr), through the
+    // scratch behind the forward's workspace, carved as KpScratch lays it out.  kws: the bytes at kpart
+    Request req;
     float* kheat = nullptr;
     float2* kpart = nullptr;
-    // esahrnet_forward_keypoints_final2: the same, decoded with get_final2.  kbmax: the VALU output layer's blurred tile maxima;
-    // kws: the bytes at kpart that launch_keypoints_final2(_nhwc) may use
-    bool final2 = false;
     float* kbmax = nullptr;
     size_t kws = 0;
-    // esahrnet_forward_keypoints_final2_hess: f64 [n * K][3], the Hessian each get_final2 step used (nullptr: not asked for)
-    double* hess = nullptr;
-    // esahrnet_forward_keypoints_gaussfit: the same scratch as esahrnet_forward_keypoints, decoded with the Gaussian fit.  status
-    // int32 [n * K] (never null then), fit f64 [n * K][8] and hess f64 [n * K][3] (may be null); without idx the arg-max index
-    // passes through status
-    bool gaussfit = false;
-    double* fit = nullptr;
-    int* status = nullptr;
-    // esahrnet_forward_keypoints_gaussfit_cov: f64 [n * K][3] each, the covariance of the fitted centre and -cov^-1 (both nullptr:
-    // not asked for, the kernels of esahrnet_forward_keypoints_gaussfit)
-    double* cov = nullptr;
-    double* info = nullptr;
-    double cov_floor = 0.0;
 };
 
-// What esahrnet_forward_keypoints keeps behind the forward's workspace (at ShapePlan::bytes, a multiple of 256): the per-tile
-// maxima of the output layer and, where that is the matrix-core kernel, its heat-maps (that kernel writes them in any case)
-// esahrnet_forward_keypoints_final2 keeps: seg_hrnet3, get_final2's per-tile raw and blurred maxima of the NHWC heat-maps
-// (part: esa::final2_workspace_bytes); the matrix-core output layer, its heat-maps and the same; the VALU output layer, the
-// raw (part) and blurred (bmax) maxima of its 22 x 22 tiles.  No N*K*H*W term but the matrix-core one.
+// What a decoder keeps behind the forward's workspace (at ShapePlan::bytes, a multiple of 256), one row per decoder: heat,
+// then part, then bmax.
+//   get_final, Gaussian fit   the per-tile maxima of the output layer (part) and, where that is the matrix-core kernel, its
+//                             heat-maps (that kernel writes them in any case)
+//   get_final2                seg_hrnet3, get_final2's per-tile raw and blurred maxima of the NHWC heat-maps (part:
+//                             esa::final2_workspace_bytes); the matrix-core output layer, its heat-maps and the same; the VALU
+//                             output layer, the raw (part) and blurred (bmax) maxima of its 22 x 22 tiles
+// No N*K*H*W term but the matrix-core one.
 struct KpScratch {
     int ntiles = 0;
     size_t heat = 0, part = 0, bmax = 0;
+    size_t part_off() const { return heat; }
+    size_t bmax_off() const { return heat + part; }
+    size_t total() const { return heat + part + bmax; }
 };
-static KpScratch kp_scratch(const esahrnet_ctx& c, int n, int height, int width, bool final2 = false) {
+static KpScratch kp_scratch(const esahrnet_ctx& c, int n, int height, int width, Decoder d) {
     KpScratch s;
     const int K = c.cfg.num_keypoints;
     const long long planes = (long long)n * K;
-    if (final2) {
-        if (c.cfg.variant != 1 && c.opt.final_mfma) s.heat = ((size_t)planes * height * width * 4 + 255) & ~(size_t)255;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    if (d == DEC_NONE) return s;
+    if (c.cfg.variant != 1 && c.opt.final_mfma) s.heat = pad((size_t)planes * height * width * 4);
+    if (d == DEC_FINAL2) {
         if (c.cfg.variant == 1 || c.opt.final_mfma) {
             s.ntiles = esa::final2_tiles(height, width);
             s.part = esa::final2_workspace_bytes(planes, height, width);
         } else {
             s.ntiles = esa::final2_valu_tiles(height, width);
-            s.part = ((size_t)planes * s.ntiles * 8 + 255) & ~(size_t)255;
-            s.bmax = ((size_t)planes * s.ntiles * 4 + 255) & ~(size_t)255;
+            s.part = pad((size_t)planes * s.ntiles * 8);
+            s.bmax = pad((size_t)planes * s.ntiles * 4);
         }
         return s;
     }
-    if (c.cfg.variant == 1) {
-        s.ntiles = esa::to_nchw_part_tiles(height, width);
-    } else if (c.opt.final_mfma) {
-        s.ntiles = esa::final_part_tiles(K, c.cfg.cin, height, width);
-        s.heat = ((size_t)n * K * height * width * 4 + 255) & ~(size_t)255;
-    } else {
-        s.ntiles = esa::final_kp_tiles(K, c.cfg.cin, height, width);
-    }
-    s.part = ((size_t)n * K * s.ntiles * 8 + 255) & ~(size_t)255;
+    s.ntiles = c.cfg.variant == 1 ? esa::to_nchw_part_tiles(height, width)
+             : c.opt.final_mfma ? esa::final_part_tiles(K, c.cfg.cin, height, width)
+                                : esa::final_kp_tiles(K, c.cfg.cin, height, width);
+    s.part = pad((size_t)planes * s.ntiles * 8);
     return s;
+}
+
+// The decode step of a forward with a request: decoder x source of the maps.  The sources: fp == nullptr, seg_hrnet3's NHWC
+// maps (`maps`, in format `fmt` with Cp channels per pixel); otherwise the output layer with the parameters *fp, the VALU
+// kernel (it decodes behind its own tiles: no heat-maps at all) or the matrix-core one (heat-maps into the scratch, then the
+// stand-alone decoder's kernels on them).  Returns what the failing launch returned, or 0.
+static int run_decode(const esahrnet_ctx& c, const Buffers& b, const esa::FinalParams* fp, const char* maps, int fmt, int Cp, int n,
+                      int height, int width, hipStream_t stream) {
+    const Request& r = b.req;
+    const int K = c.cfg.num_keypoints;
+    const bool final2 = r.decoder == DEC_FINAL2, gaussfit = r.decoder == DEC_GAUSSFIT;
+    esa::FinalParams p = fp ? *fp : esa::FinalParams{};
+    if (fp && !c.final_wpk) {
+        p.out = nullptr;
+        p.part = b.kpart;
+        return final2 ? esa::launch_final2_kp(p, b.kbmax, r.kp, r.idx, stream, r.hess)
+             : gaussfit ? esa::launch_final_gf_cov(p, r.kp, r.idx, r.fit, r.status, r.hess, r.cov, r.info, r.cov_floor, stream)
+             : esa::launch_final_kp(p, r.kp, r.idx, stream);
+    }
+    int rc = 0;
+    if (fp) {
+        p.out = b.kheat;
+        p.part = final2 ? nullptr : b.kpart;        // get_final2 takes its own tile maxima
+        rc = esa::launch_final(p, stream);
+        if (rc) return rc;
+    }
+    if (final2)
+        return fp ? esa::launch_keypoints_final2(p.out, n * K, height, width, r.kp, r.idx, b.kpart, b.kws, stream, r.hess)
+                  : esa::launch_keypoints_final2_nhwc(fmt, maps, n, K, height, width, Cp, r.kp, r.idx, b.kpart, b.kws, stream, r.hess);
+    // get_final, and the Gaussian fit behind it: tile maxima, then the finish.  The fit reads the arg-max index: without idx it
+    // passes through status
+    int* const idx = gaussfit && !r.idx ? r.status : r.idx;
+    if (fp)
+        rc = esa::launch_keypoints_finish(p.out, p.part, esa::final_part_tiles(p.K, p.cin, height, width), n * K, height, width,
+                                          r.kp, idx, stream);
+    else {
+        rc = esa::launch_tile_max(fmt, maps, n, K, height, width, Cp, b.kpart, stream);
+        if (!rc)
+            rc = esa::launch_keypoints_finish_nhwc(fmt, maps, n, K, height, width, Cp, b.kpart,
+                                                   esa::to_nchw_part_tiles(height, width), r.kp, idx, stream);
+    }
+    if (rc || !gaussfit) return rc;
+    return fp ? esa::launch_gaussfit_fit_cov(p.out, idx, n * K, height, width, r.kp, r.fit, r.status, r.hess, r.cov, r.info,
+                                             r.cov_floor, stream)
+              : esa::launch_gaussfit_fit_nhwc_cov(fmt, maps, n, K, height, width, Cp, idx, r.kp, r.fit, r.status, r.hess, r.cov,
+                                                  r.info, r.cov_floor, stream);
 }
 
 // Op `o` at the shape `sp` decided: every dispatch decision is made here, once, and the launch parameters are built once.
@@ -1813,26 +1876,9 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
             const bool f32 = c.tensors[o.in].f32;       // (bf16 mode: the output layer's f32 heat-maps)
             const int fmt = f32 ? esa::FMT_F32 : c.opt.fmt;
             if (desc) plain(f32 ? "f32_to_nchw" : "sb_to_nchw");
-            else if (b.kp && b.gaussfit) {              // esahrnet_forward_keypoints_gaussfit: maxima, refine and fit on the NHWC maps
-                const int K = c.cfg.num_keypoints, Cp = c.tensors[o.in].Cp;
-                int* const idx = b.idx ? b.idx : b.status;
-                rc = esa::launch_tile_max(fmt, T(o.in), n, K, height, width, Cp, b.kpart, stream);
-                if (!rc)
-                    rc = esa::launch_keypoints_finish_nhwc(fmt, T(o.in), n, K, height, width, Cp, b.kpart,
-                                                           esa::to_nchw_part_tiles(height, width), b.kp, idx, stream);
-                if (!rc)
-                    rc = esa::launch_gaussfit_fit_nhwc_cov(fmt, T(o.in), n, K, height, width, Cp, idx, b.kp, b.fit, b.status, b.hess,
-                                                           b.cov, b.info, b.cov_floor, stream);
-            } else if (b.kp && b.final2)                // esahrnet_forward_keypoints_final2: get_final2 on the NHWC maps
-                rc = esa::launch_keypoints_final2_nhwc(fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
-                                                       b.kp, b.idx, b.kpart, b.kws, stream, b.hess);
-            else if (b.kp) {                            // esahrnet_forward_keypoints: maxima and refine on the NHWC maps
-                const int K = c.cfg.num_keypoints, Cp = c.tensors[o.in].Cp;
-                rc = esa::launch_tile_max(fmt, T(o.in), n, K, height, width, Cp, b.kpart, stream);
-                if (!rc)
-                    rc = esa::launch_keypoints_finish_nhwc(fmt, T(o.in), n, K, height, width, Cp, b.kpart,
-                                                           esa::to_nchw_part_tiles(height, width), b.kp, b.idx, stream);
-            } else if (b.part)                            // esahrnet_forward_partials: the same maps plus each tile's maximum
+            else if (b.req.decoder != DEC_NONE)         // keypoints instead of heat-maps: the decoder on the NHWC maps
+                rc = run_decode(c, b, nullptr, T(o.in), fmt, c.tensors[o.in].Cp, n, height, width, stream);
+            else if (b.part)                              // esahrnet_forward_partials: the same maps plus each tile's maximum
                 rc = esa::launch_to_nchw_part(fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
                                               static_cast<float*>(b.heat), static_cast<float2*>(b.part), stream);
             else rc = esa::launch_fmt_to_nchw(fmt, T(o.in), n, c.cfg.num_keypoints, height, width, c.tensors[o.in].Cp,
@@ -2063,43 +2109,9 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 describe(desc, c.hf() ? "final_kernel<fp16>" : "final_kernel", "%s", s.name.c_str());
                 desc->flops = 2.0 * n * height * width * s.cout * s.cin * 9;
                 desc->bytes = tbytes(o.in) + (double)n * height * width * (c.cfg.cin + s.cout) * 4;
-            } else if (b.kp && b.gaussfit && !c.final_wpk) { // esahrnet_forward_keypoints_gaussfit, VALU: no heat-maps at all
-                p.out = nullptr;
-                p.part = b.kpart;
-                rc = esa::launch_final_gf_cov(p, b.kp, b.idx, b.fit, b.status, b.hess, b.cov, b.info, b.cov_floor, stream);
-            } else if (b.kp && b.gaussfit) {            // ... matrix-core: heat-maps and maxima into the scratch, then the fit on them
-                int* const idx = b.idx ? b.idx : b.status;
-                p.out = b.kheat;
-                p.part = b.kpart;
-                rc = esa::launch_final(p, stream);
-                if (!rc)
-                    rc = esa::launch_keypoints_finish(p.out, p.part, esa::final_part_tiles(p.K, p.cin, height, width), n * p.K,
-                                                      height, width, b.kp, idx, stream);
-                if (!rc)
-                    rc = esa::launch_gaussfit_fit_cov(p.out, idx, n * p.K, height, width, b.kp, b.fit, b.status, b.hess, b.cov, b.info,
-                                                      b.cov_floor, stream);
-            } else if (b.kp && b.final2 && !c.final_wpk) {   // esahrnet_forward_keypoints_final2, VALU: the blurring output layer
-                p.out = nullptr;
-                p.part = b.kpart;
-                rc = esa::launch_final2_kp(p, b.kbmax, b.kp, b.idx, stream, b.hess);
-            } else if (b.kp && b.final2) {              // ... matrix-core: heat-maps into the scratch, then get_final2 on them
-                p.out = b.kheat;
-                p.part = nullptr;
-                rc = esa::launch_final(p, stream);
-                if (!rc)
-                    rc = esa::launch_keypoints_final2(p.out, n * p.K, height, width, b.kp, b.idx, b.kpart, b.kws, stream, b.hess);
-            } else if (b.kp && !c.final_wpk) {         // esahrnet_forward_keypoints, VALU output layer: no heat-maps at all
-                p.out = nullptr;
-                p.part = b.kpart;
-                rc = esa::launch_final_kp(p, b.kp, b.idx, stream);
-            } else if (b.kp) {                          // ... matrix-core output layer: heat-maps and maxima into the scratch
-                p.out = b.kheat;
-                p.part = b.kpart;
-                rc = esa::launch_final(p, stream);
-                if (!rc)
-                    rc = esa::launch_keypoints_finish(p.out, p.part, esa::final_part_tiles(p.K, p.cin, height, width), n * p.K,
-                                                      height, width, b.kp, b.idx, stream);
-            } else rc = esa::launch_final(p, stream);
+            } else if (b.req.decoder != DEC_NONE)       // keypoints instead of heat-maps: the decoder in or behind the output layer
+                rc = run_decode(c, b, &p, nullptr, 0, 0, n, height, width, stream);
+            else rc = esa::launch_final(p, stream);
             break;
         }
     }
@@ -2107,37 +2119,26 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
     return 0;
 }
 
-// kp_dev != nullptr: esahrnet_forward_keypoints, or with final2 esahrnet_forward_keypoints_final2, or with status_dev
-// esahrnet_forward_keypoints_gaussfit (heat_dev and part_dev unused)
-static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, int width,
-                       void* heat_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream_,
-                       hipEvent_t* events, void* part_dev = nullptr, void* kp_dev = nullptr, void* idx_dev = nullptr,
-                       bool final2 = false, void* hess_dev = nullptr, void* fit_dev = nullptr, void* status_dev = nullptr,
-                       void* cov_dev = nullptr, void* info_dev = nullptr, double cov_floor = 0.0) {
-    if (!h || !x_dev || !(heat_dev || kp_dev) || !ws_dev) return fail("forward: null argument");
+// req == nullptr: heat-maps into heat_dev (and, with part_dev, their per-tile maxima).  Otherwise the decoder of *req runs in
+// place of the last launch and nothing but its outputs reaches caller memory (heat_dev and part_dev unused, req->kp never null)
+static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* heat_dev, void* part_dev,
+                       void* ws_dev, size_t ws_bytes, esahrnet_stream stream_, hipEvent_t* events, const Request* req) {
+    if (!h || !x_dev || !(heat_dev || req) || !ws_dev) return fail("forward: null argument");
     if (!h->committed) return fail("forward: esahrnet_commit has not been called");
     if (plan_shape(*h, n, height, width)) return 1;
-    const KpScratch ks = kp_dev ? kp_scratch(*h, n, height, width, final2) : KpScratch{};
-    const size_t need = h->sp.bytes + ks.heat + ks.part + ks.bmax;
+    const KpScratch ks = kp_scratch(*h, n, height, width, req ? req->decoder : DEC_NONE);
+    const size_t need = h->sp.bytes + ks.total();
     if (ws_bytes < need) return fail("forward: workspace too small (%zu < %zu)", ws_bytes, need);
     if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("forward: workspace must be 256-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Buffers bufs{x_dev, heat_dev, static_cast<char*>(ws_dev), part_dev};
-    if (kp_dev) {
-        bufs.kp = static_cast<float*>(kp_dev);
-        bufs.idx = static_cast<int*>(idx_dev);
-        bufs.kheat = reinterpret_cast<float*>(bufs.ws + h->sp.bytes);
-        bufs.kpart = reinterpret_cast<float2*>(bufs.ws + h->sp.bytes + ks.heat);
-        bufs.final2 = final2;
-        bufs.kbmax = reinterpret_cast<float*>(bufs.ws + h->sp.bytes + ks.heat + ks.part);
+    if (req) {
+        char* const scratch = bufs.ws + h->sp.bytes;
+        bufs.req = *req;
+        bufs.kheat = reinterpret_cast<float*>(scratch);
+        bufs.kpart = reinterpret_cast<float2*>(scratch + ks.part_off());
+        bufs.kbmax = reinterpret_cast<float*>(scratch + ks.bmax_off());
         bufs.kws = ks.part;
-        bufs.gaussfit = status_dev != nullptr;
-        bufs.fit = static_cast<double*>(fit_dev);
-        bufs.status = static_cast<int*>(status_dev);
-        bufs.hess = final2 || status_dev ? static_cast<double*>(hess_dev) : nullptr;
-        bufs.cov = status_dev ? static_cast<double*>(cov_dev) : nullptr;
-        bufs.info = status_dev ? static_cast<double*>(info_dev) : nullptr;
-        bufs.cov_floor = cov_floor;
     }
     int op_index = 0;
     if (events && hipEventRecord(events[0], stream) != hipSuccess) return fail("forward: hipEventRecord failed");
@@ -2180,7 +2181,7 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
 
 int esahrnet_forward(esahrnet_handle h, const void* x_dev, int n, int height, int width,
                      void* heat_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
-    return run_forward(h, x_dev, n, height, width, heat_dev, ws_dev, ws_bytes, stream, nullptr);
+    return run_forward(h, x_dev, n, height, width, heat_dev, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr);
 }
 
 int esahrnet_forward_timed(esahrnet_handle h, const void* x_dev, int n, int height, int width,
@@ -2200,7 +2201,7 @@ int esahrnet_forward_timed(esahrnet_handle h, const void* x_dev, int n, int heig
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!rc && (hipEventRecord(nul[0], st) != hipSuccess || hipEventRecord(nul[1], st) != hipSuccess))
         rc = fail("forward_timed: hipEventRecord failed");
-    if (!rc) rc = run_forward(h, x_dev, n, height, width, heat_dev, ws_dev, ws_bytes, stream, ev.data());
+    if (!rc) rc = run_forward(h, x_dev, n, height, width, heat_dev, nullptr, ws_dev, ws_bytes, stream, ev.data(), nullptr);
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("forward_timed: stream sync failed");
     float null_ms = 0.f;
     if (!rc && hipEventElapsedTime(&null_ms, nul[0], nul[1]) != hipSuccess) rc = fail("forward_timed: hipEventElapsedTime failed");
@@ -2240,325 +2241,209 @@ int esahrnet_forward_partials(esahrnet_handle h, const void* x_dev, int n, int h
         if (esahrnet_partial_tiles(h, height, width, &nt)) return 1;
         if (nt <= 0) return fail("forward_partials: this handle's output layer does not report per-tile maxima (esahrnet_partial_tiles = 0)");
     }
-    return run_forward(h, x_dev, n, height, width, heat_dev, ws_dev, ws_bytes, stream, nullptr, part_dev);
+    return run_forward(h, x_dev, n, height, width, heat_dev, part_dev, ws_dev, ws_bytes, stream, nullptr, nullptr);
+}
+
+// ---- the workspace of a forward: the plan's tensors, then the decoder's scratch ----------------------------------------
+static int forward_workspace_bytes(const char* who, esahrnet_handle h, int n, int height, int width, Decoder d, size_t* bytes) {
+    if (!h || !bytes) return fail("%s: null argument", who);
+    if (plan_shape(*h, n, height, width)) return 1;
+    *bytes = h->sp.bytes + kp_scratch(*h, n, height, width, d).total();
+    return 0;
+}
+
+int esahrnet_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
+    return forward_workspace_bytes("workspace_bytes", h, n, height, width, DEC_NONE, bytes);
 }
 
 int esahrnet_keypoints_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
-    if (!h || !bytes) return fail("keypoints_workspace_bytes: null argument");
-    if (plan_shape(*h, n, height, width)) return 1;
-    const KpScratch ks = kp_scratch(*h, n, height, width);
-    *bytes = h->sp.bytes + ks.heat + ks.part;
-    return 0;
+    return forward_workspace_bytes("keypoints_workspace_bytes", h, n, height, width, DEC_FINAL, bytes);
+}
+
+int esahrnet_keypoints_final2_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
+    return forward_workspace_bytes("keypoints_final2_forward_workspace_bytes", h, n, height, width, DEC_FINAL2, bytes);
+}
+
+int esahrnet_keypoints_gaussfit_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
+    return forward_workspace_bytes("keypoints_gaussfit_forward_workspace_bytes", h, n, height, width, DEC_GAUSSFIT, bytes);
+}
+
+// ---- the forward straight to keypoints ----------------------------------------------------------------------------------
+static int forward_request(const char* who, esahrnet_handle h, const void* x_dev, int n, int height, int width, const Request& r,
+                           void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
+    if (!h || !r.kp) return fail("%s: null argument", who);
+    return run_forward(h, x_dev, n, height, width, nullptr, nullptr, ws_dev, ws_bytes, stream, nullptr, &r);
 }
 
 int esahrnet_forward_keypoints(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* kp_dev, void* idx_dev,
                                void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
-    if (!h || !kp_dev) return fail("forward_keypoints: null argument");
-    return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev);
-}
-
-int esahrnet_keypoints_final2_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
-    if (!h || !bytes) return fail("keypoints_final2_forward_workspace_bytes: null argument");
-    if (plan_shape(*h, n, height, width)) return 1;
-    const KpScratch ks = kp_scratch(*h, n, height, width, true);
-    *bytes = h->sp.bytes + ks.heat + ks.part + ks.bmax;
-    return 0;
+    return forward_request("forward_keypoints", h, x_dev, n, height, width, make_request(DEC_FINAL, kp_dev, idx_dev), ws_dev,
+                           ws_bytes, stream);
 }
 
 int esahrnet_forward_keypoints_final2(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* kp_dev,
                                       void* idx_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
-    if (!h || !kp_dev) return fail("forward_keypoints_final2: null argument");
-    return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev, true);
+    return forward_request("forward_keypoints_final2", h, x_dev, n, height, width, make_request(DEC_FINAL2, kp_dev, idx_dev), ws_dev,
+                           ws_bytes, stream);
 }
 
 int esahrnet_forward_keypoints_final2_hess(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* kp_dev,
                                            void* idx_dev, void* hess_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
-    if (!h || !kp_dev) return fail("forward_keypoints_final2_hess: null argument");
-    return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev, true,
-                       hess_dev);
-}
-
-int esahrnet_keypoints_gaussfit_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
-    if (!h || !bytes) return fail("keypoints_gaussfit_forward_workspace_bytes: null argument");
-    return esahrnet_keypoints_workspace_bytes(h, n, height, width, bytes);      // the scratch of esahrnet_forward_keypoints
+    return forward_request("forward_keypoints_final2_hess", h, x_dev, n, height, width,
+                           make_request(DEC_FINAL2, kp_dev, idx_dev, hess_dev), ws_dev, ws_bytes, stream);
 }
 
 // what esahrnet_forward_keypoints_gaussfit and the loader in front of it refuse about the decoder's outputs
-static int check_gaussfit_outputs(const char* who, const esahrnet_ctx& c, const void* kp_dev, const void* idx_dev, const void* fit_dev,
-                                  const void* status_dev, const void* hess_dev) {
-    if ((reinterpret_cast<uintptr_t>(kp_dev) | reinterpret_cast<uintptr_t>(idx_dev) | reinterpret_cast<uintptr_t>(status_dev)) & 3)
+static int check_gaussfit_outputs(const char* who, const esahrnet_ctx& c, const Request& r) {
+    if ((reinterpret_cast<uintptr_t>(r.kp) | reinterpret_cast<uintptr_t>(r.idx) | reinterpret_cast<uintptr_t>(r.status)) & 3)
         return fail("%s: kp_dev, idx_dev and status_dev must be 4-byte aligned", who);
-    if ((reinterpret_cast<uintptr_t>(fit_dev) | reinterpret_cast<uintptr_t>(hess_dev)) & 7)
+    if ((reinterpret_cast<uintptr_t>(r.fit) | reinterpret_cast<uintptr_t>(r.hess)) & 7)
         return fail("%s: fit_dev and hess_dev must be 8-byte aligned", who);
     if (c.cfg.variant != 1 && !c.opt.final_mfma && c.cfg.cin > 8)
         return fail("%s: the VALU output layer's fit stages at most 8 input channels (this handle takes %d)", who, c.cfg.cin);
     return 0;
 }
 
+// esahrnet_forward_keypoints_gaussfit and, with_cov, esahrnet_forward_keypoints_gaussfit_cov
+static int forward_gaussfit(const char* who, bool with_cov, esahrnet_handle h, const void* x_dev, int n, int height, int width,
+                            const Request& r, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
+    if (!h || !x_dev || !r.kp || !r.status || !ws_dev) return fail("%s: null argument", who);
+    if (check_gaussfit_outputs(who, *h, r) || (with_cov && esa::check_cov_args(who, r.cov, r.info, r.cov_floor))) return 1;
+    return run_forward(h, x_dev, n, height, width, nullptr, nullptr, ws_dev, ws_bytes, stream, nullptr, &r);
+}
+
 int esahrnet_forward_keypoints_gaussfit(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* kp_dev,
                                         void* idx_dev, void* fit_dev, void* status_dev, void* hess_dev, void* ws_dev,
                                         size_t ws_bytes, esahrnet_stream stream) {
-    if (!h || !x_dev || !kp_dev || !status_dev || !ws_dev) return fail("forward_keypoints_gaussfit: null argument");
-    if (check_gaussfit_outputs("forward_keypoints_gaussfit", *h, kp_dev, idx_dev, fit_dev, status_dev, hess_dev)) return 1;
-    return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev, false,
-                       hess_dev, fit_dev, status_dev);
-}
-
-// what the _cov entries refuse about their three additions
-static int check_cov_args(const char* who, const void* cov_dev, const void* info_dev, double cov_floor) {
-    if ((reinterpret_cast<uintptr_t>(cov_dev) | reinterpret_cast<uintptr_t>(info_dev)) & 7)
-        return fail("%s: cov_dev and info_dev must be 8-byte aligned", who);
-    if (!(cov_floor >= 0.0)) return fail("%s: cov_floor must be a number >= 0 (got %g)", who, cov_floor);
-    return 0;
+    return forward_gaussfit("forward_keypoints_gaussfit", false, h, x_dev, n, height, width,
+                            make_request(DEC_GAUSSFIT, kp_dev, idx_dev, hess_dev, fit_dev, status_dev), ws_dev, ws_bytes, stream);
 }
 
 int esahrnet_forward_keypoints_gaussfit_cov(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* kp_dev,
                                             void* idx_dev, void* fit_dev, void* status_dev, void* hess_dev, void* cov_dev,
                                             void* info_dev, double cov_floor, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
-    if (!h || !x_dev || !kp_dev || !status_dev || !ws_dev) return fail("forward_keypoints_gaussfit_cov: null argument");
-    if (check_gaussfit_outputs("forward_keypoints_gaussfit_cov", *h, kp_dev, idx_dev, fit_dev, status_dev, hess_dev) ||
-        check_cov_args("forward_keypoints_gaussfit_cov", cov_dev, info_dev, cov_floor))
-        return 1;
-    return run_forward(h, x_dev, n, height, width, nullptr, ws_dev, ws_bytes, stream, nullptr, nullptr, kp_dev, idx_dev, false,
-                       hess_dev, fit_dev, status_dev, cov_dev, info_dev, cov_floor);
-}
-
-int esahrnet_keypoints_finish(const void* heat_dev, const void* part_dev, int ntiles, int n, int k, int height, int width,
-                              void* kp_dev, void* idx_dev, esahrnet_stream stream) {
-    if (!heat_dev || !part_dev || !kp_dev || n <= 0 || k <= 0 || ntiles <= 0) return fail("keypoints_finish: bad argument");
-    const int rc = esa::launch_keypoints_finish(static_cast<const float*>(heat_dev), static_cast<const float2*>(part_dev), ntiles,
-                                                n * k, height, width, static_cast<float*>(kp_dev), static_cast<int*>(idx_dev),
-                                                static_cast<hipStream_t>(stream));
-    if (rc) return fail("keypoints_finish: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
-}
-
-int esahrnet_keypoints_ex(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev,
-                          esahrnet_stream stream) {
-    if (!heat_dev || !kp_dev || n <= 0 || k <= 0) return fail("keypoints: bad argument");
-    const int rc = esa::launch_keypoints(static_cast<const float*>(heat_dev), n * k, height, width,
-                                         static_cast<float*>(kp_dev), static_cast<int*>(idx_dev),
-                                         static_cast<hipStream_t>(stream));
-    if (rc) return fail("keypoints: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
-}
-
-int esahrnet_keypoints_final2_workspace_bytes(int n, int k, int height, int width, size_t* bytes) {
-    if (!bytes) return fail("keypoints_final2_workspace_bytes: null argument");
-    if (n <= 0 || k <= 0 || height <= 0 || width <= 0 || (long long)height * width > 0x7fffffffLL)
-        return fail("keypoints_final2_workspace_bytes: bad shape %d x %d x %d x %d", n, k, height, width);
-    *bytes = esa::final2_workspace_bytes((long long)n * k, height, width);
-    return 0;
-}
-
-int esahrnet_keypoints_final2(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev, void* ws_dev,
-                              size_t ws_bytes, esahrnet_stream stream) {
-    return esahrnet_keypoints_final2_hess(heat_dev, n, k, height, width, kp_dev, idx_dev, nullptr, ws_dev, ws_bytes, stream);
-}
-
-int esahrnet_keypoints_final2_hess(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev,
-                                   void* hess_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
-    if (!heat_dev || !kp_dev || !ws_dev) return fail("keypoints_final2: null argument");
-    size_t need = 0;
-    if (esahrnet_keypoints_final2_workspace_bytes(n, k, height, width, &need)) return 1;
-    if ((long long)n * k * esa::final2_tiles(height, width) > 0x7fffffLL)
-        return fail("keypoints_final2: %d x %d planes of %d x %d: too many tiles for one launch", n, k, height, width);
-    if (ws_bytes < need) return fail("keypoints_final2: workspace too small (%zu < %zu)", ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("keypoints_final2: workspace must be 256-byte aligned");
-    const int rc = esa::launch_keypoints_final2(static_cast<const float*>(heat_dev), n * k, height, width, static_cast<float*>(kp_dev),
-                                                static_cast<int*>(idx_dev), ws_dev, ws_bytes, static_cast<hipStream_t>(stream),
-                                                static_cast<double*>(hess_dev));
-    if (rc) return fail("keypoints_final2: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
-}
-
-int esahrnet_keypoints_gaussfit(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev,
-                                void* fit_dev, void* status_dev, void* hess_dev, esahrnet_stream stream) {
-    if (!heat_dev || !kp_dev || !status_dev) return fail("keypoints_gaussfit: null argument");
-    if (n <= 0 || k <= 0 || height <= 0 || width <= 0 || (long long)height * width > 0x7fffffffLL ||
-        (long long)n * k > 0x7fffffffLL)
-        return fail("keypoints_gaussfit: bad shape %d x %d x %d x %d", n, k, height, width);
-    if ((reinterpret_cast<uintptr_t>(heat_dev) | reinterpret_cast<uintptr_t>(kp_dev) | reinterpret_cast<uintptr_t>(idx_dev) |
-         reinterpret_cast<uintptr_t>(status_dev)) & 3)
-        return fail("keypoints_gaussfit: heat_dev, kp_dev, idx_dev and status_dev must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(fit_dev) | reinterpret_cast<uintptr_t>(hess_dev)) & 7)
-        return fail("keypoints_gaussfit: fit_dev and hess_dev must be 8-byte aligned");
-    const int rc = esa::launch_keypoints_gaussfit(static_cast<const float*>(heat_dev), n * k, height, width,
-                                                  static_cast<float*>(kp_dev), static_cast<int*>(idx_dev),
-                                                  static_cast<double*>(fit_dev), static_cast<int*>(status_dev),
-                                                  static_cast<double*>(hess_dev), static_cast<hipStream_t>(stream));
-    if (rc) return fail("keypoints_gaussfit: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
-}
-
-int esahrnet_keypoints_gaussfit_cov(const void* heat_dev, int n, int k, int height, int width, void* kp_dev, void* idx_dev,
-                                    void* fit_dev, void* status_dev, void* hess_dev, void* cov_dev, void* info_dev, double cov_floor,
-                                    esahrnet_stream stream) {
-    if (!heat_dev || !kp_dev || !status_dev) return fail("keypoints_gaussfit_cov: null argument");
-    if (n <= 0 || k <= 0 || height <= 0 || width <= 0 || (long long)height * width > 0x7fffffffLL ||
-        (long long)n * k > 0x7fffffffLL)
-        return fail("keypoints_gaussfit_cov: bad shape %d x %d x %d x %d", n, k, height, width);
-    if ((reinterpret_cast<uintptr_t>(heat_dev) | reinterpret_cast<uintptr_t>(kp_dev) | reinterpret_cast<uintptr_t>(idx_dev) |
-         reinterpret_cast<uintptr_t>(status_dev)) & 3)
-        return fail("keypoints_gaussfit_cov: heat_dev, kp_dev, idx_dev and status_dev must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(fit_dev) | reinterpret_cast<uintptr_t>(hess_dev)) & 7)
-        return fail("keypoints_gaussfit_cov: fit_dev and hess_dev must be 8-byte aligned");
-    if (check_cov_args("keypoints_gaussfit_cov", cov_dev, info_dev, cov_floor)) return 1;
-    const int rc = esa::launch_keypoints_gaussfit_cov(static_cast<const float*>(heat_dev), n * k, height, width,
-                                                      static_cast<float*>(kp_dev), static_cast<int*>(idx_dev),
-                                                      static_cast<double*>(fit_dev), static_cast<int*>(status_dev),
-                                                      static_cast<double*>(hess_dev), static_cast<double*>(cov_dev),
-                                                      static_cast<double*>(info_dev), cov_floor, static_cast<hipStream_t>(stream));
-    if (rc) return fail("keypoints_gaussfit_cov: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
-}
-
-int esahrnet_keypoints(const void* heat_dev, int n, int k, int height, int width, void* kp_dev,
-                       esahrnet_stream stream) {
-    return esahrnet_keypoints_ex(heat_dev, n, k, height, width, kp_dev, nullptr, stream);
-}
-
-int esahrnet_crops(const void* frames_dev, int n, int frame_h, int frame_w, const void* boxes_dev, int scale,
-                   float mean, float stdv, void* out_dev, esahrnet_stream stream) {
-    if (!frames_dev || !boxes_dev || !out_dev || n <= 0 || scale <= 0 || !(stdv > 0.f)) return fail("crops: bad argument");
-    const int rc = esa::launch_crops(static_cast<const unsigned char*>(frames_dev), static_cast<const int*>(boxes_dev),
-                                     static_cast<float*>(out_dev), n, frame_h, frame_w, scale, mean, stdv,
-                                     static_cast<hipStream_t>(stream));
-    if (rc) return fail("crops: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
+    return forward_gaussfit("forward_keypoints_gaussfit_cov", true, h, x_dev, n, height, width,
+                            make_request(DEC_GAUSSFIT, kp_dev, idx_dev, hess_dev, fit_dev, status_dev, cov_dev, info_dev, cov_floor),
+                            ws_dev, ws_bytes, stream);
 }
 
 // ---- the loader on the device: detector boxes + frames -> crops -> keypoints (frontend.hip) ----------------------------
-static const int kFrontendMaxRows = 0xffffff;       // launch_crops_ex: one block per output row, m * scale of them
-
-static int check_boxes_args(const char* who, int m, int frame_h, int frame_w, int scale, int rule) {
-    if (m <= 0) return fail("%s: the number of boxes must be positive (got %d)", who, m);
-    if (frame_h <= 0 || frame_w <= 0) return fail("%s: bad frame size %d x %d", who, frame_h, frame_w);
-    if (scale <= 0 || (long long)m * scale > kFrontendMaxRows)
-        return fail("%s: scale %d with %d boxes (scale positive, boxes * scale at most %d)", who, scale, m, kFrontendMaxRows);
-    if (rule != 0 && rule != 1) return fail("%s: rule=%d unknown (0: val, data_load_val.py; 1: train / demo, data_load4.py)", who, rule);
-    return 0;
-}
-
-static int check_crops_args(const char* who, int nframes, int pixel_format, float stdv) {
-    if (nframes <= 0) return fail("%s: the number of frames must be positive (got %d)", who, nframes);
-    if (pixel_format != 0 && pixel_format != 1) return fail("%s: pixel_format=%d unknown (0: gray8, 1: RGB8 interleaved)", who, pixel_format);
-    if (!(stdv > 0.f)) return fail("%s: stdv must be positive", who);
-    return 0;
-}
-
-int esahrnet_boxes(const void* det_boxes_dev, int m, int frame_h, int frame_w, int scale, int rule, void* crop_boxes_dev,
-                   void* rates_dev, void* valid_dev, esahrnet_stream stream) {
-    if (!det_boxes_dev || !crop_boxes_dev || !rates_dev || !valid_dev) return fail("boxes: null argument");
-    if (check_boxes_args("boxes", m, frame_h, frame_w, scale, rule)) return 1;
-    const int rc = esa::launch_boxes(static_cast<const int*>(det_boxes_dev), nullptr, 0, m, frame_h, frame_w, scale, rule,
-                                     static_cast<int*>(crop_boxes_dev), static_cast<double*>(rates_dev),
-                                     static_cast<int*>(valid_dev), static_cast<hipStream_t>(stream));
-    if (rc) return fail("boxes: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
-}
-
-int esahrnet_crops_ex(const void* frames_dev, int nframes, int frame_h, int frame_w, int pixel_format, const void* frame_idx_dev,
-                      const void* crop_boxes_dev, const void* valid_dev, int m, int scale, float mean, float stdv, void* out_dev,
-                      esahrnet_stream stream) {
-    if (!frames_dev || !crop_boxes_dev || !out_dev) return fail("crops_ex: null argument");
-    if (check_boxes_args("crops_ex", m, frame_h, frame_w, scale, 0) || check_crops_args("crops_ex", nframes, pixel_format, stdv)) return 1;
-    if (!frame_idx_dev && m != nframes)
-        return fail("crops_ex: %d crops of %d frames need a frame index (NULL is the identity: crop i reads frame i)", m, nframes);
-    const int rc = esa::launch_crops_ex(static_cast<const unsigned char*>(frames_dev), nframes, frame_h, frame_w, pixel_format,
-                                        static_cast<const int*>(frame_idx_dev), static_cast<const int*>(crop_boxes_dev),
-                                        static_cast<const int*>(valid_dev), static_cast<float*>(out_dev), m, scale, mean, stdv,
-                                        static_cast<hipStream_t>(stream));
-    if (rc) return fail("crops_ex: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
-}
+// what the loader entries take besides the handle and the decoder's outputs
+struct FramesArgs {
+    const void* frames;
+    int nframes, frame_h, frame_w, pixel_format;
+    const void* det_boxes;
+    const void* frame_idx;
+    int m, scale, rule;
+    float mean, stdv;
+    void *crop_boxes, *rates, *valid;
+    void* ws;
+    size_t ws_bytes;
+    esahrnet_stream stream;
+};
 
 static size_t frontend_crop_bytes(int m, int scale) { return ((size_t)m * scale * scale * sizeof(float) + 255) & ~(size_t)255; }
 
-int esahrnet_frames_keypoints_workspace_bytes(esahrnet_handle h, int m, int scale, int decoder, size_t* bytes) {
-    if (!h || !bytes) return fail("frames_keypoints_workspace_bytes: null argument");
-    if (decoder != 0 && decoder != 1) return fail("frames_keypoints: decoder=%d unknown (0: get_final, 1: get_final2)", decoder);
+// the loader's workspace: its crops, then the workspace of the forward with decoder `d` on them
+static int frames_workspace_bytes(const char* who, esahrnet_handle h, int m, int scale, Decoder d, size_t* bytes) {
     if (h->cfg.cin != 1)
-        return fail("frames_keypoints: the loader makes 1-channel crops (data_load_val.py / data_load4.py); this handle takes %d channels",
+        return fail("%s: the loader makes 1-channel crops (data_load_val.py / data_load4.py); this handle takes %d channels", who,
                     h->cfg.cin);
-    if (m <= 0 || scale <= 0 || (long long)m * scale > kFrontendMaxRows)
-        return fail("frames_keypoints: scale %d with %d boxes (both positive, boxes * scale at most %d)", scale, m, kFrontendMaxRows);
+    if (m <= 0 || scale <= 0 || (long long)m * scale > esa::kFrontendMaxRows)
+        return fail("%s: scale %d with %d boxes (both positive, boxes * scale at most %d)", who, scale, m, esa::kFrontendMaxRows);
     size_t fw = 0;
-    if (decoder ? esahrnet_keypoints_final2_forward_workspace_bytes(h, m, scale, scale, &fw)
-                : esahrnet_keypoints_workspace_bytes(h, m, scale, scale, &fw))
-        return 1;
+    if (forward_workspace_bytes(who, h, m, scale, scale, d, &fw)) return 1;
     *bytes = frontend_crop_bytes(m, scale) + fw;
     return 0;
 }
 
-// esahrnet_frames_keypoints / esahrnet_frames_correspondences after their argument checks (`who` names the caller in the
-// messages): boxes -> crops -> forward + decoder -> NaN rows for invalid crops.  hess_dev: decoder 1 only, may be null.
-// decoder 2 (esahrnet_frames_keypoints_gaussfit only): the Gaussian fit, with fit_dev / hess_dev (may be null) and status_dev.
-static int frames_run(const char* who, esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
-                      int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale, int rule, float mean,
-                      float stdv, int decoder, void* kp_dev, void* idx_dev, void* hess_dev, void* crop_boxes_dev, void* rates_dev,
-                      void* valid_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream, void* fit_dev = nullptr,
-                      void* status_dev = nullptr, void* cov_dev = nullptr, void* info_dev = nullptr, double cov_floor = 0.0) {
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc = esa::launch_boxes(static_cast<const int*>(det_boxes_dev), static_cast<const int*>(frame_idx_dev), nframes, m, frame_h,
-                               frame_w, scale, rule, static_cast<int*>(crop_boxes_dev), static_cast<double*>(rates_dev),
-                               static_cast<int*>(valid_dev), st);
-    if (!rc)
-        rc = esa::launch_crops_ex(static_cast<const unsigned char*>(frames_dev), nframes, frame_h, frame_w, pixel_format,
-                                  static_cast<const int*>(frame_idx_dev), static_cast<const int*>(crop_boxes_dev),
-                                  static_cast<const int*>(valid_dev), static_cast<float*>(ws_dev), m, scale, mean, stdv, st);
-    if (rc) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)rc));
-    const size_t head = frontend_crop_bytes(m, scale);
-    if (run_forward(h, ws_dev, m, scale, scale, nullptr, static_cast<char*>(ws_dev) + head, ws_bytes - head, stream, nullptr, nullptr,
-                    kp_dev, idx_dev, decoder == 1, hess_dev, fit_dev, decoder == 2 ? status_dev : nullptr, cov_dev, info_dev, cov_floor))
+int esahrnet_frames_keypoints_workspace_bytes(esahrnet_handle h, int m, int scale, int decoder, size_t* bytes) {
+    if (!h || !bytes) return fail("frames_keypoints_workspace_bytes: null argument");
+    if (decoder != 0 && decoder != 1) return fail("frames_keypoints: decoder=%d unknown (0: get_final, 1: get_final2)", decoder);
+    return frames_workspace_bytes("frames_keypoints", h, m, scale, decoder ? DEC_FINAL2 : DEC_FINAL, bytes);
+}
+
+int esahrnet_frames_keypoints_gaussfit_workspace_bytes(esahrnet_handle h, int m, int scale, size_t* bytes) {
+    if (!h || !bytes) return fail("frames_keypoints_gaussfit_workspace_bytes: null argument");
+    return frames_workspace_bytes("frames_keypoints_gaussfit", h, m, scale, DEC_GAUSSFIT, bytes);
+}
+
+// what every loader entry refuses about the frames and the boxes
+static int check_frames_args(const char* who, const FramesArgs& a) {
+    if (esa::check_boxes_args(who, a.m, a.frame_h, a.frame_w, a.scale, a.rule) ||
+        esa::check_crops_args(who, a.nframes, a.pixel_format, a.stdv))
         return 1;
-    if (decoder == 2)
-        rc = esa::launch_mark_invalid_gaussfit_cov(static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints,
-                                                   static_cast<float*>(kp_dev), static_cast<int*>(idx_dev),
-                                                   static_cast<double*>(fit_dev), static_cast<int*>(status_dev),
-                                                   static_cast<double*>(hess_dev), static_cast<double*>(cov_dev),
-                                                   static_cast<double*>(info_dev), st);
-    else
-        rc = esa::launch_mark_invalid(static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints, static_cast<float*>(kp_dev),
-                                      static_cast<int*>(idx_dev), st);
+    if (!a.frame_idx && a.m != a.nframes)
+        return fail("%s: %d boxes on %d frames need a frame index (NULL is the identity: box i lies on frame i)", who, a.m, a.nframes);
+    return 0;
+}
+
+// The loader entries after their argument checks (`who` names the caller in the messages): boxes -> crops at the head of the
+// workspace -> forward + the decoder of `r` -> NaN rows for invalid crops.
+static int frames_run(const char* who, esahrnet_handle h, const FramesArgs& a, const Request& r) {
+    const hipStream_t st = static_cast<hipStream_t>(a.stream);
+    const int* const frame_idx = static_cast<const int*>(a.frame_idx);
+    int* const crop_boxes = static_cast<int*>(a.crop_boxes);
+    int* const valid = static_cast<int*>(a.valid);
+    int rc = esa::launch_boxes(static_cast<const int*>(a.det_boxes), frame_idx, a.nframes, a.m, a.frame_h, a.frame_w, a.scale, a.rule,
+                               crop_boxes, static_cast<double*>(a.rates), valid, st);
+    if (!rc)
+        rc = esa::launch_crops_ex(static_cast<const unsigned char*>(a.frames), a.nframes, a.frame_h, a.frame_w, a.pixel_format,
+                                  frame_idx, crop_boxes, valid, static_cast<float*>(a.ws), a.m, a.scale, a.mean, a.stdv, st);
+    if (rc) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+    const size_t head = frontend_crop_bytes(a.m, a.scale);
+    if (run_forward(h, a.ws, a.m, a.scale, a.scale, nullptr, nullptr, static_cast<char*>(a.ws) + head, a.ws_bytes - head, a.stream,
+                    nullptr, &r))
+        return 1;
+    if (r.decoder == DEC_GAUSSFIT)
+        rc = esa::launch_mark_invalid_gaussfit_cov(valid, a.m, h->cfg.num_keypoints, r.kp, r.idx, r.fit, r.status, r.hess, r.cov,
+                                                   r.info, st);
+    else rc = esa::launch_mark_invalid(valid, a.m, h->cfg.num_keypoints, r.kp, r.idx, st);
     if (rc) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)rc));
     return 0;
+}
+
+// The three esahrnet_frames_keypoints* entries: everything that can be refused is refused here, before the first launch.
+// abi_decoder: the `decoder` argument of esahrnet_frames_keypoints as given (refused by its workspace query when unknown);
+// unused by the Gaussian-fit entries.  Each entry keeps the order of its refusals: the _cov form checks its three additions
+// before the handle's commit.
+static int frames_keypoints(const char* who, bool with_cov, esahrnet_handle h, const FramesArgs& a, int abi_decoder,
+                            const Request& r) {
+    const bool gaussfit = r.decoder == DEC_GAUSSFIT;
+    if (!h || !a.frames || !a.det_boxes || !r.kp || (gaussfit && !r.status) || !a.crop_boxes || !a.rates || !a.valid || !a.ws)
+        return fail("%s: null argument", who);
+    if (check_frames_args(who, a)) return 1;
+    if (with_cov && esa::check_cov_args(who, r.cov, r.info, r.cov_floor)) return 1;
+    if (!h->committed) return fail("%s: esahrnet_commit has not been called", who);
+    if (gaussfit && check_gaussfit_outputs(who, *h, r)) return 1;
+    size_t need = 0;
+    if (gaussfit ? esahrnet_frames_keypoints_gaussfit_workspace_bytes(h, a.m, a.scale, &need)
+                 : esahrnet_frames_keypoints_workspace_bytes(h, a.m, a.scale, abi_decoder, &need))
+        return 1;
+    if (a.ws_bytes < need) return fail("%s: workspace too small (%zu < %zu)", who, a.ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(a.ws) & 255) return fail("%s: workspace must be 256-byte aligned", who);
+    return frames_run(who, h, a, r);
 }
 
 int esahrnet_frames_keypoints(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w, int pixel_format,
                               const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale, int rule, float mean,
                               float stdv, int decoder, void* kp_dev, void* idx_dev, void* crop_boxes_dev, void* rates_dev,
                               void* valid_dev, void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
-    if (!h || !frames_dev || !det_boxes_dev || !kp_dev || !crop_boxes_dev || !rates_dev || !valid_dev || !ws_dev)
-        return fail("frames_keypoints: null argument");
-    // everything that can be refused is refused here, before the first launch
-    if (check_boxes_args("frames_keypoints", m, frame_h, frame_w, scale, rule) ||
-        check_crops_args("frames_keypoints", nframes, pixel_format, stdv))
-        return 1;
-    if (!frame_idx_dev && m != nframes)
-        return fail("frames_keypoints: %d boxes on %d frames need a frame index (NULL is the identity: box i lies on frame i)", m, nframes);
-    if (!h->committed) return fail("frames_keypoints: esahrnet_commit has not been called");
-    size_t need = 0;
-    if (esahrnet_frames_keypoints_workspace_bytes(h, m, scale, decoder, &need)) return 1;
-    if (ws_bytes < need) return fail("frames_keypoints: workspace too small (%zu < %zu)", ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("frames_keypoints: workspace must be 256-byte aligned");
-    return frames_run("frames_keypoints", h, frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m,
-                      scale, rule, mean, stdv, decoder, kp_dev, idx_dev, nullptr, crop_boxes_dev, rates_dev, valid_dev, ws_dev,
-                      ws_bytes, stream);
+    const FramesArgs a{frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m, scale, rule, mean, stdv,
+                       crop_boxes_dev, rates_dev, valid_dev, ws_dev, ws_bytes, stream};
+    return frames_keypoints("frames_keypoints", false, h, a, decoder,
+                            make_request(decoder == 1 ? DEC_FINAL2 : DEC_FINAL, kp_dev, idx_dev));
 }
 
-int esahrnet_frames_keypoints_gaussfit_workspace_bytes(esahrnet_handle h, int m, int scale, size_t* bytes) {
-    if (!h || !bytes) return fail("frames_keypoints_gaussfit_workspace_bytes: null argument");
-    if (h->cfg.cin != 1)
-        return fail("frames_keypoints_gaussfit: the loader makes 1-channel crops (data_load_val.py / data_load4.py); this handle takes %d channels",
-                    h->cfg.cin);
-    if (m <= 0 || scale <= 0 || (long long)m * scale > kFrontendMaxRows)
-        return fail("frames_keypoints_gaussfit: scale %d with %d boxes (both positive, boxes * scale at most %d)", scale, m,
-                    kFrontendMaxRows);
-    size_t fw = 0;
-    if (esahrnet_keypoints_gaussfit_forward_workspace_bytes(h, m, scale, scale, &fw)) return 1;
-    *bytes = frontend_crop_bytes(m, scale) + fw;
-    return 0;
+int esahrnet_frames_keypoints_gaussfit(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                                       int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale,
+                                       int rule, float mean, float stdv, void* kp_dev, void* idx_dev, void* fit_dev, void* status_dev,
+                                       void* hess_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev, void* ws_dev,
+                                       size_t ws_bytes, esahrnet_stream stream) {
+    const FramesArgs a{frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m, scale, rule, mean, stdv,
+                       crop_boxes_dev, rates_dev, valid_dev, ws_dev, ws_bytes, stream};
+    return frames_keypoints("frames_keypoints_gaussfit", false, h, a, 0,
+                            make_request(DEC_GAUSSFIT, kp_dev, idx_dev, hess_dev, fit_dev, status_dev));
 }
 
 int esahrnet_frames_keypoints_gaussfit_cov(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
@@ -2567,79 +2452,18 @@ int esahrnet_frames_keypoints_gaussfit_cov(esahrnet_handle h, const void* frames
                                            void* status_dev, void* hess_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev,
                                            void* cov_dev, void* info_dev, double cov_floor, void* ws_dev, size_t ws_bytes,
                                            esahrnet_stream stream) {
-    const char* who = "frames_keypoints_gaussfit_cov";
-    if (!h || !frames_dev || !det_boxes_dev || !kp_dev || !status_dev || !crop_boxes_dev || !rates_dev || !valid_dev || !ws_dev)
-        return fail("%s: null argument", who);
-    // everything that can be refused is refused here, before the first launch; the order of esahrnet_frames_keypoints_gaussfit
-    if (check_boxes_args(who, m, frame_h, frame_w, scale, rule) || check_crops_args(who, nframes, pixel_format, stdv)) return 1;
-    if (!frame_idx_dev && m != nframes)
-        return fail("%s: %d boxes on %d frames need a frame index (NULL is the identity: box i lies on frame i)", who, m, nframes);
-    if (check_cov_args(who, cov_dev, info_dev, cov_floor)) return 1;
-    if (!h->committed) return fail("%s: esahrnet_commit has not been called", who);
-    if (check_gaussfit_outputs(who, *h, kp_dev, idx_dev, fit_dev, status_dev, hess_dev)) return 1;
-    size_t need = 0;
-    if (esahrnet_frames_keypoints_gaussfit_workspace_bytes(h, m, scale, &need)) return 1;
-    if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("%s: workspace must be 256-byte aligned", who);
-    return frames_run(who, h, frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m, scale, rule,
-                      mean, stdv, 2, kp_dev, idx_dev, hess_dev, crop_boxes_dev, rates_dev, valid_dev, ws_dev, ws_bytes, stream,
-                      fit_dev, status_dev, cov_dev, info_dev, cov_floor);
-}
-
-int esahrnet_frames_keypoints_gaussfit(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
-                                       int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale,
-                                       int rule, float mean, float stdv, void* kp_dev, void* idx_dev, void* fit_dev, void* status_dev,
-                                       void* hess_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev, void* ws_dev,
-                                       size_t ws_bytes, esahrnet_stream stream) {
-    if (!h || !frames_dev || !det_boxes_dev || !kp_dev || !status_dev || !crop_boxes_dev || !rates_dev || !valid_dev || !ws_dev)
-        return fail("frames_keypoints_gaussfit: null argument");
-    // everything that can be refused is refused here, before the first launch
-    if (check_boxes_args("frames_keypoints_gaussfit", m, frame_h, frame_w, scale, rule) ||
-        check_crops_args("frames_keypoints_gaussfit", nframes, pixel_format, stdv))
-        return 1;
-    if (!frame_idx_dev && m != nframes)
-        return fail("frames_keypoints_gaussfit: %d boxes on %d frames need a frame index (NULL is the identity: box i lies on frame i)",
-                    m, nframes);
-    if (!h->committed) return fail("frames_keypoints_gaussfit: esahrnet_commit has not been called");
-    if (check_gaussfit_outputs("frames_keypoints_gaussfit", *h, kp_dev, idx_dev, fit_dev, status_dev, hess_dev)) return 1;
-    size_t need = 0;
-    if (esahrnet_frames_keypoints_gaussfit_workspace_bytes(h, m, scale, &need)) return 1;
-    if (ws_bytes < need) return fail("frames_keypoints_gaussfit: workspace too small (%zu < %zu)", ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("frames_keypoints_gaussfit: workspace must be 256-byte aligned");
-    return frames_run("frames_keypoints_gaussfit", h, frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev,
-                      frame_idx_dev, m, scale, rule, mean, stdv, 2, kp_dev, idx_dev, hess_dev, crop_boxes_dev, rates_dev, valid_dev,
-                      ws_dev, ws_bytes, stream, fit_dev, status_dev);
+    const FramesArgs a{frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m, scale, rule, mean, stdv,
+                       crop_boxes_dev, rates_dev, valid_dev, ws_dev, ws_bytes, stream};
+    return frames_keypoints("frames_keypoints_gaussfit_cov", true, h, a, 0,
+                            make_request(DEC_GAUSSFIT, kp_dev, idx_dev, hess_dev, fit_dev, status_dev, cov_dev, info_dev, cov_floor));
 }
 
 // ---- keypoints -> correspondences for the pose solver (correspond.hip) --------------------------------------------------
-static int check_corr_args(const char* who, int m, int k, int mode) {
-    if (m <= 0) return fail("%s: the number of crops must be positive (got %d)", who, m);
-    if (k < 1 || k > 32) return fail("%s: %d keypoints per crop unsupported (1..32: one wave per crop)", who, k);
-    if (mode != 0 && mode != 1) return fail("%s: mode=%d unknown (0: peak weights, 1: get_final2 Hessian weights)", who, mode);
-    return 0;
-}
-
-int esahrnet_correspondences(const void* kp_dev, const void* hess_dev, const void* crop_boxes_dev, const void* rates_dev,
-                             const void* valid_dev, int m, int k, double thresh, int min_k, int mode, void* count_dev,
-                             void* order_dev, void* pts_dev, void* w_dev, esahrnet_stream stream) {
-    if (!kp_dev || !crop_boxes_dev || !rates_dev || !valid_dev || !count_dev || !order_dev || !pts_dev || !w_dev)
-        return fail("correspondences: null argument");
-    if (check_corr_args("correspondences", m, k, mode)) return 1;
-    if (mode == 1 && !hess_dev) return fail("correspondences: mode 1 (Hessian weights) needs hess_dev (esahrnet_keypoints_final2_hess)");
-    const int rc = esa::launch_correspond(static_cast<const float*>(kp_dev), static_cast<const double*>(hess_dev),
-                                          static_cast<const int*>(crop_boxes_dev), static_cast<const double*>(rates_dev),
-                                          static_cast<const int*>(valid_dev), m, k, thresh, min_k, mode, static_cast<int*>(count_dev),
-                                          static_cast<int*>(order_dev), static_cast<double*>(pts_dev), static_cast<double*>(w_dev),
-                                          static_cast<hipStream_t>(stream));
-    if (rc) return fail("correspondences: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
-}
-
 static size_t frontend_hess_bytes(int m, int k) { return ((size_t)m * k * 3 * sizeof(double) + 255) & ~(size_t)255; }
 
 int esahrnet_frames_correspondences_workspace_bytes(esahrnet_handle h, int m, int scale, int decoder, int mode, size_t* bytes) {
     if (!h || !bytes) return fail("frames_correspondences_workspace_bytes: null argument");
-    if (check_corr_args("frames_correspondences", m, h->cfg.num_keypoints, mode)) return 1;
+    if (esa::check_corr_args("frames_correspondences", m, h->cfg.num_keypoints, mode)) return 1;
     if (mode == 1 && decoder == 0)
         return fail("frames_correspondences: mode 1 (Hessian weights) needs decoder 1: get_final (decoder 0) computes no Hessian");
     size_t fk = 0;
@@ -2654,34 +2478,30 @@ int esahrnet_frames_correspondences(esahrnet_handle h, const void* frames_dev, i
                                     void* idx_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev, void* count_dev,
                                     void* order_dev, void* pts_dev, void* w_dev, void* ws_dev, size_t ws_bytes,
                                     esahrnet_stream stream) {
+    const char* who = "frames_correspondences";
     if (!h || !frames_dev || !det_boxes_dev || !kp_dev || !crop_boxes_dev || !rates_dev || !valid_dev || !count_dev || !order_dev ||
         !pts_dev || !w_dev || !ws_dev)
-        return fail("frames_correspondences: null argument");
+        return fail("%s: null argument", who);
     // everything that can be refused is refused here, before the first launch
-    if (check_boxes_args("frames_correspondences", m, frame_h, frame_w, scale, rule) ||
-        check_crops_args("frames_correspondences", nframes, pixel_format, stdv))
-        return 1;
-    if (!frame_idx_dev && m != nframes)
-        return fail("frames_correspondences: %d boxes on %d frames need a frame index (NULL is the identity: box i lies on frame i)", m,
-                    nframes);
-    if (!h->committed) return fail("frames_correspondences: esahrnet_commit has not been called");
+    FramesArgs a{frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m, scale, rule, mean, stdv,
+                 crop_boxes_dev, rates_dev, valid_dev, ws_dev, ws_bytes, stream};
+    if (check_frames_args(who, a)) return 1;
+    if (!h->committed) return fail("%s: esahrnet_commit has not been called", who);
     size_t need = 0, fk = 0;
     if (esahrnet_frames_correspondences_workspace_bytes(h, m, scale, decoder, mode, &need) ||
         esahrnet_frames_keypoints_workspace_bytes(h, m, scale, decoder, &fk))
         return 1;
-    if (ws_bytes < need) return fail("frames_correspondences: workspace too small (%zu < %zu)", ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("frames_correspondences: workspace must be 256-byte aligned");
-    const size_t fk_al = (fk + 255) & ~(size_t)255;
-    void* hess = mode == 1 ? static_cast<char*>(ws_dev) + fk_al : nullptr;
-    if (frames_run("frames_correspondences", h, frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m,
-                   scale, rule, mean, stdv, decoder, kp_dev, idx_dev, hess, crop_boxes_dev, rates_dev, valid_dev, ws_dev, fk_al, stream))
-        return 1;
+    if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("%s: workspace must be 256-byte aligned", who);
+    a.ws_bytes = (fk + 255) & ~(size_t)255;         // the loader's share; the Hessians of mode 1 lie behind it
+    void* hess = mode == 1 ? static_cast<char*>(ws_dev) + a.ws_bytes : nullptr;
+    if (frames_run(who, h, a, make_request(decoder == 1 ? DEC_FINAL2 : DEC_FINAL, kp_dev, idx_dev, hess))) return 1;
     const int rc = esa::launch_correspond(static_cast<const float*>(kp_dev), static_cast<const double*>(hess),
                                           static_cast<const int*>(crop_boxes_dev), static_cast<const double*>(rates_dev),
                                           static_cast<const int*>(valid_dev), m, h->cfg.num_keypoints, thresh, min_k, mode,
                                           static_cast<int*>(count_dev), static_cast<int*>(order_dev), static_cast<double*>(pts_dev),
                                           static_cast<double*>(w_dev), static_cast<hipStream_t>(stream));
-    if (rc) return fail("frames_correspondences: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (rc) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)rc));
     return 0;
 }
 

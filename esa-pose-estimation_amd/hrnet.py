@@ -356,6 +356,20 @@ class _Runtime:
     handle per device, so replicas do not serialise each other."""
 
     WS_SHAPES_PER_DEVICE = 4     # eager scratch tensors kept per device (LRU)
+    # workspace kind -> (the cache its tensors live in, its size query, that query's arguments between the handle and the result).
+    # The loader's kinds take n crops of hh x hh, share one cache and are told apart by the key's `keep`: the decoder,
+    # "gaussfit", or (decoder, mode) with the correspondences
+    _crops = lambda n, hh, ww, keep: (n, hh, ww)      # noqa: E731  (used by the table below only)
+    WS_KINDS = {
+        "forward": ("forward", "esahrnet_workspace_bytes", _crops),
+        "keypoints": ("keypoints", "esahrnet_keypoints_workspace_bytes", _crops),
+        "final2": ("final2", "esahrnet_keypoints_final2_forward_workspace_bytes", _crops),
+        "gaussfit": ("gaussfit", "esahrnet_keypoints_gaussfit_forward_workspace_bytes", _crops),
+        "frames": ("frames", "esahrnet_frames_keypoints_workspace_bytes", lambda n, hh, ww, keep: (n, hh, 0)),
+        "frames_final2": ("frames", "esahrnet_frames_keypoints_workspace_bytes", lambda n, hh, ww, keep: (n, hh, 1)),
+        "frames_gaussfit": ("frames", "esahrnet_frames_keypoints_gaussfit_workspace_bytes", lambda n, hh, ww, keep: (n, hh)),
+        "corr": ("frames", "esahrnet_frames_correspondences_workspace_bytes", lambda n, hh, ww, keep: (n, hh, *keep)),
+    }
 
     def __init__(self, cfg_struct):
         self.cfg = cfg_struct
@@ -363,11 +377,7 @@ class _Runtime:
         self.lock = threading.RLock()
         self.handles = {}        # device index -> (handle, weight-version key)
         self.dev_locks = {}      # device index -> lock serialising the enqueues of that device's handle
-        self.ws = {}             # (device, stream, n, h, w, keep) -> uint8 tensor, insertion order = LRU order
-        self.kp_ws = {}          # the same for esahrnet_forward_keypoints (its own size: esahrnet_keypoints_workspace_bytes)
-        self.f2_ws = {}          # the same for forward_final2 (esahrnet_keypoints_final2_forward_workspace_bytes)
-        self.fr_ws = {}          # the same for frames_keypoints (esahrnet_frames_keypoints_workspace_bytes), every decoder
-        self.gf_ws = {}          # the same for forward_gaussfit (esahrnet_keypoints_gaussfit_forward_workspace_bytes)
+        self.ws = {}             # cache name (WS_KINDS) -> {(device, stream, n, h, w, keep): uint8 tensor}, insertion order = LRU order
         self.part_tiles = {}     # (handle, h, w) -> tiles per heat-map with partial maxima (0: none)
         self._probe = self._create(-1)
 
@@ -460,10 +470,10 @@ class _Runtime:
     def release_workspaces(self):
         with self.lock:
             self.ws.clear()
-            self.kp_ws.clear()
-            self.f2_ws.clear()
-            self.fr_ws.clear()
-            self.gf_ws.clear()
+
+    def ws_cache(self, kind):
+        """The cached scratch tensors of one workspace kind (WS_KINDS): {(device, stream, n, h, w, keep): uint8 tensor}."""
+        return self.ws.setdefault(self.WS_KINDS[kind][0], {})
 
     def _workspace(self, h, device, stream, n, hh, ww, keep, kind="forward"):
         """Scratch for one forward.  Contract: while the stream is being CAPTURED into a HIP
@@ -472,27 +482,9 @@ class _Runtime:
         eager cache; eager forwards share a small per-device LRU of scratch tensors, keyed by stream and shape
         (two streams never share scratch) and protected by record_stream."""
         nbytes = C.c_size_t()
-        if kind == "keypoints":
-            _lib.check(self.lib.esahrnet_keypoints_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
-            cache = self.kp_ws
-        elif kind == "final2":
-            _lib.check(self.lib.esahrnet_keypoints_final2_forward_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
-            cache = self.f2_ws
-        elif kind == "gaussfit":
-            _lib.check(self.lib.esahrnet_keypoints_gaussfit_forward_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
-            cache = self.gf_ws
-        elif kind == "frames_gaussfit":                 # n crops of hh x hh; keep = "gaussfit" keeps its entries apart
-            _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit_workspace_bytes(h, n, hh, C.byref(nbytes)))
-            cache = self.fr_ws
-        elif kind == "corr":                            # n crops of hh x hh; keep = (decoder, mode)
-            _lib.check(self.lib.esahrnet_frames_correspondences_workspace_bytes(h, n, hh, keep[0], keep[1], C.byref(nbytes)))
-            cache = self.fr_ws
-        elif kind in ("frames", "frames_final2"):       # n crops of hh x hh; `keep` tells the two decoders' entries apart
-            _lib.check(self.lib.esahrnet_frames_keypoints_workspace_bytes(h, n, hh, int(kind == "frames_final2"), C.byref(nbytes)))
-            cache = self.fr_ws
-        else:
-            _lib.check(self.lib.esahrnet_workspace_bytes(h, n, hh, ww, C.byref(nbytes)))
-            cache = self.ws
+        _, query, args = self.WS_KINDS[kind]
+        _lib.check(getattr(self.lib, query)(h, *args(n, hh, ww, keep), C.byref(nbytes)))
+        cache = self.ws_cache(kind)
         if torch.cuda.is_current_stream_capturing():
             ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=device)
         else:
@@ -515,7 +507,10 @@ class _Runtime:
                 lk = self.dev_locks.setdefault(index, threading.RLock())
         return lk
 
-    def forward(self, module, x0, keep=False):
+    def _enqueue(self, module, x0, kind, entry, outputs, keep=False):
+        """One forward entry `h, x, n, h, w, <outputs>, ws, ws_bytes, stream` on the current stream of x's device, with the
+        workspace of `kind`.  outputs(h, n, hh, ww, new) allocates what the entry writes (new(dtype, *shape): an empty tensor
+        on that device) and returns the entry's output arguments in order: tensors, None, plain numbers.  -> those outputs."""
         x = self._check_input(module, x0)
         n, _, hh, ww = x.shape
         dev = x.device
@@ -525,25 +520,34 @@ class _Runtime:
         with self._device_lock(dev.index):
             h = self._handle_for(module, dev)
             _lib.check(self.lib.esahrnet_set_debug_keep(h, 1 if keep else 0))
-            ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, n, hh, ww, keep)
-            heat = torch.empty((n, module._k, hh, ww), dtype=torch.float32, device=dev)
-            # per-tile maxima beside the heat-maps (include/esahrnet.h: esahrnet_forward_partials): 8 bytes per plane
-            # and 16x16 tile, so that inference.heatmaps_to_keypoints need not sweep the maps again
-            nt = self._partial_tiles(h, hh, ww)
-            part = torch.empty((n * module._k, nt, 2), dtype=torch.float32, device=dev) if nt else None
-            args = (h, x.data_ptr(), n, hh, ww, heat.data_ptr(), part.data_ptr() if nt else None, ws_ptr, ws_bytes,
+            ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, n, hh, ww, keep, kind=kind)
+            outs = outputs(h, n, hh, ww, lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev))
+            args = (h, x.data_ptr(), n, hh, ww, *[o.data_ptr() if isinstance(o, torch.Tensor) else o for o in outs], ws_ptr, ws_bytes,
                     C.c_void_p(ts.cuda_stream))
+            fn = getattr(self.lib, entry)
             if torch.cuda.current_device() == dev.index:
-                rc = self.lib.esahrnet_forward_partials(*args)
+                rc = fn(*args)
             else:
                 with torch.cuda.device(dev):
-                    rc = self.lib.esahrnet_forward_partials(*args)
+                    rc = fn(*args)
             _lib.check(rc)
         ws.record_stream(ts)
         x.record_stream(ts)
-        if nt:
+        return outs
+
+    def forward(self, module, x0, keep=False):
+        k = module._k
+
+        def outputs(h, n, hh, ww, new):
+            # per-tile maxima beside the heat-maps (include/esahrnet.h: esahrnet_forward_partials): 8 bytes per plane
+            # and 16x16 tile, so that inference.heatmaps_to_keypoints need not sweep the maps again
+            nt = self._partial_tiles(h, hh, ww)
+            return new(torch.float32, n, k, hh, ww), new(torch.float32, n * k, nt, 2) if nt else None
+
+        heat, part = self._enqueue(module, x0, "forward", "esahrnet_forward_partials", outputs, keep)
+        if part is not None:
             try:
-                heat._esa_partials = (part, nt, heat._version)
+                heat._esa_partials = (part, part.shape[1], heat._version)
             except RuntimeError:            # torch.inference_mode(): no version counter, so no way to tell a later edit
                 pass
         return heat
@@ -551,94 +555,30 @@ class _Runtime:
     def forward_keypoints(self, module, x0, want_index):
         """esahrnet_forward_keypoints: (kp f32 [N,K,3], idx int32 [N,K] or None), no heat-map in caller memory.  Same device
         lock, workspace contract (graph capture included) and record_stream handling as forward()."""
-        x = self._check_input(module, x0)
-        n, _, hh, ww = x.shape
-        dev = x.device
-        ts = torch.cuda.current_stream(dev)
-        with self._device_lock(dev.index):
-            h = self._handle_for(module, dev)
-            _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
-            ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, n, hh, ww, False, kind="keypoints")
-            kp = torch.empty((n, module._k, 3), dtype=torch.float32, device=dev)
-            idx = torch.empty((n, module._k), dtype=torch.int32, device=dev) if want_index else None
-            args = (h, x.data_ptr(), n, hh, ww, kp.data_ptr(), idx.data_ptr() if want_index else None, ws_ptr, ws_bytes,
-                    C.c_void_p(ts.cuda_stream))
-            if torch.cuda.current_device() == dev.index:
-                rc = self.lib.esahrnet_forward_keypoints(*args)
-            else:
-                with torch.cuda.device(dev):
-                    rc = self.lib.esahrnet_forward_keypoints(*args)
-            _lib.check(rc)
-        ws.record_stream(ts)
-        x.record_stream(ts)
-        return kp, idx
+        k = module._k
+        return self._enqueue(module, x0, "keypoints", "esahrnet_forward_keypoints", lambda h, n, hh, ww, new: (
+            new(torch.float32, n, k, 3), new(torch.int32, n, k) if want_index else None))
 
     def forward_final2(self, module, x0, want_index, want_hessian=False):
         """net(x, output="keypoints", refine="get_final2"): esahrnet_forward_keypoints_final2, the forward with get_final2 in
-        place of its last launch; nothing but (kp, idx) reaches caller memory.  Same device lock, workspace contract (graph
-        capture included) and record_stream handling as forward()."""
-        x = self._check_input(module, x0)
-        n, _, hh, ww = x.shape
-        dev = x.device
-        ts = torch.cuda.current_stream(dev)
+        place of its last launch; nothing but (kp, idx) — and the Hessians, if asked for — reaches caller memory."""
         k = module._k
-        with self._device_lock(dev.index):
-            h = self._handle_for(module, dev)
-            _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
-            ws, ws_ptr, nbytes = self._workspace(h, dev, ts, n, hh, ww, False, kind="final2")
-            kp = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
-            idx = torch.empty((n, k), dtype=torch.int32, device=dev) if want_index else None
-            hess = torch.empty((n, k, 3), dtype=torch.float64, device=dev) if want_hessian else None
-            with torch.cuda.device(dev):
-                if want_hessian:
-                    _lib.check(self.lib.esahrnet_forward_keypoints_final2_hess(
-                        h, x.data_ptr(), n, hh, ww, kp.data_ptr(), idx.data_ptr() if want_index else None, hess.data_ptr(), ws_ptr,
-                        nbytes, C.c_void_p(ts.cuda_stream)))
-                else:
-                    _lib.check(self.lib.esahrnet_forward_keypoints_final2(h, x.data_ptr(), n, hh, ww, kp.data_ptr(),
-                                                                          idx.data_ptr() if want_index else None, ws_ptr, nbytes,
-                                                                          C.c_void_p(ts.cuda_stream)))
-        ws.record_stream(ts)
-        x.record_stream(ts)
-        return (kp, idx, hess) if want_hessian else (kp, idx)
+        return self._enqueue(module, x0, "final2", "esahrnet_forward_keypoints_final2" + ("_hess" if want_hessian else ""),
+                             lambda h, n, hh, ww, new: (new(torch.float32, n, k, 3), new(torch.int32, n, k) if want_index else None)
+                             + ((new(torch.float64, n, k, 3),) if want_hessian else ()))
 
     def forward_gaussfit(self, module, x0, want_fit, want_index, want_hessian=True, cov=None):
         """esahrnet_forward_keypoints_gaussfit: -> (kp f32 [N,K,3], fit f64 [N,K,8] or None, status int32 [N,K], hess f64 [N,K,3]
-        or None, idx int32 [N,K] or None); nothing else reaches caller memory.  Same device lock, weight-staleness key,
-        workspace contract (graph capture included) and record_stream handling as forward_final2().  cov = cov_floor (not
-        None): esahrnet_forward_keypoints_gaussfit_cov, -> (..., cov f64 [N,K,3], info f64 [N,K,3]) appended."""
-        x = self._check_input(module, x0)
-        n, _, hh, ww = x.shape
-        dev = x.device
-        ts = torch.cuda.current_stream(dev)
+        or None, idx int32 [N,K] or None); nothing else reaches caller memory.  cov = cov_floor (not None):
+        esahrnet_forward_keypoints_gaussfit_cov, -> (..., cov f64 [N,K,3], info f64 [N,K,3]) appended."""
         k = module._k
-        with self._device_lock(dev.index):
-            h = self._handle_for(module, dev)
-            _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
-            ws, ws_ptr, nbytes = self._workspace(h, dev, ts, n, hh, ww, False, kind="gaussfit")
-            with torch.cuda.device(dev):
-                kp = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
-                idx = torch.empty((n, k), dtype=torch.int32, device=dev) if want_index else None
-                fit = torch.empty((n, k, 8), dtype=torch.float64, device=dev) if want_fit else None
-                status = torch.empty((n, k), dtype=torch.int32, device=dev)
-                hess = torch.empty((n, k, 3), dtype=torch.float64, device=dev) if want_hessian else None
-                if cov is not None:
-                    cv = torch.empty((n, k, 3), dtype=torch.float64, device=dev)
-                    info = torch.empty((n, k, 3), dtype=torch.float64, device=dev)
-                    _lib.check(self.lib.esahrnet_forward_keypoints_gaussfit_cov(
-                        h, x.data_ptr(), n, hh, ww, kp.data_ptr(), idx.data_ptr() if want_index else None,
-                        fit.data_ptr() if want_fit else None, status.data_ptr(), hess.data_ptr() if want_hessian else None,
-                        cv.data_ptr(), info.data_ptr(), float(cov), ws_ptr, nbytes, C.c_void_p(ts.cuda_stream)))
-                else:
-                    _lib.check(self.lib.esahrnet_forward_keypoints_gaussfit(
-                        h, x.data_ptr(), n, hh, ww, kp.data_ptr(), idx.data_ptr() if want_index else None,
-                        fit.data_ptr() if want_fit else None, status.data_ptr(), hess.data_ptr() if want_hessian else None, ws_ptr,
-                        nbytes, C.c_void_p(ts.cuda_stream)))
-        ws.record_stream(ts)
-        x.record_stream(ts)
-        if cov is not None:
-            return kp, fit, status, hess, idx, cv, info
-        return kp, fit, status, hess, idx
+        kp, idx, fit, status, hess, *more = self._enqueue(
+            module, x0, "gaussfit", "esahrnet_forward_keypoints_gaussfit" + ("" if cov is None else "_cov"),
+            lambda h, n, hh, ww, new: (new(torch.float32, n, k, 3), new(torch.int32, n, k) if want_index else None,
+                                       new(torch.float64, n, k, 8) if want_fit else None, new(torch.int32, n, k),
+                                       new(torch.float64, n, k, 3) if want_hessian else None)
+            + (() if cov is None else (new(torch.float64, n, k, 3), new(torch.float64, n, k, 3), float(cov))))
+        return (kp, fit, status, hess, idx, *more[:2])
 
     def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None, cov=None):
         """esahrnet_frames_keypoints (arguments already checked by crops.check_device_loader_args).  The outputs are views
@@ -662,6 +602,7 @@ class _Runtime:
         nframes, fh, fw = frames.shape[:3]
         k = module._k
         ts = torch.cuda.current_stream(dev)
+        stream = C.c_void_p(ts.cuda_stream)
         with torch.cuda.device(dev):
             det = crops.to_device_int32(det_boxes, dev)
             fidx = None if frame_idx is None else crops.to_device_int32(frame_idx, dev)
@@ -677,67 +618,51 @@ class _Runtime:
             boxes = part("boxes", torch.int32, m, 4)
             valid = part("valid", torch.int32, m)
             idx = part("idx", torch.int32, m, k)
+            out = (kp, boxes, rates, valid, idx, packed)
             if decoder == 2:
                 fit, status, hess = part("fit", torch.float64, m, k, 8), part("status", torch.int32, m, k), \
                     part("hess", torch.float64, m, k, 3)
+                out += (fit, status, hess)
             if cov is not None:
                 cv, info = part("cov", torch.float64, m, k, 3), part("info", torch.float64, m, k, 3)
+                out += (cv, info)
+            if corr is not None:
+                thresh, min_k, mode = corr
+                count, order, pts, w, cpacked = pack_correspondences(m, k, dev)
+                out = (count, order, pts, w, kp, boxes, rates, valid, cpacked, packed)
             with self._device_lock(dev.index):
                 h = self._handle_for(module, dev)
                 _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
-                if decoder == 2:                    # its own entry point; the correspondences, if asked for, behind it
+                loader = (h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m,
+                          scale, rule, mean, std)
+                placed = (boxes.data_ptr(), rates.data_ptr(), valid.data_ptr())
+                if decoder == 2:                    # its own entry points; the correspondences, if asked for, behind them
                     ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, "gaussfit", kind="frames_gaussfit")
+                    fitted = (kp.data_ptr(), idx.data_ptr(), fit.data_ptr(), status.data_ptr(), hess.data_ptr())
                     if cov is not None:
                         _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit_cov(
-                            h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(),
-                            m, scale, rule, mean, std, kp.data_ptr(), idx.data_ptr(), fit.data_ptr(), status.data_ptr(),
-                            hess.data_ptr(), boxes.data_ptr(), rates.data_ptr(), valid.data_ptr(), cv.data_ptr(), info.data_ptr(),
-                            float(cov), ws_ptr, ws_bytes, C.c_void_p(ts.cuda_stream)))
+                            *loader, *fitted, *placed, cv.data_ptr(), info.data_ptr(), float(cov), ws_ptr, ws_bytes, stream))
                     else:
-                        _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit(
-                            h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(),
-                            m, scale, rule, mean, std, kp.data_ptr(), idx.data_ptr(), fit.data_ptr(), status.data_ptr(),
-                            hess.data_ptr(), boxes.data_ptr(), rates.data_ptr(), valid.data_ptr(), ws_ptr, ws_bytes,
-                            C.c_void_p(ts.cuda_stream)))
+                        _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit(*loader, *fitted, *placed, ws_ptr, ws_bytes, stream))
                     if corr is not None:
-                        thresh, min_k, mode = corr
-                        count, order, pts, w, cpacked = pack_correspondences(m, k, dev)
                         wsrc = info if cov is not None else hess         # weights="covariance": -cov^-1 in the Hessian's place
                         _lib.check(self.lib.esahrnet_correspondences(
-                            kp.data_ptr(), wsrc.data_ptr() if mode else None, boxes.data_ptr(), rates.data_ptr(), valid.data_ptr(),
-                            m, k, thresh, min_k, mode, count.data_ptr(), order.data_ptr(), pts.data_ptr(), w.data_ptr(),
-                            C.c_void_p(ts.cuda_stream)))
-                    for t in (ws, frames, det, fidx):
-                        if t is not None:
-                            t.record_stream(ts)
-                    if corr is not None:
-                        return count, order, pts, w, kp, boxes, rates, valid, cpacked, packed
-                    if cov is not None:
-                        return kp, boxes, rates, valid, idx, packed, fit, status, hess, cv, info
-                    return kp, boxes, rates, valid, idx, packed, fit, status, hess
-                if corr is not None:
-                    thresh, min_k, mode = corr
-                    count, order, pts, w, cpacked = pack_correspondences(m, k, dev)
+                            kp.data_ptr(), wsrc.data_ptr() if mode else None, *placed, m, k, thresh, min_k, mode, count.data_ptr(),
+                            order.data_ptr(), pts.data_ptr(), w.data_ptr(), stream))
+                elif corr is not None:
                     ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, (decoder, mode), kind="corr")
                     _lib.check(self.lib.esahrnet_frames_correspondences(
-                        h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m,
-                        scale, rule, mean, std, decoder, thresh, min_k, mode, kp.data_ptr(), idx.data_ptr(), boxes.data_ptr(),
-                        rates.data_ptr(), valid.data_ptr(), count.data_ptr(), order.data_ptr(), pts.data_ptr(), w.data_ptr(),
-                        ws_ptr, ws_bytes, C.c_void_p(ts.cuda_stream)))
-                    for t in (ws, frames, det, fidx):
-                        if t is not None:
-                            t.record_stream(ts)
-                    return count, order, pts, w, kp, boxes, rates, valid, cpacked, packed
-                ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, bool(decoder),
-                                                       kind="frames_final2" if decoder else "frames")
-                _lib.check(self.lib.esahrnet_frames_keypoints(
-                    h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m,
-                    scale, rule, mean, std, decoder, kp.data_ptr(), idx.data_ptr(), boxes.data_ptr(), rates.data_ptr(),
-                    valid.data_ptr(), ws_ptr, ws_bytes, C.c_void_p(ts.cuda_stream)))
+                        *loader, decoder, thresh, min_k, mode, kp.data_ptr(), idx.data_ptr(), *placed, count.data_ptr(),
+                        order.data_ptr(), pts.data_ptr(), w.data_ptr(), ws_ptr, ws_bytes, stream))
+                else:
+                    ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, bool(decoder),
+                                                           kind="frames_final2" if decoder else "frames")
+                    _lib.check(self.lib.esahrnet_frames_keypoints(*loader, decoder, kp.data_ptr(), idx.data_ptr(), *placed, ws_ptr,
+                                                                  ws_bytes, stream))
         for t in (ws, frames, det, fidx):
             if t is not None:
                 t.record_stream(ts)
-        return kp, boxes, rates, valid, idx, packed
+        return out
 
     def _partial_tiles(self, h, hh, ww):
         if os.environ.get("ESAHRNET_NO_PARTIALS"):

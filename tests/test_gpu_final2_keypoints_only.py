@@ -171,15 +171,15 @@ def test_cached_workspace_has_no_heatmap_term(env, name, precision):
     n, hh, ww = 8, 128, 128
     x = env["synth"].make_crops(n, 1, hh, ww, seed=3).cuda()
     rt = net._rt
-    rt.f2_ws.clear()
+    rt.ws_cache("final2").clear()
     with torch.no_grad():
         net(x, output="keypoints", refine="get_final2")
         net(x, output="keypoints")
     torch.cuda.synchronize()
-    kw = max(t.numel() for t in rt.kp_ws.values())
+    kw = max(t.numel() for t in rt.ws_cache("keypoints").values())
     planes = n * net.num_keypoints
     bound = kw + 12 * planes * (-(-hh // F2V_T)) * (-(-ww // F2V_T)) + 4096
-    f2 = [t.numel() for t in rt.f2_ws.values()]
+    f2 = [t.numel() for t in rt.ws_cache("final2").values()]
     assert f2 and max(f2) <= bound, (f2, kw, bound)
     assert max(f2) - kw < planes * hh * ww * 4 // 8           # far from the N*K*H*W*4 bytes of the heat-maps
 

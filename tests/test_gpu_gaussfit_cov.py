@@ -346,10 +346,21 @@ def test_loader_equals_its_parts(env, name):
     """esahrnet_frames_keypoints_gaussfit_cov: valid rows bit-identical to crops -> esahrnet_forward_keypoints_gaussfit_cov and
     to esahrnet_frames_keypoints_gaussfit; an invalid crop has NaN cov and info; frames_to_correspondences(weights=
     "covariance") equals the loader followed by keypoints_to_correspondences on its info."""
+    _loader_equals_its_parts(env, name, "fp32", 64)
+
+
+def test_loader_equals_its_parts_behind_the_matrix_core_output_layer(env):
+    """The same on split bf16, where the output layer is the matrix-core kernel and the fit reads its heat-maps from the
+    workspace: the one source of the maps that the loader's Gaussian-fit entries (with and without the covariance, and the
+    correspondences behind them) meet in no other test.  Crops of 48 x 48 (the loader's crops are square): partial last tiles
+    at every level, and 13 x 13 fit windows that meet the border."""
+    _loader_equals_its_parts(env, "seg_hrnet2", "bf16x3", 48)
+
+
+def _loader_equals_its_parts(env, name, precision, scale):
     inf, crops = env["inference"], env["crops"]
-    net, _ = F._build(env, name, "fp32", gain=1.0)
+    net, _ = F._build(env, name, precision, gain=1.0)
     frames = F._frames(env, "frames", 2)
-    scale = 64
     k = net.num_keypoints
     with torch.no_grad():
         x, _, _, _ = crops.crop_batch_device(frames, F.SCENE_BOXES, frame_idx=F.SCENE_FIDX, scale=scale)
