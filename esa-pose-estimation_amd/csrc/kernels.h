@@ -322,6 +322,18 @@ int launch_keypoints(const float* heat, int planes, int H, int W, float* kp, int
 // launch_keypoints' row, rows m >= 1 the best local maxima at Chebyshev distance > r from every earlier one (NaN x 3, -1: none)
 int launch_keypoints_candidates(const float* heat, int planes, int H, int W, int M, int r, float* cand, int* cidx,
                                 hipStream_t stream);
+// the same bits from one sweep and a table of per-cell bests (keypoints_candidates_onepass.hip), on eligible planes: heat 16-byte
+// aligned, W a multiple of 4, at most kOnepassMaxCells cells of 8 x 8 pixels; hipErrorInvalidValue on any other plane
+constexpr int kOnepassMaxCells = 4096;
+// launch_keypoints_candidates_auto (the fused paths, form -1) runs the one-sweep kernel on an eligible plane from this M on: its
+// slowest window beat the multi-sweep kernel's fastest at M = 2, 3 and 4; at M = 1, where there is no runner-up to find, its
+// sweep costs twice the multi-sweep kernel's
+constexpr int kOnepassFromM = 2;
+bool keypoints_candidates_onepass_eligible(const float* heat, int H, int W);
+int launch_keypoints_candidates_onepass(const float* heat, int planes, int H, int W, int M, int r, float* cand, int* cidx,
+                                        hipStream_t stream);
+int launch_keypoints_candidates_auto(const float* heat, int planes, int H, int W, int M, int r, float* cand, int* cidx,
+                                     hipStream_t stream);
 // same result from the per-tile maxima of the output-layer kernel (FinalParams::part, `ntiles` pairs per plane)
 int launch_keypoints_finish(const float* heat, const float2* part, int ntiles, int planes, int H, int W, float* kp, int* idx_out,
                             hipStream_t stream);

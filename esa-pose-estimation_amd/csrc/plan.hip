@@ -1621,7 +1621,8 @@ static void describe(esahrnet_op_desc* d, const char* kernel, const char* label,
 }
 
 // What a forward leaves in caller memory in place of heat-maps: the decoder and where its results go.
-enum Decoder { DEC_NONE, DEC_FINAL, DEC_FINAL2, DEC_GAUSSFIT };     // none (heat-maps), get_final, get_final2, the Gaussian fit
+// none (heat-maps), get_final, get_final2, the Gaussian fit, the M best peaks (get_final at each)
+enum Decoder { DEC_NONE, DEC_FINAL, DEC_FINAL2, DEC_GAUSSFIT, DEC_CAND };
 struct Request {
     Decoder decoder = DEC_NONE;
     float* kp = nullptr;        // f32 [n * K][3], never null
@@ -1632,13 +1633,17 @@ struct Request {
     double* cov = nullptr;      // ... f64 [n * K][3] each, the covariance of the fitted centre and -cov^-1 (both nullptr: not
     double* info = nullptr;     // asked for, the kernels then compute what esahrnet_forward_keypoints_gaussfit computes)
     double cov_floor = 0.0;
+    float* cand = nullptr;      // the candidates: f32 [n * K][M][3] (= kp, never null) and int32 [n * K][M] (= idx, may be null),
+    int* cidx = nullptr;        // M in 1..ESAHRNET_MAX_CANDIDATES peaks per plane, r >= 0 pixels apart
+    int M = 0, r = 0;
 };
 
 // The one place a request is built, for the four forms the entries come in: (kp, idx), + hess, + fit and status, + cov, info and
 // cov_floor.  Two rules are stated here and nowhere else: get_final computes no Hessian, so hess is ignored by it; cov and
-// info belong to the Gaussian fit, and are ignored without it.
+// info belong to the Gaussian fit, and are ignored without it.  The candidates' form is (cand, cidx) in the place of (kp, idx),
+// with M and r.
 static Request make_request(Decoder d, void* kp, void* idx, void* hess = nullptr, void* fit = nullptr, void* status = nullptr,
-                            void* cov = nullptr, void* info = nullptr, double cov_floor = 0.0) {
+                            void* cov = nullptr, void* info = nullptr, double cov_floor = 0.0, int M = 0, int nms_radius = 0) {
     Request r;
     r.decoder = d;
     r.kp = static_cast<float*>(kp);
@@ -1649,7 +1654,16 @@ static Request make_request(Decoder d, void* kp, void* idx, void* hess = nullptr
     r.cov = d == DEC_GAUSSFIT ? static_cast<double*>(cov) : nullptr;
     r.info = d == DEC_GAUSSFIT ? static_cast<double*>(info) : nullptr;
     r.cov_floor = cov_floor;
+    if (d == DEC_CAND) {
+        r.cand = r.kp;
+        r.cidx = r.idx;
+        r.M = M;
+        r.r = nms_radius;
+    }
     return r;
+}
+static Request make_candidates_request(void* cand, void* cidx, int M, int nms_radius) {
+    return make_request(DEC_CAND, cand, cidx, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, M, nms_radius);
 }
 
 // the device buffers of one forward (all nullptr when an op is only described)
@@ -1674,7 +1688,8 @@ struct Buffers {
 //   get_final2                seg_hrnet3, get_final2's per-tile raw and blurred maxima of the NHWC heat-maps (part:
 //                             esa::final2_workspace_bytes); the matrix-core output layer, its heat-maps and the same; the VALU
 //                             output layer, the raw (part) and blurred (bmax) maxima of its 22 x 22 tiles
-// No N*K*H*W term but the matrix-core one.
+//   candidates                the heat-maps, for every network and precision: the runner-up rule needs whole planes
+// No N*K*H*W term but the matrix-core one and the candidates'.
 struct KpScratch {
     int ntiles = 0;
     size_t heat = 0, part = 0, bmax = 0;
@@ -1688,6 +1703,10 @@ static KpScratch kp_scratch(const esahrnet_ctx& c, int n, int height, int width,
     const long long planes = (long long)n * K;
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     if (d == DEC_NONE) return s;
+    if (d == DEC_CAND) {
+        s.heat = pad((size_t)planes * height * width * 4);
+        return s;
+    }
     if (c.cfg.variant != 1 && c.opt.final_mfma) s.heat = pad((size_t)planes * height * width * 4);
     if (d == DEC_FINAL2) {
         if (c.cfg.variant == 1 || c.opt.final_mfma) {
@@ -1717,6 +1736,16 @@ static int run_decode(const esahrnet_ctx& c, const Buffers& b, const esa::FinalP
     const int K = c.cfg.num_keypoints;
     const bool final2 = r.decoder == DEC_FINAL2, gaussfit = r.decoder == DEC_GAUSSFIT;
     esa::FinalParams p = fp ? *fp : esa::FinalParams{};
+    if (r.decoder == DEC_CAND) {                    // whole planes into the scratch (the output layer, either kernel, or
+        int rc;                                     // seg_hrnet3's conversion, with another destination), then the decoder
+        if (fp) {
+            p.out = b.kheat;
+            p.part = nullptr;
+            rc = esa::launch_final(p, stream);
+        } else rc = esa::launch_fmt_to_nchw(fmt, maps, n, K, height, width, Cp, b.kheat, stream);
+        if (rc) return rc;
+        return esa::launch_keypoints_candidates_auto(b.kheat, n * K, height, width, r.M, r.r, r.cand, r.cidx, stream);
+    }
     if (fp && !c.final_wpk) {
         p.out = nullptr;
         p.part = b.kpart;
@@ -2268,6 +2297,10 @@ int esahrnet_keypoints_gaussfit_forward_workspace_bytes(esahrnet_handle h, int n
     return forward_workspace_bytes("keypoints_gaussfit_forward_workspace_bytes", h, n, height, width, DEC_GAUSSFIT, bytes);
 }
 
+int esahrnet_keypoints_candidates_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
+    return forward_workspace_bytes("keypoints_candidates_forward_workspace_bytes", h, n, height, width, DEC_CAND, bytes);
+}
+
 // ---- the forward straight to keypoints ----------------------------------------------------------------------------------
 static int forward_request(const char* who, esahrnet_handle h, const void* x_dev, int n, int height, int width, const Request& r,
                            void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
@@ -2327,6 +2360,26 @@ int esahrnet_forward_keypoints_gaussfit_cov(esahrnet_handle h, const void* x_dev
                             ws_dev, ws_bytes, stream);
 }
 
+// what esahrnet_forward_keypoints_candidates and the loader in front of it refuse about the decoder's arguments
+static int check_candidates_request(const char* who, const Request& r) {
+    if (r.M < 1 || r.M > ESAHRNET_MAX_CANDIDATES)
+        return fail("%s: %d candidates per heat-map unsupported (1..%d)", who, r.M, ESAHRNET_MAX_CANDIDATES);
+    if (r.r < 0) return fail("%s: negative nms_radius %d", who, r.r);
+    if ((reinterpret_cast<uintptr_t>(r.cand) | reinterpret_cast<uintptr_t>(r.cidx)) & 3)
+        return fail("%s: cand_dev and cidx_dev must be 4-byte aligned", who);
+    return 0;
+}
+
+int esahrnet_forward_keypoints_candidates(esahrnet_handle h, const void* x_dev, int n, int height, int width, int candidates,
+                                          int nms_radius, void* cand_dev, void* cidx_dev, void* ws_dev, size_t ws_bytes,
+                                          esahrnet_stream stream) {
+    const char* who = "forward_keypoints_candidates";
+    const Request r = make_candidates_request(cand_dev, cidx_dev, candidates, nms_radius);
+    if (!h || !r.cand) return fail("%s: null argument", who);
+    if (check_candidates_request(who, r)) return 1;
+    return run_forward(h, x_dev, n, height, width, nullptr, nullptr, ws_dev, ws_bytes, stream, nullptr, &r);
+}
+
 // ---- the loader on the device: detector boxes + frames -> crops -> keypoints (frontend.hip) ----------------------------
 // what the loader entries take besides the handle and the decoder's outputs
 struct FramesArgs {
@@ -2368,6 +2421,11 @@ int esahrnet_frames_keypoints_gaussfit_workspace_bytes(esahrnet_handle h, int m,
     return frames_workspace_bytes("frames_keypoints_gaussfit", h, m, scale, DEC_GAUSSFIT, bytes);
 }
 
+int esahrnet_frames_keypoints_candidates_workspace_bytes(esahrnet_handle h, int m, int scale, size_t* bytes) {
+    if (!h || !bytes) return fail("frames_keypoints_candidates_workspace_bytes: null argument");
+    return frames_workspace_bytes("frames_keypoints_candidates", h, m, scale, DEC_CAND, bytes);
+}
+
 // what every loader entry refuses about the frames and the boxes
 static int check_frames_args(const char* who, const FramesArgs& a) {
     if (esa::check_boxes_args(who, a.m, a.frame_h, a.frame_w, a.scale, a.rule) ||
@@ -2395,7 +2453,9 @@ static int frames_run(const char* who, esahrnet_handle h, const FramesArgs& a, c
     if (run_forward(h, a.ws, a.m, a.scale, a.scale, nullptr, nullptr, static_cast<char*>(a.ws) + head, a.ws_bytes - head, a.stream,
                     nullptr, &r))
         return 1;
-    if (r.decoder == DEC_GAUSSFIT)
+    if (r.decoder == DEC_CAND)                      // a crop's K * M candidate rows: the kp / idx rows of K * M keypoints
+        rc = esa::launch_mark_invalid(valid, a.m, h->cfg.num_keypoints * r.M, r.cand, r.cidx, st);
+    else if (r.decoder == DEC_GAUSSFIT)
         rc = esa::launch_mark_invalid_gaussfit_cov(valid, a.m, h->cfg.num_keypoints, r.kp, r.idx, r.fit, r.status, r.hess, r.cov,
                                                    r.info, st);
     else rc = esa::launch_mark_invalid(valid, a.m, h->cfg.num_keypoints, r.kp, r.idx, st);
@@ -2403,10 +2463,10 @@ static int frames_run(const char* who, esahrnet_handle h, const FramesArgs& a, c
     return 0;
 }
 
-// The three esahrnet_frames_keypoints* entries: everything that can be refused is refused here, before the first launch.
+// The four esahrnet_frames_keypoints* entries: everything that can be refused is refused here, before the first launch.
 // abi_decoder: the `decoder` argument of esahrnet_frames_keypoints as given (refused by its workspace query when unknown);
 // unused by the Gaussian-fit entries.  Each entry keeps the order of its refusals: the _cov form checks its three additions
-// before the handle's commit.
+// before the handle's commit, and so does the candidates' form with M, r and the alignment of its outputs.
 static int frames_keypoints(const char* who, bool with_cov, esahrnet_handle h, const FramesArgs& a, int abi_decoder,
                             const Request& r) {
     const bool gaussfit = r.decoder == DEC_GAUSSFIT;
@@ -2414,10 +2474,12 @@ static int frames_keypoints(const char* who, bool with_cov, esahrnet_handle h, c
         return fail("%s: null argument", who);
     if (check_frames_args(who, a)) return 1;
     if (with_cov && esa::check_cov_args(who, r.cov, r.info, r.cov_floor)) return 1;
+    if (r.decoder == DEC_CAND && check_candidates_request(who, r)) return 1;
     if (!h->committed) return fail("%s: esahrnet_commit has not been called", who);
     if (gaussfit && check_gaussfit_outputs(who, *h, r)) return 1;
     size_t need = 0;
-    if (gaussfit ? esahrnet_frames_keypoints_gaussfit_workspace_bytes(h, a.m, a.scale, &need)
+    if (r.decoder == DEC_CAND ? esahrnet_frames_keypoints_candidates_workspace_bytes(h, a.m, a.scale, &need)
+        : gaussfit ? esahrnet_frames_keypoints_gaussfit_workspace_bytes(h, a.m, a.scale, &need)
                  : esahrnet_frames_keypoints_workspace_bytes(h, a.m, a.scale, abi_decoder, &need))
         return 1;
     if (a.ws_bytes < need) return fail("%s: workspace too small (%zu < %zu)", who, a.ws_bytes, need);
@@ -2456,6 +2518,17 @@ int esahrnet_frames_keypoints_gaussfit_cov(esahrnet_handle h, const void* frames
                        crop_boxes_dev, rates_dev, valid_dev, ws_dev, ws_bytes, stream};
     return frames_keypoints("frames_keypoints_gaussfit_cov", true, h, a, 0,
                             make_request(DEC_GAUSSFIT, kp_dev, idx_dev, hess_dev, fit_dev, status_dev, cov_dev, info_dev, cov_floor));
+}
+
+int esahrnet_frames_keypoints_candidates(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                                         int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m, int scale,
+                                         int rule, float mean, float stdv, int candidates, int nms_radius, void* cand_dev,
+                                         void* cidx_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev, void* ws_dev,
+                                         size_t ws_bytes, esahrnet_stream stream) {
+    const FramesArgs a{frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m, scale, rule, mean, stdv,
+                       crop_boxes_dev, rates_dev, valid_dev, ws_dev, ws_bytes, stream};
+    return frames_keypoints("frames_keypoints_candidates", false, h, a, 0,
+                            make_candidates_request(cand_dev, cidx_dev, candidates, nms_radius));
 }
 
 // ---- keypoints -> correspondences for the pose solver (correspond.hip) --------------------------------------------------

@@ -250,6 +250,40 @@ class HighResolutionNet(nn.Module):
         kp, fit, status, hess, _ = self._rt.forward_gaussfit(self, x0, bool(return_fit), False)
         return (kp, fit, status, hess) if return_fit else (kp, status, hess)
 
+    def candidates(self, x0: torch.Tensor, candidates: int = 3, nms_radius: int = 6, return_index: bool = False):
+        """The forward with the candidate decoder in place of its last launch (include/esahrnet.h
+        esahrnet_forward_keypoints_candidates): -> cand f32 cuda [N,K,M,3] = (x, y, peak), the M = `candidates` (1..4) best peaks of
+        every heat-map, `nms_radius` pixels apart, best first; with return_index=True (cand, cidx int32 [N,K,M]).  Bit-identical to
+        inference.heatmaps_to_candidates(net(x), candidates, nms_radius, return_index), without heat-maps in caller memory (they
+        live in the workspace: the runner-up rule needs whole planes)."""
+        if self.training:
+            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
+                               "(the reference callers do, val.py:95 / demo.py:80)")
+        cand, cidx = self._rt.forward_candidates(self, x0, int(candidates), int(nms_radius), bool(return_index))
+        return (cand, cidx) if return_index else cand
+
+    def frames_to_candidates(self, frames: torch.Tensor, det_boxes, frame_idx=None, scale: int = 256, rule: str = "val",
+                             candidates: int = 3, nms_radius: int = 6, mean=None, std: float = crops.STD, pixel_format=None):
+        """frames_to_keypoints with the candidate decoder (include/esahrnet.h esahrnet_frames_keypoints_candidates): box rule,
+        crops, forward and the M best peaks of every heat-map in one library call.  -> (cand f32 [m,K,M,3], crop_boxes int32 [m,4],
+        rates f64 [m], valid int32 [m]), all on the device; cand equals crops.crop_batch -> net.candidates(x, candidates,
+        nms_radius) bit for bit, except that the rows of an invalid crop (valid == 0) are NaN."""
+        return self._frames_to_candidates(frames, det_boxes, frame_idx, scale, rule, candidates, nms_radius, mean, std,
+                                          pixel_format)[:4]
+
+    def _frames_to_candidates(self, frames, det_boxes, frame_idx, scale, rule, candidates, nms_radius, mean, std, pixel_format):
+        """frames_to_candidates, plus (cidx int32 [m,K,M], packed): every output is a view of `packed` (one uint8 buffer,
+        inference.packed_layout(m, K, candidates=M)), so a caller that needs them on the host fetches them with one copy; cidx is
+        -1 in the rows of an invalid crop."""
+        if self.training:
+            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
+                               "(the reference callers do, val.py:95 / demo.py:80)")
+        rule_n, fmt, m = crops.check_device_loader_args(frames, det_boxes, frame_idx, rule, pixel_format)
+        if mean is None:
+            mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
+        return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
+                                         0, cand=(int(candidates), int(nms_radius)))
+
     def _frames_to_keypoints(self, frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format, cov_floor=None):
         """frames_to_keypoints, plus (idx int32 [m,K], packed): every output is a view of `packed` (one uint8 buffer), so a
         caller that needs them on the host fetches them with one copy (pipeline.estimate_poses).  refine="gaussfit": plus (fit
@@ -365,7 +399,9 @@ class _Runtime:
         "keypoints": ("keypoints", "esahrnet_keypoints_workspace_bytes", _crops),
         "final2": ("final2", "esahrnet_keypoints_final2_forward_workspace_bytes", _crops),
         "gaussfit": ("gaussfit", "esahrnet_keypoints_gaussfit_forward_workspace_bytes", _crops),
+        "candidates": ("candidates", "esahrnet_keypoints_candidates_forward_workspace_bytes", _crops),
         "frames": ("frames", "esahrnet_frames_keypoints_workspace_bytes", lambda n, hh, ww, keep: (n, hh, 0)),
+        "frames_candidates": ("frames", "esahrnet_frames_keypoints_candidates_workspace_bytes", lambda n, hh, ww, keep: (n, hh)),
         "frames_final2": ("frames", "esahrnet_frames_keypoints_workspace_bytes", lambda n, hh, ww, keep: (n, hh, 1)),
         "frames_gaussfit": ("frames", "esahrnet_frames_keypoints_gaussfit_workspace_bytes", lambda n, hh, ww, keep: (n, hh)),
         "corr": ("frames", "esahrnet_frames_correspondences_workspace_bytes", lambda n, hh, ww, keep: (n, hh, *keep)),
@@ -580,7 +616,18 @@ class _Runtime:
             + (() if cov is None else (new(torch.float64, n, k, 3), new(torch.float64, n, k, 3), float(cov))))
         return (kp, fit, status, hess, idx, *more[:2])
 
-    def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None, cov=None):
+    def forward_candidates(self, module, x0, candidates, nms_radius, want_index):
+        """esahrnet_forward_keypoints_candidates: (cand f32 [N,K,M,3], cidx int32 [N,K,M] or None); the library refuses M outside
+        1..4 and a negative radius with its own text (nothing is allocated by M before that)."""
+        k = module._k
+        mm = min(max(candidates, 1), _lib.MAX_CANDIDATES)
+        _, _, cand, cidx = self._enqueue(module, x0, "candidates", "esahrnet_forward_keypoints_candidates",
+                                         lambda h, n, hh, ww, new: (candidates, nms_radius, new(torch.float32, n, k, mm, 3),
+                                                                    new(torch.int32, n, k, mm) if want_index else None))
+        return cand, cidx
+
+    def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None, cov=None,
+                         cand=None):
         """esahrnet_frames_keypoints (arguments already checked by crops.check_device_loader_args).  The outputs are views
         of one packed buffer: rates f64 [m] | kp f32 [m,K,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,K]
         (inference.packed_layout; decoder 2, the Gaussian fit, also fit, hess and status, returned behind `packed`).
@@ -588,7 +635,11 @@ class _Runtime:
         forward().  corr = (thresh, min_k, mode): esahrnet_frames_correspondences instead -> (count, order, pts, w, kp, boxes,
         rates, valid, cpacked, packed), the first four views of `cpacked` (inference.pack_correspondences), the next four of `packed`.  cov = cov_floor (decoder 2
         only): esahrnet_frames_keypoints_gaussfit_cov; cov and info ride in `packed` behind hess and are returned last, and the
-        correspondences, if asked for with mode 1, take info in hess' place."""
+        correspondences, if asked for with mode 1, take info in hess' place.  cand = (M, nms_radius) (decoder 0, no corr):
+        esahrnet_frames_keypoints_candidates instead -> (cand f32 [m,K,M,3], boxes, rates, valid, cidx int32 [m,K,M], packed), views
+        of the buffer inference.packed_layout(m, K, candidates=M) lays out."""
+        if cand is not None and (decoder != 0 or corr is not None or cov is not None):
+            raise ValueError("the candidates belong to the get_final decoder, without correspondences")
         if cov is not None and decoder != 2:
             raise ValueError("the covariance of the fitted centre belongs to the Gaussian-fit decoder")
         if module._cin != 1:
@@ -606,7 +657,7 @@ class _Runtime:
         with torch.cuda.device(dev):
             det = crops.to_device_int32(det_boxes, dev)
             fidx = None if frame_idx is None else crops.to_device_int32(frame_idx, dev)
-            lay = packed_layout(m, k, decoder == 2, cov is not None)
+            lay = packed_layout(m, k, decoder == 2, cov is not None, candidates=None if cand is None else cand[0])
             packed = torch.empty(lay["total"][1], dtype=torch.uint8, device=dev)
 
             def part(name, dtype, *shape):
@@ -614,10 +665,14 @@ class _Runtime:
                 return packed[o:o + b].view(dtype).view(*shape)
 
             rates = part("rates", torch.float64, m)
-            kp = part("kp", torch.float32, m, k, 3)
             boxes = part("boxes", torch.int32, m, 4)
             valid = part("valid", torch.int32, m)
-            idx = part("idx", torch.int32, m, k)
+            if cand is None:
+                kp = part("kp", torch.float32, m, k, 3)
+                idx = part("idx", torch.int32, m, k)
+            else:                                   # the candidate rows lie where the keypoint rows lie otherwise
+                kp = part("cand", torch.float32, m, k, cand[0], 3)
+                idx = part("cidx", torch.int32, m, k, cand[0])
             out = (kp, boxes, rates, valid, idx, packed)
             if decoder == 2:
                 fit, status, hess = part("fit", torch.float64, m, k, 8), part("status", torch.int32, m, k), \
@@ -636,7 +691,12 @@ class _Runtime:
                 loader = (h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m,
                           scale, rule, mean, std)
                 placed = (boxes.data_ptr(), rates.data_ptr(), valid.data_ptr())
-                if decoder == 2:                    # its own entry points; the correspondences, if asked for, behind them
+                if cand is not None:
+                    # ("candidates" as the cache key's `keep`: it only keeps this workspace apart from the other loader kinds)
+                    ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, "candidates", kind="frames_candidates")
+                    _lib.check(self.lib.esahrnet_frames_keypoints_candidates(*loader, int(cand[0]), int(cand[1]), kp.data_ptr(),
+                                                                             idx.data_ptr(), *placed, ws_ptr, ws_bytes, stream))
+                elif decoder == 2:                  # its own entry points; the correspondences, if asked for, behind them
                     ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, "gaussfit", kind="frames_gaussfit")
                     fitted = (kp.data_ptr(), idx.data_ptr(), fit.data_ptr(), status.data_ptr(), hess.data_ptr())
                     if cov is not None:

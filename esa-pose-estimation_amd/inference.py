@@ -116,13 +116,16 @@ def heatmaps_to_keypoints(heat: torch.Tensor, refine: str = "get_final", return_
     return (out[0], out[2]) if return_hessian else out[0]
 
 
-def heatmaps_to_candidates(heat: torch.Tensor, candidates: int = 3, nms_radius: int = 6, return_index: bool = False):
+def heatmaps_to_candidates(heat: torch.Tensor, candidates: int = 3, nms_radius: int = 6, return_index: bool = False, form=None):
     """f32 cuda [N,K,H,W] -> f32 cuda [N,K,M,3] = (x, y, peak), the M = `candidates` (1..4) best peaks of every heat-map, best
     first (include/esahrnet.h esahrnet_keypoints_candidates, one kernel, no host sync).  Candidate 0 is the row of
     heatmaps_to_keypoints, bit for bit; candidate m >= 1 is the largest local maximum (>= its 8 neighbours, neither NaN nor
     -inf, no NaN neighbour) at Chebyshev distance > nms_radius from every earlier candidate, ties to the lower index, refined
     by the same get_final step at its own pixel; rows without a qualifying pixel are NaN.  return_index=True: -> (cand, idx int32
-    cuda [N,K,M] = row * W + column of each candidate, -1 where there is none).  pnp.candidates_to_pose_batch solves on them."""
+    cuda [N,K,M] = row * W + column of each candidate, -1 where there is none).  pnp.candidates_to_pose_batch solves on them.
+    form (esahrnet_keypoints_candidates_form): 0 the multi-sweep kernel, 1 the one-sweep kernel (the same bits; refused on a plane
+    it does not serve: not 16-byte aligned, W no multiple of 4, more than 4096 cells of 8 x 8), -1 what the fused paths launch;
+    None (default): esahrnet_keypoints_candidates, the multi-sweep kernel."""
     if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
         raise ValueError("expected a 4-D tensor [N, K, H, W]")
     if not heat.is_cuda:
@@ -137,8 +140,13 @@ def heatmaps_to_candidates(heat: torch.Tensor, candidates: int = 3, nms_radius: 
     idx = torch.empty(cand.shape[:3], dtype=torch.int32, device=heat.device) if return_index else None
     stream = torch.cuda.current_stream(heat.device).cuda_stream
     with torch.cuda.device(heat.device):
-        _lib.check(_lib.lib().esahrnet_keypoints_candidates(heat.data_ptr(), n, k, h, w, m, int(nms_radius), cand.data_ptr(),
-                                                            idx.data_ptr() if return_index else None, C.c_void_p(stream)))
+        if form is None:
+            _lib.check(_lib.lib().esahrnet_keypoints_candidates(heat.data_ptr(), n, k, h, w, m, int(nms_radius), cand.data_ptr(),
+                                                                idx.data_ptr() if return_index else None, C.c_void_p(stream)))
+        else:
+            _lib.check(_lib.lib().esahrnet_keypoints_candidates_form(heat.data_ptr(), n, k, h, w, m, int(nms_radius), int(form),
+                                                                     cand.data_ptr(), idx.data_ptr() if return_index else None,
+                                                                     C.c_void_p(stream)))
     return (cand, idx) if return_index else cand
 
 
@@ -241,14 +249,28 @@ def check_weights(weights, refine="get_final2"):
     return int(weights != "peak")
 
 
-def packed_layout(m: int, k: int, gaussfit: bool = False, cov: bool = False):
+def packed_layout(m: int, k: int, gaussfit: bool = False, cov: bool = False, candidates=None):
     """The packed buffer of net.frames_to_keypoints' outputs: name -> (offset, bytes).  rates f64 [m] | kp f32 [m,k,3] |
     crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,k]; with gaussfit the decoder's f64 outputs come right behind
     rates (8-byte aligned) and its status last: rates | fit f64 [m,k,8] | hess f64 [m,k,3] | kp | crop_boxes | valid | idx |
     status int32 [m,k]; with cov (gaussfit only) cov f64 [m,k,3] | info f64 [m,k,3] follow hess.  "total" -> (0, bytes of the
-    buffer)."""
+    buffer).  candidates=M (net.frames_to_candidates; not with gaussfit): rates | cand f32 [m,k,M,3] | crop_boxes | valid | cidx
+    int32 [m,k,M]."""
     if cov and not gaussfit:
         raise ValueError("cov=True belongs to gaussfit=True")
+    if candidates is not None:
+        if gaussfit:
+            raise ValueError("candidates=M belongs to the get_final decoder (gaussfit=False)")
+        mm = int(candidates)
+        if not 1 <= mm <= _lib.MAX_CANDIDATES:
+            raise ValueError(f"candidates must be in 1..{_lib.MAX_CANDIDATES}, got {candidates!r}")
+        parts = [("rates", 8 * m), ("cand", 12 * m * k * mm), ("boxes", 16 * m), ("valid", 4 * m), ("cidx", 4 * m * k * mm)]
+        out, off = {}, 0
+        for name, b in parts:
+            out[name] = (off, b)
+            off += b
+        out["total"] = (0, off)
+        return out
     parts = [("rates", 8 * m)] + ([("fit", 64 * m * k), ("hess", 24 * m * k)] if gaussfit else [])
     parts += [("cov", 24 * m * k), ("info", 24 * m * k)] if cov else []
     parts += [("kp", 12 * m * k), ("boxes", 16 * m), ("valid", 4 * m), ("idx", 4 * m * k)]

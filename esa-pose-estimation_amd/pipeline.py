@@ -109,6 +109,9 @@ def pose_pool(workers: int):
 FALLBACK_POSE = ((1.0, 0.0, 0.0, 0.0), (0.0, 0.0, 10.0))   # identity attitude, 10 m down the boresight
 
 
+CANDIDATES_PATHS = ("heatmaps", "fused", "loader")
+
+
 class PoseFailure(ValueError):
     """No pose for an image (fewer than 4 usable keypoints, RANSAC found no consensus, or a gate of estimate_poses withdrew it)."""
 
@@ -118,7 +121,8 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
                    on_fail: str = "raise", keypoints_only: bool = False, refine: str = "get_final",
                    device_loader: bool = False, frame_idx=None, rule: str = "val", device_select: bool = False,
                    weights: str = "peak", threads: int = 0, cov_floor: float = 1e-6, return_report: bool = False,
-                   max_rms_px=None, min_inliers=None, candidates: int = 1, nms_radius: int = 6, min_ratio: float = 0.3):
+                   max_rms_px=None, min_inliers=None, candidates: int = 1, nms_radius: int = 6, min_ratio: float = 0.3,
+                   candidates_path: str = "heatmaps"):
     """One batch of the val.py:136-233 loop.  frames uint8 cuda [N,H,W]; bboxes N x (x, y, x2, y2);
     kp3d [K3, 3] model keypoints; K camera matrix.  -> list of (q [w,x,y,z], t) per image.
     An image without a solution (the native solver reports it as a NaN row; the reference would die inside
@@ -155,10 +159,19 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
     (inference.heatmaps_to_candidates, `nms_radius` pixels apart), ONE device->host copy of them, and the native solve swaps a
     runner-up with at least `min_ratio` of the primary's peak in where the RANSAC consensus pose says the primary is wrong
     (pnp.candidates_to_pose_batch; the report then carries .used and .rescued).  It is refused together with keypoints_only,
-    device_loader, device_select, distributed, native=False and any other refine; candidates=1 leaves every path as it is."""
+    device_loader, device_select, distributed, native=False and any other refine; candidates=1 leaves every path as it is.
+    candidates_path (with candidates > 1 only) says where the runner-ups are decoded: "heatmaps" (default) as above; "fused":
+    host crops, then net.candidates(x, M, nms_radius), the decoder in the forward, no heat-map tensor in caller memory; "loader":
+    net._frames_to_candidates does the box rule, the crops, the forward and the decoder in one library call and ONE device->host
+    copy of its packed buffer feeds the solve — bboxes are integers, frame_idx and rule are accepted and an invalid crop has no
+    pose, as with device_loader=True.  The poses, .used and .rescued are those of "heatmaps", bit for bit."""
     inference.check_refine(refine)
     inference.check_weights(weights, refine)
     want = return_report or max_rms_px is not None or min_inliers is not None
+    if candidates_path not in CANDIDATES_PATHS:
+        raise ValueError(f"candidates_path must be one of {CANDIDATES_PATHS}, got {candidates_path!r}")
+    if candidates == 1 and candidates_path != "heatmaps":
+        raise ValueError(f"candidates_path={candidates_path!r} belongs to candidates > 1 (candidates=1 decodes no runner-up)")
     if candidates != 1:
         for name, on in (("keypoints_only", keypoints_only), ("device_loader", device_loader), ("device_select", device_select),
                          ("distributed", distributed), ("native=False", not native), (f"refine='{refine}'", refine != "get_final")):
@@ -223,13 +236,41 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
                 rep = pnp.PoseReport(raw)
         poses = [(np.full(4, np.nan), np.full(3, np.nan)) if b else p for p, b in zip(poses, bad)]
         return finish(poses, rep)
+    if candidates != 1 and candidates_path == "loader":
+        with torch.no_grad():
+            out = net._frames_to_candidates(frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, None, crops.STD, None)
+        m, k, mm = out[0].shape[:3]
+        host = out[5].cpu().numpy()                         # the only device->host copy
+        lay = inference.packed_layout(m, k, candidates=mm)
+        rates, cand, boxes, valid = (host[lay[name][0]:lay[name][0] + lay[name][1]] for name in ("rates", "cand", "boxes", "valid"))
+        cand = cand.view(np.float32).reshape(m, k, mm, 3)
+        boxes = boxes.view(np.int32).reshape(m, 4).tolist()
+        bad = valid.view(np.int32) == 0
+        # an invalid crop (NaN candidate rows) is kept away from the solver and reported as the NaN row that "no solution" is
+        rates = [1.0 if b else float(r) for r, b in zip(rates.view(np.float64), bad)]
+        q, t, _, *rep = pnp.candidates_to_pose_batch(np.where(bad[:, None, None, None], np.float32(0), cand), kp3d,
+                                                     np.asarray(K, np.float64), [(b[0], b[1]) for b in boxes], rates, thresh, min_k,
+                                                     min_ratio, threads, report=want)
+        rep = rep[0] if want else None
+        if want and bad.any():                              # no crop, no correspondences: the row of "fewer than 4", with n = 0
+            raw = rep.raw.copy()
+            raw[bad] = np.nan
+            raw[bad, 0], raw[bad, 2] = 1.0, 0.0
+            fixed = pnp.PoseReport(raw)
+            fixed.used, fixed.rescued = rep.used.copy(), rep.rescued.copy()
+            fixed.used[bad], fixed.rescued[bad] = -1, False     # no keypoint of such an image entered a solve
+            rep = fixed
+        return finish([(np.full(4, np.nan), np.full(3, np.nan)) if b else (q[i], t[i]) for i, b in enumerate(bad)], rep)
     if frame_idx is not None or rule != "val":
         raise ValueError("frame_idx and rule belong to device_loader=True (crops.crop_batch: one val box per frame)")
     rk = {} if refine == "get_final" else {"refine": refine}
     x, boxes, rates = crops.crop_batch(frames, bboxes, scale)
     if candidates != 1:
         with torch.no_grad():
-            cand = inference.heatmaps_to_candidates(net(x), candidates, nms_radius)
+            if candidates_path == "fused":
+                cand = net.candidates(x, candidates, nms_radius)
+            else:
+                cand = inference.heatmaps_to_candidates(net(x), candidates, nms_radius)
         cand = cand.cpu().numpy()                           # the only device->host copy: N*K*M*3 floats
         q, t, _, *rep = pnp.candidates_to_pose_batch(cand, kp3d, np.asarray(K, np.float64), [(b[0], b[1]) for b in boxes], rates,
                                                      thresh, min_k, min_ratio, threads, report=want)

@@ -381,6 +381,45 @@ int esahrnet_frames_keypoints_gaussfit_cov(esahrnet_handle h, const void* frames
                                            void* cov_dev, void* info_dev, double cov_floor,
                                            void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
 
+/* ---- runner-up peaks in one sweep, in the forward and behind the loader (csrc/keypoints_candidates_onepass.hip) ----------------
+ * esahrnet_keypoints_candidates_form: esahrnet_keypoints_candidates with the kernel named.  form 0: the multi-sweep kernel of
+ * esahrnet_keypoints_candidates (one sweep of the plane per candidate).  form 1: the one-sweep kernel: one sweep finds every
+ * qualifying local maximum and keeps the best of each 8 x 8 cell in an LDS table, and each runner-up rescans only the cells its
+ * predecessor's suppression square touches; cand_dev and cidx_dev are bit-identical to form 0's.  It serves planes with heat_dev
+ * 16-byte aligned, width a multiple of 4 and at most 4096 cells (ceil(height / 8) * ceil(width / 8): 512 x 512); on any other
+ * plane form 1 is an argument error.  form -1: what the fused entries below launch: the one-sweep kernel where it serves and is
+ * the faster one (M >= 2), the multi-sweep kernel otherwise, so every plane has a result.  The other argument errors
+ * and their texts are esahrnet_keypoints_candidates'; all are reported before anything is enqueued.  No workspace, no allocation,
+ * no synchronisation; a plane's result does not depend on its batch. */
+int esahrnet_keypoints_candidates_form(const void* heat_dev, int n, int k, int height, int width, int candidates, int nms_radius,
+                                       int form, void* cand_dev, void* cidx_dev, esahrnet_stream stream);
+
+/* esahrnet_forward_keypoints_candidates: the forward with the candidate decoder in place of its last launch.  cand_dev f32
+ * [n][K][M][3] and cidx_dev int32 [n][K][M] (NULL: not written) are bit-identical to esahrnet_forward followed by
+ * esahrnet_keypoints_candidates on its heat-maps; no heat-map reaches caller memory.  The runner-up rule needs whole planes, so
+ * the output layer (or seg_hrnet3's conversion) writes them into the workspace: esahrnet_keypoints_candidates_forward_workspace_bytes
+ * is esahrnet_workspace_bytes plus n * K * height * width * 4 bytes, padded to 256.  Allocates nothing, does not synchronise, may
+ * be captured into a graph.  The refusals, in their order: a NULL handle or cand_dev; M outside 1..ESAHRNET_MAX_CANDIDATES; r < 0; a
+ * cand_dev or cidx_dev that is not 4-byte aligned; then those of esahrnet_forward_keypoints (NULL x_dev or ws_dev, a handle
+ * without esahrnet_commit, the shape, the workspace's size and alignment) -- all before anything is enqueued. */
+int esahrnet_keypoints_candidates_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes);
+int esahrnet_forward_keypoints_candidates(esahrnet_handle h, const void* x_dev, int n, int height, int width, int candidates,
+                                          int nms_radius, void* cand_dev, void* cidx_dev, void* ws_dev, size_t ws_bytes,
+                                          esahrnet_stream stream);
+
+/* esahrnet_frames_keypoints_candidates: esahrnet_frames_keypoints with the candidate decoder: esahrnet_boxes -> esahrnet_crops_ex
+ * into the head of the workspace -> esahrnet_forward_keypoints_candidates on the rest -> the rows of an invalid crop (valid == 0)
+ * become NaN in cand_dev and -1 in cidx_dev (NULL: not written); valid rows are bit-identical to the calls it is built from.
+ * ws_dev: esahrnet_frames_keypoints_candidates_workspace_bytes bytes, 256-byte aligned.  The refusals (cin != 1 among them) and
+ * the graph-capture contract are esahrnet_frames_keypoints'; M, r and the alignment of cand_dev / cidx_dev are checked behind
+ * the frames' and boxes' arguments and before the handle's commit. */
+int esahrnet_frames_keypoints_candidates_workspace_bytes(esahrnet_handle h, int m, int scale, size_t* bytes);
+int esahrnet_frames_keypoints_candidates(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                                         int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m,
+                                         int scale, int rule, float mean, float stdv, int candidates, int nms_radius,
+                                         void* cand_dev, void* cidx_dev, void* crop_boxes_dev, void* rates_dev, void* valid_dev,
+                                         void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+
 /* ---- keypoints to the record the pose solver consumes, on the device (val.py:172-180) -------------------------------------
  * esahrnet_correspondences (correspond_kernel, one wave per crop, k <= 32): kp_dev f32 [m][k][3] keypoint rows, crop_boxes_dev /
  *   rates_dev / valid_dev as esahrnet_boxes wrote them ->

@@ -7,6 +7,10 @@ alternate window by window, so that they share whatever the machine is doing; a 
 per form the median window and the [min, max] spread, in microseconds per call, and the ratio to M times the existing decoder
 (the M sweeps it logically is).  One JSON line per form.
 
+--form 0,1 (any of 0, 1, -1): the kernels of `esahrnet_keypoints_candidates_form` against each other instead — 0 the multi-sweep
+kernel, 1 the one-sweep kernel, -1 what the fused paths launch — at M = 1..4 on the same planes, the same alternating windows;
+one JSON line per (form, M), with the ratio to `esahrnet_keypoints_ex` and whether the form's bits are those of form 0.
+
 --host: host poses/s of `esahrnet_pnp_batch_cand` (M = 1 and M = 3) against `esahrnet_pnp_batch_ex` on candidate 0, on one
 synthetic record of --poses images (11 keypoints, sigma 0.5 px, --bad wrong primaries per image whose true place is candidate
 1), alternating windows as tools/pnp_report_bench.py's.  Needs no GPU.  One JSON line."""
@@ -66,6 +70,56 @@ def decoder(a):
                           "candidates_found_at_M4": found}), flush=True)
 
 
+def kernels(a):
+    import torch
+    from esa_pose_estimation_amd import _lib, synth
+    if not torch.cuda.is_available():
+        raise SystemExit("candidates_bench needs a GPU (--host runs without one)")
+    kinds = [int(f) for f in a.form.split(",")]
+    n, k, s = a.images, a.keypoints, a.size
+    heat = synth.make_gaussian_heatmaps(n, k, s, s, seed=0) + 0.7 * synth.make_gaussian_heatmaps(n, k, s, s, seed=1, noise=0.0)
+    heat = heat.cuda().contiguous()
+    lib = _lib.lib()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    kp = torch.empty((n, k, 3), dtype=torch.float32, device="cuda")
+    idx = torch.empty((n, k), dtype=torch.int32, device="cuda")
+    outs = {(f, M): (torch.empty((n, k, M, 3), dtype=torch.float32, device="cuda"), torch.empty((n, k, M), dtype=torch.int32, device="cuda"))
+            for f in set(kinds) | {0} for M in range(1, _lib.MAX_CANDIDATES + 1)}
+    forms = {"keypoints_ex": lambda: lib.esahrnet_keypoints_ex(heat.data_ptr(), n, k, s, s, kp.data_ptr(), idx.data_ptr(), stream)}
+    call = lambda f, M: lib.esahrnet_keypoints_candidates_form(heat.data_ptr(), n, k, s, s, M, a.radius, f,               # noqa: E731
+                                                               outs[f, M][0].data_ptr(), outs[f, M][1].data_ptr(), stream)
+    for M in range(1, _lib.MAX_CANDIDATES + 1):
+        _lib.check(call(0, M))                            # the bits every form is held to
+        for f in kinds:
+            forms[f"form{f}_M{M}"] = lambda f=f, M=M: call(f, M)
+    for f in forms.values():                              # warm-up: code objects loaded, the planes in the caches as in the windows
+        for _ in range(3):
+            _lib.check(f())
+    torch.cuda.synchronize()
+    same = {(f, M): bool(torch.equal(outs[f, M][0].view(torch.int32), outs[0, M][0].view(torch.int32)) and
+                         torch.equal(outs[f, M][1], outs[0, M][1])) for f in kinds for M in range(1, _lib.MAX_CANDIDATES + 1)}
+    found = int((outs[0, _lib.MAX_CANDIDATES][1] >= 0).sum())
+    us = {name: [] for name in forms}
+    for _ in range(a.reps):
+        for name, f in forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.steps):
+                f()
+            e1.record()
+            e1.synchronize()
+            us[name].append(1e3 * e0.elapsed_time(e1) / a.steps)
+    base = statistics.median(us["keypoints_ex"])
+    for name, v in us.items():
+        row = {"form": name, "planes": n * k, "plane": [s, s], "nms_radius": a.radius, "steps": a.steps, "reps": a.reps,
+               "us_per_call": round(statistics.median(v), 2), "spread_us": [round(min(v), 2), round(max(v), 2)],
+               "ratio_to_keypoints_ex": round(statistics.median(v) / base, 3), "candidates_found_at_M4": found}
+        if name != "keypoints_ex":
+            f, M = name[4:].split("_M")
+            row["bits_of_form0"] = same[int(f), int(M)]
+        print(json.dumps(row), flush=True)
+
+
 def host(a):
     from esa_pose_estimation_amd import _lib, synth
     m, k, M = a.poses, 11, 3
@@ -115,6 +169,7 @@ def host(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--host", action="store_true")
+    ap.add_argument("--form", default=None, help="comma-separated kernels of esahrnet_keypoints_candidates_form to compare, e.g. 0,1")
     ap.add_argument("--images", type=int, default=32)
     ap.add_argument("--keypoints", type=int, default=11)
     ap.add_argument("--size", type=int, default=256)
@@ -125,7 +180,7 @@ def main():
     ap.add_argument("--bad", type=int, default=2)
     ap.add_argument("--threads", type=int, default=16)
     a = ap.parse_args()
-    host(a) if a.host else decoder(a)
+    host(a) if a.host else kernels(a) if a.form else decoder(a)
 
 
 if __name__ == "__main__":
