@@ -27,7 +27,8 @@ import torch.nn as nn
 
 from . import _lib, crops
 from .fold import fold_conv
-from .inference import check_cov_floor, check_refine, check_weights, pack_correspondences, packed_layout
+from .inference import (check_cov_floor, check_refine, check_weights, pack_correspondences, record_fields, record_outputs,
+                        record_views)
 
 logger = logging.getLogger(__name__)
 BN_MOMENTUM = 0.01           # models/seg_hrnet.py:23 (irrelevant at inference, kept for parity)
@@ -147,6 +148,19 @@ class HighResolutionNet(nn.Module):
             model_dict.update({k: v for k, v in pretrained_dict.items() if k in model_dict})
             self.load_state_dict(model_dict)
 
+    def _inference_only(self):
+        if self.training:
+            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
+                               "(the reference callers do, val.py:95 / demo.py:80)")
+
+    def _loader_args(self, frames, det_boxes, frame_idx, rule, mean, pixel_format):
+        """The loader's argument check and the rule's default mean, for the three loader calls (behind _inference_only and the
+        checks of their own arguments): -> (rule number, pixel format, number of boxes, mean)."""
+        rule_n, fmt, m = crops.check_device_loader_args(frames, det_boxes, frame_idx, rule, pixel_format)
+        if mean is None:
+            mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
+        return rule_n, fmt, m, mean
+
     OUTPUTS = ("heatmaps", "keypoints", "keypoints+index")
 
     def forward(self, x0: torch.Tensor, output: str = "heatmaps", refine: str = "get_final"):
@@ -157,9 +171,7 @@ class HighResolutionNet(nn.Module):
         inference.heatmaps_to_keypoints(net(x), refine="get_final2"), without writing heat-maps either
         (include/esahrnet.h esahrnet_forward_keypoints_final2).  refine="gaussfit": the Gaussian-fit decoder fused into the
         forward (esahrnet_forward_keypoints_gaussfit), the kp of keypoints_gaussfit."""
-        if self.training:
-            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
-                               "(the reference callers do, val.py:95 / demo.py:80)")
+        self._inference_only()
         check_refine(refine)
         if output == "heatmaps":
             if refine != "get_final":
@@ -211,15 +223,11 @@ class HighResolutionNet(nn.Module):
         """frames_to_correspondences, plus (cpacked, packed): count, order, pts and w are views of `cpacked` (one uint8 buffer,
         inference.pack_correspondences), which a caller that needs them on the host fetches with one copy; kp, crop_boxes, rates
         and valid are views of `packed`, the keypoint record (inference.packed_layout), as _frames_to_keypoints returns it."""
-        if self.training:
-            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
-                               "(the reference callers do, val.py:95 / demo.py:80)")
+        self._inference_only()
         check_refine(refine)
         mode = check_weights(weights, refine)
         cov = check_cov_floor(cov_floor) if weights == "covariance" else None
-        rule_n, fmt, m = crops.check_device_loader_args(frames, det_boxes, frame_idx, rule, pixel_format)
-        if mean is None:
-            mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
+        rule_n, fmt, m, mean = self._loader_args(frames, det_boxes, frame_idx, rule, mean, pixel_format)
         return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
                                          REFINE_DECODER[refine], corr=(float(thresh), int(min_k), mode), cov=cov)
 
@@ -228,9 +236,7 @@ class HighResolutionNet(nn.Module):
         [N,K], hess f64 [N,K,3] = (dxx, dxy, dyy), NaN where no step was taken), bit-identical to
         inference.heatmaps_to_keypoints(net(x), refine="get_final2", return_hessian=True), without heat-maps in caller memory
         (include/esahrnet.h esahrnet_forward_keypoints_final2_hess)."""
-        if self.training:
-            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
-                               "(the reference callers do, val.py:95 / demo.py:80)")
+        self._inference_only()
         return self._rt.forward_final2(self, x0, True, want_hessian=True)
 
     def keypoints_gaussfit(self, x0: torch.Tensor, return_fit: bool = False, return_cov: bool = False, cov_floor: float = 1e-6):
@@ -240,9 +246,7 @@ class HighResolutionNet(nn.Module):
         heat-maps in caller memory.  return_cov=True (esahrnet_forward_keypoints_gaussfit_cov) appends (cov, info) f64 [N,K,3]
         each, the covariance of the fitted centre and -cov^-1 as inference.gaussfit_keypoints(net(x), return_cov=True,
         cov_floor=cov_floor) gives them, bit for bit; the other outputs keep their bits."""
-        if self.training:
-            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
-                               "(the reference callers do, val.py:95 / demo.py:80)")
+        self._inference_only()
         if return_cov:
             kp, fit, status, hess, _, cov, info = self._rt.forward_gaussfit(self, x0, bool(return_fit), False,
                                                                             cov=check_cov_floor(cov_floor))
@@ -256,9 +260,7 @@ class HighResolutionNet(nn.Module):
         every heat-map, `nms_radius` pixels apart, best first; with return_index=True (cand, cidx int32 [N,K,M]).  Bit-identical to
         inference.heatmaps_to_candidates(net(x), candidates, nms_radius, return_index), without heat-maps in caller memory (they
         live in the workspace: the runner-up rule needs whole planes)."""
-        if self.training:
-            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
-                               "(the reference callers do, val.py:95 / demo.py:80)")
+        self._inference_only()
         cand, cidx = self._rt.forward_candidates(self, x0, int(candidates), int(nms_radius), bool(return_index))
         return (cand, cidx) if return_index else cand
 
@@ -275,12 +277,8 @@ class HighResolutionNet(nn.Module):
         """frames_to_candidates, plus (cidx int32 [m,K,M], packed): every output is a view of `packed` (one uint8 buffer,
         inference.packed_layout(m, K, candidates=M)), so a caller that needs them on the host fetches them with one copy; cidx is
         -1 in the rows of an invalid crop."""
-        if self.training:
-            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
-                               "(the reference callers do, val.py:95 / demo.py:80)")
-        rule_n, fmt, m = crops.check_device_loader_args(frames, det_boxes, frame_idx, rule, pixel_format)
-        if mean is None:
-            mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
+        self._inference_only()
+        rule_n, fmt, m, mean = self._loader_args(frames, det_boxes, frame_idx, rule, mean, pixel_format)
         return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
                                          0, cand=(int(candidates), int(nms_radius)))
 
@@ -289,13 +287,9 @@ class HighResolutionNet(nn.Module):
         caller that needs them on the host fetches them with one copy (pipeline.estimate_poses).  refine="gaussfit": plus (fit
         f64 [m,K,8], status int32 [m,K], hess f64 [m,K,3]), views of `packed` too (inference.packed_layout); with cov_floor
         (refine="gaussfit" only) plus (cov, info) f64 [m,K,3] behind them (esahrnet_frames_keypoints_gaussfit_cov)."""
-        if self.training:
-            raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
-                               "(the reference callers do, val.py:95 / demo.py:80)")
+        self._inference_only()
         check_refine(refine)
-        rule_n, fmt, m = crops.check_device_loader_args(frames, det_boxes, frame_idx, rule, pixel_format)
-        if mean is None:
-            mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
+        rule_n, fmt, m, mean = self._loader_args(frames, det_boxes, frame_idx, rule, mean, pixel_format)
         cov = None if cov_floor is None else check_cov_floor(cov_floor)
         return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
                                          REFINE_DECODER[refine], cov=cov)
@@ -629,15 +623,16 @@ class _Runtime:
     def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None, cov=None,
                          cand=None):
         """esahrnet_frames_keypoints (arguments already checked by crops.check_device_loader_args).  The outputs are views
-        of one packed buffer: rates f64 [m] | kp f32 [m,K,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,K]
-        (inference.packed_layout; decoder 2, the Gaussian fit, also fit, hess and status, returned behind `packed`).
+        of one packed buffer (inference.record_fields / record_views), returned as inference.record_outputs orders them: rates f64
+        [m] | kp f32 [m,K,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,K]; decoder 2, the Gaussian fit, also fit,
+        hess and status, returned behind `packed`.
         Same device lock, weight-staleness key, workspace contract (graph capture included) and record_stream handling as
         forward().  corr = (thresh, min_k, mode): esahrnet_frames_correspondences instead -> (count, order, pts, w, kp, boxes,
-        rates, valid, cpacked, packed), the first four views of `cpacked` (inference.pack_correspondences), the next four of `packed`.  cov = cov_floor (decoder 2
-        only): esahrnet_frames_keypoints_gaussfit_cov; cov and info ride in `packed` behind hess and are returned last, and the
-        correspondences, if asked for with mode 1, take info in hess' place.  cand = (M, nms_radius) (decoder 0, no corr):
-        esahrnet_frames_keypoints_candidates instead -> (cand f32 [m,K,M,3], boxes, rates, valid, cidx int32 [m,K,M], packed), views
-        of the buffer inference.packed_layout(m, K, candidates=M) lays out."""
+        rates, valid, cpacked, packed), the first four views of `cpacked` (inference.pack_correspondences), the next four of
+        `packed`.  cov = cov_floor (decoder 2 only): esahrnet_frames_keypoints_gaussfit_cov; cov and info ride in `packed` behind
+        hess and are returned last, and the correspondences, if asked for with mode 1, take info in hess' place.  cand = (M,
+        nms_radius) (decoder 0, no corr): esahrnet_frames_keypoints_candidates instead -> (cand f32 [m,K,M,3], boxes, rates, valid,
+        cidx int32 [m,K,M], packed), views of the candidates record (inference.record_fields(K, "candidates", candidates=M))."""
         if cand is not None and (decoder != 0 or corr is not None or cov is not None):
             raise ValueError("the candidates belong to the get_final decoder, without correspondences")
         if cov is not None and decoder != 2:
@@ -657,68 +652,49 @@ class _Runtime:
         with torch.cuda.device(dev):
             det = crops.to_device_int32(det_boxes, dev)
             fidx = None if frame_idx is None else crops.to_device_int32(frame_idx, dev)
-            lay = packed_layout(m, k, decoder == 2, cov is not None, candidates=None if cand is None else cand[0])
-            packed = torch.empty(lay["total"][1], dtype=torch.uint8, device=dev)
-
-            def part(name, dtype, *shape):
-                o, b = lay[name]
-                return packed[o:o + b].view(dtype).view(*shape)
-
-            rates = part("rates", torch.float64, m)
-            boxes = part("boxes", torch.int32, m, 4)
-            valid = part("valid", torch.int32, m)
-            if cand is None:
-                kp = part("kp", torch.float32, m, k, 3)
-                idx = part("idx", torch.int32, m, k)
-            else:                                   # the candidate rows lie where the keypoint rows lie otherwise
-                kp = part("cand", torch.float32, m, k, cand[0], 3)
-                idx = part("cidx", torch.int32, m, k, cand[0])
-            out = (kp, boxes, rates, valid, idx, packed)
-            if decoder == 2:
-                fit, status, hess = part("fit", torch.float64, m, k, 8), part("status", torch.int32, m, k), \
-                    part("hess", torch.float64, m, k, 3)
-                out += (fit, status, hess)
-            if cov is not None:
-                cv, info = part("cov", torch.float64, m, k, 3), part("info", torch.float64, m, k, 3)
-                out += (cv, info)
+            fields = record_fields(k, "keypoints" if cand is None else "candidates", decoder == 2, cov is not None,
+                                   None if cand is None else cand[0])
+            packed = torch.empty(m * sum(b for _, b in fields), dtype=torch.uint8, device=dev)
+            views = record_views(packed, m, k, fields)
+            out = record_outputs(views, packed)
+            p = {name: t.data_ptr() for name, t in views.items()}
             if corr is not None:
                 thresh, min_k, mode = corr
                 count, order, pts, w, cpacked = pack_correspondences(m, k, dev)
-                out = (count, order, pts, w, kp, boxes, rates, valid, cpacked, packed)
+                out = (count, order, pts, w, *out[:4], cpacked, packed)
+                selected = (count.data_ptr(), order.data_ptr(), pts.data_ptr(), w.data_ptr())
             with self._device_lock(dev.index):
                 h = self._handle_for(module, dev)
                 _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
                 loader = (h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m,
                           scale, rule, mean, std)
-                placed = (boxes.data_ptr(), rates.data_ptr(), valid.data_ptr())
+                placed = (p["boxes"], p["rates"], p["valid"])
                 if cand is not None:
                     # ("candidates" as the cache key's `keep`: it only keeps this workspace apart from the other loader kinds)
                     ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, "candidates", kind="frames_candidates")
-                    _lib.check(self.lib.esahrnet_frames_keypoints_candidates(*loader, int(cand[0]), int(cand[1]), kp.data_ptr(),
-                                                                             idx.data_ptr(), *placed, ws_ptr, ws_bytes, stream))
+                    _lib.check(self.lib.esahrnet_frames_keypoints_candidates(*loader, int(cand[0]), int(cand[1]), p["cand"],
+                                                                             p["cidx"], *placed, ws_ptr, ws_bytes, stream))
                 elif decoder == 2:                  # its own entry points; the correspondences, if asked for, behind them
                     ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, "gaussfit", kind="frames_gaussfit")
-                    fitted = (kp.data_ptr(), idx.data_ptr(), fit.data_ptr(), status.data_ptr(), hess.data_ptr())
+                    fitted = (p["kp"], p["idx"], p["fit"], p["status"], p["hess"])
                     if cov is not None:
                         _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit_cov(
-                            *loader, *fitted, *placed, cv.data_ptr(), info.data_ptr(), float(cov), ws_ptr, ws_bytes, stream))
+                            *loader, *fitted, *placed, p["cov"], p["info"], float(cov), ws_ptr, ws_bytes, stream))
                     else:
                         _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit(*loader, *fitted, *placed, ws_ptr, ws_bytes, stream))
                     if corr is not None:
-                        wsrc = info if cov is not None else hess         # weights="covariance": -cov^-1 in the Hessian's place
+                        wsrc = p["info"] if cov is not None else p["hess"]   # weights="covariance": -cov^-1 in the Hessian's place
                         _lib.check(self.lib.esahrnet_correspondences(
-                            kp.data_ptr(), wsrc.data_ptr() if mode else None, *placed, m, k, thresh, min_k, mode, count.data_ptr(),
-                            order.data_ptr(), pts.data_ptr(), w.data_ptr(), stream))
+                            p["kp"], wsrc if mode else None, *placed, m, k, thresh, min_k, mode, *selected, stream))
                 elif corr is not None:
                     ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, (decoder, mode), kind="corr")
                     _lib.check(self.lib.esahrnet_frames_correspondences(
-                        *loader, decoder, thresh, min_k, mode, kp.data_ptr(), idx.data_ptr(), *placed, count.data_ptr(),
-                        order.data_ptr(), pts.data_ptr(), w.data_ptr(), ws_ptr, ws_bytes, stream))
+                        *loader, decoder, thresh, min_k, mode, p["kp"], p["idx"], *placed, *selected, ws_ptr, ws_bytes, stream))
                 else:
                     ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, bool(decoder),
                                                            kind="frames_final2" if decoder else "frames")
-                    _lib.check(self.lib.esahrnet_frames_keypoints(*loader, decoder, kp.data_ptr(), idx.data_ptr(), *placed, ws_ptr,
-                                                                  ws_bytes, stream))
+                    _lib.check(self.lib.esahrnet_frames_keypoints(*loader, decoder, p["kp"], p["idx"], *placed, ws_ptr, ws_bytes,
+                                                                  stream))
         for t in (ws, frames, det, fidx):
             if t is not None:
                 t.record_stream(ts)

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import heapq
+import math
 
 import numpy as np
 import torch
@@ -249,36 +250,101 @@ def check_weights(weights, refine="get_final2"):
     return int(weights != "peak")
 
 
-def packed_layout(m: int, k: int, gaussfit: bool = False, cov: bool = False, candidates=None):
-    """The packed buffer of net.frames_to_keypoints' outputs: name -> (offset, bytes).  rates f64 [m] | kp f32 [m,k,3] |
-    crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,k]; with gaussfit the decoder's f64 outputs come right behind
-    rates (8-byte aligned) and its status last: rates | fit f64 [m,k,8] | hess f64 [m,k,3] | kp | crop_boxes | valid | idx |
-    status int32 [m,k]; with cov (gaussfit only) cov f64 [m,k,3] | info f64 [m,k,3] follow hess.  "total" -> (0, bytes of the
-    buffer).  candidates=M (net.frames_to_candidates; not with gaussfit): rates | cand f32 [m,k,M,3] | crop_boxes | valid | cidx
-    int32 [m,k,M]."""
+RECORD_KINDS = ("keypoints", "correspondences", "candidates")
+# THE description of the packed records; every layout, view and exchange below and in hrnet / parallel / pipeline derives from it.
+# Element type and trailing shape of every field (k = keypoints per crop, M = candidates per keypoint) ...
+_RECORD_TYPES = {"rates": (torch.float64, ()), "fit": (torch.float64, ("k", 8)), "hess": (torch.float64, ("k", 3)),
+                 "cov": (torch.float64, ("k", 3)), "info": (torch.float64, ("k", 3)), "kp": (torch.float32, ("k", 3)),
+                 "boxes": (torch.int32, (4,)), "valid": (torch.int32, ()), "idx": (torch.int32, ("k",)),
+                 "status": (torch.int32, ("k",)), "pts": (torch.float64, ("k", 2)), "w": (torch.float64, ("k", 3)),
+                 "count": (torch.int32, ()), "order": (torch.int32, ("k",)), "cand": (torch.float32, ("k", "M", 3)),
+                 "cidx": (torch.int32, ("k", "M"))}
+# ... and the fields of each record in memory order (the f64 parts first: 8-byte aligned); fit, hess and status are there with
+# gaussfit only, cov and info with cov only
+_RECORD_ORDER = {"keypoints": ("rates", "fit", "hess", "cov", "info", "kp", "boxes", "valid", "idx", "status"),
+                 "correspondences": ("pts", "w", "count", "order"),
+                 "candidates": ("rates", "cand", "boxes", "valid", "cidx")}
+_RECORD_SWITCH = {"fit": "gaussfit", "hess": "gaussfit", "status": "gaussfit", "cov": "cov", "info": "cov"}
+_NUMPY_TYPES = {torch.float64: np.dtype(np.float64), torch.float32: np.dtype(np.float32), torch.int32: np.dtype(np.int32)}
+
+
+def _dims(name, k, mm):
+    return tuple(k if d == "k" else mm if d == "M" else d for d in _RECORD_TYPES[name][1])
+
+
+def _field_bytes(name, k, mm=1):
+    """Bytes per crop of a field with k keypoints per crop and mm candidates per keypoint."""
+    return _NUMPY_TYPES[_RECORD_TYPES[name][0]].itemsize * math.prod(_dims(name, k, mm))
+
+
+def record_fields(k: int, kind: str, gaussfit: bool = False, cov: bool = False, candidates=None):
+    """The fields of a packed record in memory order, as ((name, bytes per crop), ...): kind="keypoints" the buffer of
+    net._frames_to_keypoints (rates | [fit | hess | [cov | info]] | kp | boxes | valid | idx | [status]), kind="correspondences"
+    the buffer of pack_correspondences (pts | w | count | order), kind="candidates" the buffer of net._frames_to_candidates with
+    candidates=M (rates | cand | boxes | valid | cidx).  A record is field-major, so field f of m crops takes m * bytes and
+    starts at m * (the bytes of the fields in front of it); every size is a multiple of 4.  This is the description the views
+    (record_views), the offsets (packed_layout) and the exchange of a sharded batch (parallel.gather_records,
+    esahrnet_gather_records) work from."""
+    if kind not in RECORD_KINDS:
+        raise ValueError(f"kind must be one of {RECORD_KINDS}, got {kind!r}")
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k = {k}: a record has at least one keypoint per crop")
+    if kind == "correspondences" and (gaussfit or cov):
+        raise ValueError("gaussfit and cov belong to kind='keypoints'")
     if cov and not gaussfit:
         raise ValueError("cov=True belongs to gaussfit=True")
-    if candidates is not None:
+    mm = 1
+    if kind == "candidates":
         if gaussfit:
             raise ValueError("candidates=M belongs to the get_final decoder (gaussfit=False)")
-        mm = int(candidates)
-        if not 1 <= mm <= _lib.MAX_CANDIDATES:
+        if candidates is None or not 1 <= int(candidates) <= _lib.MAX_CANDIDATES:
             raise ValueError(f"candidates must be in 1..{_lib.MAX_CANDIDATES}, got {candidates!r}")
-        parts = [("rates", 8 * m), ("cand", 12 * m * k * mm), ("boxes", 16 * m), ("valid", 4 * m), ("cidx", 4 * m * k * mm)]
-        out, off = {}, 0
-        for name, b in parts:
-            out[name] = (off, b)
-            off += b
-        out["total"] = (0, off)
-        return out
-    parts = [("rates", 8 * m)] + ([("fit", 64 * m * k), ("hess", 24 * m * k)] if gaussfit else [])
-    parts += [("cov", 24 * m * k), ("info", 24 * m * k)] if cov else []
-    parts += [("kp", 12 * m * k), ("boxes", 16 * m), ("valid", 4 * m), ("idx", 4 * m * k)]
-    parts += [("status", 4 * m * k)] if gaussfit else []
+        mm = int(candidates)
+    elif candidates is not None:
+        raise ValueError("candidates=M belongs to kind='candidates'")
+    on = {"gaussfit": gaussfit, "cov": cov, None: True}
+    return tuple((name, _field_bytes(name, k, mm)) for name in _RECORD_ORDER[kind] if on[_RECORD_SWITCH.get(name)])
+
+
+def record_views(packed, m: int, k: int, fields):
+    """The typed views of a packed record of m crops (uint8 [m * bytes per crop], laid out as `fields` = record_fields(...)
+    says): name -> tensor, e.g. kp f32 [m,k,3], rates f64 [m], order int32 [m,k], cand f32 [m,k,M,3] (M from the field's bytes).
+    `packed` a numpy uint8 array (the record copied to the host): numpy views of the same shapes and types."""
+    host = isinstance(packed, np.ndarray)
+    have, need = packed.size if host else packed.numel(), m * sum(b for _, b in fields)
+    if have != need:
+        raise ValueError(f"a record of {m} crops has {need} bytes, the buffer {have}")
     out, off = {}, 0
-    for name, b in parts:
-        out[name] = (off, b)
-        off += b
+    for name, b in fields:
+        dtype = _RECORD_TYPES[name][0]
+        shape = (m, *_dims(name, k, b // _field_bytes(name, k)))        # (b // the bytes with M = 1: M, where the field has one)
+        part = packed[off:off + m * b]
+        out[name] = part.view(_NUMPY_TYPES[dtype]).reshape(shape) if host else part.view(dtype).view(shape)
+        off += m * b
+    return out
+
+
+def record_outputs(views, packed):
+    """The views of a keypoint record (or of a candidates record: cand and cidx in kp's and idx' places) -> what
+    net._frames_to_keypoints returns: (kp, boxes, rates, valid, idx, packed[, fit, status, hess[, cov, info]])."""
+    v = views
+    rows, index = ("kp", "idx") if "kp" in v else ("cand", "cidx")
+    return (v[rows], v["boxes"], v["rates"], v["valid"], v[index], packed,
+            *(v[n] for n in ("fit", "status", "hess", "cov", "info") if n in v))
+
+
+def packed_layout(m: int, k: int, gaussfit: bool = False, cov: bool = False, candidates=None):
+    """The packed buffer of net.frames_to_keypoints' outputs: name -> (offset, bytes), the fields of record_fields(k, "keypoints",
+    gaussfit, cov) for m crops: rates f64 [m] | kp f32 [m,k,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,k]; with
+    gaussfit the decoder's f64 outputs come right behind rates (8-byte aligned) and its status last: rates | fit f64 [m,k,8] |
+    hess f64 [m,k,3] | kp | crop_boxes | valid | idx | status int32 [m,k]; with cov (gaussfit only) cov f64 [m,k,3] | info f64
+    [m,k,3] follow hess.  "total" -> (0, bytes of the buffer).  candidates=M (net.frames_to_candidates; not with gaussfit), the
+    fields of record_fields(k, "candidates", candidates=M): rates | cand f32 [m,k,M,3] | crop_boxes | valid | cidx int32 [m,k,M]."""
+    out, off = {}, 0
+    for name, b in record_fields(k, "keypoints" if candidates is None else "candidates", gaussfit, cov, candidates):
+        out[name] = (off, m * b)
+        off += m * b
     out["total"] = (0, off)
     return out
 
@@ -286,71 +352,16 @@ def packed_layout(m: int, k: int, gaussfit: bool = False, cov: bool = False, can
 def pack_correspondences(m: int, k: int, device):
     """One uint8 buffer and its views count int32 [m] | order int32 [m,k] | pts f64 [m,k,2] | w f64 [m,k,3] (pts first in
     memory: 8-byte aligned), so that a caller fetches the whole record with one copy.  -> (count, order, pts, w, packed)."""
-    sizes = (16 * m * k, 24 * m * k, 4 * m, 4 * m * k)
-    offs = [0]
-    for b in sizes:
-        offs.append(offs[-1] + b)
-    packed = torch.empty(offs[-1], dtype=torch.uint8, device=device)
-    pts = packed[offs[0]:offs[1]].view(torch.float64).view(m, k, 2)
-    w = packed[offs[1]:offs[2]].view(torch.float64).view(m, k, 3)
-    count = packed[offs[2]:offs[3]].view(torch.int32)
-    order = packed[offs[3]:offs[4]].view(torch.int32).view(m, k)
-    return count, order, pts, w, packed
-
-
-RECORD_KINDS = ("keypoints", "correspondences")
-# element type and trailing shape of every field of the two packed records (k = keypoints per crop)
-_RECORD_TYPES = {"rates": (torch.float64, ()), "fit": (torch.float64, ("k", 8)), "hess": (torch.float64, ("k", 3)),
-                 "cov": (torch.float64, ("k", 3)), "info": (torch.float64, ("k", 3)), "kp": (torch.float32, ("k", 3)),
-                 "boxes": (torch.int32, (4,)), "valid": (torch.int32, ()), "idx": (torch.int32, ("k",)),
-                 "status": (torch.int32, ("k",)), "pts": (torch.float64, ("k", 2)), "w": (torch.float64, ("k", 3)),
-                 "count": (torch.int32, ()), "order": (torch.int32, ("k",))}
-
-
-def record_fields(k: int, kind: str, gaussfit: bool = False, cov: bool = False):
-    """The fields of a packed record in memory order, as ((name, bytes per crop), ...): kind="keypoints" the buffer of
-    packed_layout(m, k, gaussfit, cov), kind="correspondences" the buffer of pack_correspondences.  A record is field-major, so
-    field f of m crops takes m * bytes and starts at m * (the bytes of the fields in front of it); every size is a multiple of 4.
-    This is the description the exchange of a sharded batch works from (parallel.gather_records, esahrnet_gather_records)."""
-    if kind not in RECORD_KINDS:
-        raise ValueError(f"kind must be one of {RECORD_KINDS}, got {kind!r}")
-    k = int(k)
-    if k < 1:
-        raise ValueError(f"k = {k}: a record has at least one keypoint per crop")
-    if kind == "correspondences":
-        if gaussfit or cov:
-            raise ValueError("gaussfit and cov belong to kind='keypoints'")
-        return (("pts", 16 * k), ("w", 24 * k), ("count", 4), ("order", 4 * k))
-    if cov and not gaussfit:
-        raise ValueError("cov=True belongs to gaussfit=True")
-    parts = [("rates", 8)] + ([("fit", 64 * k), ("hess", 24 * k)] if gaussfit else [])
-    parts += [("cov", 24 * k), ("info", 24 * k)] if cov else []
-    parts += [("kp", 12 * k), ("boxes", 16), ("valid", 4), ("idx", 4 * k)]
-    parts += [("status", 4 * k)] if gaussfit else []
-    return tuple(parts)
-
-
-def record_views(packed: torch.Tensor, m: int, k: int, fields):
-    """The typed views of a packed record of m crops (uint8 [m * bytes per crop], laid out as `fields` = record_fields(...)
-    says): name -> tensor, e.g. kp f32 [m,k,3], rates f64 [m], order int32 [m,k]."""
-    out, off = {}, 0
-    for name, b in fields:
-        dtype, tail = _RECORD_TYPES[name]
-        out[name] = packed[off:off + m * b].view(dtype).view(m, *(k if d == "k" else d for d in tail))
-        off += m * b
-    if off != packed.numel():
-        raise ValueError(f"a record of {m} crops has {off} bytes, the buffer {packed.numel()}")
-    return out
+    fields = record_fields(k, "correspondences")
+    packed = torch.empty(m * sum(b for _, b in fields), dtype=torch.uint8, device=device)
+    v = record_views(packed, m, k, fields)
+    return v["count"], v["order"], v["pts"], v["w"], packed
 
 
 def unpack_correspondences(host: np.ndarray, m: int, k: int):
     """pack_correspondences' buffer, copied to the host -> (count, order, pts, w) as numpy views."""
-    offs = np.cumsum([0, 16 * m * k, 24 * m * k, 4 * m, 4 * m * k])
-    pts = host[offs[0]:offs[1]].view(np.float64).reshape(m, k, 2)
-    w = host[offs[1]:offs[2]].view(np.float64).reshape(m, k, 3)
-    count = host[offs[2]:offs[3]].view(np.int32)
-    order = host[offs[3]:offs[4]].view(np.int32).reshape(m, k)
-    return count, order, pts, w
+    v = record_views(host, m, k, record_fields(k, "correspondences"))
+    return v["count"], v["order"], v["pts"], v["w"]
 
 
 def keypoints_to_correspondences(kp: torch.Tensor, crop_boxes: torch.Tensor, rates: torch.Tensor, valid: torch.Tensor,

@@ -20,6 +20,8 @@ import ctypes as C
 import torch
 import torch.distributed as dist
 
+from .crops import STD
+
 
 def shard_bounds(n_total: int, world_size: int, rank: int):
     """Contiguous split; the first (n_total % world_size) ranks get one extra crop."""
@@ -226,14 +228,11 @@ def _sharded_frames_to_keypoints(net, frames, det_boxes, frame_idx, group, frame
         local = net._frames_to_keypoints(frames, boxes, idx, scale, rule, refine, mean, std, pixel_format,
                                          *((cov_floor,) if cov else ()))[5]
     packed = gather_records(local, hi - lo, n_total, fields, group, device=frames.device)
-    v = inference.record_views(packed, n_total, k, fields)
-    out = (v["kp"], v["boxes"], v["rates"], v["valid"], v["idx"], packed)
-    out += (v["fit"], v["status"], v["hess"]) if gauss else ()
-    return out + ((v["cov"], v["info"]) if cov else ())
+    return inference.record_outputs(inference.record_views(packed, n_total, k, fields), packed)
 
 
 def sharded_frames_to_keypoints(net, frames, det_boxes, frame_idx=None, *, group=None, frame_base: int = 0, scale: int = 256,
-                                rule: str = "val", refine: str = "get_final", mean=None, std: float = 0.229, pixel_format=None,
+                                rule: str = "val", refine: str = "get_final", mean=None, std: float = STD, pixel_format=None,
                                 return_cov: bool = False, cov_floor: float = 1e-6):
     """net.frames_to_keypoints over the ranks of `group`: EVERY rank passes the full list of boxes (and frame indices); rank r
     runs boxes [lo_r, hi_r) (shard_bounds) through net._frames_to_keypoints, one library call, and the packed records are
@@ -271,13 +270,13 @@ def _sharded_frames_to_correspondences(net, frames, det_boxes, frame_idx, group,
     cpacked = gather_records(clocal, hi - lo, n_total, cfields, group, device=frames.device)
     packed = gather_records(klocal, hi - lo, n_total, kfields, group, device=frames.device)
     c = inference.record_views(cpacked, n_total, k, cfields)
-    v = inference.record_views(packed, n_total, k, kfields)
-    return c["count"], c["order"], c["pts"], c["w"], v["kp"], v["boxes"], v["rates"], v["valid"], cpacked, packed
+    out = inference.record_outputs(inference.record_views(packed, n_total, k, kfields), packed)
+    return (c["count"], c["order"], c["pts"], c["w"], *out[:4], cpacked, packed)
 
 
 def sharded_frames_to_correspondences(net, frames, det_boxes, frame_idx=None, *, group=None, frame_base: int = 0,
                                       scale: int = 256, rule: str = "val", refine: str = "get_final", thresh: float = 0.8,
-                                      min_k: int = 24, weights: str = "peak", mean=None, std: float = 0.229, pixel_format=None,
+                                      min_k: int = 24, weights: str = "peak", mean=None, std: float = STD, pixel_format=None,
                                       cov_floor: float = 1e-6):
     """net.frames_to_correspondences over the ranks of `group`, under the contract of sharded_frames_to_keypoints (full box
     list on every rank, rank r runs boxes [lo_r, hi_r), frame_idx=None and frame_base as there): -> (count int32 [m], order

@@ -180,111 +180,122 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
                                  "heat-map path (get_final) and solved by the native entry")
     if want and not native:
         raise ValueError("return_report and the max_rms_px / min_inliers gates read the native solver's report (native=False has none)")
-
-    def finish(poses, rep):
-        if want:
-            poses = _gated_poses(poses, rep, max_rms_px, min_inliers)
-        poses = _checked_poses(poses, on_fail)
-        return (poses, rep) if return_report else poses
-
     if weights != "peak" and not device_select:
         raise ValueError(f"weights='{weights}' belongs to device_select=True (the host selection weighs by the peak)")
+    if device_select and not native:
+        raise ValueError("device_select=True hands its record to the native solver (native=False has no entry for it)")
+
+    # the solve on decoded rows, solve(rows, boxes, rates) -> (poses, report or None); the paths differ in where the rows come from
+    def keypoint_poses(kp, boxes, rates):
+        poses = poses_from_keypoints(kp, boxes, rates, kp3d, K, thresh, min_k, pool, native, threads, report=want)
+        return poses if want else (poses, None)
+
+    def candidate_poses(cand, boxes, rates):
+        q, t, _, *rep = pnp.candidates_to_pose_batch(cand, kp3d, np.asarray(K, np.float64), [(b[0], b[1]) for b in boxes], rates,
+                                                     thresh, min_k, min_ratio, threads, report=want)
+        return [(q[i], t[i]) for i in range(len(boxes))], rep[0] if want else None
+
+    solve = keypoint_poses if candidates == 1 else candidate_poses
     if device_select:
-        if not native:
-            raise ValueError("device_select=True hands its record to the native solver (native=False has no entry for it)")
-        with torch.no_grad():
-            if distributed:                 # every rank its shard of the boxes, then the two records gathered: all poses on all ranks
-                out = parallel._sharded_frames_to_correspondences(net, frames, bboxes, frame_idx, None, 0, scale, rule, refine,
-                                                                  thresh, min_k, weights, None, crops.STD, None, cov_floor)
-            elif weights == "covariance":
-                out = net._frames_to_correspondences(frames, bboxes, frame_idx, scale, rule, refine, thresh, min_k, weights, None,
-                                                     crops.STD, None, cov_floor)
-            else:
-                out = net._frames_to_correspondences(frames, bboxes, frame_idx, scale, rule, refine, thresh, min_k, weights, None,
-                                                     crops.STD, None)
-        m, k = out[4].shape[:2]
-        count, order, pts, w = inference.unpack_correspondences(out[8].cpu().numpy(), m, k)     # the only device->host copy
-        q, t, *rep = pnp.correspondences_to_pose_batch(pts, w, count, order, kp3d, np.asarray(K, np.float64), threads, report=want)
-        return finish([(q[i], t[i]) for i in range(m)], rep[0] if want else None)
-    if device_loader:
-        with torch.no_grad():
-            if distributed:
-                out = parallel._sharded_frames_to_keypoints(net, frames, bboxes, frame_idx, None, 0, scale, rule, refine, None,
-                                                            crops.STD, None)
-            else:
-                out = net._frames_to_keypoints(frames, bboxes, frame_idx, scale, rule, refine, None, crops.STD, None)
-        m, k = out[0].shape[:2]
-        host = out[5].cpu().numpy()                         # the only device->host copy
-        lay = inference.packed_layout(m, k, refine == "gaussfit")
-        rates, kp, boxes, valid = (host[lay[name][0]:lay[name][0] + lay[name][1]] for name in ("rates", "kp", "boxes", "valid"))
-        rates = rates.view(np.float64)
-        kp = kp.view(np.float32).reshape(m, k, 3)
-        boxes = boxes.view(np.int32).reshape(m, 4).tolist()
-        valid = valid.view(np.int32)
-        # an invalid crop (NaN keypoint rows) is kept away from the solver and reported as the NaN row that "no solution" is
-        bad = valid == 0
-        rates = [1.0 if b else float(r) for r, b in zip(rates, bad)]
-        poses = poses_from_keypoints(np.where(bad[:, None, None], np.float32(0), kp), boxes, rates, kp3d, K, thresh, min_k,
-                                     pool, native, threads, report=want)
-        rep = None
-        if want:
-            poses, rep = poses
-            if bad.any():                                   # no crop, no correspondences: the row of "fewer than 4", with n = 0
-                raw = rep.raw.copy()
-                raw[bad] = np.nan
-                raw[bad, 0], raw[bad, 2] = 1.0, 0.0
-                rep = pnp.PoseReport(raw)
-        poses = [(np.full(4, np.nan), np.full(3, np.nan)) if b else p for p, b in zip(poses, bad)]
-        return finish(poses, rep)
-    if candidates != 1 and candidates_path == "loader":
-        with torch.no_grad():
-            out = net._frames_to_candidates(frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, None, crops.STD, None)
-        m, k, mm = out[0].shape[:3]
-        host = out[5].cpu().numpy()                         # the only device->host copy
-        lay = inference.packed_layout(m, k, candidates=mm)
-        rates, cand, boxes, valid = (host[lay[name][0]:lay[name][0] + lay[name][1]] for name in ("rates", "cand", "boxes", "valid"))
-        cand = cand.view(np.float32).reshape(m, k, mm, 3)
-        boxes = boxes.view(np.int32).reshape(m, 4).tolist()
-        bad = valid.view(np.int32) == 0
-        # an invalid crop (NaN candidate rows) is kept away from the solver and reported as the NaN row that "no solution" is
-        rates = [1.0 if b else float(r) for r, b in zip(rates.view(np.float64), bad)]
-        q, t, _, *rep = pnp.candidates_to_pose_batch(np.where(bad[:, None, None, None], np.float32(0), cand), kp3d,
-                                                     np.asarray(K, np.float64), [(b[0], b[1]) for b in boxes], rates, thresh, min_k,
-                                                     min_ratio, threads, report=want)
-        rep = rep[0] if want else None
-        if want and bad.any():                              # no crop, no correspondences: the row of "fewer than 4", with n = 0
-            raw = rep.raw.copy()
-            raw[bad] = np.nan
-            raw[bad, 0], raw[bad, 2] = 1.0, 0.0
-            fixed = pnp.PoseReport(raw)
+        poses, rep = _device_select_poses(net, frames, bboxes, frame_idx, distributed, scale, rule, refine, thresh, min_k, weights,
+                                          cov_floor, kp3d, K, threads, want)
+    elif device_loader:
+        poses, rep = _device_loader_poses(net, frames, bboxes, frame_idx, distributed, scale, rule, refine, solve)
+    elif candidates != 1 and candidates_path == "loader":
+        poses, rep = _loader_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, solve)
+    else:
+        poses, rep = _host_crops_poses(net, frames, bboxes, frame_idx, scale, rule, refine, distributed, keypoints_only,
+                                       candidates, nms_radius, candidates_path, solve)
+    if want:
+        poses = _gated_poses(poses, rep, max_rms_px, min_inliers)
+    poses = _checked_poses(poses, on_fail)
+    return (poses, rep) if return_report else poses
+
+
+def _fetch(packed, m, k, fields):
+    """A path's only device->host copy: the packed record of m crops, and its numpy views (inference.record_views)."""
+    return inference.record_views(packed.cpu().numpy(), m, k, fields)
+
+
+def _solve_valid_crops(rows, v, solve):
+    """solve(rows, boxes, rates) -> (poses, report or None) on the rows (kp [m,K,3] or cand [m,K,M,3]) of a loader's fetched
+    record `v`, with the crops the loader could not make (valid == 0: NaN rows) kept away from it: their rows go in as zeros with
+    rate 1.0, their poses come back as the NaN row that "no solution" is, their report rows are those of "fewer than 4" with
+    n = 0 (status 1, the rest NaN), and in a candidates report no keypoint of theirs entered a solve (.used -1, .rescued False)."""
+    bad = v["valid"] == 0
+    rates = [1.0 if b else float(r) for r, b in zip(v["rates"], bad)]
+    poses, rep = solve(np.where(bad.reshape(-1, *[1] * (rows.ndim - 1)), np.float32(0), rows), v["boxes"].tolist(), rates)
+    if rep is not None and bad.any():
+        raw = rep.raw.copy()
+        raw[bad] = np.nan
+        raw[bad, 0], raw[bad, 2] = 1.0, 0.0
+        fixed = pnp.PoseReport(raw)
+        if rep.used is not None:
             fixed.used, fixed.rescued = rep.used.copy(), rep.rescued.copy()
-            fixed.used[bad], fixed.rescued[bad] = -1, False     # no keypoint of such an image entered a solve
-            rep = fixed
-        return finish([(np.full(4, np.nan), np.full(3, np.nan)) if b else (q[i], t[i]) for i, b in enumerate(bad)], rep)
+            fixed.used[bad], fixed.rescued[bad] = -1, False
+        rep = fixed
+    return [(np.full(4, np.nan), np.full(3, np.nan)) if b else p for p, b in zip(poses, bad)], rep
+
+
+def _device_select_poses(net, frames, bboxes, frame_idx, distributed, scale, rule, refine, thresh, min_k, weights, cov_floor, kp3d, K,
+                         threads, want):
+    """device_select=True."""
+    with torch.no_grad():
+        if distributed:                     # every rank its shard of the boxes, then the two records gathered: all poses on all ranks
+            out = parallel._sharded_frames_to_correspondences(net, frames, bboxes, frame_idx, None, 0, scale, rule, refine, thresh,
+                                                              min_k, weights, None, crops.STD, None, cov_floor)
+        else:
+            out = net._frames_to_correspondences(frames, bboxes, frame_idx, scale, rule, refine, thresh, min_k, weights, None,
+                                                 crops.STD, None, cov_floor)
+    m, k = out[4].shape[:2]
+    v = _fetch(out[8], m, k, inference.record_fields(k, "correspondences"))
+    q, t, *rep = pnp.correspondences_to_pose_batch(v["pts"], v["w"], v["count"], v["order"], kp3d, np.asarray(K, np.float64), threads,
+                                                   report=want)
+    return [(q[i], t[i]) for i in range(m)], rep[0] if want else None
+
+
+def _device_loader_poses(net, frames, bboxes, frame_idx, distributed, scale, rule, refine, solve):
+    """device_loader=True."""
+    with torch.no_grad():
+        if distributed:
+            out = parallel._sharded_frames_to_keypoints(net, frames, bboxes, frame_idx, None, 0, scale, rule, refine, None,
+                                                        crops.STD, None)
+        else:
+            out = net._frames_to_keypoints(frames, bboxes, frame_idx, scale, rule, refine, None, crops.STD, None)
+    m, k = out[0].shape[:2]
+    v = _fetch(out[5], m, k, inference.record_fields(k, "keypoints", refine == "gaussfit"))
+    return _solve_valid_crops(v["kp"], v, solve)
+
+
+def _loader_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, solve):
+    """candidates > 1 with candidates_path="loader"."""
+    with torch.no_grad():
+        out = net._frames_to_candidates(frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, None, crops.STD, None)
+    m, k, mm = out[0].shape[:3]
+    v = _fetch(out[5], m, k, inference.record_fields(k, "candidates", candidates=mm))
+    return _solve_valid_crops(v["cand"], v, solve)
+
+
+def _host_crops_poses(net, frames, bboxes, frame_idx, scale, rule, refine, distributed, keypoints_only, candidates, nms_radius,
+                      candidates_path, solve):
+    """Crops made by crops.crop_batch: the keypoint form, and candidates > 1 with candidates_path "heatmaps" or "fused"."""
     if frame_idx is not None or rule != "val":
         raise ValueError("frame_idx and rule belong to device_loader=True (crops.crop_batch: one val box per frame)")
     rk = {} if refine == "get_final" else {"refine": refine}
     x, boxes, rates = crops.crop_batch(frames, bboxes, scale)
-    if candidates != 1:
-        with torch.no_grad():
-            if candidates_path == "fused":
-                cand = net.candidates(x, candidates, nms_radius)
-            else:
-                cand = inference.heatmaps_to_candidates(net(x), candidates, nms_radius)
-        cand = cand.cpu().numpy()                           # the only device->host copy: N*K*M*3 floats
-        q, t, _, *rep = pnp.candidates_to_pose_batch(cand, kp3d, np.asarray(K, np.float64), [(b[0], b[1]) for b in boxes], rates,
-                                                     thresh, min_k, min_ratio, threads, report=want)
-        return finish([(q[i], t[i]) for i in range(len(boxes))], rep[0] if want else None)
     with torch.no_grad():
-        if distributed:
-            kp = parallel.sharded_keypoints(net, x, keypoints_only=keypoints_only, **rk)
+        if candidates != 1 and candidates_path == "fused":
+            rows = net.candidates(x, candidates, nms_radius)
+        elif candidates != 1:
+            rows = inference.heatmaps_to_candidates(net(x), candidates, nms_radius)
+        elif distributed:
+            rows = parallel.sharded_keypoints(net, x, keypoints_only=keypoints_only, **rk)
         elif keypoints_only:
-            kp = net(x, output="keypoints", **rk)
+            rows = net(x, output="keypoints", **rk)
         else:
-            kp = inference.heatmaps_to_keypoints(net(x), **rk)
-    kp = kp.cpu().numpy()                                   # the only device->host copy: N*K*3 floats
-    poses = poses_from_keypoints(kp, boxes, rates, kp3d, K, thresh, min_k, pool, native, threads, report=want)
-    return finish(*poses) if want else finish(poses, None)
+            rows = inference.heatmaps_to_keypoints(net(x), **rk)
+    rows = rows.cpu().numpy()                               # the only device->host copy: N*K*3 floats (N*K*M*3 with candidates)
+    return solve(rows, boxes, rates)
 
 
 def _gated_poses(poses, rep, max_rms_px, min_inliers):

@@ -153,3 +153,60 @@ def test_rccl_world_size_1_drives_the_sharded_device_path(env, monkeypatch):
         assert _same_poses(pipeline.estimate_poses(*args, distributed=True, device_loader=True, **pkw), want_loader)
     finally:
         dist.destroy_process_group()
+
+
+# ---- 4. the loader's outputs lie in `packed` where the record says -------------------------------------------------------------
+# The record of each form written out here, field by field in memory order (name, element type, shape for m crops of K keypoints),
+# so that the offsets below are counted from this statement and not from inference's table.
+F64, F32, I32 = torch.float64, torch.float32, torch.int32
+
+
+def _keypoint_record(m, k, gauss=False, cov=False):
+    rec = [("rates", F64, (m,))]
+    rec += [("fit", F64, (m, k, 8)), ("hess", F64, (m, k, 3))] if gauss else []
+    rec += [("cov", F64, (m, k, 3)), ("info", F64, (m, k, 3))] if cov else []
+    rec += [("kp", F32, (m, k, 3)), ("boxes", I32, (m, 4)), ("valid", I32, (m,)), ("idx", I32, (m, k))]
+    return rec + ([("status", I32, (m, k))] if gauss else [])
+
+
+KP = ("kp", "boxes", "rates", "valid", "idx")
+# form -> (the net's call, its arguments behind (frames, BOXES, FIDX, SCALE, "val"), the record, record_fields' arguments behind k,
+# which packed_layout takes behind (m, k), the fields in the order the call returns them, `packed` left out)
+VIEW_FORMS = {
+    "get_final": ("_frames_to_keypoints", ("get_final", None, 0.229, None), _keypoint_record, ("keypoints", False, False, None), KP),
+    "get_final2": ("_frames_to_keypoints", ("get_final2", None, 0.229, None), _keypoint_record, ("keypoints", False, False, None), KP),
+    "gaussfit": ("_frames_to_keypoints", ("gaussfit", None, 0.229, None), lambda m, k: _keypoint_record(m, k, True),
+                 ("keypoints", True, False, None), KP + ("fit", "status", "hess")),
+    "gaussfit+cov": ("_frames_to_keypoints", ("gaussfit", None, 0.229, None, 1e-6), lambda m, k: _keypoint_record(m, k, True, True),
+                     ("keypoints", True, True, None), KP + ("fit", "status", "hess", "cov", "info")),
+    "candidates=3": ("_frames_to_candidates", (3, 6, None, 0.229, None),
+                     lambda m, k: [("rates", F64, (m,)), ("cand", F32, (m, k, 3, 3)), ("boxes", I32, (m, 4)), ("valid", I32, (m,)),
+                                   ("cidx", I32, (m, k, 3))],
+                     ("candidates", False, False, 3), ("cand", "boxes", "rates", "valid", "cidx")),
+}
+
+
+@pytest.mark.parametrize("form", list(VIEW_FORMS))
+def test_loader_outputs_are_the_views_of_the_field_table(env, form):
+    inf, net, frames = env["inference"], env["net"], env["frames"]
+    call, rest, record, desc, names = VIEW_FORMS[form]
+    m, k = len(BOXES), net.num_keypoints
+    with torch.no_grad():
+        out = getattr(net, call)(frames, BOXES, FIDX, SCALE, "val", *rest)
+    torch.cuda.synchronize()
+    packed, returned = out[5], dict(zip(names, out[:5] + out[6:]))
+    assert len(out) == len(names) + 1 and packed.dtype == torch.uint8 and packed.dim() == 1
+    fields = inf.record_fields(k, *desc)
+    views = inf.record_views(packed, m, k, fields)
+    host = inf.record_views(packed.cpu().numpy(), m, k, fields)
+    off = 0
+    for name, dtype, shape in record(m, k):
+        for t in (returned.pop(name), views.pop(name)):                 # what the call returns, and what record_views makes of `packed`
+            assert t.data_ptr() - packed.data_ptr() == off and t.dtype == dtype and tuple(t.shape) == shape, (form, name)
+            assert t.is_contiguous()
+        a, t = host.pop(name), t.cpu().numpy()
+        assert a.shape == shape and a.dtype == t.dtype and a.tobytes() == t.tobytes(), (form, name)
+        off += t.nbytes
+    assert not returned and not views and not host                      # every field, and nothing else
+    assert off == packed.numel() == inf.packed_layout(m, k, *desc[1:])["total"][1]
+    assert out[3].tolist() == [1, 1, 0, 1, 1]                           # position 2: the empty box

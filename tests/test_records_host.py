@@ -46,6 +46,35 @@ def test_record_fields_rebuild_both_layouts(m, k):
     again = inference.record_views(packed, m, k, fields)
     for name, t in (("count", count), ("order", order), ("pts", pts), ("w", w)):
         assert again[name].data_ptr() == t.data_ptr() and again[name].shape == t.shape and again[name].dtype == t.dtype
+    # the candidates form: the third kind against the third layout
+    forms = [fields] + [inference.record_fields(k, "keypoints", gaussfit, cov) for gaussfit, cov in LAYOUTS]
+    for M in (1, 2, 3, 4):
+        lay = inference.packed_layout(m, k, candidates=M)
+        fields = inference.record_fields(k, "candidates", candidates=M)
+        assert [n for n, _ in fields] == [n for n in lay if n != "total"] == ["rates", "cand", "boxes", "valid", "cidx"]
+        off = 0
+        for name, b in fields:
+            assert b > 0 and b % 4 == 0
+            assert lay[name] == (off, m * b), (name, M)
+            off += m * b
+        assert lay["total"] == (0, off)
+        forms.append(fields)
+    # the numpy form of the views, all three kinds: the offsets, shapes and types of the torch views, on the same bytes
+    for fields in forms:
+        packed = torch.randint(0, 256, (m * sum(b for _, b in fields),), dtype=torch.uint8, generator=torch.Generator().manual_seed(k))
+        host = packed.numpy().copy()
+        tv, nv = inference.record_views(packed, m, k, fields), inference.record_views(host, m, k, fields)
+        assert list(tv) == list(nv) == [n for n, _ in fields]
+        for name, t in tv.items():
+            a = nv[name]
+            assert isinstance(a, np.ndarray) and np.shares_memory(a, host)                        # a view, no copy
+            assert a.ctypes.data - host.ctypes.data == t.data_ptr() - packed.data_ptr()
+            assert a.shape == tuple(t.shape) and a.dtype == t.numpy().dtype and a.tobytes() == t.numpy().tobytes()
+        if "cand" in tv:
+            M = fields[1][1] // (12 * k)
+            assert tv["cand"].shape == (m, k, M, 3) and tv["cidx"].shape == (m, k, M)             # M from the field's bytes
+        with pytest.raises(ValueError, match="bytes"):
+            inference.record_views(host[:-4], m, k, fields)
 
 
 def test_record_fields_refuses_what_the_layouts_refuse():
