@@ -106,8 +106,8 @@ struct StemParams {
 };
 int launch_stem(const StemParams& p, hipStream_t stream);
 // the same convolution + the per-channel (sum, max) of the output over slabs of pixels, in pool_partial's layout
-// [N][slabs][cout][2] (cbam.hip); stem_pool_slabs: slabs per image, 0 = not available (needs cin 1, cout 64).  FMT_BF: the
-// partials are of the bf16-rounded values the tensor holds
+// [N][slabs][cout][2] (cbam.hip); stem_pool_slabs: slabs per image, 0 = not available (needs cin 1, cout 64).  The partials
+// are of the values the tensor holds (FMT_BF: rounded to bf16; FMT_SB: hi + lo)
 int stem_pool_slabs(int cin, int cout, int H, int W);
 int launch_stem_pool(const StemParams& p, float* pool, hipStream_t stream);
 

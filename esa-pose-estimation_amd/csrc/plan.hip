@@ -2727,6 +2727,13 @@ int esahrnet_op_fuse_ex(const void* const* xs_dev, const int* hs, const int* ws,
 int esahrnet_op_cbam(const void* x_dev, const void* res_dev, int n, int c, int height, int width, const float* w_fc0,
                      const float* w_fc2, const float* w_sa, int relu, void* y_dev, int cy, int c0, int fused, int precision,
                      esahrnet_stream stream_) {
+    return esahrnet_op_cbam_steps(x_dev, res_dev, n, c, height, width, w_fc0, w_fc2, w_sa, relu, y_dev, cy, c0, fused, precision,
+                                  0, nullptr, nullptr, nullptr, stream_);
+}
+
+int esahrnet_op_cbam_steps(const void* x_dev, const void* res_dev, int n, int c, int height, int width, const float* w_fc0,
+                           const float* w_fc2, const float* w_sa, int relu, void* y_dev, int cy, int c0, int fused, int precision,
+                           int slabs, void* partial_out, void* ca_out, void* maps_out, esahrnet_stream stream_) {
     if (!x_dev || !w_fc0 || !w_fc2 || !w_sa || !y_dev || n <= 0 || height <= 0 || width <= 0) return fail("op_cbam: bad argument");
     if (precision < 0 || precision > 2) return fail("op_cbam: precision %d", precision);
     if (c < 16 || (c & 7)) return fail("op_cbam: c=%d (a multiple of 8, at least 16: ChannelAttention's ratio)", c);
@@ -2734,9 +2741,14 @@ int esahrnet_op_cbam(const void* x_dev, const void* res_dev, int n, int c, int h
     const int fmt = bf ? esa::FMT_BF : precision == 2 ? esa::FMT_F32 : esa::FMT_SB;
     const int eb = bf ? 2 : 4;
     const int cp = bf ? pad64(c) : pad32(c), cyp = bf ? pad64(cy) : pad32(cy);
+    if (cp > 512) return fail("op_cbam: c=%d is %d channels padded, ca_mlp serves at most 512", c, cp);
     if (c0 < 0 || (c0 & 7) || c0 + cp > cyp) return fail("op_cbam: slice [%d, %d) outside the %d channels of y", c0, c0 + cp, cyp);
     if (fused && !esa::cbam_spatial_supported(cp)) return fail("op_cbam: cbam_spatial does not serve %d channels", cp);
-    const int cr = c / 16, hw = height * width, P = std::min(Builder::POOL_SLABS, hw);
+    if (fused && maps_out) return fail("op_cbam: maps_out with fused = 1 (cbam_spatial keeps the maps in LDS)");
+    if ((long long)height * width > 0x7fffffffLL / n) return fail("op_cbam: %d x %d x %d pixels", n, height, width);
+    const int cr = c / 16, hw = height * width;
+    if (slabs < 0 || slabs > std::min(1024, hw)) return fail("op_cbam: slabs=%d (0, or 1 .. min(1024, %d pixels))", slabs, hw);
+    const int P = slabs ? slabs : std::min(Builder::POOL_SLABS, hw);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const std::vector<float> h0(w_fc0, w_fc0 + (size_t)cr * c), h2(w_fc2, w_fc2 + (size_t)c * cr), hs(w_sa, w_sa + 98);
     void *xs = nullptr, *rs = nullptr, *ys = nullptr, *part = nullptr, *ca = nullptr, *maps = nullptr, *w0 = nullptr,
@@ -2744,9 +2756,11 @@ int esahrnet_op_cbam(const void* x_dev, const void* res_dev, int n, int c, int h
     auto cleanup = [&]() { for (void* p : {xs, rs, ys, part, ca, maps, w0, w2, wsa}) if (p) (void)hipFree(p); };
     if (upload(h0, &w0) || upload(h2, &w2) || upload(hs, &wsa)) { cleanup(); return 1; }
     const size_t npix = (size_t)n * hw;
+    const size_t part_bytes = (size_t)n * P * cp * 2 * sizeof(float), ca_bytes = (size_t)n * cp * sizeof(float),
+                 maps_bytes = npix * 2 * sizeof(float);
     if (hipMalloc(&xs, npix * cp * eb) != hipSuccess || (res_dev && hipMalloc(&rs, npix * cp * eb) != hipSuccess) ||
-        hipMalloc(&ys, npix * cyp * eb) != hipSuccess || hipMalloc(&part, (size_t)n * P * cp * 2 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&ca, (size_t)n * cp * sizeof(float)) != hipSuccess || hipMalloc(&maps, npix * 2 * sizeof(float)) != hipSuccess) {
+        hipMalloc(&ys, npix * cyp * eb) != hipSuccess || hipMalloc(&part, part_bytes) != hipSuccess ||
+        hipMalloc(&ca, ca_bytes) != hipSuccess || hipMalloc(&maps, maps_bytes) != hipSuccess) {
         cleanup();
         return fail("op_cbam: hipMalloc failed");
     }
@@ -2764,10 +2778,54 @@ int esahrnet_op_cbam(const void* x_dev, const void* res_dev, int n, int c, int h
     if (!rc && !fused) rc = esa::launch_cbam_maps(ap.x, ap.ca, static_cast<float*>(maps), n, hw, c, cp, stream, fmt);
     if (!rc && !fused) rc = esa::launch_cbam_apply(ap, stream);
     if (!rc) rc = esa::launch_fmt_to_nchw(fmt, static_cast<const char*>(ys), n, cy, height, width, cyp, static_cast<float*>(y_dev), stream);
+    hipError_t ce = hipSuccess;         // the steps' own buffers, as the kernels left them
+    if (!rc && partial_out) ce = hipMemcpyAsync(partial_out, part, part_bytes, hipMemcpyDeviceToDevice, stream);
+    if (!rc && ce == hipSuccess && ca_out) ce = hipMemcpyAsync(ca_out, ca, ca_bytes, hipMemcpyDeviceToDevice, stream);
+    if (!rc && ce == hipSuccess && maps_out) ce = hipMemcpyAsync(maps_out, maps, maps_bytes, hipMemcpyDeviceToDevice, stream);
     hipError_t se = hipStreamSynchronize(stream);
     cleanup();
     if (rc) return fail("op_cbam: launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (ce != hipSuccess) return fail("op_cbam: copying a step's output: %s", hipGetErrorString(ce));
     if (se != hipSuccess) return fail("op_cbam: %s", hipGetErrorString(se));
+    return 0;
+}
+
+int esahrnet_op_stem(const void* x_dev, int n, int height, int width, const float* w, const float* b, int relu, int pooled,
+                     int precision, void* y_dev, void* partial_out, int* slabs_out, esahrnet_stream stream_) {
+    if (!x_dev || !w || !b || !y_dev || n <= 0 || height <= 0 || width <= 0) return fail("op_stem: bad argument");
+    if (precision < 0 || precision > 2) return fail("op_stem: precision %d (0, 1 or 2)", precision);
+    if ((long long)height * width > 0x7fffffffLL / 64 / n) return fail("op_stem: %d x %d x %d pixels", n, height, width);
+    constexpr int cout = 64;            // padded alike in every format
+    const int slabs = pooled ? esa::stem_pool_slabs(1, cout, height, width) : 0;
+    if (pooled && (!partial_out || !slabs_out)) return fail("op_stem: pooled = 1 needs partial_out and slabs_out");
+    if (pooled && slabs <= 0) return fail("op_stem: launch_stem_pool does not serve %d x %d", height, width);
+    const bool bf = precision == 1;
+    const int fmt = bf ? esa::FMT_BF : precision == 2 ? esa::FMT_F32 : esa::FMT_SB;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    std::vector<float> wp((size_t)cout * 9, 0.f), bp(b, b + cout);          // [cout/8][1][9][8], as esahrnet_commit packs conv1
+    for (int co = 0; co < cout; ++co)
+        for (int t = 0; t < 9; ++t) wp[((size_t)(co >> 3) * 9 + t) * 8 + (co & 7)] = w[(size_t)co * 9 + t];
+    void *dw = nullptr, *db = nullptr, *ys = nullptr, *part = nullptr;
+    auto cleanup = [&]() { for (void* p : {dw, db, ys, part}) if (p) (void)hipFree(p); };
+    if (upload(wp, &dw) || upload(bp, &db)) { cleanup(); return 1; }
+    const size_t part_bytes = (size_t)n * slabs * cout * 2 * sizeof(float);
+    if (hipMalloc(&ys, (size_t)n * height * width * cout * (bf ? 2 : 4)) != hipSuccess ||
+        (pooled && hipMalloc(&part, part_bytes) != hipSuccess)) {
+        cleanup();
+        return fail("op_stem: hipMalloc failed");
+    }
+    esa::StemParams p{static_cast<const float*>(x_dev), static_cast<char*>(ys), static_cast<const float*>(dw),
+                      static_cast<const float*>(db), n, height, width, 1, cout, relu ? 1 : 0, fmt};
+    int rc = pooled ? esa::launch_stem_pool(p, static_cast<float*>(part), stream) : esa::launch_stem(p, stream);
+    if (!rc) rc = esa::launch_fmt_to_nchw(fmt, static_cast<const char*>(ys), n, cout, height, width, cout, static_cast<float*>(y_dev), stream);
+    hipError_t ce = hipSuccess;
+    if (!rc && pooled) ce = hipMemcpyAsync(partial_out, part, part_bytes, hipMemcpyDeviceToDevice, stream);
+    hipError_t se = hipStreamSynchronize(stream);
+    cleanup();
+    if (rc) return fail("op_stem: launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (ce != hipSuccess) return fail("op_stem: copying the partials: %s", hipGetErrorString(ce));
+    if (se != hipSuccess) return fail("op_stem: %s", hipGetErrorString(se));
+    if (pooled) *slabs_out = slabs;
     return 0;
 }
 

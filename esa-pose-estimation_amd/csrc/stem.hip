@@ -87,7 +87,7 @@ constexpr int STEM_PX = 8;
 // block also reduces its 8 x (256 / G) pixels per channel into slab `y * gridDim.x + blockIdx.x` of `pool` — the layout
 // pool_partial_kernel writes (cbam.hip), so that kernel's 537 MB read of the tensor just written is not needed.
 // BFQ (bf16 mode, stem1_pool_bf_kernel): the outputs are rounded to bf16 first, so that the partials are those of the
-// values the BF tensor holds — what pool_partial would compute from it.
+// values the BF tensor holds — what pool_partial would compute from it.  The split format does the same with its hi + lo.
 // HF: y is an HF tensor (fp16 mode), see stem_kernel
 template <bool POOL, bool BFQ, bool HF = false>
 __device__ __forceinline__ void stem1_body(const StemParams& p, int xgroups, long long total, float* pool, float* psum, float* pmax) {
@@ -152,9 +152,19 @@ __device__ __forceinline__ void stem1_body(const StemParams& p, int xgroups, lon
         }
         if (BFQ) unpack8_bf16(pack8_bf16(acc), acc);
         if (x >= p.W || !live) continue;
+        // split format: the partials are those of the values the SB tensor holds (hi + lo), as in the bf16 mode — pool_partial
+        // reading the tensor back finds these, not the f32 accumulators (they differ by up to 2^-17 relative)
         if (POOL) {
+            float pv[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) { ps[i] += acc[i]; pm[i] = fmaxf(pm[i], acc[i]); }
+            for (int i = 0; i < 8; ++i) pv[i] = acc[i];
+            if (!BFQ && p.fmt == FMT_SB) {
+                uint4 h, l;
+                split8(acc, h, l);
+                join8(h, l, pv);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { ps[i] += pv[i]; pm[i] = fmaxf(pm[i], pv[i]); }
         }
         if (HF) {
             *reinterpret_cast<uint4*>(p.y + (((size_t)(n * p.H + y) * p.W + x) * p.cout) * 2 + c8 * 16) = pack8_f16(acc);
@@ -170,6 +180,9 @@ __device__ __forceinline__ void stem1_body(const StemParams& p, int xgroups, lon
             char* o = p.y + (((size_t)(n * p.H + y) * p.W + x) * p.cout) * 4 + c8 * 32;
             *reinterpret_cast<uint4*>(o) = hi;
             *reinterpret_cast<uint4*>(o + 16) = lo;
+            // gfx950 reads a 16-byte store's data late; with the pooled values in flight hipcc reuses lo's registers one
+            // wait state behind the branch that follows, unpadded (tests/test_isa_hazards.py)
+            if (POOL) asm volatile("s_nop 1");
         }
     }
     if (POOL) {

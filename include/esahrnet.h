@@ -609,6 +609,29 @@ int esahrnet_op_fuse_ex(const void* const* xs_dev, const int* hs, const int* ws,
 int esahrnet_op_cbam(const void* x_dev, const void* res_dev, int n, int c, int height, int width, const float* w_fc0,
                      const float* w_fc2, const float* w_sa, int relu, void* y_dev, int cy, int c0, int fused, int precision,
                      esahrnet_stream stream);
+/* esahrnet_op_cbam with its steps shown (esahrnet_op_cbam is this call with slabs = 0 and the three outputs NULL): the same
+ * launches, and afterwards the buffers the steps left, copied to optional DEVICE outputs.
+ *   slabs        0: the plan's rule P = min(64, height * width); otherwise P itself, 1 <= P <= min(1024, height * width) —
+ *                pool_partial and ca_mlp at the slab counts the pooling stem produces.  Slab s of an image holds the pixels
+ *                [s * S, min(HW, s * S + S)), S = ceil(HW / P), in row-major order; a slab past the last pixel holds (0, -inf).
+ *   partial_out  f32 [n][P][C'][2]: (sum, max) of every channel over every slab (pool_partial)
+ *   ca_out       f32 [n][C']: the channel attention (ca_mlp), zero in the padding channels
+ *   maps_out     f32 [n][height][width][2]: (mean, max) over the c real channels of ca * x (cbam_maps); with fused = 1 the maps
+ *                never leave the workgroup, and passing maps_out is refused.
+ * C' = c padded (32; bf16: 64) and at most 512 (ca_mlp's limit).  Every argument is checked before anything is enqueued.
+ * Synchronous; test use only. */
+int esahrnet_op_cbam_steps(const void* x_dev, const void* res_dev, int n, int c, int height, int width, const float* w_fc0,
+                           const float* w_fc2, const float* w_sa, int relu, void* y_dev, int cy, int c0, int fused, int precision,
+                           int slabs, void* partial_out, void* ca_out, void* maps_out, esahrnet_stream stream);
+/* conv1 of the stem on its own, cin = 1 and cout = 64: y = [relu]( conv3x3_pad1(x; w) + b ) in the format of `precision`
+ * (0, 1 or 2), converted back exactly to f32 NCHW.  x_dev: f32 [n][1][height][width]; w [64][1][3][3] and b [64]: host f32,
+ * packed as esahrnet_commit packs conv1; y_dev: f32 [n][64][height][width].  pooled = 0: launch_stem.  pooled = 1:
+ * launch_stem_pool, which also leaves the per-channel (sum, max) of its output over slabs of pixels: partial_out (device) f32
+ * [n][slabs][64][2] and *slabs_out = height * ceil(width / 256), both required then.  Slab `row * pieces + piece`, pieces =
+ * ceil(width / 256), holds the pixels [256 * piece, min(width, 256 * piece + 256)) of that row; in the bf16 format the partials
+ * are those of the rounded values y holds.  Checked before anything is enqueued; synchronous; test use only. */
+int esahrnet_op_stem(const void* x_dev, int n, int height, int width, const float* w, const float* b, int relu, int pooled,
+                     int precision, void* y_dev, void* partial_out, int* slabs_out, esahrnet_stream stream);
 /* resample_slice on its own, in the format of `precision` (0, 1 or 2; 3 is refused: the kernel does not serve fp16):
  * y[:, c0 : c0 + c] = bilinear(x -> (height, width)) under F.interpolate's rule for align (0: align_corners=False, 1: True);
  * h == height and w == width is the copy path.  x_dev: f32 NCHW [n][c][h][w]; y_dev: f32 NCHW [n][cy][height][width], read

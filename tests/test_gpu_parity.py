@@ -617,6 +617,22 @@ def test_hrnet3_cbam_forms_agree(env, monkeypatch):
         monkeypatch.delenv(name)
         assert len(ops3) != len(ops) or [o["kernel"] for o in ops3] != [o["kernel"] for o in ops], name
         assert (y3 - y).abs().max().item() <= 2e-5 * max(1.0, y.abs().max().item()), name
+    # odd level sizes (70x50: 35x25 / 18x13 / 9x7 / 5x4, the deepest smaller than the 7x7 window and than a cbam_spatial tile),
+    # three images, small widths, every precision: merged and one-launch-per-step plans give the same bits there too
+    xo = env["synth"].make_crops(3, 1, 70, 50, seed=14).cuda()
+    for precision in ("bf16x3", "bf16", "fp32"):
+        monkeypatch.delenv("ESAHRNET_NO_CBAM_JOBS", raising=False)
+        neta, _ = _build(env, "seg_hrnet3", (16, 32, 64, 128), 14, precision=precision)
+        with torch.no_grad():
+            ya, opsa = neta.forward_timed(xo)
+        assert any(o["kernel"].startswith("cbam_jobs") for o in opsa), precision
+        monkeypatch.setenv("ESAHRNET_NO_CBAM_JOBS", "1")
+        netb, _ = _build(env, "seg_hrnet3", (16, 32, 64, 128), 14, precision=precision)
+        with torch.no_grad():
+            yb, opsb = netb.forward_timed(xo)
+        monkeypatch.delenv("ESAHRNET_NO_CBAM_JOBS")
+        assert not any(o["kernel"].startswith("cbam_jobs") for o in opsb), precision
+        assert bool(torch.isfinite(ya).all()) and torch.equal(ya, yb), precision
 
 
 def test_every_legal_crop_size_runs(env):
