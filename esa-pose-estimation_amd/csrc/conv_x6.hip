@@ -16,21 +16,28 @@
 // the split-bf16 format) and are split by the staging threads on their way into LDS, once per workgroup and tile — the
 // epilogue stores accumulators as they are.
 //
-// Tiling.  256 threads = 4 waves, ONE workgroup per CU (up to 512 VGPRs per lane): a wave owns one 16-cout MFMA tile x NR
-// rows x 16 columns; every B fragment (16 pixels x 32 channels of one term) read from LDS feeds 6 MFMAs per tap and up
-// to three taps; the wave's weights — 9 taps x 3 terms = 27 fragments of a 32-channel chunk — live in registers and are
-// refilled kx-third by kx-third for the next step as soon as a phase is done.  The workgroup covers 16*CT couts x
-// (4/CT)*NR rows (64 couts x 16 rows at stride 1); it walks a persistent stream of (item, chunk) steps with two tile
-// buffers in LDS and ONE barrier per step: the tile of step s+1 is loaded, split and written while step s computes.
-// A step is 864 MFMAs per wave at stride 1 (13.8 k cycles) against 3 barriers and 216 MFMAs in the split-bf16 stream
-// kernel (conv_s2c32.hip).  (A wave with TWO cout tiles — twice the MFMAs per LDS read — needs 216 weight registers and
-// spilled at 512; LDS reads are 2.6 k of a step's 13.8 k cycles as it is.)
+// Tiling.  256 threads = 4 waves, TWO workgroups per CU (X6_MODE 2 below: SIMD partners belong to different workgroups and
+// never meet at a barrier; 256 VGPRs per lane): a wave owns one 16-cout MFMA tile x NR rows x 16 columns; every B fragment
+// (16 pixels x 32 channels of one term) read from LDS feeds 6 MFMAs per tap and up to three taps.  The workgroup covers
+// 16*CT couts x (4/CT)*NR rows (64 couts x 8 rows or 32 couts x 8 rows at stride 1, 4 rows at stride 2); it walks a
+// persistent stream of (item, chunk) steps with two tile buffers in LDS and ONE barrier per step: the tile of step s+1 is
+// loaded, split and written while step s computes (stride 2: one buffer, two barriers).  A step is 432 MFMAs per wave in
+// the 64-cout stride-1 tiling, 216 in the 32-cout one.
+// Weights.  A wave's weights are 9 taps x 3 terms = 27 fragments (27 KB) per 32-channel chunk, and there are two schemes.
+// RELOADING (any number of chunks, any walk over the cout slices): two kx-thirds (72 registers) are live and the third a
+// phase has finished with is refilled, unconditionally, for the phase after the next — also when the next step needs the
+// very fragments the wave holds.  RESIDENT (x6_body<..., WRES>: a convolution of ONE chunk whose workgroups never change
+// their cout slice, in the tilings that have the registers: x6_has_resident): all 27 fragments (108 registers) are loaded
+// once per workgroup and the step loop holds no weight load.  The host picks the scheme per launch (x6_resident_for);
+// both run the same MFMAs on the same operands in the same order.  (A wave with TWO cout tiles — twice the MFMAs per LDS
+// read — needs 216 weight registers and spills.)
 //
 // K order inside a 32-channel chunk.  A staging thread (pixel, sg) loads two 16-byte quads of the pixel's 128-byte
 // chunk: channels 4sg .. 4sg+3 and 16+4sg .. 16+4sg+3 — four consecutive lanes read 64 contiguous bytes per load —
 // so MFMA K index (k-group sg, element j) is channel  j < 4 ? 4sg + j : 16 + 4sg + (j - 4);  the packed weights use
 // the same permutation (x6_chan_of_k).
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <type_traits>
 
@@ -198,6 +205,7 @@ struct X6Cfg {
 struct X6Geo {
     int tiles_x, tiles_y, ctiles, nitems;
     uint32_t m_ct, m_tx, m_ty;
+    int resident = 0;       // 1: this launch runs the resident-weights body (x6_resident_for: decided on the host, per launch)
 };
 __device__ __forceinline__ int x6_div(int b, int d, uint32_t m) {
     int q = (int)__umulhi((uint32_t)b, m);
@@ -219,7 +227,7 @@ struct X6StemSrc {
     const float* x0;      // f32 [N][1][H][W]
     const float* w1;      // f32 [2 chunks][4 k-groups][9 taps + bias][8]: channel chunk*32 + x6_chan_of_k(sg, j)
 };
-template <int KS, int S, int CT, int NR, int NW, bool STEM = false, int NBUF = 2>
+template <int KS, int S, int CT, int NR, int NW, bool STEM = false, int NBUF = 2, bool WRES = false>
 __device__ __forceinline__ void x6_body(const ConvParams& p, const X6Geo& geo, const int bid, const int G, const X6StemSrc stem = X6StemSrc{}) {
     using C = X6Cfg<KS, S, CT, NR, NW, NBUF>;
     constexpr int QSTEP = C::NT / 4;            // tile pixels staged per iteration
@@ -455,7 +463,10 @@ __device__ __forceinline__ void x6_body(const ConvParams& p, const X6Geo& geo, c
     // W2 (3x3): TWO thirds live — phase i (three per step, counted across steps) multiplies from buffer i & 1 while the third
     // of phase i + 1 lands in the other one, which phase i - 1 has finished with: 72 weight registers instead of 108.  The
     // buffer of a phase is a compile-time index, so the step loop is unrolled by two (PAR = step parity).  1x1: wf[1][3].
-    constexpr bool W2 = KS == 3 && X6_W2BUF;
+    // WRES (one 32-channel chunk, a cout slice that never changes: x6_resident_for): ALL TAPS x 3 fragments — 108 registers
+    // for a 3x3 — are loaded in the prologue and stay; the step loop holds no weight load at all.
+    static_assert(!WRES || (KS == 3 && !STEM), "the resident-weights form is built for the one-chunk 3x3 convolutions");
+    constexpr bool W2 = KS == 3 && X6_W2BUF && !WRES;
     bf16x8 wf[W2 ? 2 * KS : TAPS][3];
     auto load_w = [&](int ct, int ch, int kx, int b) __attribute__((always_inline)) {     // b: buffer (W2 only)
         const uint4* ws = p.w + ((size_t)((ct * CT + cw) * nchunks + ch) * TAPS) * 3 * 64 + lane;
@@ -511,6 +522,12 @@ __device__ __forceinline__ void x6_body(const ConvParams& p, const X6Geo& geo, c
     f32x4 bv = load_bias(cur.ct);
     asm volatile("" : "+v"(bv));                // (waited for here, once: at the loop head hipcc would otherwise merge "bias pending
                                                 // behind 27 weight loads" into every iteration's state and drain vmcnt(0) there)
+    if constexpr (WRES) {                       // likewise the resident fragments: complete before the loop, nothing pending at its head
+#pragma unroll
+        for (int tp = 0; tp < TAPS; ++tp)
+#pragma unroll
+            for (int t = 0; t < 3; ++t) asm volatile("" : "+v"(wf[tp][t]));
+    }
 
     const char* const xrd0 = smem + ((rg * NR * S) * C::IW + px * S) * 16 + g * (3 * C::PLANE) + (S == 2 ? (g & 1) * 16 : 0) +
                              (X6_KG_SKEW ? (g >> 1) * 64 : 0);       // plane_off(g, 0) + pixel slot
@@ -565,7 +582,8 @@ __device__ __forceinline__ void x6_body(const ConvParams& p, const X6Geo& geo, c
         }
         // bias of the next step's cout slice: the OLDEST load of the step, so that the wait in front of the next item's
         // accumulator start leaves the weight thirds issued behind it in flight
-        f32x4 bvn = load_bias(wct);
+        f32x4 bvn = bv;                         // (WRES: the slice, and with it the bias, never changes)
+        if constexpr (!WRES) bvn = load_bias(wct);
         __builtin_amdgcn_sched_barrier(0);
         // output addressing of this wave's rows; the residual rows (last chunk) are loaded a few rows ahead of their use
         const int co0 = (cur.ct * CT + cw) * 16 + g * 4;
@@ -704,16 +722,16 @@ __device__ __forceinline__ void x6_body(const ConvParams& p, const X6Geo& geo, c
             asm volatile("" : "+v"(bvn));
             X6_TR(3)
             if constexpr (W2) load_w(cur.ct, cur.c, 2, B0);       // this step's last third
-            else load_w(wct, wch, 0, 0);
+            else if constexpr (!WRES) load_w(wct, wch, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             phase(std::integral_constant<int, 1>{}, F, WN, IB1);
             X6_TR(4)
             if constexpr (W2) load_w(wct, wch, 0, B1);            // the next step's first third
-            else load_w(wct, wch, 1, 0);
+            else if constexpr (!WRES) load_w(wct, wch, 1, 0);
             __builtin_amdgcn_sched_barrier(0);
             phase(std::integral_constant<int, 2>{}, T, WN, IB0);
             X6_TR(5)
-            if constexpr (!W2) load_w(wct, wch, 2, 0);
+            if constexpr (!W2 && !WRES) load_w(wct, wch, 2, 0);
             __syncthreads();            // every wave is done reading the tile
             if constexpr (STEM) stage_stem(0, nxt, (sidx + 1) & 1);
             else write_tile(0, H0);     // (published by the barrier at the top of the next step)
@@ -742,16 +760,16 @@ __device__ __forceinline__ void x6_body(const ConvParams& p, const X6Geo& geo, c
             }
             if constexpr (XH < XITER) load_tile(nxt, H1);
             if constexpr (W2) load_w(cur.ct, cur.c, 2, B0);       // this step's last third
-            else load_w(wct, wch, 0, 0);
+            else if constexpr (!WRES) load_w(wct, wch, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             phase(std::integral_constant<int, 1>{}, F, W1, IB1);
             X6_TR(4)
             if constexpr (W2) load_w(wct, wch, 0, B1);            // the next step's first third
-            else load_w(wct, wch, 1, 0);
+            else if constexpr (!WRES) load_w(wct, wch, 1, 0);
             __builtin_amdgcn_sched_barrier(0);
             phase(std::integral_constant<int, 2>{}, T, WN, IB0);
             X6_TR(5)
-            if constexpr (!W2) load_w(wct, wch, 2, 0);
+            if constexpr (!W2 && !WRES) load_w(wct, wch, 2, 0);
         } else {
             if constexpr (DEEP) {
 #pragma unroll
@@ -796,11 +814,38 @@ __device__ __forceinline__ void x6_body(const ConvParams& p, const X6Geo& geo, c
     }
 }
 
+// The two weight schemes.  RELOADING (x6_body<..., WRES = false>): two kx-thirds in registers, refilled every step — any
+// number of chunks, any walk over the cout slices.  RESIDENT (WRES = true): all 27 fragments loaded once per workgroup — for a
+// convolution of ONE 32-channel chunk whose workgroups never change their cout slice the reloading loop fetches the same
+// 27 KB per wave and step again, the largest stream of bytes such a step pulls.  Same MFMAs, same operands, same order:
+// the two bodies agree bit for bit.  A tiling carries the resident body only where it still fits two workgroups per CU
+// without scratch (build/resource_usage.json): the stride-1 32-cout tiling (16 accumulator registers: 232 VGPRs with the
+// resident body).  The single-buffer stride-2 tilings hold a whole tile in registers beside the operand ring and spill
+// with 108 weight registers (CT = 2: 5 VGPRs, CT = 4: 59): they keep reloading.
+template <int KS, int S, int CT, int NR, int NBUF>
+constexpr bool x6_has_resident() { return KS == 3 && S == 1 && CT == 2 && NR == 4 && NBUF == 2; }
+// Chosen per launch on the host, from the layer and the grid rule only (never the data), and handed to the kernel in
+// X6Geo::resident — a uniform branch at entry, no load behind a run-time condition inside the loop.  The slice of a
+// workgroup is constant when the grid stride is a multiple of ctiles or no workgroup has a second item.
+inline int x6_resident_for(const ConvParams& p, const X6Geo& geo, int grid, bool built) {
+    return built && !p.x6_reload && p.Cinp == 32 && (grid % geo.ctiles == 0 || grid >= geo.nitems) ? 1 : 0;
+}
+template <int KS, int S, int CT, int NR, int NW, int NBUF>
+__device__ __forceinline__ void x6_run(const ConvParams& p, const X6Geo& geo, const int bid, const int G) {
+    if constexpr (x6_has_resident<KS, S, CT, NR, NBUF>()) {
+        if (geo.resident) {
+            x6_body<KS, S, CT, NR, NW, false, NBUF, true>(p, geo, bid, G);
+            return;
+        }
+    }
+    x6_body<KS, S, CT, NR, NW, false, NBUF, false>(p, geo, bid, G);
+}
+
 // OCC: workgroups per CU the register / LDS budget is cut for
 template <int KS, int S, int CT, int NR, int NW, int OCC, int NBUF>
 __global__ __launch_bounds__(NW * 64, OCC * NW / 4) void conv_x6_kernel(ConvParams p, X6Geo geo) {
     static_assert(OCC * X6Cfg<KS, S, CT, NR, NW, NBUF>::LDS <= 160 * 1024, "tile buffers of OCC workgroups exceed the CU's LDS");
-    x6_body<KS, S, CT, NR, NW, false, NBUF>(p, geo, (int)blockIdx.x, (int)gridDim.x);
+    x6_run<KS, S, CT, NR, NW, NBUF>(p, geo, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // fused stem: conv1 (VALU, inside the staging) -> conv2 3x3 stride 2 (models/seg_hrnet.py:426-431), cin = 1
@@ -841,17 +886,22 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_x6_jobs_kernel(X6Jobs jobs) 
 #pragma unroll
     for (int k = 1; k < X6_MAXJOBS; ++k) j += (k < jobs.njobs && b >= jobs.start[k]) ? 1 : 0;
     const int bid = b - jobs.start[j], G = jobs.start[j + 1] - jobs.start[j];
-    if (jobs.ct[j] == 4) x6_body<KS, S, 4, X6JobCfg<KS, S>::NR4, 4, false, X6JobCfg<KS, S>::NBUF>(jobs.p[j], jobs.geo[j], bid, G);
-    else x6_body<KS, S, 2, X6JobCfg<KS, S>::NR2, 4, false, X6JobCfg<KS, S>::NBUF>(jobs.p[j], jobs.geo[j], bid, G);
+    if (jobs.ct[j] == 4) x6_run<KS, S, 4, X6JobCfg<KS, S>::NR4, 4, X6JobCfg<KS, S>::NBUF>(jobs.p[j], jobs.geo[j], bid, G);
+    else x6_run<KS, S, 2, X6JobCfg<KS, S>::NR2, 4, X6JobCfg<KS, S>::NBUF>(jobs.p[j], jobs.geo[j], bid, G);
 }
 
 uint32_t x6_magic(int d) { return (uint32_t)(0xffffffffull / (uint64_t)d); }
+
+// workgroups one tile-stream launch (one member of a merged launch) may have; lowered only by tests
+// (esahrnet_debug_set_x6_grid_limit): with a small grid every workgroup walks many items of a small tensor
+std::atomic<int> g_x6_grid_limit{0x7fffffff};
+int x6_slots(int occ) { return std::min(occ * device_cus(), g_x6_grid_limit.load(std::memory_order_relaxed)); }
 
 template <int KS, int S>
 int launch_x6_jobs_t(const ConvParams* ps, int n, hipStream_t stream) {
     using J = X6JobCfg<KS, S>;
     X6Jobs jobs{};
-    const int slots = 2 * device_cus();
+    const int slots = x6_slots(2);
     struct Ord { int idx, grid; long long steps; };
     Ord order[X6_MAXJOBS];
     X6Geo geos[X6_MAXJOBS];
@@ -873,6 +923,7 @@ int launch_x6_jobs_t(const ConvParams* ps, int n, hipStream_t stream) {
         geo.m_ty = x6_magic(geo.tiles_y);
         int grid = (int)(nitems < slots ? nitems : slots);
         if (grid > geo.ctiles) grid -= grid % geo.ctiles;
+        geo.resident = x6_resident_for(p, geo, grid, ct == 4 ? x6_has_resident<KS, S, 4, J::NR4, J::NBUF>() : x6_has_resident<KS, S, 2, J::NR2, J::NBUF>());
         order[j] = {j, grid, ((nitems + grid - 1) / grid) * (p.Cinp >> 5)};
     }
     std::sort(order, order + n, [](const Ord& a, const Ord& b) { return a.steps > b.steps; });      // longest workgroups first
@@ -905,9 +956,10 @@ int launch_x6_t(const ConvParams& p, hipStream_t stream) {
     geo.m_ct = x6_magic(geo.ctiles);
     geo.m_tx = x6_magic(geo.tiles_x);
     geo.m_ty = x6_magic(geo.tiles_y);
-    const int cus = OCC * device_cus();
+    const int cus = x6_slots(OCC);
     int grid = (int)(nitems < cus ? nitems : cus);
     if (grid > geo.ctiles) grid -= grid % geo.ctiles;   // grid stride keeps the cout slice of a workgroup constant
+    geo.resident = x6_resident_for(p, geo, grid, x6_has_resident<KS, S, CT, NR, NBUF>());
     auto kern = conv_x6_kernel<KS, S, CT, NR, NW, OCC, NBUF>;
     if (const int e_ = ensure_dyn_lds(reinterpret_cast<const void*>(kern), C::LDS)) return e_;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C::NT), C::LDS, stream, p, geo);
@@ -915,6 +967,8 @@ int launch_x6_t(const ConvParams& p, hipStream_t stream) {
 }
 
 }  // namespace
+
+void set_x6_grid_limit(int workgroups) { g_x6_grid_limit.store(workgroups > 0 ? workgroups : 0x7fffffff, std::memory_order_relaxed); }
 
 // one IMAGE must be addressable with 31-bit byte offsets (per-image buffer descriptors, OOB marker 2^31); the batch
 // size is unlimited (the image base is a 64-bit pointer)

@@ -34,6 +34,8 @@ struct ConvParams {
     // (couts hb[h] .. hb[h+1]-1 of the concatenation, multiples of 32) goes to its own SB tensor yh[h] of
     // hb[h+1]-hb[h] channels with its own ReLU flag.  nheads <= 1: the plain form above (y, relu).
     int nheads;
+    int x6_reload;      // FMT_F32, conv_x6.hip: 1 keeps the weight-reloading step loop where the launch would take the resident-
+                        //    weights body (plan switch ESAHRNET_X6_RELOAD_WEIGHTS); same bits either way
     char* yh[3];
     int hb[4];
     int hrelu[3];
@@ -87,6 +89,7 @@ const char* conv_x6_kernel_name(const ConvParams& p, int k, int stride);
 // 2..6 independent convolutions of one kernel size and stride on FMT_F32 tensors as ONE launch (conv_x6_jobs_kernel)
 bool conv_x6_jobs_supported(const ConvParams* ps, int n, int k, int stride);
 int launch_conv_x6_jobs(const ConvParams* ps, int n, int k, int stride, hipStream_t stream);
+void set_x6_grid_limit(int workgroups);            // test hook: workgroups per tile-stream launch (<= 0: the device's slots)
 // 1x1 with all input channels of a wave's pixels in registers (<= 256 input channels, no residual); launch_conv_x6 routes here
 bool conv1x1_x6_supported(const ConvParams& p);
 int launch_conv1x1_x6(const ConvParams& p, hipStream_t stream);

@@ -166,7 +166,7 @@ enum HeadForm { HEAD_UNFUSED, HEAD_SB, HEAD_BF, HEAD_X6 };
 struct PlanOptions {
     // ESAHRNET_<NAME>, on unless unset, empty or "0"
     bool unfused, head_v1, final_valu, no_multihead, no_jobs, no_bblock, no_cbam_jobs, cbam_unfused, stem_pool_separate,
-         head3_direct, head3_cout32, bf_unfused_head, bf_head_valu, x6_unfused_head, x6_unfused_stem, tap_all;
+         head3_direct, head3_cout32, bf_unfused_head, bf_head_valu, x6_unfused_head, x6_unfused_stem, x6_reload_weights, tap_all;
     int nlanes;                 // 4 if ESAHRNET_STREAMS > 1 (the wave executor), else 1: everything on the caller's stream
     int fmt;                    // tensor format: FMT_SB (precision 0), FMT_BF (1: single bf16), FMT_F32 (2: bf16x6 arithmetic),
                                 // FMT_HF (3: single fp16 — the bf16 mode's plan op for op, fp16 elements)
@@ -187,6 +187,7 @@ PlanOptions plan_options(const esahrnet_cfg& g) {
     o.head3_cout32 = on("ESAHRNET_HEAD3_COUT32"); o.bf_unfused_head = on("ESAHRNET_BF_UNFUSED_HEAD");
     o.bf_head_valu = on("ESAHRNET_BF_HEAD_VALU"); o.x6_unfused_head = on("ESAHRNET_X6_UNFUSED_HEAD");
     o.x6_unfused_stem = on("ESAHRNET_X6_UNFUSED_STEM"); o.tap_all = on("ESAHRNET_TAP_ALL");
+    o.x6_reload_weights = on("ESAHRNET_X6_RELOAD_WEIGHTS");     // (changes no op: the same launches, the same names)
     const char* streams = getenv("ESAHRNET_STREAMS");
     o.nlanes = streams && atoi(streams) > 1 ? 4 : 1;
     o.fmt = g.precision == 1 ? esa::FMT_BF : g.precision == 2 ? esa::FMT_F32 : g.precision == 3 ? esa::FMT_HF : esa::FMT_SB;
@@ -1043,6 +1044,7 @@ esa::ConvParams conv_params_of(const esahrnet_ctx& c, const Op& o, const ShapePl
     p.w = static_cast<const uint4*>(d.w); p.bias = d.bias;
     p.N = sp.n; p.H = sp.lh[ti.level]; p.W = sp.lw[ti.level]; p.OH = sp.lh[to.level]; p.OW = sp.lw[to.level];
     p.Cinp = d.cinp; p.Coutp = d.coutp; p.relu = o.relu; p.out_f32 = d.out_f32 && !c.x6(); p.fmt = c.opt.fmt;      // (fp32-grade: every tensor is plain f32)
+    p.x6_reload = c.opt.x6_reload_weights;
     return p;
 }
 
@@ -1345,6 +1347,11 @@ int esahrnet_debug_devstate(int* kernel_device_entries, int* devices) {
 
 int esahrnet_debug_set_launch_limit(long long bytes) {
     esa::set_stream_launch_limit(bytes);
+    return 0;
+}
+
+int esahrnet_debug_set_x6_grid_limit(int workgroups) {
+    esa::set_x6_grid_limit(workgroups);
     return 0;
 }
 
@@ -2679,6 +2686,8 @@ int esahrnet_op_conv_ex(const void* x_dev, int n, int cin, int height, int width
         p.w = static_cast<const uint4*>(dw); p.bias = static_cast<const float*>(db);
         p.N = n; p.H = height; p.W = width; p.OH = oh; p.OW = ow; p.Cinp = cinp; p.Coutp = coutp; p.relu = relu;
         p.fmt = fmt;
+        const char* rw = getenv("ESAHRNET_X6_RELOAD_WEIGHTS");       // (no handle here: the call is its own create)
+        p.x6_reload = rw && rw[0] && strcmp(rw, "0") != 0;
         rc = esa::launch_conv(p, k, stride, stream);
     }
     if (!rc) rc = esa::launch_fmt_to_nchw(fmt, static_cast<const char*>(ys), n, cout, oh, ow, coutp, static_cast<float*>(y_dev), stream);

@@ -653,6 +653,10 @@ int esahrnet_debug_devstate(int* kernel_device_entries, int* devices);
 /* Bytes one launch of the stream convolution kernels may address (default and maximum 2^31 - 1); batches beyond it
  * are cut into image ranges on the host.  Lowered by the tests to exercise the cut at small sizes; 0 restores. */
 int esahrnet_debug_set_launch_limit(long long bytes);
+/* Workgroups one launch of the fp32-grade tile-stream convolution kernels may have (each member of a merged launch on its
+ * own; default: two per CU).  Lowered by the tests so that a workgroup walks many items of a small tensor — the launcher
+ * still rounds a grid above the number of cout slices down to a multiple of it.  workgroups <= 0 restores. */
+int esahrnet_debug_set_x6_grid_limit(int workgroups);
 /* Where launch `index` (0 .. esahrnet_launch_count-1) sits in the wave schedule: launches of one wave on different
  * lanes run concurrently (lane 0 = the caller's stream), waves one after another.  All zero on a one-lane handle. */
 int esahrnet_debug_op_schedule(esahrnet_handle h, int index, int* wave, int* lane);
