@@ -9,6 +9,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -45,8 +47,20 @@ inline int ensure_dyn_lds(const void* kern, int bytes) {
     return 0;
 }
 
-// CU count of the current device (256 on MI355X; the fallback if the query fails)
-inline int device_cus() {
+// test hook (esahrnet_debug_set_cu_limit): an upper limit on what device_cus() reports, so that the launchers take on a
+// small tensor the forms a large batch gives them (persistent walks of many items, the wide-launch 1x1 variants).  Every
+// caller of device_cus() only SIZES with it — a grid, a number of cout slices, the choice between two variants of one
+// kernel; none derives an address from it — so any positive value is a valid launch.  <= 0 restores.
+inline std::atomic<int>& cu_limit() {
+    static std::atomic<int> v{0x7fffffff};
+    return v;
+}
+inline void set_cu_limit(int cus) { cu_limit().store(cus > 0 ? cus : 0x7fffffff, std::memory_order_relaxed); }
+
+// CU count of the current device (256 on MI355X; the fallback if the query fails), at most the test hook's limit
+inline int device_cus_real();
+inline int device_cus() { return std::min(device_cus_real(), cu_limit().load(std::memory_order_relaxed)); }
+inline int device_cus_real() {
     const int dev = current_device();
     DevState& s = dev_state();
     std::lock_guard<std::mutex> lk(s.mu);

@@ -1048,6 +1048,27 @@ esa::ConvParams conv_params_of(const esahrnet_ctx& c, const Op& o, const ShapePl
     return p;
 }
 
+// May these convolutions of one format, kernel size and stride run as ONE merged launch?  A stride-1 3x3 of the other
+// formats must be a stream-kernel launch on its own too (conv_is_stream_s1): the kernel serving a layer never depends
+// on the grouping.  The rule of job_on_for and of esahrnet_op_conv_group.
+bool conv_group_mergeable(int fmt, const esa::ConvParams* ps, int n, int k, int stride) {
+    if (fmt == esa::FMT_F32) return esa::conv_x6_jobs_supported(ps, n, k, stride);
+    if (k == 1) return esa::conv1x1_jobs_supported(ps, n);
+    if (stride == 1)
+        for (int j = 0; j < n; ++j)
+            if (!esa::conv_is_stream_s1(ps[j])) return false;
+    return esa::conv_jobs_supported(ps, n, stride);
+}
+
+// name of the kernel that merged launch runs, as rocprofv3 prints it (op_desc_get, esahrnet_op_conv_group)
+void conv_group_kernel_name(char* out, size_t cap, int fmt, const esa::ConvParams* ps, int n, int k, int stride) {
+    if (fmt == esa::FMT_F32 && k == 1 && esa::conv1x1_x6_jobs_supported(ps, n)) snprintf(out, cap, "conv1x1_x6_jobs_kernel");
+    else if (fmt == esa::FMT_F32) snprintf(out, cap, "conv_x6_jobs_kernel<%d, %d>", k, stride);
+    else if (k == 1) snprintf(out, cap, "conv1x1_jobs_kernel");
+    else snprintf(out, cap, "conv_s2c32_jobs_kernel<%d, %d, %s>", stride, stride == 1 ? 8 : 4,
+                  fmt == esa::FMT_HF ? "fp16" : esa::fmt_half(fmt) ? "true" : "false");
+}
+
 // is this job group evaluated as ONE launch at this shape?  Every member must be a stream-kernel launch of its own
 // there (the kernel serving a layer depends on the shape only, never on the grouping)
 bool job_on_for(const esahrnet_ctx& c, const JobGroup& g, const ShapePlan& sp) {
@@ -1058,12 +1079,9 @@ bool job_on_for(const esahrnet_ctx& c, const JobGroup& g, const ShapePlan& sp) {
         ps[k] = conv_params_of(c, c.ops[g.op[k]], sp, nullptr);
         const ConvSpec& sk = c.specs[c.dconvs[c.ops[g.op[k]].dconv].spec];
         // fp32-grade mode: conv_x6_jobs_kernel serves every kernel size / stride of the module, but one per launch
-        if (c.x6() ? sk.k != s0.k || sk.stride != s0.stride
-                   : s0.k != 1 && (sk.stride != s0.stride || (sk.stride == 1 && !esa::conv_is_stream_s1(ps[k]))))
-            return false;
+        if (c.x6() ? sk.k != s0.k || sk.stride != s0.stride : s0.k != 1 && sk.stride != s0.stride) return false;
     }
-    if (c.x6()) return esa::conv_x6_jobs_supported(ps, g.n, s0.k, s0.stride);
-    return s0.k == 1 ? esa::conv1x1_jobs_supported(ps, g.n) : esa::conv_jobs_supported(ps, g.n, s0.stride);
+    return conv_group_mergeable(c.opt.fmt, ps, g.n, s0.k, s0.stride);
 }
 
 // The per-shape dispatch decisions: level sizes, the head generation, which multi-head and job groups run as one launch.
@@ -1352,6 +1370,11 @@ int esahrnet_debug_set_launch_limit(long long bytes) {
 
 int esahrnet_debug_set_x6_grid_limit(int workgroups) {
     esa::set_x6_grid_limit(workgroups);
+    return 0;
+}
+
+int esahrnet_debug_set_cu_limit(int cus) {
+    esa::set_cu_limit(cus);
     return 0;
 }
 
@@ -1988,10 +2011,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                     break;
                 }
                 char kernel[sizeof desc->kernel];
-                if (c.x6() && s.k == 1 && esa::conv1x1_x6_jobs_supported(ps, g.n)) snprintf(kernel, sizeof kernel, "conv1x1_x6_jobs_kernel");
-                else if (c.x6()) snprintf(kernel, sizeof kernel, "conv_x6_jobs_kernel<%d, %d>", s.k, s.stride);
-                else if (s.k == 1) snprintf(kernel, sizeof kernel, "conv1x1_jobs_kernel");
-                else snprintf(kernel, sizeof kernel, "conv_s2c32_jobs_kernel<%d, %d, %s>", s.stride, s.stride == 1 ? 8 : 4, c.hf() ? "fp16" : c.h16() ? "true" : "false");
+                conv_group_kernel_name(kernel, sizeof kernel, c.opt.fmt, ps, g.n, s.k, s.stride);
                 std::string lab;
                 for (int k = 0; k < g.n; ++k) {
                     const Op& ok = c.ops[g.op[k]];
@@ -2889,6 +2909,245 @@ int esahrnet_op_zero_slice(void* y_dev, int n, int cy, int height, int width, in
     (void)hipFree(ys);
     if (rc) return fail("op_zero_slice: launch failed: %s", hipGetErrorString((hipError_t)rc));
     if (se != hipSuccess) return fail("op_zero_slice: %s", hipGetErrorString(se));
+    return 0;
+}
+
+// ---- every convolution launcher on its own (tests/test_gpu_conv.py) --------------------------------------------------
+// The format of a precision code: element bytes and the channel multiple its tensors are padded to.
+struct OpFmt {
+    int fmt, eb, cm;
+    bool half, hf, x6;
+    int pad(int c) const { return (c + cm - 1) / cm * cm; }
+};
+static bool op_fmt(int precision, OpFmt* f) {
+    if (precision < 0 || precision > 3) return false;
+    f->hf = precision == 3; f->half = precision == 1 || f->hf; f->x6 = precision == 2;
+    f->fmt = f->hf ? esa::FMT_HF : f->half ? esa::FMT_BF : f->x6 ? esa::FMT_F32 : esa::FMT_SB;
+    f->eb = f->half ? 2 : 4; f->cm = f->half ? 64 : 32;
+    return true;
+}
+static bool op_conv_dims_ok(int n, int cin, int cout, int h, int w, int k, int stride) {
+    if (n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return false;
+    if (!((k == 1 && stride == 1) || (k == 3 && (stride == 1 || stride == 2)))) return false;
+    return (long long)n * h * w * (long long)((std::max(cin, cout) + 63) & ~63) * 4 <= 0x7fffffffLL;      // (test tensors)
+}
+// ConvParams of a stand-alone convolution, as esahrnet_op_conv_ex builds them — shapes and flags only; `res` stands for
+// "there is a residual" until op_conv_device puts the device tensors in
+static esa::ConvParams op_conv_shape(const OpFmt& f, int n, int cin, int cout, int h, int w, int stride, int relu, const void* res) {
+    esa::ConvParams p{};
+    p.N = n; p.H = h; p.W = w; p.OH = stride == 2 ? (h + 1) / 2 : h; p.OW = stride == 2 ? (w + 1) / 2 : w;
+    p.Cinp = f.pad(cin); p.Coutp = f.pad(cout); p.relu = relu; p.fmt = f.fmt;
+    p.res = static_cast<const char*>(res);
+    const char* rw = getenv("ESAHRNET_X6_RELOAD_WEIGHTS");
+    p.x6_reload = rw && rw[0] && strcmp(rw, "0") != 0;
+    return p;
+}
+struct OpConvMem {
+    void *dw = nullptr, *db = nullptr, *xs = nullptr, *ys = nullptr, *rs = nullptr;
+    void release() { for (void** p : {&dw, &db, &xs, &ys, &rs}) if (*p) { (void)hipFree(*p); *p = nullptr; } }
+};
+static std::vector<char> op_pack(const OpFmt& f, const float* w, int cout, int cin, int k, int coutp, int cinp) {
+    std::vector<char> packed(f.half ? esa::packed_weight_bytes_bf(coutp, cinp, k) : f.x6 ? esa::packed_weight_bytes_x6(coutp, cinp, k)
+                                                                                         : esa::packed_weight_bytes(coutp, cinp, k), 0);
+    if (f.half) esa::pack_conv_weights_bf(w, cout, cin, k, coutp, cinp, packed.data(), f.hf);
+    else if (f.x6) esa::pack_conv_weights_x6(w, cout, cin, k, coutp, cinp, packed.data());
+    else esa::pack_conv_weights(w, cout, cin, k, coutp, cinp, packed.data());
+    return packed;
+}
+// weights packed and uploaded, x and res converted to the format, y allocated; p's pointers set.  Non-zero: an error is set.
+static int op_conv_device(const OpFmt& f, esa::ConvParams& p, int cin, int cout, int k, const float* w, const float* b,
+                          const void* x_dev, const void* res_dev, OpConvMem& m, hipStream_t stream) {
+    std::vector<float> bias(p.Coutp, 0.f);
+    std::copy(b, b + cout, bias.begin());
+    if (upload(op_pack(f, w, cout, cin, k, p.Coutp, p.Cinp), &m.dw) || upload(bias, &m.db)) return 1;
+    const size_t xb = (size_t)p.N * p.H * p.W * p.Cinp * f.eb, yb = (size_t)p.N * p.OH * p.OW * p.Coutp * f.eb;
+    if (hipMalloc(&m.xs, xb) != hipSuccess || hipMalloc(&m.ys, yb) != hipSuccess || (res_dev && hipMalloc(&m.rs, yb) != hipSuccess))
+        return fail("op_conv_group: hipMalloc failed");
+    int rc = esa::launch_nchw_to_fmt(f.fmt, static_cast<const float*>(x_dev), p.N, cin, p.H, p.W, static_cast<char*>(m.xs), p.Cinp, stream);
+    if (!rc && res_dev) rc = esa::launch_nchw_to_fmt(f.fmt, static_cast<const float*>(res_dev), p.N, cout, p.OH, p.OW, static_cast<char*>(m.rs), p.Coutp, stream);
+    if (rc) return fail("op_conv_group: layout conversion failed: %s", hipGetErrorString((hipError_t)rc));
+    p.x = static_cast<const char*>(m.xs); p.y = static_cast<char*>(m.ys); p.res = static_cast<const char*>(m.rs);
+    p.w = static_cast<const uint4*>(m.dw); p.bias = static_cast<const float*>(m.db);
+    return 0;
+}
+
+int esahrnet_op_conv_kernel(int n, int cin, int cout, int height, int width, int k, int stride, int has_res, int precision,
+                            char* out, size_t cap) {
+    OpFmt f;
+    if (!out || cap == 0) return fail("op_conv_kernel: null argument");
+    if (!op_fmt(precision, &f)) return fail("op_conv_kernel: precision %d", precision);
+    if (!op_conv_dims_ok(n, cin, cout, height, width, k, stride))
+        return fail("op_conv_kernel: n=%d cin=%d cout=%d %dx%d k=%d stride=%d unsupported", n, cin, cout, height, width, k, stride);
+    static const char some_residual = 0;
+    const esa::ConvParams p = op_conv_shape(f, n, cin, cout, height, width, stride, 0, has_res ? &some_residual : nullptr);
+    snprintf(out, cap, "%s", esa::conv_kernel_name(p, k, stride));
+    return 0;
+}
+
+int esahrnet_op_conv_group(int count, const void* const* xs_dev, const int* ns, const int* cins, const int* heights, const int* widths,
+                           const float* const* ws, const float* const* bs, const int* couts, int k, int stride, const int* relus,
+                           const void* const* res_dev, void* const* ys_dev, int precision, char* kernel_out, size_t kernel_cap,
+                           esahrnet_stream stream_) {
+    const char* who = "op_conv_group";
+    OpFmt f;
+    if (!xs_dev || !ns || !cins || !heights || !widths || !ws || !bs || !couts || !relus || !ys_dev) return fail("%s: null argument", who);
+    if (count < 1 || count > 6) return fail("%s: count=%d (1 .. 6)", who, count);
+    if (!op_fmt(precision, &f)) return fail("%s: precision %d", who, precision);
+    esa::ConvParams ps[6];
+    for (int j = 0; j < count; ++j) {
+        if (!xs_dev[j] || !ws[j] || !bs[j] || !ys_dev[j]) return fail("%s: null argument (member %d)", who, j);
+        if (!op_conv_dims_ok(ns[j], cins[j], couts[j], heights[j], widths[j], k, stride))
+            return fail("%s: member %d: n=%d cin=%d cout=%d %dx%d k=%d stride=%d unsupported", who, j, ns[j], cins[j], couts[j],
+                        heights[j], widths[j], k, stride);
+        ps[j] = op_conv_shape(f, ns[j], cins[j], couts[j], heights[j], widths[j], stride, relus[j], res_dev ? res_dev[j] : nullptr);
+    }
+    char kernel[64];
+    if (count == 1) {
+        snprintf(kernel, sizeof kernel, "%s", esa::conv_kernel_name(ps[0], k, stride));
+        if (!strcmp(kernel, "none")) return fail("%s: no kernel of precision %d serves this convolution", who, precision);
+    } else {
+        if (!conv_group_mergeable(f.fmt, ps, count, k, stride))
+            return fail("%s: these %d convolutions (k=%d, stride=%d, precision %d) have no merged launch", who, count, k, stride, precision);
+        conv_group_kernel_name(kernel, sizeof kernel, f.fmt, ps, count, k, stride);
+    }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    OpConvMem mem[6];
+    auto cleanup = [&]() { for (OpConvMem& m : mem) m.release(); };
+    for (int j = 0; j < count; ++j)
+        if (op_conv_device(f, ps[j], cins[j], couts[j], k, ws[j], bs[j], xs_dev[j], res_dev ? res_dev[j] : nullptr, mem[j], stream)) {
+            (void)hipStreamSynchronize(stream);
+            cleanup();
+            return 1;
+        }
+    int rc = count == 1 ? esa::launch_conv(ps[0], k, stride, stream)
+           : f.x6 ? esa::launch_conv_x6_jobs(ps, count, k, stride, stream)
+           : k == 1 ? esa::launch_conv1x1_jobs(ps, count, stream) : esa::launch_conv_jobs(ps, count, stride, stream);
+    for (int j = 0; j < count && !rc; ++j)      // all C' channels: the padding comes back too
+        rc = esa::launch_fmt_to_nchw(f.fmt, ps[j].y, ps[j].N, ps[j].Coutp, ps[j].OH, ps[j].OW, ps[j].Coutp, static_cast<float*>(ys_dev[j]), stream);
+    hipError_t se = hipStreamSynchronize(stream);
+    cleanup();
+    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
+    if (kernel_out && kernel_cap) snprintf(kernel_out, kernel_cap, "%s", kernel);
+    return 0;
+}
+
+int esahrnet_op_conv_multi(const void* x_dev, int n, int cin, int height, int width, int nheads, const float* const* ws,
+                           const float* const* bs, const int* couts, const int* relus, void* const* ys_dev, esahrnet_stream stream_) {
+    const char* who = "op_conv_multi";
+    OpFmt f;
+    op_fmt(0, &f);
+    if (!x_dev || !ws || !bs || !couts || !relus || !ys_dev) return fail("%s: null argument", who);
+    if (nheads < 2 || nheads > 3) return fail("%s: nheads=%d (2 or 3)", who, nheads);
+    int total = 0;
+    for (int h = 0; h < nheads; ++h) {
+        if (!ws[h] || !bs[h] || !ys_dev[h]) return fail("%s: null argument (head %d)", who, h);
+        if (couts[h] <= 0 || (couts[h] & 31)) return fail("%s: head %d has %d couts (a positive multiple of 32)", who, h, couts[h]);
+        total += couts[h];
+    }
+    if (!op_conv_dims_ok(n, cin, total, height, width, 3, 2)) return fail("%s: n=%d cin=%d couts=%d %dx%d unsupported", who, n, cin, total, height, width);
+    esa::ConvParams p = op_conv_shape(f, n, cin, total, height, width, 2, 0, nullptr);
+    p.nheads = nheads;
+    std::vector<char> packed;
+    std::vector<float> bias;
+    for (int h = 0; h < nheads; ++h) {          // members' packed weights / biases back to back, as esahrnet_commit lays them
+        const std::vector<char> wh = op_pack(f, ws[h], couts[h], cin, 3, couts[h], p.Cinp);
+        packed.insert(packed.end(), wh.begin(), wh.end());
+        bias.insert(bias.end(), bs[h], bs[h] + couts[h]);
+        p.hb[h + 1] = p.hb[h] + couts[h];
+        p.hrelu[h] = relus[h] ? 1 : 0;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    void *dw = nullptr, *db = nullptr, *xs = nullptr, *yh[3] = {nullptr, nullptr, nullptr};
+    auto cleanup = [&]() { for (void* q : {dw, db, xs, yh[0], yh[1], yh[2]}) if (q) (void)hipFree(q); };
+    if (upload(packed, &dw) || upload(bias, &db)) { cleanup(); return 1; }
+    bool ok = hipMalloc(&xs, (size_t)n * height * width * p.Cinp * 4) == hipSuccess;
+    for (int h = 0; h < nheads && ok; ++h) ok = hipMalloc(&yh[h], (size_t)n * p.OH * p.OW * couts[h] * 4) == hipSuccess;
+    if (!ok) { cleanup(); return fail("%s: hipMalloc failed", who); }
+    p.x = static_cast<const char*>(xs); p.w = static_cast<const uint4*>(dw); p.bias = static_cast<const float*>(db);
+    for (int h = 0; h < nheads; ++h) p.yh[h] = static_cast<char*>(yh[h]);
+    if (!esa::conv_s2c32_multi_supported(p)) { cleanup(); return fail("%s: launch_conv_s2c32_multi does not serve these heads", who); }
+    int rc = esa::launch_nchw_to_fmt(f.fmt, static_cast<const float*>(x_dev), n, cin, height, width, static_cast<char*>(xs), p.Cinp, stream);
+    if (!rc) rc = esa::launch_conv_s2c32_multi(p, stream);
+    for (int h = 0; h < nheads && !rc; ++h)
+        rc = esa::launch_fmt_to_nchw(f.fmt, p.yh[h], n, couts[h], p.OH, p.OW, couts[h], static_cast<float*>(ys_dev[h]), stream);
+    hipError_t se = hipStreamSynchronize(stream);
+    cleanup();
+    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
+    return 0;
+}
+
+int esahrnet_op_block32(const void* x_dev, int n, int height, int width, const float* w1, const float* b1, const float* w2,
+                        const float* b2, void* y_dev, esahrnet_stream stream_) {
+    const char* who = "op_block32";
+    OpFmt f;
+    op_fmt(0, &f);
+    if (!x_dev || !w1 || !b1 || !w2 || !b2 || !y_dev) return fail("%s: null argument", who);
+    if (!op_conv_dims_ok(n, 32, 32, height, width, 3, 1)) return fail("%s: n=%d %dx%d unsupported", who, n, height, width);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    void *d1 = nullptr, *d2 = nullptr, *db1 = nullptr, *db2 = nullptr, *xs = nullptr, *ys = nullptr;
+    auto cleanup = [&]() { for (void* q : {d1, d2, db1, db2, xs, ys}) if (q) (void)hipFree(q); };
+    const std::vector<float> hb1(b1, b1 + 32), hb2(b2, b2 + 32);
+    if (upload(op_pack(f, w1, 32, 32, 3, 32, 32), &d1) || upload(op_pack(f, w2, 32, 32, 3, 32, 32), &d2) || upload(hb1, &db1) ||
+        upload(hb2, &db2)) { cleanup(); return 1; }
+    const size_t bytes = (size_t)n * height * width * 128;
+    if (hipMalloc(&xs, bytes) != hipSuccess || hipMalloc(&ys, bytes) != hipSuccess) { cleanup(); return fail("%s: hipMalloc failed", who); }
+    esa::BlockParams p{};
+    p.x = static_cast<const char*>(xs); p.y = static_cast<char*>(ys);
+    p.w1 = static_cast<const uint4*>(d1); p.w2 = static_cast<const uint4*>(d2);
+    p.bias1 = static_cast<const float*>(db1); p.bias2 = static_cast<const float*>(db2);
+    p.N = n; p.H = height; p.W = width;
+    int rc = esa::launch_nchw_to_fmt(f.fmt, static_cast<const float*>(x_dev), n, 32, height, width, static_cast<char*>(xs), 32, stream);
+    if (!rc) rc = esa::launch_bblock32(p, stream);
+    if (!rc) rc = esa::launch_fmt_to_nchw(f.fmt, p.y, n, 32, height, width, 32, static_cast<float*>(y_dev), stream);
+    hipError_t se = hipStreamSynchronize(stream);
+    cleanup();
+    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
+    return 0;
+}
+
+int esahrnet_op_stem2(const void* x_dev, int n, int cin, int height, int width, const float* w1, const float* b1, int cmid,
+                      const float* w2, const float* b2, int cout, int precision, void* y_dev, esahrnet_stream stream_) {
+    const char* who = "op_stem2";
+    OpFmt f;
+    if (!x_dev || !w1 || !b1 || !w2 || !b2 || !y_dev) return fail("%s: null argument", who);
+    if (precision != 0 && precision != 2) return fail("%s: precision %d (0: stem_fused, 2: stem_x6_kernel)", who, precision);
+    op_fmt(precision, &f);
+    if (cin < 1 || cin > 4) return fail("%s: cin=%d (1 .. 4)", who, cin);
+    if (cmid <= 0 || (cmid & 31)) return fail("%s: cmid=%d (a positive multiple of 32)", who, cmid);
+    if (!op_conv_dims_ok(n, cmid, cout, height, width, 3, 2)) return fail("%s: n=%d cmid=%d cout=%d %dx%d unsupported", who, n, cmid, cout, height, width);
+    const int coutp = f.pad(cout), oh = (height + 1) / 2, ow = (width + 1) / 2;
+    if (f.x6 && !esa::stem_fused_x6_supported(cin, cmid, coutp)) return fail("%s: stem_x6_kernel does not serve cin=%d cmid=%d cout=%d", who, cin, cmid, cout);
+    std::vector<float> w1p, b1p(b1, b1 + cmid), b2p(coutp, 0.f);
+    std::copy(b2, b2 + cout, b2p.begin());
+    if (f.x6) {                                 // conv1 in stem_x6_kernel's layout (bias inside), as esahrnet_commit packs it
+        w1p.assign(2 * 4 * 10 * 8, 0.f);
+        esa::pack_stem_w1_x6(w1, b1, w1p.data());
+    } else {                                    // [cmid/8][cin][9][8]
+        w1p.assign((size_t)cmid * cin * 9, 0.f);
+        for (int co = 0; co < cmid; ++co)
+            for (int ci = 0; ci < cin; ++ci)
+                for (int t = 0; t < 9; ++t)
+                    w1p[(((size_t)(co >> 3) * cin + ci) * 9 + t) * 8 + (co & 7)] = w1[((size_t)co * cin + ci) * 9 + t];
+    }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    void *dw1 = nullptr, *db1 = nullptr, *dw2 = nullptr, *db2 = nullptr, *ys = nullptr;
+    auto cleanup = [&]() { for (void* q : {dw1, db1, dw2, db2, ys}) if (q) (void)hipFree(q); };
+    if (upload(w1p, &dw1) || upload(b1p, &db1) || upload(op_pack(f, w2, cout, cmid, 3, coutp, cmid), &dw2) || upload(b2p, &db2)) { cleanup(); return 1; }
+    if (hipMalloc(&ys, (size_t)n * oh * ow * coutp * 4) != hipSuccess) { cleanup(); return fail("%s: hipMalloc failed", who); }
+    esa::StemFusedParams p{};
+    p.x = static_cast<const float*>(x_dev); p.y = static_cast<char*>(ys);
+    p.w1 = static_cast<const float*>(dw1); p.bias1 = static_cast<const float*>(db1);
+    p.w2 = static_cast<const uint4*>(dw2); p.bias2 = static_cast<const float*>(db2);
+    p.N = n; p.H = height; p.W = width; p.OH = oh; p.OW = ow; p.cin = cin; p.Cmid = cmid; p.Coutp = coutp;
+    int rc = f.x6 ? esa::launch_stem_fused_x6(p, stream) : esa::launch_stem_fused(p, stream);
+    if (!rc) rc = esa::launch_fmt_to_nchw(f.fmt, p.y, n, coutp, oh, ow, coutp, static_cast<float*>(y_dev), stream);
+    hipError_t se = hipStreamSynchronize(stream);
+    cleanup();
+    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
     return 0;
 }
 

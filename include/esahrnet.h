@@ -646,6 +646,40 @@ int esahrnet_op_resample(const void* x_dev, int n, int c, int h, int w, void* y_
 int esahrnet_op_zero_slice(void* y_dev, int n, int cy, int height, int width, int c0, int nchan, int precision,
                            esahrnet_stream stream);
 
+/* ---- every convolution launcher on its own (test use only; none of these is on a forward path) --------------------------
+ * All are synchronous, check every argument before anything is enqueued (a refusal returns non-zero with esahrnet_last_error
+ * set, launches nothing and leaves the outputs as they were), take w / b as HOST f32 pointers and pack them on the spot, and
+ * take `precision` as esahrnet_op_conv_ex does (0: split-bf16, 1: bf16, 2: bf16x6, 3: fp16).  Outputs are f32 NCHW with
+ * C' = cout padded to the mode's channel multiple (32; bf16 / fp16: 64) channels: the padding channels come back too. */
+/* Name of the kernel esahrnet_op_conv_ex / esahrnet_op_conv_group(count = 1) runs for these parameters ("none": no kernel of
+ * the precision serves them).  Host only: no device call is made. */
+int esahrnet_op_conv_kernel(int n, int cin, int cout, int height, int width, int k, int stride, int has_res, int precision,
+                            char* out, size_t cap);
+/* `count` convolutions of one kernel size, stride and precision, member j on its own tensors: x [ns[j]][cins[j]][heights[j]]
+ * [widths[j]] -> y [ns[j]][C'][oh][ow], y = [relu]( conv(x; w) + b [+ res] ); res_dev may be NULL, or hold NULL for a member
+ * without residual.  count == 1: launch_conv of the member (esahrnet_op_conv_ex with the padded output).  count 2 .. 6: ONE
+ * merged launch under the rule the plan applies to an HRModule's job groups — launch_conv_x6_jobs (precision 2),
+ * launch_conv1x1_jobs (k = 1) or launch_conv_jobs (k = 3; a stride-1 member must be a stream-kernel launch on its own);
+ * a group that rule rejects is refused.  kernel_out (optional): the kernel's name as esahrnet_op_desc_get reports it. */
+int esahrnet_op_conv_group(int count, const void* const* xs_dev, const int* ns, const int* cins, const int* heights, const int* widths,
+                           const float* const* ws, const float* const* bs, const int* couts, int k, int stride, const int* relus,
+                           const void* const* res_dev, void* const* ys_dev, int precision, char* kernel_out, size_t kernel_cap,
+                           esahrnet_stream stream);
+/* launch_conv_s2c32_multi: 2 or 3 3x3 stride-2 convolutions of ONE input in one launch (split-bf16 only), head h with couts[h]
+ * (a multiple of 32) output channels, its own ReLU flag and its own output ys_dev[h] f32 [n][couts[h]][oh][ow]. */
+int esahrnet_op_conv_multi(const void* x_dev, int n, int cin, int height, int width, int nheads, const float* const* ws,
+                           const float* const* bs, const int* couts, const int* relus, void* const* ys_dev, esahrnet_stream stream);
+/* launch_bblock32 (split-bf16): y = relu( conv3x3(relu(conv3x3(x; w1) + b1); w2) + b2 + x ), x and y f32 [n][32][height][width],
+ * w1 / w2 [32][32][3][3], b1 / b2 [32]. */
+int esahrnet_op_block32(const void* x_dev, int n, int height, int width, const float* w1, const float* b1, const float* w2,
+                        const float* b2, void* y_dev, esahrnet_stream stream);
+/* The fused stem: y = relu( conv3x3_s2( relu(conv3x3(x; w1) + b1); w2 ) + b2 ), x f32 [n][cin][height][width], w1 [cmid][cin][3][3],
+ * w2 [cout][cmid][3][3], y f32 [n][C'][ceil(height/2)][ceil(width/2)].  precision 0: launch_stem_fused (cin 1 .. 4, cmid a
+ * multiple of 32); precision 2: launch_stem_fused_x6 where stem_fused_x6_supported (cin 1, cmid 64, C' a multiple of 64).
+ * Weights are packed as esahrnet_commit packs them. */
+int esahrnet_op_stem2(const void* x_dev, int n, int cin, int height, int width, const float* w1, const float* b1, int cmid,
+                      const float* w2, const float* b2, int cout, int precision, void* y_dev, esahrnet_stream stream);
+
 /* ---- test hooks ------------------------------------------------------------------------------------ */
 /* Launch state is kept per DEVICE (dynamic-LDS limits raised per kernel and device, CU counts), never in
  * process-wide flags: number of (kernel, device) entries and of devices seen so far. */
@@ -657,6 +691,14 @@ int esahrnet_debug_set_launch_limit(long long bytes);
  * own; default: two per CU).  Lowered by the tests so that a workgroup walks many items of a small tensor — the launcher
  * still rounds a grid above the number of cout slices down to a multiple of it.  workgroups <= 0 restores. */
 int esahrnet_debug_set_x6_grid_limit(int workgroups);
+/* An upper limit on the CU count the launchers size with (device_cus() reports min(the device's, cus)); cus <= 0 restores.
+ * With a limit of 1 .. 3 a small tensor gets the launch forms of a large batch: persistent workgroups that walk many items
+ * across cout slices and image boundaries (the tile and stream convolution kernels, bblock32), the single-buffered stream
+ * variant, the two-groups-per-wave 1x1 kernel of the 16-bit formats, fewer cout splits of the 1x1 kernels.  Every use of the
+ * count is sizing — a grid, a slice count, the choice between variants of one kernel — never an address, so every value is
+ * a valid launch and the results must not depend on it.  The fp32-grade tile-stream kernels keep their own hook above
+ * (both limits apply).  Process-wide; test use only. */
+int esahrnet_debug_set_cu_limit(int cus);
 /* Where launch `index` (0 .. esahrnet_launch_count-1) sits in the wave schedule: launches of one wave on different
  * lanes run concurrently (lane 0 = the caller's stream), waves one after another.  All zero on a one-lane handle. */
 int esahrnet_debug_op_schedule(esahrnet_handle h, int index, int* wave, int* lane);

@@ -104,16 +104,10 @@ def _sb3(x, w, stride=1):
 
 
 def _conv(precision, x, w, b, relu):
-    """One convolution of the format: w, b folded f32; the result stored in the format."""
-    bb = 0.0 if b is None else b[None, :, None, None]
-    if precision == 0:
-        y = _sb3(x, w) + bb
-    elif precision == 2:
-        y = F.conv2d(x, w, None, 1, (w.shape[-1] - 1) // 2) + bb
-    else:
-        q = QSTORE[precision]
-        y = F.conv2d(x, q(w), None, 1, (w.shape[-1] - 1) // 2) + bb
-    return QSTORE[precision](F.relu(y) if relu else y)
+    """One convolution of the format: w, b folded f32; the result stored in the format.  (conv_ref.conv is the one definition,
+    with stride and residual; conv_ref imports this module, hence the late import.)"""
+    import conv_ref
+    return conv_ref.conv(precision, x, w, b, relu=relu)
 
 
 def _fold32(sd, name, bn):
