@@ -49,6 +49,33 @@ class DebugOp(C.Structure):
                 ("nregions", C.c_int32), ("regions", DebugRegion * 8)]
 
 
+# One record of the activation range report (include/esahrnet.h: ESAHRNET_STATS_FIELDS, the same names in the same order; the
+# header test holds the two together).  The ctypes struct and the numpy dtype below both come from this table.
+STATS_RECORD_BYTES = 64
+STATS_FIELDS = (("sum_abs", "f8"), ("max_abs", "f4"), ("min", "f4"), ("max", "f4"), ("n_finite", "u4"), ("n_nan", "u4"),
+                ("n_inf", "u4"), ("n_zero", "u4"), ("n_ge_f16max", "u4"), ("n_f16_tiny", "u4"))
+_STATS_CTYPES = {"f8": C.c_double, "f4": C.c_float, "u4": C.c_uint32}
+STATS_NCHW = -1                   # esahrnet_stats_row_desc.fmt of the heat-maps row; 0..3: the plan's storage formats
+STATS_FORMATS = {0: "bf16x3", 1: "bf16", 2: "f32", 3: "fp16", STATS_NCHW: "f32 NCHW"}
+
+
+class StatsRecord(C.Structure):
+    _fields_ = [(name, _STATS_CTYPES[t]) for name, t in STATS_FIELDS] + [("reserved", C.c_uint32 * 5)]
+
+
+def stats_dtype():
+    """numpy dtype of a record: the fields of STATS_FIELDS at their offsets, 64 bytes."""
+    import numpy as np
+    names = [name for name, _ in STATS_FIELDS]
+    return np.dtype({"names": names, "formats": [t for _, t in STATS_FIELDS],
+                     "offsets": [getattr(StatsRecord, name).offset for name in names], "itemsize": STATS_RECORD_BYTES})
+
+
+class StatsRowDesc(C.Structure):
+    _fields_ = [("name", C.c_char * 96), ("def_op", C.c_int32), ("c", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("fmt", C.c_int32), ("scanned", C.c_int32)]
+
+
 class EsaHrnetError(RuntimeError):
     pass
 
@@ -176,6 +203,15 @@ _SIGS = {
                                      C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "esahrnet_tap_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "esahrnet_stats_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "esahrnet_stats_row_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(StatsRowDesc)]),
+    "esahrnet_forward_stats_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "esahrnet_forward_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_void_p]),
+    "esahrnet_tensor_stats_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       C.POINTER(C.c_size_t)]),
+    "esahrnet_tensor_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_void_p]),
     "esahrnet_op_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "esahrnet_op_fuse": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,

@@ -440,4 +440,17 @@ int launch_to_nchw_part(int fmt, const char* x, int N, int C, int H, int W, int 
 // the same per-tile maxima without the NCHW copy
 int launch_tile_max(int fmt, const char* x, int N, int C, int H, int W, int Cp, float2* part, hipStream_t s);
 
+// ---- stats.hip: the activation range report (esahrnet_stats_record, include/esahrnet.h) ----------------------------------
+// One tensor to scan: x [N][H][W][Cp] in format fmt (HW = H * W pixels, real channels 0..C-1), or, fmt == STATS_NCHW, plain f32
+// [N][C][H][W] (Cp unused).  Its N records go to records[row * N + image].
+constexpr int STATS_NCHW = -1;
+struct StatsJob {
+    const void* x;
+    int fmt, C, Cp, HW, row;
+};
+// partial records per image the scan of such a tensor leaves (a function of the shape alone); 0: a shape it does not serve
+int stats_parts(int fmt, int C, int Cp, int HW);
+// scan + finish of njobs tensors of N images; partials: room for sum_j stats_parts(job j) * N records, 8-byte aligned
+int launch_stats(const StatsJob* jobs, int njobs, int N, void* partials, void* records, hipStream_t stream);
+
 }  // namespace esa

@@ -2665,6 +2665,154 @@ int esahrnet_tap_read(esahrnet_handle h, const char* name, int n, int height, in
     return 0;
 }
 
+// ---- activation range report (stats.hip) -------------------------------------------------------------------------------
+// Rows: the plan's tensors in plan order, then "heatmaps".  The storage format of a tensor, as esahrnet_tap_read takes it:
+static int stats_fmt(const esahrnet_ctx& c, const Tensor& t) { return t.f32 ? (int)esa::FMT_F32 : c.opt.fmt; }
+
+// Does the scan read tensor `t` at this shape?  Not the flat scratch, the T layout or the head alternative that does not run,
+// and no tensor without the padded-channel layout of its format (CBAM's two-plane maps): stats_parts refuses those.
+static bool stats_scanned(const esahrnet_ctx& c, const ShapePlan& sp, const Tensor& t) {
+    if (t.flat || t.tlayout || t.def < 0) return false;
+    if (t.alt != 0 && t.alt != (sp.head2 ? 2 : 1)) return false;
+    const long long hw = (long long)sp.lh[t.level] * sp.lw[t.level];
+    return hw <= 0x7fffffffLL && esa::stats_parts(stats_fmt(c, t), t.C, t.Cp, (int)hw) > 0;
+}
+
+// partial records of one image over all scanned rows, heat-maps included; -1: the heat-maps are beyond the scan
+static long long stats_partials_per_image(const esahrnet_ctx& c, const ShapePlan& sp) {
+    const int hp = esa::stats_parts(esa::STATS_NCHW, c.cfg.num_keypoints, 0, sp.h * sp.w);
+    if (hp <= 0) return -1;
+    long long parts = hp;
+    for (const Tensor& t : c.tensors)
+        if (stats_scanned(c, sp, t)) parts += esa::stats_parts(stats_fmt(c, t), t.C, t.Cp, sp.lh[t.level] * sp.lw[t.level]);
+    return parts;
+}
+
+int esahrnet_stats_rows(esahrnet_handle h, int* rows) {
+    if (!h || !rows) return fail("stats_rows: null argument");
+    *rows = (int)h->tensors.size() + 1;
+    return 0;
+}
+
+int esahrnet_stats_row_get(esahrnet_handle h, int row, int n, int height, int width, esahrnet_stats_row_desc* out) {
+    if (!h || !out) return fail("stats_row_get: null argument");
+    const int nt = (int)h->tensors.size();
+    if (row < 0 || row > nt) return fail("stats_row_get: row %d out of range (0..%d)", row, nt);
+    if (check_shape(n, height, width)) return 1;
+    memset(out, 0, sizeof *out);
+    if (row == nt) {
+        snprintf(out->name, sizeof out->name, "heatmaps");
+        out->def_op = (int)h->ops.size() - 1;
+        out->c = h->cfg.num_keypoints; out->h = height; out->w = width;
+        out->fmt = esa::STATS_NCHW;
+        out->scanned = 1;
+        return 0;
+    }
+    const Tensor& t = h->tensors[row];
+    const ShapePlan sp = shape_decisions(*h, n, height, width);
+    out->def_op = t.def;
+    out->fmt = t.flat ? (int)esa::FMT_F32 : stats_fmt(*h, t);
+    if (!t.flat) { out->c = t.C; out->h = sp.lh[t.level]; out->w = sp.lw[t.level]; }
+    out->scanned = stats_scanned(*h, sp, t) ? 1 : 0;
+    if (!t.tap.empty()) snprintf(out->name, sizeof out->name, "%s", t.tap.c_str());
+    else if (t.def >= 0) {
+        esahrnet_op_desc d;
+        memset(&d, 0, sizeof d);
+        if (run_op(*h, h->ops[t.def], sp, Buffers{}, nullptr, &d)) return 1;
+        snprintf(out->name, sizeof out->name, "%s", d.label);
+    } else snprintf(out->name, sizeof out->name, "(tensor %d)", row);
+    return 0;
+}
+
+static size_t stats_pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// the keep-mode plan of the shape, then the partials behind it; the handle's keep state is put back by the caller
+static int stats_plan(const char* who, esahrnet_ctx& c, int n, int height, int width, size_t* bytes) {
+    if (plan_shape(c, n, height, width)) return 1;
+    const long long parts = stats_partials_per_image(c, c.sp);
+    if (parts < 0) return fail("%s: crop %dx%d is beyond the scan of the heat-maps", who, height, width);
+    *bytes = stats_pad256(stats_pad256(c.sp.bytes) + (size_t)parts * n * sizeof(esahrnet_stats_record));
+    return 0;
+}
+
+int esahrnet_forward_stats_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
+    if (!h || !bytes) return fail("forward_stats_workspace_bytes: null argument");
+    const bool keep = h->keep;
+    h->keep = true;
+    const int rc = stats_plan("forward_stats_workspace_bytes", *h, n, height, width, bytes);
+    h->keep = keep;
+    return rc;
+}
+
+int esahrnet_forward_stats(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* heat_dev, void* ws_dev,
+                           size_t ws_bytes, void* stats_dev, esahrnet_stream stream_) {
+    if (!h || !x_dev || !heat_dev || !ws_dev || !stats_dev) return fail("forward_stats: null argument");
+    if (!h->committed) return fail("forward_stats: esahrnet_commit has not been called");
+    const bool keep = h->keep;
+    h->keep = true;
+    auto body = [&]() -> int {
+        size_t need = 0;
+        if (stats_plan("forward_stats", *h, n, height, width, &need)) return 1;
+        if (ws_bytes < need) return fail("forward_stats: workspace too small (%zu < %zu)", ws_bytes, need);
+        if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("forward_stats: workspace must be 256-byte aligned");
+        if (reinterpret_cast<uintptr_t>(stats_dev) & 7) return fail("forward_stats: stats_dev must be 8-byte aligned");
+        hipStream_t stream = static_cast<hipStream_t>(stream_);
+        const size_t rows = h->tensors.size() + 1;
+        HIP_OK(hipMemsetAsync(stats_dev, 0, rows * n * sizeof(esahrnet_stats_record), stream));   // the rows not scanned
+        if (run_forward(h, x_dev, n, height, width, heat_dev, nullptr, ws_dev, ws_bytes, stream_, nullptr, nullptr)) return 1;
+        const ShapePlan& sp = h->sp;
+        char* const ws = static_cast<char*>(ws_dev);
+        std::vector<esa::StatsJob> jobs;
+        for (size_t ti = 0; ti < h->tensors.size(); ++ti) {
+            const Tensor& t = h->tensors[ti];
+            if (stats_scanned(*h, sp, t))
+                jobs.push_back({ws + t.off, stats_fmt(*h, t), t.C, t.Cp, sp.lh[t.level] * sp.lw[t.level], (int)ti});
+        }
+        jobs.push_back({heat_dev, esa::STATS_NCHW, h->cfg.num_keypoints, 0, height * width, (int)rows - 1});
+        const int rc = esa::launch_stats(jobs.data(), (int)jobs.size(), n, ws + stats_pad256(sp.bytes), stats_dev, stream);
+        if (rc) return fail("forward_stats: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        return 0;
+    };
+    const int rc = body();
+    h->keep = keep;
+    return rc;
+}
+
+static int tensor_stats_parts(const char* who, int fmt, int n, int c, int cp, int h, int w, int* parts) {
+    if (n < 1) return fail("%s: batch must be positive (got %d)", who, n);
+    const long long hw = (long long)h * w;
+    *parts = h > 0 && w > 0 && hw <= 0x7fffffffLL && fmt >= esa::STATS_NCHW && fmt <= esa::FMT_HF
+                 ? esa::stats_parts(fmt, c, cp, (int)hw) : 0;
+    if (*parts <= 0)
+        return fail("%s: no scan for format %d, %d channels (%d padded), %dx%d (formats -1..3; SB: padded channels a multiple "
+                    "of 8, BF / HF of 8, F32 of 4; an image below 2 GiB)", who, fmt, c, cp, h, w);
+    return 0;
+}
+
+int esahrnet_tensor_stats_workspace_bytes(int fmt, int n, int c, int cp, int h, int w, size_t* bytes) {
+    if (!bytes) return fail("tensor_stats_workspace_bytes: null argument");
+    int parts = 0;
+    if (tensor_stats_parts("tensor_stats_workspace_bytes", fmt, n, c, cp, h, w, &parts)) return 1;
+    *bytes = (size_t)parts * n * sizeof(esahrnet_stats_record);
+    return 0;
+}
+
+int esahrnet_tensor_stats(const void* t_dev, int fmt, int n, int c, int cp, int h, int w, void* ws_dev, size_t ws_bytes,
+                          void* stats_dev, esahrnet_stream stream) {
+    if (!t_dev || !ws_dev || !stats_dev) return fail("tensor_stats: null argument");
+    int parts = 0;
+    if (tensor_stats_parts("tensor_stats", fmt, n, c, cp, h, w, &parts)) return 1;
+    const size_t need = (size_t)parts * n * sizeof(esahrnet_stats_record);
+    if (ws_bytes < need) return fail("tensor_stats: workspace too small (%zu < %zu)", ws_bytes, need);
+    if (fmt != esa::STATS_NCHW && (reinterpret_cast<uintptr_t>(t_dev) & 15)) return fail("tensor_stats: t_dev must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(ws_dev) & 7) return fail("tensor_stats: workspace must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(stats_dev) & 7) return fail("tensor_stats: stats_dev must be 8-byte aligned");
+    const esa::StatsJob job{t_dev, fmt, c, cp, h * w, 0};
+    const int rc = esa::launch_stats(&job, 1, n, ws_dev, stats_dev, static_cast<hipStream_t>(stream));
+    if (rc) return fail("tensor_stats: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
 // ---- stand-alone operators on f32 NCHW tensors (tests) ---------------------------------------
 int esahrnet_op_conv(const void* x_dev, int n, int cin, int height, int width, const float* w,
                      const float* b, int cout, int k, int stride, int relu, const void* res_dev,

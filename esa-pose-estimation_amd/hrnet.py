@@ -314,6 +314,12 @@ class HighResolutionNet(nn.Module):
         """Debug: run a forward keeping every intermediate; returns {name: f32 NCHW tensor}."""
         return self._rt.taps(self, x0)
 
+    def activation_stats(self, x0: torch.Tensor) -> "ActivationStats":
+        """The activation range report of one forward (include/esahrnet.h: esahrnet_forward_stats): every tensor of the plan
+        scanned on the device where the forward left it, one 64-byte record per (tensor, crop), one device -> host copy.
+        Which precision can these weights afford: see ActivationStats.headroom_fp16, saturated, first_nonfinite."""
+        return self._rt.forward_stats(self, x0)
+
     # ---- weight-version tracking (an eager forward must not walk the module tree: val.py:112 calls the
     # net once per image) ---------------------------------------------------------------------------
     def _weight_tensors(self):
@@ -399,6 +405,7 @@ class _Runtime:
         "frames_final2": ("frames", "esahrnet_frames_keypoints_workspace_bytes", lambda n, hh, ww, keep: (n, hh, 1)),
         "frames_gaussfit": ("frames", "esahrnet_frames_keypoints_gaussfit_workspace_bytes", lambda n, hh, ww, keep: (n, hh)),
         "corr": ("frames", "esahrnet_frames_correspondences_workspace_bytes", lambda n, hh, ww, keep: (n, hh, *keep)),
+        "stats": ("stats", "esahrnet_forward_stats_workspace_bytes", _crops),
     }
 
     def __init__(self, cfg_struct):
@@ -735,6 +742,39 @@ class _Runtime:
                             flops=d.flops, bytes=d.bytes))
         return heat, ops
 
+    def stats_rows(self, h, n, hh, ww):
+        """The row descriptions of a handle's report at a shape (esahrnet_stats_row_get): no GPU needed."""
+        rows = C.c_int(0)
+        _lib.check(self.lib.esahrnet_stats_rows(h, C.byref(rows)))
+        descs = []
+        for i in range(rows.value):
+            d = _lib.StatsRowDesc()
+            _lib.check(self.lib.esahrnet_stats_row_get(h, i, n, hh, ww, C.byref(d)))
+            descs.append(d)
+        return descs
+
+    def forward_stats(self, module, x0):
+        """esahrnet_forward_stats on the current stream of x's device: -> ActivationStats.  Same device lock, workspace contract
+        and record_stream handling as forward(); the records come back in one copy."""
+        x = self._check_input(module, x0)
+        n, _, hh, ww = x.shape
+        dev = x.device
+        ts = torch.cuda.current_stream(dev)
+        with self._device_lock(dev.index):
+            h = self._handle_for(module, dev)
+            _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
+            descs = self.stats_rows(h, n, hh, ww)
+            ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, n, hh, ww, False, kind="stats")
+            heat = torch.empty((n, module._k, hh, ww), dtype=torch.float32, device=dev)
+            stats = torch.empty((len(descs), n, _lib.STATS_RECORD_BYTES), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(self.lib.esahrnet_forward_stats(h, x.data_ptr(), n, hh, ww, heat.data_ptr(), ws_ptr, ws_bytes,
+                                                           stats.data_ptr(), C.c_void_p(ts.cuda_stream)))
+        ws.record_stream(ts)
+        x.record_stream(ts)
+        rec = stats.cpu().numpy().reshape(-1).view(_lib.stats_dtype()).reshape(len(descs), n)
+        return ActivationStats(descs, rec, heat)
+
     def taps(self, module, x0):
         x = self._check_input(module, x0)
         n, _, hh, ww = x.shape
@@ -758,6 +798,72 @@ class _Runtime:
             out[name.decode()] = t
         _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
         return out
+
+
+class ActivationStats:
+    """net.activation_stats(x): per-tensor ranges of one forward.
+
+    per_image   the raw records, a structured numpy array [rows, n] (_lib.STATS_FIELDS); rows not scanned are all zero
+    rows        one dict per row in plan order, the last one "heatmaps": name, def_op, shape (c, h, w), format, scanned and
+                the batch-combined figures (maxima and counts exactly, sum_abs added in crop order, mean_abs = sum_abs / n_finite)
+    heatmaps    the forward's heat-maps (f32 [n, K, H, W] on the device), the bits net(x) returns"""
+
+    F16_MAX = 65504.0
+    COUNTS = tuple(name for name, t in _lib.STATS_FIELDS if t == "u4")
+
+    def __init__(self, descs, per_image, heatmaps):
+        self.per_image = per_image
+        self.heatmaps = heatmaps
+        self.rows = []
+        for d, rec in zip(descs, per_image):
+            row = dict(name=d.name.decode(), def_op=d.def_op, shape=(d.c, d.h, d.w), format=_lib.STATS_FORMATS[d.fmt],
+                       scanned=bool(d.scanned))
+            row["max_abs"] = float(rec["max_abs"].max())
+            row["min"] = float(rec["min"].min())
+            row["max"] = float(rec["max"].max())
+            sum_abs = 0.0
+            for v in rec["sum_abs"]:
+                sum_abs += float(v)
+            row["sum_abs"] = sum_abs
+            for name in self.COUNTS:
+                row[name] = int(rec[name].astype(np.int64).sum())
+            row["mean_abs"] = sum_abs / row["n_finite"] if row["n_finite"] else 0.0
+            self.rows.append(row)
+
+    def scanned(self):
+        return [r for r in self.rows if r["scanned"]]
+
+    def first_nonfinite(self):
+        """Name of the first scanned row in plan order that holds a NaN or an infinity, or None."""
+        for r in self.scanned():
+            if r["n_nan"] + r["n_inf"] > 0:
+                return r["name"]
+        return None
+
+    def headroom_fp16(self) -> float:
+        """65504 / the largest finite |value| any stored tensor holds (the heat-maps row is caller memory, not a stored
+        tensor): 1.0 in an fp16 net that saturates, below 1.0 in another format where fp16 would clamp."""
+        top = max((r["max_abs"] for r in self.scanned()[:-1]), default=0.0)
+        return self.F16_MAX / top if top > 0 else float("inf")
+
+    def saturated(self):
+        """The scanned rows with a finite |value| >= 65504: in an fp16 net the saturated stores (a genuine 65504 cannot be told
+        apart from one), in the other formats the values fp16 would clamp."""
+        return [r for r in self.scanned() if r["n_ge_f16max"] > 0]
+
+    def table(self) -> str:
+        head = f"{'row':>4} {'op':>4} {'name':<44} {'shape':<14} {'format':<8} {'max_abs':>11} {'mean_abs':>11} {'min':>11} " \
+               f"{'max':>11} {'nan':>6} {'inf':>6} {'>=65504':>8} {'f16 tiny':>9} {'zero':>9}"
+        lines = [head]
+        for i, r in enumerate(self.rows):
+            shape = "x".join(str(v) for v in r["shape"])
+            if not r["scanned"]:
+                lines.append(f"{i:>4} {r['def_op']:>4} {r['name'][:44]:<44} {shape:<14} {r['format']:<8} (not scanned)")
+                continue
+            lines.append(f"{i:>4} {r['def_op']:>4} {r['name'][:44]:<44} {shape:<14} {r['format']:<8} {r['max_abs']:>11.4e} "
+                         f"{r['mean_abs']:>11.4e} {r['min']:>11.4e} {r['max']:>11.4e} {r['n_nan']:>6} {r['n_inf']:>6} "
+                         f"{r['n_ge_f16max']:>8} {r['n_f16_tiny']:>9} {r['n_zero']:>9}")
+        return "\n".join(lines)
 
 
 def get_seg_model(cfg, **kwargs):

@@ -581,6 +581,68 @@ int esahrnet_tap_shape(esahrnet_handle h, const char* name, int height, int widt
 int esahrnet_tap_read(esahrnet_handle h, const char* name, int n, int height, int width,
                       const void* ws_dev, void* out_dev, esahrnet_stream stream);
 
+/* ---- activation range report ---------------------------------------------------------------------------------------------
+ * Which precision can a checkpoint afford?  precision 3 (fp16) saturates every stored value at +-65504 and precision 0's error
+ * grows with the activation scale; the report shows, tensor by tensor, how far a forward's values are from either.
+ *
+ * One record per (row, image), 64 bytes.  ESAHRNET_STATS_FIELDS is the one description of its layout (the struct below, the
+ * ctypes / numpy forms of the Python binding and the tests all come from it): X(C type, name), in memory order, no holes.
+ *   sum_abs                 sum of |x| over the finite values
+ *   max_abs, min, max       over the finite values; 0, +inf, -inf when there is none
+ *   n_finite, n_nan, n_inf  of the real channels (padding channels are read but never counted)
+ *   n_zero                  +0 and -0
+ *   n_ge_f16max             finite values with |x| >= 65504.  In an fp16 tensor these are the saturated stores (a genuine
+ *                           65504 cannot be told apart from a saturated one); in the other formats, the values fp16 would clamp
+ *   n_f16_tiny              non-zero finite values with |x| < 2^-14 (fp16's subnormal range)
+ *   reserved                zero
+ * The records are bit-reproducible and an image's record does not depend on the batch it is in: a workgroup owns a fixed pixel
+ * range of one image, the finish adds an image's partials in index order, and there are no atomics. */
+#define ESAHRNET_STATS_RECORD_BYTES 64
+#define ESAHRNET_STATS_FIELDS(X) \
+    X(double, sum_abs)           \
+    X(float, max_abs)            \
+    X(float, min)                \
+    X(float, max)                \
+    X(uint32_t, n_finite)        \
+    X(uint32_t, n_nan)           \
+    X(uint32_t, n_inf)           \
+    X(uint32_t, n_zero)          \
+    X(uint32_t, n_ge_f16max)     \
+    X(uint32_t, n_f16_tiny)
+typedef struct esahrnet_stats_record {
+#define ESAHRNET_STATS_X(type, name) type name;
+    ESAHRNET_STATS_FIELDS(ESAHRNET_STATS_X)
+#undef ESAHRNET_STATS_X
+    uint32_t reserved[5];
+} esahrnet_stats_record;
+
+/* The rows of a handle's report: every tensor of its plan in plan order, then a last row "heatmaps" (the output in caller
+ * memory).  Both queries work on an uncommitted handle and change nothing. */
+typedef struct esahrnet_stats_row_desc {
+    char name[96];               /* the tap name where the tensor has one, else the label of the op that defines it */
+    int def_op;                  /* index of that op (esahrnet_op_desc_get); "heatmaps": the last op */
+    int c, h, w;                 /* real channels and extent at this crop size (0, 0, 0 for flat scratch) */
+    int fmt;                     /* storage: 0 split bf16, 1 bf16, 2 f32 NHWC, 3 fp16, -1 f32 NCHW (the heat-maps) */
+    int scanned;                 /* 0: not read at this shape, the row's records stay all zero: plain f32 scratch without the
+                                  * padded-channel layout (CBAM's pooled vectors, channel weights and two-plane maps), the head
+                                  * terms in the transposed T layout, and the tensors of the head alternative that does not run */
+} esahrnet_stats_row_desc;
+int esahrnet_stats_rows(esahrnet_handle h, int* rows);
+int esahrnet_stats_row_get(esahrnet_handle h, int row, int n, int height, int width, esahrnet_stats_row_desc* out);
+/* The forward with every buffer kept (the plan and the launches of esahrnet_forward under esahrnet_set_debug_keep(h, 1)), then
+ * the scan of every scanned row where it lies.  heat_dev: the heat-maps, as esahrnet_forward writes them.  stats_dev:
+ * esahrnet_stats_record [rows][n], every byte written.  Nothing is allocated, nothing synchronised; the handle's keep state is
+ * left as found.  Refused before the first launch, in esahrnet_forward's order: null argument, not committed, shape,
+ * workspace size (esahrnet_forward_stats_workspace_bytes), workspace alignment (256), stats_dev alignment (8). */
+int esahrnet_forward_stats_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes);
+int esahrnet_forward_stats(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* heat_dev, void* ws_dev,
+                           size_t ws_bytes, void* stats_dev, esahrnet_stream stream);
+/* The scan alone, of one raw tensor t_dev [n][h][w][cp] in format fmt (0..3 as above; real channels 0..c-1), or, fmt == -1,
+ * plain f32 [n][c][h][w] (cp ignored): n records into stats_dev.  ws_dev: 8-byte aligned scratch for the partials. */
+int esahrnet_tensor_stats_workspace_bytes(int fmt, int n, int c, int cp, int h, int w, size_t* bytes);
+int esahrnet_tensor_stats(const void* t_dev, int fmt, int n, int c, int cp, int h, int w, void* ws_dev, size_t ws_bytes,
+                          void* stats_dev, esahrnet_stream stream);
+
 /* Stand-alone convolution on f32 NCHW device tensors through the same MFMA kernels:
  * y = [relu]( conv_{k,stride,pad=(k-1)/2}(x; w) + b [+ res] ).  w,b are HOST pointers
  * (packed and uploaded on the spot; synchronous; test use only). */
