@@ -1295,6 +1295,17 @@ int upload(const std::vector<T>& host, void** dev) {
     return 0;
 }
 
+// conv1 of a stem: host f32 [cout][cin][3][3] -> the stem kernels' [coutp/8][cin][9][8] (stem.hip, stem_fused.hip), the channels
+// cout .. coutp-1 zero.  The one packing of that layout: esahrnet_commit and the stem test entries all come through here.
+std::vector<float> pack_stem_w(const float* w, int cout, int cin, int coutp) {
+    std::vector<float> out((size_t)coutp * cin * 9, 0.f);
+    for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int t = 0; t < 9; ++t)
+                out[(((size_t)(co >> 3) * cin + ci) * 9 + t) * 8 + (co & 7)] = w[((size_t)co * cin + ci) * 9 + t];
+    return out;
+}
+
 }  // namespace
 
 // ============================================ C ABI ============================================
@@ -1546,13 +1557,8 @@ int esahrnet_commit(esahrnet_handle h) {
     {   // stem: [cout/8][cin][9][8]
         const ConvSpec& s = h->specs[h->spec_stem];
         const int coutp = h->padc(s.cout);
-        std::vector<float> w((size_t)coutp * s.cin * 9, 0.f), b(coutp, 0.f);
-        for (int co = 0; co < s.cout; ++co) {
-            b[co] = s.b[co];
-            for (int ci = 0; ci < s.cin; ++ci)
-                for (int t = 0; t < 9; ++t)
-                    w[(((size_t)(co >> 3) * s.cin + ci) * 9 + t) * 8 + (co & 7)] = s.w[((size_t)co * s.cin + ci) * 9 + t];
-        }
+        std::vector<float> w = pack_stem_w(s.w.data(), s.cout, s.cin, coutp), b(coutp, 0.f);
+        std::copy(s.b.begin(), s.b.begin() + s.cout, b.begin());
         if (h->opt.stem == STEM_FUSED_X6) {      // stem_x6_kernel reads conv1 in its own layout (bias inside)
             std::vector<float> wx(2 * 4 * 10 * 8, 0.f);
             esa::pack_stem_w1_x6(s.w.data(), s.b.data(), wx.data());
@@ -1583,11 +1589,7 @@ int esahrnet_commit(esahrnet_handle h) {
         if (o.kind == OP_STEMRAW) {   // un-normalised conv1 in the stem kernel's [cout/8][cin][9][8] layout, zero bias
             const AuxSpec& a = h->aux[o.aux[0]];
             const int cout = a.shape[0], cin = a.shape[1], coutp = h->padc(cout);
-            std::vector<float> w((size_t)coutp * cin * 9, 0.f), b(coutp, 0.f);
-            for (int co = 0; co < cout; ++co)
-                for (int ci = 0; ci < cin; ++ci)
-                    for (int t = 0; t < 9; ++t)
-                        w[(((size_t)(co >> 3) * cin + ci) * 9 + t) * 8 + (co & 7)] = a.data[((size_t)co * cin + ci) * 9 + t];
+            const std::vector<float> w = pack_stem_w(a.data.data(), cout, cin, coutp), b(coutp, 0.f);
             if (upload(w, reinterpret_cast<void**>(&h->stemraw_w)) || upload(b, reinterpret_cast<void**>(&h->stemraw_b))) return 1;
         }
     if (h->spec_l0 >= 0) {   // fused head: W0 slice (standard pack), W3 (permuted-K pack), biases
@@ -2979,9 +2981,7 @@ int esahrnet_op_stem(const void* x_dev, int n, int height, int width, const floa
     const bool bf = precision == 1;
     const int fmt = bf ? esa::FMT_BF : precision == 2 ? esa::FMT_F32 : esa::FMT_SB;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    std::vector<float> wp((size_t)cout * 9, 0.f), bp(b, b + cout);          // [cout/8][1][9][8], as esahrnet_commit packs conv1
-    for (int co = 0; co < cout; ++co)
-        for (int t = 0; t < 9; ++t) wp[((size_t)(co >> 3) * 9 + t) * 8 + (co & 7)] = w[(size_t)co * 9 + t];
+    const std::vector<float> wp = pack_stem_w(w, cout, 1, cout), bp(b, b + cout);      // [cout/8][1][9][8], esahrnet_commit's packing
     void *dw = nullptr, *db = nullptr, *ys = nullptr, *part = nullptr;
     auto cleanup = [&]() { for (void* p : {dw, db, ys, part}) if (p) (void)hipFree(p); };
     if (upload(wp, &dw) || upload(bp, &db)) { cleanup(); return 1; }
@@ -3274,11 +3274,7 @@ int esahrnet_op_stem2(const void* x_dev, int n, int cin, int height, int width, 
         w1p.assign(2 * 4 * 10 * 8, 0.f);
         esa::pack_stem_w1_x6(w1, b1, w1p.data());
     } else {                                    // [cmid/8][cin][9][8]
-        w1p.assign((size_t)cmid * cin * 9, 0.f);
-        for (int co = 0; co < cmid; ++co)
-            for (int ci = 0; ci < cin; ++ci)
-                for (int t = 0; t < 9; ++t)
-                    w1p[(((size_t)(co >> 3) * cin + ci) * 9 + t) * 8 + (co & 7)] = w1[((size_t)co * cin + ci) * 9 + t];
+        w1p = pack_stem_w(w1, cmid, cin, cmid);
     }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     void *dw1 = nullptr, *db1 = nullptr, *dw2 = nullptr, *db2 = nullptr, *ys = nullptr;
@@ -3296,6 +3292,88 @@ int esahrnet_op_stem2(const void* x_dev, int n, int cin, int height, int width, 
     cleanup();
     if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
     if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
+    return 0;
+}
+
+// ---- the stem outside esahrnet_op_stem's one configuration, the layout conversions and the tile-maximum kernels on their own
+// (tests/test_gpu_layout.py) ---------------------------------------------------------------------------------------------------
+int esahrnet_op_stem_ex(const void* x_dev, int n, int cin, int height, int width, const float* w, const float* b, int cout,
+                        int relu, int precision, void* y_dev, esahrnet_stream stream_) {
+    const char* who = "op_stem_ex";
+    OpFmt f;
+    if (!x_dev || !w || !b || !y_dev) return fail("%s: null argument", who);
+    if (!op_fmt(precision, &f)) return fail("%s: precision %d (0 .. 3)", who, precision);
+    if (cin < 1 || cin > 4) return fail("%s: cin=%d (1 .. 4)", who, cin);
+    if (cout <= 0 || (cout & 31)) return fail("%s: cout=%d (a positive multiple of 32)", who, cout);
+    if (f.half && (cout & 63)) return fail("%s: cout=%d (the 16-bit formats hold blocks of 64 channels)", who, cout);
+    if (n <= 0 || height <= 0 || width <= 0 || (long long)n * height * width * cout * 4 > 0x7fffffffLL)
+        return fail("%s: n=%d %dx%d cout=%d unsupported", who, n, height, width, cout);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const std::vector<float> wp = pack_stem_w(w, cout, cin, cout), bp(b, b + cout);     // esahrnet_commit's packing of conv1
+    void *dw = nullptr, *db = nullptr, *ys = nullptr;
+    auto cleanup = [&]() { for (void* q : {dw, db, ys}) if (q) (void)hipFree(q); };
+    if (upload(wp, &dw) || upload(bp, &db)) { cleanup(); return 1; }
+    if (hipMalloc(&ys, (size_t)n * height * width * cout * f.eb) != hipSuccess) { cleanup(); return fail("%s: hipMalloc failed", who); }
+    esa::StemParams p{static_cast<const float*>(x_dev), static_cast<char*>(ys), static_cast<const float*>(dw),
+                      static_cast<const float*>(db), n, height, width, cin, cout, relu ? 1 : 0, f.fmt};
+    int rc = esa::launch_stem(p, stream);
+    if (!rc) rc = esa::launch_fmt_to_nchw(f.fmt, static_cast<const char*>(ys), n, cout, height, width, cout, static_cast<float*>(y_dev), stream);
+    hipError_t se = hipStreamSynchronize(stream);
+    cleanup();
+    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
+    return 0;
+}
+
+int esahrnet_op_layout(int dir, const void* x_dev, int n, int c, int height, int width, int cp, int precision, void* raw_dev,
+                       void* y_dev, esahrnet_stream stream_) {
+    const char* who = "op_layout";
+    OpFmt f;
+    if (dir != 0 && dir != 1) return fail("%s: dir=%d (0: f32 NCHW -> raw -> f32 NCHW, 1: raw -> f32 NCHW)", who, dir);
+    if (!raw_dev || !y_dev || (dir == 0 && !x_dev)) return fail("%s: null argument", who);
+    if (!op_fmt(precision, &f)) return fail("%s: precision %d (0 .. 3)", who, precision);
+    if (n <= 0 || c <= 0 || height <= 0 || width <= 0) return fail("%s: n=%d c=%d %dx%d unsupported", who, n, c, height, width);
+    if (cp < c || (cp & 7)) return fail("%s: cp=%d (a multiple of 8, at least c=%d)", who, cp, c);
+    if ((long long)n * height * width * cp * 4 > 0x7fffffffLL) return fail("%s: n=%d cp=%d %dx%d unsupported", who, n, cp, height, width);
+    if ((reinterpret_cast<uintptr_t>(raw_dev) & 15) || (reinterpret_cast<uintptr_t>(y_dev) & 3) || (reinterpret_cast<uintptr_t>(x_dev) & 3))
+        return fail("%s: raw_dev must be 16-byte aligned, x_dev and y_dev 4-byte aligned", who);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc = 0;
+    if (dir == 0) rc = esa::launch_nchw_to_fmt(f.fmt, static_cast<const float*>(x_dev), n, c, height, width, static_cast<char*>(raw_dev), cp, stream);
+    if (!rc) rc = esa::launch_fmt_to_nchw(f.fmt, static_cast<const char*>(raw_dev), n, c, height, width, cp, static_cast<float*>(y_dev), stream);
+    hipError_t se = hipStreamSynchronize(stream);
+    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
+    return 0;
+}
+
+int esahrnet_op_tile_max(const void* raw_dev, int n, int c, int height, int width, int cp, int precision, int store, void* y_dev,
+                         void* part_dev, int* ntiles_out, void* kp_dev, void* idx_dev, esahrnet_stream stream_) {
+    const char* who = "op_tile_max";
+    if (!raw_dev || !part_dev || !ntiles_out) return fail("%s: null argument", who);
+    if (precision != 0 && precision != 2) return fail("%s: precision %d (0: split-bf16, 2: f32)", who, precision);
+    if (store != 0 && store != 1) return fail("%s: store=%d (0 or 1)", who, store);
+    if (store && !y_dev) return fail("%s: store = 1 needs y_dev", who);
+    if (n <= 0 || height <= 0 || width <= 0) return fail("%s: n=%d %dx%d unsupported", who, n, height, width);
+    if (c < 1 || c > 32) return fail("%s: c=%d (1 .. 32)", who, c);
+    if (cp < c || (cp & 7)) return fail("%s: cp=%d (a multiple of 8, at least c=%d)", who, cp, c);
+    if ((long long)n * height * width * cp * 4 > 0x7fffffffLL) return fail("%s: n=%d cp=%d %dx%d unsupported", who, n, cp, height, width);
+    if ((reinterpret_cast<uintptr_t>(raw_dev) & 15) || (reinterpret_cast<uintptr_t>(part_dev) & 7) || (reinterpret_cast<uintptr_t>(y_dev) & 3) ||
+        (reinterpret_cast<uintptr_t>(kp_dev) & 3) || (reinterpret_cast<uintptr_t>(idx_dev) & 3))
+        return fail("%s: raw_dev must be 16-byte aligned, part_dev 8-byte, y_dev, kp_dev and idx_dev 4-byte", who);
+    const int fmt = precision == 2 ? esa::FMT_F32 : esa::FMT_SB, ntiles = esa::to_nchw_part_tiles(height, width);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const char* raw = static_cast<const char*>(raw_dev);
+    float2* part = static_cast<float2*>(part_dev);
+    int rc = store ? esa::launch_to_nchw_part(fmt, raw, n, c, height, width, cp, static_cast<float*>(y_dev), part, stream)
+                   : esa::launch_tile_max(fmt, raw, n, c, height, width, cp, part, stream);
+    if (!rc && kp_dev)
+        rc = esa::launch_keypoints_finish_nhwc(fmt, raw, n, c, height, width, cp, part, ntiles, static_cast<float*>(kp_dev),
+                                               static_cast<int*>(idx_dev), stream);
+    hipError_t se = hipStreamSynchronize(stream);
+    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
+    *ntiles_out = ntiles;
     return 0;
 }
 

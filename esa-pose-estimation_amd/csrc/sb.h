@@ -25,7 +25,9 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t b) { return __uint_as_float(b << 16); }
 
 // Round-to-nearest-even f32 -> bf16 bits (finite inputs; the network never produces NaN
-// from finite weights/inputs).
+// from finite weights/inputs).  The carry runs into the exponent and into infinity: every |v| from bit pattern 0x7f7f8000 up
+// becomes +-inf.  Subnormal inputs and results are kept; a NaN stays a NaN (quieted).  tests/layout_ref.py states all of it on
+// bit patterns, tests/test_gpu_layout.py holds the device to that.
 __device__ __forceinline__ uint32_t f32_to_bf16_bits(float x) {
     __bf16 h = (__bf16)x;
     return (uint32_t)__builtin_bit_cast(unsigned short, h);
@@ -44,7 +46,9 @@ typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
 // Two floats -> one dword of hi bf16 (a in the low half) + one dword of lo bf16: v_cvt_pk_bf16_f32 on
 // the pair, the residuals against the packed hi halves, v_cvt_pk_bf16_f32 again (6 VALU ops per pair;
-// same round-to-nearest-even results as split_bf16 element by element).
+// same round-to-nearest-even results as split_bf16 element by element).  The subtraction is exact while hi is finite, and
+// subnormal hi / lo parts are stored as such.  The format has no inf and no value from 0x7f7f8000 up: hi = +-inf there, the
+// residual is -+inf (NaN for an inf), and the join hi + lo is NaN — a finite f32 in the top 2^-9 of the range included.
 __device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
     const f32x2 v = {a, b};
     const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
@@ -205,7 +209,9 @@ __device__ __forceinline__ f32x4 mfma_el(bf16x8 a, bf16x8 b, f32x4 c) {
 // Two floats -> two fp16 in one dword, round to nearest even (v_cvt_pk_f16_f32 on gfx950 — NOT v_cvt_pkrtz_f16_f32,
 // which truncates), then SATURATED on the packed halves: |v| beyond 65504 — the conversion's +-inf — becomes +-65504
 // (v_pk_min_f16 / v_pk_max_f16, one VALU op each per pair).  An inf would meet a zero interpolation weight in the
-// next fuse (inf * 0 = NaN) and the decoder takes a NaN for the arg-max.  Subnormal results are kept.
+// next fuse (inf * 0 = NaN) and the decoder takes a NaN for the arg-max.  Subnormal results are kept.  A NaN is stored as
+// +65504 whatever its sign: the packed min returns the operand that is a number, the max keeps it (measured: tests/
+// test_gpu_layout.py; tests/fp16_emu.py's q16 keeps the NaN, the one class where it differs from this store).
 #ifndef ESA_HF_NOCLAMP
 #define ESA_HF_NOCLAMP 0      // timing experiment only: 1 compiles the saturation out.  0 in the product build.
 #endif

@@ -237,7 +237,7 @@ int launch_stem_pool(const StemParams& p, float* pool, hipStream_t stream) {
 }
 
 int launch_stem(const StemParams& p, hipStream_t stream) {
-    if ((p.cout & 31) || p.cin < 1 || p.cin > 4 || (p.fmt == FMT_HF && (p.cout & 63))) return (int)hipErrorInvalidValue;
+    if ((p.cout & 31) || p.cin < 1 || p.cin > 4 || (fmt_half(p.fmt) && (p.cout & 63))) return (int)hipErrorInvalidValue;      // BF / HF: blocks of 64 channels (sb.h)
     if (p.cin == 1) {
         const int xgroups = (p.W + STEM_PX - 1) / STEM_PX;
         const long long total1 = (long long)p.N * p.H * xgroups * (p.cout >> 3);

@@ -742,6 +742,31 @@ int esahrnet_op_block32(const void* x_dev, int n, int height, int width, const f
 int esahrnet_op_stem2(const void* x_dev, int n, int cin, int height, int width, const float* w1, const float* b1, int cmid,
                       const float* w2, const float* b2, int cout, int precision, void* y_dev, esahrnet_stream stream);
 
+/* ---- the stem, the layout conversions and the tile-maximum kernels on their own (test use only; none of these is on a
+ * forward path) ------------------------------------------------------------------------------------------------------------
+ * All are synchronous and check every argument before anything is allocated or enqueued: a refusal returns non-zero with
+ * esahrnet_last_error set and leaves the outputs as they were.  `precision` as above (0: split-bf16, 1: bf16, 2: f32, 3: fp16). */
+/* conv1 of a stem through launch_stem, any cin 1 .. 4 and any cout the launcher takes (a multiple of 32; of 64 in the two
+ * 16-bit formats): y = [relu]( conv3x3_pad1(x; w) + b ) in the format of `precision`, converted back exactly to f32 NCHW.
+ * x_dev f32 [n][cin][height][width]; w [cout][cin][3][3] and b [cout]: host f32, packed by the function esahrnet_commit packs
+ * conv1 with; y_dev f32 [n][cout][height][width].  cin == 1 runs stem1_kernel / stem1_hf_kernel, cin 2 .. 4 stem_kernel. */
+int esahrnet_op_stem_ex(const void* x_dev, int n, int cin, int height, int width, const float* w, const float* b, int cout,
+                        int relu, int precision, void* y_dev, esahrnet_stream stream);
+/* The conversions of layout.hip.  raw_dev: the tensor [n][height][width][cp] in the format of `precision`, n * height * width *
+ * cp * (2 in the 16-bit formats, else 4) bytes the caller owns, 16-byte aligned; c <= cp, cp a multiple of 8.
+ * dir 0: launch_nchw_to_fmt from x_dev (f32 [n][c][height][width]) into raw_dev — every byte of it is written, the channels
+ * c .. cp-1 as +0 —, then launch_fmt_to_nchw from raw_dev into y_dev (f32 [n][c][height][width]).  dir 1: only the second
+ * step, on the bytes raw_dev holds (x_dev is not used). */
+int esahrnet_op_layout(int dir, const void* x_dev, int n, int c, int height, int width, int cp, int precision, void* raw_dev,
+                       void* y_dev, esahrnet_stream stream);
+/* The tile maxima of heat-maps raw_dev [n][height][width][cp] (precision 0: split-bf16, 2: f32; c <= 32, c <= cp, cp a multiple
+ * of 8): part_dev 8 bytes x [n * c][ntiles] (f32 value, int32 index row * width + column) — each tile of 256 row-major pixels'
+ * first maximum, a NaN counting as the largest —, *ntiles_out = ceil(height * width / 256).  store 1: launch_to_nchw_part, which
+ * also writes y_dev f32 [n][c][height][width]; store 0: launch_tile_max, y_dev is not touched and may be NULL.  kp_dev not NULL:
+ * launch_keypoints_finish_nhwc over the same part, kp_dev f32 [n][c][3] and idx_dev int32 [n][c] (may be NULL). */
+int esahrnet_op_tile_max(const void* raw_dev, int n, int c, int height, int width, int cp, int precision, int store, void* y_dev,
+                         void* part_dev, int* ntiles_out, void* kp_dev, void* idx_dev, esahrnet_stream stream);
+
 /* ---- test hooks ------------------------------------------------------------------------------------ */
 /* Launch state is kept per DEVICE (dynamic-LDS limits raised per kernel and device, CU counts), never in
  * process-wide flags: number of (kernel, device) entries and of devices seen so far. */

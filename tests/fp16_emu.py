@@ -33,7 +33,9 @@ EMU_THREADS = 4
 
 
 def q16(t: torch.Tensor) -> torch.Tensor:
-    """f32 -> fp16 (nearest even) -> f32, +-inf of the conversion replaced by +-65504."""
+    """f32 -> fp16 (nearest even) -> f32, +-inf of the conversion replaced by +-65504.  A NaN stays a NaN here (torch.clamp
+    propagates it), where sb.h's pack2_f16 stores +65504: the one class on which the two differ (tests/layout_ref.py
+    F16_NAN_STORE); no tensor of a forward with finite weights and crops holds one."""
     return t.to(torch.float16).to(torch.float32).clamp(-F16_MAX, F16_MAX)
 
 
