@@ -76,6 +76,15 @@ class StatsRowDesc(C.Structure):
                 ("fmt", C.c_int32), ("scanned", C.c_int32)]
 
 
+SCALE_MAX_RANGES = 4              # ESAHRNET_SCALE_MAX_RANGES
+SCALE_MAX_EXPONENT = 32           # ESAHRNET_SCALE_MAX_EXPONENT
+
+
+class ScaleConv(C.Structure):
+    _fields_ = [("out_group", C.c_int32), ("nranges", C.c_int32), ("c0", C.c_int32 * SCALE_MAX_RANGES),
+                ("c1", C.c_int32 * SCALE_MAX_RANGES), ("in_group", C.c_int32 * SCALE_MAX_RANGES)]
+
+
 class EsaHrnetError(RuntimeError):
     pass
 
@@ -208,6 +217,18 @@ _SIGS = {
     "esahrnet_forward_stats_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "esahrnet_forward_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_void_p]),
+    "esahrnet_forward_stats_h0_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "esahrnet_forward_stats_h0": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esahrnet_scale_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "esahrnet_scale_group_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]),
+    "esahrnet_scale_conv_get": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ScaleConv)]),
+    "esahrnet_scale_row_group": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "esahrnet_set_scale_exponents": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "esahrnet_get_scale_exponents": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "esahrnet_debug_scaled_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "esahrnet_scale_exponents_from_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                      C.POINTER(C.c_int32), C.c_int]),
     "esahrnet_tensor_stats_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                        C.POINTER(C.c_size_t)]),
     "esahrnet_tensor_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,

@@ -19,6 +19,7 @@
 // after it.  Unpinned against the reference by itself; the bf16 network tests cover it (tests/test_gpu_bf16.py).
 #include <algorithm>
 
+#include "../../include/esahrnet.h"
 #include "devstate.h"
 #include "kernels.h"
 #include "sb.h"
@@ -73,8 +74,18 @@ __device__ __forceinline__ uint32_t lane_xor4(uint32_t v, bool hi) {
 // EL (sb.h): EL_BF, or EL_HF for the fp16 mode (esahrnet_cfg.precision = 3) — the same kernel on v_mfma_f32_16x16x32_f16 with
 // fp16 tensors, weights and U.  The interpolation weights of the 2x / 4x / 8x grids are exact in fp16 as they are in bf16
 // (numerators < 256 over a power of two); h0 and h3 are rounded to nearest even and saturated (sb.h pack2_f16).
-template <int NB0, int M3, bool MF, int EL = EL_BF>
-__global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(HeadParams p, int tiles_x, int tiles_y, int ulo) {
+// RANGE (the second instantiation, head_fused_bf_kernel<.., uint2*>: the calibration form behind esahrnet_forward_stats_h0): the same arithmetic, the same y, and
+// beside it the range of h0, which no tensor holds — each lane keeps the largest finite h0 BEFORE its rounding (after the ReLU,
+// so h0 = |h0|, and a non-negative float orders as its bit pattern: an integer maximum, exact in any order) and the number of
+// values at or above 65504 (+inf included), over the pixels inside the image; a wave combines them by DPP inside its rows and
+// by readlane across them, the eight waves through the dynamic LDS the chunks no longer need, and the workgroup leaves ONE
+// partial (max bits, count) at range_part[(n * tiles_y + ty) * tiles_x + tx] with an ordinary vector store.  No atomics:
+// head_range_finish_kernel combines a crop's partials, and maximum and integer sum do not depend on the order.
+__device__ __forceinline__ uint2* range_arg() { return nullptr; }
+__device__ __forceinline__ uint2* range_arg(uint2* part) { return part; }
+template <int NB0, int M3, bool MF, int EL = EL_BF, typename... R>
+__global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(HeadParams p, int tiles_x, int tiles_y, int ulo, R... range) {
+    constexpr bool RANGE = sizeof...(R) != 0;       // the range form takes one more argument: uint2* range_part
     constexpr int WFR = 2 * NB0 * 2 + M3;               // 1-KB weight fragments per chunk: W0 [m][block][step], W3 [m]
     constexpr int WBYTES = WFR * 1024;
     constexpr int TB = MF ? TBYTES : BBUF;
@@ -251,6 +262,8 @@ __global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(Hea
     f32x4 acc3[M3];
 #pragma unroll
     for (int m = 0; m < M3; ++m) acc3[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int rmax = 0;                           // RANGE: bits of the lane's largest finite h0
+    uint32_t rcnt = 0;                      // RANGE: the lane's h0 values >= 65504
 
     HB_PREFETCH(0)
     HB_COMMIT(0)
@@ -306,6 +319,16 @@ __global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(Hea
             v[i] = relu1(a[0][i] + s[0][i]);
             v[4 + i] = relu1(a[1][i] + s[1][i]);
         }
+        if constexpr (RANGE) {
+            if (in) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int vb = __builtin_bit_cast(int, v[i]);        // >= 0 behind relu1; above 0x7f800000: a NaN
+                    rmax = vb < 0x7f800000 ? max(rmax, vb) : rmax;
+                    rcnt += vb >= 0x477fe000 && vb <= 0x7f800000;         // 0x477fe000 = 65504.f
+                }
+            }
+        }
         const bf16x8 hh = __builtin_bit_cast(bf16x8, pack8_el<EL>(v));
 #pragma unroll
         for (int m = 0; m < M3; ++m) {
@@ -334,6 +357,57 @@ __global__ __launch_bounds__(BTHREADS, MF ? 4 : 1) void head_fused_bf_kernel(Hea
         }
         for (int c = M3 * 16 + q * 4; c < p.C3p; c += 16) *reinterpret_cast<uint2*>(o + c * 2) = make_uint2(0, 0);
     }
+    if constexpr (RANGE) {
+        // inside a row of 16 lanes: xor 1, xor 2 (quad_perm), then the two mirrors — every lane of the row ends with the row's
+        // result; across the four rows by readlane
+#define HB_ROW_STEP(CTRL)                                                                                          \
+        {                                                                                                          \
+            rmax = max(rmax, __builtin_amdgcn_update_dpp(0, rmax, CTRL, 0xf, 0xf, false));                         \
+            rcnt += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)rcnt, CTRL, 0xf, 0xf, false);                    \
+        }
+        HB_ROW_STEP(0xB1) HB_ROW_STEP(0x4E) HB_ROW_STEP(0x141) HB_ROW_STEP(0x140)
+#undef HB_ROW_STEP
+        int wmax = 0;
+        uint32_t wcnt = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            wmax = max(wmax, __builtin_amdgcn_readlane(rmax, r * 16));
+            wcnt += (uint32_t)__builtin_amdgcn_readlane((int)rcnt, r * 16);
+        }
+        __syncthreads();                    // the last chunk's fragments have been read by every wave
+        uint2* const red = reinterpret_cast<uint2*>(smem);
+        if (lane == 0) red[wave] = make_uint2((uint32_t)wmax, wcnt);
+        __syncthreads();
+        if (tid == 0) {
+            uint2 r = red[0];
+#pragma unroll
+            for (int w_ = 1; w_ < BHY; ++w_) { r.x = max(r.x, red[w_].x); r.y += red[w_].y; }
+            range_arg(range...)[((size_t)n * tiles_y + ty) * tiles_x + tx] = r;
+        }
+    }
+}
+
+// One crop's partials -> its record: one wave per crop, the lanes stride over the crop's tiles.
+__global__ __launch_bounds__(64) void head_range_finish_kernel(const uint2* part, int tiles, esahrnet_stats_record* rec) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    uint32_t mx = 0, cnt = 0;
+    for (int t = lane; t < tiles; t += 64) {
+        const uint2 v = part[(size_t)n * tiles + t];
+        mx = max(mx, v.x);
+        cnt += v.y;
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, m));
+        cnt += (uint32_t)__shfl_xor((int)cnt, m);
+    }
+    if (lane == 0) {
+        esahrnet_stats_record r{};
+        r.max_abs = __uint_as_float(mx);
+        r.max = r.max_abs;
+        r.n_ge_f16max = cnt;
+        rec[n] = r;
+    }
 }
 
 template <int NB0, int M3, bool MF, int EL = EL_BF>
@@ -348,6 +422,22 @@ int launch_head_bf_t(const HeadParams& p, hipStream_t stream) {
     const long long nblk = (long long)p.N * tiles_x * tiles_y;
     if (nblk <= 0 || nblk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(BTHREADS), lds, stream, p, tiles_x, tiles_y, ulo);
+    return (int)hipGetLastError();
+}
+
+template <int NB0, int M3, int EL>
+int launch_head_bf_range_t(const HeadParams& p, uint2* part, esahrnet_stats_record* rec, hipStream_t stream) {
+    auto kern = head_fused_bf_kernel<NB0, M3, true, EL, uint2*>;
+    const int lds = 2 * (TBYTES + (2 * NB0 * 2 + M3) * 1024);
+    int ulo = 0;
+    for (int b = 0; b < 3; ++b) ulo |= (p.th[b] << (b + 1)) != p.H || (p.tw[b] << (b + 1)) != p.W;
+    if (const int e_ = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds)) return e_;
+    const int tiles_x = (p.W + BHT - 1) / BHT, tiles_y = (p.H + BHY - 1) / BHY;
+    const long long nblk = (long long)p.N * tiles_x * tiles_y;
+    if (nblk <= 0 || nblk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(BTHREADS), lds, stream, p, tiles_x, tiles_y, ulo, part);
+    if (const int e_ = (int)hipGetLastError()) return e_;
+    hipLaunchKernelGGL(head_range_finish_kernel, dim3((unsigned)p.N), dim3(64), 0, stream, part, tiles_x * tiles_y, rec);
     return (int)hipGetLastError();
 }
 
@@ -400,6 +490,29 @@ int launch_head_bf(const HeadParams& p, hipStream_t stream) {
     if (p.C0p == 64 && m3 == 2) return launch_head_bf_t<1, 2, true>(p, stream);
     if (p.C0p == 128 && m3 == 1) return launch_head_bf_t<2, 1, true>(p, stream);
     if (p.C0p == 128 && m3 == 2) return launch_head_bf_t<2, 2, true>(p, stream);
+    return (int)hipErrorInvalidValue;
+}
+
+// The calibration form: launch_head_bf's matrix-core kernel with the range of h0 beside it.  part: head_bf_range_tiles(H, W) * N
+// partials of 8 bytes (8-byte aligned, every one written), rec: N records of which max_abs (= max), and n_ge_f16max are filled
+// and the rest is zero.  y is what launch_head_bf writes, bit for bit.
+int head_bf_range_tiles(int H, int W) { return ((W + BHT - 1) / BHT) * ((H + BHY - 1) / BHY); }
+int launch_head_bf_range(const HeadParams& p, void* part, void* rec, hipStream_t stream) {
+    if ((p.Ctp & 31) || (p.C3p & 3) || p.valu || !part || !rec) return (int)hipErrorInvalidValue;
+    const int m3 = p.K <= 16 ? 1 : 2;
+    uint2* const pt = static_cast<uint2*>(part);
+    esahrnet_stats_record* const r = static_cast<esahrnet_stats_record*>(rec);
+    if (p.hf) {
+        if (p.C0p == 64 && m3 == 1) return launch_head_bf_range_t<1, 1, EL_HF>(p, pt, r, stream);
+        if (p.C0p == 64 && m3 == 2) return launch_head_bf_range_t<1, 2, EL_HF>(p, pt, r, stream);
+        if (p.C0p == 128 && m3 == 1) return launch_head_bf_range_t<2, 1, EL_HF>(p, pt, r, stream);
+        if (p.C0p == 128 && m3 == 2) return launch_head_bf_range_t<2, 2, EL_HF>(p, pt, r, stream);
+        return (int)hipErrorInvalidValue;
+    }
+    if (p.C0p == 64 && m3 == 1) return launch_head_bf_range_t<1, 1, EL_BF>(p, pt, r, stream);
+    if (p.C0p == 64 && m3 == 2) return launch_head_bf_range_t<1, 2, EL_BF>(p, pt, r, stream);
+    if (p.C0p == 128 && m3 == 1) return launch_head_bf_range_t<2, 1, EL_BF>(p, pt, r, stream);
+    if (p.C0p == 128 && m3 == 2) return launch_head_bf_range_t<2, 2, EL_BF>(p, pt, r, stream);
     return (int)hipErrorInvalidValue;
 }
 

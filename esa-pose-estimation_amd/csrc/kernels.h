@@ -222,6 +222,11 @@ void pack_head_w3(const float* w, int K, int Ct, int Ctp, void* dst);
 // [Ctp/16][C0p/64][K-step][64], w3 = pack_head_w3_bf [M3][Ctp/32][64] (one bf16 fragment per chunk)
 int launch_head_bf(const HeadParams& p, hipStream_t stream);
 bool head_fused_bf_supported(int H, int W, const int th[3], const int tw[3], int C0p, int K);
+// the calibration form (esahrnet_forward_stats_h0): the matrix-core kernel of launch_head_bf with the range of h0 — which is
+// rounded in registers and never stored — beside it.  part: head_bf_range_tiles(H, W) * N partials of 8 bytes, rec: N
+// esahrnet_stats_record (max_abs, max and n_ge_f16max filled, taken BEFORE the rounding; the rest zero).  Not for p.valu.
+int head_bf_range_tiles(int H, int W);
+int launch_head_bf_range(const HeadParams& p, void* part, void* rec, hipStream_t stream);
 size_t head_w3_bf_bytes(int K, int Ctp);
 void pack_head_w3_bf(const float* w, int K, int Ct, int Ctp, void* dst, bool half = false);     // half: fp16 elements (FMT_HF)
 
@@ -433,6 +438,8 @@ int launch_f32_to_nchw(const char* x, int N, int C, int H, int W, int Cp, float*
 // by format code
 int launch_nchw_to_fmt(int fmt, const float* x, int N, int C, int H, int W, char* y, int Cp, hipStream_t s);
 int launch_fmt_to_nchw(int fmt, const char* x, int N, int C, int H, int W, int Cp, float* y, hipStream_t s);
+// FMT_HF only: the same conversion times `scale`, a power of two (esahrnet_tap_read under fp16 scale exponents)
+int launch_hf_to_nchw_scaled(const char* x, int N, int C, int H, int W, int Cp, float* y, float scale, hipStream_t s);
 // f32 / SB (fmt) NHWC heat-maps -> f32 NCHW plus each tile's first maximum, part [N*C][to_nchw_part_tiles(H, W)] (value,
 // index bits) as keypoints_finish reads it; C <= 32
 int to_nchw_part_tiles(int H, int W);

@@ -57,6 +57,21 @@ __global__ __launch_bounds__(256) void sb_to_nchw_kernel(const char* x, int N, i
     y[idx] = bf16_bits_to_f32(hi) + bf16_bits_to_f32(lo);
 }
 
+// HF -> NCHW at true scale (esahrnet_tap_read of a tensor stored as T * 2^-e): the conversion above times 2^e, one exact
+// multiply (a power of two; beyond f32's range only for a value no forward can hold).  A kernel of its own, so that the
+// conversion every other caller uses keeps its code.
+__global__ __launch_bounds__(256) void hf_to_nchw_scaled_kernel(const char* x, int C, long long hw, int Cp, float* y, long long total,
+                                                                float scale) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;   // over (n, c, s), s fastest
+    if (idx >= total) return;
+    const long long s = idx % hw;
+    const long long nc = idx / hw;
+    const int c = (int)(nc % C);
+    const long long n = nc / C;
+    const uint32_t b = *reinterpret_cast<const unsigned short*>(x + ((size_t)n * hw + s) * (size_t)(Cp * 2) + c * 2);
+    y[idx] = f16_bits_to_f32(b) * scale;
+}
+
 // SB -> NCHW for the network output: thread = (pixel, 8-channel group), group fastest, so a wave reads whole pixels
 // (contiguous 32-byte groups) and writes 64-byte runs of 16 consecutive pixels into each of its planes.  The element-wise
 // kernel above (thread = output element) touches a different 128-byte line per lane for two bytes: 0.9 TB/s.
@@ -269,6 +284,14 @@ int launch_hf_to_nchw(const char* x, int N, int C, int H, int W, int Cp, float* 
     const long long nblk = (total + 255) / 256;
     if (nblk <= 0 || nblk > 0x7fffffffLL || C > Cp) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(sb_to_nchw_kernel<EL_HF>, dim3((unsigned)nblk), dim3(256), 0, s, x, N, C, H, W, Cp, y, total);
+    return (int)hipGetLastError();
+}
+
+int launch_hf_to_nchw_scaled(const char* x, int N, int C, int H, int W, int Cp, float* y, float scale, hipStream_t s) {
+    const long long total = (long long)N * C * H * W;
+    const long long nblk = (total + 255) / 256;
+    if (nblk <= 0 || nblk > 0x7fffffffLL || C > Cp) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(hf_to_nchw_scaled_kernel, dim3((unsigned)nblk), dim3(256), 0, s, x, C, (long long)H * W, Cp, y, total, scale);
     return (int)hipGetLastError();
 }
 

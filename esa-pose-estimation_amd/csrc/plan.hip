@@ -276,6 +276,13 @@ struct esahrnet_ctx {
     int stemraw_partial = -1;   // seg_hrnet3: tensor of the pooled partials of the raw stem output when the stem kernel makes them
     std::vector<Multi> multis;
     std::vector<JobGroup> jobs;
+    // fp16 scale groups (build_scale_groups; variant 0 in a 16-bit format, else none): the group of every tensor (-1: none), a
+    // name per group, and the exponent the host gave each (tensor T of group g is stored as T * 2^-exps[g]; all zero by default)
+    std::vector<int> tgroup;
+    std::vector<std::string> gnames;
+    std::vector<int32_t> exps;
+    bool scaled() const { for (int32_t e : exps) if (e) return true; return false; }
+    int gexp(int g) const { return g < 0 ? 0 : exps[g]; }
 };
 
 namespace {
@@ -968,6 +975,135 @@ int build_plan_ops(esahrnet_ctx& c) {
     return 0;
 }
 
+// ---- fp16 scale groups ------------------------------------------------------------------------------------
+// With BatchNorm folded, seg_hrnet / seg_hrnet2 is convolution, bias, ReLU, sums and bilinear interpolation, all of which
+// commute exactly with a power of two: tensor T may be stored as T * 2^-e if the next convolution's weights take 2^(e_in -
+// e_out) and its bias 2^-e_out.  Tensors that reach each other WITHOUT convolution weights in between must share e: a
+// residual and the sum it enters, the terms of a fuse sum and its result, the slices of last_layer[0] with the h0 the fused
+// head forms from them in registers, the head3 of either head alternative (one output layer reads both).  Read off the op
+// list, so every stage table gets its own groups.  Groups are numbered by their first tensor in plan order.
+int build_scale_groups(esahrnet_ctx& c) {
+    c.tgroup.assign(c.tensors.size(), -1);
+    c.gnames.clear();
+    c.exps.clear();
+    if (c.cfg.variant != 0 || !c.h16()) return 0;
+    std::vector<int> parent(c.tensors.size());
+    for (size_t i = 0; i < parent.size(); ++i) parent[i] = (int)i;
+    auto find = [&](int a) { while (parent[a] != a) a = parent[a] = parent[parent[a]]; return a; };
+    auto join = [&](int a, int b) {
+        if (a < 0 || b < 0) return;
+        a = find(a); b = find(b);
+        if (a != b) parent[std::max(a, b)] = std::min(a, b);      // the root is the group's first tensor
+    };
+    int final_in = -1;
+    for (const Op& o : c.ops) {
+        switch (o.kind) {
+            case OP_STEM: break;
+            case OP_CONV: join(o.out, o.res); break;
+            case OP_FUSE: for (int i = 0; i < o.nterms; ++i) join(o.out, o.terms[i]); break;
+            case OP_HEADBF: for (int i = 1; i < o.nterms; ++i) join(o.terms[0], o.terms[i]); break;
+            case OP_FINAL: join(final_in, o.in); final_in = o.in; break;
+            default: return fail("scale groups: the plan holds an op (kind %d) the 16-bit formats of variant 0 do not have", (int)o.kind);
+        }
+    }
+    std::vector<int> gid(c.tensors.size(), -1);
+    for (size_t t = 0; t < c.tensors.size(); ++t) {
+        if (c.tensors[t].flat || c.tensors[t].f32 || c.tensors[t].def < 0) continue;
+        const int r = find((int)t);
+        if (gid[r] < 0) { gid[r] = (int)c.gnames.size(); c.gnames.push_back(""); }
+        c.tgroup[t] = gid[r];
+    }
+    // names: the branch stream a "stageS.I" tap belongs to, else a tap of the group (stem1, stem2, head0, head3), else the
+    // convolution that writes the group's first tensor
+    for (size_t t = 0; t < c.tensors.size(); ++t) {
+        const int g = c.tgroup[t];
+        if (g < 0) continue;
+        const std::string& tap = c.tensors[t].tap;
+        int s = 0, i = 0;
+        char tail = 0;
+        if (sscanf(tap.c_str(), "stage%d.%d%c", &s, &i, &tail) == 2) c.gnames[g] = "stream" + std::to_string(i);
+        else if (c.gnames[g].empty() && !tap.empty() && tap.compare(0, 5, "conv:") != 0 && tap != "layer1" && tap != "head3_fused") c.gnames[g] = tap;
+    }
+    for (size_t t = 0; t < c.tensors.size(); ++t) {
+        const int g = c.tgroup[t];
+        if (g < 0 || !c.gnames[g].empty()) continue;
+        const Op& o = c.ops[c.tensors[t].def];
+        c.gnames[g] = o.kind == OP_CONV ? c.specs[c.dconvs[o.dconv].spec].name : "tensor" + std::to_string(t);
+    }
+    c.exps.assign(c.gnames.size(), 0);
+    return 0;
+}
+
+// Where convolution `index` (a host spec) sits among the groups: the group its output is stored in (-1: none, the f32 heat-maps)
+// and the group of each range of its input channels (-1: the f32 crop), ranges in channel order.
+struct ScaleRange { int c0, c1, group; };
+int scale_conv_info(const esahrnet_ctx& c, int index, int* out_group, std::vector<ScaleRange>& ranges) {
+    ranges.clear();
+    const ConvSpec& s = c.specs[index];
+    if (c.gnames.empty()) return fail("scale groups: this handle has none (variant 0 with precision 1 or 3 only)");
+    int og = -2;
+    auto add = [&](int c0, int c1, int in_group, int out) -> int {
+        if (og != -2 && og != out) return fail("scale groups: the outputs of '%s' lie in two groups", s.name.c_str());
+        og = out;
+        for (const ScaleRange& r : ranges)
+            if (r.c0 == c0) return r.c1 == c1 && r.group == in_group ? 0 : fail("scale groups: input slices of '%s' disagree", s.name.c_str());
+        ranges.push_back({c0, c1, in_group});
+        return 0;
+    };
+    for (const Op& o : c.ops) {
+        if (o.kind == OP_STEM && index == c.spec_stem) { if (add(0, s.cin, -1, c.tgroup[o.out])) return 1; }
+        else if (o.kind == OP_FINAL && index == c.spec_final) {
+            const int K = c.cfg.num_keypoints;
+            if (add(0, K, c.tgroup[o.in], -1) || add(K, s.cin, -1, -1)) return 1;
+        } else if (o.kind == OP_CONV && c.dconvs[o.dconv].spec == index) {
+            const DevConv& d = c.dconvs[o.dconv];
+            if (add(d.c0, d.c1, c.tgroup[o.in], c.tgroup[o.out])) return 1;
+        } else if (o.kind == OP_HEADBF && index == c.spec_l0) {
+            if (add(0, c.head_c0, c.tgroup[o.in], c.tgroup[o.terms[0]])) return 1;
+        } else if (o.kind == OP_HEADBF && index == c.spec_l3) {
+            if (add(0, s.cin, c.tgroup[o.terms[0]], c.tgroup[o.out])) return 1;
+        }
+    }
+    std::sort(ranges.begin(), ranges.end(), [](const ScaleRange& a, const ScaleRange& b) { return a.c0 < b.c0; });
+    int at = 0;
+    for (const ScaleRange& r : ranges) { if (r.c0 != at) break; at = r.c1; }
+    if (og == -2 || at != s.cin) return fail("scale groups: the plan does not cover the input channels of '%s'", s.name.c_str());
+    *out_group = og;
+    return 0;
+}
+
+// Convolution `index` as esahrnet_commit packs it: the host's folded weights with 2^(e_in - e_out) on every range of input
+// channels and 2^-e_out on the bias — ldexpf, exact unless the result leaves f32's normal range.  shift_at (optional): the
+// exponent each input channel's weights were given.
+int scaled_conv(const esahrnet_ctx& c, int index, std::vector<float>& w, std::vector<float>& b, std::vector<int>* shift_at) {
+    const ConvSpec& s = c.specs[index];
+    w = s.w; b = s.b;
+    if (shift_at) shift_at->assign(s.cin, 0);
+    if (!c.scaled()) return 0;
+    int og = -1;
+    std::vector<ScaleRange> ranges;
+    if (scale_conv_info(c, index, &og, ranges)) return 1;
+    const int taps = s.k * s.k, eo = c.gexp(og);
+    for (const ScaleRange& r : ranges) {
+        const int sh = c.gexp(r.group) - eo;
+        for (int ci = r.c0; ci < r.c1; ++ci) {
+            if (shift_at) (*shift_at)[ci] = sh;
+            if (!sh) continue;
+            for (int co = 0; co < s.cout; ++co)
+                for (int t = 0; t < taps; ++t) {
+                    float& v = w[((size_t)co * s.cin + ci) * taps + t];
+                    v = ldexpf(v, sh);
+                }
+        }
+    }
+    if (eo) for (float& v : b) v = ldexpf(v, -eo);
+    for (float v : w)
+        if (!std::isfinite(v)) return fail("commit: a weight of '%s' is not finite in f32 under its scale shift", s.name.c_str());
+    for (float v : b)
+        if (!std::isfinite(v)) return fail("commit: a bias of '%s' is not finite in f32 under its scale shift 2^%d", s.name.c_str(), -eo);
+    return 0;
+}
+
 void level_dims(const esahrnet_ctx& c, int h, int w, std::vector<int>& lh, std::vector<int>& lw) {
     lh.assign(c.max_level + 1, 0);
     lw.assign(c.max_level + 1, 0);
@@ -1354,7 +1490,7 @@ int esahrnet_create(const esahrnet_cfg* cfg, int device, esahrnet_handle* out) {
         return fail("precision=3 (fp16) needs the matrix-core output layer: unset ESAHRNET_FINAL_VALU (num_keypoints=%d, cin=%d)",
                     cfg->num_keypoints, cfg->cin);
     }
-    if (build_plan(*c)) { delete c; return 1; }
+    if (build_plan(*c) || build_scale_groups(*c)) { delete c; return 1; }
     *out = c;
     return 0;
 }
@@ -1506,14 +1642,30 @@ int esahrnet_commit(esahrnet_handle h) {
         if (!s.set) return fail("commit: weights of '%s' were never set", s.name.c_str());
     for (const AuxSpec& a : h->aux)
         if (!a.set) return fail("commit: tensor '%s' was never set", a.name.c_str());
+    // the scale exponents (esahrnet_set_scale_exponents), applied in f32 before any packer runs: the specs hold the scaled
+    // weights for the length of this call and get the host's back when it returns.  All zero: nothing is touched.
+    struct Unfold {
+        esahrnet_ctx* c;
+        std::vector<std::vector<float>> w, b;
+        ~Unfold() { for (size_t i = 0; i < w.size(); ++i) { c->specs[i].w.swap(w[i]); c->specs[i].b.swap(b[i]); } }
+    } unfold{h, {}, {}};
+    std::vector<std::vector<int>> shifts(h->specs.size());
+    if (h->scaled()) {
+        std::vector<std::vector<float>> w(h->specs.size()), b(h->specs.size());
+        for (size_t i = 0; i < h->specs.size(); ++i)
+            if (scaled_conv(*h, (int)i, w[i], b[i], &shifts[i])) return 1;
+        for (size_t i = 0; i < h->specs.size(); ++i) { h->specs[i].w.swap(w[i]); h->specs[i].b.swap(b[i]); }
+        unfold.w.swap(w); unfold.b.swap(b);
+    }
     if (h->hf()) {      // a folded weight that rounds to +-inf in fp16 is refused, not saturated (conv1 and the output layer stay f32 / split bf16)
         for (size_t i = 0; i < h->specs.size(); ++i) {
             const ConvSpec& s = h->specs[i];
             if ((int)i == h->spec_stem || (int)i == h->spec_final) continue;
-            for (float v : s.w)
-                if (!esa::host_f16_finite(v))
-                    return fail("commit: weight %g of '%s' is not finite in fp16 (|w| must stay below 65520): precision 'fp16' cannot hold "
-                                "this network, use 'bf16'", (double)v, s.name.c_str());
+            for (size_t j = 0; j < s.w.size(); ++j)
+                if (!esa::host_f16_finite(s.w[j]))
+                    return fail("commit: weight %g of '%s' is not finite in fp16 (|w| must stay below 65520; scale shift 2^%d): precision "
+                                "'fp16' cannot hold this network, use 'bf16'", (double)s.w[j], s.name.c_str(),
+                                shifts[i].empty() ? 0 : shifts[i][(j / ((size_t)s.k * s.k)) % s.cin]);
         }
     }
     int ndev = 0;
@@ -1636,6 +1788,129 @@ int esahrnet_commit(esahrnet_handle h) {
     return 0;
 }
 
+// ---- fp16 scale groups: queries, exponents, the folded weights (host only) -------------------------------------------------
+int esahrnet_scale_groups(esahrnet_handle h, int* groups) {
+    if (!h || !groups) return fail("scale_groups: null argument");
+    *groups = (int)h->gnames.size();
+    return 0;
+}
+
+int esahrnet_scale_group_name(esahrnet_handle h, int group, char* out, size_t cap) {
+    if (!h || !out || !cap) return fail("scale_group_name: null argument");
+    if (group < 0 || group >= (int)h->gnames.size()) return fail("scale_group_name: group %d out of range (%zu groups)", group, h->gnames.size());
+    snprintf(out, cap, "%s", h->gnames[group].c_str());
+    return 0;
+}
+
+int esahrnet_scale_conv_get(esahrnet_handle h, int index, esahrnet_scale_conv* out) {
+    if (!h || !out) return fail("scale_conv_get: null argument");
+    if (index < 0 || index >= host_specs(h)) return fail("scale_conv_get: bad index %d", index);
+    std::vector<ScaleRange> ranges;
+    int og = -1;
+    if (scale_conv_info(*h, index, &og, ranges)) return 1;
+    if (ranges.size() > ESAHRNET_SCALE_MAX_RANGES) return fail("scale_conv_get: '%s' reads %zu ranges", h->specs[index].name.c_str(), ranges.size());
+    memset(out, 0, sizeof *out);
+    out->out_group = og;
+    out->nranges = (int)ranges.size();
+    for (size_t i = 0; i < ranges.size(); ++i) { out->c0[i] = ranges[i].c0; out->c1[i] = ranges[i].c1; out->in_group[i] = ranges[i].group; }
+    return 0;
+}
+
+int esahrnet_scale_row_group(esahrnet_handle h, int row, int* group) {
+    if (!h || !group) return fail("scale_row_group: null argument");
+    const int nt = (int)h->tensors.size();
+    if (row < 0 || row > nt) return fail("scale_row_group: row %d out of range (0..%d)", row, nt);
+    *group = row == nt ? -1 : h->tgroup[row];
+    return 0;
+}
+
+int esahrnet_set_scale_exponents(esahrnet_handle h, const int32_t* exponents, int count) {
+    if (!h || (!exponents && count)) return fail("set_scale_exponents: null argument");
+    if (count != (int)h->gnames.size())
+        return fail("set_scale_exponents: %d exponents for a handle with %zu scale groups", count, h->gnames.size());
+    for (int g = 0; g < count; ++g) {
+        if (exponents[g] < -ESAHRNET_SCALE_MAX_EXPONENT || exponents[g] > ESAHRNET_SCALE_MAX_EXPONENT)
+            return fail("set_scale_exponents: exponent %d of group %d ('%s') is outside [-%d, %d]", exponents[g], g, h->gnames[g].c_str(),
+                        ESAHRNET_SCALE_MAX_EXPONENT, ESAHRNET_SCALE_MAX_EXPONENT);
+        if (exponents[g] && h->cfg.precision != 3)
+            return fail("set_scale_exponents: a non-zero exponent (group %d, '%s': %d) needs precision 3 (fp16); this handle has precision %d, "
+                        "whose format has f32's exponent range", g, h->gnames[g].c_str(), exponents[g], h->cfg.precision);
+    }
+    h->exps.assign(exponents, exponents + count);
+    h->committed = false;       // the packed weights on the device belong to the old exponents: esahrnet_commit again
+    return 0;
+}
+
+int esahrnet_get_scale_exponents(esahrnet_handle h, int32_t* exponents, int count) {
+    if (!h || (!exponents && count)) return fail("get_scale_exponents: null argument");
+    if (count != (int)h->exps.size()) return fail("get_scale_exponents: room for %d exponents, the handle has %zu scale groups", count, h->exps.size());
+    std::copy(h->exps.begin(), h->exps.end(), exponents);
+    return 0;
+}
+
+int esahrnet_debug_scaled_conv(esahrnet_handle h, int index, float* w, float* b) {
+    if (!h || !w || !b) return fail("debug_scaled_conv: null argument");
+    if (index < 0 || index >= host_specs(h)) return fail("debug_scaled_conv: bad index %d", index);
+    if (!h->specs[index].set) return fail("debug_scaled_conv: weights of '%s' were never set", h->specs[index].name.c_str());
+    std::vector<float> sw, sb;
+    if (scaled_conv(*h, index, sw, sb, nullptr)) return 1;
+    std::copy(sw.begin(), sw.end(), w);
+    std::copy(sb.begin(), sb.end(), b);
+    return 0;
+}
+
+static int stats_row_name(esahrnet_handle h, int row, char* out, size_t cap);
+
+int esahrnet_scale_exponents_from_stats(esahrnet_handle h, const void* records, int rows, int n_total, const void* h0_records,
+                                        int headroom_bits, int32_t* exponents, int count) {
+    if (!h || !records || !exponents) return fail("scale_exponents_from_stats: null argument");
+    const int ng = (int)h->gnames.size();
+    if (!ng) return fail("scale_exponents_from_stats: this handle has no scale groups (variant 0 with precision 1 or 3 only)");
+    if (count != ng) return fail("scale_exponents_from_stats: room for %d exponents, the handle has %d scale groups", count, ng);
+    if (rows != (int)h->tensors.size() + 1) return fail("scale_exponents_from_stats: %d rows, the handle's report has %zu", rows, h->tensors.size() + 1);
+    if (n_total < 1) return fail("scale_exponents_from_stats: n_total must be positive (got %d)", n_total);
+    if (headroom_bits < 0 || headroom_bits > 14) return fail("scale_exponents_from_stats: headroom_bits %d outside 0..14", headroom_bits);
+    const esahrnet_stats_record* rec = static_cast<const esahrnet_stats_record*>(records);
+    const esahrnet_stats_record* h0 = static_cast<const esahrnet_stats_record*>(h0_records);
+    std::vector<float> top(ng, 0.f);
+    char name[96];
+    for (int r = 0; r < rows; ++r)
+        for (int i = 0; i < n_total; ++i) {
+            const esahrnet_stats_record& v = rec[(size_t)r * n_total + i];
+            if (v.n_nan || v.n_inf) {
+                if (stats_row_name(h, r, name, sizeof name)) snprintf(name, sizeof name, "?");
+                return fail("scale_exponents_from_stats: row %d ('%s') holds %u NaN and %u infinite values in crop %d: no exponent cures that",
+                            r, name, v.n_nan, v.n_inf, i);
+            }
+            const int g = r < rows - 1 ? h->tgroup[r] : -1;
+            if (g >= 0 && std::isfinite(v.max_abs)) top[g] = std::max(top[g], v.max_abs);
+        }
+    if (h0) {
+        int g0 = -1;
+        for (const Op& o : h->ops)
+            if (o.kind == OP_HEADBF) g0 = h->tgroup[o.terms[0]];
+        for (size_t t = 0; t < h->tensors.size() && g0 < 0; ++t)
+            if (h->tensors[t].tap == "head0") g0 = h->tgroup[t];
+        for (int i = 0; i < n_total && g0 >= 0; ++i) {
+            if (h0[i].n_nan || h0[i].n_inf)
+                return fail("scale_exponents_from_stats: h0 holds %u NaN and %u infinite values in crop %d", h0[i].n_nan, h0[i].n_inf, i);
+            if (std::isfinite(h0[i].max_abs)) top[g0] = std::max(top[g0], h0[i].max_abs);
+        }
+    }
+    // M * 2^-e in (2^(14 - headroom), 2^(15 - headroom)]: e = ceil(log2 M) - (15 - headroom); frexp: M = m * 2^k, 0.5 <= m < 1
+    for (int g = 0; g < ng; ++g) {
+        int e = 0;
+        if (top[g] > 0.f) {
+            int k = 0;
+            const float m = frexpf(top[g], &k);
+            e = (m == 0.5f ? k - 1 : k) - (15 - headroom_bits);
+            e = std::max(-ESAHRNET_SCALE_MAX_EXPONENT, std::min(ESAHRNET_SCALE_MAX_EXPONENT, e));
+        }
+        exponents[g] = e;
+    }
+    return 0;
+}
+
 int esahrnet_set_debug_keep(esahrnet_handle h, int keep) {
     if (!h) return fail("null handle");
     h->keep = keep != 0;
@@ -1711,6 +1986,9 @@ struct Buffers {
     float2* kpart = nullptr;
     float* kbmax = nullptr;
     size_t kws = 0;
+    // esahrnet_forward_stats_h0: the fused 16-bit head runs in its range form (launch_head_bf_range) and leaves the range of h0
+    void* h0_part = nullptr;
+    void* h0_rec = nullptr;
 };
 
 // What a decoder keeps behind the forward's workspace (at ShapePlan::bytes, a multiple of 256), one row per decoder: heat,
@@ -2083,7 +2361,8 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                 desc->bytes = tbytes(o.in) + tbytes(o.out);
                 for (int i = 0; i < 3; ++i) desc->bytes += tbytes(o.terms[i]);
             } else if (o.kind == OP_HEADBF) {
-                rc = c.x6() ? esa::launch_head_x6(p, stream) : esa::launch_head_bf(p, stream);
+                rc = c.x6() ? esa::launch_head_x6(p, stream)
+                   : b.h0_rec ? esa::launch_head_bf_range(p, b.h0_part, b.h0_rec, stream) : esa::launch_head_bf(p, stream);
             } else {
                 if (!esa::head_fused_supported(p.H, p.W, p.th, p.tw, p.C0p, p.K))
                     return fail("forward: fused head does not support this shape (%dx%d)", p.H, p.W);
@@ -2180,7 +2459,8 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
 // req == nullptr: heat-maps into heat_dev (and, with part_dev, their per-tile maxima).  Otherwise the decoder of *req runs in
 // place of the last launch and nothing but its outputs reaches caller memory (heat_dev and part_dev unused, req->kp never null)
 static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* heat_dev, void* part_dev,
-                       void* ws_dev, size_t ws_bytes, esahrnet_stream stream_, hipEvent_t* events, const Request* req) {
+                       void* ws_dev, size_t ws_bytes, esahrnet_stream stream_, hipEvent_t* events, const Request* req,
+                       void* h0_part = nullptr, void* h0_rec = nullptr) {
     if (!h || !x_dev || !(heat_dev || req) || !ws_dev) return fail("forward: null argument");
     if (!h->committed) return fail("forward: esahrnet_commit has not been called");
     if (plan_shape(*h, n, height, width)) return 1;
@@ -2190,6 +2470,7 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
     if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("forward: workspace must be 256-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Buffers bufs{x_dev, heat_dev, static_cast<char*>(ws_dev), part_dev};
+    bufs.h0_part = h0_part; bufs.h0_rec = h0_rec;
     if (req) {
         char* const scratch = bufs.ws + h->sp.bytes;
         bufs.req = *req;
@@ -2660,7 +2941,12 @@ int esahrnet_tap_read(esahrnet_handle h, const char* name, int n, int height, in
     if (plan_shape(*h, n, height, width)) return 1;
     if (t->alt != 0 && t->alt != (h->sp.head2 ? 2 : 1))
         return fail("tap_read: '%s' belongs to the head alternative that does not run at this shape", name);
-    const int rc = esa::launch_fmt_to_nchw(t->f32 ? esa::FMT_F32 : h->opt.fmt,
+    // a tensor stored as T * 2^-e (fp16 scale exponents) comes back as T: the conversion takes the factor
+    const int e = h->gexp(h->tgroup[t - h->tensors.data()]);
+    const int rc = e ? esa::launch_hf_to_nchw_scaled(static_cast<const char*>(ws_dev) + t->off, n, t->C, h->sp.lh[t->level],
+                                                     h->sp.lw[t->level], t->Cp, static_cast<float*>(out_dev), ldexpf(1.f, e),
+                                                     static_cast<hipStream_t>(stream))
+                     : esa::launch_fmt_to_nchw(t->f32 ? esa::FMT_F32 : h->opt.fmt,
         static_cast<const char*>(ws_dev) + t->off, n, t->C, h->sp.lh[t->level], h->sp.lw[t->level], t->Cp,
         static_cast<float*>(out_dev), static_cast<hipStream_t>(stream));
     if (rc) return fail("tap_read: %s", hipGetErrorString((hipError_t)rc));
@@ -2746,22 +3032,36 @@ int esahrnet_forward_stats_workspace_bytes(esahrnet_handle h, int n, int height,
     return rc;
 }
 
-int esahrnet_forward_stats(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* heat_dev, void* ws_dev,
-                           size_t ws_bytes, void* stats_dev, esahrnet_stream stream_) {
-    if (!h || !x_dev || !heat_dev || !ws_dev || !stats_dev) return fail("forward_stats: null argument");
-    if (!h->committed) return fail("forward_stats: esahrnet_commit has not been called");
+// the partials of the fused head's range form behind the scan's (esahrnet_forward_stats_h0); 0 where that head does not run
+static size_t stats_h0_bytes(const esahrnet_ctx& c, const ShapePlan& sp) {
+    if (c.head2_op < 0 || c.ops[c.head2_op].kind != OP_HEADBF || c.x6() || !sp.head2) return 0;
+    const Tensor& t0 = c.tensors[c.ops[c.head2_op].in];
+    return stats_pad256((size_t)esa::head_bf_range_tiles(sp.lh[t0.level], sp.lw[t0.level]) * sp.n * 8);
+}
+
+// esahrnet_forward_stats (h0_dev == nullptr, with_h0 false) and esahrnet_forward_stats_h0
+static int forward_stats(const char* who, bool with_h0, esahrnet_handle h, const void* x_dev, int n, int height, int width,
+                         void* heat_dev, void* ws_dev, size_t ws_bytes, void* stats_dev, void* h0_dev, esahrnet_stream stream_) {
+    if (!h || !x_dev || !heat_dev || !ws_dev || !stats_dev || (with_h0 && !h0_dev)) return fail("%s: null argument", who);
+    if (!h->committed) return fail("%s: esahrnet_commit has not been called", who);
+    if (with_h0 && h->gnames.empty()) return fail("%s: variant 0 with precision 1 or 3 only (the head that rounds h0 in registers)", who);
+    if (with_h0 && h->opt.bf_head_valu && !h->hf()) return fail("%s: the range form is the matrix-core head's: unset ESAHRNET_BF_HEAD_VALU", who);
     const bool keep = h->keep;
     h->keep = true;
     auto body = [&]() -> int {
         size_t need = 0;
-        if (stats_plan("forward_stats", *h, n, height, width, &need)) return 1;
-        if (ws_bytes < need) return fail("forward_stats: workspace too small (%zu < %zu)", ws_bytes, need);
-        if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("forward_stats: workspace must be 256-byte aligned");
-        if (reinterpret_cast<uintptr_t>(stats_dev) & 7) return fail("forward_stats: stats_dev must be 8-byte aligned");
+        if (stats_plan(who, *h, n, height, width, &need)) return 1;
+        const size_t h0_off = need, h0_bytes = with_h0 ? stats_h0_bytes(*h, h->sp) : 0;
+        need += h0_bytes;
+        if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+        if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("%s: workspace must be 256-byte aligned", who);
+        if (reinterpret_cast<uintptr_t>(stats_dev) & 7) return fail("%s: stats_dev must be 8-byte aligned", who);
+        if (with_h0 && (reinterpret_cast<uintptr_t>(h0_dev) & 7)) return fail("%s: h0_dev must be 8-byte aligned", who);
         hipStream_t stream = static_cast<hipStream_t>(stream_);
         const size_t rows = h->tensors.size() + 1;
         HIP_OK(hipMemsetAsync(stats_dev, 0, rows * n * sizeof(esahrnet_stats_record), stream));   // the rows not scanned
-        if (run_forward(h, x_dev, n, height, width, heat_dev, nullptr, ws_dev, ws_bytes, stream_, nullptr, nullptr)) return 1;
+        if (run_forward(h, x_dev, n, height, width, heat_dev, nullptr, ws_dev, ws_bytes, stream_, nullptr, nullptr,
+                        h0_bytes ? static_cast<char*>(ws_dev) + h0_off : nullptr, h0_bytes ? h0_dev : nullptr)) return 1;
         const ShapePlan& sp = h->sp;
         char* const ws = static_cast<char*>(ws_dev);
         std::vector<esa::StatsJob> jobs;
@@ -2772,12 +3072,47 @@ int esahrnet_forward_stats(esahrnet_handle h, const void* x_dev, int n, int heig
         }
         jobs.push_back({heat_dev, esa::STATS_NCHW, h->cfg.num_keypoints, 0, height * width, (int)rows - 1});
         const int rc = esa::launch_stats(jobs.data(), (int)jobs.size(), n, ws + stats_pad256(sp.bytes), stats_dev, stream);
-        if (rc) return fail("forward_stats: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (rc) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+        if (with_h0 && !h0_bytes) {     // the materialised head ran: h0 is the stored row "head0"
+            int row = -1;
+            for (size_t ti = 0; ti < h->tensors.size(); ++ti)
+                if (h->tensors[ti].tap == "head0" && stats_scanned(*h, sp, h->tensors[ti])) row = (int)ti;
+            if (row < 0) return fail("%s: no head0 tensor at this shape", who);
+            HIP_OK(hipMemcpyAsync(h0_dev, static_cast<const esahrnet_stats_record*>(stats_dev) + (size_t)row * n,
+                                  (size_t)n * sizeof(esahrnet_stats_record), hipMemcpyDeviceToDevice, stream));
+        }
         return 0;
     };
     const int rc = body();
     h->keep = keep;
     return rc;
+}
+
+int esahrnet_forward_stats(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* heat_dev, void* ws_dev,
+                           size_t ws_bytes, void* stats_dev, esahrnet_stream stream) {
+    return forward_stats("forward_stats", false, h, x_dev, n, height, width, heat_dev, ws_dev, ws_bytes, stats_dev, nullptr, stream);
+}
+
+int esahrnet_forward_stats_h0_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes) {
+    if (!h || !bytes) return fail("forward_stats_h0_workspace_bytes: null argument");
+    const bool keep = h->keep;
+    h->keep = true;
+    int rc = stats_plan("forward_stats_h0_workspace_bytes", *h, n, height, width, bytes);
+    if (!rc) *bytes += stats_h0_bytes(*h, h->sp);
+    h->keep = keep;
+    return rc;
+}
+
+int esahrnet_forward_stats_h0(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* heat_dev, void* ws_dev,
+                              size_t ws_bytes, void* stats_dev, void* h0_dev, esahrnet_stream stream) {
+    return forward_stats("forward_stats_h0", true, h, x_dev, n, height, width, heat_dev, ws_dev, ws_bytes, stats_dev, h0_dev, stream);
+}
+
+static int stats_row_name(esahrnet_handle h, int row, char* out, size_t cap) {
+    esahrnet_stats_row_desc d;
+    if (esahrnet_stats_row_get(h, row, 1, 64, 64, &d)) return 1;
+    snprintf(out, cap, "%s", d.name);
+    return 0;
 }
 
 static int tensor_stats_parts(const char* who, int fmt, int n, int c, int cp, int h, int w, int* parts) {

@@ -113,6 +113,7 @@ class HighResolutionNet(nn.Module):
         # seg_hrnet2 only: seg_hrnet3 raises the library's message)
         self._cfg_struct = _cfg_struct(config, cin, k, int(kwargs.pop("variant", self.VARIANT)),
                                        kwargs.pop("precision", self.DEFAULT_PRECISION))
+        self.__dict__["_config"] = config      # calibrate_fp16 builds a bf16 twin from it
         object.__setattr__(self, "_rt", _Runtime(self._cfg_struct))
         self._descs = self._rt.conv_descs()
         for d in self._descs:
@@ -320,6 +321,73 @@ class HighResolutionNet(nn.Module):
         Which precision can these weights afford: see ActivationStats.headroom_fp16, saturated, first_nonfinite."""
         return self._rt.forward_stats(self, x0)
 
+    # ---- fp16 scale exponents (include/esahrnet.h: fp16 scale groups; DESIGN.md 3e) ---------------------------------
+    @property
+    def fp16_scale_groups(self):
+        """Names of the handle's scale groups, in the library's order ("stream0", "stem1", "head0", a conv1's name, ...); ()
+        for a network without them (seg_hrnet3, the 32-bit formats)."""
+        return self._rt.scale_group_names()
+
+    @property
+    def fp16_exponents(self):
+        """One exponent per scale group: the tensors of group g are stored as T * 2^-e[g] and the weights absorb the
+        difference, so the heat-maps keep their scale.  All zero unless set (or calibrated: calibrate_fp16)."""
+        e = self.__dict__.get("_fp16_exp")
+        return tuple(e) if e is not None else (0,) * len(self.fp16_scale_groups)
+
+    @fp16_exponents.setter
+    def fp16_exponents(self, exponents):
+        e = [int(v) for v in exponents]
+        self._rt.check_scale_exponents(e)           # the library's refusals (count, range, precision), raised here
+        self.__dict__["_fp16_exp"] = e
+        self.invalidate_weights()                   # every device's handle re-commits on its next call
+
+    def calibrate_fp16(self, x_or_batches, headroom_bits: int = 3) -> "Fp16Calibration":
+        """Choose and set the scale exponents of an fp16 net from calibration crops (one cuda tensor [N,Cin,H,W] or several).
+        A temporary bf16 twin — the same plan row for row, with f32's exponent range, so nothing saturates or underflows in
+        it — runs one range-scanning forward per batch (esahrnet_forward_stats_h0: every stored tensor, and the h0 the fused
+        head rounds in registers); the library turns the records into one exponent per group, the largest magnitude of a
+        group landing in (2^(14 - headroom_bits), 2^(15 - headroom_bits)]; the exponents are set on this net, which then
+        runs one verifying scan per batch: no stored value and no h0 may reach 65504 (RuntimeError naming the rows).  A
+        weight the shift pushes out of fp16's range is the library's commit error, passed through."""
+        self._inference_only()
+        if self._cfg_struct.precision != PRECISIONS["fp16"]:
+            raise ValueError("calibrate_fp16 belongs to precision='fp16' (the other formats have f32's exponent range)")
+        batches = [x_or_batches] if isinstance(x_or_batches, torch.Tensor) else list(x_or_batches)
+        if not batches:
+            raise ValueError("calibrate_fp16 needs at least one batch of crops")
+        twin = type(self)(self._config, cin=self._cin, num_keypoints=self._k, variant=self._cfg_struct.variant, precision="bf16")
+        try:
+            twin.load_state_dict(self.state_dict())
+            twin.to(batches[0].device)
+            scans = [twin._rt.forward_stats(twin, x, with_h0=True) for x in batches]
+            n, _, hh, ww = batches[0].shape
+            mine = self._rt.stats_rows(self._rt._probe, n, hh, ww)
+            if [d.name for d in mine] != [d.name for d in scans[0].descs]:
+                raise RuntimeError("calibrate_fp16: the bf16 twin's report rows are not the fp16 net's")
+            exps = twin._rt.exponents_from_stats(np.concatenate([st.per_image for st in scans], axis=1),
+                                                 np.concatenate([st.h0 for st in scans]), int(headroom_bits))
+        finally:
+            twin._rt.close()            # its handles, packed weights and scratch, now
+        self.fp16_exponents = exps
+        names = self.fp16_scale_groups
+        stored = [0.0] * len(names)
+        bad = []
+        for x in batches:
+            st = self._rt.forward_stats(self, x, with_h0=True)
+            bad += [r["name"] for r in st.saturated() if r["group"] >= 0]       # (the f32 heat-maps are no fp16 store)
+            if int(st.h0["n_ge_f16max"].astype(np.int64).sum()):
+                bad.append("h0")
+            for r in st.scanned():
+                if r["group"] >= 0:
+                    stored[r["group"]] = max(stored[r["group"]], r["max_abs"])
+            if "head0" in names:        # h0 is formed at the scale of its group: the record is a stored magnitude as it stands
+                stored[names.index("head0")] = max(stored[names.index("head0")], float(st.h0["max_abs"].max()))
+        if bad:
+            raise RuntimeError(f"calibrate_fp16: values still reach 65504 under exponents {tuple(exps)} in {sorted(set(bad))}; "
+                               "raise headroom_bits or calibrate on crops that cover the deployment's range")
+        return Fp16Calibration(tuple(exps), tuple(names), tuple(stored), int(headroom_bits))
+
     # ---- weight-version tracking (an eager forward must not walk the module tree: val.py:112 calls the
     # net once per image) ---------------------------------------------------------------------------
     def _weight_tensors(self):
@@ -406,6 +474,7 @@ class _Runtime:
         "frames_gaussfit": ("frames", "esahrnet_frames_keypoints_gaussfit_workspace_bytes", lambda n, hh, ww, keep: (n, hh)),
         "corr": ("frames", "esahrnet_frames_correspondences_workspace_bytes", lambda n, hh, ww, keep: (n, hh, *keep)),
         "stats": ("stats", "esahrnet_forward_stats_workspace_bytes", _crops),
+        "stats_h0": ("stats", "esahrnet_forward_stats_h0_workspace_bytes", _crops),
     }
 
     def __init__(self, cfg_struct):
@@ -432,11 +501,20 @@ class _Runtime:
         _lib.check(self.lib.esahrnet_create(C.byref(self.cfg), max(device, 0), C.byref(h)))
         return h
 
-    def __del__(self):
-        try:
+    def close(self):
+        """Destroy every handle (their packed weights on the devices) and drop the scratch; the runtime is unusable afterwards."""
+        with self.lock:
             for h, _ in self.handles.values():
                 self.lib.esahrnet_destroy(h)
-            self.lib.esahrnet_destroy(self._probe)
+            self.handles.clear()
+            self.ws.clear()
+            if self._probe is not None:
+                self.lib.esahrnet_destroy(self._probe)
+                self._probe = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 
@@ -456,6 +534,38 @@ class _Runtime:
             out.append(dict(name=d.name.decode(), bn=d.bn.decode(), cin=d.cin, cout=d.cout, k=d.k,
                             stride=d.stride, has_bias=bool(d.has_bias), relu=bool(d.relu)))
         return out
+
+    def scale_group_names(self):
+        g = C.c_int(0)
+        _lib.check(self.lib.esahrnet_scale_groups(self._probe, C.byref(g)))
+        buf = C.create_string_buffer(96)
+        names = []
+        for i in range(g.value):
+            _lib.check(self.lib.esahrnet_scale_group_name(self._probe, i, buf, 96))
+            names.append(buf.value.decode())
+        return tuple(names)
+
+    def check_scale_exponents(self, exps):
+        """esahrnet_set_scale_exponents on the probe handle (host only): its refusals, before anything is kept."""
+        arr = (C.c_int32 * len(exps))(*exps)
+        _lib.check(self.lib.esahrnet_set_scale_exponents(self._probe, arr, len(exps)))
+
+    def exponents_from_stats(self, records, h0, headroom_bits):
+        """esahrnet_scale_exponents_from_stats: records [rows, n_total] and h0 [n_total] (structured, _lib.stats_dtype)."""
+        def laid_out(a):            # numpy drops a structured type's padding when it concatenates: back to the 64-byte record
+            out = np.zeros(a.shape, dtype=_lib.stats_dtype())
+            for name, _ in _lib.STATS_FIELDS:
+                out[name] = a[name]
+            return out
+
+        records = laid_out(records)
+        h0 = None if h0 is None else laid_out(h0)
+        g = len(self.scale_group_names())
+        out = (C.c_int32 * g)()
+        _lib.check(self.lib.esahrnet_scale_exponents_from_stats(
+            self._probe, records.ctypes.data_as(C.c_void_p), records.shape[0], records.shape[1],
+            None if h0 is None else h0.ctypes.data_as(C.c_void_p), headroom_bits, out, g))
+        return [int(v) for v in out]
 
     def flops_per_crop(self, h, w):
         f = C.c_double()
@@ -483,6 +593,9 @@ class _Runtime:
             for i, a in enumerate(master._aux):
                 w = np.ascontiguousarray(sd[a["name"]].detach().cpu().float().numpy())
                 _lib.check(self.lib.esahrnet_set_aux(h, i, w.ctypes.data_as(C.c_void_p)))
+            exps = master.__dict__.get("_fp16_exp")
+            if exps is not None:        # fp16 scale exponents: folded into the weights by the commit below
+                _lib.check(self.lib.esahrnet_set_scale_exponents(h, (C.c_int32 * len(exps))(*exps), len(exps)))
             with torch.cuda.device(device):
                 _lib.check(self.lib.esahrnet_commit(h))
             self.handles[device.index] = (h, key)
@@ -753,9 +866,10 @@ class _Runtime:
             descs.append(d)
         return descs
 
-    def forward_stats(self, module, x0):
+    def forward_stats(self, module, x0, with_h0=False):
         """esahrnet_forward_stats on the current stream of x's device: -> ActivationStats.  Same device lock, workspace contract
-        and record_stream handling as forward(); the records come back in one copy."""
+        and record_stream handling as forward(); the records come back in one copy.  with_h0: esahrnet_forward_stats_h0, the
+        same rows plus ActivationStats.h0, one record per crop for the h0 of the fused head."""
         x = self._check_input(module, x0)
         n, _, hh, ww = x.shape
         dev = x.device
@@ -764,16 +878,29 @@ class _Runtime:
             h = self._handle_for(module, dev)
             _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
             descs = self.stats_rows(h, n, hh, ww)
-            ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, n, hh, ww, False, kind="stats")
+            ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, n, hh, ww, bool(with_h0), kind="stats_h0" if with_h0 else "stats")
             heat = torch.empty((n, module._k, hh, ww), dtype=torch.float32, device=dev)
-            stats = torch.empty((len(descs), n, _lib.STATS_RECORD_BYTES), dtype=torch.uint8, device=dev)
+            # (one buffer: the rows, then, with_h0, the h0 records behind them)
+            stats = torch.empty((len(descs) + bool(with_h0), n, _lib.STATS_RECORD_BYTES), dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
-                _lib.check(self.lib.esahrnet_forward_stats(h, x.data_ptr(), n, hh, ww, heat.data_ptr(), ws_ptr, ws_bytes,
-                                                           stats.data_ptr(), C.c_void_p(ts.cuda_stream)))
+                if with_h0:
+                    _lib.check(self.lib.esahrnet_forward_stats_h0(h, x.data_ptr(), n, hh, ww, heat.data_ptr(), ws_ptr, ws_bytes,
+                                                                  stats.data_ptr(), stats[len(descs)].data_ptr(),
+                                                                  C.c_void_p(ts.cuda_stream)))
+                else:
+                    _lib.check(self.lib.esahrnet_forward_stats(h, x.data_ptr(), n, hh, ww, heat.data_ptr(), ws_ptr, ws_bytes,
+                                                               stats.data_ptr(), C.c_void_p(ts.cuda_stream)))
+            groups = []
+            g = C.c_int(0)
+            for i in range(len(descs)):
+                _lib.check(self.lib.esahrnet_scale_row_group(h, i, C.byref(g)))
+                groups.append(g.value)
         ws.record_stream(ts)
         x.record_stream(ts)
-        rec = stats.cpu().numpy().reshape(-1).view(_lib.stats_dtype()).reshape(len(descs), n)
-        return ActivationStats(descs, rec, heat)
+        rec = stats.cpu().numpy().reshape(-1).view(_lib.stats_dtype()).reshape(len(descs) + bool(with_h0), n)
+        master = module.__dict__.get("_master", module)
+        return ActivationStats(descs, rec[:len(descs)], heat, groups=groups, exponents=master.fp16_exponents,
+                               h0=rec[len(descs)] if with_h0 else None)
 
     def taps(self, module, x0):
         x = self._check_input(module, x0)
@@ -806,18 +933,26 @@ class ActivationStats:
     per_image   the raw records, a structured numpy array [rows, n] (_lib.STATS_FIELDS); rows not scanned are all zero
     rows        one dict per row in plan order, the last one "heatmaps": name, def_op, shape (c, h, w), format, scanned and
                 the batch-combined figures (maxima and counts exactly, sum_abs added in crop order, mean_abs = sum_abs / n_finite)
-    heatmaps    the forward's heat-maps (f32 [n, K, H, W] on the device), the bits net(x) returns"""
+                each row also carries `group`, its fp16 scale group (-1: none) and `exponent`, that group's exponent: the
+                figures are those of the STORED values T * 2^-exponent, so the saturation counts keep their meaning
+    heatmaps    the forward's heat-maps (f32 [n, K, H, W] on the device), the bits net(x) returns
+    h0          with esahrnet_forward_stats_h0 only: the records [n] of the fused head's h0 (max_abs and n_ge_f16max before its
+                rounding where the fused head ran, the stored row "head0" otherwise), else None"""
 
     F16_MAX = 65504.0
     COUNTS = tuple(name for name, t in _lib.STATS_FIELDS if t == "u4")
 
-    def __init__(self, descs, per_image, heatmaps):
+    def __init__(self, descs, per_image, heatmaps, groups=None, exponents=(), h0=None):
+        self.descs = descs
         self.per_image = per_image
         self.heatmaps = heatmaps
+        self.h0 = h0
         self.rows = []
-        for d, rec in zip(descs, per_image):
+        for i, (d, rec) in enumerate(zip(descs, per_image)):
             row = dict(name=d.name.decode(), def_op=d.def_op, shape=(d.c, d.h, d.w), format=_lib.STATS_FORMATS[d.fmt],
                        scanned=bool(d.scanned))
+            row["group"] = groups[i] if groups is not None else -1
+            row["exponent"] = int(exponents[row["group"]]) if row["group"] >= 0 and len(exponents) else 0
             row["max_abs"] = float(rec["max_abs"].max())
             row["min"] = float(rec["min"].min())
             row["max"] = float(rec["max"].max())
@@ -863,6 +998,23 @@ class ActivationStats:
             lines.append(f"{i:>4} {r['def_op']:>4} {r['name'][:44]:<44} {shape:<14} {r['format']:<8} {r['max_abs']:>11.4e} "
                          f"{r['mean_abs']:>11.4e} {r['min']:>11.4e} {r['max']:>11.4e} {r['n_nan']:>6} {r['n_inf']:>6} "
                          f"{r['n_ge_f16max']:>8} {r['n_f16_tiny']:>9} {r['n_zero']:>9}")
+        return "\n".join(lines)
+
+
+class Fp16Calibration:
+    """What net.calibrate_fp16 chose: exponents[g] for group names[g], and stored_max[g], the largest magnitude the verifying
+    forward found stored in that group (true magnitude = stored_max[g] * 2^exponents[g])."""
+
+    def __init__(self, exponents, names, stored_max, headroom_bits):
+        self.exponents, self.names, self.stored_max, self.headroom_bits = exponents, names, stored_max, headroom_bits
+
+    def as_dict(self):
+        return {n: e for n, e in zip(self.names, self.exponents)}
+
+    def table(self) -> str:
+        lines = [f"{'group':<40} {'exponent':>8} {'stored max':>12} {'true max':>12}"]
+        for n, e, m in zip(self.names, self.exponents, self.stored_max):
+            lines.append(f"{n[:40]:<40} {e:>8d} {m:>12.4e} {m * 2.0 ** e:>12.4e}")
         return "\n".join(lines)
 
 

@@ -70,7 +70,9 @@ typedef struct esahrnet_cfg {
                                        f32 accumulate and bias, f32 heat-maps; heatmap L_inf ~7e-4, nine times closer to
                                        the reference than mode 1 inside fp16's range; variant 0 only (esahrnet_create
                                        refuses variant 1); esahrnet_commit refuses a folded weight that is not finite in
-                                       fp16.  A value of this field, not a new field or symbol: the ABI version stays */
+                                       fp16.  A checkpoint whose tensors leave fp16's range is brought into it by per-tensor
+                                       power-of-two scales (esahrnet_set_scale_exponents, below), at no cost per forward.
+                                       A value of this field, not a new field or symbol: the ABI version stays */
 } esahrnet_cfg;
 
 /* A parameter tensor that is not a convolution of the main graph (variant 1: the CBAM weights). */
@@ -642,6 +644,64 @@ int esahrnet_forward_stats(esahrnet_handle h, const void* x_dev, int n, int heig
 int esahrnet_tensor_stats_workspace_bytes(int fmt, int n, int c, int cp, int h, int w, size_t* bytes);
 int esahrnet_tensor_stats(const void* t_dev, int fmt, int n, int c, int cp, int h, int w, void* ws_dev, size_t ws_bytes,
                           void* stats_dev, esahrnet_stream stream);
+
+/* ---- fp16 scale groups: per-tensor power-of-two scales for precision 3 ---------------------------------------
+ * precision 3 holds only inside fp16's range: stores saturate at +-65504, values below 2^-14 lose bits.  With BatchNorm folded,
+ * seg_hrnet / seg_hrnet2 is convolution, bias, ReLU, sums and bilinear interpolation, which all commute exactly with a power of
+ * two.  So tensor T may be STORED as T * 2^-e: esahrnet_commit gives the next convolution's weights 2^(e_in - e_out) per range
+ * of input channels and its bias 2^-e_out, in f32 (exact) before the packers run; conv1 keeps its f32 weights and gets
+ * 2^-e(stem1); the output layer gets 2^+e(head3) on its K heat-map input channels.  The forward is the same launches on the same
+ * plan and the heat-maps come out at true scale.
+ * A scale GROUP is a set of stored tensors that must share one exponent, because one reaches the other, or both enter one sum,
+ * without convolution weights in between: a branch stream (its identity residuals, the terms and the results of its fuse sums,
+ * the output of layer1.0.downsample), stem1, stem2, each BasicBlock's conv1 output, each non-final link of a fuse-down chain,
+ * head0 (the slices of last_layer[0] and the h0 the fused head forms from them in registers), head3.  The groups are derived
+ * from the handle's plan, numbered by their first tensor in plan order.  Handles of variant 0 with precision 1 or 3 have them
+ * (precision 1: the same plan, for calibration; its exponents must stay zero); every other handle has 0 groups.  The f32 crop
+ * and the heat-maps belong to no group (-1, exponent 0).  All of these are host calls that work on an uncommitted handle. */
+#define ESAHRNET_SCALE_MAX_RANGES 4
+#define ESAHRNET_SCALE_MAX_EXPONENT 32
+typedef struct esahrnet_scale_conv {
+    int32_t out_group;                           /* group the convolution's output is stored in, -1: none (output_layer.0) */
+    int32_t nranges;                             /* ranges of input channels [c0, c1), in channel order, covering 0 .. cin */
+    int32_t c0[ESAHRNET_SCALE_MAX_RANGES], c1[ESAHRNET_SCALE_MAX_RANGES];
+    int32_t in_group[ESAHRNET_SCALE_MAX_RANGES]; /* group of the tensor a range reads, -1: the f32 crop.  last_layer.0 reads four
+                                                    ranges (one per branch), output_layer.0 two (head3, the crop) */
+} esahrnet_scale_conv;
+int esahrnet_scale_groups(esahrnet_handle h, int* groups);
+/* "stream0".."stream3", "stem1", "stem2", "head0", "head3", else the name of the convolution that writes the group's first tensor */
+int esahrnet_scale_group_name(esahrnet_handle h, int group, char* out, size_t cap);
+int esahrnet_scale_conv_get(esahrnet_handle h, int index, esahrnet_scale_conv* out);   /* index as esahrnet_conv_desc_get */
+int esahrnet_scale_row_group(esahrnet_handle h, int row, int* group);                  /* row as esahrnet_stats_row_get; -1: none */
+/* exponents int32 [count], count = esahrnet_scale_groups, each in [-32, 32]; all zero after esahrnet_create, and with all zero
+ * every byte esahrnet_commit uploads and every launch is what it is without this call.  Refused, with esahrnet_last_error set and
+ * nothing changed: a wrong count, an exponent out of range, a non-zero exponent on a handle whose precision is not 3.  A
+ * successful set un-commits the handle: call esahrnet_commit again (the weights the host handed over are kept).  A weight the
+ * shift pushes out of fp16's range is refused by esahrnet_commit, as without a shift; nothing constrains the exponents by the
+ * weights beforehand. */
+int esahrnet_set_scale_exponents(esahrnet_handle h, const int32_t* exponents, int count);
+int esahrnet_get_scale_exponents(esahrnet_handle h, int32_t* exponents, int count);
+/* Test use: convolution `index` as esahrnet_commit would pack it under the current exponents — w f32 [cout][cin][k][k] and b f32
+ * [cout], the arrays of esahrnet_set_conv with the shifts applied.  Host only. */
+int esahrnet_debug_scaled_conv(esahrnet_handle h, int index, float* w, float* b);
+/* esahrnet_forward_stats plus the range of the one fp16-rounded tensor the plan never stores: h0 of the fused head (head_fused_bf
+ * rounds and saturates it in registers).  h0_dev: esahrnet_stats_record [n].  Where the fused head runs at the shape, it runs in
+ * its range form — the same kernel instantiated a second time, same heat-maps and head3 bit for bit — and a record holds max_abs
+ * (= max) over the finite h0 BEFORE the rounding and n_ge_f16max, the values at or above 65504 (+inf included), the other fields
+ * zero; per-lane maxima and counts, DPP and LDS inside the workgroup, one plainly stored partial per workgroup, a finish kernel
+ * per crop, no atomics: bit-reproducible and independent of the batch like the rows.  Where the materialised head runs, the
+ * record is the stored row "head0".  stats_dev is what esahrnet_forward_stats writes.  Variant 0 with precision 1 or 3. */
+int esahrnet_forward_stats_h0_workspace_bytes(esahrnet_handle h, int n, int height, int width, size_t* bytes);
+int esahrnet_forward_stats_h0(esahrnet_handle h, const void* x_dev, int n, int height, int width, void* heat_dev, void* ws_dev,
+                              size_t ws_bytes, void* stats_dev, void* h0_dev, esahrnet_stream stream);
+/* Exponents from records (host): records = esahrnet_stats_record [rows][n_total] (host copies; the crops of several batches side
+ * by side), h0_records [n_total] or NULL.  Per group, M = the largest finite max_abs over its rows and crops (head0: h0 too); the
+ * exponent e puts M * 2^-e into (2^(14 - headroom_bits), 2^(15 - headroom_bits)] — headroom_bits in 0..14, 3 leaves a factor 8
+ * to 65504 —, clamped to [-32, 32]; a group whose rows are all zero keeps 0.  Any record with n_nan or n_inf above zero is an
+ * error that names its row.  Taken on a precision-1 twin of an fp16 handle (same plan, row for row; bf16 has f32's exponent
+ * range, so nothing saturates or underflows there), one pass yields the exponents of the fp16 handle. */
+int esahrnet_scale_exponents_from_stats(esahrnet_handle h, const void* records, int rows, int n_total, const void* h0_records,
+                                        int headroom_bits, int32_t* exponents, int count);
 
 /* Stand-alone convolution on f32 NCHW device tensors through the same MFMA kernels:
  * y = [relu]( conv_{k,stride,pad=(k-1)/2}(x; w) + b [+ res] ).  w,b are HOST pointers

@@ -5,10 +5,14 @@ Prints the table (one row per tensor of the plan in plan order, then the heat-ma
 (65504 / the largest stored |value|), the rows that hold a finite |value| >= 65504 or a NaN / infinity, and max|heat-map|.
 
     python tools/range_report.py [--net seg_hrnet2] [--widths 32,64,128,256] [--precision fp32] [--state-dict FILE.pth]
-                                 [--crops FILE.npy | --size 256 --batch 4] [--gain 0.5]
+                                 [--crops FILE.npy | --size 256 --batch 4] [--gain 0.5] [--calibrate [--headroom-bits 3]]
 
 Without --state-dict the synthetic weights of synth.make_state_dict (gain --gain) are used; without --crops, synthetic
-normalised crops.  A crops file holds f32 [n, cin, h, w], already normalised as the network expects them."""
+normalised crops.  A crops file holds f32 [n, cin, h, w], already normalised as the network expects them.
+
+--calibrate (precision fp16 only): first net.calibrate_fp16 on the crops and its table — one exponent per scale
+group, the largest stored and true magnitude of each —; the report that follows is the calibrated net's, whose rows are the
+STORED values (true value x 2^-exponent)."""
 import argparse
 import os
 import sys
@@ -32,7 +36,11 @@ def main():
     ap.add_argument("--crops", default=None)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--calibrate", action="store_true")
+    ap.add_argument("--headroom-bits", type=int, default=3)
     a = ap.parse_args()
+    if a.calibrate and a.precision != "fp16":
+        raise SystemExit("--calibrate belongs to --precision fp16")
     import importlib
 
     import numpy as np
@@ -52,6 +60,10 @@ def main():
     cin = NETS[a.net][0]
     x = torch.from_numpy(np.load(a.crops).astype(np.float32)) if a.crops else synth.make_crops(a.batch, cin, a.size, a.size, seed=0)
     with torch.no_grad():
+        if a.calibrate:
+            cal = net.calibrate_fp16(x.cuda(), headroom_bits=a.headroom_bits)
+            print(cal.table())
+            print()
         st = net.activation_stats(x.cuda())
     print(st.table())
     print()
