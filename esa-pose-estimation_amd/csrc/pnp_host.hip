@@ -740,7 +740,9 @@ void pose_one(const float* kp, int k, const double* kp3d, const Cam& K, int x0, 
 
 // ---- one image from its candidate rows cand [k][M][3]: pose_one on candidate 0, then the repair step (include/esahrnet.h:
 // esahrnet_pnp_batch_cand; pnp.py: candidates_to_pose is the oracle) -------------------------------------------------------
-void pose_one_cand(const float* cand, int k, int M, const double* kp3d, const Cam& K, int x0, int y0, double rate, double thresh,
+// hess: null (the peak weights), or the image's f64 [k][M][3] Hessians / infos: the LM weight of a point that enters a solve with
+// candidate m is corr_hessian_weight(hess[j][m], rate) (esahrnet_pnp_batch_cand_w); nothing else differs
+void pose_one_cand(const float* cand, const double* hess, int k, int M, const double* kp3d, const Cam& K, int x0, int y0, double rate, double thresh,
                    int min_k, double min_ratio, double q[4], double t[3], double* rep, int* used) {
     const double reproj = 5.0;                             // ransac()'s threshold
     std::vector<int> order;
@@ -748,6 +750,8 @@ void pose_one_cand(const float* cand, int k, int M, const double* kp3d, const Ca
     const int large = correspond_rows(cand, 3 * M, k, kp3d, x0, y0, rate, thresh, min_k, order, p3, p2, wv);
     for (int j = 0; j < k; ++j) used[j] = -1;
     for (int i = 0; i < large; ++i) used[order[i]] = 0;
+    if (hess)
+        for (int i = 0; i < large; ++i) esa::corr_hessian_weight(hess + (size_t)order[i] * M * 3, rate, &wv[i * 3]);
     double r1[ESAHRNET_POSE_REPORT_DOUBLES];
     Mat3 Rj;
     double tj[3];
@@ -774,7 +778,8 @@ void pose_one_cand(const float* cand, int k, int M, const double* kp3d, const Ca
         if (pick[i]) {
             p2[i * 2] = bx;
             p2[i * 2 + 1] = by;
-            wv[i * 3] = wv[i * 3 + 2] = (double)c[pick[i] * 3 + 2];
+            if (hess) esa::corr_hessian_weight(hess + ((size_t)order[i] * M + pick[i]) * 3, rate, &wv[i * 3]);
+            else wv[i * 3] = wv[i * 3 + 2] = (double)c[pick[i] * 3 + 2];
             swapped = true;
         }
     }
@@ -852,21 +857,37 @@ extern "C" int esahrnet_pnp_batch_w(const double* pts, const double* w, const in
     return esahrnet_pnp_batch_w_ex(pts, w, count, m, k, kp3d, order, K9, threads, q_out, t_out, nullptr);
 }
 
-extern "C" int esahrnet_pnp_batch_cand(const float* cand, int n, int k, int candidates, const double* kp3d, const double* K9,
-                                       const int* boxes_xy, const double* rates, double thresh, int min_k, double min_ratio,
-                                       int threads, double* q_out, double* t_out, double* report, int* used) {
-    if (!cand || !kp3d || !K9 || !boxes_xy || !rates || !q_out || !t_out || !used) return esa::set_error("pnp_batch_cand: null argument");
-    if (n < 0) return esa::set_error("pnp_batch_cand: negative image count %d", n);
-    if (k < 1 || k > 64) return esa::set_error("pnp_batch_cand: %d keypoints per image unsupported (1..64)", k);
+// esahrnet_pnp_batch_cand (hess null, who = its name) and esahrnet_pnp_batch_cand_w
+static int pnp_batch_cand(const char* who, const float* cand, const double* hess, int n, int k, int candidates, const double* kp3d,
+                          const double* K9, const int* boxes_xy, const double* rates, double thresh, int min_k, double min_ratio,
+                          int threads, double* q_out, double* t_out, double* report, int* used) {
+    if (!cand || !kp3d || !K9 || !boxes_xy || !rates || !q_out || !t_out || !used) return esa::set_error("%s: null argument", who);
+    if (n < 0) return esa::set_error("%s: negative image count %d", who, n);
+    if (k < 1 || k > 64) return esa::set_error("%s: %d keypoints per image unsupported (1..64)", who, k);
     if (candidates < 1 || candidates > ESAHRNET_MAX_CANDIDATES)
-        return esa::set_error("pnp_batch_cand: %d candidates per keypoint unsupported (1..%d)", candidates, ESAHRNET_MAX_CANDIDATES);
-    if (!(min_ratio >= 0.0)) return esa::set_error("pnp_batch_cand: min_ratio %g must be a number >= 0", min_ratio);
+        return esa::set_error("%s: %d candidates per keypoint unsupported (1..%d)", who, candidates, ESAHRNET_MAX_CANDIDATES);
+    if (!(min_ratio >= 0.0)) return esa::set_error("%s: min_ratio %g must be a number >= 0", who, min_ratio);
     const Cam K{K9[0], K9[4], K9[2], K9[5]};
     run_batch(n, threads, [&](int lo, int hi) {
         for (int i = lo; i < hi; ++i)
-            pose_one_cand(cand + (size_t)i * k * candidates * 3, k, candidates, kp3d, K, boxes_xy[i * 2], boxes_xy[i * 2 + 1], rates[i],
-                          thresh, min_k, min_ratio, q_out + (size_t)i * 4, t_out + (size_t)i * 3,
-                          report ? report + (size_t)i * ESAHRNET_POSE_REPORT_DOUBLES : nullptr, used + (size_t)i * k);
+            pose_one_cand(cand + (size_t)i * k * candidates * 3, hess ? hess + (size_t)i * k * candidates * 3 : nullptr, k, candidates,
+                          kp3d, K, boxes_xy[i * 2], boxes_xy[i * 2 + 1], rates[i], thresh, min_k, min_ratio, q_out + (size_t)i * 4,
+                          t_out + (size_t)i * 3, report ? report + (size_t)i * ESAHRNET_POSE_REPORT_DOUBLES : nullptr,
+                          used + (size_t)i * k);
     });
     return 0;
+}
+
+extern "C" int esahrnet_pnp_batch_cand(const float* cand, int n, int k, int candidates, const double* kp3d, const double* K9,
+                                       const int* boxes_xy, const double* rates, double thresh, int min_k, double min_ratio,
+                                       int threads, double* q_out, double* t_out, double* report, int* used) {
+    return pnp_batch_cand("pnp_batch_cand", cand, nullptr, n, k, candidates, kp3d, K9, boxes_xy, rates, thresh, min_k, min_ratio,
+                          threads, q_out, t_out, report, used);
+}
+
+extern "C" int esahrnet_pnp_batch_cand_w(const float* cand, const double* hess, int n, int k, int candidates, const double* kp3d,
+                                         const double* K9, const int* boxes_xy, const double* rates, double thresh, int min_k,
+                                         double min_ratio, int threads, double* q_out, double* t_out, double* report, int* used) {
+    return pnp_batch_cand("pnp_batch_cand_w", cand, hess, n, k, candidates, kp3d, K9, boxes_xy, rates, thresh, min_k, min_ratio,
+                          threads, q_out, t_out, report, used);
 }

@@ -117,7 +117,82 @@ def heatmaps_to_keypoints(heat: torch.Tensor, refine: str = "get_final", return_
     return (out[0], out[2]) if return_hessian else out[0]
 
 
-def heatmaps_to_candidates(heat: torch.Tensor, candidates: int = 3, nms_radius: int = 6, return_index: bool = False, form=None):
+def _check_at_outputs(refine, return_hessian, return_fit, return_cov, cov_floor):
+    """What refine_at and heatmaps_to_candidates(refine=...) may be asked for: -> (decoder of esahrnet_keypoints_at, cov_floor)."""
+    check_refine(refine)
+    if return_hessian and refine == "get_final":
+        raise ValueError("return_hessian=True needs refine='get_final2' or 'gaussfit': get_final computes no Hessian")
+    if (return_fit or return_cov) and refine != "gaussfit":
+        raise ValueError("return_fit=True and return_cov=True need refine='gaussfit': only the Gaussian fit has parameters and a covariance")
+    return REFINES.index(refine), check_cov_floor(cov_floor)
+
+
+def _at_outputs(shape, decoder, return_hessian, return_fit, return_cov, device):
+    """The optional outputs of esahrnet_keypoints_at for slots of `shape`: name -> tensor or None."""
+    new = lambda dt, *tail: torch.empty((*shape, *tail), dtype=dt, device=device)      # noqa: E731
+    return {"fit": new(torch.float64, 8) if return_fit else None,
+            "status": new(torch.int32) if decoder == 2 else None,
+            "hess": new(torch.float64, 3) if return_hessian else None,
+            "cov": new(torch.float64, 3) if return_cov else None,
+            "info": new(torch.float64, 3) if return_cov else None}
+
+
+def _at_workspace(n, k, h, w, decoder, device):
+    """Scratch of esahrnet_keypoints_at, 256-byte aligned: (tensor or None, pointer or None, bytes)."""
+    nbytes = C.c_size_t()
+    _lib.check(_lib.lib().esahrnet_keypoints_at_workspace_bytes(n, k, h, w, decoder, C.byref(nbytes)))
+    if not nbytes.value:
+        return None, None, 0
+    ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, nbytes.value
+
+
+def _at_returns(o, return_hessian, return_fit, return_cov):
+    return (*((o["fit"], o["status"]) if return_fit else ()), *((o["hess"],) if return_hessian else ()),
+            *((o["cov"], o["info"]) if return_cov else ()))
+
+
+def refine_at(heat: torch.Tensor, at: torch.Tensor, refine: str = "get_final", return_hessian: bool = False,
+              return_fit: bool = False, return_cov: bool = False, cov_floor: float = 1e-6):
+    """The decoders at pixels the caller names (include/esahrnet.h esahrnet_keypoints_at): heat f32 cuda [N,K,H,W], at int32 cuda
+    [N,K] or [N,K,M] = row * W + column (the index heatmaps_to_candidates(return_index=True) and the decoders' idx hold) -> kp f32
+    cuda of at's shape + (3,) = (x, y, raw value at the pixel), refined by `refine` AT that pixel: "get_final" a row of the
+    reference's get_final(hm, coords); "get_final2" its get_final2(hm, coords), the rescale factor still the whole plane's;
+    "gaussfit" the Gaussian fit on the window around the pixel (a rejected fit keeps the get_final row).  At a plane's arg-max these
+    are the rows of heatmaps_to_keypoints / gaussfit_keypoints, bit for bit.  A pixel outside the plane (-1: no candidate) gives NaN
+    rows and status -1.  The optional outputs follow kp in the order of the existing decoders' returns, each of at's shape + its
+    own: return_fit (gaussfit) fit f64 (8,), status int32; return_hessian (get_final2, gaussfit) hess f64 (3,); return_cov
+    (gaussfit) cov f64 (3,), info f64 (3,).  No host sync; `heat` and `at` are not modified."""
+    decoder, cov_floor = _check_at_outputs(refine, return_hessian, return_fit, return_cov, cov_floor)
+    if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
+        raise ValueError("expected a 4-D tensor [N, K, H, W]")
+    if not heat.is_cuda:
+        raise RuntimeError("refine_at runs on the GPU only (no CPU fallback)")
+    if heat.dtype != torch.float32:
+        raise TypeError(f"expected float32 heatmaps, got {heat.dtype}")
+    n, k, h, w = heat.shape
+    if not (isinstance(at, torch.Tensor) and at.device == heat.device and at.dtype == torch.int32 and at.dim() in (2, 3) and
+            tuple(at.shape[:2]) == (n, k) and at.numel() > 0):
+        raise ValueError(f"at must be an int32 tensor [{n}, {k}] or [{n}, {k}, M] on {heat.device}")
+    heat, at = heat.contiguous(), at.contiguous()
+    m = at.shape[2] if at.dim() == 3 else 1
+    dev = heat.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ptr = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
+    with torch.cuda.device(dev):
+        kp = torch.empty((*at.shape, 3), dtype=torch.float32, device=dev)
+        o = _at_outputs(at.shape, decoder, return_hessian, return_fit, return_cov, dev)
+        ws, ws_ptr, ws_bytes = _at_workspace(n, k, h, w, decoder, dev)
+        _lib.check(_lib.lib().esahrnet_keypoints_at(heat.data_ptr(), n, k, h, w, at.data_ptr(), m, decoder, kp.data_ptr(),
+                                                    ptr(o["hess"]), ptr(o["fit"]), ptr(o["status"]), ptr(o["cov"]), ptr(o["info"]),
+                                                    cov_floor, ws_ptr, ws_bytes, C.c_void_p(stream)))
+    rest = _at_returns(o, return_hessian, return_fit, return_cov)
+    return (kp, *rest) if rest else kp
+
+
+def heatmaps_to_candidates(heat: torch.Tensor, candidates: int = 3, nms_radius: int = 6, return_index: bool = False, form=None,
+                           refine: str = "get_final", return_hessian: bool = False, return_fit: bool = False,
+                           return_cov: bool = False, cov_floor: float = 1e-6):
     """f32 cuda [N,K,H,W] -> f32 cuda [N,K,M,3] = (x, y, peak), the M = `candidates` (1..4) best peaks of every heat-map, best
     first (include/esahrnet.h esahrnet_keypoints_candidates, one kernel, no host sync).  Candidate 0 is the row of
     heatmaps_to_keypoints, bit for bit; candidate m >= 1 is the largest local maximum (>= its 8 neighbours, neither NaN nor
@@ -126,7 +201,15 @@ def heatmaps_to_candidates(heat: torch.Tensor, candidates: int = 3, nms_radius: 
     cuda [N,K,M] = row * W + column of each candidate, -1 where there is none).  pnp.candidates_to_pose_batch solves on them.
     form (esahrnet_keypoints_candidates_form): 0 the multi-sweep kernel, 1 the one-sweep kernel (the same bits; refused on a plane
     it does not serve: not 16-byte aligned, W no multiple of 4, more than 4096 cells of 8 x 8), -1 what the fused paths launch;
-    None (default): esahrnet_keypoints_candidates, the multi-sweep kernel."""
+    None (default): esahrnet_keypoints_candidates, the multi-sweep kernel.
+    refine="get_final2" / "gaussfit", or any of return_hessian / return_fit / return_cov (include/esahrnet.h
+    esahrnet_keypoints_candidates_refined, form None or -1 only): the same search, then every candidate's (x, y) refined by that decoder
+    at the candidate's own pixel, as refine_at does on the index; the peak column is the raw value there either way.  The optional
+    outputs follow cand (and idx) in refine_at's order, each [N,K,M] + its own shape; rows without a candidate are NaN, status -1."""
+    decoder, cov_floor = _check_at_outputs(refine, return_hessian, return_fit, return_cov, cov_floor)
+    refined = decoder != 0 or return_hessian or return_fit or return_cov
+    if refined and form not in (None, -1):
+        raise ValueError(f"form={form!r} names a kernel of the plain search: a refined call (refine={refine!r}) takes form None or -1")
     if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
         raise ValueError("expected a 4-D tensor [N, K, H, W]")
     if not heat.is_cuda:
@@ -138,9 +221,20 @@ def heatmaps_to_candidates(heat: torch.Tensor, candidates: int = 3, nms_radius: 
     m = int(candidates)
     # (the library refuses M outside 1..4 and a negative radius with its own text; nothing is allocated by M before that)
     cand = torch.empty((n, k, min(max(m, 1), _lib.MAX_CANDIDATES), 3), dtype=torch.float32, device=heat.device)
-    idx = torch.empty(cand.shape[:3], dtype=torch.int32, device=heat.device) if return_index else None
+    idx = torch.empty(cand.shape[:3], dtype=torch.int32, device=heat.device) if return_index or refined else None
     stream = torch.cuda.current_stream(heat.device).cuda_stream
     with torch.cuda.device(heat.device):
+        if refined:
+            ptr = lambda t: None if t is None else t.data_ptr()             # noqa: E731
+            o = _at_outputs(cand.shape[:3], decoder, return_hessian, return_fit, return_cov, heat.device)
+            ws, ws_ptr, ws_bytes = _at_workspace(n, k, h, w, decoder, heat.device)
+            _lib.check(_lib.lib().esahrnet_keypoints_candidates_refined(heat.data_ptr(), n, k, h, w, m, int(nms_radius), decoder,
+                                                                        cand.data_ptr(), idx.data_ptr(), ptr(o["hess"]),
+                                                                        ptr(o["fit"]), ptr(o["status"]), ptr(o["cov"]),
+                                                                        ptr(o["info"]), cov_floor, ws_ptr, ws_bytes,
+                                                                        C.c_void_p(stream)))
+            out = (cand, *((idx,) if return_index else ()), *_at_returns(o, return_hessian, return_fit, return_cov))
+            return out if len(out) > 1 else cand
         if form is None:
             _lib.check(_lib.lib().esahrnet_keypoints_candidates(heat.data_ptr(), n, k, h, w, m, int(nms_radius), cand.data_ptr(),
                                                                 idx.data_ptr() if return_index else None, C.c_void_p(stream)))
@@ -418,7 +512,7 @@ def get_max_preds(batch_heatmaps):
 def get_final(hm, coords=None):
     """inference.py:136-152 contract for one sample: hm [1,K,H,W] -> refined preds [K,2].
     `coords` (the caller's integer arg-max list) is accepted and ignored: the fused kernel
-    recomputes the identical arg-max."""
+    recomputes the identical arg-max.  get_final_at refines at the coords it is given."""
     t = _to_device(hm)
     kp = heatmaps_to_keypoints(t[:1])
     return kp[0, :, :2].cpu().numpy()
@@ -428,9 +522,46 @@ def get_final2(hm, coords=None):
     """inference.py:154-169 contract for one sample: hm [1,K,H,W] -> refined preds [K,2] (blur + full-Hessian Newton step).
     `coords` is accepted and ignored: the kernel recomputes the identical arg-max of the raw maps.  Unlike the reference,
     `hm` is NOT modified (the reference blurs the caller's array in place), and a plane whose maxima, rescale factor or
-    offset are not finite keeps its integer coordinates."""
+    offset are not finite keeps its integer coordinates.  get_final2_at refines at the coords it is given."""
     t = _to_device(hm)
     kp = heatmaps_to_keypoints(t[:1], refine="get_final2")
+    return kp[0, :, :2].cpu().numpy()
+
+
+def _coords_to_at(hm, coords):
+    """coords [K,2] = integer-valued (x, y) inside the planes of hm [1,K,H,W] -> int32 tensor [1,K] = y * W + x (host)."""
+    if len(hm.shape) != 4 or hm.shape[0] < 1:
+        raise ValueError("expected heat-maps [1, K, H, W]")
+    k, h, w = hm.shape[1:]
+    c = np.asarray(coords.detach().cpu() if isinstance(coords, torch.Tensor) else coords, np.float64)
+    if c.shape != (k, 2):
+        raise ValueError(f"coords must be [{k}, 2] = (x, y) per heat-map, got {c.shape}")
+    if not (np.isfinite(c).all() and (c == np.floor(c)).all()):
+        raise ValueError("coords must be integer-valued pixels (x, y): the reference takes int(coord) of the arg-max it was handed")
+    if not ((c >= 0).all() and (c[:, 0] < w).all() and (c[:, 1] < h).all()):
+        raise ValueError(f"coords outside the {h} x {w} plane")
+    at = c[:, 1].astype(np.int64) * w + c[:, 0].astype(np.int64)
+    return torch.from_numpy(at.astype(np.int32)).reshape(1, k)
+
+
+def get_final_at(hm, coords):
+    """inference.py:136-152 with `coords` honoured: hm [1,K,H,W], coords [K,2] the integer-valued (x, y) to refine at (the
+    reference's get_final(hm, coords) reads int(coord[0]), int(coord[1])) -> refined preds [K,2].  get_final ignores coords and
+    refines at the arg-max; this one refines where it is told (refine_at).  Coordinates that are not integer-valued or lie outside
+    the plane raise ValueError.  `hm` is not modified."""
+    at = _coords_to_at(hm, coords)                     # (refusals first: they need no device)
+    t = _to_device(hm)
+    kp = refine_at(t[:1], at.to(t.device))
+    return kp[0, :, :2].cpu().numpy()
+
+
+def get_final2_at(hm, coords):
+    """inference.py:154-169 with `coords` honoured, as get_final_at: blur, rescale by the plane's raw maximum over its blurred
+    maximum, log, full-Hessian Newton step at the given pixel.  Unlike the reference `hm` is NOT modified, and a plane whose maxima,
+    rescale factor or offset are not finite keeps its integer coordinates (as get_final2)."""
+    at = _coords_to_at(hm, coords)
+    t = _to_device(hm)
+    kp = refine_at(t[:1], at.to(t.device), refine="get_final2")
     return kp[0, :, :2].cpu().numpy()
 
 

@@ -212,6 +212,46 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
     return (poses, rep) if return_report else poses
 
 
+def candidate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, candidates: int = 3, refine: str = "get_final2",
+                    weights: str = "hessian", nms_radius: int = 6, min_ratio: float = 0.3, scale: int = 256, thresh: float = 0.8,
+                    min_k: int = 24, on_fail: str = "raise", return_report: bool = False, max_rms_px=None, min_inliers=None,
+                    cov_floor: float = 1e-6, threads: int = 0):
+    """Runner-up repair AND anisotropic weights, the combination estimate_poses refuses (its candidates=M is get_final with peak
+    weights; its weights="hessian" / "covariance" know the arg-max only).  frames, bboxes, kp3d, K, scale, thresh, min_k, on_fail,
+    the report and the gates as in estimate_poses -> list of (q, t) per image[, report with .used and .rescued].
+    Host crops as on the "heatmaps" path (crops.crop_batch), then inference.heatmaps_to_candidates(net(x), candidates, nms_radius,
+    refine=refine, ...): every candidate of every heat-map is refined by `refine` at its own pixel and carries the decoder's
+    Hessian (weights="hessian": refine "get_final2" or "gaussfit") or the information of its fitted centre (weights="covariance":
+    refine="gaussfit"), ONE device->host copy of candidates and weights, then pnp.candidates_to_pose_batch(..., hess=...): the
+    repair step of estimate_poses(candidates=M), with every point, a swapped-in runner-up included, weighed by
+    rate * (-H)^(1/2) in the refinement.  weights="peak" passes no Hessian; with refine="get_final" that is
+    estimate_poses(..., candidates=M), bit for bit.  The forward-fused and device-loader forms, device_select and distributed are
+    not built for this combination."""
+    inference.check_refine(refine)
+    mode = inference.check_weights(weights, refine)
+    cov_floor = inference.check_cov_floor(cov_floor)
+    want = return_report or max_rms_px is not None or min_inliers is not None
+    x, boxes, rates = crops.crop_batch(frames, bboxes, scale)
+    ask = {"return_hessian": weights == "hessian", "return_cov": weights == "covariance", "cov_floor": cov_floor}
+    with torch.no_grad():
+        out = inference.heatmaps_to_candidates(net(x), candidates, nms_radius, refine=refine, **ask)
+    cand, hess = (out[0], out[-1]) if mode else (out, None)            # (return_cov: cov, info — info is what weighs)
+    if mode:                                            # the only device->host copy: one buffer, hess | cand (the f64 part first)
+        n, k, mm = cand.shape[:3]
+        host = torch.cat([hess.reshape(-1).view(torch.uint8), cand.reshape(-1).view(torch.uint8)]).cpu().numpy()
+        hess = host[:n * k * mm * 24].view(np.float64).reshape(n, k, mm, 3)
+        cand = host[n * k * mm * 24:].view(np.float32).reshape(n, k, mm, 3)
+    else:
+        cand = cand.cpu().numpy()
+    q, t, _, *rep = pnp.candidates_to_pose_batch(cand, kp3d, np.asarray(K, np.float64), [(b[0], b[1]) for b in boxes], rates, thresh,
+                                                 min_k, min_ratio, threads, report=want, hess=hess)
+    poses, rep = [(q[i], t[i]) for i in range(len(boxes))], rep[0] if want else None
+    if want:
+        poses = _gated_poses(poses, rep, max_rms_px, min_inliers)
+    poses = _checked_poses(poses, on_fail)
+    return (poses, rep) if return_report else poses
+
+
 def _fetch(packed, m, k, fields):
     """A path's only device->host copy: the packed record of m crops, and its numpy views (inference.record_views)."""
     return inference.record_views(packed.cpu().numpy(), m, k, fields)

@@ -512,7 +512,25 @@ def correspondences_to_pose_batch(pts, w, count, order, kp3d, K, threads=0, repo
     return q, t
 
 
-def candidates_to_pose_batch(cand, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=24, min_ratio=0.3, threads=0, report=False):
+def hessian_weight(H, rate):
+    """csrc/correspond.h corr_hessian_weight in numpy: H = (dxx, dxy, dyy) -> rate * (-H)^(1/2) as (wxx, wxy, wyy), the 2x2 weight
+    of uncertainty_pnp.cpp:30-31 in image pixels; zeros where -H is not positive definite, H holds a NaN or the weight is not
+    finite.  Closed form for A = -H = [[a, b], [b, c]]: s = sqrt(det A), t = sqrt(a + c + 2 s), A^(1/2) = (A + s I) / t."""
+    f = np.float64
+    a, b, c = -f(H[0]), -f(H[1]), -f(H[2])
+    rate = f(rate)
+    with np.errstate(all="ignore"):
+        det = a * c - b * b
+        if not (a > 0.0 and det > 0.0):
+            return np.zeros(3)
+        s = np.sqrt(det)
+        t = np.sqrt((a + c) + f(2.0) * s)
+        w = np.array([rate * ((a + s) / t), rate * (b / t), rate * ((c + s) / t)])
+    return w if np.isfinite(w).all() else np.zeros(3)
+
+
+def candidates_to_pose_batch(cand, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=24, min_ratio=0.3, threads=0, report=False,
+                             hess=None):
     """keypoints_to_pose_batch on the candidates of inference.heatmaps_to_candidates, with the repair step of
     `esahrnet_pnp_batch_cand` (include/esahrnet.h): cand [N,K,M,3] f32 = (x, y, peak), best first.  Per image the solve on
     candidate 0; where that pose has a RANSAC consensus, every selected keypoint whose primary lies >= 5 px from its projection
@@ -521,7 +539,11 @@ def candidates_to_pose_batch(cand, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=2
     -> (q [N,4], t [N,3], used [N,K] int32: the candidate rank each keypoint entered the returned solve with, -1 = not selected).
     With M = 1, and for images in which nothing is replaced, the bits of keypoints_to_pose_batch on cand[:, :, 0].
     `candidates_to_pose` below is its oracle.  report=True: -> (q, t, used, rep), rep a PoseReport of the returned poses with
-    rep.used and rep.rescued."""
+    rep.used and rep.rescued.
+    hess [N,K,M,3] f64 (`esahrnet_pnp_batch_cand_w`): every candidate's Hessian, or gaussfit's info, from
+    inference.heatmaps_to_candidates(refine=..., return_hessian / return_cov=True).  The same steps; the LM weighs every point, a
+    primary or a runner-up that was swapped in, by hessian_weight(hess[i, j, m], rate) instead of its peak (zero where -H is not
+    positive definite or NaN: the point still reaches EPnP / RANSAC)."""
     import ctypes as C
     import os
     from . import _lib
@@ -541,8 +563,17 @@ def candidates_to_pose_batch(cand, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=2
     if threads <= 0:
         threads = min(16, len(os.sched_getaffinity(0))) if hasattr(os, "sched_getaffinity") else 4
     p = lambda a: a.ctypes.data_as(C.c_void_p)                       # noqa: E731
-    _lib.check(_lib.lib().esahrnet_pnp_batch_cand(p(cand), n, k, m, p(kp3d), p(K9), p(bxy), p(rt), float(thresh), int(min_k),
-                                                  float(min_ratio), int(threads), p(q), p(t), p(rep) if report else None, p(used)))
+    if hess is not None:
+        hess = np.ascontiguousarray(hess, np.float64)
+        if hess.shape != (n, k, m, 3):
+            raise ValueError(f"expected hess [N, K, M, 3] = {(n, k, m, 3)}, got {hess.shape}")
+        _lib.check(_lib.lib().esahrnet_pnp_batch_cand_w(p(cand), p(hess), n, k, m, p(kp3d), p(K9), p(bxy), p(rt), float(thresh),
+                                                        int(min_k), float(min_ratio), int(threads), p(q), p(t),
+                                                        p(rep) if report else None, p(used)))
+    else:
+        _lib.check(_lib.lib().esahrnet_pnp_batch_cand(p(cand), n, k, m, p(kp3d), p(K9), p(bxy), p(rt), float(thresh), int(min_k),
+                                                      float(min_ratio), int(threads), p(q), p(t), p(rep) if report else None,
+                                                      p(used)))
     if not report:
         return q, t, used
     rep = PoseReport(rep)
@@ -551,10 +582,11 @@ def candidates_to_pose_batch(cand, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=2
     return q, t, used, rep
 
 
-def candidates_to_pose(cand, kp3d, K, bbox_xy, rate, thresh=0.8, min_k=24, min_ratio=0.3, reproj_err=5.0):
+def candidates_to_pose(cand, kp3d, K, bbox_xy, rate, thresh=0.8, min_k=24, min_ratio=0.3, reproj_err=5.0, hess=None):
     """The numpy statement of one image of candidates_to_pose_batch (its oracle): cand [K,M,3] -> (q [w,x,y,z], t, used [K]).
     keypoints_to_pose's steps on candidate 0, the judge = solve_pnp_ransac's pose (EPnP on the consensus set), the swap rule,
-    then the same steps on the repaired points; taken iff the consensus grew."""
+    then the same steps on the repaired points; taken iff the consensus grew.  hess [K,M,3]: cpnp_m gets the [n,3] weights
+    hessian_weight(hess[j, m], rate) of the candidates that enter each solve instead of their peaks."""
     from .inference import crop_to_image, select_keypoints
     cand = np.asarray(cand, np.float32)
     assert cand.ndim == 3 and cand.shape[2] == 3, cand.shape
@@ -570,7 +602,8 @@ def candidates_to_pose(cand, kp3d, K, bbox_xy, rate, thresh=0.8, min_k=24, min_r
         return rotation_to_quat_wxyz(rodrigues(cam[:3])), cam[3:], (R, t), inliers, fallback
 
     p2d = crop_to_image(c64[:, 0, :2], rate, bbox_xy[0], bbox_xy[1])[idxs]
-    w = c64[idxs, 0, 2]
+    weight = (lambda j, m: c64[j, m, 2]) if hess is None else (lambda j, m: hessian_weight(np.asarray(hess, np.float64)[j, m], rate))
+    w = np.array([weight(j, 0) for j in idxs]) if hess is not None else c64[idxs, 0, 2]
     used = np.full(nk, -1, np.int32)
     used[idxs] = 0
     q1, t1, judge, inl1, fallback = solve(p2d, w)
@@ -590,7 +623,7 @@ def candidates_to_pose(cand, kp3d, K, bbox_xy, rate, thresh=0.8, min_k=24, min_r
             xy = crop_to_image(c64[j, m, :2], rate, bbox_xy[0], bbox_xy[1])
             d = float(np.linalg.norm(proj[i] - xy))
             if d < best:
-                best, pick[i], p2d[i], w[i] = d, m, xy, c64[j, m, 2]
+                best, pick[i], p2d[i], w[i] = d, m, xy, weight(j, m)
     if not pick.any():
         return q1, t1, used
     try:

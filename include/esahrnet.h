@@ -532,6 +532,66 @@ int esahrnet_pnp_batch_cand(const float* cand, int n, int k, int candidates, con
                             const int* boxes_xy, const double* rates, double thresh, int min_k, double min_ratio, int threads,
                             double* q_out, double* t_out, double* report, int* used);
 
+/* ---- the decoders at pixels the caller names (csrc/keypoints_at.hip) ---------------------------------------------
+ * esahrnet_keypoints_at: heat_dev f32 [n][k][height][width] and at_dev int32 [n][k][m], m >= 1 pixels per heat-map as row * width +
+ * column (what idx_dev and cidx_dev of the other decoders hold) -> kp_dev f32 [n][k][m][3] = (x, y, raw value at the pixel), slot
+ * (plane, j) decoded at at_dev[plane][j] by one wave:
+ *   decoder 0  get_final: the row esahrnet_keypoints_ex writes for a plane whose arg-max is that pixel, the row
+ *              esahrnet_keypoints_candidates writes for a candidate there, bit for bit; a row of the reference's
+ *              get_final(hm, coords) (inference.py:136-152) plus the raw value.  Optional outputs: none.
+ *   decoder 1  get_final2 (inference.py:154-169).  The rescale factor stays a quantity of the whole plane, raw maximum over blurred
+ *              maximum (inference.py:104-109): the tile pass of esahrnet_keypoints_final2 runs once per plane, whatever m, and the
+ *              finish of a slot evaluates the 13 blurred points around its own pixel, then the guards and the Newton step of
+ *              esahrnet_keypoints_final2_hess.  When no step is taken (a pixel within 2 px of the border, det == 0, a maximum, factor
+ *              or offset that is not finite) the row keeps the integer pixel and hess is NaN x 3.  The third column is the raw value
+ *              at the pixel, not the plane's maximum.  Optional output: hess_dev f64 [n][k][m][3] = (dxx, dxy, dyy).  At the plane's
+ *              arg-max kp and hess have the bits of esahrnet_keypoints_final2_hess.  ws_dev: esahrnet_keypoints_at_workspace_bytes
+ *              bytes (what esahrnet_keypoints_final2_workspace_bytes asks for: it does not grow with m), 256-byte aligned; the
+ *              result does not depend on what it held.
+ *   decoder 2  gaussfit: decoder 0's row at the pixel, then the fit of esahrnet_keypoints_gaussfit_cov on the 13 x 13 window around
+ *              that pixel; an accepted fit replaces x and y, a rejected one keeps decoder 0's row.  status_dev is required; optional
+ *              outputs: fit_dev f64 [n][k][m][8], hess_dev, cov_dev and info_dev f64 [n][k][m][3], with the meaning they have in
+ *              esahrnet_keypoints_gaussfit_cov (cov_floor too); at the plane's arg-max every output has that entry's bits.
+ * Decoders 0 and 2 need no workspace (0 bytes; ws_dev may be NULL).  status_dev int32 [n][k][m] (NULL with decoders 0 and 1: not
+ * written): decoder 2's fit status, 0 with decoders 0 and 1; -1 for a pixel outside the plane.
+ * A pixel outside [0, height * width) cannot be refused from inside a kernel (-1 is what cidx_dev holds where a heat-map has no
+ * candidate): that slot gets NaN x 3 in kp_dev, NaN in every f64 output and status -1, and nothing of the plane is read for it.
+ * Every output is written whole; heat_dev and at_dev are only read.  A slot's result depends on its plane and its pixel alone, not
+ * on n, k, m or its place among them.  The call allocates nothing, does not synchronise and may be captured into a graph.
+ * Refused, in this order and before anything is enqueued: a NULL heat_dev, at_dev or kp_dev; a size that is not positive, height *
+ * width or n * k beyond int32; m < 1 (or n * k * m beyond int32); a decoder outside 0..2; an output the decoder does not write that
+ * is not NULL (decoder 0: hess_dev, fit_dev, cov_dev, info_dev; decoder 1: fit_dev, cov_dev, info_dev); decoder 2 without
+ * status_dev; a cov_floor that is negative or not finite (every decoder); heat_dev, at_dev, kp_dev or status_dev not 4-byte aligned;
+ * hess_dev, fit_dev, cov_dev or info_dev not 8-byte aligned; decoder 1: more than 2^23 - 1 tiles, a workspace that is NULL or too
+ * small, a workspace that is not 256-byte aligned.
+ *
+ * esahrnet_keypoints_candidates_refined: esahrnet_keypoints_candidates_form(form -1) into cand_dev f32 [n][k][M][3] and cidx_dev int32
+ * [n][k][M] (required here), then the kernels above with at_dev = cidx_dev and kp_dev = cand_dev: the refined (x, y) of every
+ * candidate go into cand_dev, the peak column keeps the candidate kernel's value (the raw value at the pixel), rows without a
+ * candidate stay NaN.  With decoder 0 cand_dev and cidx_dev are esahrnet_keypoints_candidates', bit for bit (nothing more is launched
+ * unless status_dev is given); with decoders 1 and 2 every output has the bits of the two calls made one after the other.  Refused:
+ * a NULL heat_dev, cand_dev or cidx_dev, the shape, M outside 1..ESAHRNET_MAX_CANDIDATES, r < 0, then everything above with m = M. */
+int esahrnet_keypoints_at_workspace_bytes(int n, int k, int height, int width, int decoder, size_t* bytes);
+int esahrnet_keypoints_at(const void* heat_dev, int n, int k, int height, int width, const void* at_dev, int m, int decoder,
+                          void* kp_dev, void* hess_dev, void* fit_dev, void* status_dev, void* cov_dev, void* info_dev,
+                          double cov_floor, void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+int esahrnet_keypoints_candidates_refined(const void* heat_dev, int n, int k, int height, int width, int candidates, int nms_radius,
+                                          int decoder, void* cand_dev, void* cidx_dev, void* hess_dev, void* fit_dev,
+                                          void* status_dev, void* cov_dev, void* info_dev, double cov_floor, void* ws_dev,
+                                          size_t ws_bytes, esahrnet_stream stream);
+
+/* esahrnet_pnp_batch_cand with the 2x2 weights of esahrnet_correspondences(mode 1) in the refinement: hess = f64 [n][k][M][3], for
+ * every candidate the Hessian (hess_dev of esahrnet_keypoints_at / _candidates_refined with decoder 1 or 2) or gaussfit's info_dev
+ * (decoder 2), a host copy.  The same steps 1-6: selection and back-projection (csrc/correspond.h), the RANSAC consensus pose as the
+ * judge, the swap rule on distances and peak ratios, acceptance iff the consensus grew.  One thing differs: in both solves the LM
+ * weight of every point, a primary or a runner-up that was swapped in, is rate * (-hess[i][j][m])^(1/2) (corr_hessian_weight, the
+ * weight esahrnet_correspondences(mode 1) gives), which is zero where -H is not positive definite or holds a NaN -- such a point
+ * still reaches EPnP / RANSAC.  hess == NULL: the peak weights, esahrnet_pnp_batch_cand's outputs bit for bit.  A row depends on
+ * its image alone: the same bits for any `threads`.  Refused: what esahrnet_pnp_batch_cand refuses, with this entry's name. */
+int esahrnet_pnp_batch_cand_w(const float* cand, const double* hess, int n, int k, int candidates, const double* kp3d,
+                              const double* K9, const int* boxes_xy, const double* rates, double thresh, int min_k,
+                              double min_ratio, int threads, double* q_out, double* t_out, double* report, int* used);
+
 /* The packed records of the device path after the all-gather of a sharded batch (csrc/records.hip).  A packed record is
  * field-major: field f holds field_bytes[f] bytes per crop, all crops of field 0 first, then field 1, ..., so field f of a
  * record laid out for m crops starts at off_f(m) = m * (field_bytes[0] + ... + field_bytes[f-1]).  gathered_dev: `world`

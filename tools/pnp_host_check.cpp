@@ -93,6 +93,37 @@ static int check_candidates(const char* path) {
             std::fprintf(stderr, "candidate record %d: one candidate is not esahrnet_pnp_batch_ex\n", nrec);
             return 1;
         }
+        // esahrnet_pnp_batch_cand_w: a Hessian per candidate row (NaN where the row is, a saddle every 13th), exactly sized;
+        // the same bits at 1 and 4 threads, with and without a report; with hess null the bits of esahrnet_pnp_batch_cand
+        std::vector<double> hess((size_t)m * k * M * 3), qw0, tw0, repw0;
+        for (size_t i = 0; i < (size_t)m * k * M; ++i) {
+            const bool none = std::isnan(cand[i * 3]);
+            hess[i * 3 + 0] = none ? NAN : i % 13 == 12 ? 0.1 : -(0.05 + 0.01 * (double)(i % 7));
+            hess[i * 3 + 1] = none ? NAN : 0.01 * ((double)(i % 5) - 2.0);
+            hess[i * 3 + 2] = none ? NAN : -(0.08 + 0.01 * (double)(i % 3));
+        }
+        std::vector<int32_t> usedw0;
+        for (int threads : {1, 4})
+            for (int with_report = 0; with_report < 2; ++with_report)
+                for (int with_hess = 0; with_hess < 2; ++with_hess) {
+                    std::vector<double> q((size_t)m * 4), t((size_t)m * 3), rep(with_report ? m * R : 0);
+                    std::vector<int32_t> used((size_t)m * k);
+                    if (esahrnet_pnp_batch_cand_w(cand.data(), with_hess ? hess.data() : nullptr, m, k, M, kp3d.data(), K9.data(), boxes.data(),
+                                                  rates.data(), sel[0], (int)sel[1], sel[2], threads, q.data(), t.data(),
+                                                  with_report ? rep.data() : nullptr, used.data())) {
+                        std::fprintf(stderr, "candidate record %d: %s\n", nrec, esa::g_err);
+                        return 1;
+                    }
+                    if (with_hess && qw0.empty()) { qw0 = q; tw0 = t; usedw0 = used; }
+                    if (with_hess && with_report && repw0.empty()) repw0 = rep;
+                    const bool ok = with_hess ? same(q, qw0) && same(t, tw0) && used == usedw0 && (!with_report || same(rep, repw0))
+                                              : same(q, q0) && same(t, t0) && used == used0 && (!with_report || same(rep, rep0));
+                    if (!ok) {
+                        std::fprintf(stderr, "candidate record %d: weighted results differ (threads %d, report %d, hess %d)\n", nrec, threads,
+                                     with_report, with_hess);
+                        return 1;
+                    }
+                }
         int rescued = 0, swaps = 0, solved = 0;
         for (int i = 0; i < m; ++i) {
             int s = 0;
@@ -115,6 +146,12 @@ static int check_candidates(const char* path) {
         esahrnet_pnp_batch_cand(c, 1, 11, 1, z, z, b, z, 0.5, 0, -1.0, 1, q, t, nullptr, used) != 1 || !std::strstr(esa::g_err, "min_ratio") ||
         esahrnet_pnp_batch_cand(c, 1, 11, 1, z, z, b, z, 0.5, 0, 0.3, 1, q, t, nullptr, nullptr) != 1 || !std::strstr(esa::g_err, "null")) {
         std::fprintf(stderr, "a bad argument of esahrnet_pnp_batch_cand was not refused\n");
+        return 1;
+    }
+    if (esahrnet_pnp_batch_cand_w(c, z, 1, 11, 5, z, z, b, z, 0.5, 0, 0.3, 1, q, t, nullptr, used) != 1 || !std::strstr(esa::g_err, "pnp_batch_cand_w") ||
+        esahrnet_pnp_batch_cand_w(c, z, 1, 11, 1, z, z, b, z, 0.5, 0, -1.0, 1, q, t, nullptr, used) != 1 || !std::strstr(esa::g_err, "min_ratio") ||
+        esahrnet_pnp_batch_cand_w(nullptr, z, 1, 11, 1, z, z, b, z, 0.5, 0, 0.3, 1, q, t, nullptr, used) != 1 || !std::strstr(esa::g_err, "null")) {
+        std::fprintf(stderr, "a bad argument of esahrnet_pnp_batch_cand_w was not refused\n");
         return 1;
     }
     std::printf("ok: %d candidate records\n", nrec);
