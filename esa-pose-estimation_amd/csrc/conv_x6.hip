@@ -50,7 +50,9 @@
 // debug build only (tools/trace_x6.py, -DX6_TRACE=1): shader-clock stamps of the first workgroups' wave 0, 8 events x 32 steps
 __device__ unsigned long long g_x6_trace[64 * 32 * 8];
 extern "C" int esa_debug_x6_trace(void* dst) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_x6_trace), sizeof(g_x6_trace)); }
-__device__ unsigned long long g_x6_wg[1024 * 4];      // per workgroup: wall clock (100 MHz) at start / end, steps, HW_ID
+// per workgroup: wall clock (100 MHz) at start / end, steps, HW_ID, shader clock at start / loop entry, wall clock at loop
+// entry, shader clock at end
+__device__ unsigned long long g_x6_wg[1024 * 8];
 extern "C" int esa_debug_x6_wg(void* dst) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_x6_wg), sizeof(g_x6_wg)); }
 #endif
 
@@ -88,6 +90,9 @@ extern "C" int esa_debug_x6_wg(void* dst) { return (int)hipMemcpyFromSymbol(dst,
 #endif
 #ifndef X6_PRIO_FLIP
 #define X6_PRIO_FLIP 1
+#endif
+#ifndef X6_SERIAL_PROLOGUE
+#define X6_SERIAL_PROLOGUE 0     // 1: x6_body starts its stream as it did before "one exposed round trip": three dependent trips
 #endif
 
 namespace esa {
@@ -243,6 +248,9 @@ __device__ __forceinline__ void x6_body(const ConvParams& p, const X6Geo& geo, c
     X6Pos cur;
     cur.item = xcd_contiguous(bid, G);
     if (cur.item >= geo.nitems) return;
+#ifdef X6_TRACE
+    const unsigned long long tr_rt0 = __builtin_amdgcn_s_memrealtime(), tr_c0 = __builtin_amdgcn_s_memtime();      // stored at loop entry
+#endif
     auto decode = [&](X6Pos& q) {
         const int q1 = x6_div(q.item, geo.ctiles, geo.m_ct);
         q.ct = q.item - q1 * geo.ctiles;
@@ -490,36 +498,78 @@ __device__ __forceinline__ void x6_body(const ConvParams& p, const X6Geo& geo, c
 #pragma unroll
         for (int it = i0; it < i0 + XH; ++it) write_unit(buf, i0, it);
     };
+    auto load_w_first = [&]() __attribute__((always_inline)) {
+        if constexpr (W2) {
+            load_w(cur.ct, 0, 0, 0);            // step 0's first third; the others are loaded one phase ahead inside the steps
+        } else {
+#pragma unroll
+            for (int kx = 0; kx < KS; ++kx) load_w(cur.ct, 0, kx, 0);
+        }
+    };
     tile_offsets(cur);
-    if constexpr (STEM) {
-        raw_load(cur);
-        raw_commit(0);
-        __syncthreads();            // (also publishes w1s)
-        stage_stem(0, cur, 0);
+    X6Pos nxt;
+    f32x4 bv;
+    if constexpr (X6_SERIAL_PROLOGUE || STEM) {
+        // The start as it was, three dependent round trips: tile half, wait, tile half, wait, weights, wait.  The fused stem
+        // (crop, barrier, conv1 of a tile, next crop, weights) keeps it: its workgroups walk 32 steps and the launch's time
+        // did not move when the weights and the next crop were issued ahead of conv1 (DESIGN 5.0a "How a stream starts").
+        if constexpr (STEM) {
+            raw_load(cur);
+            raw_commit(0);
+            __syncthreads();            // (also publishes w1s)
+            stage_stem(0, cur, 0);
+        } else {
+            load_tile(cur, H0);
+            write_tile(0, H0);
+            if constexpr (XH < XITER) {
+                load_tile(cur, H1);
+                write_tile(0, H1);
+            }
+        }
+        nxt = advance(cur);
+        if (nxt.c == 0) tile_offsets(nxt);
+        if constexpr (STEM) {
+            raw_load(nxt);
+            raw_commit(1);              // (published by the loop's first barrier)
+        }
+        if constexpr (DEEP) load_next(nxt);
+        __builtin_amdgcn_sched_barrier(0);
+        load_w_first();
+        bv = load_bias(cur.ct);
     } else {
+        // ONE exposed round trip: every load of the start is issued back to back — the whole tile of step 0 (its second half
+        // into registers of its own, live only here: the accumulators and the operand ring are dead), then the weights, then
+        // the bias.  Loads return in order, so the tile is waited for with a counted vmcnt while the weights are still in
+        // flight; the split + LDS writes of both halves and the stream's next position run under the weights' latency.
+        u32x4 xp[XH < XITER ? XITER - XH : 1][2];
         load_tile(cur, H0);
+        if constexpr (XH < XITER) {
+            const __amdgpu_buffer_rsrc_t rx = x6_rsrc(p.x + (size_t)cur.n * ximg, ximg);
+#pragma unroll
+            for (int it = XH; it < XITER; ++it) {
+                if (!(X6_ABL & 1)) {
+                    xp[it - XH][0] = __builtin_amdgcn_raw_buffer_load_b128(rx, (int)xoff[it], cur.c * 128, 0);
+                    xp[it - XH][1] = __builtin_amdgcn_raw_buffer_load_b128(rx, (int)xoff[it], cur.c * 128 + 64, 0);
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);      // (tile before weights: the counted wait below relies on the order)
+        load_w_first();
+        bv = load_bias(cur.ct);
+        __builtin_amdgcn_sched_barrier(0);
+        nxt = advance(cur);
+        if (nxt.c == 0) tile_offsets(nxt);      // (the loads above have taken their offsets; integer VALU in the loads' shadow)
+        __builtin_amdgcn_sched_barrier(0);
         write_tile(0, H0);
         if constexpr (XH < XITER) {
-            load_tile(cur, H1);
-            write_tile(0, H1);
+#pragma unroll
+            for (int it = XH; it < XITER; ++it)
+                if (!(X6_ABL & 2)) emit_unit(0, it, xp[it - XH]);
         }
-    }
-    X6Pos nxt = advance(cur);
-    if (nxt.c == 0) tile_offsets(nxt);
-    if constexpr (STEM) {
-        raw_load(nxt);
-        raw_commit(1);              // (published by the loop's first barrier)
+        if constexpr (DEEP) load_next(nxt);
+        __builtin_amdgcn_sched_barrier(0);
     }
     int sidx = 0;
-    if constexpr (DEEP) load_next(nxt);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (W2) {
-        load_w(cur.ct, 0, 0, 0);            // step 0's first third; the others are loaded one phase ahead inside the steps
-    } else {
-#pragma unroll
-        for (int kx = 0; kx < KS; ++kx) load_w(cur.ct, 0, kx, 0);
-    }
-    f32x4 bv = load_bias(cur.ct);
     asm volatile("" : "+v"(bv));                // (waited for here, once: at the loop head hipcc would otherwise merge "bias pending
                                                 // behind 27 weight loads" into every iteration's state and drain vmcnt(0) there)
     if constexpr (WRES) {                       // likewise the resident fragments: complete before the loop, nothing pending at its head
@@ -539,9 +589,12 @@ __device__ __forceinline__ void x6_body(const ConvParams& p, const X6Geo& geo, c
     constexpr bool TSEL = KS == 3 && (X6_TRACE == 3 ? STEM : (S == X6_TRACE && !STEM));      // (-DX6_TRACE=3: the fused stem)
     const bool ton = TSEL && bid < 64 && tid == 0;
     const bool wgon = TSEL && bid < 1024 && tid == 0;
-    if (wgon) {
-        g_x6_wg[bid * 4] = __builtin_amdgcn_s_memrealtime();
-        g_x6_wg[bid * 4 + 3] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
+    if (wgon) {         // loop entry: the prologue is complete (nothing pending), the first step's barrier comes next
+        g_x6_wg[bid * 8] = tr_rt0;
+        g_x6_wg[bid * 8 + 3] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
+        g_x6_wg[bid * 8 + 4] = tr_c0;
+        g_x6_wg[bid * 8 + 5] = __builtin_amdgcn_s_memtime();
+        g_x6_wg[bid * 8 + 6] = __builtin_amdgcn_s_memrealtime();
     }
 #define X6_TR(EV) if (ton && tstep < 32) g_x6_trace[(bid * 32 + tstep) * 8 + (EV)] = __builtin_amdgcn_s_memtime();
 #else
@@ -789,7 +842,11 @@ __device__ __forceinline__ void x6_body(const ConvParams& p, const X6Geo& geo, c
         ++tstep;
 #endif
 #ifdef X6_TRACE
-        if (wgon && !nxt.ok) { g_x6_wg[bid * 4 + 1] = __builtin_amdgcn_s_memrealtime(); g_x6_wg[bid * 4 + 2] = tstep; }
+        if (wgon && !nxt.ok) {
+            g_x6_wg[bid * 8 + 1] = __builtin_amdgcn_s_memrealtime();
+            g_x6_wg[bid * 8 + 2] = tstep;
+            g_x6_wg[bid * 8 + 7] = __builtin_amdgcn_s_memtime();
+        }
 #endif
         if constexpr (STEM) raw_commit(sidx & 1);       // crop of step s+2 (this buffer's readers were step s-1's staging)
         ++sidx;

@@ -1,6 +1,9 @@
 """Phase trace of conv_x6_kernel (debug build: ESA_HIPCC_FLAGS=-DX6_TRACE=1 python esa-pose-estimation_amd/build.py --force).
 Runs one 3x3 stride-1 convolution and prints, per traced workgroup, the cycles between the stamps of every step:
-barrier wait | phase-0 preamble (decode, tile loads) | phase 0 | phase 1 (+ reloads) | phase 2 | tail."""
+barrier wait | phase-0 preamble (decode, tile loads) | phase 0 | phase 1 (+ reloads) | phase 2 | tail.
+Its last line is the start-up summary of the traced form: prologue cycles (kernel entry to loop entry), cycles per step and
+workgroup lifetime, medians over the traced workgroups (compare a build with -DX6_SERIAL_PROLOGUE=1).
+usage: trace_x6.py [stem | N CIN COUT H W [STRIDE]]"""
 import ctypes as C
 import os
 import sys
@@ -16,6 +19,7 @@ if STEM:
     sys.argv = sys.argv[:1]
 n, cin, cout, h, w = [int(v) for v in (sys.argv[1:6] if len(sys.argv) > 5 else (128, 64, 64, 64, 64))]
 stride = int(sys.argv[6]) if len(sys.argv) > 6 else 1        # build with -DX6_TRACE=<stride>
+form = "stem" if STEM else f"{n} x {cin}->{cout} {h}x{w} 3x3 stride {stride}"
 lib = _lib.lib()
 raw = C.CDLL(_lib.LIB_PATH) if hasattr(_lib, "LIB_PATH") else lib
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -57,11 +61,11 @@ for wg in (0, 1, 7, 33):
         gap = int(t[wg, s + 1, 0] - t[wg, s, 6]) if s + 1 < 32 and t[wg, s + 1, 0] else 0
         print(f"  step {s:2d}: " + "  ".join(f"{nm} {v:6d}" for nm, v in zip(names, d)) + f"  next {gap:5d}  total {int(t[wg, s, 6] - t[wg, s, 0]):6d}")
 
-wg = np.zeros(1024 * 4, np.uint64)
+wg = np.zeros(1024 * 8, np.uint64)
 fn2 = raw.esa_debug_x6_wg
 fn2.argtypes = [C.c_void_p]
 assert fn2(wg.ctypes.data_as(C.c_void_p)) == 0
-wg = wg.reshape(1024, 4).astype(np.int64)
+wg = wg.reshape(1024, 8).astype(np.int64)
 live = wg[:, 1] > 0
 G = int(live.sum())
 t0 = wg[live, 0].min()
@@ -93,3 +97,14 @@ for b in (0, 1, 7, 33):
     last = max(s_ for s_ in range(32) if t[b, s_, 6])
     loop = (int(t[b, last, 7]) - int(t[b, 0, 7])) * 0.01
     print(f"workgroup {b}: prologue {pro:.1f} us, steps 0..{last - 1} {loop:.1f} us, whole {d[b]:.1f} us")
+
+# start-up summary: shader-clock cycles from kernel entry to loop entry (every load of the start complete), per step, per life
+pro_c = wg[:G, 5] - wg[:G, 4]
+life_c = wg[:G, 7] - wg[:G, 4]
+nst = np.maximum(wg[:G, 2], 1)
+step_c = (wg[:G, 7] - wg[:G, 5]) / nst
+ghz = np.median(life_c / np.maximum(d * 1e3, 1e-9))
+print(f"startup {form}: {G} workgroups, steps {int(nst.min())}..{int(nst.max())}, shader clock {ghz:.2f} GHz; "
+      f"prologue cycles median {np.median(pro_c):.0f} (p10 {np.percentile(pro_c, 10):.0f}, p90 {np.percentile(pro_c, 90):.0f}); "
+      f"cycles per step median {np.median(step_c):.0f}; lifetime cycles median {np.median(life_c):.0f} = {np.median(d):.2f} us; "
+      f"launch {en.max():.1f} us")
