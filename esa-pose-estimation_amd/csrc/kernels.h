@@ -11,7 +11,8 @@ namespace esa {
 enum { FMT_SB = 0, FMT_BF = 1, FMT_F32 = 2, FMT_HF = 3 };
 inline bool fmt_half(int fmt) { return fmt == FMT_BF || fmt == FMT_HF; }       // 2 bytes per channel, channels padded to 64
 
-// thread-local error text behind esahrnet_last_error() (plan.hip); returns 1 so that `return set_error(...)` reads well
+// thread-local error text behind esahrnet_last_error() (plan.hip; abi_decode.hip and op_abi.hip report through it); returns 1 so
+// that `return set_error(...)` reads well
 int set_error(const char* fmt, ...);
 
 // ---- implicit-GEMM convolution on MFMA (conv_mfma.hip) -------------------------------------

@@ -1,5 +1,6 @@
 // plan.hip — host runtime behind the C-ABI (include/esahrnet.h): stage table -> static plan
-// (list of fused kernels over SB tensors), weight packing, workspace planning, forward.
+// (list of fused kernels over SB tensors), weight packing, workspace planning, forward.  Every entry that takes a handle is
+// here; the ones that take none are in abi_decode.hip and op_abi.hip (the stand-alone operator entries, esahrnet_op_*).
 //
 // Reference being replaced: models/seg_hrnet.py:260-423 (module construction) and :425-473
 // (forward).  The plan is NOT a transcription of the module tree:
@@ -26,6 +27,7 @@
 
 #include "../../include/esahrnet.h"
 #include "devstate.h"
+#include "host_util.h"
 #include "kernels.h"
 
 namespace esa {
@@ -50,15 +52,9 @@ int fail(const char* fmt, ...) {
     return 1;
 }
 
-#define HIP_OK(expr)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess) return fail("%s: %s", #expr, hipGetErrorString(e_));     \
-    } while (0)
-
-inline int pad32(int c) { return (c + 31) & ~31; }
-constexpr int STEM_POOL_SLABS_MAX = 1024;   // pooled partials of the raw stem tensor: slabs reserved per image
-inline int pad64(int c) { return (c + 63) & ~63; }
+using esa::pad32;
+using esa::pad64;
+using esa::upload;
 
 struct ConvSpec {               // one Conv2d of the reference module tree
     std::string name, bn;
@@ -177,8 +173,8 @@ struct PlanOptions {
     bool final_mfma;            // seg_hrnet / seg_hrnet2: output layer on the matrix cores (final_mfma_kernel)
 };
 
-PlanOptions plan_options(const esahrnet_cfg& g) {
-    auto on = [](const char* name) { const char* e = getenv(name); return e && e[0] && strcmp(e, "0") != 0; };
+PlanOptions plan_options(const esahrnet_cfg& g, const esa::Format& format) {
+    const auto on = esa::env_on;
     PlanOptions o;
     o.unfused = on("ESAHRNET_UNFUSED"); o.head_v1 = on("ESAHRNET_HEAD_V1"); o.final_valu = on("ESAHRNET_FINAL_VALU");
     o.no_multihead = on("ESAHRNET_NO_MULTIHEAD"); o.no_jobs = on("ESAHRNET_NO_JOBS"); o.no_bblock = on("ESAHRNET_NO_BBLOCK");
@@ -190,7 +186,7 @@ PlanOptions plan_options(const esahrnet_cfg& g) {
     o.x6_reload_weights = on("ESAHRNET_X6_RELOAD_WEIGHTS");     // (changes no op: the same launches, the same names)
     const char* streams = getenv("ESAHRNET_STREAMS");
     o.nlanes = streams && atoi(streams) > 1 ? 4 : 1;
-    o.fmt = g.precision == 1 ? esa::FMT_BF : g.precision == 2 ? esa::FMT_F32 : g.precision == 3 ? esa::FMT_HF : esa::FMT_SB;
+    o.fmt = format.fmt;
     const bool sb = o.fmt == esa::FMT_SB, v0 = g.variant == 0;
     // the fused stem kernels: stem_fused serves every (cin, stem width) in the split format, stem_x6_kernel one; none in bf16
     const bool x6_stem = esa::stem_fused_x6_supported(g.cin, pad32(g.stem_width), pad32(g.stem_width)) && g.stem_width == 64;
@@ -222,6 +218,27 @@ int esa::set_error(const char* fmt, ...) {
     return 1;
 }
 
+// May these convolutions of one format, kernel size and stride run as ONE merged launch?  A stride-1 3x3 of the other
+// formats must be a stream-kernel launch on its own too (conv_is_stream_s1): the kernel serving a layer never depends
+// on the grouping.  The rule of job_on_for and of esahrnet_op_conv_group.
+bool esa::conv_group_mergeable(int fmt, const esa::ConvParams* ps, int n, int k, int stride) {
+    if (fmt == esa::FMT_F32) return esa::conv_x6_jobs_supported(ps, n, k, stride);
+    if (k == 1) return esa::conv1x1_jobs_supported(ps, n);
+    if (stride == 1)
+        for (int j = 0; j < n; ++j)
+            if (!esa::conv_is_stream_s1(ps[j])) return false;
+    return esa::conv_jobs_supported(ps, n, stride);
+}
+
+// name of the kernel that merged launch runs, as rocprofv3 prints it (op_desc_get, esahrnet_op_conv_group)
+void esa::conv_group_kernel_name(char* out, size_t cap, int fmt, const esa::ConvParams* ps, int n, int k, int stride) {
+    if (fmt == esa::FMT_F32 && k == 1 && esa::conv1x1_x6_jobs_supported(ps, n)) snprintf(out, cap, "conv1x1_x6_jobs_kernel");
+    else if (fmt == esa::FMT_F32) snprintf(out, cap, "conv_x6_jobs_kernel<%d, %d>", k, stride);
+    else if (k == 1) snprintf(out, cap, "conv1x1_jobs_kernel");
+    else snprintf(out, cap, "conv_s2c32_jobs_kernel<%d, %d, %s>", stride, stride == 1 ? 8 : 4,
+                  fmt == esa::FMT_HF ? "fp16" : esa::fmt_half(fmt) ? "true" : "false");
+}
+
 struct esahrnet_ctx {
     esahrnet_cfg cfg;
     int device;
@@ -241,25 +258,14 @@ struct esahrnet_ctx {
     bool committed = false;
     bool keep = false;
     PlanOptions opt;
-    // half-width format: the tensors are single bf16 (sb.h "BF") or single fp16 ("HF"), 2 bytes per channel, channels padded
-    // to 64; hf(): the element type is fp16
-    bool h16() const { return esa::fmt_half(opt.fmt); }
-    bool hf() const { return opt.fmt == esa::FMT_HF; }
-    bool x6() const { return opt.fmt == esa::FMT_F32; }
-    int padc(int ch) const { return h16() ? pad64(ch) : pad32(ch); }
-    int eb() const { return h16() ? 2 : 4; }     // bytes per stored channel
-    size_t wbytes(int coutp, int cinp, int k) const {
-        return h16() ? esa::packed_weight_bytes_bf(coutp, cinp, k) : x6() ? esa::packed_weight_bytes_x6(coutp, cinp, k)
-                                                                         : esa::packed_weight_bytes(coutp, cinp, k);
-    }
-    // w [cout][cin][k][k] packed for the plan's format (wbytes(coutp, cinp, k) bytes)
-    std::vector<char> pack(const float* w, int cout, int cin, int k, int coutp, int cinp) const {
-        std::vector<char> p(wbytes(coutp, cinp, k), 0);
-        if (h16()) esa::pack_conv_weights_bf(w, cout, cin, k, coutp, cinp, p.data(), hf());
-        else if (x6()) esa::pack_conv_weights_x6(w, cout, cin, k, coutp, cinp, p.data());
-        else esa::pack_conv_weights(w, cout, cin, k, coutp, cinp, p.data());
-        return p;
-    }
+    esa::Format format;         // the format of cfg.precision (host_util.h; opt.fmt is its code): what the members below answer from
+    bool h16() const { return format.half; }
+    bool hf() const { return format.hf; }
+    bool x6() const { return format.x6; }
+    int padc(int ch) const { return format.pad(ch); }
+    int eb() const { return format.eb; }
+    size_t wbytes(int coutp, int cinp, int k) const { return format.wbytes(coutp, cinp, k); }
+    std::vector<char> pack(const float* w, int cout, int cin, int k, int coutp, int cinp) const { return format.pack(w, cout, cin, k, coutp, cinp); }
     int head2_op = -1;          // index of the OP_HEAD2 op, -1 if the plan has none
     // wave executor (schedule_waves): the launches of a wave that do not depend on each other run on up to four lanes
     // (the caller's stream + three side streams), fork/join through the caller's stream at every wave boundary (opt.nlanes)
@@ -374,14 +380,13 @@ struct Builder {
     }
     // CBAM (seg_hrnet3.py:32-61, 90-91): y[:, c0:c0+C] = [relu]( sa(ca*x) * (ca*x) [+ res] ); prefix p
     // names the owner of .ca / .sa ("" = the network's own).  Returns nothing: writes into `y`.
-    static constexpr int POOL_SLABS = 64;
     void cbam(const std::string& p, int x, int C, int res, bool relu, int y, int y_c0) {
         const std::string q = p.empty() ? "" : p + ".";
         const int cr = C / 16;
         const int a0 = aux(q + "ca.fc.0.weight", cr, C, 1, 1), a1 = aux(q + "ca.fc.2.weight", C, cr, 1, 1);
         const int a2 = aux(q + "sa.conv1.weight", 1, 2, 7, 7);
         const int level = c.tensors[x].level, Cp = c.tensors[x].Cp;
-        const int partial = flat_tensor(POOL_SLABS * Cp * 2), cav = flat_tensor(Cp);
+        const int partial = flat_tensor(esa::POOL_SLABS * Cp * 2), cav = flat_tensor(Cp);
         Tensor mt; mt.C = 2; mt.Cp = 2; mt.level = level; mt.f32 = true;       // (f32 [N][H][W][2] in every format)
         c.tensors.push_back(mt);
         const int maps = (int)c.tensors.size() - 1;
@@ -855,7 +860,7 @@ int build_plan_ops(esahrnet_ctx& c) {
                 if (so.kind == OP_STEMRAW) {
                     const int partial = c.ops[first_cbam_op].out;
                     so.out2 = partial;
-                    c.tensors[partial].flat = STEM_POOL_SLABS_MAX * c.tensors[stem_raw].Cp * 2;
+                    c.tensors[partial].flat = esa::STEM_POOL_SLABS_MAX * c.tensors[stem_raw].Cp * 2;
                     c.stemraw_partial = partial;
                 }
         { Op o; o.kind = OP_RESAMPLE; o.in = h3; o.out = cat2; o.terms[0] = cat2; o.c0 = sw; o.nchan = K; o.align = 1; B.push(o); }
@@ -1184,27 +1189,6 @@ esa::ConvParams conv_params_of(const esahrnet_ctx& c, const Op& o, const ShapePl
     return p;
 }
 
-// May these convolutions of one format, kernel size and stride run as ONE merged launch?  A stride-1 3x3 of the other
-// formats must be a stream-kernel launch on its own too (conv_is_stream_s1): the kernel serving a layer never depends
-// on the grouping.  The rule of job_on_for and of esahrnet_op_conv_group.
-bool conv_group_mergeable(int fmt, const esa::ConvParams* ps, int n, int k, int stride) {
-    if (fmt == esa::FMT_F32) return esa::conv_x6_jobs_supported(ps, n, k, stride);
-    if (k == 1) return esa::conv1x1_jobs_supported(ps, n);
-    if (stride == 1)
-        for (int j = 0; j < n; ++j)
-            if (!esa::conv_is_stream_s1(ps[j])) return false;
-    return esa::conv_jobs_supported(ps, n, stride);
-}
-
-// name of the kernel that merged launch runs, as rocprofv3 prints it (op_desc_get, esahrnet_op_conv_group)
-void conv_group_kernel_name(char* out, size_t cap, int fmt, const esa::ConvParams* ps, int n, int k, int stride) {
-    if (fmt == esa::FMT_F32 && k == 1 && esa::conv1x1_x6_jobs_supported(ps, n)) snprintf(out, cap, "conv1x1_x6_jobs_kernel");
-    else if (fmt == esa::FMT_F32) snprintf(out, cap, "conv_x6_jobs_kernel<%d, %d>", k, stride);
-    else if (k == 1) snprintf(out, cap, "conv1x1_jobs_kernel");
-    else snprintf(out, cap, "conv_s2c32_jobs_kernel<%d, %d, %s>", stride, stride == 1 ? 8 : 4,
-                  fmt == esa::FMT_HF ? "fp16" : esa::fmt_half(fmt) ? "true" : "false");
-}
-
 // is this job group evaluated as ONE launch at this shape?  Every member must be a stream-kernel launch of its own
 // there (the kernel serving a layer depends on the shape only, never on the grouping)
 bool job_on_for(const esahrnet_ctx& c, const JobGroup& g, const ShapePlan& sp) {
@@ -1217,7 +1201,7 @@ bool job_on_for(const esahrnet_ctx& c, const JobGroup& g, const ShapePlan& sp) {
         // fp32-grade mode: conv_x6_jobs_kernel serves every kernel size / stride of the module, but one per launch
         if (c.x6() ? sk.k != s0.k || sk.stride != s0.stride : s0.k != 1 && sk.stride != s0.stride) return false;
     }
-    return conv_group_mergeable(c.opt.fmt, ps, g.n, s0.k, s0.stride);
+    return esa::conv_group_mergeable(c.opt.fmt, ps, g.n, s0.k, s0.stride);
 }
 
 // The per-shape dispatch decisions: level sizes, the head generation, which multi-head and job groups run as one launch.
@@ -1244,7 +1228,7 @@ ShapePlan shape_decisions(const esahrnet_ctx& c, int n, int h, int w) {
 int stem_pools(const esahrnet_ctx& c, int height, int width) {
     if (c.stemraw_partial < 0) return 0;
     const int slabs = esa::stem_pool_slabs(c.cfg.cin, c.padc(c.cfg.stem_width), height, width);
-    return slabs <= STEM_POOL_SLABS_MAX ? slabs : 0;
+    return slabs <= esa::STEM_POOL_SLABS_MAX ? slabs : 0;
 }
 
 bool cbam_fused(const esahrnet_ctx& c, int Cp, int hh, int ww) {
@@ -1260,7 +1244,7 @@ esa::CbamJob cbam_job(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, c
     const Tensor& tx = c.tensors[o.kind == OP_MLP ? o.terms[0] : o.in];
     const int hh = sp.lh[tx.level], ww = sp.lw[tx.level];
     q.ap.N = sp.n; q.ap.H = hh; q.ap.W = ww; q.ap.Cp = tx.Cp; q.ap.C = o.nchan; q.ap.fmt = c.opt.fmt;
-    q.HW = hh * ww; q.P = std::min(Builder::POOL_SLABS, q.HW); q.Cr = o.nchan / 16;
+    q.HW = hh * ww; q.P = std::min(esa::POOL_SLABS, q.HW); q.Cr = o.nchan / 16;
     switch (o.kind) {
         case OP_POOL:
             if (o.out == c.stemraw_partial && stem_pools(c, sp.h, sp.w)) break;       // made by the stem kernel
@@ -1424,16 +1408,11 @@ void free_weights(esahrnet_ctx& c) {
     c.committed = false;
 }
 
-template <typename T>
-int upload(const std::vector<T>& host, void** dev) {
-    HIP_OK(hipMalloc(dev, host.size() * sizeof(T)));
-    HIP_OK(hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
+}  // namespace
 
 // conv1 of a stem: host f32 [cout][cin][3][3] -> the stem kernels' [coutp/8][cin][9][8] (stem.hip, stem_fused.hip), the channels
 // cout .. coutp-1 zero.  The one packing of that layout: esahrnet_commit and the stem test entries all come through here.
-std::vector<float> pack_stem_w(const float* w, int cout, int cin, int coutp) {
+std::vector<float> esa::pack_stem_w(const float* w, int cout, int cin, int coutp) {
     std::vector<float> out((size_t)coutp * cin * 9, 0.f);
     for (int co = 0; co < cout; ++co)
         for (int ci = 0; ci < cin; ++ci)
@@ -1442,7 +1421,7 @@ std::vector<float> pack_stem_w(const float* w, int cout, int cin, int coutp) {
     return out;
 }
 
-}  // namespace
+using esa::pack_stem_w;
 
 // ============================================ C ABI ============================================
 extern "C" {
@@ -1483,7 +1462,8 @@ int esahrnet_create(const esahrnet_cfg* cfg, int device, esahrnet_handle* out) {
     esahrnet_ctx* c = new esahrnet_ctx();
     c->cfg = *cfg;
     c->device = device;
-    c->opt = plan_options(*cfg);
+    c->format = esa::Format(cfg->precision);
+    c->opt = plan_options(*cfg, c->format);
     // fp16 tensors reach the output layer through the matrix-core kernel only (head.hip final_mfma_kernel<.., HF>)
     if (c->hf() && !c->opt.final_mfma) {
         delete c;
@@ -2291,7 +2271,7 @@ static int run_op(const esahrnet_ctx& c, const Op& o, const ShapePlan& sp, const
                     break;
                 }
                 char kernel[sizeof desc->kernel];
-                conv_group_kernel_name(kernel, sizeof kernel, c.opt.fmt, ps, g.n, s.k, s.stride);
+                esa::conv_group_kernel_name(kernel, sizeof kernel, c.opt.fmt, ps, g.n, s.k, s.stride);
                 std::string lab;
                 for (int k = 0; k < g.n; ++k) {
                     const Op& ok = c.ops[g.op[k]];
@@ -3147,568 +3127,6 @@ int esahrnet_tensor_stats(const void* t_dev, int fmt, int n, int c, int cp, int 
     const esa::StatsJob job{t_dev, fmt, c, cp, h * w, 0};
     const int rc = esa::launch_stats(&job, 1, n, ws_dev, stats_dev, static_cast<hipStream_t>(stream));
     if (rc) return fail("tensor_stats: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
-}
-
-// ---- stand-alone operators on f32 NCHW tensors (tests) ---------------------------------------
-int esahrnet_op_conv(const void* x_dev, int n, int cin, int height, int width, const float* w,
-                     const float* b, int cout, int k, int stride, int relu, const void* res_dev,
-                     void* y_dev, esahrnet_stream stream_) {
-    return esahrnet_op_conv_ex(x_dev, n, cin, height, width, w, b, cout, k, stride, relu, res_dev, y_dev, 0, stream_);
-}
-
-int esahrnet_op_conv_ex(const void* x_dev, int n, int cin, int height, int width, const float* w,
-                        const float* b, int cout, int k, int stride, int relu, const void* res_dev,
-                        void* y_dev, int precision, esahrnet_stream stream_) {
-    if (!x_dev || !w || !b || !y_dev) return fail("op_conv: null argument");
-    if (precision < 0 || precision > 3) return fail("op_conv: precision %d", precision);
-    const bool hf = precision == 3, bf = precision == 1 || hf, x6 = precision == 2;       // bf: half-width format (bf16 or fp16)
-    const int fmt = hf ? esa::FMT_HF : bf ? esa::FMT_BF : x6 ? esa::FMT_F32 : esa::FMT_SB;
-    const int eb = bf ? 2 : 4;
-    if (!((k == 1 && stride == 1) || (k == 3 && (stride == 1 || stride == 2)))) return fail("op_conv: k=%d stride=%d unsupported", k, stride);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int cinp = bf ? pad64(cin) : pad32(cin), coutp = bf ? pad64(cout) : pad32(cout);
-    const int oh = stride == 2 ? (height + 1) / 2 : height, ow = stride == 2 ? (width + 1) / 2 : width;
-    std::vector<char> packed(bf ? esa::packed_weight_bytes_bf(coutp, cinp, k) : x6 ? esa::packed_weight_bytes_x6(coutp, cinp, k)
-                                                                                    : esa::packed_weight_bytes(coutp, cinp, k), 0);
-    if (bf) esa::pack_conv_weights_bf(w, cout, cin, k, coutp, cinp, packed.data(), hf);
-    else if (x6) esa::pack_conv_weights_x6(w, cout, cin, k, coutp, cinp, packed.data());
-    else esa::pack_conv_weights(w, cout, cin, k, coutp, cinp, packed.data());
-    std::vector<float> bias(coutp, 0.f);
-    std::copy(b, b + cout, bias.begin());
-    void *dw = nullptr, *db = nullptr, *xs = nullptr, *ys = nullptr, *rs = nullptr;
-    int rc = 0;
-    auto cleanup = [&]() { for (void* p : {dw, db, xs, ys, rs}) if (p) (void)hipFree(p); };
-    if (upload(packed, &dw) || upload(bias, &db)) { cleanup(); return 1; }
-    const size_t xb = (size_t)n * height * width * cinp * eb, yb = (size_t)n * oh * ow * coutp * eb;
-    if (hipMalloc(&xs, xb) != hipSuccess || hipMalloc(&ys, yb) != hipSuccess ||
-        (res_dev && hipMalloc(&rs, yb) != hipSuccess)) { cleanup(); return fail("op_conv: hipMalloc failed"); }
-    rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(x_dev), n, cin, height, width, static_cast<char*>(xs), cinp, stream);
-    if (!rc && res_dev) rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(res_dev), n, cout, oh, ow, static_cast<char*>(rs), coutp, stream);
-    if (!rc) {
-        esa::ConvParams p{};
-        p.x = static_cast<const char*>(xs); p.y = static_cast<char*>(ys); p.res = static_cast<const char*>(rs);
-        p.w = static_cast<const uint4*>(dw); p.bias = static_cast<const float*>(db);
-        p.N = n; p.H = height; p.W = width; p.OH = oh; p.OW = ow; p.Cinp = cinp; p.Coutp = coutp; p.relu = relu;
-        p.fmt = fmt;
-        const char* rw = getenv("ESAHRNET_X6_RELOAD_WEIGHTS");       // (no handle here: the call is its own create)
-        p.x6_reload = rw && rw[0] && strcmp(rw, "0") != 0;
-        rc = esa::launch_conv(p, k, stride, stream);
-    }
-    if (!rc) rc = esa::launch_fmt_to_nchw(fmt, static_cast<const char*>(ys), n, cout, oh, ow, coutp, static_cast<float*>(y_dev), stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    cleanup();
-    if (rc) return fail("op_conv: launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (se != hipSuccess) return fail("op_conv: %s", hipGetErrorString(se));
-    return 0;
-}
-
-int esahrnet_op_fuse(const void* const* xs_dev, const int* hs, const int* ws, int nterms, int n, int c,
-                     int height, int width, int relu, void* y_dev, esahrnet_stream stream_) {
-    return esahrnet_op_fuse_ex(xs_dev, hs, ws, nterms, n, c, height, width, relu, y_dev, 0, stream_);
-}
-
-int esahrnet_op_fuse_ex(const void* const* xs_dev, const int* hs, const int* ws, int nterms, int n, int c,
-                        int height, int width, int relu, void* y_dev, int precision, esahrnet_stream stream_) {
-    if (!xs_dev || !hs || !ws || !y_dev || nterms < 1 || nterms > 4) return fail("op_fuse: bad argument");
-    if (precision < 0 || precision > 3) return fail("op_fuse: precision %d", precision);
-    const bool bf = precision == 1 || precision == 3;      // half-width format (bf16 or fp16)
-    const int fmt = precision == 3 ? esa::FMT_HF : bf ? esa::FMT_BF : precision == 2 ? esa::FMT_F32 : esa::FMT_SB;
-    const int eb = bf ? 2 : 4;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int cp = bf ? pad64(c) : pad32(c);
-    void* bufs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    auto cleanup = [&]() { for (void* p : bufs) if (p) (void)hipFree(p); };
-    int rc = 0;
-    esa::FuseParams p{};
-    p.nterms = nterms; p.N = n; p.H = height; p.W = width; p.Cp = cp; p.relu = relu; p.fmt = fmt;
-    for (int i = 0; i < nterms && !rc; ++i) {
-        if (hipMalloc(&bufs[i], (size_t)n * hs[i] * ws[i] * cp * eb) != hipSuccess) { cleanup(); return fail("op_fuse: hipMalloc failed"); }
-        rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(xs_dev[i]), n, c, hs[i], ws[i], static_cast<char*>(bufs[i]), cp, stream);
-        p.x[i] = static_cast<const char*>(bufs[i]); p.h[i] = hs[i]; p.w[i] = ws[i];
-    }
-    if (!rc && hipMalloc(&bufs[4], (size_t)n * height * width * cp * eb) != hipSuccess) { cleanup(); return fail("op_fuse: hipMalloc failed"); }
-    p.y = static_cast<char*>(bufs[4]);
-    if (!rc) rc = esa::launch_fuse(p, stream);
-    if (!rc) rc = esa::launch_fmt_to_nchw(fmt, p.y, n, c, height, width, cp, static_cast<float*>(y_dev), stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    cleanup();
-    if (rc) return fail("op_fuse: launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (se != hipSuccess) return fail("op_fuse: %s", hipGetErrorString(se));
-    return 0;
-}
-
-int esahrnet_op_cbam(const void* x_dev, const void* res_dev, int n, int c, int height, int width, const float* w_fc0,
-                     const float* w_fc2, const float* w_sa, int relu, void* y_dev, int cy, int c0, int fused, int precision,
-                     esahrnet_stream stream_) {
-    return esahrnet_op_cbam_steps(x_dev, res_dev, n, c, height, width, w_fc0, w_fc2, w_sa, relu, y_dev, cy, c0, fused, precision,
-                                  0, nullptr, nullptr, nullptr, stream_);
-}
-
-int esahrnet_op_cbam_steps(const void* x_dev, const void* res_dev, int n, int c, int height, int width, const float* w_fc0,
-                           const float* w_fc2, const float* w_sa, int relu, void* y_dev, int cy, int c0, int fused, int precision,
-                           int slabs, void* partial_out, void* ca_out, void* maps_out, esahrnet_stream stream_) {
-    if (!x_dev || !w_fc0 || !w_fc2 || !w_sa || !y_dev || n <= 0 || height <= 0 || width <= 0) return fail("op_cbam: bad argument");
-    if (precision < 0 || precision > 2) return fail("op_cbam: precision %d", precision);
-    if (c < 16 || (c & 7)) return fail("op_cbam: c=%d (a multiple of 8, at least 16: ChannelAttention's ratio)", c);
-    const bool bf = precision == 1;
-    const int fmt = bf ? esa::FMT_BF : precision == 2 ? esa::FMT_F32 : esa::FMT_SB;
-    const int eb = bf ? 2 : 4;
-    const int cp = bf ? pad64(c) : pad32(c), cyp = bf ? pad64(cy) : pad32(cy);
-    if (cp > 512) return fail("op_cbam: c=%d is %d channels padded, ca_mlp serves at most 512", c, cp);
-    if (c0 < 0 || (c0 & 7) || c0 + cp > cyp) return fail("op_cbam: slice [%d, %d) outside the %d channels of y", c0, c0 + cp, cyp);
-    if (fused && !esa::cbam_spatial_supported(cp)) return fail("op_cbam: cbam_spatial does not serve %d channels", cp);
-    if (fused && maps_out) return fail("op_cbam: maps_out with fused = 1 (cbam_spatial keeps the maps in LDS)");
-    if ((long long)height * width > 0x7fffffffLL / n) return fail("op_cbam: %d x %d x %d pixels", n, height, width);
-    const int cr = c / 16, hw = height * width;
-    if (slabs < 0 || slabs > std::min(1024, hw)) return fail("op_cbam: slabs=%d (0, or 1 .. min(1024, %d pixels))", slabs, hw);
-    const int P = slabs ? slabs : std::min(Builder::POOL_SLABS, hw);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const std::vector<float> h0(w_fc0, w_fc0 + (size_t)cr * c), h2(w_fc2, w_fc2 + (size_t)c * cr), hs(w_sa, w_sa + 98);
-    void *xs = nullptr, *rs = nullptr, *ys = nullptr, *part = nullptr, *ca = nullptr, *maps = nullptr, *w0 = nullptr,
-         *w2 = nullptr, *wsa = nullptr;
-    auto cleanup = [&]() { for (void* p : {xs, rs, ys, part, ca, maps, w0, w2, wsa}) if (p) (void)hipFree(p); };
-    if (upload(h0, &w0) || upload(h2, &w2) || upload(hs, &wsa)) { cleanup(); return 1; }
-    const size_t npix = (size_t)n * hw;
-    const size_t part_bytes = (size_t)n * P * cp * 2 * sizeof(float), ca_bytes = (size_t)n * cp * sizeof(float),
-                 maps_bytes = npix * 2 * sizeof(float);
-    if (hipMalloc(&xs, npix * cp * eb) != hipSuccess || (res_dev && hipMalloc(&rs, npix * cp * eb) != hipSuccess) ||
-        hipMalloc(&ys, npix * cyp * eb) != hipSuccess || hipMalloc(&part, part_bytes) != hipSuccess ||
-        hipMalloc(&ca, ca_bytes) != hipSuccess || hipMalloc(&maps, maps_bytes) != hipSuccess) {
-        cleanup();
-        return fail("op_cbam: hipMalloc failed");
-    }
-    int rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(x_dev), n, c, height, width, static_cast<char*>(xs), cp, stream);
-    if (!rc && res_dev) rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(res_dev), n, c, height, width, static_cast<char*>(rs), cp, stream);
-    if (!rc) rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(y_dev), n, cy, height, width, static_cast<char*>(ys), cyp, stream);
-    if (!rc) rc = esa::launch_pool_partial(static_cast<const char*>(xs), static_cast<float*>(part), n, hw, cp, P, stream, fmt);
-    if (!rc) rc = esa::launch_ca_mlp(static_cast<const float*>(part), static_cast<const float*>(w0), static_cast<const float*>(w2),
-                                     static_cast<float*>(ca), n, hw, c, cp, cr, P, stream);
-    esa::CbamApplyParams ap{};
-    ap.x = static_cast<const char*>(xs); ap.res = static_cast<const char*>(rs); ap.ca = static_cast<const float*>(ca);
-    ap.maps = static_cast<const float*>(maps); ap.w_sa = static_cast<const float*>(wsa); ap.y = static_cast<char*>(ys);
-    ap.N = n; ap.H = height; ap.W = width; ap.Cp = cp; ap.y_pix_bytes = cyp * eb; ap.y_c0 = c0; ap.relu = relu; ap.C = c; ap.fmt = fmt;
-    if (!rc && fused) rc = esa::launch_cbam_spatial(ap, stream);
-    if (!rc && !fused) rc = esa::launch_cbam_maps(ap.x, ap.ca, static_cast<float*>(maps), n, hw, c, cp, stream, fmt);
-    if (!rc && !fused) rc = esa::launch_cbam_apply(ap, stream);
-    if (!rc) rc = esa::launch_fmt_to_nchw(fmt, static_cast<const char*>(ys), n, cy, height, width, cyp, static_cast<float*>(y_dev), stream);
-    hipError_t ce = hipSuccess;         // the steps' own buffers, as the kernels left them
-    if (!rc && partial_out) ce = hipMemcpyAsync(partial_out, part, part_bytes, hipMemcpyDeviceToDevice, stream);
-    if (!rc && ce == hipSuccess && ca_out) ce = hipMemcpyAsync(ca_out, ca, ca_bytes, hipMemcpyDeviceToDevice, stream);
-    if (!rc && ce == hipSuccess && maps_out) ce = hipMemcpyAsync(maps_out, maps, maps_bytes, hipMemcpyDeviceToDevice, stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    cleanup();
-    if (rc) return fail("op_cbam: launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (ce != hipSuccess) return fail("op_cbam: copying a step's output: %s", hipGetErrorString(ce));
-    if (se != hipSuccess) return fail("op_cbam: %s", hipGetErrorString(se));
-    return 0;
-}
-
-int esahrnet_op_stem(const void* x_dev, int n, int height, int width, const float* w, const float* b, int relu, int pooled,
-                     int precision, void* y_dev, void* partial_out, int* slabs_out, esahrnet_stream stream_) {
-    if (!x_dev || !w || !b || !y_dev || n <= 0 || height <= 0 || width <= 0) return fail("op_stem: bad argument");
-    if (precision < 0 || precision > 2) return fail("op_stem: precision %d (0, 1 or 2)", precision);
-    if ((long long)height * width > 0x7fffffffLL / 64 / n) return fail("op_stem: %d x %d x %d pixels", n, height, width);
-    constexpr int cout = 64;            // padded alike in every format
-    const int slabs = pooled ? esa::stem_pool_slabs(1, cout, height, width) : 0;
-    if (pooled && (!partial_out || !slabs_out)) return fail("op_stem: pooled = 1 needs partial_out and slabs_out");
-    if (pooled && slabs <= 0) return fail("op_stem: launch_stem_pool does not serve %d x %d", height, width);
-    const bool bf = precision == 1;
-    const int fmt = bf ? esa::FMT_BF : precision == 2 ? esa::FMT_F32 : esa::FMT_SB;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const std::vector<float> wp = pack_stem_w(w, cout, 1, cout), bp(b, b + cout);      // [cout/8][1][9][8], esahrnet_commit's packing
-    void *dw = nullptr, *db = nullptr, *ys = nullptr, *part = nullptr;
-    auto cleanup = [&]() { for (void* p : {dw, db, ys, part}) if (p) (void)hipFree(p); };
-    if (upload(wp, &dw) || upload(bp, &db)) { cleanup(); return 1; }
-    const size_t part_bytes = (size_t)n * slabs * cout * 2 * sizeof(float);
-    if (hipMalloc(&ys, (size_t)n * height * width * cout * (bf ? 2 : 4)) != hipSuccess ||
-        (pooled && hipMalloc(&part, part_bytes) != hipSuccess)) {
-        cleanup();
-        return fail("op_stem: hipMalloc failed");
-    }
-    esa::StemParams p{static_cast<const float*>(x_dev), static_cast<char*>(ys), static_cast<const float*>(dw),
-                      static_cast<const float*>(db), n, height, width, 1, cout, relu ? 1 : 0, fmt};
-    int rc = pooled ? esa::launch_stem_pool(p, static_cast<float*>(part), stream) : esa::launch_stem(p, stream);
-    if (!rc) rc = esa::launch_fmt_to_nchw(fmt, static_cast<const char*>(ys), n, cout, height, width, cout, static_cast<float*>(y_dev), stream);
-    hipError_t ce = hipSuccess;
-    if (!rc && pooled) ce = hipMemcpyAsync(partial_out, part, part_bytes, hipMemcpyDeviceToDevice, stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    cleanup();
-    if (rc) return fail("op_stem: launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (ce != hipSuccess) return fail("op_stem: copying the partials: %s", hipGetErrorString(ce));
-    if (se != hipSuccess) return fail("op_stem: %s", hipGetErrorString(se));
-    if (pooled) *slabs_out = slabs;
-    return 0;
-}
-
-// the slice kernels' formats (precisions 0, 1, 2): format code, and a channel count padded as that format pads it
-static int slice_fmt(int precision) { return precision == 1 ? esa::FMT_BF : precision == 2 ? esa::FMT_F32 : esa::FMT_SB; }
-static int slice_pad(int precision, int c) { return precision == 1 ? pad64(c) : pad32(c); }
-
-int esahrnet_op_resample(const void* x_dev, int n, int c, int h, int w, void* y_dev, int cy, int c0, int height, int width,
-                         int align, int precision, esahrnet_stream stream_) {
-    if (!x_dev || !y_dev || n <= 0 || c <= 0 || cy <= 0 || h <= 0 || w <= 0 || height <= 0 || width <= 0) return fail("op_resample: bad argument");
-    if (precision < 0 || precision > 2) return fail("op_resample: precision %d (resample_slice serves 0, 1 and 2)", precision);
-    const int fmt = slice_fmt(precision), eb = precision == 1 ? 2 : 4, cp = slice_pad(precision, c), cyp = slice_pad(precision, cy);
-    const int cw = (c + 7) & ~7;        // the kernel writes whole 8-channel groups
-    if (c0 < 0 || (c0 & 7)) return fail("op_resample: c0=%d is not a multiple of 8", c0);
-    if (c0 + cw > cyp) return fail("op_resample: slice [%d, %d) outside the %d channels of y", c0, c0 + cw, cyp);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    void *xs = nullptr, *ys = nullptr;
-    auto cleanup = [&]() { for (void* p : {xs, ys}) if (p) (void)hipFree(p); };
-    if (hipMalloc(&xs, (size_t)n * h * w * cp * eb) != hipSuccess || hipMalloc(&ys, (size_t)n * height * width * cyp * eb) != hipSuccess) {
-        cleanup();
-        return fail("op_resample: hipMalloc failed");
-    }
-    int rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(x_dev), n, c, h, w, static_cast<char*>(xs), cp, stream);
-    if (!rc) rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(y_dev), n, cy, height, width, static_cast<char*>(ys), cyp, stream);
-    esa::ResampleParams p{};
-    p.x = static_cast<const char*>(xs); p.y = static_cast<char*>(ys); p.N = n; p.h = h; p.w = w; p.H = height; p.W = width;
-    p.C = c; p.Cp_src = cp; p.y_pix_bytes = cyp * eb; p.y_c0 = c0; p.align = align ? 1 : 0; p.fmt = fmt;
-    if (!rc) rc = esa::launch_resample_slice(p, stream);
-    if (!rc) rc = esa::launch_fmt_to_nchw(fmt, static_cast<const char*>(ys), n, cy, height, width, cyp, static_cast<float*>(y_dev), stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    cleanup();
-    if (rc) return fail("op_resample: launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (se != hipSuccess) return fail("op_resample: %s", hipGetErrorString(se));
-    return 0;
-}
-
-int esahrnet_op_zero_slice(void* y_dev, int n, int cy, int height, int width, int c0, int nchan, int precision,
-                           esahrnet_stream stream_) {
-    if (!y_dev || n <= 0 || cy <= 0 || height <= 0 || width <= 0) return fail("op_zero_slice: bad argument");
-    if (precision < 0 || precision > 2) return fail("op_zero_slice: precision %d (zero_slice serves 0, 1 and 2)", precision);
-    const int fmt = slice_fmt(precision), eb = precision == 1 ? 2 : 4, cyp = slice_pad(precision, cy);
-    if (c0 < 0 || (c0 & 7) || nchan <= 0 || (nchan & 7)) return fail("op_zero_slice: c0=%d, nchan=%d must be multiples of 8", c0, nchan);
-    if (nchan > cyp - c0) return fail("op_zero_slice: slice [%d, %d) outside the %d channels of y", c0, c0 + nchan, cyp);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    void* ys = nullptr;
-    const long long npix = (long long)n * height * width;
-    if (hipMalloc(&ys, (size_t)npix * cyp * eb) != hipSuccess) return fail("op_zero_slice: hipMalloc failed");
-    int rc = esa::launch_nchw_to_fmt(fmt, static_cast<const float*>(y_dev), n, cy, height, width, static_cast<char*>(ys), cyp, stream);
-    if (!rc) rc = esa::launch_zero_slice(static_cast<char*>(ys), npix, cyp * eb, c0, nchan, stream, fmt);
-    if (!rc) rc = esa::launch_fmt_to_nchw(fmt, static_cast<const char*>(ys), n, cy, height, width, cyp, static_cast<float*>(y_dev), stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    (void)hipFree(ys);
-    if (rc) return fail("op_zero_slice: launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (se != hipSuccess) return fail("op_zero_slice: %s", hipGetErrorString(se));
-    return 0;
-}
-
-// ---- every convolution launcher on its own (tests/test_gpu_conv.py) --------------------------------------------------
-// The format of a precision code: element bytes and the channel multiple its tensors are padded to.
-struct OpFmt {
-    int fmt, eb, cm;
-    bool half, hf, x6;
-    int pad(int c) const { return (c + cm - 1) / cm * cm; }
-};
-static bool op_fmt(int precision, OpFmt* f) {
-    if (precision < 0 || precision > 3) return false;
-    f->hf = precision == 3; f->half = precision == 1 || f->hf; f->x6 = precision == 2;
-    f->fmt = f->hf ? esa::FMT_HF : f->half ? esa::FMT_BF : f->x6 ? esa::FMT_F32 : esa::FMT_SB;
-    f->eb = f->half ? 2 : 4; f->cm = f->half ? 64 : 32;
-    return true;
-}
-static bool op_conv_dims_ok(int n, int cin, int cout, int h, int w, int k, int stride) {
-    if (n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return false;
-    if (!((k == 1 && stride == 1) || (k == 3 && (stride == 1 || stride == 2)))) return false;
-    return (long long)n * h * w * (long long)((std::max(cin, cout) + 63) & ~63) * 4 <= 0x7fffffffLL;      // (test tensors)
-}
-// ConvParams of a stand-alone convolution, as esahrnet_op_conv_ex builds them — shapes and flags only; `res` stands for
-// "there is a residual" until op_conv_device puts the device tensors in
-static esa::ConvParams op_conv_shape(const OpFmt& f, int n, int cin, int cout, int h, int w, int stride, int relu, const void* res) {
-    esa::ConvParams p{};
-    p.N = n; p.H = h; p.W = w; p.OH = stride == 2 ? (h + 1) / 2 : h; p.OW = stride == 2 ? (w + 1) / 2 : w;
-    p.Cinp = f.pad(cin); p.Coutp = f.pad(cout); p.relu = relu; p.fmt = f.fmt;
-    p.res = static_cast<const char*>(res);
-    const char* rw = getenv("ESAHRNET_X6_RELOAD_WEIGHTS");
-    p.x6_reload = rw && rw[0] && strcmp(rw, "0") != 0;
-    return p;
-}
-struct OpConvMem {
-    void *dw = nullptr, *db = nullptr, *xs = nullptr, *ys = nullptr, *rs = nullptr;
-    void release() { for (void** p : {&dw, &db, &xs, &ys, &rs}) if (*p) { (void)hipFree(*p); *p = nullptr; } }
-};
-static std::vector<char> op_pack(const OpFmt& f, const float* w, int cout, int cin, int k, int coutp, int cinp) {
-    std::vector<char> packed(f.half ? esa::packed_weight_bytes_bf(coutp, cinp, k) : f.x6 ? esa::packed_weight_bytes_x6(coutp, cinp, k)
-                                                                                         : esa::packed_weight_bytes(coutp, cinp, k), 0);
-    if (f.half) esa::pack_conv_weights_bf(w, cout, cin, k, coutp, cinp, packed.data(), f.hf);
-    else if (f.x6) esa::pack_conv_weights_x6(w, cout, cin, k, coutp, cinp, packed.data());
-    else esa::pack_conv_weights(w, cout, cin, k, coutp, cinp, packed.data());
-    return packed;
-}
-// weights packed and uploaded, x and res converted to the format, y allocated; p's pointers set.  Non-zero: an error is set.
-static int op_conv_device(const OpFmt& f, esa::ConvParams& p, int cin, int cout, int k, const float* w, const float* b,
-                          const void* x_dev, const void* res_dev, OpConvMem& m, hipStream_t stream) {
-    std::vector<float> bias(p.Coutp, 0.f);
-    std::copy(b, b + cout, bias.begin());
-    if (upload(op_pack(f, w, cout, cin, k, p.Coutp, p.Cinp), &m.dw) || upload(bias, &m.db)) return 1;
-    const size_t xb = (size_t)p.N * p.H * p.W * p.Cinp * f.eb, yb = (size_t)p.N * p.OH * p.OW * p.Coutp * f.eb;
-    if (hipMalloc(&m.xs, xb) != hipSuccess || hipMalloc(&m.ys, yb) != hipSuccess || (res_dev && hipMalloc(&m.rs, yb) != hipSuccess))
-        return fail("op_conv_group: hipMalloc failed");
-    int rc = esa::launch_nchw_to_fmt(f.fmt, static_cast<const float*>(x_dev), p.N, cin, p.H, p.W, static_cast<char*>(m.xs), p.Cinp, stream);
-    if (!rc && res_dev) rc = esa::launch_nchw_to_fmt(f.fmt, static_cast<const float*>(res_dev), p.N, cout, p.OH, p.OW, static_cast<char*>(m.rs), p.Coutp, stream);
-    if (rc) return fail("op_conv_group: layout conversion failed: %s", hipGetErrorString((hipError_t)rc));
-    p.x = static_cast<const char*>(m.xs); p.y = static_cast<char*>(m.ys); p.res = static_cast<const char*>(m.rs);
-    p.w = static_cast<const uint4*>(m.dw); p.bias = static_cast<const float*>(m.db);
-    return 0;
-}
-
-int esahrnet_op_conv_kernel(int n, int cin, int cout, int height, int width, int k, int stride, int has_res, int precision,
-                            char* out, size_t cap) {
-    OpFmt f;
-    if (!out || cap == 0) return fail("op_conv_kernel: null argument");
-    if (!op_fmt(precision, &f)) return fail("op_conv_kernel: precision %d", precision);
-    if (!op_conv_dims_ok(n, cin, cout, height, width, k, stride))
-        return fail("op_conv_kernel: n=%d cin=%d cout=%d %dx%d k=%d stride=%d unsupported", n, cin, cout, height, width, k, stride);
-    static const char some_residual = 0;
-    const esa::ConvParams p = op_conv_shape(f, n, cin, cout, height, width, stride, 0, has_res ? &some_residual : nullptr);
-    snprintf(out, cap, "%s", esa::conv_kernel_name(p, k, stride));
-    return 0;
-}
-
-int esahrnet_op_conv_group(int count, const void* const* xs_dev, const int* ns, const int* cins, const int* heights, const int* widths,
-                           const float* const* ws, const float* const* bs, const int* couts, int k, int stride, const int* relus,
-                           const void* const* res_dev, void* const* ys_dev, int precision, char* kernel_out, size_t kernel_cap,
-                           esahrnet_stream stream_) {
-    const char* who = "op_conv_group";
-    OpFmt f;
-    if (!xs_dev || !ns || !cins || !heights || !widths || !ws || !bs || !couts || !relus || !ys_dev) return fail("%s: null argument", who);
-    if (count < 1 || count > 6) return fail("%s: count=%d (1 .. 6)", who, count);
-    if (!op_fmt(precision, &f)) return fail("%s: precision %d", who, precision);
-    esa::ConvParams ps[6];
-    for (int j = 0; j < count; ++j) {
-        if (!xs_dev[j] || !ws[j] || !bs[j] || !ys_dev[j]) return fail("%s: null argument (member %d)", who, j);
-        if (!op_conv_dims_ok(ns[j], cins[j], couts[j], heights[j], widths[j], k, stride))
-            return fail("%s: member %d: n=%d cin=%d cout=%d %dx%d k=%d stride=%d unsupported", who, j, ns[j], cins[j], couts[j],
-                        heights[j], widths[j], k, stride);
-        ps[j] = op_conv_shape(f, ns[j], cins[j], couts[j], heights[j], widths[j], stride, relus[j], res_dev ? res_dev[j] : nullptr);
-    }
-    char kernel[64];
-    if (count == 1) {
-        snprintf(kernel, sizeof kernel, "%s", esa::conv_kernel_name(ps[0], k, stride));
-        if (!strcmp(kernel, "none")) return fail("%s: no kernel of precision %d serves this convolution", who, precision);
-    } else {
-        if (!conv_group_mergeable(f.fmt, ps, count, k, stride))
-            return fail("%s: these %d convolutions (k=%d, stride=%d, precision %d) have no merged launch", who, count, k, stride, precision);
-        conv_group_kernel_name(kernel, sizeof kernel, f.fmt, ps, count, k, stride);
-    }
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OpConvMem mem[6];
-    auto cleanup = [&]() { for (OpConvMem& m : mem) m.release(); };
-    for (int j = 0; j < count; ++j)
-        if (op_conv_device(f, ps[j], cins[j], couts[j], k, ws[j], bs[j], xs_dev[j], res_dev ? res_dev[j] : nullptr, mem[j], stream)) {
-            (void)hipStreamSynchronize(stream);
-            cleanup();
-            return 1;
-        }
-    int rc = count == 1 ? esa::launch_conv(ps[0], k, stride, stream)
-           : f.x6 ? esa::launch_conv_x6_jobs(ps, count, k, stride, stream)
-           : k == 1 ? esa::launch_conv1x1_jobs(ps, count, stream) : esa::launch_conv_jobs(ps, count, stride, stream);
-    for (int j = 0; j < count && !rc; ++j)      // all C' channels: the padding comes back too
-        rc = esa::launch_fmt_to_nchw(f.fmt, ps[j].y, ps[j].N, ps[j].Coutp, ps[j].OH, ps[j].OW, ps[j].Coutp, static_cast<float*>(ys_dev[j]), stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    cleanup();
-    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
-    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
-    if (kernel_out && kernel_cap) snprintf(kernel_out, kernel_cap, "%s", kernel);
-    return 0;
-}
-
-int esahrnet_op_conv_multi(const void* x_dev, int n, int cin, int height, int width, int nheads, const float* const* ws,
-                           const float* const* bs, const int* couts, const int* relus, void* const* ys_dev, esahrnet_stream stream_) {
-    const char* who = "op_conv_multi";
-    OpFmt f;
-    op_fmt(0, &f);
-    if (!x_dev || !ws || !bs || !couts || !relus || !ys_dev) return fail("%s: null argument", who);
-    if (nheads < 2 || nheads > 3) return fail("%s: nheads=%d (2 or 3)", who, nheads);
-    int total = 0;
-    for (int h = 0; h < nheads; ++h) {
-        if (!ws[h] || !bs[h] || !ys_dev[h]) return fail("%s: null argument (head %d)", who, h);
-        if (couts[h] <= 0 || (couts[h] & 31)) return fail("%s: head %d has %d couts (a positive multiple of 32)", who, h, couts[h]);
-        total += couts[h];
-    }
-    if (!op_conv_dims_ok(n, cin, total, height, width, 3, 2)) return fail("%s: n=%d cin=%d couts=%d %dx%d unsupported", who, n, cin, total, height, width);
-    esa::ConvParams p = op_conv_shape(f, n, cin, total, height, width, 2, 0, nullptr);
-    p.nheads = nheads;
-    std::vector<char> packed;
-    std::vector<float> bias;
-    for (int h = 0; h < nheads; ++h) {          // members' packed weights / biases back to back, as esahrnet_commit lays them
-        const std::vector<char> wh = op_pack(f, ws[h], couts[h], cin, 3, couts[h], p.Cinp);
-        packed.insert(packed.end(), wh.begin(), wh.end());
-        bias.insert(bias.end(), bs[h], bs[h] + couts[h]);
-        p.hb[h + 1] = p.hb[h] + couts[h];
-        p.hrelu[h] = relus[h] ? 1 : 0;
-    }
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    void *dw = nullptr, *db = nullptr, *xs = nullptr, *yh[3] = {nullptr, nullptr, nullptr};
-    auto cleanup = [&]() { for (void* q : {dw, db, xs, yh[0], yh[1], yh[2]}) if (q) (void)hipFree(q); };
-    if (upload(packed, &dw) || upload(bias, &db)) { cleanup(); return 1; }
-    bool ok = hipMalloc(&xs, (size_t)n * height * width * p.Cinp * 4) == hipSuccess;
-    for (int h = 0; h < nheads && ok; ++h) ok = hipMalloc(&yh[h], (size_t)n * p.OH * p.OW * couts[h] * 4) == hipSuccess;
-    if (!ok) { cleanup(); return fail("%s: hipMalloc failed", who); }
-    p.x = static_cast<const char*>(xs); p.w = static_cast<const uint4*>(dw); p.bias = static_cast<const float*>(db);
-    for (int h = 0; h < nheads; ++h) p.yh[h] = static_cast<char*>(yh[h]);
-    if (!esa::conv_s2c32_multi_supported(p)) { cleanup(); return fail("%s: launch_conv_s2c32_multi does not serve these heads", who); }
-    int rc = esa::launch_nchw_to_fmt(f.fmt, static_cast<const float*>(x_dev), n, cin, height, width, static_cast<char*>(xs), p.Cinp, stream);
-    if (!rc) rc = esa::launch_conv_s2c32_multi(p, stream);
-    for (int h = 0; h < nheads && !rc; ++h)
-        rc = esa::launch_fmt_to_nchw(f.fmt, p.yh[h], n, couts[h], p.OH, p.OW, couts[h], static_cast<float*>(ys_dev[h]), stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    cleanup();
-    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
-    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
-    return 0;
-}
-
-int esahrnet_op_block32(const void* x_dev, int n, int height, int width, const float* w1, const float* b1, const float* w2,
-                        const float* b2, void* y_dev, esahrnet_stream stream_) {
-    const char* who = "op_block32";
-    OpFmt f;
-    op_fmt(0, &f);
-    if (!x_dev || !w1 || !b1 || !w2 || !b2 || !y_dev) return fail("%s: null argument", who);
-    if (!op_conv_dims_ok(n, 32, 32, height, width, 3, 1)) return fail("%s: n=%d %dx%d unsupported", who, n, height, width);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    void *d1 = nullptr, *d2 = nullptr, *db1 = nullptr, *db2 = nullptr, *xs = nullptr, *ys = nullptr;
-    auto cleanup = [&]() { for (void* q : {d1, d2, db1, db2, xs, ys}) if (q) (void)hipFree(q); };
-    const std::vector<float> hb1(b1, b1 + 32), hb2(b2, b2 + 32);
-    if (upload(op_pack(f, w1, 32, 32, 3, 32, 32), &d1) || upload(op_pack(f, w2, 32, 32, 3, 32, 32), &d2) || upload(hb1, &db1) ||
-        upload(hb2, &db2)) { cleanup(); return 1; }
-    const size_t bytes = (size_t)n * height * width * 128;
-    if (hipMalloc(&xs, bytes) != hipSuccess || hipMalloc(&ys, bytes) != hipSuccess) { cleanup(); return fail("%s: hipMalloc failed", who); }
-    esa::BlockParams p{};
-    p.x = static_cast<const char*>(xs); p.y = static_cast<char*>(ys);
-    p.w1 = static_cast<const uint4*>(d1); p.w2 = static_cast<const uint4*>(d2);
-    p.bias1 = static_cast<const float*>(db1); p.bias2 = static_cast<const float*>(db2);
-    p.N = n; p.H = height; p.W = width;
-    int rc = esa::launch_nchw_to_fmt(f.fmt, static_cast<const float*>(x_dev), n, 32, height, width, static_cast<char*>(xs), 32, stream);
-    if (!rc) rc = esa::launch_bblock32(p, stream);
-    if (!rc) rc = esa::launch_fmt_to_nchw(f.fmt, p.y, n, 32, height, width, 32, static_cast<float*>(y_dev), stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    cleanup();
-    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
-    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
-    return 0;
-}
-
-int esahrnet_op_stem2(const void* x_dev, int n, int cin, int height, int width, const float* w1, const float* b1, int cmid,
-                      const float* w2, const float* b2, int cout, int precision, void* y_dev, esahrnet_stream stream_) {
-    const char* who = "op_stem2";
-    OpFmt f;
-    if (!x_dev || !w1 || !b1 || !w2 || !b2 || !y_dev) return fail("%s: null argument", who);
-    if (precision != 0 && precision != 2) return fail("%s: precision %d (0: stem_fused, 2: stem_x6_kernel)", who, precision);
-    op_fmt(precision, &f);
-    if (cin < 1 || cin > 4) return fail("%s: cin=%d (1 .. 4)", who, cin);
-    if (cmid <= 0 || (cmid & 31)) return fail("%s: cmid=%d (a positive multiple of 32)", who, cmid);
-    if (!op_conv_dims_ok(n, cmid, cout, height, width, 3, 2)) return fail("%s: n=%d cmid=%d cout=%d %dx%d unsupported", who, n, cmid, cout, height, width);
-    const int coutp = f.pad(cout), oh = (height + 1) / 2, ow = (width + 1) / 2;
-    if (f.x6 && !esa::stem_fused_x6_supported(cin, cmid, coutp)) return fail("%s: stem_x6_kernel does not serve cin=%d cmid=%d cout=%d", who, cin, cmid, cout);
-    std::vector<float> w1p, b1p(b1, b1 + cmid), b2p(coutp, 0.f);
-    std::copy(b2, b2 + cout, b2p.begin());
-    if (f.x6) {                                 // conv1 in stem_x6_kernel's layout (bias inside), as esahrnet_commit packs it
-        w1p.assign(2 * 4 * 10 * 8, 0.f);
-        esa::pack_stem_w1_x6(w1, b1, w1p.data());
-    } else {                                    // [cmid/8][cin][9][8]
-        w1p = pack_stem_w(w1, cmid, cin, cmid);
-    }
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    void *dw1 = nullptr, *db1 = nullptr, *dw2 = nullptr, *db2 = nullptr, *ys = nullptr;
-    auto cleanup = [&]() { for (void* q : {dw1, db1, dw2, db2, ys}) if (q) (void)hipFree(q); };
-    if (upload(w1p, &dw1) || upload(b1p, &db1) || upload(op_pack(f, w2, cout, cmid, 3, coutp, cmid), &dw2) || upload(b2p, &db2)) { cleanup(); return 1; }
-    if (hipMalloc(&ys, (size_t)n * oh * ow * coutp * 4) != hipSuccess) { cleanup(); return fail("%s: hipMalloc failed", who); }
-    esa::StemFusedParams p{};
-    p.x = static_cast<const float*>(x_dev); p.y = static_cast<char*>(ys);
-    p.w1 = static_cast<const float*>(dw1); p.bias1 = static_cast<const float*>(db1);
-    p.w2 = static_cast<const uint4*>(dw2); p.bias2 = static_cast<const float*>(db2);
-    p.N = n; p.H = height; p.W = width; p.OH = oh; p.OW = ow; p.cin = cin; p.Cmid = cmid; p.Coutp = coutp;
-    int rc = f.x6 ? esa::launch_stem_fused_x6(p, stream) : esa::launch_stem_fused(p, stream);
-    if (!rc) rc = esa::launch_fmt_to_nchw(f.fmt, p.y, n, coutp, oh, ow, coutp, static_cast<float*>(y_dev), stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    cleanup();
-    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
-    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
-    return 0;
-}
-
-// ---- the stem outside esahrnet_op_stem's one configuration, the layout conversions and the tile-maximum kernels on their own
-// (tests/test_gpu_layout.py) ---------------------------------------------------------------------------------------------------
-int esahrnet_op_stem_ex(const void* x_dev, int n, int cin, int height, int width, const float* w, const float* b, int cout,
-                        int relu, int precision, void* y_dev, esahrnet_stream stream_) {
-    const char* who = "op_stem_ex";
-    OpFmt f;
-    if (!x_dev || !w || !b || !y_dev) return fail("%s: null argument", who);
-    if (!op_fmt(precision, &f)) return fail("%s: precision %d (0 .. 3)", who, precision);
-    if (cin < 1 || cin > 4) return fail("%s: cin=%d (1 .. 4)", who, cin);
-    if (cout <= 0 || (cout & 31)) return fail("%s: cout=%d (a positive multiple of 32)", who, cout);
-    if (f.half && (cout & 63)) return fail("%s: cout=%d (the 16-bit formats hold blocks of 64 channels)", who, cout);
-    if (n <= 0 || height <= 0 || width <= 0 || (long long)n * height * width * cout * 4 > 0x7fffffffLL)
-        return fail("%s: n=%d %dx%d cout=%d unsupported", who, n, height, width, cout);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const std::vector<float> wp = pack_stem_w(w, cout, cin, cout), bp(b, b + cout);     // esahrnet_commit's packing of conv1
-    void *dw = nullptr, *db = nullptr, *ys = nullptr;
-    auto cleanup = [&]() { for (void* q : {dw, db, ys}) if (q) (void)hipFree(q); };
-    if (upload(wp, &dw) || upload(bp, &db)) { cleanup(); return 1; }
-    if (hipMalloc(&ys, (size_t)n * height * width * cout * f.eb) != hipSuccess) { cleanup(); return fail("%s: hipMalloc failed", who); }
-    esa::StemParams p{static_cast<const float*>(x_dev), static_cast<char*>(ys), static_cast<const float*>(dw),
-                      static_cast<const float*>(db), n, height, width, cin, cout, relu ? 1 : 0, f.fmt};
-    int rc = esa::launch_stem(p, stream);
-    if (!rc) rc = esa::launch_fmt_to_nchw(f.fmt, static_cast<const char*>(ys), n, cout, height, width, cout, static_cast<float*>(y_dev), stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    cleanup();
-    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
-    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
-    return 0;
-}
-
-int esahrnet_op_layout(int dir, const void* x_dev, int n, int c, int height, int width, int cp, int precision, void* raw_dev,
-                       void* y_dev, esahrnet_stream stream_) {
-    const char* who = "op_layout";
-    OpFmt f;
-    if (dir != 0 && dir != 1) return fail("%s: dir=%d (0: f32 NCHW -> raw -> f32 NCHW, 1: raw -> f32 NCHW)", who, dir);
-    if (!raw_dev || !y_dev || (dir == 0 && !x_dev)) return fail("%s: null argument", who);
-    if (!op_fmt(precision, &f)) return fail("%s: precision %d (0 .. 3)", who, precision);
-    if (n <= 0 || c <= 0 || height <= 0 || width <= 0) return fail("%s: n=%d c=%d %dx%d unsupported", who, n, c, height, width);
-    if (cp < c || (cp & 7)) return fail("%s: cp=%d (a multiple of 8, at least c=%d)", who, cp, c);
-    if ((long long)n * height * width * cp * 4 > 0x7fffffffLL) return fail("%s: n=%d cp=%d %dx%d unsupported", who, n, cp, height, width);
-    if ((reinterpret_cast<uintptr_t>(raw_dev) & 15) || (reinterpret_cast<uintptr_t>(y_dev) & 3) || (reinterpret_cast<uintptr_t>(x_dev) & 3))
-        return fail("%s: raw_dev must be 16-byte aligned, x_dev and y_dev 4-byte aligned", who);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc = 0;
-    if (dir == 0) rc = esa::launch_nchw_to_fmt(f.fmt, static_cast<const float*>(x_dev), n, c, height, width, static_cast<char*>(raw_dev), cp, stream);
-    if (!rc) rc = esa::launch_fmt_to_nchw(f.fmt, static_cast<const char*>(raw_dev), n, c, height, width, cp, static_cast<float*>(y_dev), stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
-    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
-    return 0;
-}
-
-int esahrnet_op_tile_max(const void* raw_dev, int n, int c, int height, int width, int cp, int precision, int store, void* y_dev,
-                         void* part_dev, int* ntiles_out, void* kp_dev, void* idx_dev, esahrnet_stream stream_) {
-    const char* who = "op_tile_max";
-    if (!raw_dev || !part_dev || !ntiles_out) return fail("%s: null argument", who);
-    if (precision != 0 && precision != 2) return fail("%s: precision %d (0: split-bf16, 2: f32)", who, precision);
-    if (store != 0 && store != 1) return fail("%s: store=%d (0 or 1)", who, store);
-    if (store && !y_dev) return fail("%s: store = 1 needs y_dev", who);
-    if (n <= 0 || height <= 0 || width <= 0) return fail("%s: n=%d %dx%d unsupported", who, n, height, width);
-    if (c < 1 || c > 32) return fail("%s: c=%d (1 .. 32)", who, c);
-    if (cp < c || (cp & 7)) return fail("%s: cp=%d (a multiple of 8, at least c=%d)", who, cp, c);
-    if ((long long)n * height * width * cp * 4 > 0x7fffffffLL) return fail("%s: n=%d cp=%d %dx%d unsupported", who, n, cp, height, width);
-    if ((reinterpret_cast<uintptr_t>(raw_dev) & 15) || (reinterpret_cast<uintptr_t>(part_dev) & 7) || (reinterpret_cast<uintptr_t>(y_dev) & 3) ||
-        (reinterpret_cast<uintptr_t>(kp_dev) & 3) || (reinterpret_cast<uintptr_t>(idx_dev) & 3))
-        return fail("%s: raw_dev must be 16-byte aligned, part_dev 8-byte, y_dev, kp_dev and idx_dev 4-byte", who);
-    const int fmt = precision == 2 ? esa::FMT_F32 : esa::FMT_SB, ntiles = esa::to_nchw_part_tiles(height, width);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const char* raw = static_cast<const char*>(raw_dev);
-    float2* part = static_cast<float2*>(part_dev);
-    int rc = store ? esa::launch_to_nchw_part(fmt, raw, n, c, height, width, cp, static_cast<float*>(y_dev), part, stream)
-                   : esa::launch_tile_max(fmt, raw, n, c, height, width, cp, part, stream);
-    if (!rc && kp_dev)
-        rc = esa::launch_keypoints_finish_nhwc(fmt, raw, n, c, height, width, cp, part, ntiles, static_cast<float*>(kp_dev),
-                                               static_cast<int*>(idx_dev), stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    if (rc) return fail("%s: launch failed: %s", who, hipGetErrorString((hipError_t)rc));
-    if (se != hipSuccess) return fail("%s: %s", who, hipGetErrorString(se));
-    *ntiles_out = ntiles;
     return 0;
 }
 

@@ -763,7 +763,8 @@ int esahrnet_forward_stats_h0(esahrnet_handle h, const void* x_dev, int n, int h
 int esahrnet_scale_exponents_from_stats(esahrnet_handle h, const void* records, int rows, int n_total, const void* h0_records,
                                         int headroom_bits, int32_t* exponents, int count);
 
-/* Stand-alone convolution on f32 NCHW device tensors through the same MFMA kernels:
+/* ---- stand-alone operator entries (esahrnet_op_conv .. esahrnet_op_tile_max; csrc/op_abi.hip): test use only, no handle ----
+ * Stand-alone convolution on f32 NCHW device tensors through the same MFMA kernels:
  * y = [relu]( conv_{k,stride,pad=(k-1)/2}(x; w) + b [+ res] ).  w,b are HOST pointers
  * (packed and uploaded on the spot; synchronous; test use only). */
 int esahrnet_op_conv(const void* x_dev, int n, int cin, int height, int width,

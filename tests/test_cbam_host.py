@@ -100,7 +100,7 @@ def test_reference_self_check(case):
 
 # ---------------------------------------------------------------------------------------------- geometry against the sources
 def test_slab_geometry_and_case_table():
-    plan, cbam, stem = _src("plan.hip"), _src("cbam.hip"), _src("stem.hip")
+    plan, cbam, stem = _src("host_util.h"), _src("cbam.hip"), _src("stem.hip")     # (host_util.h: what plan.hip and op_abi.hip share)
     pool_slabs = int(re.search(r"static constexpr int POOL_SLABS = (\d+);", plan).group(1))
     stem_px = int(re.search(r"constexpr int STEM_PX = (\d+);", stem).group(1))
     stem_max = int(re.search(r"constexpr int STEM_POOL_SLABS_MAX = (\d+);", plan).group(1))

@@ -326,7 +326,11 @@ def test_entries_are_declared_and_abi_stays():
         if fn.endswith(".py") and fn != "_lib.py":
             with open(os.path.join(pkg, fn)) as f:
                 assert not any(n in f.read() for n in names), fn
-    with open(os.path.join(pkg, "csrc", "plan.hip")) as f:
-        src = f.read()
-    assert src.count("pack_stem_w(") == 6                                     # one packing: its definition, esahrnet_commit (2), the three stem entries
-    assert src.count("* 9 + t) * 8 + (co & 7)]") == 1                          # and no copy of it written inline
+    src = {}
+    for fn in ("plan.hip", "op_abi.hip", "host_util.h"):
+        with open(os.path.join(pkg, "csrc", fn)) as f:
+            src[fn] = f.read()
+    # one packing: its definition and esahrnet_commit (2) in plan.hip, the three stem entries in op_abi.hip, the declaration they share
+    assert [src[fn].count("pack_stem_w(") for fn in src] == [3, 3, 1]
+    assert "std::vector<float> esa::pack_stem_w(" in src["plan.hip"] and src["host_util.h"].count("std::vector<float> pack_stem_w(") == 1
+    assert sum(s.count("* 9 + t) * 8 + (co & 7)]") for s in src.values()) == 1  # and no copy of it written inline
