@@ -76,6 +76,31 @@ class StatsRowDesc(C.Structure):
                 ("fmt", C.c_int32), ("scanned", C.c_int32)]
 
 
+# One record of the precision report (include/esahrnet.h: ESAHRNET_DIFF_FIELDS, held together by the header test as above)
+DIFF_RECORD_BYTES = 64
+DIFF_FIELDS = (("sum_abs_err", "f8"), ("sum_sq_err", "f8"), ("sum_sq_ref", "f8"), ("max_abs_err", "f4"), ("max_abs_ref", "f4"),
+               ("max_abs_test", "f4"), ("at", "u4"), ("n_compared", "u4"), ("n_nonfinite_test", "u4"), ("n_nonfinite_ref", "u4"),
+               ("n_class_differs", "u4"))
+DIFF_AT_NONE = 0xFFFFFFFF         # esahrnet_diff_record.at when nothing was compared
+
+
+class DiffRecord(C.Structure):
+    _fields_ = [(name, _STATS_CTYPES[t]) for name, t in DIFF_FIELDS] + [("reserved", C.c_uint32 * 2)]
+
+
+def diff_dtype():
+    """numpy dtype of a record: the fields of DIFF_FIELDS at their offsets, 64 bytes."""
+    import numpy as np
+    names = [name for name, _ in DIFF_FIELDS]
+    return np.dtype({"names": names, "formats": [t for _, t in DIFF_FIELDS],
+                     "offsets": [getattr(DiffRecord, name).offset for name in names], "itemsize": DIFF_RECORD_BYTES})
+
+
+class DiffRowDesc(C.Structure):
+    _fields_ = [("key", C.c_char * 96), ("ref_row", C.c_int32), ("c", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("fmt", C.c_int32), ("ref_fmt", C.c_int32), ("exponent", C.c_int32), ("compared", C.c_int32)]
+
+
 SCALE_MAX_RANGES = 4              # ESAHRNET_SCALE_MAX_RANGES
 SCALE_MAX_EXPONENT = 32           # ESAHRNET_SCALE_MAX_EXPONENT
 
@@ -243,6 +268,14 @@ _SIGS = {
                                                        C.POINTER(C.c_size_t)]),
     "esahrnet_tensor_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                         C.c_void_p, C.c_void_p]),
+    "esahrnet_tensor_diff_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.POINTER(C.c_size_t)]),
+    "esahrnet_tensor_diff": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "esahrnet_diff_row_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DiffRowDesc)]),
+    "esahrnet_forward_diff_workspace_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "esahrnet_forward_diff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "esahrnet_op_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "esahrnet_op_fuse": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,

@@ -461,4 +461,20 @@ int stats_parts(int fmt, int C, int Cp, int HW);
 // scan + finish of njobs tensors of N images; partials: room for sum_j stats_parts(job j) * N records, 8-byte aligned
 int launch_stats(const StatsJob* jobs, int njobs, int N, void* partials, void* records, hipStream_t stream);
 
+// ---- diff.hip: the precision report (esahrnet_diff_record, include/esahrnet.h) --------------------------------------------
+// One pair of tensors to compare: a [N][H][W][cp_a] in fmt_a (FMT_SB .. FMT_HF), stored times 2^-e, against b [N][H][W][cp_b]
+// in FMT_F32; or fmt_a == fmt_b == STATS_NCHW: plain f32 [N][C][H][W] on both sides.  Real channels 0..C-1, HW pixels.  Its N
+// records go to records[row * N + image].
+struct DiffJob {
+    const void* a;
+    int fmt_a, cp_a;
+    const void* b;
+    int fmt_b, cp_b;
+    int C, HW, e, row;
+};
+// partial records per image (a function of the shape alone); 0: a pair the scan does not serve
+int diff_parts(int fmt_a, int cp_a, int fmt_b, int cp_b, int C, int HW);
+// scan + finish of njobs pairs of N images; partials: room for sum_j diff_parts(job j) * N records, 8-byte aligned
+int launch_diff(const DiffJob* jobs, int njobs, int N, void* partials, void* records, hipStream_t stream);
+
 }  // namespace esa

@@ -94,6 +94,8 @@ struct Tensor {
     int C, Cp, level;
     int flat = 0;               // > 0: plain f32 scratch of `flat` floats per sample (no spatial extent)
     std::string tap;            // name for esahrnet_tap_read, "" if anonymous
+    std::string key;            // what the tensor is, whatever launch writes it (esahrnet_diff_row_get): the tap name, else the
+                                // convolution whose output it is, else a name the builder gives it; "" for scratch
     bool tlayout = false;       // head term in the transposed T layout (head_t.hip): row pitch head_t_xp(w)
     bool f32 = false;           // plain f32 NHWC whatever the plan's format (the output of an out_f32 convolution)
     int alt = 0;                // 0: always; 1 / 2: only when the first / second generation head runs
@@ -319,7 +321,7 @@ struct Builder {
     }
     int tensor(int C, int level, const std::string& tap = "") {
         Tensor t;
-        t.C = C; t.Cp = c.padc(C); t.level = level; t.tap = tap;
+        t.C = C; t.Cp = c.padc(C); t.level = level; t.tap = tap; t.key = tap;
         c.tensors.push_back(t);
         return (int)c.tensors.size() - 1;
     }
@@ -342,16 +344,19 @@ struct Builder {
         // ESAHRNET_TAP_ALL=1 (debugging): every convolution output becomes a named tap
         o.out = tensor(s.cout, s.level, tap.empty() && !out_f32 && c.opt.tap_all ? "conv:" + s.name : tap);
         c.tensors[o.out].f32 = out_f32;
+        c.tensors[o.out].key = !tap.empty() ? tap : d.c0 != 0 || d.c1 != s.cin
+            ? s.name + "[:, " + std::to_string(d.c0) + ":" + std::to_string(d.c1) + "]" : s.name;
         const int idx = (int)c.ops.size();
         c.tensors[o.out].def = idx;
         use(in, idx); use(res, idx);
         c.ops.push_back(o);
         return o.out;
     }
-    int fuse(const std::vector<int>& terms, int C, int level, bool relu, const std::string& tap = "") {
+    int fuse(const std::vector<int>& terms, int C, int level, bool relu, const std::string& tap = "", const std::string& key = "") {
         Op o;
         o.kind = OP_FUSE; o.nterms = (int)terms.size(); o.relu = relu;
         o.out = tensor(C, level, tap);
+        if (tap.empty()) c.tensors[o.out].key = key;
         const int idx = (int)c.ops.size();
         c.tensors[o.out].def = idx;
         for (int i = 0; i < o.nterms; ++i) { o.terms[i] = terms[i]; use(terms[i], idx); }
@@ -388,6 +393,7 @@ struct Builder {
         const int level = c.tensors[x].level, Cp = c.tensors[x].Cp;
         const int partial = flat_tensor(esa::POOL_SLABS * Cp * 2), cav = flat_tensor(Cp);
         Tensor mt; mt.C = 2; mt.Cp = 2; mt.level = level; mt.f32 = true;       // (f32 [N][H][W][2] in every format)
+        mt.key = q + "sa.maps";
         c.tensors.push_back(mt);
         const int maps = (int)c.tensors.size() - 1;
         // inside an HRModule branch (jkey >= 0) the four CBAM launches take the next depth keys behind the block's two
@@ -411,6 +417,7 @@ struct Builder {
         const int o1 = conv(c1, x, -1, true);
         const int o2 = conv(c2, o1, -1, false);
         const int y = tensor(cout, level, tap);
+        if (tap.empty()) c.tensors[y].key = p + ".cbam";
         cbam(p, o2, cout, res, true, y, 0);
         return y;
     }
@@ -433,6 +440,7 @@ struct Builder {
                 (k ? o.dconv2 : o.dconv) = (int)c.dconvs.size() - 1;
             }
             o.out = tensor(cout, level, tap);
+            if (tap.empty()) c.tensors[o.out].key = c.specs[c2].name;
             const int idx = (int)c.ops.size();
             c.tensors[o.out].def = idx;
             use(x, idx);
@@ -777,7 +785,8 @@ int build_plan_ops(esahrnet_ctx& c) {
             for (int i = 0; i < nb; ++i) {
                 const bool final_module = m == g.modules[s - 1] - 1;
                 outs.push_back(B.fuse(terms[i], cur[i], 1 + i, true,
-                                      final_module ? "stage" + std::to_string(s) + "." + std::to_string(i) : ""));
+                                      final_module ? "stage" + std::to_string(s) + "." + std::to_string(i) : "",
+                                      p + ".fuse." + std::to_string(i)));
             }
             xs = outs;
         }
@@ -3127,6 +3136,217 @@ int esahrnet_tensor_stats(const void* t_dev, int fmt, int n, int c, int cp, int 
     const esa::StatsJob job{t_dev, fmt, c, cp, h * w, 0};
     const int rc = esa::launch_stats(&job, 1, n, ws_dev, stats_dev, static_cast<hipStream_t>(stream));
     if (rc) return fail("tensor_stats: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
+// ---- precision report (diff.hip) -----------------------------------------------------------------------------------------
+// Rows are the range report's.  Two rows of two handles hold the same tensor if they carry the same key (Tensor::key, given by
+// the builder from what the tensor is: no label is parsed), and the key names one row only in either handle.
+static std::string diff_key(const esahrnet_ctx& c, int row) {
+    return row == (int)c.tensors.size() ? std::string("heatmaps") : c.tensors[row].key;
+}
+
+static int diff_find(const esahrnet_ctx& c, const std::string& key) {       // the one row with this key; -1: none or several
+    if (key.empty()) return -1;
+    int found = -1;
+    for (int r = 0; r <= (int)c.tensors.size(); ++r)
+        if (diff_key(c, r) == key) {
+            if (found >= 0) return -1;
+            found = r;
+        }
+    return found;
+}
+
+// one row of h against href under the two shape plans (shape_decisions, or the handles' own after plan_shape)
+static void diff_row(const esahrnet_ctx& a, const ShapePlan& spa, const esahrnet_ctx& b, const ShapePlan& spb, int row,
+                     int height, int width, esahrnet_diff_row_desc* out) {
+    memset(out, 0, sizeof *out);
+    const int nta = (int)a.tensors.size(), ntb = (int)b.tensors.size();
+    const std::string key = diff_key(a, row);
+    snprintf(out->key, sizeof out->key, "%s", key.c_str());
+    out->ref_row = diff_find(a, key) == row ? diff_find(b, key) : -1;
+    const int rr = out->ref_row;
+    if (row == nta) {
+        out->c = a.cfg.num_keypoints; out->h = height; out->w = width; out->fmt = esa::STATS_NCHW;
+        if (rr < 0) return;
+        out->ref_fmt = esa::STATS_NCHW;
+        out->compared = rr == ntb && b.cfg.num_keypoints == out->c &&
+                        esa::diff_parts(esa::STATS_NCHW, 0, esa::STATS_NCHW, 0, out->c, height * width) > 0;
+        return;
+    }
+    const Tensor& ta = a.tensors[row];
+    out->fmt = ta.flat ? (int)esa::FMT_F32 : stats_fmt(a, ta);
+    if (!ta.flat) { out->c = ta.C; out->h = spa.lh[ta.level]; out->w = spa.lw[ta.level]; }
+    out->exponent = a.gexp(a.tgroup.empty() ? -1 : a.tgroup[row]);
+    if (rr < 0 || rr == ntb) { if (rr == ntb) out->ref_row = -1; return; }
+    const Tensor& tb = b.tensors[rr];
+    out->ref_fmt = tb.flat ? (int)esa::FMT_F32 : stats_fmt(b, tb);
+    if (ta.flat || tb.flat || tb.C != out->c || spb.lh[tb.level] != out->h || spb.lw[tb.level] != out->w) return;
+    out->compared = stats_scanned(a, spa, ta) && stats_scanned(b, spb, tb) &&
+                    esa::diff_parts(out->fmt, ta.Cp, out->ref_fmt, tb.Cp, ta.C, out->h * out->w) > 0;
+}
+
+int esahrnet_diff_row_get(esahrnet_handle h, esahrnet_handle href, int row, int n, int height, int width,
+                          esahrnet_diff_row_desc* out) {
+    if (!h || !href || !out) return fail("diff_row_get: null argument");
+    const int nt = (int)h->tensors.size();
+    if (row < 0 || row > nt) return fail("diff_row_get: row %d out of range (0..%d)", row, nt);
+    if (check_shape(n, height, width)) return 1;
+    const ShapePlan spa = shape_decisions(*h, n, height, width);
+    if (h == href) diff_row(*h, spa, *h, spa, row, height, width, out);
+    else diff_row(*h, spa, *href, shape_decisions(*href, n, height, width), row, height, width, out);
+    return 0;
+}
+
+// name of the first configuration field in which the handles differ, `precision` aside; nullptr: none
+static const char* diff_cfg_field(const esahrnet_cfg& a, const esahrnet_cfg& b, int* va, int* vb) {
+    static thread_local char name[32];
+    auto differ = [&](int x, int y, const char* fmt, int i, int j) {
+        if (x == y) return false;
+        snprintf(name, sizeof name, fmt, i, j);
+        *va = x; *vb = y;
+        return true;
+    };
+    if (differ(a.variant, b.variant, "variant", 0, 0) || differ(a.cin, b.cin, "cin", 0, 0) ||
+        differ(a.num_keypoints, b.num_keypoints, "num_keypoints", 0, 0) || differ(a.stem_width, b.stem_width, "stem_width", 0, 0))
+        return name;
+    for (int i = 0; i < ESAHRNET_MAX_BRANCHES; ++i)
+        if (differ(a.widths[i], b.widths[i], "widths[%d]", i, 0)) return name;
+    for (int s = 0; s < 4; ++s)
+        for (int i = 0; i < ESAHRNET_MAX_BRANCHES; ++i)
+            if (differ(a.blocks[s][i], b.blocks[s][i], "blocks[%d][%d]", s, i)) return name;
+    for (int s = 0; s < 4; ++s)
+        if (differ(a.modules[s], b.modules[s], "modules[%d]", s, 0)) return name;
+    if (differ(a.final_conv_kernel, b.final_conv_kernel, "final_conv_kernel", 0, 0)) return name;
+    return nullptr;
+}
+
+struct DiffPlan {
+    size_t off_b = 0, off_parts = 0, bytes = 0;       // href's forward and the partials inside the workspace (h's forward at 0)
+    std::vector<esahrnet_diff_row_desc> rows;
+};
+
+// both keep-mode plans of the shape (the caller has set keep on both handles and puts it back), the rows, the workspace
+static int diff_plan(const char* who, esahrnet_ctx& a, esahrnet_ctx& b, int n, int height, int width, DiffPlan* dp) {
+    int va = 0, vb = 0;
+    if (const char* f = diff_cfg_field(a.cfg, b.cfg, &va, &vb))
+        return fail("%s: the handles differ in %s (%d against %d): they may differ in precision only", who, f, va, vb);
+    if (plan_shape(a, n, height, width)) return 1;
+    if (&a != &b && plan_shape(b, n, height, width)) return 1;
+    const int rows = (int)a.tensors.size() + 1;
+    dp->rows.resize(rows);
+    long long parts = 0;
+    for (int r = 0; r < rows; ++r) {
+        esahrnet_diff_row_desc& d = dp->rows[r];
+        diff_row(a, a.sp, b, b.sp, r, height, width, &d);
+        if (!d.compared) continue;
+        parts += r == rows - 1 ? esa::diff_parts(esa::STATS_NCHW, 0, esa::STATS_NCHW, 0, d.c, height * width)
+                               : esa::diff_parts(d.fmt, a.tensors[r].Cp, d.ref_fmt, b.tensors[d.ref_row].Cp, d.c, d.h * d.w);
+    }
+    if (!dp->rows[rows - 1].compared) return fail("%s: crop %dx%d is beyond the scan of the heat-maps", who, height, width);
+    dp->off_b = stats_pad256(a.sp.bytes);
+    dp->off_parts = dp->off_b + stats_pad256(b.sp.bytes);
+    dp->bytes = stats_pad256(dp->off_parts + (size_t)parts * n * sizeof(esahrnet_diff_record));
+    return 0;
+}
+
+int esahrnet_forward_diff_workspace_bytes(esahrnet_handle h, esahrnet_handle href, int n, int height, int width, size_t* bytes) {
+    if (!h || !href || !bytes) return fail("forward_diff_workspace_bytes: null argument");
+    const bool keep = h->keep, keep_ref = href->keep;
+    h->keep = href->keep = true;
+    DiffPlan dp;
+    const int rc = diff_plan("forward_diff_workspace_bytes", *h, *href, n, height, width, &dp);
+    h->keep = keep; href->keep = keep_ref;
+    if (!rc) *bytes = dp.bytes;
+    return rc;
+}
+
+int esahrnet_forward_diff(esahrnet_handle h, esahrnet_handle href, const void* x_dev, int n, int height, int width,
+                          void* heat_dev, void* heat_ref_dev, void* ws_dev, size_t ws_bytes, void* diff_dev, esahrnet_stream stream_) {
+    const char* who = "forward_diff";
+    if (!h || !href || !x_dev || !heat_dev || !heat_ref_dev || !ws_dev || !diff_dev) return fail("%s: null argument", who);
+    if (!h->committed || !href->committed)
+        return fail("%s: esahrnet_commit has not been called on the %s handle", who, !h->committed ? "tested" : "reference");
+    if (h->device != href->device) return fail("%s: the handles live on different devices (%d and %d)", who, h->device, href->device);
+    const bool keep = h->keep, keep_ref = href->keep;
+    h->keep = href->keep = true;
+    auto body = [&]() -> int {
+        DiffPlan dp;
+        if (diff_plan(who, *h, *href, n, height, width, &dp)) return 1;
+        if (ws_bytes < dp.bytes) return fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, dp.bytes);
+        if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("%s: workspace must be 256-byte aligned", who);
+        if (reinterpret_cast<uintptr_t>(diff_dev) & 7) return fail("%s: diff_dev must be 8-byte aligned", who);
+        hipStream_t stream = static_cast<hipStream_t>(stream_);
+        const int rows = (int)dp.rows.size();
+        char* const ws = static_cast<char*>(ws_dev);
+        char* const ws_b = h == href ? ws : ws + dp.off_b;
+        HIP_OK(hipMemsetAsync(diff_dev, 0, (size_t)rows * n * sizeof(esahrnet_diff_record), stream));     // the rows not compared
+        if (run_forward(h, x_dev, n, height, width, heat_dev, nullptr, ws, dp.off_b, stream_, nullptr, nullptr)) return 1;
+        if (h != href) {
+            if (run_forward(href, x_dev, n, height, width, heat_ref_dev, nullptr, ws_b, dp.off_parts - dp.off_b, stream_, nullptr, nullptr))
+                return 1;
+        } else if (heat_ref_dev != heat_dev) {
+            HIP_OK(hipMemcpyAsync(heat_ref_dev, heat_dev, (size_t)n * h->cfg.num_keypoints * height * width * sizeof(float),
+                                  hipMemcpyDeviceToDevice, stream));
+        }
+        std::vector<esa::DiffJob> jobs;
+        for (int r = 0; r + 1 < rows; ++r) {
+            const esahrnet_diff_row_desc& d = dp.rows[r];
+            if (!d.compared) continue;
+            const Tensor& ta = h->tensors[r];
+            const Tensor& tb = href->tensors[d.ref_row];
+            jobs.push_back({ws + ta.off, d.fmt, ta.Cp, ws_b + tb.off, d.ref_fmt, tb.Cp, d.c, d.h * d.w, d.exponent, r});
+        }
+        jobs.push_back({heat_dev, esa::STATS_NCHW, 0, heat_ref_dev, esa::STATS_NCHW, 0, h->cfg.num_keypoints, height * width, 0, rows - 1});
+        const int rc = esa::launch_diff(jobs.data(), (int)jobs.size(), n, ws + dp.off_parts, diff_dev, stream);
+        if (rc) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)rc));
+        return 0;
+    };
+    const int rc = body();
+    h->keep = keep; href->keep = keep_ref;
+    return rc;
+}
+
+static int tensor_diff_parts(const char* who, int fmt_a, int cp_a, int fmt_b, int cp_b, int exponent, int n, int c, int h, int w,
+                             int* parts) {
+    if (n < 1) return fail("%s: batch must be positive (got %d)", who, n);
+    if (exponent < -ESAHRNET_SCALE_MAX_EXPONENT || exponent > ESAHRNET_SCALE_MAX_EXPONENT)
+        return fail("%s: exponent %d outside -%d..%d", who, exponent, ESAHRNET_SCALE_MAX_EXPONENT, ESAHRNET_SCALE_MAX_EXPONENT);
+    const bool nchw = fmt_a == esa::STATS_NCHW && fmt_b == esa::STATS_NCHW;
+    if (!nchw && (fmt_a < esa::FMT_SB || fmt_a > esa::FMT_HF || fmt_b != esa::FMT_F32))
+        return fail("%s: no scan for format %d against format %d (0..3 against 2, or -1 against -1)", who, fmt_a, fmt_b);
+    const long long hw = (long long)h * w;
+    *parts = h > 0 && w > 0 && hw <= 0x7fffffffLL ? esa::diff_parts(fmt_a, cp_a, fmt_b, cp_b, c, (int)hw) : 0;
+    if (*parts <= 0)
+        return fail("%s: no scan for %d channels (%d and %d padded), %dx%d (padded channels a multiple of 8 and at least the "
+                    "channels; an image below 2 GiB on either side)", who, c, cp_a, cp_b, h, w);
+    return 0;
+}
+
+int esahrnet_tensor_diff_workspace_bytes(int fmt_a, int cp_a, int fmt_b, int cp_b, int n, int c, int h, int w, size_t* bytes) {
+    if (!bytes) return fail("tensor_diff_workspace_bytes: null argument");
+    int parts = 0;
+    if (tensor_diff_parts("tensor_diff_workspace_bytes", fmt_a, cp_a, fmt_b, cp_b, 0, n, c, h, w, &parts)) return 1;
+    *bytes = (size_t)parts * n * sizeof(esahrnet_diff_record);
+    return 0;
+}
+
+int esahrnet_tensor_diff(const void* a_dev, int fmt_a, int cp_a, const void* b_dev, int fmt_b, int cp_b, int exponent,
+                         int n, int c, int h, int w, void* ws_dev, size_t ws_bytes, void* diff_dev, esahrnet_stream stream) {
+    if (!a_dev || !b_dev || !ws_dev || !diff_dev) return fail("tensor_diff: null argument");
+    int parts = 0;
+    if (tensor_diff_parts("tensor_diff", fmt_a, cp_a, fmt_b, cp_b, exponent, n, c, h, w, &parts)) return 1;
+    const size_t need = (size_t)parts * n * sizeof(esahrnet_diff_record);
+    if (ws_bytes < need) return fail("tensor_diff: workspace too small (%zu < %zu)", ws_bytes, need);
+    if (fmt_a != esa::STATS_NCHW && ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(b_dev)) & 15))
+        return fail("tensor_diff: a_dev and b_dev must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(b_dev)) & 3)
+        return fail("tensor_diff: a_dev and b_dev must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(ws_dev) & 7) return fail("tensor_diff: workspace must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(diff_dev) & 7) return fail("tensor_diff: diff_dev must be 8-byte aligned");
+    const esa::DiffJob job{a_dev, fmt_a, cp_a, b_dev, fmt_b, cp_b, c, h * w, exponent, 0};
+    const int rc = esa::launch_diff(&job, 1, n, ws_dev, diff_dev, static_cast<hipStream_t>(stream));
+    if (rc) return fail("tensor_diff: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return 0;
 }
 

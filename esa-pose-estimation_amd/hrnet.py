@@ -321,6 +321,24 @@ class HighResolutionNet(nn.Module):
         Which precision can these weights afford: see ActivationStats.headroom_fp16, saturated, first_nonfinite."""
         return self._rt.forward_stats(self, x0)
 
+    def precision_report(self, x0: torch.Tensor, reference=None) -> "PrecisionReport":
+        """What this net's precision costs on its own weights and these crops, tensor by tensor (include/esahrnet.h:
+        esahrnet_forward_diff): the crops go through this net and through `reference`, every tensor of both
+        plans is kept, and a two-operand scan leaves one 64-byte error record per (tensor, crop); one device -> host copy.
+        reference=None: an fp32-grade twin of the same class and configuration, built from this net's state dict and closed
+        again.  A caller's own net (same configuration; any precision, but only tensors the reference stores in f32 and the
+        heat-maps are compared) is left as it is."""
+        self._inference_only()
+        if reference is not None:
+            return self._rt.forward_diff(self, reference, x0)
+        twin = type(self)(self._config, cin=self._cin, num_keypoints=self._k, variant=self._cfg_struct.variant, precision="fp32")
+        try:
+            twin.load_state_dict(self.state_dict())
+            twin.to(x0.device).eval()
+            return self._rt.forward_diff(self, twin, x0)
+        finally:
+            twin._rt.close()            # its handles, packed weights and scratch, now
+
     # ---- fp16 scale exponents (include/esahrnet.h: fp16 scale groups; DESIGN.md 3e) ---------------------------------
     @property
     def fp16_scale_groups(self):
@@ -475,6 +493,8 @@ class _Runtime:
         "corr": ("frames", "esahrnet_frames_correspondences_workspace_bytes", lambda n, hh, ww, keep: (n, hh, *keep)),
         "stats": ("stats", "esahrnet_forward_stats_workspace_bytes", _crops),
         "stats_h0": ("stats", "esahrnet_forward_stats_h0_workspace_bytes", _crops),
+        # (the key's `keep` is the reference handle's address: both forwards and the partials live in this one workspace)
+        "diff": ("diff", "esahrnet_forward_diff_workspace_bytes", lambda n, hh, ww, keep: (C.c_void_p(keep), n, hh, ww)),
     }
 
     def __init__(self, cfg_struct):
@@ -902,6 +922,42 @@ class _Runtime:
         return ActivationStats(descs, rec[:len(descs)], heat, groups=groups, exponents=master.fp16_exponents,
                                h0=rec[len(descs)] if with_h0 else None)
 
+    def diff_rows(self, h, href, n, hh, ww):
+        """The rows of h's report paired with href's at a shape (esahrnet_diff_row_get): no GPU needed."""
+        rows = C.c_int(0)
+        _lib.check(self.lib.esahrnet_stats_rows(h, C.byref(rows)))
+        descs = []
+        for i in range(rows.value):
+            d = _lib.DiffRowDesc()
+            _lib.check(self.lib.esahrnet_diff_row_get(h, href, i, n, hh, ww, C.byref(d)))
+            descs.append(d)
+        return descs
+
+    def forward_diff(self, module, ref_module, x0):
+        """esahrnet_forward_diff on the current stream of x's device: -> PrecisionReport.  Same device lock (this runtime's, then
+        the reference's), workspace contract and record_stream handling as forward_stats(); the records come back in one copy."""
+        x = self._check_input(module, x0)
+        ref_rt = ref_module._rt
+        ref_rt._check_input(ref_module, x)
+        n, _, hh, ww = x.shape
+        dev = x.device
+        ts = torch.cuda.current_stream(dev)
+        with self._device_lock(dev.index), ref_rt._device_lock(dev.index):
+            h = self._handle_for(module, dev)
+            href = h if ref_module is module else ref_rt._handle_for(ref_module, dev)
+            descs = self.diff_rows(h, href, n, hh, ww)
+            ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, n, hh, ww, href.value, kind="diff")
+            heat = torch.empty((n, module._k, hh, ww), dtype=torch.float32, device=dev)
+            heat_ref = torch.empty_like(heat)
+            rec_dev = torch.empty((len(descs), n, _lib.DIFF_RECORD_BYTES), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(self.lib.esahrnet_forward_diff(h, href, x.data_ptr(), n, hh, ww, heat.data_ptr(), heat_ref.data_ptr(),
+                                                          ws_ptr, ws_bytes, rec_dev.data_ptr(), C.c_void_p(ts.cuda_stream)))
+        ws.record_stream(ts)
+        x.record_stream(ts)
+        rec = rec_dev.cpu().numpy().reshape(-1).view(_lib.diff_dtype()).reshape(len(descs), n)
+        return PrecisionReport(descs, rec, heat, heat_ref)
+
     def taps(self, module, x0):
         x = self._check_input(module, x0)
         n, _, hh, ww = x.shape
@@ -998,6 +1054,93 @@ class ActivationStats:
             lines.append(f"{i:>4} {r['def_op']:>4} {r['name'][:44]:<44} {shape:<14} {r['format']:<8} {r['max_abs']:>11.4e} "
                          f"{r['mean_abs']:>11.4e} {r['min']:>11.4e} {r['max']:>11.4e} {r['n_nan']:>6} {r['n_inf']:>6} "
                          f"{r['n_ge_f16max']:>8} {r['n_f16_tiny']:>9} {r['n_zero']:>9}")
+        return "\n".join(lines)
+
+
+class PrecisionReport:
+    """net.precision_report(x): the error of one forward against the reference net's, tensor by tensor.
+
+    per_image     the raw records, a structured numpy array [rows, n] (_lib.DIFF_FIELDS); rows not compared are all zero
+    keys          one key per row of the tested net's report in plan order, the last one "heatmaps": what the tensor is (its
+                  tap name, else the convolution whose output it is), the same in every plan of the configuration
+    compared      bool [rows]: the key names one row in both plans, the shapes agree and both tensors were scanned
+    descs         the row descriptions (_lib.DiffRowDesc): shape, formats, ref_row, exponent
+    heatmaps, heatmaps_ref    the two forwards' heat-maps (f32 [n, K, H, W] on the device), the bits net(x) returns"""
+
+    def __init__(self, descs, per_image, heatmaps, heatmaps_ref):
+        self.descs = descs
+        self.per_image = per_image
+        self.heatmaps = heatmaps
+        self.heatmaps_ref = heatmaps_ref
+        self.keys = [d.key.decode() for d in descs]
+        self.compared = np.array([bool(d.compared) for d in descs])
+
+    def max_abs_err(self):
+        """f32 [rows]: the largest |a - b| of each row over the crops (0 for a row not compared)."""
+        return self.per_image["max_abs_err"].max(axis=1)
+
+    def rel_max(self):
+        """f64 [rows]: max_abs_err over the largest |b| of the row (0 where that is 0)."""
+        ref = self.per_image["max_abs_ref"].max(axis=1).astype(np.float64)
+        return np.divide(self.max_abs_err().astype(np.float64), ref, out=np.zeros_like(ref), where=ref > 0)
+
+    def rel_rms(self):
+        """f64 [rows]: sqrt(sum of err^2 / sum of b^2) over the compared elements of all crops (0 where the reference is 0)."""
+        num = self.per_image["sum_sq_err"].sum(axis=1)
+        den = self.per_image["sum_sq_ref"].sum(axis=1)
+        return np.sqrt(np.divide(num, den, out=np.zeros_like(den), where=den > 0))
+
+    def where(self, row: int, i: int):
+        """(c, y, x) of the element record.at names in crop i of `row`; None when nothing was compared."""
+        at = int(self.per_image["at"][row, i])
+        if at == _lib.DIFF_AT_NONE:
+            return None
+        d = self.descs[row]
+        if d.fmt == _lib.STATS_NCHW:
+            return at // (d.h * d.w), at % (d.h * d.w) // d.w, at % d.w
+        return at % d.c, at // d.c // d.w, at // d.c % d.w
+
+    def worst(self, k: int = 5):
+        """The k compared rows with the largest rel_max, largest first: dicts of row, key, shape, rel_max, rel_rms,
+        max_abs_err, and the crop and (c, y, x) of that error."""
+        rel, rms, err = self.rel_max(), self.rel_rms(), self.max_abs_err()
+        order = sorted((r for r in range(len(self.keys)) if self.compared[r]), key=lambda r: -rel[r])[:k]
+        out = []
+        for r in order:
+            i = int(self.per_image["max_abs_err"][r].argmax())
+            d = self.descs[r]
+            out.append(dict(row=r, key=self.keys[r], shape=(d.c, d.h, d.w), rel_max=float(rel[r]), rel_rms=float(rms[r]),
+                            max_abs_err=float(err[r]), crop=i, where=self.where(r, i)))
+        return out
+
+    def keypoints(self, refine: str = "get_final"):
+        """Both heat-map tensors through the device decoder (inference.heatmaps_to_keypoints): -> dict of max_shift and
+        mean_shift (f64 [n]: the largest and the mean distance in pixels between a crop's keypoints and the reference's),
+        argmax_differs (planes whose arg-max pixel differs), kp and kp_ref (f32 [n, K, 3] on the device)."""
+        from .inference import _keypoints
+        kp, idx = _keypoints(self.heatmaps, True, refine)[:2]
+        kp_ref, idx_ref = _keypoints(self.heatmaps_ref, True, refine)[:2]
+        shift = (kp[..., :2].double() - kp_ref[..., :2].double()).norm(dim=-1).cpu().numpy()
+        return dict(max_shift=shift.max(axis=1), mean_shift=shift.mean(axis=1),
+                    argmax_differs=int((idx != idx_ref).sum().item()), kp=kp, kp_ref=kp_ref)
+
+    def table(self) -> str:
+        rel, rms, err = self.rel_max(), self.rel_rms(), self.max_abs_err()
+        head = f"{'row':>4} {'ref':>4} {'key':<44} {'shape':<14} {'format':<8} {'exp':>4} {'max_abs_err':>12} {'rel_max':>10} " \
+               f"{'rel_rms':>10} {'max_abs_ref':>12} {'nonfin a':>9} {'nonfin b':>9} {'class !=':>9}"
+        lines = [head]
+        for r, d in enumerate(self.descs):
+            shape = "x".join(str(v) for v in (d.c, d.h, d.w))
+            fmt = _lib.STATS_FORMATS[d.fmt]
+            if not self.compared[r]:
+                lines.append(f"{r:>4} {d.ref_row:>4} {self.keys[r][:44]:<44} {shape:<14} {fmt:<8} (not compared)")
+                continue
+            rec = self.per_image[r]
+            lines.append(f"{r:>4} {d.ref_row:>4} {self.keys[r][:44]:<44} {shape:<14} {fmt:<8} {d.exponent:>4} {err[r]:>12.4e} "
+                         f"{rel[r]:>10.3e} {rms[r]:>10.3e} {rec['max_abs_ref'].max():>12.4e} "
+                         f"{int(rec['n_nonfinite_test'].astype(np.int64).sum()):>9} "
+                         f"{int(rec['n_nonfinite_ref'].astype(np.int64).sum()):>9} "
+                         f"{int(rec['n_class_differs'].astype(np.int64).sum()):>9}")
         return "\n".join(lines)
 
 

@@ -705,6 +705,83 @@ int esahrnet_tensor_stats_workspace_bytes(int fmt, int n, int c, int cp, int h, 
 int esahrnet_tensor_stats(const void* t_dev, int fmt, int n, int c, int cp, int h, int w, void* ws_dev, size_t ws_bytes,
                           void* stats_dev, esahrnet_stream stream);
 
+/* ---- precision report: the error of a handle against a reference handle, tensor by tensor ---------------------
+ * What does a fast precision cost on these weights and these crops?  The same crops go through two handles that differ in
+ * nothing but `precision`, every tensor is kept, and a two-operand scan reads tensor A (tested) and tensor B (reference) where
+ * the two forwards left them.
+ *
+ * One record per (row, image), 64 bytes; ESAHRNET_DIFF_FIELDS is the one description of its layout, as ESAHRNET_STATS_FIELDS is
+ * of the range report's.  Per element, in f32: d = a - b (one rounding), err = |d|; an element is COMPARED only if a and b are
+ * both finite.  A tensor stored as T * 2^-e (fp16 scale exponents) enters as ldexpf(a, e).
+ *   sum_abs_err, sum_sq_err   sums of err and err^2 over the compared elements
+ *   sum_sq_ref                sum of b^2 over the compared elements
+ *   max_abs_err, max_abs_ref, max_abs_test   over the compared elements; 0 when there is none
+ *   at                        smallest NHWC index pixel * c + channel among the elements that reach max_abs_err (f32 NCHW
+ *                             operands: the flat index inside the image); 0xFFFFFFFF when nothing was compared
+ *   n_compared                elements with a and b both finite
+ *   n_nonfinite_test, n_nonfinite_ref        elements of A / of B that are not finite
+ *   n_class_differs           elements where exactly one side is finite, or the sides are different kinds of non-finite
+ *                             (NaN / +inf / -inf)
+ *   reserved                  zero
+ * Padding channels are read and never counted, whatever they hold.  The records have the determinism of the range report's: a
+ * workgroup owns a fixed pixel range of one image, the finish merges an image's partials in index order, no atomics. */
+#define ESAHRNET_DIFF_RECORD_BYTES 64
+#define ESAHRNET_DIFF_FIELDS(X)   \
+    X(double, sum_abs_err)        \
+    X(double, sum_sq_err)         \
+    X(double, sum_sq_ref)         \
+    X(float, max_abs_err)         \
+    X(float, max_abs_ref)         \
+    X(float, max_abs_test)        \
+    X(uint32_t, at)               \
+    X(uint32_t, n_compared)       \
+    X(uint32_t, n_nonfinite_test) \
+    X(uint32_t, n_nonfinite_ref)  \
+    X(uint32_t, n_class_differs)
+typedef struct esahrnet_diff_record {
+#define ESAHRNET_DIFF_X(type, name) type name;
+    ESAHRNET_DIFF_FIELDS(ESAHRNET_DIFF_X)
+#undef ESAHRNET_DIFF_X
+    uint32_t reserved[2];
+} esahrnet_diff_record;
+
+/* The scan alone on raw tensors, beside esahrnet_tensor_stats.  a_dev [n][h][w][cp_a] in fmt_a (0 split bf16, 1 bf16, 2 f32
+ * NHWC, 3 fp16) against b_dev [n][h][w][cp_b] in fmt_b = 2; or fmt_a = fmt_b = -1: plain f32 [n][c][h][w] on both sides (cp
+ * ignored).  Channel padding: a multiple of 8, and at least c.  A enters as ldexpf(a, exponent), |exponent| <= 32.  n records
+ * into diff_dev; ws_dev: 8-byte aligned scratch for the partials.  Refused before any launch: null pointers, a format pair
+ * outside the five above, c / cp / h / w out of range, the exponent, workspace size, alignment (tensors 16, the rest 8). */
+int esahrnet_tensor_diff_workspace_bytes(int fmt_a, int cp_a, int fmt_b, int cp_b, int n, int c, int h, int w, size_t* bytes);
+int esahrnet_tensor_diff(const void* a_dev, int fmt_a, int cp_a, const void* b_dev, int fmt_b, int cp_b, int exponent,
+                         int n, int c, int h, int w, void* ws_dev, size_t ws_bytes, void* diff_dev, esahrnet_stream stream);
+
+/* Row `row` of h's report (esahrnet_stats_rows(h)) and the row of href's report that holds the same tensor.  The key says what
+ * the tensor is: its tap name where it has one, else the name of the convolution whose output it is (with its input-channel
+ * slice, where it reads one), "<block>.cbam" / "<module>.fuse.<branch>" for the anonymous results of seg_hrnet3's blocks and of
+ * the fuse sums, "heatmaps" for the last row; it does not depend on how the plan merges launches.  Works on uncommitted handles
+ * and needs no device. */
+typedef struct esahrnet_diff_row_desc {
+    char key[96];
+    int ref_row;                 /* the row of href with the same key; -1: none, or the key is not unique in either handle */
+    int c, h, w;                 /* of h's row, as esahrnet_stats_row_get */
+    int fmt, ref_fmt;            /* storage formats (ref_fmt 0 when ref_row < 0) */
+    int exponent;                /* h's scale exponent for the row's group, else 0: the tensor is stored times 2^-exponent */
+    int compared;                /* 1 only if the key is unique in both handles, the shapes agree, both rows are scanned at this
+                                  * shape and the format pair is one esahrnet_tensor_diff serves */
+} esahrnet_diff_row_desc;
+int esahrnet_diff_row_get(esahrnet_handle h, esahrnet_handle href, int row, int n, int height, int width,
+                          esahrnet_diff_row_desc* out);
+/* The keep-mode forward of h, then the keep-mode forward of href (each the plan and the launches of esahrnet_forward under
+ * esahrnet_set_debug_keep, each in its own part of the one workspace), then the scan of every compared row, the heat-maps last.
+ * heat_dev / heat_ref_dev: the two heat-map tensors, f32 [n][K][height][width].  diff_dev: esahrnet_diff_record [rows of h][n],
+ * every byte written, uncompared rows all zero.  Nothing is allocated, nothing synchronised; both handles' keep states are left
+ * as found.  h == href is allowed: the forward runs once and every error is zero.  Refused before the first launch, in
+ * esahrnet_forward's order: null argument, either handle uncommitted, handles on different devices, configurations that differ
+ * in anything but `precision` (the message names the first differing field), shape, workspace size, workspace alignment (256),
+ * diff_dev alignment (8). */
+int esahrnet_forward_diff_workspace_bytes(esahrnet_handle h, esahrnet_handle href, int n, int height, int width, size_t* bytes);
+int esahrnet_forward_diff(esahrnet_handle h, esahrnet_handle href, const void* x_dev, int n, int height, int width,
+                          void* heat_dev, void* heat_ref_dev, void* ws_dev, size_t ws_bytes, void* diff_dev, esahrnet_stream stream);
+
 /* ---- fp16 scale groups: per-tensor power-of-two scales for precision 3 ---------------------------------------
  * precision 3 holds only inside fp16's range: stores saturate at +-65504, values below 2^-14 lose bits.  With BatchNorm folded,
  * seg_hrnet / seg_hrnet2 is convolution, bias, ReLU, sums and bilinear interpolation, which all commute exactly with a power of
