@@ -10,7 +10,8 @@
 // The resize restates OpenCV's published 8-bit INTER_LINEAR: half-pixel centres, coefficients
 // quantised to 11 bits (INTER_RESIZE_COEF_BITS), horizontal pass in int32, vertical pass
 // ((b0*(r0>>4))>>16) + ((b1*(r1>>4))>>16) + 2) >> 2.  PARITY UNPINNED against cv2 itself (not
-// installable here); bit-exact against oracle/crops_ref.py, which restates the same arithmetic.
+// installable here); bit-exact against oracle/crops_ref.py, which restates the same arithmetic.  The geometry is held to
+// float64 bilinear interpolation within B = 1.19458 gray levels by tests/test_crops_ref_host.py and tests/test_gpu_crops.py.
 #include "kernels.h"
 
 namespace esa {

@@ -3,7 +3,8 @@
 Follows data_load_val.py:127-187 for the box arithmetic and the (swapped) edge pad, and restates
 OpenCV's published 8-bit INTER_LINEAR resize (half-pixel centres, 11-bit coefficients, int32 horizontal
 pass, ((b0*(r0>>4))>>16 + (b1*(r1>>4))>>16 + 2) >> 2 vertical pass) for cv2.resize.  PARITY UNPINNED
-against cv2 itself: it is not installable here and the reference holds no image fixture."""
+against cv2 itself: it is not installable here and the reference holds no image fixture.  The geometry is held to float64
+bilinear interpolation within B = 1.19458 gray levels by tests/test_crops_ref_host.py and tests/test_gpu_crops.py."""
 import numpy as np
 
 
