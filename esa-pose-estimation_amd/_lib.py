@@ -231,6 +231,19 @@ _SIGS = {
     "esahrnet_keypoints_candidates_refined": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "esahrnet_keypoints_candidates_refined_forward_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                                               C.POINTER(C.c_size_t)]),
+    "esahrnet_forward_keypoints_candidates_refined": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_size_t,
+                                                                C.c_void_p]),
+    "esahrnet_frames_keypoints_candidates_refined_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                                              C.POINTER(C.c_size_t)]),
+    "esahrnet_frames_keypoints_candidates_refined": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                               C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "esahrnet_pnp_batch_cand_w": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),

@@ -10,6 +10,7 @@
 //                        identical on gray frames with the identity index) with a frame index per crop, RGB8 frames reduced
 //                        by PIL's convert('L') before the resize, and invalid crops written as zeros.
 //   mark_invalid_kernel  keypoint rows of invalid crops become NaN (index -1) after the forward.
+//   mark_invalid_refined_kernel  the same for the refined candidates' outputs: K * M rows per crop, f64 outputs and a status.
 #include "kernels.h"
 
 namespace esa {
@@ -165,6 +166,31 @@ __global__ __launch_bounds__(256) void mark_invalid_gfcov_kernel(const int* vali
     status[t] = -1;
 }
 
+// for esahrnet_frames_keypoints_candidates_refined: one thread per (crop, slot), slots = K * M candidate rows per crop; every
+// output but cand is optional
+__global__ __launch_bounds__(256) void mark_invalid_refined_kernel(const int* valid, int m, int slots, float* cand, int* cidx,
+                                                                   int* status, double* hess, double* fit, double* cov,
+                                                                   double* info) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m * slots) return;
+    if (valid[t / slots]) return;
+    const float nan = __int_as_float(0x7fc00000);
+    const double dnan = __longlong_as_double(0x7ff8000000000000LL);
+    cand[(size_t)t * 3 + 0] = nan;
+    cand[(size_t)t * 3 + 1] = nan;
+    cand[(size_t)t * 3 + 2] = nan;
+    if (cidx) cidx[t] = -1;
+    if (status) status[t] = -1;
+    if (fit)
+        for (int i = 0; i < 8; ++i) fit[(size_t)t * 8 + i] = dnan;
+    if (hess)
+        for (int i = 0; i < 3; ++i) hess[(size_t)t * 3 + i] = dnan;
+    if (cov)
+        for (int i = 0; i < 3; ++i) cov[(size_t)t * 3 + i] = dnan;
+    if (info)
+        for (int i = 0; i < 3; ++i) info[(size_t)t * 3 + i] = dnan;
+}
+
 }  // namespace
 
 int launch_boxes(const int* det, const int* frame_idx, int nframes, int m, int FH, int FW, int S, int rule, int* crop,
@@ -209,6 +235,14 @@ int launch_mark_invalid_gaussfit_cov(const int* valid, int m, int K, float* kp, 
     if (m <= 0 || K <= 0 || (long long)m * K > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(mark_invalid_gfcov_kernel, dim3((unsigned)(((long long)m * K + 255) / 256)), dim3(256), 0, s, valid, m, K, kp,
                        idx, fit, status, hess, cov, info);
+    return (int)hipGetLastError();
+}
+
+int launch_mark_invalid_refined(const int* valid, int m, int slots, float* cand, int* cidx, int* status, double* hess, double* fit,
+                                double* cov, double* info, hipStream_t s) {
+    if (m <= 0 || slots <= 0 || (long long)m * slots > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(mark_invalid_refined_kernel, dim3((unsigned)(((long long)m * slots + 255) / 256)), dim3(256), 0, s, valid, m,
+                       slots, cand, cidx, status, hess, fit, cov, info);
     return (int)hipGetLastError();
 }
 

@@ -417,6 +417,17 @@ int launch_mark_invalid_gaussfit(const int* valid, int m, int K, float* kp, int*
 // the same plus cov and info f64 [m][K][3] (may be null) -> NaN (mark_invalid_gfcov_kernel)
 int launch_mark_invalid_gaussfit_cov(const int* valid, int m, int K, float* kp, int* idx, double* fit, int* status, double* hess,
                                      double* cov, double* info, hipStream_t s);
+// the refined candidates' outputs (mark_invalid_refined_kernel), one thread per slot of [m][K * M]: cand f32 [..][3] -> NaN; cidx
+// and status int32 [..] -> -1; hess, cov, info f64 [..][3] and fit f64 [..][8] -> NaN.  Every pointer but cand may be null
+int launch_mark_invalid_refined(const int* valid, int m, int slots, float* cand, int* cidx, int* status, double* hess, double* fit,
+                                double* cov, double* info, hipStream_t s);
+
+// ---- the decoders at caller-given pixels (keypoints_at.hip): heat f32 [planes][H][W], at int32 [planes][m] -> kp f32
+// [planes][m][3]; decoder 0 get_final, 1 get_final2 (ws: at_workspace_bytes, 256-byte aligned), 2 the Gaussian fit (status not
+// null).  hess, fit, cov, info (f64) and status may be null where the decoder allows it; every argument has been checked
+size_t at_workspace_bytes(long long planes, int H, int W, int decoder);
+int launch_keypoints_at(const float* heat, int planes, int H, int W, const int* at, int m, int decoder, float* kp, double* hess,
+                        double* fit, int* status, double* cov, double* info, double cov_floor, void* ws, hipStream_t stream);
 
 // ---- keypoints -> the record the pose solver consumes (correspond.hip, correspond.h) ----------------------------------
 // kp f32 [m][K][3], hess f64 [m][K][3] (mode 1; may be null in mode 0), crop / rates / valid as launch_boxes wrote them ->

@@ -106,7 +106,9 @@ __global__ __launch_bounds__(64) void at_gaussfit_kernel(const float* heat, cons
                         cov_floor);
 }
 
-// the launches of one call; every argument has been checked
+}  // namespace
+
+// the launches of one call; every argument has been checked (kernels.h: the fused forward launches them too)
 int launch_keypoints_at(const float* heat, int planes, int H, int W, const int* at, int m, int decoder, float* kp, double* hess,
                         double* fit, int* status, double* cov, double* info, double cov_floor, void* ws, hipStream_t stream) {
     const unsigned slots = (unsigned)((long long)planes * m);
@@ -121,6 +123,7 @@ int launch_keypoints_at(const float* heat, int planes, int H, int W, const int* 
     }
     const int ntiles = final2_tiles(H, W);                 // (the workspace of launch_final2, final2.h: tile records, then maxima)
     const size_t nt = (size_t)planes * ntiles;
+    if (nt > 0x7fffffu) return (int)hipErrorInvalidValue;  // (check_at_args refuses it by name; the fused forward gets here without)
     float2* part = static_cast<float2*>(ws);
     float* bmax = reinterpret_cast<float*>(static_cast<char*>(ws) + ((nt * 8 + 255) & ~(size_t)255));
     hipLaunchKernelGGL(final2_tile_kernel<F2Nchw>, dim3((unsigned)nt), dim3(F2_T), 0, stream, F2Nchw{heat}, H, W,
@@ -135,6 +138,8 @@ int launch_keypoints_at(const float* heat, int planes, int H, int W, const int* 
 size_t at_workspace_bytes(long long planes, int H, int W, int decoder) {
     return decoder == 1 ? final2_workspace_bytes(planes, H, W) : 0;
 }
+
+namespace {
 
 // every refusal of esahrnet_keypoints_at, in the order include/esahrnet.h documents; `who` names the entry in the message
 int check_at_args(const char* who, const void* heat_dev, int n, int k, int height, int width, const void* at_dev, int m, int decoder,

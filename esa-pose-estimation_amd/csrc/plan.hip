@@ -1932,14 +1932,17 @@ struct Request {
     float* cand = nullptr;      // the candidates: f32 [n * K][M][3] (= kp, never null) and int32 [n * K][M] (= idx, may be null),
     int* cidx = nullptr;        // M in 1..ESAHRNET_MAX_CANDIDATES peaks per plane, r >= 0 pixels apart
     int M = 0, r = 0;
+    int refine = -1;            // the candidates refined at their own pixels: the decoder of keypoints_at.hip (0..2) behind the
+                                // search, its outputs in hess / fit / status / cov / info; -1: the plain search
 };
 
 // The one place a request is built, for the four forms the entries come in: (kp, idx), + hess, + fit and status, + cov, info and
 // cov_floor.  Two rules are stated here and nowhere else: get_final computes no Hessian, so hess is ignored by it; cov and
 // info belong to the Gaussian fit, and are ignored without it.  The candidates' form is (cand, cidx) in the place of (kp, idx),
-// with M and r.
+// with M and r, and with `refine` (0..2) the decoder that refines every candidate and may write all of the other outputs.
 static Request make_request(Decoder d, void* kp, void* idx, void* hess = nullptr, void* fit = nullptr, void* status = nullptr,
-                            void* cov = nullptr, void* info = nullptr, double cov_floor = 0.0, int M = 0, int nms_radius = 0) {
+                            void* cov = nullptr, void* info = nullptr, double cov_floor = 0.0, int M = 0, int nms_radius = 0,
+                            int refine = -1) {
     Request r;
     r.decoder = d;
     r.kp = static_cast<float*>(kp);
@@ -1947,14 +1950,15 @@ static Request make_request(Decoder d, void* kp, void* idx, void* hess = nullptr
     r.hess = d == DEC_FINAL ? nullptr : static_cast<double*>(hess);
     r.fit = static_cast<double*>(fit);
     r.status = static_cast<int*>(status);
-    r.cov = d == DEC_GAUSSFIT ? static_cast<double*>(cov) : nullptr;
-    r.info = d == DEC_GAUSSFIT ? static_cast<double*>(info) : nullptr;
+    r.cov = d == DEC_GAUSSFIT || d == DEC_CAND ? static_cast<double*>(cov) : nullptr;
+    r.info = d == DEC_GAUSSFIT || d == DEC_CAND ? static_cast<double*>(info) : nullptr;
     r.cov_floor = cov_floor;
     if (d == DEC_CAND) {
         r.cand = r.kp;
         r.cidx = r.idx;
         r.M = M;
         r.r = nms_radius;
+        r.refine = refine;
     }
     return r;
 }
@@ -1975,6 +1979,8 @@ struct Buffers {
     float2* kpart = nullptr;
     float* kbmax = nullptr;
     size_t kws = 0;
+    int* kcidx = nullptr;       // the refined candidates: the pixels of the candidates where the caller keeps none, and the
+    void* kat = nullptr;        // workspace of the decoder at those pixels
     // esahrnet_forward_stats_h0: the fused 16-bit head runs in its range form (launch_head_bf_range) and leaves the range of h0
     void* h0_part = nullptr;
     void* h0_rec = nullptr;
@@ -1988,15 +1994,19 @@ struct Buffers {
 //                             esa::final2_workspace_bytes); the matrix-core output layer, its heat-maps and the same; the VALU
 //                             output layer, the raw (part) and blurred (bmax) maxima of its 22 x 22 tiles
 //   candidates                the heat-maps, for every network and precision: the runner-up rule needs whole planes
+//   refined candidates        behind those heat-maps: cidx, the pixels of ESAHRNET_MAX_CANDIDATES candidates per plane (the
+//                             query knows no M), then at, the workspace of keypoints_at.hip's decoder (get_final2 only)
 // No N*K*H*W term but the matrix-core one and the candidates'.
 struct KpScratch {
     int ntiles = 0;
-    size_t heat = 0, part = 0, bmax = 0;
+    size_t heat = 0, part = 0, bmax = 0, cidx = 0, at = 0;
     size_t part_off() const { return heat; }
     size_t bmax_off() const { return heat + part; }
-    size_t total() const { return heat + part + bmax; }
+    size_t cidx_off() const { return heat + part + bmax; }
+    size_t at_off() const { return heat + part + bmax + cidx; }
+    size_t total() const { return heat + part + bmax + cidx + at; }
 };
-static KpScratch kp_scratch(const esahrnet_ctx& c, int n, int height, int width, Decoder d) {
+static KpScratch kp_scratch(const esahrnet_ctx& c, int n, int height, int width, Decoder d, int refine = -1) {
     KpScratch s;
     const int K = c.cfg.num_keypoints;
     const long long planes = (long long)n * K;
@@ -2004,6 +2014,10 @@ static KpScratch kp_scratch(const esahrnet_ctx& c, int n, int height, int width,
     if (d == DEC_NONE) return s;
     if (d == DEC_CAND) {
         s.heat = pad((size_t)planes * height * width * 4);
+        if (refine >= 0) {
+            s.cidx = pad((size_t)planes * ESAHRNET_MAX_CANDIDATES * 4);
+            s.at = esa::at_workspace_bytes(planes, height, width, refine);
+        }
         return s;
     }
     if (c.cfg.variant != 1 && c.opt.final_mfma) s.heat = pad((size_t)planes * height * width * 4);
@@ -2043,7 +2057,14 @@ static int run_decode(const esahrnet_ctx& c, const Buffers& b, const esa::FinalP
             rc = esa::launch_final(p, stream);
         } else rc = esa::launch_fmt_to_nchw(fmt, maps, n, K, height, width, Cp, b.kheat, stream);
         if (rc) return rc;
-        return esa::launch_keypoints_candidates_auto(b.kheat, n * K, height, width, r.M, r.r, r.cand, r.cidx, stream);
+        // refined: the decoder at every candidate's pixel behind the search (decoder 0 refines nothing: the search's rows are
+        // its rows, and only a status asked for is left to write); the pixels go to the scratch where the caller keeps none
+        const bool at = r.refine > 0 || (r.refine == 0 && r.status);
+        int* const cidx = at && !r.cidx ? b.kcidx : r.cidx;
+        rc = esa::launch_keypoints_candidates_auto(b.kheat, n * K, height, width, r.M, r.r, r.cand, cidx, stream);
+        if (rc || !at) return rc;
+        return esa::launch_keypoints_at(b.kheat, n * K, height, width, cidx, r.M, r.refine, r.cand, r.hess, r.fit, r.status, r.cov,
+                                        r.info, r.cov_floor, b.kat, stream);
     }
     if (fp && !c.final_wpk) {
         p.out = nullptr;
@@ -2453,7 +2474,7 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
     if (!h || !x_dev || !(heat_dev || req) || !ws_dev) return fail("forward: null argument");
     if (!h->committed) return fail("forward: esahrnet_commit has not been called");
     if (plan_shape(*h, n, height, width)) return 1;
-    const KpScratch ks = kp_scratch(*h, n, height, width, req ? req->decoder : DEC_NONE);
+    const KpScratch ks = kp_scratch(*h, n, height, width, req ? req->decoder : DEC_NONE, req ? req->refine : -1);
     const size_t need = h->sp.bytes + ks.total();
     if (ws_bytes < need) return fail("forward: workspace too small (%zu < %zu)", ws_bytes, need);
     if (reinterpret_cast<uintptr_t>(ws_dev) & 255) return fail("forward: workspace must be 256-byte aligned");
@@ -2467,6 +2488,8 @@ static int run_forward(esahrnet_handle h, const void* x_dev, int n, int height, 
         bufs.kpart = reinterpret_cast<float2*>(scratch + ks.part_off());
         bufs.kbmax = reinterpret_cast<float*>(scratch + ks.bmax_off());
         bufs.kws = ks.part;
+        bufs.kcidx = reinterpret_cast<int*>(scratch + ks.cidx_off());
+        bufs.kat = scratch + ks.at_off();
     }
     int op_index = 0;
     if (events && hipEventRecord(events[0], stream) != hipSuccess) return fail("forward: hipEventRecord failed");
@@ -2573,10 +2596,11 @@ int esahrnet_forward_partials(esahrnet_handle h, const void* x_dev, int n, int h
 }
 
 // ---- the workspace of a forward: the plan's tensors, then the decoder's scratch ----------------------------------------
-static int forward_workspace_bytes(const char* who, esahrnet_handle h, int n, int height, int width, Decoder d, size_t* bytes) {
+static int forward_workspace_bytes(const char* who, esahrnet_handle h, int n, int height, int width, Decoder d, size_t* bytes,
+                                   int refine = -1) {
     if (!h || !bytes) return fail("%s: null argument", who);
     if (plan_shape(*h, n, height, width)) return 1;
-    *bytes = h->sp.bytes + kp_scratch(*h, n, height, width, d).total();
+    *bytes = h->sp.bytes + kp_scratch(*h, n, height, width, d, refine).total();
     return 0;
 }
 
@@ -2679,6 +2703,53 @@ int esahrnet_forward_keypoints_candidates(esahrnet_handle h, const void* x_dev, 
     return run_forward(h, x_dev, n, height, width, nullptr, nullptr, ws_dev, ws_bytes, stream, nullptr, &r);
 }
 
+// ---- the candidates refined at their own pixels, in the forward (keypoints_at.hip behind the search) -------------------------
+// What esahrnet_forward_keypoints_candidates_refined and the loader in front of it refuse about the decoder's arguments, in the
+// order include/esahrnet.h gives; `decoder` as the caller passed it.  The texts are those of esahrnet_keypoints_candidates_refined.
+static int check_refined_decoder(const char* who, int decoder) {
+    if (decoder < 0 || decoder > 2) return fail("%s: decoder=%d unknown (0: get_final, 1: get_final2, 2: gaussfit)", who, decoder);
+    return 0;
+}
+static int check_refined_request(const char* who, const Request& r, int decoder) {
+    if (r.M < 1 || r.M > ESAHRNET_MAX_CANDIDATES)
+        return fail("%s: %d candidates per heat-map unsupported (1..%d)", who, r.M, ESAHRNET_MAX_CANDIDATES);
+    if (r.r < 0) return fail("%s: negative nms_radius %d", who, r.r);
+    if (check_refined_decoder(who, decoder)) return 1;
+    if (decoder == 0 && (r.hess || r.fit || r.cov || r.info))
+        return fail("%s: decoder 0 (get_final) writes no hess_dev, fit_dev, cov_dev or info_dev: pass NULL", who);
+    if (decoder == 1 && (r.fit || r.cov || r.info))
+        return fail("%s: decoder 1 (get_final2) writes no fit_dev, cov_dev or info_dev: pass NULL", who);
+    if (decoder == 2 && !r.status) return fail("%s: decoder 2 (gaussfit) needs status_dev", who);
+    if (!(r.cov_floor >= 0.0) || !std::isfinite(r.cov_floor))
+        return fail("%s: cov_floor must be a finite number >= 0 (got %g)", who, r.cov_floor);
+    if ((reinterpret_cast<uintptr_t>(r.cand) | reinterpret_cast<uintptr_t>(r.cidx) | reinterpret_cast<uintptr_t>(r.status)) & 3)
+        return fail("%s: cand_dev, cidx_dev and status_dev must be 4-byte aligned", who);
+    if ((reinterpret_cast<uintptr_t>(r.hess) | reinterpret_cast<uintptr_t>(r.fit) | reinterpret_cast<uintptr_t>(r.cov) |
+         reinterpret_cast<uintptr_t>(r.info)) & 7)
+        return fail("%s: hess_dev, fit_dev, cov_dev and info_dev must be 8-byte aligned", who);
+    return 0;
+}
+
+int esahrnet_keypoints_candidates_refined_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, int decoder,
+                                                                  size_t* bytes) {
+    const char* who = "keypoints_candidates_refined_forward_workspace_bytes";
+    if (!h || !bytes) return fail("%s: null argument", who);
+    if (check_refined_decoder(who, decoder)) return 1;
+    return forward_workspace_bytes(who, h, n, height, width, DEC_CAND, bytes, decoder);
+}
+
+int esahrnet_forward_keypoints_candidates_refined(esahrnet_handle h, const void* x_dev, int n, int height, int width, int candidates,
+                                                  int nms_radius, int decoder, void* cand_dev, void* cidx_dev, void* hess_dev,
+                                                  void* fit_dev, void* status_dev, void* cov_dev, void* info_dev, double cov_floor,
+                                                  void* ws_dev, size_t ws_bytes, esahrnet_stream stream) {
+    const char* who = "forward_keypoints_candidates_refined";
+    const Request r = make_request(DEC_CAND, cand_dev, cidx_dev, hess_dev, fit_dev, status_dev, cov_dev, info_dev, cov_floor,
+                                   candidates, nms_radius, decoder);
+    if (!h || !r.cand) return fail("%s: null argument", who);
+    if (check_refined_request(who, r, decoder)) return 1;
+    return run_forward(h, x_dev, n, height, width, nullptr, nullptr, ws_dev, ws_bytes, stream, nullptr, &r);
+}
+
 // ---- the loader on the device: detector boxes + frames -> crops -> keypoints (frontend.hip) ----------------------------
 // what the loader entries take besides the handle and the decoder's outputs
 struct FramesArgs {
@@ -2697,14 +2768,14 @@ struct FramesArgs {
 static size_t frontend_crop_bytes(int m, int scale) { return ((size_t)m * scale * scale * sizeof(float) + 255) & ~(size_t)255; }
 
 // the loader's workspace: its crops, then the workspace of the forward with decoder `d` on them
-static int frames_workspace_bytes(const char* who, esahrnet_handle h, int m, int scale, Decoder d, size_t* bytes) {
+static int frames_workspace_bytes(const char* who, esahrnet_handle h, int m, int scale, Decoder d, size_t* bytes, int refine = -1) {
     if (h->cfg.cin != 1)
         return fail("%s: the loader makes 1-channel crops (data_load_val.py / data_load4.py); this handle takes %d channels", who,
                     h->cfg.cin);
     if (m <= 0 || scale <= 0 || (long long)m * scale > esa::kFrontendMaxRows)
         return fail("%s: scale %d with %d boxes (both positive, boxes * scale at most %d)", who, scale, m, esa::kFrontendMaxRows);
     size_t fw = 0;
-    if (forward_workspace_bytes(who, h, m, scale, scale, d, &fw)) return 1;
+    if (forward_workspace_bytes(who, h, m, scale, scale, d, &fw, refine)) return 1;
     *bytes = frontend_crop_bytes(m, scale) + fw;
     return 0;
 }
@@ -2723,6 +2794,12 @@ int esahrnet_frames_keypoints_gaussfit_workspace_bytes(esahrnet_handle h, int m,
 int esahrnet_frames_keypoints_candidates_workspace_bytes(esahrnet_handle h, int m, int scale, size_t* bytes) {
     if (!h || !bytes) return fail("frames_keypoints_candidates_workspace_bytes: null argument");
     return frames_workspace_bytes("frames_keypoints_candidates", h, m, scale, DEC_CAND, bytes);
+}
+
+int esahrnet_frames_keypoints_candidates_refined_workspace_bytes(esahrnet_handle h, int m, int scale, int decoder, size_t* bytes) {
+    if (!h || !bytes) return fail("frames_keypoints_candidates_refined_workspace_bytes: null argument");
+    if (check_refined_decoder("frames_keypoints_candidates_refined", decoder)) return 1;
+    return frames_workspace_bytes("frames_keypoints_candidates_refined", h, m, scale, DEC_CAND, bytes, decoder);
 }
 
 // what every loader entry refuses about the frames and the boxes
@@ -2752,7 +2829,10 @@ static int frames_run(const char* who, esahrnet_handle h, const FramesArgs& a, c
     if (run_forward(h, a.ws, a.m, a.scale, a.scale, nullptr, nullptr, static_cast<char*>(a.ws) + head, a.ws_bytes - head, a.stream,
                     nullptr, &r))
         return 1;
-    if (r.decoder == DEC_CAND)                      // a crop's K * M candidate rows: the kp / idx rows of K * M keypoints
+    if (r.decoder == DEC_CAND && r.refine >= 0)     // every output of the refined candidates has K * M rows per crop
+        rc = esa::launch_mark_invalid_refined(valid, a.m, h->cfg.num_keypoints * r.M, r.cand, r.cidx, r.status, r.hess, r.fit, r.cov,
+                                              r.info, st);
+    else if (r.decoder == DEC_CAND)                 // a crop's K * M candidate rows: the kp / idx rows of K * M keypoints
         rc = esa::launch_mark_invalid(valid, a.m, h->cfg.num_keypoints * r.M, r.cand, r.cidx, st);
     else if (r.decoder == DEC_GAUSSFIT)
         rc = esa::launch_mark_invalid_gaussfit_cov(valid, a.m, h->cfg.num_keypoints, r.kp, r.idx, r.fit, r.status, r.hess, r.cov,
@@ -2828,6 +2908,32 @@ int esahrnet_frames_keypoints_candidates(esahrnet_handle h, const void* frames_d
                        crop_boxes_dev, rates_dev, valid_dev, ws_dev, ws_bytes, stream};
     return frames_keypoints("frames_keypoints_candidates", false, h, a, 0,
                             make_candidates_request(cand_dev, cidx_dev, candidates, nms_radius));
+}
+
+// esahrnet_frames_keypoints_candidates with the refined candidates' forward in the place of the plain one.  The refusals sit
+// where that entry has them: the frames' and boxes' arguments, then the decoder's own, then the handle's commit
+int esahrnet_frames_keypoints_candidates_refined(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                                                 int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m,
+                                                 int scale, int rule, float mean, float stdv, int candidates, int nms_radius,
+                                                 int decoder, void* cand_dev, void* cidx_dev, void* hess_dev, void* fit_dev,
+                                                 void* status_dev, void* cov_dev, void* info_dev, double cov_floor,
+                                                 void* crop_boxes_dev, void* rates_dev, void* valid_dev, void* ws_dev, size_t ws_bytes,
+                                                 esahrnet_stream stream) {
+    const char* who = "frames_keypoints_candidates_refined";
+    const FramesArgs a{frames_dev, nframes, frame_h, frame_w, pixel_format, det_boxes_dev, frame_idx_dev, m, scale, rule, mean, stdv,
+                       crop_boxes_dev, rates_dev, valid_dev, ws_dev, ws_bytes, stream};
+    const Request r = make_request(DEC_CAND, cand_dev, cidx_dev, hess_dev, fit_dev, status_dev, cov_dev, info_dev, cov_floor,
+                                   candidates, nms_radius, decoder);
+    if (!h || !a.frames || !a.det_boxes || !r.cand || !a.crop_boxes || !a.rates || !a.valid || !a.ws)
+        return fail("%s: null argument", who);
+    if (check_frames_args(who, a)) return 1;
+    if (check_refined_request(who, r, decoder)) return 1;
+    if (!h->committed) return fail("%s: esahrnet_commit has not been called", who);
+    size_t need = 0;
+    if (esahrnet_frames_keypoints_candidates_refined_workspace_bytes(h, a.m, a.scale, decoder, &need)) return 1;
+    if (a.ws_bytes < need) return fail("%s: workspace too small (%zu < %zu)", who, a.ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(a.ws) & 255) return fail("%s: workspace must be 256-byte aligned", who);
+    return frames_run(who, h, a, r);
 }
 
 // ---- keypoints -> correspondences for the pose solver (correspond.hip) --------------------------------------------------

@@ -27,8 +27,8 @@ import torch.nn as nn
 
 from . import _lib, crops
 from .fold import fold_conv
-from .inference import (check_cov_floor, check_refine, check_weights, pack_correspondences, record_fields, record_outputs,
-                        record_views)
+from .inference import (_at_returns, _check_at_outputs, check_cov_floor, check_refine, check_weights, pack_correspondences,
+                        record_fields, record_outputs, record_views)
 
 logger = logging.getLogger(__name__)
 BN_MOMENTUM = 0.01           # models/seg_hrnet.py:23 (irrelevant at inference, kept for parity)
@@ -255,33 +255,61 @@ class HighResolutionNet(nn.Module):
         kp, fit, status, hess, _ = self._rt.forward_gaussfit(self, x0, bool(return_fit), False)
         return (kp, fit, status, hess) if return_fit else (kp, status, hess)
 
-    def candidates(self, x0: torch.Tensor, candidates: int = 3, nms_radius: int = 6, return_index: bool = False):
+    def candidates(self, x0: torch.Tensor, candidates: int = 3, nms_radius: int = 6, return_index: bool = False,
+                   refine: str = "get_final", return_hessian: bool = False, return_fit: bool = False, return_cov: bool = False,
+                   cov_floor: float = 1e-6):
         """The forward with the candidate decoder in place of its last launch (include/esahrnet.h
         esahrnet_forward_keypoints_candidates): -> cand f32 cuda [N,K,M,3] = (x, y, peak), the M = `candidates` (1..4) best peaks of
         every heat-map, `nms_radius` pixels apart, best first; with return_index=True (cand, cidx int32 [N,K,M]).  Bit-identical to
         inference.heatmaps_to_candidates(net(x), candidates, nms_radius, return_index), without heat-maps in caller memory (they
-        live in the workspace: the runner-up rule needs whole planes)."""
+        live in the workspace: the runner-up rule needs whole planes).
+        refine="get_final2" / "gaussfit" and return_hessian / return_fit / return_cov (esahrnet_forward_keypoints_candidates_refined):
+        every candidate refined by that decoder at its own pixel, still in the one call; -> the tuple
+        inference.heatmaps_to_candidates(net(x), ...) returns for the same keywords, in the same order and bit for bit."""
         self._inference_only()
-        cand, cidx = self._rt.forward_candidates(self, x0, int(candidates), int(nms_radius), bool(return_index))
-        return (cand, cidx) if return_index else cand
+        decoder, cov_floor = _check_at_outputs(refine, return_hessian, return_fit, return_cov, cov_floor)
+        if decoder == 0:                    # (get_final takes none of the optional outputs: _check_at_outputs has refused them)
+            cand, cidx = self._rt.forward_candidates(self, x0, int(candidates), int(nms_radius), bool(return_index))
+            return (cand, cidx) if return_index else cand
+        cand, cidx, o = self._rt.forward_candidates_refined(self, x0, int(candidates), int(nms_radius), bool(return_index), decoder,
+                                                            bool(return_hessian), bool(return_fit), bool(return_cov), cov_floor)
+        out = (cand, *((cidx,) if return_index else ()), *_at_returns(o, return_hessian, return_fit, return_cov))
+        return out if len(out) > 1 else cand
 
     def frames_to_candidates(self, frames: torch.Tensor, det_boxes, frame_idx=None, scale: int = 256, rule: str = "val",
-                             candidates: int = 3, nms_radius: int = 6, mean=None, std: float = crops.STD, pixel_format=None):
+                             candidates: int = 3, nms_radius: int = 6, mean=None, std: float = crops.STD, pixel_format=None,
+                             refine: str = "get_final", return_hessian: bool = False, return_fit: bool = False,
+                             return_cov: bool = False, cov_floor: float = 1e-6):
         """frames_to_keypoints with the candidate decoder (include/esahrnet.h esahrnet_frames_keypoints_candidates): box rule,
         crops, forward and the M best peaks of every heat-map in one library call.  -> (cand f32 [m,K,M,3], crop_boxes int32 [m,4],
         rates f64 [m], valid int32 [m]), all on the device; cand equals crops.crop_batch -> net.candidates(x, candidates,
-        nms_radius) bit for bit, except that the rows of an invalid crop (valid == 0) are NaN."""
-        return self._frames_to_candidates(frames, det_boxes, frame_idx, scale, rule, candidates, nms_radius, mean, std,
-                                          pixel_format)[:4]
+        nms_radius) bit for bit, except that the rows of an invalid crop (valid == 0) are NaN.
+        refine="get_final2" / "gaussfit" (esahrnet_frames_keypoints_candidates_refined): every candidate refined at its own pixel;
+        the outputs asked for follow in net.candidates' order, [fit f64 [m,K,M,8], status int32 [m,K,M]], [hess f64 [m,K,M,3]],
+        [cov, info f64 [m,K,M,3]], equal to crops.crop_batch -> net.candidates(x, ..., refine=...) bit for bit; in the rows of an
+        invalid crop the f64 outputs are NaN and status is -1."""
+        out = self._frames_to_candidates(frames, det_boxes, frame_idx, scale, rule, candidates, nms_radius, mean, std, pixel_format,
+                                         refine, return_hessian, return_fit, return_cov, cov_floor)
+        if refine == "get_final":
+            return out[:4]
+        rest = list(out[6:])            # record_outputs' order: [cand_fit, cand_status,] cand_hess[, cand_cov, cand_info]
+        fit = (rest.pop(0), rest.pop(0)) if refine == "gaussfit" else ()
+        return (*out[:4], *(fit if return_fit else ()), *(rest[:1] if return_hessian else ()), *(rest[1:] if return_cov else ()))
 
-    def _frames_to_candidates(self, frames, det_boxes, frame_idx, scale, rule, candidates, nms_radius, mean, std, pixel_format):
+    def _frames_to_candidates(self, frames, det_boxes, frame_idx, scale, rule, candidates, nms_radius, mean, std, pixel_format,
+                              refine="get_final", return_hessian=False, return_fit=False, return_cov=False, cov_floor=1e-6):
         """frames_to_candidates, plus (cidx int32 [m,K,M], packed): every output is a view of `packed` (one uint8 buffer,
         inference.packed_layout(m, K, candidates=M)), so a caller that needs them on the host fetches them with one copy; cidx is
-        -1 in the rows of an invalid crop."""
+        -1 in the rows of an invalid crop.  refine="get_final2" / "gaussfit": `packed` is the refined candidates' record
+        (inference.record_fields(K, "candidates_refined", refine == "gaussfit", return_cov, M)) and its decoder outputs follow it as
+        inference.record_outputs orders them: ([cand_fit, cand_status,] cand_hess[, cand_cov, cand_info]); the record holds the
+        Hessians (and a fit's parameters and status) whether or not the caller asked for them."""
         self._inference_only()
+        decoder, cov_floor = _check_at_outputs(refine, return_hessian, return_fit, return_cov, cov_floor)
         rule_n, fmt, m, mean = self._loader_args(frames, det_boxes, frame_idx, rule, mean, pixel_format)
+        refined = None if decoder == 0 else (decoder, cov_floor if return_cov else None)
         return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
-                                         0, cand=(int(candidates), int(nms_radius)))
+                                         0, cand=(int(candidates), int(nms_radius)), refined=refined)
 
     def _frames_to_keypoints(self, frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format, cov_floor=None):
         """frames_to_keypoints, plus (idx int32 [m,K], packed): every output is a view of `packed` (one uint8 buffer), so a
@@ -486,6 +514,11 @@ class _Runtime:
         "final2": ("final2", "esahrnet_keypoints_final2_forward_workspace_bytes", _crops),
         "gaussfit": ("gaussfit", "esahrnet_keypoints_gaussfit_forward_workspace_bytes", _crops),
         "candidates": ("candidates", "esahrnet_keypoints_candidates_forward_workspace_bytes", _crops),
+        # (the refined candidates: the key's `keep` is ("refined", decoder), the decoder the query's last argument)
+        "candidates_refined": ("candidates", "esahrnet_keypoints_candidates_refined_forward_workspace_bytes",
+                               lambda n, hh, ww, keep: (n, hh, ww, keep[1])),
+        "frames_candidates_refined": ("frames", "esahrnet_frames_keypoints_candidates_refined_workspace_bytes",
+                                      lambda n, hh, ww, keep: (n, hh, keep[1])),
         "frames": ("frames", "esahrnet_frames_keypoints_workspace_bytes", lambda n, hh, ww, keep: (n, hh, 0)),
         "frames_candidates": ("frames", "esahrnet_frames_keypoints_candidates_workspace_bytes", lambda n, hh, ww, keep: (n, hh)),
         "frames_final2": ("frames", "esahrnet_frames_keypoints_workspace_bytes", lambda n, hh, ww, keep: (n, hh, 1)),
@@ -677,10 +710,11 @@ class _Runtime:
                 lk = self.dev_locks.setdefault(index, threading.RLock())
         return lk
 
-    def _enqueue(self, module, x0, kind, entry, outputs, keep=False):
+    def _enqueue(self, module, x0, kind, entry, outputs, keep=False, ws_key=None):
         """One forward entry `h, x, n, h, w, <outputs>, ws, ws_bytes, stream` on the current stream of x's device, with the
         workspace of `kind`.  outputs(h, n, hh, ww, new) allocates what the entry writes (new(dtype, *shape): an empty tensor
-        on that device) and returns the entry's output arguments in order: tensors, None, plain numbers.  -> those outputs."""
+        on that device) and returns the entry's output arguments in order: tensors, None, plain numbers.  -> those outputs.
+        ws_key: what the workspace kind's size query and cache key take in the place of `keep`."""
         x = self._check_input(module, x0)
         n, _, hh, ww = x.shape
         dev = x.device
@@ -690,7 +724,7 @@ class _Runtime:
         with self._device_lock(dev.index):
             h = self._handle_for(module, dev)
             _lib.check(self.lib.esahrnet_set_debug_keep(h, 1 if keep else 0))
-            ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, n, hh, ww, keep, kind=kind)
+            ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, n, hh, ww, keep if ws_key is None else ws_key, kind=kind)
             outs = outputs(h, n, hh, ww, lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev))
             args = (h, x.data_ptr(), n, hh, ww, *[o.data_ptr() if isinstance(o, torch.Tensor) else o for o in outs], ws_ptr, ws_bytes,
                     C.c_void_p(ts.cuda_stream))
@@ -760,8 +794,26 @@ class _Runtime:
                                                                     new(torch.int32, n, k, mm) if want_index else None))
         return cand, cidx
 
+    def forward_candidates_refined(self, module, x0, candidates, nms_radius, want_index, decoder, want_hessian, want_fit, want_cov,
+                                   cov_floor):
+        """esahrnet_forward_keypoints_candidates_refined: (cand f32 [N,K,M,3], cidx int32 [N,K,M] or None, the optional outputs as
+        inference._at_outputs names them: fit, status, hess, cov, info, each [N,K,M] + its own shape or None).  Without want_index
+        the candidates' pixels stay in the workspace."""
+        k = module._k
+        mm = min(max(candidates, 1), _lib.MAX_CANDIDATES)
+
+        def outputs(h, n, hh, ww, new):
+            slot = lambda on, dt, *tail: new(dt, n, k, mm, *tail) if on else None          # noqa: E731
+            return (candidates, nms_radius, decoder, new(torch.float32, n, k, mm, 3), slot(want_index, torch.int32),
+                    slot(want_hessian, torch.float64, 3), slot(want_fit, torch.float64, 8), slot(decoder == 2, torch.int32),
+                    slot(want_cov, torch.float64, 3), slot(want_cov, torch.float64, 3), float(cov_floor))
+
+        _, _, _, cand, cidx, hess, fit, status, cov, info, _ = self._enqueue(
+            module, x0, "candidates_refined", "esahrnet_forward_keypoints_candidates_refined", outputs, ws_key=("refined", decoder))
+        return cand, cidx, {"fit": fit, "status": status, "hess": hess, "cov": cov, "info": info}
+
     def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None, cov=None,
-                         cand=None):
+                         cand=None, refined=None):
         """esahrnet_frames_keypoints (arguments already checked by crops.check_device_loader_args).  The outputs are views
         of one packed buffer (inference.record_fields / record_views), returned as inference.record_outputs orders them: rates f64
         [m] | kp f32 [m,K,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,K]; decoder 2, the Gaussian fit, also fit,
@@ -772,9 +824,14 @@ class _Runtime:
         `packed`.  cov = cov_floor (decoder 2 only): esahrnet_frames_keypoints_gaussfit_cov; cov and info ride in `packed` behind
         hess and are returned last, and the correspondences, if asked for with mode 1, take info in hess' place.  cand = (M,
         nms_radius) (decoder 0, no corr): esahrnet_frames_keypoints_candidates instead -> (cand f32 [m,K,M,3], boxes, rates, valid,
-        cidx int32 [m,K,M], packed), views of the candidates record (inference.record_fields(K, "candidates", candidates=M))."""
+        cidx int32 [m,K,M], packed), views of the candidates record (inference.record_fields(K, "candidates", candidates=M)).
+        refined = (decoder 1 or 2 of esahrnet_keypoints_at, cov_floor or None) beside cand:
+        esahrnet_frames_keypoints_candidates_refined instead, on the record of kind "candidates_refined"; its decoder outputs follow
+        `packed` (inference.record_outputs)."""
         if cand is not None and (decoder != 0 or corr is not None or cov is not None):
             raise ValueError("the candidates belong to the get_final decoder, without correspondences")
+        if refined is not None and cand is None:
+            raise ValueError("a refined decoder belongs to the candidates")
         if cov is not None and decoder != 2:
             raise ValueError("the covariance of the fitted centre belongs to the Gaussian-fit decoder")
         if module._cin != 1:
@@ -792,8 +849,11 @@ class _Runtime:
         with torch.cuda.device(dev):
             det = crops.to_device_int32(det_boxes, dev)
             fidx = None if frame_idx is None else crops.to_device_int32(frame_idx, dev)
-            fields = record_fields(k, "keypoints" if cand is None else "candidates", decoder == 2, cov is not None,
-                                   None if cand is None else cand[0])
+            if refined is not None:
+                fields = record_fields(k, "candidates_refined", refined[0] == 2, refined[1] is not None, cand[0])
+            else:
+                fields = record_fields(k, "keypoints" if cand is None else "candidates", decoder == 2, cov is not None,
+                                       None if cand is None else cand[0])
             packed = torch.empty(m * sum(b for _, b in fields), dtype=torch.uint8, device=dev)
             views = record_views(packed, m, k, fields)
             out = record_outputs(views, packed)
@@ -809,7 +869,14 @@ class _Runtime:
                 loader = (h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m,
                           scale, rule, mean, std)
                 placed = (p["boxes"], p["rates"], p["valid"])
-                if cand is not None:
+                if refined is not None:
+                    ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, ("refined", refined[0]),
+                                                           kind="frames_candidates_refined")
+                    _lib.check(self.lib.esahrnet_frames_keypoints_candidates_refined(
+                        *loader, int(cand[0]), int(cand[1]), refined[0], p["cand"], p["cidx"], p["cand_hess"], p.get("cand_fit"),
+                        p.get("cand_status"), p.get("cand_cov"), p.get("cand_info"), float(refined[1] or 0.0), *placed, ws_ptr,
+                        ws_bytes, stream))
+                elif cand is not None:
                     # ("candidates" as the cache key's `keep`: it only keeps this workspace apart from the other loader kinds)
                     ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, "candidates", kind="frames_candidates")
                     _lib.check(self.lib.esahrnet_frames_keypoints_candidates(*loader, int(cand[0]), int(cand[1]), p["cand"],

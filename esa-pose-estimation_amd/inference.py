@@ -344,7 +344,7 @@ def check_weights(weights, refine="get_final2"):
     return int(weights != "peak")
 
 
-RECORD_KINDS = ("keypoints", "correspondences", "candidates")
+RECORD_KINDS = ("keypoints", "correspondences", "candidates", "candidates_refined")
 # THE description of the packed records; every layout, view and exchange below and in hrnet / parallel / pipeline derives from it.
 # Element type and trailing shape of every field (k = keypoints per crop, M = candidates per keypoint) ...
 _RECORD_TYPES = {"rates": (torch.float64, ()), "fit": (torch.float64, ("k", 8)), "hess": (torch.float64, ("k", 3)),
@@ -352,13 +352,20 @@ _RECORD_TYPES = {"rates": (torch.float64, ()), "fit": (torch.float64, ("k", 8)),
                  "boxes": (torch.int32, (4,)), "valid": (torch.int32, ()), "idx": (torch.int32, ("k",)),
                  "status": (torch.int32, ("k",)), "pts": (torch.float64, ("k", 2)), "w": (torch.float64, ("k", 3)),
                  "count": (torch.int32, ()), "order": (torch.int32, ("k",)), "cand": (torch.float32, ("k", "M", 3)),
-                 "cidx": (torch.int32, ("k", "M"))}
+                 "cidx": (torch.int32, ("k", "M")),
+                 # the refined candidates' outputs, one row per candidate: names of their own, since their shapes carry M
+                 "cand_fit": (torch.float64, ("k", "M", 8)), "cand_hess": (torch.float64, ("k", "M", 3)),
+                 "cand_cov": (torch.float64, ("k", "M", 3)), "cand_info": (torch.float64, ("k", "M", 3)),
+                 "cand_status": (torch.int32, ("k", "M"))}
 # ... and the fields of each record in memory order (the f64 parts first: 8-byte aligned); fit, hess and status are there with
-# gaussfit only, cov and info with cov only
+# gaussfit only, cov and info with cov only (cand_fit, cand_status, cand_cov and cand_info likewise; cand_hess is always there)
 _RECORD_ORDER = {"keypoints": ("rates", "fit", "hess", "cov", "info", "kp", "boxes", "valid", "idx", "status"),
                  "correspondences": ("pts", "w", "count", "order"),
-                 "candidates": ("rates", "cand", "boxes", "valid", "cidx")}
-_RECORD_SWITCH = {"fit": "gaussfit", "hess": "gaussfit", "status": "gaussfit", "cov": "cov", "info": "cov"}
+                 "candidates": ("rates", "cand", "boxes", "valid", "cidx"),
+                 "candidates_refined": ("rates", "cand_fit", "cand_hess", "cand_cov", "cand_info", "cand", "boxes", "valid", "cidx",
+                                        "cand_status")}
+_RECORD_SWITCH = {"fit": "gaussfit", "hess": "gaussfit", "status": "gaussfit", "cov": "cov", "info": "cov",
+                  "cand_fit": "gaussfit", "cand_status": "gaussfit", "cand_cov": "cov", "cand_info": "cov"}
 _NUMPY_TYPES = {torch.float64: np.dtype(np.float64), torch.float32: np.dtype(np.float32), torch.int32: np.dtype(np.int32)}
 
 
@@ -375,7 +382,10 @@ def record_fields(k: int, kind: str, gaussfit: bool = False, cov: bool = False, 
     """The fields of a packed record in memory order, as ((name, bytes per crop), ...): kind="keypoints" the buffer of
     net._frames_to_keypoints (rates | [fit | hess | [cov | info]] | kp | boxes | valid | idx | [status]), kind="correspondences"
     the buffer of pack_correspondences (pts | w | count | order), kind="candidates" the buffer of net._frames_to_candidates with
-    candidates=M (rates | cand | boxes | valid | cidx).  A record is field-major, so field f of m crops takes m * bytes and
+    candidates=M (rates | cand | boxes | valid | cidx), kind="candidates_refined" the buffer of net._frames_to_candidates with a
+    refine other than "get_final" (rates | [cand_fit] | cand_hess | [cand_cov | cand_info] | cand | boxes | valid | cidx |
+    [cand_status]: the decoder's outputs for every candidate, f64 first; gaussfit=True is refine="gaussfit", False "get_final2").
+    A record is field-major, so field f of m crops takes m * bytes and
     starts at m * (the bytes of the fields in front of it); every size is a multiple of 4.  This is the description the views
     (record_views), the offsets (packed_layout) and the exchange of a sharded batch (parallel.gather_records,
     esahrnet_gather_records) work from."""
@@ -389,14 +399,14 @@ def record_fields(k: int, kind: str, gaussfit: bool = False, cov: bool = False, 
     if cov and not gaussfit:
         raise ValueError("cov=True belongs to gaussfit=True")
     mm = 1
-    if kind == "candidates":
-        if gaussfit:
+    if kind in ("candidates", "candidates_refined"):
+        if gaussfit and kind == "candidates":
             raise ValueError("candidates=M belongs to the get_final decoder (gaussfit=False)")
         if candidates is None or not 1 <= int(candidates) <= _lib.MAX_CANDIDATES:
             raise ValueError(f"candidates must be in 1..{_lib.MAX_CANDIDATES}, got {candidates!r}")
         mm = int(candidates)
     elif candidates is not None:
-        raise ValueError("candidates=M belongs to kind='candidates'")
+        raise ValueError("candidates=M belongs to kind='candidates'")     # (and to 'candidates_refined')
     on = {"gaussfit": gaussfit, "cov": cov, None: True}
     return tuple((name, _field_bytes(name, k, mm)) for name in _RECORD_ORDER[kind] if on[_RECORD_SWITCH.get(name)])
 
@@ -421,22 +431,28 @@ def record_views(packed, m: int, k: int, fields):
 
 def record_outputs(views, packed):
     """The views of a keypoint record (or of a candidates record: cand and cidx in kp's and idx' places) -> what
-    net._frames_to_keypoints returns: (kp, boxes, rates, valid, idx, packed[, fit, status, hess[, cov, info]])."""
+    net._frames_to_keypoints returns: (kp, boxes, rates, valid, idx, packed[, fit, status, hess[, cov, info]]); of a refined
+    candidates' record (cand, boxes, rates, valid, cidx, packed, [cand_fit, cand_status,] cand_hess[, cand_cov, cand_info])."""
     v = views
     rows, index = ("kp", "idx") if "kp" in v else ("cand", "cidx")
     return (v[rows], v["boxes"], v["rates"], v["valid"], v[index], packed,
-            *(v[n] for n in ("fit", "status", "hess", "cov", "info") if n in v))
+            *(v[n] for n in ("fit", "status", "hess", "cov", "info", "cand_fit", "cand_status", "cand_hess", "cand_cov", "cand_info")
+              if n in v))
 
 
-def packed_layout(m: int, k: int, gaussfit: bool = False, cov: bool = False, candidates=None):
+def packed_layout(m: int, k: int, gaussfit: bool = False, cov: bool = False, candidates=None, kind=None):
     """The packed buffer of net.frames_to_keypoints' outputs: name -> (offset, bytes), the fields of record_fields(k, "keypoints",
     gaussfit, cov) for m crops: rates f64 [m] | kp f32 [m,k,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,k]; with
     gaussfit the decoder's f64 outputs come right behind rates (8-byte aligned) and its status last: rates | fit f64 [m,k,8] |
     hess f64 [m,k,3] | kp | crop_boxes | valid | idx | status int32 [m,k]; with cov (gaussfit only) cov f64 [m,k,3] | info f64
     [m,k,3] follow hess.  "total" -> (0, bytes of the buffer).  candidates=M (net.frames_to_candidates; not with gaussfit), the
-    fields of record_fields(k, "candidates", candidates=M): rates | cand f32 [m,k,M,3] | crop_boxes | valid | cidx int32 [m,k,M]."""
+    fields of record_fields(k, "candidates", candidates=M): rates | cand f32 [m,k,M,3] | crop_boxes | valid | cidx int32 [m,k,M].
+    kind (default: "keypoints", or "candidates" with candidates=M) names another record of record_fields, "candidates_refined" among
+    them."""
     out, off = {}, 0
-    for name, b in record_fields(k, "keypoints" if candidates is None else "candidates", gaussfit, cov, candidates):
+    if kind is None:
+        kind = "keypoints" if candidates is None else "candidates"
+    for name, b in record_fields(k, kind, gaussfit, cov, candidates):
         out[name] = (off, m * b)
         off += m * b
     out["total"] = (0, off)

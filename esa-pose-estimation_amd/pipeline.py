@@ -215,7 +215,7 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
 def candidate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, candidates: int = 3, refine: str = "get_final2",
                     weights: str = "hessian", nms_radius: int = 6, min_ratio: float = 0.3, scale: int = 256, thresh: float = 0.8,
                     min_k: int = 24, on_fail: str = "raise", return_report: bool = False, max_rms_px=None, min_inliers=None,
-                    cov_floor: float = 1e-6, threads: int = 0):
+                    cov_floor: float = 1e-6, threads: int = 0, candidates_path: str = "heatmaps", frame_idx=None, rule: str = "val"):
     """Runner-up repair AND anisotropic weights, the combination estimate_poses refuses (its candidates=M is get_final with peak
     weights; its weights="hessian" / "covariance" know the arg-max only).  frames, bboxes, kp3d, K, scale, thresh, min_k, on_fail,
     the report and the gates as in estimate_poses -> list of (q, t) per image[, report with .used and .rescued].
@@ -225,27 +225,49 @@ def candidate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, candidates: int 
     refine="gaussfit"), ONE device->host copy of candidates and weights, then pnp.candidates_to_pose_batch(..., hess=...): the
     repair step of estimate_poses(candidates=M), with every point, a swapped-in runner-up included, weighed by
     rate * (-H)^(1/2) in the refinement.  weights="peak" passes no Hessian; with refine="get_final" that is
-    estimate_poses(..., candidates=M), bit for bit.  The forward-fused and device-loader forms, device_select and distributed are
-    not built for this combination."""
+    estimate_poses(..., candidates=M), bit for bit.
+    candidates_path says where the candidates are decoded, as in estimate_poses: "heatmaps" (default) as above; "fused": host
+    crops, then net.candidates(x, candidates, nms_radius, refine=refine, ...), search and refinement inside the forward's one
+    library call, no heat-map tensor in caller memory; "loader": net._frames_to_candidates(..., refine=refine) does the box rule,
+    the crops, the forward and the refined candidates in one library call and ONE device->host copy of its packed record
+    (inference.record_fields(K, "candidates_refined", ...)) feeds the same solve with the loader's boxes and rates -- bboxes are
+    integers, frame_idx and rule are accepted, and a crop the loader could not make has the NaN pose: on_fail applies, its report
+    row is that of "fewer than 4" with n = 0.  The poses, the report, .used and .rescued are those of "heatmaps", bit for bit.
+    device_select and distributed are not built for this combination."""
     inference.check_refine(refine)
     mode = inference.check_weights(weights, refine)
     cov_floor = inference.check_cov_floor(cov_floor)
+    if candidates_path not in CANDIDATES_PATHS:
+        raise ValueError(f"candidates_path must be one of {CANDIDATES_PATHS}, got {candidates_path!r}")
+    if candidates_path != "loader" and (frame_idx is not None or rule != "val"):
+        raise ValueError("frame_idx and rule belong to candidates_path='loader' (crops.crop_batch: one val box per frame)")
     want = return_report or max_rms_px is not None or min_inliers is not None
-    x, boxes, rates = crops.crop_batch(frames, bboxes, scale)
     ask = {"return_hessian": weights == "hessian", "return_cov": weights == "covariance", "cov_floor": cov_floor}
-    with torch.no_grad():
-        out = inference.heatmaps_to_candidates(net(x), candidates, nms_radius, refine=refine, **ask)
-    cand, hess = (out[0], out[-1]) if mode else (out, None)            # (return_cov: cov, info — info is what weighs)
-    if mode:                                            # the only device->host copy: one buffer, hess | cand (the f64 part first)
-        n, k, mm = cand.shape[:3]
-        host = torch.cat([hess.reshape(-1).view(torch.uint8), cand.reshape(-1).view(torch.uint8)]).cpu().numpy()
-        hess = host[:n * k * mm * 24].view(np.float64).reshape(n, k, mm, 3)
-        cand = host[n * k * mm * 24:].view(np.float32).reshape(n, k, mm, 3)
+
+    def solve(cand, boxes, rates, hess):
+        q, t, _, *rep = pnp.candidates_to_pose_batch(cand, kp3d, np.asarray(K, np.float64), [(b[0], b[1]) for b in boxes], rates,
+                                                     thresh, min_k, min_ratio, threads, report=want, hess=hess)
+        return [(q[i], t[i]) for i in range(len(boxes))], rep[0] if want else None
+
+    if candidates_path == "loader":
+        poses, rep = _loader_refined_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, refine,
+                                                      weights, ask, solve)
     else:
-        cand = cand.cpu().numpy()
-    q, t, _, *rep = pnp.candidates_to_pose_batch(cand, kp3d, np.asarray(K, np.float64), [(b[0], b[1]) for b in boxes], rates, thresh,
-                                                 min_k, min_ratio, threads, report=want, hess=hess)
-    poses, rep = [(q[i], t[i]) for i in range(len(boxes))], rep[0] if want else None
+        x, boxes, rates = crops.crop_batch(frames, bboxes, scale)
+        with torch.no_grad():
+            if candidates_path == "fused":
+                out = net.candidates(x, candidates, nms_radius, refine=refine, **ask)
+            else:
+                out = inference.heatmaps_to_candidates(net(x), candidates, nms_radius, refine=refine, **ask)
+        cand, hess = (out[0], out[-1]) if mode else (out, None)        # (return_cov: cov, info — info is what weighs)
+        if mode:                                        # the only device->host copy: one buffer, hess | cand (the f64 part first)
+            n, k, mm = cand.shape[:3]
+            host = torch.cat([hess.reshape(-1).view(torch.uint8), cand.reshape(-1).view(torch.uint8)]).cpu().numpy()
+            hess = host[:n * k * mm * 24].view(np.float64).reshape(n, k, mm, 3)
+            cand = host[n * k * mm * 24:].view(np.float32).reshape(n, k, mm, 3)
+        else:
+            cand = cand.cpu().numpy()
+        poses, rep = solve(cand, boxes, rates, hess)
     if want:
         poses = _gated_poses(poses, rep, max_rms_px, min_inliers)
     poses = _checked_poses(poses, on_fail)
@@ -314,6 +336,20 @@ def _loader_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candid
     m, k, mm = out[0].shape[:3]
     v = _fetch(out[5], m, k, inference.record_fields(k, "candidates", candidates=mm))
     return _solve_valid_crops(v["cand"], v, solve)
+
+
+def _loader_refined_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, refine, weights, ask, solve):
+    """candidate_poses with candidates_path="loader": solve(cand, boxes, rates, hess or None) on the fetched record."""
+    with torch.no_grad():
+        out = net._frames_to_candidates(frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, None, crops.STD, None,
+                                        refine=refine, **ask)
+    m, k, mm = out[0].shape[:3]
+    kind = "candidates" if refine == "get_final" else "candidates_refined"
+    v = _fetch(out[5], m, k, inference.record_fields(k, kind, refine == "gaussfit", weights == "covariance", mm))
+    hess = {"peak": None, "hessian": v.get("cand_hess"), "covariance": v.get("cand_info")}[weights]
+    if hess is not None:                # (the rows of an invalid crop are NaN: zeros go in, like its candidates)
+        hess = np.where((v["valid"] == 0).reshape(-1, 1, 1, 1), 0.0, hess)
+    return _solve_valid_crops(v["cand"], v, lambda rows, boxes, rates: solve(rows, boxes, rates, hess))
 
 
 def _host_crops_poses(net, frames, bboxes, frame_idx, scale, rule, refine, distributed, keypoints_only, candidates, nms_radius,

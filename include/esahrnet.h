@@ -580,6 +580,54 @@ int esahrnet_keypoints_candidates_refined(const void* heat_dev, int n, int k, in
                                           void* status_dev, void* cov_dev, void* info_dev, double cov_floor, void* ws_dev,
                                           size_t ws_bytes, esahrnet_stream stream);
 
+/* ---- the refined candidates in the forward and behind the loader (csrc/plan.hip) ------------------------------
+ * esahrnet_forward_keypoints_candidates_refined: the forward with its heat-maps written into the workspace, as
+ * esahrnet_forward_keypoints_candidates does, then esahrnet_keypoints_candidates_refined on them: the search of form -1, then the
+ * kernels of esahrnet_keypoints_at with at_dev = the candidates' pixels and kp_dev = cand_dev.  The outputs have the shapes and
+ * meanings they have there (cand_dev f32 [n][K][M][3], cidx_dev int32 [n][K][M], hess_dev / cov_dev / info_dev f64 [n][K][M][3],
+ * fit_dev f64 [n][K][M][8], status_dev int32 [n][K][M]) and every one is bit-identical to esahrnet_forward followed by
+ * esahrnet_keypoints_candidates_refined on its heat-maps.  cidx_dev may be NULL here (the stand-alone entry requires it): the
+ * pixels then stay in the workspace and the other outputs keep their bits.  decoder 0: the bits of
+ * esahrnet_forward_keypoints_candidates, and nothing more is launched unless status_dev is given.
+ * Workspace: esahrnet_keypoints_candidates_refined_forward_workspace_bytes(decoder) =
+ *     esahrnet_keypoints_candidates_forward_workspace_bytes
+ *   + n * K * ESAHRNET_MAX_CANDIDATES * 4 bytes padded to 256 (the pixels; always, the query knows no M)
+ *   + decoder 1 only: esahrnet_keypoints_at_workspace_bytes(n, K, height, width, 1);
+ * 256-byte aligned; the result does not depend on what it held on entry.  Allocates nothing, does not synchronise, may be captured
+ * into a graph; every output is written whole.  No heat-map reaches caller memory.
+ * Refused, in this order and before anything is enqueued (a handle without weights or a device answers): a NULL handle or
+ * cand_dev; M outside 1..ESAHRNET_MAX_CANDIDATES; r < 0; a decoder outside 0..2; an output the decoder does not write that is not
+ * NULL (decoder 0: hess_dev, fit_dev, cov_dev, info_dev; decoder 1: fit_dev, cov_dev, info_dev); decoder 2 without status_dev; a
+ * cov_floor that is negative or not finite; cand_dev, cidx_dev or status_dev not 4-byte aligned; hess_dev, fit_dev, cov_dev or
+ * info_dev not 8-byte aligned; then those of esahrnet_forward_keypoints (NULL x_dev or ws_dev, a handle without esahrnet_commit, the
+ * shape, the workspace's size and alignment).  The query refuses a NULL argument, then a decoder outside 0..2, then the shape. */
+int esahrnet_keypoints_candidates_refined_forward_workspace_bytes(esahrnet_handle h, int n, int height, int width, int decoder,
+                                                                  size_t* bytes);
+int esahrnet_forward_keypoints_candidates_refined(esahrnet_handle h, const void* x_dev, int n, int height, int width, int candidates,
+                                                  int nms_radius, int decoder, void* cand_dev, void* cidx_dev, void* hess_dev,
+                                                  void* fit_dev, void* status_dev, void* cov_dev, void* info_dev, double cov_floor,
+                                                  void* ws_dev, size_t ws_bytes, esahrnet_stream stream);
+
+/* esahrnet_frames_keypoints_candidates_refined: esahrnet_frames_keypoints_candidates with the entry above in the place of
+ * esahrnet_forward_keypoints_candidates: esahrnet_boxes -> esahrnet_crops_ex into the head of the workspace -> the refined
+ * candidates' forward on the rest.  The rows of a valid crop are bit-identical to the calls it is built from; the rows of an
+ * invalid crop (valid == 0: an empty box, a frame index out of range) are NaN in cand_dev and in every f64 output and -1 in cidx_dev
+ * and status_dev (mark_invalid_refined_kernel; NULL outputs are not written).  ws_dev:
+ * esahrnet_frames_keypoints_candidates_refined_workspace_bytes(decoder) bytes = the crops (m * scale * scale * 4 padded to 256) plus
+ * the entry above's workspace for m crops of scale x scale; 256-byte aligned.  The graph-capture contract is
+ * esahrnet_frames_keypoints'.  Refused, before anything is enqueued: a NULL handle, frames, boxes, cand_dev, crop_boxes_dev,
+ * rates_dev, valid_dev or ws_dev; the frames' and boxes' arguments as esahrnet_frames_keypoints refuses them; then the entry above's
+ * own checks from M to the alignment of the outputs; then a handle without esahrnet_commit; a handle that takes cin != 1 channels;
+ * the workspace's size and alignment. */
+int esahrnet_frames_keypoints_candidates_refined_workspace_bytes(esahrnet_handle h, int m, int scale, int decoder, size_t* bytes);
+int esahrnet_frames_keypoints_candidates_refined(esahrnet_handle h, const void* frames_dev, int nframes, int frame_h, int frame_w,
+                                                 int pixel_format, const void* det_boxes_dev, const void* frame_idx_dev, int m,
+                                                 int scale, int rule, float mean, float stdv, int candidates, int nms_radius,
+                                                 int decoder, void* cand_dev, void* cidx_dev, void* hess_dev, void* fit_dev,
+                                                 void* status_dev, void* cov_dev, void* info_dev, double cov_floor,
+                                                 void* crop_boxes_dev, void* rates_dev, void* valid_dev, void* ws_dev, size_t ws_bytes,
+                                                 esahrnet_stream stream);
+
 /* esahrnet_pnp_batch_cand with the 2x2 weights of esahrnet_correspondences(mode 1) in the refinement: hess = f64 [n][k][M][3], for
  * every candidate the Hessian (hess_dev of esahrnet_keypoints_at / _candidates_refined with decoder 1 or 2) or gaussfit's info_dev
  * (decoder 2), a host copy.  The same steps 1-6: selection and back-projection (csrc/correspond.h), the RANSAC consensus pose as the
