@@ -199,4 +199,32 @@ int esahrnet_correspondences(const void* kp_dev, const void* hess_dev, const voi
     return 0;
 }
 
+int esahrnet_correspondences_cand(const void* cand_dev, const void* hess_dev, const void* crop_boxes_dev, const void* rates_dev,
+                                  const void* valid_dev, int m, int k, int candidates, double thresh, int min_k, int mode,
+                                  void* count_dev, void* order_dev, void* cpts_dev, void* cw_dev, void* cpeak_dev,
+                                  esahrnet_stream stream) {
+    if (!cand_dev || !crop_boxes_dev || !rates_dev || !valid_dev || !count_dev || !order_dev || !cpts_dev || !cw_dev || !cpeak_dev ||
+        (mode == 1 && !hess_dev))
+        return set_error("correspondences_cand: null argument (hess_dev may be null with mode 0 only)");
+    if (m <= 0) return set_error("correspondences_cand: the number of crops must be positive (got %d)", m);
+    if (k < 1 || k > 32) return set_error("correspondences_cand: %d keypoints per crop unsupported (1..32: one wave per crop)", k);
+    if (candidates < 1 || candidates > ESAHRNET_MAX_CANDIDATES)
+        return set_error("correspondences_cand: %d candidates per keypoint unsupported (1..%d)", candidates, ESAHRNET_MAX_CANDIDATES);
+    if (mode != 0 && mode != 1)
+        return set_error("correspondences_cand: mode=%d unknown (0: peak weights, 1: Hessian weights)", mode);
+    const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if ((at(cand_dev) | at(crop_boxes_dev) | at(valid_dev) | at(count_dev) | at(order_dev) | at(cpeak_dev)) & 3)
+        return set_error("correspondences_cand: cand_dev, crop_boxes_dev, valid_dev, count_dev, order_dev and cpeak_dev must be 4-byte aligned");
+    if (((mode == 1 ? at(hess_dev) : 0) | at(rates_dev) | at(cpts_dev) | at(cw_dev)) & 7)
+        return set_error("correspondences_cand: hess_dev (mode 1), rates_dev, cpts_dev and cw_dev must be 8-byte aligned");
+    const int rc = esa::launch_correspond_cand(static_cast<const float*>(cand_dev), mode == 1 ? static_cast<const double*>(hess_dev) : nullptr,
+                                               static_cast<const int*>(crop_boxes_dev), static_cast<const double*>(rates_dev),
+                                               static_cast<const int*>(valid_dev), m, k, candidates, thresh, min_k, mode,
+                                               static_cast<int*>(count_dev), static_cast<int*>(order_dev), static_cast<double*>(cpts_dev),
+                                               static_cast<double*>(cw_dev), static_cast<float*>(cpeak_dev),
+                                               static_cast<hipStream_t>(stream));
+    if (rc) return set_error("correspondences_cand: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
 }  // extern "C"

@@ -434,6 +434,11 @@ int launch_keypoints_at(const float* heat, int planes, int H, int W, const int* 
 // count int32 [m], order int32 [m][K], pts f64 [m][K][2], w f64 [m][K][3].  K <= 32 (one wave per crop).
 int launch_correspond(const float* kp, const double* hess, const int* crop, const double* rates, const int* valid, int m, int K,
                       double thresh, int min_k, int mode, int* count, int* order, double* pts, double* w, hipStream_t s);
+// the same on candidate rows: cand f32 [m][K][M][3], hess f64 [m][K][M][3] (mode 1) -> count, order as above (selection by
+// candidate 0), cpts f64 [m][K][M][2], cw f64 [m][K][M][3], cpeak f32 [m][K][M] in rank order.  K <= 32, M <= 4.
+int launch_correspond_cand(const float* cand, const double* hess, const int* crop, const double* rates, const int* valid, int m, int K,
+                           int M, double thresh, int min_k, int mode, int* count, int* order, double* cpts, double* cw, float* cpeak,
+                           hipStream_t s);
 
 // ---- layout conversion f32 NCHW <-> SB (layout.hip) ----------------------------------------
 int launch_nchw_to_sb(const float* x, int N, int C, int H, int W, char* y, int Cp, hipStream_t s);

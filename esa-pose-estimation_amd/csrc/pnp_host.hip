@@ -9,7 +9,9 @@
 // fill a report row per image from the finished pose (status, RANSAC consensus, residuals, the 6x6 covariance (J^T J)^-1;
 // enum esahrnet_pose_report), which takes no part in the solve.
 // esahrnet_pnp_batch_cand solves on the candidate rows of esahrnet_keypoints_candidates: the same flow on candidate 0, then one
-// repair step judged by the RANSAC consensus pose (pose_one_cand; pnp.py: candidates_to_pose is its oracle).
+// repair step judged by the RANSAC consensus pose (pose_cand_core; pnp.py: candidates_to_pose is its oracle).  The step itself
+// works on image points: esahrnet_pnp_batch_cand / _cand_w are "selection + back-projection + weights (CandRows), then the
+// core", esahrnet_pnp_batch_cand_pts is the core on a record esahrnet_correspondences_cand already wrote (CandRecord).
 //
 // It is a line-by-line native restatement of esa-pose-estimation_amd/pnp.py (which is the oracle for it:
 // tests/test_pnp_native.py compares poses and inlier sets); like that module it restates the PUBLISHED
@@ -738,58 +740,128 @@ void pose_one(const float* kp, int k, const double* kp3d, const Cam& K, int x0, 
     pose_solve(p3.data(), p2.data(), wv.data(), large, K, q, t, rep);
 }
 
-// ---- one image from its candidate rows cand [k][M][3]: pose_one on candidate 0, then the repair step (include/esahrnet.h:
-// esahrnet_pnp_batch_cand; pnp.py: candidates_to_pose is the oracle) -------------------------------------------------------
-// hess: null (the peak weights), or the image's f64 [k][M][3] Hessians / infos: the LM weight of a point that enters a solve with
-// candidate m is corr_hessian_weight(hess[j][m], rate) (esahrnet_pnp_batch_cand_w); nothing else differs
-void pose_one_cand(const float* cand, const double* hess, int k, int M, const double* kp3d, const Cam& K, int x0, int y0, double rate, double thresh,
-                   int min_k, double min_ratio, double q[4], double t[3], double* rep, int* used) {
+// ---- the repair step on an image's selected points (include/esahrnet.h: esahrnet_pnp_batch_cand, steps 1-6; pnp.py:
+// candidates_to_pose is the oracle) -----------------------------------------------------------------------------------------
+// p3 / p2 / wv: the `large` selected points in rank order, candidate 0 of each as point and weight (p2 and wv are repaired in
+// place).  `slots` knows the runner-ups: slots.qualifies(i, m, min_ratio, xy) says whether candidate m >= 1 of rank slot i has
+// finite coordinates and peak_m >= min_ratio * peak_0, and gives its image point; slots.weight(i, m, w3) its LM weight.
+// pick [large]: the candidate each slot entered the returned pose's solve with (all 0 unless the repaired solve is taken)
+template <class Slots>
+void pose_cand_core(const Slots& slots, const double* p3, double* p2, double* wv, int large, int M, const Cam& K, double min_ratio,
+                    double q[4], double t[3], double* rep, int* pick) {
     const double reproj = 5.0;                             // ransac()'s threshold
-    std::vector<int> order;
-    std::vector<double> p3, p2, wv;
-    const int large = correspond_rows(cand, 3 * M, k, kp3d, x0, y0, rate, thresh, min_k, order, p3, p2, wv);
-    for (int j = 0; j < k; ++j) used[j] = -1;
-    for (int i = 0; i < large; ++i) used[order[i]] = 0;
-    if (hess)
-        for (int i = 0; i < large; ++i) esa::corr_hessian_weight(hess + (size_t)order[i] * M * 3, rate, &wv[i * 3]);
+    for (int i = 0; i < large; ++i) pick[i] = 0;
     double r1[ESAHRNET_POSE_REPORT_DOUBLES];
     Mat3 Rj;
     double tj[3];
-    pose_solve(p3.data(), p2.data(), wv.data(), large, K, q, t, r1, &Rj, tj);
+    pose_solve(p3, p2, wv, large, K, q, t, r1, &Rj, tj);
     if (rep) std::memcpy(rep, r1, sizeof r1);
     if (M == 1 || r1[ESAHRNET_REPORT_STATUS] != 0 || ((int)r1[ESAHRNET_REPORT_FLAGS] & 1)) return;
-    const double inv = esa::corr_inv_rate(rate);
-    std::vector<int> pick(large, 0);
+    std::vector<int> take(large, 0);
     bool swapped = false;
     for (int i = 0; i < large; ++i) {
         double pj[2];
         project1(&p3[i * 3], Rj, tj, K, pj);
         const double dx0 = pj[0] - p2[i * 2], dy0 = pj[1] - p2[i * 2 + 1];
         if (!(std::sqrt(dx0 * dx0 + dy0 * dy0) >= reproj)) continue;
-        const float* c = cand + (size_t)order[i] * M * 3;
         double best = reproj, bx = 0.0, by = 0.0;
         for (int m = 1; m < M; ++m) {
-            if (!std::isfinite(c[m * 3]) || !std::isfinite(c[m * 3 + 1])) continue;
-            if (!((double)c[m * 3 + 2] >= min_ratio * (double)c[2])) continue;
-            const double x = esa::corr_to_image(c[m * 3 + 0], inv, x0), y = esa::corr_to_image(c[m * 3 + 1], inv, y0);
+            double xy[2];
+            if (!slots.qualifies(i, m, min_ratio, xy)) continue;
+            const double x = xy[0], y = xy[1];
             const double d = std::sqrt((pj[0] - x) * (pj[0] - x) + (pj[1] - y) * (pj[1] - y));
-            if (d < best) { best = d; bx = x; by = y; pick[i] = m; }
+            if (d < best) { best = d; bx = x; by = y; take[i] = m; }
         }
-        if (pick[i]) {
+        if (take[i]) {
             p2[i * 2] = bx;
             p2[i * 2 + 1] = by;
-            if (hess) esa::corr_hessian_weight(hess + ((size_t)order[i] * M + pick[i]) * 3, rate, &wv[i * 3]);
-            else wv[i * 3] = wv[i * 3 + 2] = (double)c[pick[i] * 3 + 2];
+            slots.weight(i, take[i], &wv[i * 3]);
             swapped = true;
         }
     }
     if (!swapped) return;
     double q2[4], t2[3], r2[ESAHRNET_POSE_REPORT_DOUBLES];
-    pose_solve(p3.data(), p2.data(), wv.data(), large, K, q2, t2, r2);
+    pose_solve(p3, p2, wv, large, K, q2, t2, r2);
     if (r2[ESAHRNET_REPORT_STATUS] != 0 || !(r2[ESAHRNET_REPORT_INLIERS] > r1[ESAHRNET_REPORT_INLIERS])) return;
     std::memcpy(q, q2, sizeof q2);
     std::memcpy(t, t2, sizeof t2);
     if (rep) std::memcpy(rep, r2, sizeof r2);
+    for (int i = 0; i < large; ++i) pick[i] = take[i];
+}
+
+// the runner-ups of an image's candidate rows cand [k][M][3] in crop coordinates (esahrnet_pnp_batch_cand / _cand_w): the
+// back-projection and the weights of correspond.h, computed for the candidates the repair looks at
+struct CandRows {
+    const float* cand;
+    const double* hess;                                    // null: the peak weights
+    const int* order;
+    int M, x0, y0;
+    double rate, inv;
+    bool qualifies(int i, int m, double min_ratio, double xy[2]) const {
+        const float* c = cand + (size_t)order[i] * M * 3;
+        if (!std::isfinite(c[m * 3]) || !std::isfinite(c[m * 3 + 1])) return false;
+        if (!((double)c[m * 3 + 2] >= min_ratio * (double)c[2])) return false;
+        xy[0] = esa::corr_to_image(c[m * 3 + 0], inv, x0);
+        xy[1] = esa::corr_to_image(c[m * 3 + 1], inv, y0);
+        return true;
+    }
+    void weight(int i, int m, double* w3) const {
+        if (hess) esa::corr_hessian_weight(hess + ((size_t)order[i] * M + m) * 3, rate, w3);
+        else w3[0] = w3[2] = (double)cand[((size_t)order[i] * M + m) * 3 + 2];     // (w3[1] stays the primary's 0)
+    }
+};
+
+// the runner-ups of an image's record in image pixels, as esahrnet_correspondences_cand wrote it (esahrnet_pnp_batch_cand_pts):
+// cpts [k][M][2], cw [k][M][3], cpeak [k][M] in rank order; everything is read, nothing computed
+struct CandRecord {
+    const double* cpts;
+    const double* cw;
+    const float* cpeak;
+    int M;
+    bool qualifies(int i, int m, double min_ratio, double xy[2]) const {
+        const double* p = cpts + ((size_t)i * M + m) * 2;
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1])) return false;
+        if (!((double)cpeak[(size_t)i * M + m] >= min_ratio * (double)cpeak[(size_t)i * M])) return false;
+        xy[0] = p[0];
+        xy[1] = p[1];
+        return true;
+    }
+    void weight(int i, int m, double* w3) const {
+        for (int d = 0; d < 3; ++d) w3[d] = cw[((size_t)i * M + m) * 3 + d];
+    }
+};
+
+// ---- one image from its candidate rows cand [k][M][3]: selection, back-projection and weights of candidate 0 (pose_one's), then
+// the repair step above -----------------------------------------------------------------------------------------------------
+// hess: null (the peak weights), or the image's f64 [k][M][3] Hessians / infos: the LM weight of a point that enters a solve with
+// candidate m is corr_hessian_weight(hess[j][m], rate) (esahrnet_pnp_batch_cand_w); nothing else differs
+void pose_one_cand(const float* cand, const double* hess, int k, int M, const double* kp3d, const Cam& K, int x0, int y0, double rate, double thresh,
+                   int min_k, double min_ratio, double q[4], double t[3], double* rep, int* used) {
+    std::vector<int> order;
+    std::vector<double> p3, p2, wv;
+    const int large = correspond_rows(cand, 3 * M, k, kp3d, x0, y0, rate, thresh, min_k, order, p3, p2, wv);
+    for (int j = 0; j < k; ++j) used[j] = -1;
+    if (hess)
+        for (int i = 0; i < large; ++i) esa::corr_hessian_weight(hess + (size_t)order[i] * M * 3, rate, &wv[i * 3]);
+    std::vector<int> pick(large);
+    const CandRows rows{cand, hess, order.data(), M, x0, y0, rate, esa::corr_inv_rate(rate)};
+    pose_cand_core(rows, p3.data(), p2.data(), wv.data(), large, M, K, min_ratio, q, t, rep, pick.data());
+    for (int i = 0; i < large; ++i) used[order[i]] = pick[i];
+}
+
+// ---- one image from its record in image pixels: the first `large` rank slots, candidate 0 of each the primary ---------------
+void pose_one_cand_pts(const double* cpts, const double* cw, const float* cpeak, int large, const int* order, int k, int M,
+                       const double* kp3d, const Cam& K, double min_ratio, double q[4], double t[3], double* rep, int* used) {
+    std::vector<double> p3(3 * (size_t)large), p2(2 * (size_t)large), wv(3 * (size_t)large);
+    for (int i = 0; i < large; ++i) {
+        for (int d = 0; d < 3; ++d) p3[i * 3 + d] = kp3d[order[i] * 3 + d];
+        for (int d = 0; d < 2; ++d) p2[i * 2 + d] = cpts[(size_t)i * M * 2 + d];
+        for (int d = 0; d < 3; ++d) wv[i * 3 + d] = cw[(size_t)i * M * 3 + d];
+    }
+    for (int j = 0; j < k; ++j) used[j] = -1;
+    std::vector<int> pick(large);
+    const CandRecord rec{cpts, cw, cpeak, M};
+    pose_cand_core(rec, p3.data(), p2.data(), wv.data(), large, M, K, min_ratio, q, t, rep, pick.data());
     for (int i = 0; i < large; ++i) used[order[i]] = pick[i];
 }
 
@@ -890,4 +962,32 @@ extern "C" int esahrnet_pnp_batch_cand_w(const float* cand, const double* hess, 
                                          double min_ratio, int threads, double* q_out, double* t_out, double* report, int* used) {
     return pnp_batch_cand("pnp_batch_cand_w", cand, hess, n, k, candidates, kp3d, K9, boxes_xy, rates, thresh, min_k, min_ratio,
                           threads, q_out, t_out, report, used);
+}
+
+extern "C" int esahrnet_pnp_batch_cand_pts(const double* cpts, const double* cw, const float* cpeak, const int* count, const int* order,
+                                           int m, int k, int candidates, const double* kp3d, const double* K9, double min_ratio,
+                                           int threads, double* q_out, double* t_out, double* report, int* used) {
+    const char* who = "pnp_batch_cand_pts";
+    if (!cpts || !cw || !cpeak || !count || !order || !kp3d || !K9 || !q_out || !t_out || !used)
+        return esa::set_error("%s: null argument", who);
+    if (m < 0) return esa::set_error("%s: negative image count %d", who, m);
+    if (k < 1 || k > 64) return esa::set_error("%s: %d keypoints per image unsupported (1..64)", who, k);
+    if (candidates < 1 || candidates > ESAHRNET_MAX_CANDIDATES)
+        return esa::set_error("%s: %d candidates per keypoint unsupported (1..%d)", who, candidates, ESAHRNET_MAX_CANDIDATES);
+    if (!(min_ratio >= 0.0)) return esa::set_error("%s: min_ratio %g must be a number >= 0", who, min_ratio);
+    for (int i = 0; i < m; ++i) {
+        if (count[i] < 0 || count[i] > k) return esa::set_error("%s: count[%d] = %d outside 0..%d", who, i, count[i], k);
+        for (int j = 0; j < count[i]; ++j)
+            if (order[(size_t)i * k + j] < 0 || order[(size_t)i * k + j] >= k)
+                return esa::set_error("%s: order[%d][%d] = %d is no keypoint index (0..%d)", who, i, j, order[(size_t)i * k + j], k - 1);
+    }
+    const Cam K{K9[0], K9[4], K9[2], K9[5]};
+    const size_t per = (size_t)k * candidates;
+    run_batch(m, threads, [&](int lo, int hi) {
+        for (int i = lo; i < hi; ++i)
+            pose_one_cand_pts(cpts + i * per * 2, cw + i * per * 3, cpeak + i * per, count[i], order + (size_t)i * k, k, candidates, kp3d,
+                              K, min_ratio, q_out + (size_t)i * 4, t_out + (size_t)i * 3,
+                              report ? report + (size_t)i * ESAHRNET_POSE_REPORT_DOUBLES : nullptr, used + (size_t)i * k);
+    });
+    return 0;
 }

@@ -27,8 +27,8 @@ import torch.nn as nn
 
 from . import _lib, crops
 from .fold import fold_conv
-from .inference import (_at_returns, _check_at_outputs, check_cov_floor, check_refine, check_weights, pack_correspondences,
-                        record_fields, record_outputs, record_views)
+from .inference import (_at_returns, _check_at_outputs, check_cov_floor, check_refine, check_weights,
+                        pack_candidate_correspondences, pack_correspondences, record_fields, record_outputs, record_views)
 
 logger = logging.getLogger(__name__)
 BN_MOMENTUM = 0.01           # models/seg_hrnet.py:23 (irrelevant at inference, kept for parity)
@@ -310,6 +310,37 @@ class HighResolutionNet(nn.Module):
         refined = None if decoder == 0 else (decoder, cov_floor if return_cov else None)
         return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
                                          0, cand=(int(candidates), int(nms_radius)), refined=refined)
+
+    def frames_to_candidate_correspondences(self, frames: torch.Tensor, det_boxes, frame_idx=None, scale: int = 256,
+                                            rule: str = "val", refine: str = "get_final", candidates: int = 3, nms_radius: int = 6,
+                                            thresh: float = 0.8, min_k: int = 24, weights: str = "peak", mean=None,
+                                            std: float = crops.STD, pixel_format=None, cov_floor: float = 1e-6):
+        """frames_to_candidates and the selection, back-projection and weights of val.py:172-180 behind it, for every candidate:
+        -> (cpts f64 [m,K,M,2], cw f64 [m,K,M,3], cpeak f32 [m,K,M], count int32 [m], order int32 [m,K], cand, crop_boxes, rates,
+        valid), all on the device.  The first five are the record pnp.candidate_correspondences_to_pose_batch solves on
+        (inference.record_fields(K, "candidate_correspondences", candidates=M)): the keypoints handed to PnP by their primary's
+        peak, largest first, and in that order every candidate in image pixels with its 2x2 weight -- weights="peak": (peak, 0,
+        peak); "hessian" (refine="get_final2" or "gaussfit"): rate * (-H)^(1/2) of the candidate's own Hessian; "covariance"
+        (refine="gaussfit"): rate * cov^(-1/2) of its fitted centre, zero where cov[0] < cov_floor -- and its peak.  Two library
+        calls on one stream (esahrnet_frames_keypoints_candidates[_refined], then esahrnet_correspondences_cand on its outputs);
+        equal, bit for bit, to frames_to_candidates(refine=...) followed by inference.candidates_to_correspondences; capturable
+        into a graph.  An invalid crop has count 0."""
+        return self._frames_to_candidate_correspondences(frames, det_boxes, frame_idx, scale, rule, refine, candidates, nms_radius,
+                                                         thresh, min_k, weights, mean, std, pixel_format, cov_floor)[:9]
+
+    def _frames_to_candidate_correspondences(self, frames, det_boxes, frame_idx, scale, rule, refine, candidates, nms_radius, thresh,
+                                             min_k, weights, mean, std, pixel_format, cov_floor=1e-6):
+        """frames_to_candidate_correspondences, plus (ccpacked, packed): the first five returns are views of `ccpacked` (one uint8
+        buffer, inference.pack_candidate_correspondences), which a caller that needs them on the host fetches with one copy;
+        cand, crop_boxes, rates and valid are views of `packed`, the candidates record as _frames_to_candidates returns it."""
+        self._inference_only()
+        mode = check_weights(weights, refine)
+        decoder, cov_floor = _check_at_outputs(refine, weights == "hessian", False, weights == "covariance", cov_floor)
+        rule_n, fmt, m, mean = self._loader_args(frames, det_boxes, frame_idx, rule, mean, pixel_format)
+        refined = None if decoder == 0 else (decoder, cov_floor if weights == "covariance" else None)
+        return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
+                                         0, cand=(int(candidates), int(nms_radius)), refined=refined,
+                                         ccorr=(float(thresh), int(min_k), mode))
 
     def _frames_to_keypoints(self, frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format, cov_floor=None):
         """frames_to_keypoints, plus (idx int32 [m,K], packed): every output is a view of `packed` (one uint8 buffer), so a
@@ -813,7 +844,7 @@ class _Runtime:
         return cand, cidx, {"fit": fit, "status": status, "hess": hess, "cov": cov, "info": info}
 
     def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None, cov=None,
-                         cand=None, refined=None):
+                         cand=None, refined=None, ccorr=None):
         """esahrnet_frames_keypoints (arguments already checked by crops.check_device_loader_args).  The outputs are views
         of one packed buffer (inference.record_fields / record_views), returned as inference.record_outputs orders them: rates f64
         [m] | kp f32 [m,K,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,K]; decoder 2, the Gaussian fit, also fit,
@@ -827,7 +858,12 @@ class _Runtime:
         cidx int32 [m,K,M], packed), views of the candidates record (inference.record_fields(K, "candidates", candidates=M)).
         refined = (decoder 1 or 2 of esahrnet_keypoints_at, cov_floor or None) beside cand:
         esahrnet_frames_keypoints_candidates_refined instead, on the record of kind "candidates_refined"; its decoder outputs follow
-        `packed` (inference.record_outputs)."""
+        `packed` (inference.record_outputs).  ccorr = (thresh, min_k, mode) beside cand: esahrnet_correspondences_cand behind the
+        candidates' call on the same stream, mode 1 on the record's cand_info (refined with a cov_floor) or cand_hess -> (cpts, cw,
+        cpeak, count, order, cand, boxes, rates, valid, ccpacked, packed), the first five views of `ccpacked`
+        (inference.pack_candidate_correspondences)."""
+        if ccorr is not None and (cand is None or (ccorr[2] and refined is None)):
+            raise ValueError("the candidate correspondences belong to the candidates, their Hessian weights to a refined decoder")
         if cand is not None and (decoder != 0 or corr is not None or cov is not None):
             raise ValueError("the candidates belong to the get_final decoder, without correspondences")
         if refined is not None and cand is None:
@@ -863,6 +899,9 @@ class _Runtime:
                 count, order, pts, w, cpacked = pack_correspondences(m, k, dev)
                 out = (count, order, pts, w, *out[:4], cpacked, packed)
                 selected = (count.data_ptr(), order.data_ptr(), pts.data_ptr(), w.data_ptr())
+            if ccorr is not None:       # (M as the candidates record has it: record_fields has refused a bad one)
+                cc = pack_candidate_correspondences(m, k, views["cand"].shape[2], dev)
+                out = (*cc[:5], *out[:4], cc[5], packed)
             with self._device_lock(dev.index):
                 h = self._handle_for(module, dev)
                 _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
@@ -902,6 +941,11 @@ class _Runtime:
                                                            kind="frames_final2" if decoder else "frames")
                     _lib.check(self.lib.esahrnet_frames_keypoints(*loader, decoder, p["kp"], p["idx"], *placed, ws_ptr, ws_bytes,
                                                                   stream))
+                if ccorr is not None:               # behind the candidates' call, on its outputs
+                    wsrc = p.get("cand_info", p.get("cand_hess")) if ccorr[2] else None    # "covariance": -cov^-1 as the Hessian
+                    _lib.check(self.lib.esahrnet_correspondences_cand(
+                        p["cand"], wsrc, *placed, m, k, views["cand"].shape[2], ccorr[0], ccorr[1], ccorr[2], cc[3].data_ptr(),
+                        cc[4].data_ptr(), cc[0].data_ptr(), cc[1].data_ptr(), cc[2].data_ptr(), stream))
         for t in (ws, frames, det, fidx):
             if t is not None:
                 t.record_stream(ts)

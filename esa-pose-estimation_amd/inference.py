@@ -344,7 +344,7 @@ def check_weights(weights, refine="get_final2"):
     return int(weights != "peak")
 
 
-RECORD_KINDS = ("keypoints", "correspondences", "candidates", "candidates_refined")
+RECORD_KINDS = ("keypoints", "correspondences", "candidates", "candidate_correspondences", "candidates_refined")
 # THE description of the packed records; every layout, view and exchange below and in hrnet / parallel / pipeline derives from it.
 # Element type and trailing shape of every field (k = keypoints per crop, M = candidates per keypoint) ...
 _RECORD_TYPES = {"rates": (torch.float64, ()), "fit": (torch.float64, ("k", 8)), "hess": (torch.float64, ("k", 3)),
@@ -356,12 +356,15 @@ _RECORD_TYPES = {"rates": (torch.float64, ()), "fit": (torch.float64, ("k", 8)),
                  # the refined candidates' outputs, one row per candidate: names of their own, since their shapes carry M
                  "cand_fit": (torch.float64, ("k", "M", 8)), "cand_hess": (torch.float64, ("k", "M", 3)),
                  "cand_cov": (torch.float64, ("k", "M", 3)), "cand_info": (torch.float64, ("k", "M", 3)),
-                 "cand_status": (torch.int32, ("k", "M"))}
+                 "cand_status": (torch.int32, ("k", "M")),
+                 # the candidates in image pixels, in rank order (esahrnet_correspondences_cand): point, 2x2 weight and peak of each
+                 "cpts": (torch.float64, ("k", "M", 2)), "cw": (torch.float64, ("k", "M", 3)), "cpeak": (torch.float32, ("k", "M"))}
 # ... and the fields of each record in memory order (the f64 parts first: 8-byte aligned); fit, hess and status are there with
 # gaussfit only, cov and info with cov only (cand_fit, cand_status, cand_cov and cand_info likewise; cand_hess is always there)
 _RECORD_ORDER = {"keypoints": ("rates", "fit", "hess", "cov", "info", "kp", "boxes", "valid", "idx", "status"),
                  "correspondences": ("pts", "w", "count", "order"),
                  "candidates": ("rates", "cand", "boxes", "valid", "cidx"),
+                 "candidate_correspondences": ("cpts", "cw", "cpeak", "count", "order"),
                  "candidates_refined": ("rates", "cand_fit", "cand_hess", "cand_cov", "cand_info", "cand", "boxes", "valid", "cidx",
                                         "cand_status")}
 _RECORD_SWITCH = {"fit": "gaussfit", "hess": "gaussfit", "status": "gaussfit", "cov": "cov", "info": "cov",
@@ -384,7 +387,9 @@ def record_fields(k: int, kind: str, gaussfit: bool = False, cov: bool = False, 
     the buffer of pack_correspondences (pts | w | count | order), kind="candidates" the buffer of net._frames_to_candidates with
     candidates=M (rates | cand | boxes | valid | cidx), kind="candidates_refined" the buffer of net._frames_to_candidates with a
     refine other than "get_final" (rates | [cand_fit] | cand_hess | [cand_cov | cand_info] | cand | boxes | valid | cidx |
-    [cand_status]: the decoder's outputs for every candidate, f64 first; gaussfit=True is refine="gaussfit", False "get_final2").
+    [cand_status]: the decoder's outputs for every candidate, f64 first; gaussfit=True is refine="gaussfit", False "get_final2"),
+    kind="candidate_correspondences" the buffer of net._frames_to_candidate_correspondences with candidates=M (cpts | cw | cpeak |
+    count | order: what pnp.candidate_correspondences_to_pose_batch consumes; whatever the decoder, no gaussfit / cov switch).
     A record is field-major, so field f of m crops takes m * bytes and
     starts at m * (the bytes of the fields in front of it); every size is a multiple of 4.  This is the description the views
     (record_views), the offsets (packed_layout) and the exchange of a sharded batch (parallel.gather_records,
@@ -394,12 +399,12 @@ def record_fields(k: int, kind: str, gaussfit: bool = False, cov: bool = False, 
     k = int(k)
     if k < 1:
         raise ValueError(f"k = {k}: a record has at least one keypoint per crop")
-    if kind == "correspondences" and (gaussfit or cov):
+    if kind in ("correspondences", "candidate_correspondences") and (gaussfit or cov):
         raise ValueError("gaussfit and cov belong to kind='keypoints'")
     if cov and not gaussfit:
         raise ValueError("cov=True belongs to gaussfit=True")
     mm = 1
-    if kind in ("candidates", "candidates_refined"):
+    if kind in ("candidates", "candidates_refined", "candidate_correspondences"):
         if gaussfit and kind == "candidates":
             raise ValueError("candidates=M belongs to the get_final decoder (gaussfit=False)")
         if candidates is None or not 1 <= int(candidates) <= _lib.MAX_CANDIDATES:
@@ -500,6 +505,48 @@ def keypoints_to_correspondences(kp: torch.Tensor, crop_boxes: torch.Tensor, rat
                                                        count.data_ptr(), order.data_ptr(), pts.data_ptr(), w.data_ptr(),
                                                        C.c_void_p(stream)))
     return count, order, pts, w
+
+
+def pack_candidate_correspondences(m: int, k: int, candidates: int, device):
+    """One uint8 buffer and its views cpts f64 [m,k,M,2] | cw f64 [m,k,M,3] | cpeak f32 [m,k,M] | count int32 [m] | order int32
+    [m,k] (record_fields(k, "candidate_correspondences", candidates=M)).  -> (cpts, cw, cpeak, count, order, packed)."""
+    fields = record_fields(k, "candidate_correspondences", candidates=candidates)
+    packed = torch.empty(m * sum(b for _, b in fields), dtype=torch.uint8, device=device)
+    v = record_views(packed, m, k, fields)
+    return v["cpts"], v["cw"], v["cpeak"], v["count"], v["order"], packed
+
+
+def candidates_to_correspondences(cand: torch.Tensor, crop_boxes: torch.Tensor, rates: torch.Tensor, valid: torch.Tensor,
+                                  thresh: float = 0.8, min_k: int = 24, weights: str = "peak", hess: torch.Tensor = None):
+    """keypoints_to_correspondences for candidate rows (include/esahrnet.h esahrnet_correspondences_cand): cand f32 cuda [m,K,M,3]
+    and the crop boxes int32 [m,4], rates f64 [m] and valid int32 [m] of net.frames_to_candidates -> (cpts f64 [m,K,M,2], cw f64
+    [m,K,M,3], cpeak f32 [m,K,M], count int32 [m], order int32 [m,K]) on the device, views of one packed buffer: the selection by
+    candidate 0's peak, then in rank order every candidate in image pixels with its 2x2 weight and its peak, the record
+    pnp.candidate_correspondences_to_pose_batch solves on.  An absent runner-up (a NaN row) has a NaN point and weight zero; slots
+    beyond count are zero.  weights="hessian" / "covariance" take, as hess, the f64 [m,K,M,3] Hessians / infos of
+    frames_to_candidates(refine=..., return_hessian / return_cov=True): cw = rate (-hess)^(1/2) per candidate."""
+    mode = check_weights(weights, "gaussfit" if weights == "covariance" else "get_final2")
+    if not (isinstance(cand, torch.Tensor) and cand.is_cuda and cand.dtype == torch.float32 and cand.dim() == 4 and
+            cand.shape[3] == 3):
+        raise ValueError("cand must be a float32 cuda tensor [m, K, M, 3]")
+    m, k, mm = cand.shape[:3]
+    dev = cand.device
+    for name, t, dt, shape in (("crop_boxes", crop_boxes, torch.int32, (m, 4)), ("rates", rates, torch.float64, (m,)),
+                               ("valid", valid, torch.int32, (m,))) + ((("hess", hess, torch.float64, (m, k, mm, 3)),) if mode else ()):
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt and tuple(t.shape) == shape):
+            raise ValueError(f"{name} must be a {dt} tensor {list(shape)} on {dev}")
+    cand, crop_boxes, rates, valid = cand.contiguous(), crop_boxes.contiguous(), rates.contiguous(), valid.contiguous()
+    hess = hess.contiguous() if mode else None
+    if not 1 <= mm <= _lib.MAX_CANDIDATES:
+        raise ValueError(f"cand holds {mm} candidates per keypoint, supported are 1..{_lib.MAX_CANDIDATES}")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        cpts, cw, cpeak, count, order, _ = pack_candidate_correspondences(m, k, mm, dev)
+        _lib.check(_lib.lib().esahrnet_correspondences_cand(cand.data_ptr(), hess.data_ptr() if mode else None, crop_boxes.data_ptr(),
+                                                            rates.data_ptr(), valid.data_ptr(), m, k, mm, float(thresh), int(min_k),
+                                                            mode, count.data_ptr(), order.data_ptr(), cpts.data_ptr(),
+                                                            cw.data_ptr(), cpeak.data_ptr(), C.c_void_p(stream)))
+    return cpts, cw, cpeak, count, order
 
 
 def _to_device(hm):

@@ -11,7 +11,9 @@ The device path (net.frames_to_keypoints / net.frames_to_correspondences: loader
 on the device) is sharded the same way, by boxes: sharded_frames_to_keypoints / sharded_frames_to_correspondences run a
 rank's boxes through the net's one-call entry points and exchange the PACKED RECORD those calls write (inference.record_fields)
 with one all-gather of bytes per record; the field-major blocks are put in batch order by one kernel
-(esahrnet_gather_records, gather_records).  Nothing of this has run on more than one GPU yet, and no time has been measured.
+(esahrnet_gather_records, gather_records).  The candidates go the same way: sharded_frames_to_candidates gathers the candidates
+record, sharded_frames_to_candidate_correspondences the one record the repairing solve consumes (one all-gather, one kernel).
+Nothing of this has run on more than one GPU yet, and no time has been measured.
 """
 from __future__ import annotations
 
@@ -285,6 +287,77 @@ def sharded_frames_to_correspondences(net, frames, det_boxes, frame_idx=None, *,
     last four): two all-gathers and two kernel launches per step."""
     return _sharded_frames_to_correspondences(net, frames, det_boxes, frame_idx, group, int(frame_base), scale, rule, refine,
                                               thresh, min_k, weights, mean, std, pixel_format, cov_floor)[:8]
+
+
+def _sharded_frames_to_candidates(net, frames, det_boxes, frame_idx, group, frame_base, scale, rule, candidates, nms_radius, mean,
+                                  std, pixel_format, refine="get_final", return_hessian=False, return_fit=False, return_cov=False,
+                                  cov_floor=1e-6):
+    """sharded_frames_to_candidates with the returns of net._frames_to_candidates: (cand, crop_boxes, rates, valid, cidx, packed)
+    and, with a refine other than "get_final", the decoder outputs behind `packed` as inference.record_outputs orders them."""
+    from . import inference
+    inference._check_at_outputs(refine, return_hessian, return_fit, return_cov, cov_floor)
+    k, n_total = net.num_keypoints, len(det_boxes)
+    kind = "candidates" if refine == "get_final" else "candidates_refined"
+    fields = inference.record_fields(k, kind, refine == "gaussfit", bool(return_cov), candidates)
+    lo, hi = _shard_of(n_total, group)
+    local = None
+    if hi > lo:
+        boxes, idx = _shard_args(det_boxes, frame_idx, lo, hi, n_total, frame_base)
+        local = net._frames_to_candidates(frames, boxes, idx, scale, rule, candidates, nms_radius, mean, std, pixel_format, refine,
+                                          return_hessian, return_fit, return_cov, cov_floor)[5]
+    packed = gather_records(local, hi - lo, n_total, fields, group, device=frames.device)
+    return inference.record_outputs(inference.record_views(packed, n_total, k, fields), packed)
+
+
+def sharded_frames_to_candidates(net, frames, det_boxes, frame_idx=None, *, group=None, frame_base: int = 0, scale: int = 256,
+                                 rule: str = "val", candidates: int = 3, nms_radius: int = 6, mean=None, std: float = STD,
+                                 pixel_format=None, refine: str = "get_final", return_hessian: bool = False,
+                                 return_fit: bool = False, return_cov: bool = False, cov_floor: float = 1e-6):
+    """net.frames_to_candidates over the ranks of `group`, under the contract of sharded_frames_to_keypoints (full box list on
+    every rank, rank r runs boxes [lo_r, hi_r), frame_idx=None and frame_base as there, no library call on an empty shard): the
+    "candidates" record, or with a refine other than "get_final" the "candidates_refined" record, is gathered (one all-gather, one
+    kernel) and every rank returns what net.frames_to_candidates returns for the whole batch, the bits of the single-device call."""
+    out = _sharded_frames_to_candidates(net, frames, det_boxes, frame_idx, group, int(frame_base), scale, rule, candidates,
+                                        nms_radius, mean, std, pixel_format, refine, return_hessian, return_fit, return_cov, cov_floor)
+    if refine == "get_final":
+        return out[:4]
+    rest = list(out[6:])                # record_outputs' order: [cand_fit, cand_status,] cand_hess[, cand_cov, cand_info]
+    fit = (rest.pop(0), rest.pop(0)) if refine == "gaussfit" else ()
+    return (*out[:4], *(fit if return_fit else ()), *(rest[:1] if return_hessian else ()), *(rest[1:] if return_cov else ()))
+
+
+def _sharded_frames_to_candidate_correspondences(net, frames, det_boxes, frame_idx, group, frame_base, scale, rule, refine,
+                                                 candidates, nms_radius, thresh, min_k, weights, mean, std, pixel_format,
+                                                 cov_floor=1e-6):
+    """sharded_frames_to_candidate_correspondences, plus ccpacked, the record of the whole batch its returns are views of."""
+    from . import inference
+    inference.check_refine(refine)
+    inference.check_weights(weights, refine)
+    k, n_total = net.num_keypoints, len(det_boxes)
+    fields = inference.record_fields(k, "candidate_correspondences", candidates=candidates)
+    lo, hi = _shard_of(n_total, group)
+    local = None
+    if hi > lo:
+        boxes, idx = _shard_args(det_boxes, frame_idx, lo, hi, n_total, frame_base)
+        local = net._frames_to_candidate_correspondences(frames, boxes, idx, scale, rule, refine, candidates, nms_radius, thresh,
+                                                         min_k, weights, mean, std, pixel_format, cov_floor)[9]
+    ccpacked = gather_records(local, hi - lo, n_total, fields, group, device=frames.device)
+    c = inference.record_views(ccpacked, n_total, k, fields)
+    return (c["cpts"], c["cw"], c["cpeak"], c["count"], c["order"], ccpacked)
+
+
+def sharded_frames_to_candidate_correspondences(net, frames, det_boxes, frame_idx=None, *, group=None, frame_base: int = 0,
+                                                scale: int = 256, rule: str = "val", refine: str = "get_final",
+                                                candidates: int = 3, nms_radius: int = 6, thresh: float = 0.8, min_k: int = 24,
+                                                weights: str = "peak", mean=None, std: float = STD, pixel_format=None,
+                                                cov_floor: float = 1e-6):
+    """net.frames_to_candidate_correspondences over the ranks of `group`, under the contract of sharded_frames_to_keypoints: ->
+    (cpts f64 [m,K,M,2], cw f64 [m,K,M,3], cpeak f32 [m,K,M], count int32 [m], order int32 [m,K]) of the whole batch on every rank,
+    the bits of the single-device call.  ONE record is gathered, the one pnp.candidate_correspondences_to_pose_batch consumes: one
+    all-gather and one kernel launch per step; the candidates record stays on the rank that decoded it."""
+    return _sharded_frames_to_candidate_correspondences(net, frames, det_boxes, frame_idx, group, int(frame_base), scale, rule,
+                                                        refine, candidates, nms_radius, thresh, min_k, weights, mean, std,
+                                                        pixel_format, cov_floor)[:5]
 
 
 # ---- the measurement protocol of bench.py, importable so that the N > 1 branch runs under gloo on the CPU too ----

@@ -215,7 +215,8 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
 def candidate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, candidates: int = 3, refine: str = "get_final2",
                     weights: str = "hessian", nms_radius: int = 6, min_ratio: float = 0.3, scale: int = 256, thresh: float = 0.8,
                     min_k: int = 24, on_fail: str = "raise", return_report: bool = False, max_rms_px=None, min_inliers=None,
-                    cov_floor: float = 1e-6, threads: int = 0, candidates_path: str = "heatmaps", frame_idx=None, rule: str = "val"):
+                    cov_floor: float = 1e-6, threads: int = 0, candidates_path: str = "heatmaps", frame_idx=None, rule: str = "val",
+                    device_select: bool = False, distributed: bool = False):
     """Runner-up repair AND anisotropic weights, the combination estimate_poses refuses (its candidates=M is get_final with peak
     weights; its weights="hessian" / "covariance" know the arg-max only).  frames, bboxes, kp3d, K, scale, thresh, min_k, on_fail,
     the report and the gates as in estimate_poses -> list of (q, t) per image[, report with .used and .rescued].
@@ -233,13 +234,28 @@ def candidate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, candidates: int 
     (inference.record_fields(K, "candidates_refined", ...)) feeds the same solve with the loader's boxes and rates -- bboxes are
     integers, frame_idx and rule are accepted, and a crop the loader could not make has the NaN pose: on_fail applies, its report
     row is that of "fewer than 4" with n = 0.  The poses, the report, .used and .rescued are those of "heatmaps", bit for bit.
-    device_select and distributed are not built for this combination."""
+    device_select=True (implies the loader; candidates_path stays at its default): net._frames_to_candidate_correspondences also
+    does the top-k rule, the ordering, the back-projection and the 2x2 weight of EVERY candidate on the device
+    (esahrnet_correspondences_cand behind the loader's call), ONE device->host copy of that one record
+    (inference.record_fields(K, "candidate_correspondences", candidates=M)), then pnp.candidate_correspondences_to_pose_batch: the
+    same solve and repair on image points.  bboxes, frame_idx and rule as with "loader"; a crop the loader could not make has
+    count 0, so the solver itself answers the NaN pose and the report row of status 1 with n = 0.  The poses, the report, .used and
+    .rescued are those of candidates_path="loader", bit for bit.
+    distributed=True (with device_select=True or candidates_path="loader"): every rank passes the whole batch, runs its contiguous
+    shard of the boxes and the packed record is all-gathered (parallel.sharded_frames_to_candidate_correspondences /
+    sharded_frames_to_candidates: one record, one all-gather); every rank returns all poses."""
     inference.check_refine(refine)
     mode = inference.check_weights(weights, refine)
     cov_floor = inference.check_cov_floor(cov_floor)
     if candidates_path not in CANDIDATES_PATHS:
         raise ValueError(f"candidates_path must be one of {CANDIDATES_PATHS}, got {candidates_path!r}")
-    if candidates_path != "loader" and (frame_idx is not None or rule != "val"):
+    if device_select and candidates_path != "heatmaps":
+        raise ValueError(f"candidates_path={candidates_path!r} does not go with device_select=True, which decodes in the loader and "
+                         "selects on the device: leave candidates_path at its default")
+    if distributed and not (device_select or candidates_path == "loader"):
+        raise ValueError("distributed=True belongs to device_select=True or candidates_path='loader' (the sharded paths gather the "
+                         "loader's packed records)")
+    if candidates_path != "loader" and not device_select and (frame_idx is not None or rule != "val"):
         raise ValueError("frame_idx and rule belong to candidates_path='loader' (crops.crop_batch: one val box per frame)")
     want = return_report or max_rms_px is not None or min_inliers is not None
     ask = {"return_hessian": weights == "hessian", "return_cov": weights == "covariance", "cov_floor": cov_floor}
@@ -249,9 +265,12 @@ def candidate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, candidates: int 
                                                      thresh, min_k, min_ratio, threads, report=want, hess=hess)
         return [(q[i], t[i]) for i in range(len(boxes))], rep[0] if want else None
 
-    if candidates_path == "loader":
+    if device_select:
+        poses, rep = _device_select_candidate_poses(net, frames, bboxes, frame_idx, distributed, scale, rule, refine, candidates,
+                                                    nms_radius, thresh, min_k, weights, cov_floor, kp3d, K, min_ratio, threads, want)
+    elif candidates_path == "loader":
         poses, rep = _loader_refined_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, refine,
-                                                      weights, ask, solve)
+                                                      weights, ask, solve, distributed)
     else:
         x, boxes, rates = crops.crop_batch(frames, bboxes, scale)
         with torch.no_grad():
@@ -338,11 +357,35 @@ def _loader_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candid
     return _solve_valid_crops(v["cand"], v, solve)
 
 
-def _loader_refined_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, refine, weights, ask, solve):
+def _device_select_candidate_poses(net, frames, bboxes, frame_idx, distributed, scale, rule, refine, candidates, nms_radius, thresh,
+                                   min_k, weights, cov_floor, kp3d, K, min_ratio, threads, want):
+    """candidate_poses with device_select=True: the record's one copy, then the solve on it."""
+    with torch.no_grad():
+        if distributed:                     # every rank its shard of the boxes, then the one record gathered
+            ccpacked = parallel._sharded_frames_to_candidate_correspondences(
+                net, frames, bboxes, frame_idx, None, 0, scale, rule, refine, candidates, nms_radius, thresh, min_k, weights, None,
+                crops.STD, None, cov_floor)[5]
+        else:
+            ccpacked = net._frames_to_candidate_correspondences(frames, bboxes, frame_idx, scale, rule, refine, candidates,
+                                                                nms_radius, thresh, min_k, weights, None, crops.STD, None,
+                                                                cov_floor)[9]
+    m, k = len(bboxes), net.num_keypoints
+    v = _fetch(ccpacked, m, k, inference.record_fields(k, "candidate_correspondences", candidates=candidates))
+    q, t, _, *rep = pnp.candidate_correspondences_to_pose_batch(v["cpts"], v["cw"], v["cpeak"], v["count"], v["order"], kp3d,
+                                                                np.asarray(K, np.float64), min_ratio, threads, report=want)
+    return [(q[i], t[i]) for i in range(m)], rep[0] if want else None
+
+
+def _loader_refined_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, refine, weights, ask, solve,
+                                     distributed=False):
     """candidate_poses with candidates_path="loader": solve(cand, boxes, rates, hess or None) on the fetched record."""
     with torch.no_grad():
-        out = net._frames_to_candidates(frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, None, crops.STD, None,
-                                        refine=refine, **ask)
+        if distributed:
+            out = parallel._sharded_frames_to_candidates(net, frames, bboxes, frame_idx, None, 0, scale, rule, candidates, nms_radius,
+                                                         None, crops.STD, None, refine=refine, **ask)
+        else:
+            out = net._frames_to_candidates(frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, None, crops.STD, None,
+                                            refine=refine, **ask)
     m, k, mm = out[0].shape[:3]
     kind = "candidates" if refine == "get_final" else "candidates_refined"
     v = _fetch(out[5], m, k, inference.record_fields(k, kind, refine == "gaussfit", weights == "covariance", mm))

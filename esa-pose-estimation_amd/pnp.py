@@ -582,6 +582,49 @@ def candidates_to_pose_batch(cand, kp3d, K, boxes_xy, rates, thresh=0.8, min_k=2
     return q, t, used, rep
 
 
+def candidate_correspondences_to_pose_batch(cpts, cw, cpeak, count, order, kp3d, K, min_ratio=0.3, threads=0, report=False):
+    """candidates_to_pose_batch on records the device stage wrote (include/esahrnet.h esahrnet_correspondences_cand ->
+    `esahrnet_pnp_batch_cand_pts`): cpts [N,K,M,2] f64 image pixels, cw [N,K,M,3] f64 = (wxx, wxy, wyy), cpeak [N,K,M] f32, all in
+    rank order with candidate 0 the primary, count [N], order [N,K] int32.  The same solve and repair step: a runner-up qualifies
+    by finite cpts, cpeak >= min_ratio * the primary's and a distance < 5 px to the consensus pose's projection, and replaces
+    point and weight.  -> (q [N,4], t [N,3], used [N,K] int32 by keypoint, -1 = not selected): on the record of the same
+    candidates the bits of candidates_to_pose_batch(cand, ..., hess=...).  An image with count 0 has the NaN pose (report status 1,
+    n = 0).  report=True: -> (q, t, used, rep) with rep.used and rep.rescued."""
+    import ctypes as C
+    import os
+    from . import _lib
+    cpts = np.ascontiguousarray(cpts, np.float64)
+    if cpts.ndim != 4 or cpts.shape[3] != 2:
+        raise ValueError(f"expected cpts [N, K, M, 2], got {cpts.shape}")
+    n, k, m = cpts.shape[:3]
+    cw = np.ascontiguousarray(cw, np.float64)
+    cpeak = np.ascontiguousarray(cpeak, np.float32)
+    count = np.ascontiguousarray(count, np.int32)
+    order = np.ascontiguousarray(order, np.int32)
+    kp3d = np.ascontiguousarray(kp3d, np.float64)
+    K9 = np.ascontiguousarray(K, np.float64).reshape(9)
+    for name, a, shape in (("cw", cw, (n, k, m, 3)), ("cpeak", cpeak, (n, k, m)), ("count", count, (n,)), ("order", order, (n, k)),
+                           ("kp3d", kp3d, (k, 3))):
+        if a.shape != shape:
+            raise ValueError(f"expected {name} {list(shape)}, got {list(a.shape)}")
+    q = np.empty((n, 4), np.float64)
+    t = np.empty((n, 3), np.float64)
+    used = np.empty((n, k), np.int32)
+    rep = np.empty((n, _lib.POSE_REPORT_DOUBLES), np.float64) if report else None
+    if threads <= 0:
+        threads = min(16, len(os.sched_getaffinity(0))) if hasattr(os, "sched_getaffinity") else 4
+    p = lambda a: a.ctypes.data_as(C.c_void_p)                       # noqa: E731
+    _lib.check(_lib.lib().esahrnet_pnp_batch_cand_pts(p(cpts), p(cw), p(cpeak), p(count), p(order), n, k, m, p(kp3d), p(K9),
+                                                      float(min_ratio), int(threads), p(q), p(t), p(rep) if report else None,
+                                                      p(used)))
+    if not report:
+        return q, t, used
+    rep = PoseReport(rep)
+    rep.used = used
+    rep.rescued = (used > 0).any(1)
+    return q, t, used, rep
+
+
 def candidates_to_pose(cand, kp3d, K, bbox_xy, rate, thresh=0.8, min_k=24, min_ratio=0.3, reproj_err=5.0, hess=None):
     """The numpy statement of one image of candidates_to_pose_batch (its oracle): cand [K,M,3] -> (q [w,x,y,z], t, used [K]).
     keypoints_to_pose's steps on candidate 0, the judge = solve_pnp_ransac's pose (EPnP on the consensus set), the swap rule,

@@ -640,6 +640,42 @@ int esahrnet_pnp_batch_cand_w(const float* cand, const double* hess, int n, int 
                               const double* K9, const int* boxes_xy, const double* rates, double thresh, int min_k,
                               double min_ratio, int threads, double* q_out, double* t_out, double* report, int* used);
 
+/* ---- the candidates as the record the repairing solve consumes, on the device (csrc/correspond.hip) ---------
+ * esahrnet_correspondences_cand (correspond_cand_kernel, one wave per crop, k <= 32): esahrnet_correspondences for candidate rows.
+ * cand_dev f32 [m][k][M][3] as esahrnet_keypoints_candidates* / _refined write it, M = candidates in 1..ESAHRNET_MAX_CANDIDATES;
+ * hess_dev f64 [m][k][M][3], a Hessian or gaussfit's info per candidate (mode 1; may be NULL with mode 0); crop_boxes_dev /
+ * rates_dev / valid_dev as esahrnet_boxes wrote them ->
+ *     count_dev int32 [m], order_dev int32 [m][k]   what esahrnet_correspondences gives on the candidate-0 rows: the selection is
+ *                                  by candidate 0's peak, a NaN primary peak is never selected, -1 beyond count;
+ *     cpts_dev  f64 [m][k][M][2]   rank slot i (keypoint order[i]), candidate mm: that candidate's (x, y) in image pixels,
+ *                                  p * (1 / rate) + (x_new, y_new) (csrc/correspond.h, the bits the host solvers compute); (NaN,
+ *                                  NaN) when either crop coordinate is not finite -- the NaN row of an absent runner-up;
+ *     cw_dev    f64 [m][k][M][3]   its weight (wxx, wxy, wyy): mode 0 (peak_mm, 0, peak_mm); mode 1 rate * (-hess[c][j][mm])^(1/2),
+ *                                  zeros where esahrnet_correspondences(mode 1) gives zeros; zeros where the coordinates are not
+ *                                  finite;
+ *     cpeak_dev f32 [m][k][M]      the candidate's peak column, copied.
+ * Slot (i, 0) is the primary: cpts[.][.][0] and cw[.][.][0] are the pts and w of esahrnet_correspondences on the candidate-0 rows
+ * (with hess[.][.][0]), bit for bit, for finite primaries.  Slots at and beyond count are zero in cpts, cw and cpeak; an invalid
+ * crop has count 0.  Every output element is written exactly once; nothing is allocated or synchronised, and the call may be
+ * captured into a graph.  Refused before anything is enqueued, in this order: a NULL pointer (hess_dev only with mode 1); m <= 0;
+ * k outside 1..32; M outside 1..ESAHRNET_MAX_CANDIDATES; mode outside 0..1; a pointer that is not aligned to its element (4 bytes
+ * for f32 and int32, 8 for f64). */
+int esahrnet_correspondences_cand(const void* cand_dev, const void* hess_dev, const void* crop_boxes_dev, const void* rates_dev,
+                                  const void* valid_dev, int m, int k, int candidates, double thresh, int min_k, int mode,
+                                  void* count_dev, void* order_dev, void* cpts_dev, void* cw_dev, void* cpeak_dev,
+                                  esahrnet_stream stream);
+/* Steps 1-6 of esahrnet_pnp_batch_cand on records esahrnet_correspondences_cand wrote (host copies): image i solves on its first
+ * count[i] rank slots, model point kp3d[order[i][j]] for slot j, slot (j, 0) the primary as point and weight.  A runner-up mm >= 1
+ * qualifies when its cpts are finite, cpeak[i][j][mm] >= min_ratio * cpeak[i][j][0] and it lies < 5 px from the judge's projection;
+ * a swap replaces the point and the weight by those of slot (j, mm).  used = int32 [m][k], indexed by KEYPOINT through order, -1 for
+ * a keypoint that was not selected.  On the record of the same candidates, boxes and rates the outputs are those of
+ * esahrnet_pnp_batch_cand (mode 0) / esahrnet_pnp_batch_cand_w (mode 1), bit for bit: one body solves all three.  count[i] = 0 (an
+ * invalid crop): the NaN pose and a report row of status 1 with n = 0.  Refused: what esahrnet_pnp_batch_cand refuses, then a
+ * count outside 0..k or an order entry outside 0..k-1 among the first count, as esahrnet_pnp_batch_w does. */
+int esahrnet_pnp_batch_cand_pts(const double* cpts, const double* cw, const float* cpeak, const int* count, const int* order,
+                                int m, int k, int candidates, const double* kp3d, const double* K9, double min_ratio, int threads,
+                                double* q_out, double* t_out, double* report, int* used);
+
 /* The packed records of the device path after the all-gather of a sharded batch (csrc/records.hip).  A packed record is
  * field-major: field f holds field_bytes[f] bytes per crop, all crops of field 0 first, then field 1, ..., so field f of a
  * record laid out for m crops starts at off_f(m) = m * (field_bytes[0] + ... + field_bytes[f-1]).  gathered_dev: `world`

@@ -5,20 +5,26 @@
 // rows), with 1 and 4 threads, with and without a report buffer.  It checks what tests/test_pose_report_host.py checks at the
 // C level: the poses do not depend on the report or the thread count, nor do the report's bits, and the old entries are the
 // new ones with a null report.  A second file holds candidate records for esahrnet_pnp_batch_cand: the same bits at 1 and 4
-// threads, with and without a report, and with one candidate the bits of esahrnet_pnp_batch_ex.  Exit status 0 and "ok" when
-// all of it holds.  Pure host code: no GPU is touched.
+// threads, with and without a report, and with one candidate the bits of esahrnet_pnp_batch_ex.  The same candidates go through
+// esahrnet_pnp_batch_cand_pts as records in image pixels (make_record: M candidates and one, count = 0 images, NaN slots), held to
+// the bits of the entries on the rows, and every argument that entry refuses is tried.  Exit status 0 and "ok" when all of it
+// holds.  Pure host code: no GPU is touched.
 //
 // Build and run (tools/pnp_host_check.py does both):
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         tools/pnp_host_check.cpp esa-pose-estimation_amd/csrc/pnp_host.hip -fsanitize=address,undefined -o pnp_host_check
 //   ./pnp_host_check records.bin candidates.bin
+#include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <numeric>
 #include <vector>
 
 #include "../include/esahrnet.h"
+#include "../esa-pose-estimation_amd/csrc/correspond.h"
 
 namespace esa {
 static char g_err[512];
@@ -39,6 +45,49 @@ static bool read_vec(FILE* f, std::vector<T>& v, size_t n) {
 
 static bool same(const std::vector<double>& a, const std::vector<double>& b) {
     return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0;
+}
+
+// The record esahrnet_correspondences_cand writes (include/esahrnet.h), made on the host from the first Mr of the M candidate rows
+// with the functions of csrc/correspond.h: cpts [m][k][Mr][2], cw [m][k][Mr][3], cpeak [m][k][Mr], count [m], order [m][k], each
+// exactly sized.  Every third image (i % 3 == 2) is an invalid crop: count 0, order -1, zeros.
+static void make_record(const std::vector<float>& cand, const std::vector<double>& hess, int m, int k, int M, int Mr,
+                        const std::vector<int32_t>& boxes, const std::vector<double>& rates, double thresh, int min_k, int mode,
+                        std::vector<double>& cpts, std::vector<double>& cw, std::vector<float>& cpeak, std::vector<int32_t>& count,
+                        std::vector<int32_t>& order) {
+    cpts.assign((size_t)m * k * Mr * 2, 0.0);
+    cw.assign((size_t)m * k * Mr * 3, 0.0);
+    cpeak.assign((size_t)m * k * Mr, 0.f);
+    count.assign(m, 0);
+    order.assign((size_t)m * k, -1);
+    for (int i = 0; i < m; ++i) {
+        if (i % 3 == 2) continue;
+        const float* c = &cand[(size_t)i * k * M * 3];
+        int above = 0;
+        for (int j = 0; j < k; ++j) above += (double)c[j * M * 3 + 2] > thresh;
+        const int n = esa::corr_count(above, min_k, k);
+        std::vector<int> ord(k);
+        std::iota(ord.begin(), ord.end(), 0);
+        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return esa::corr_before(c[a * M * 3 + 2], a, c[b * M * 3 + 2], b); });
+        const double inv = esa::corr_inv_rate(rates[i]);
+        for (int s = 0; s < n; ++s) {
+            const int j = ord[s];
+            order[(size_t)i * k + s] = j;
+            for (int mm = 0; mm < Mr; ++mm) {
+                const float* r = c + ((size_t)j * M + mm) * 3;
+                const size_t at = ((size_t)i * k + s) * Mr + mm;
+                cpeak[at] = r[2];
+                if (std::isfinite(r[0]) && std::isfinite(r[1])) {
+                    cpts[at * 2 + 0] = esa::corr_to_image(r[0], inv, boxes[i * 2]);
+                    cpts[at * 2 + 1] = esa::corr_to_image(r[1], inv, boxes[i * 2 + 1]);
+                    if (mode) esa::corr_hessian_weight(&hess[(((size_t)i * k + j) * M + mm) * 3], rates[i], &cw[at * 3]);
+                    else cw[at * 3] = cw[at * 3 + 2] = (double)r[2];
+                } else {
+                    cpts[at * 2] = cpts[at * 2 + 1] = NAN;
+                }
+            }
+        }
+        count[i] = n;
+    }
 }
 
 // candidate records: int32 (m, k, M), cand f32 [m][k][M][3], kp3d f64 [k][3], K9, boxes int32 [m][2], rates f64 [m],
@@ -124,6 +173,67 @@ static int check_candidates(const char* path) {
                         return 1;
                     }
                 }
+        // esahrnet_pnp_batch_cand_pts on the record of these rows in image pixels (made here with csrc/correspond.h, as the device
+        // stage makes it; the NaN rows give NaN slots), with M candidates and with the first one alone; every third image's count
+        // is 0 (an invalid crop).  The same bits at 1 and 4 threads, with and without a report, into exactly sized buffers; mode 0
+        // is esahrnet_pnp_batch_cand, mode 1 esahrnet_pnp_batch_cand_w on the rows, bit for bit, and a count-0 image the NaN row
+        for (int mode = 0; mode < 2; ++mode)
+            for (int Mr : {M, 1}) {
+                std::vector<double> cpts, cw;
+                std::vector<float> cpeak;
+                std::vector<int32_t> count, order;
+                make_record(cand, hess, m, k, M, Mr, boxes, rates, sel[0], (int)sel[1], mode, cpts, cw, cpeak, count, order);
+                std::vector<double> qr0, tr0, repr0;
+                std::vector<int32_t> usedr0;
+                for (int threads : {1, 4})
+                    for (int with_report = 0; with_report < 2; ++with_report) {
+                        std::vector<double> q((size_t)m * 4), t((size_t)m * 3), rep(with_report ? m * R : 0);
+                        std::vector<int32_t> used((size_t)m * k);
+                        if (esahrnet_pnp_batch_cand_pts(cpts.data(), cw.data(), cpeak.data(), count.data(), order.data(), m, k, Mr,
+                                                        kp3d.data(), K9.data(), sel[2], threads, q.data(), t.data(),
+                                                        with_report ? rep.data() : nullptr, used.data())) {
+                            std::fprintf(stderr, "candidate record %d: %s\n", nrec, esa::g_err);
+                            return 1;
+                        }
+                        if (qr0.empty()) { qr0 = q; tr0 = t; usedr0 = used; }
+                        if (with_report && repr0.empty()) repr0 = rep;
+                        if (!same(q, qr0) || !same(t, tr0) || used != usedr0 || (with_report && !same(rep, repr0))) {
+                            std::fprintf(stderr, "candidate record %d: record results differ (mode %d, M %d, threads %d, report %d)\n", nrec,
+                                         mode, Mr, threads, with_report);
+                            return 1;
+                        }
+                    }
+                // the rows' own solve: the first Mr candidates of every keypoint, their Hessians in mode 1
+                std::vector<float> rows((size_t)m * k * Mr * 3);
+                std::vector<double> hrows((size_t)m * k * Mr * 3), qa((size_t)m * 4), ta((size_t)m * 3), ra(m * R);
+                std::vector<int32_t> ua((size_t)m * k);
+                for (size_t i = 0; i < (size_t)m * k; ++i) {
+                    std::memcpy(&rows[i * Mr * 3], &cand[i * M * 3], (size_t)Mr * 3 * sizeof(float));
+                    std::memcpy(&hrows[i * Mr * 3], &hess[i * M * 3], (size_t)Mr * 3 * sizeof(double));
+                }
+                if (esahrnet_pnp_batch_cand_w(rows.data(), mode ? hrows.data() : nullptr, m, k, Mr, kp3d.data(), K9.data(), boxes.data(),
+                                              rates.data(), sel[0], (int)sel[1], sel[2], 1, qa.data(), ta.data(), ra.data(), ua.data())) {
+                    std::fprintf(stderr, "candidate record %d: %s\n", nrec, esa::g_err);
+                    return 1;
+                }
+                for (int i = 0; i < m; ++i) {
+                    bool ok;
+                    if (count[i] == 0) {
+                        ok = std::isnan(qr0[i * 4]) && std::isnan(tr0[i * 3]) && repr0[i * R + ESAHRNET_REPORT_STATUS] == 1.0 &&
+                             repr0[i * R + ESAHRNET_REPORT_N] == 0.0;
+                        for (int j = 0; j < k; ++j) ok = ok && usedr0[(size_t)i * k + j] == -1;
+                    } else {
+                        ok = !std::memcmp(&qr0[i * 4], &qa[i * 4], 4 * sizeof(double)) && !std::memcmp(&tr0[i * 3], &ta[i * 3], 3 * sizeof(double)) &&
+                             !std::memcmp(&repr0[i * R], &ra[i * R], R * sizeof(double)) &&
+                             !std::memcmp(&usedr0[(size_t)i * k], &ua[(size_t)i * k], k * sizeof(int32_t));
+                    }
+                    if (!ok) {
+                        std::fprintf(stderr, "candidate record %d image %d: the solve on the record is not the solve on the rows (mode %d, M %d)\n",
+                                     nrec, i, mode, Mr);
+                        return 1;
+                    }
+                }
+            }
         int rescued = 0, swaps = 0, solved = 0;
         for (int i = 0; i < m; ++i) {
             int s = 0;
@@ -153,6 +263,34 @@ static int check_candidates(const char* path) {
         esahrnet_pnp_batch_cand_w(nullptr, z, 1, 11, 1, z, z, b, z, 0.5, 0, 0.3, 1, q, t, nullptr, used) != 1 || !std::strstr(esa::g_err, "null")) {
         std::fprintf(stderr, "a bad argument of esahrnet_pnp_batch_cand_w was not refused\n");
         return 1;
+    }
+    // esahrnet_pnp_batch_cand_pts: each refused argument, in the order of its checks (the next check would fire too)
+    {
+        double p[11 * 2] = {0}, w3[11 * 3] = {0};
+        float pk[11] = {0};
+        int cnt[1] = {4}, ord[11] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10}, over[1] = {12}, under[1] = {-1}, bad[11] = {0, 1, 2, 11};
+        const auto refused = [&](int rc, const char* text) {
+            return rc == 1 && std::strstr(esa::g_err, "pnp_batch_cand_pts") && std::strstr(esa::g_err, text);
+        };
+        if (!refused(esahrnet_pnp_batch_cand_pts(nullptr, w3, pk, cnt, ord, -1, 11, 1, z, z, 0.3, 1, q, t, nullptr, used), "null") ||
+            !refused(esahrnet_pnp_batch_cand_pts(p, w3, nullptr, cnt, ord, -1, 11, 1, z, z, 0.3, 1, q, t, nullptr, used), "null") ||
+            !refused(esahrnet_pnp_batch_cand_pts(p, w3, pk, cnt, ord, 1, 11, 1, z, z, 0.3, 1, q, t, nullptr, nullptr), "null") ||
+            !refused(esahrnet_pnp_batch_cand_pts(p, w3, pk, cnt, ord, -1, 0, 1, z, z, 0.3, 1, q, t, nullptr, used), "negative image count") ||
+            !refused(esahrnet_pnp_batch_cand_pts(p, w3, pk, cnt, ord, 1, 65, 5, z, z, 0.3, 1, q, t, nullptr, used), "keypoints per image") ||
+            !refused(esahrnet_pnp_batch_cand_pts(p, w3, pk, cnt, ord, 1, 11, 5, z, z, -1.0, 1, q, t, nullptr, used), "candidates per keypoint") ||
+            !refused(esahrnet_pnp_batch_cand_pts(p, w3, pk, cnt, ord, 1, 11, 0, z, z, -1.0, 1, q, t, nullptr, used), "candidates per keypoint") ||
+            !refused(esahrnet_pnp_batch_cand_pts(p, w3, pk, over, ord, 1, 11, 1, z, z, NAN, 1, q, t, nullptr, used), "min_ratio") ||
+            !refused(esahrnet_pnp_batch_cand_pts(p, w3, pk, over, bad, 1, 11, 1, z, z, 0.3, 1, q, t, nullptr, used), "count[0] = 12") ||
+            !refused(esahrnet_pnp_batch_cand_pts(p, w3, pk, under, bad, 1, 11, 1, z, z, 0.3, 1, q, t, nullptr, used), "count[0] = -1") ||
+            !refused(esahrnet_pnp_batch_cand_pts(p, w3, pk, cnt, bad, 1, 11, 1, z, z, 0.3, 1, q, t, nullptr, used), "order[0][3] = 11")) {
+            std::fprintf(stderr, "a bad argument of esahrnet_pnp_batch_cand_pts was not refused: %s\n", esa::g_err);
+            return 1;
+        }
+        // zero images: nothing is read or written
+        if (esahrnet_pnp_batch_cand_pts(p, w3, pk, cnt, ord, 0, 11, 1, z, z, 0.3, 1, q, t, nullptr, used) != 0) {
+            std::fprintf(stderr, "an empty batch was refused: %s\n", esa::g_err);
+            return 1;
+        }
     }
     std::printf("ok: %d candidate records\n", nrec);
     return nrec ? 0 : 2;

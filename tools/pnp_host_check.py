@@ -4,7 +4,8 @@ tests/test_pose_report_host.py (the 64-image batch of its tests 1 and 2, as a co
 same record with all but two weights zero; the six random points without a consensus) and, for esahrnet_pnp_batch_cand, on the
 scenes of tests/test_candidates_host.py (its three cases at their seeds, with 3 and with 4 candidate rows, and three-keypoint
 images without a pose); the program also runs those scenes through esahrnet_pnp_batch_cand_w with a Hessian per candidate row
-that it makes up itself.  CPU only; nothing is loaded into Python.  --sanitize "" builds it plain."""
+that it makes up itself, and through esahrnet_pnp_batch_cand_pts as the records in image pixels it makes of them (all candidates
+and one, count = 0 images, NaN slots, the refused arguments).  CPU only; nothing is loaded into Python.  --sanitize "" builds it plain."""
 import argparse
 import os
 import subprocess
