@@ -27,8 +27,8 @@ import torch.nn as nn
 
 from . import _lib, crops
 from .fold import fold_conv
-from .inference import (_at_returns, _check_at_outputs, check_cov_floor, check_refine, check_weights,
-                        pack_candidate_correspondences, pack_correspondences, record_fields, record_outputs, record_views)
+from .inference import (LoaderRequest, LoaderResult, _at_returns, _check_at_outputs, candidate_returns, check_cov_floor,
+                        check_refine, check_weights)
 
 logger = logging.getLogger(__name__)
 BN_MOMENTUM = 0.01           # models/seg_hrnet.py:23 (irrelevant at inference, kept for parity)
@@ -74,10 +74,6 @@ def _cfg_struct(config, cin: int, num_keypoints: int, variant: int = 0, precisio
             elif int(st["NUM_CHANNELS"][b]) != int(extra["STAGE4"]["NUM_CHANNELS"][b]):
                 raise ValueError("branch widths must agree across stages")
     return s
-
-
-# refine -> the decoder of esahrnet_frames_keypoints; 2 has an entry point of its own (esahrnet_frames_keypoints_gaussfit)
-REFINE_DECODER = {"get_final": 0, "get_final2": 1, "gaussfit": 2}
 
 
 class _Node(nn.Module):
@@ -154,14 +150,6 @@ class HighResolutionNet(nn.Module):
             raise RuntimeError("HighResolutionNet (MI355X path) is inference-only: call .eval() "
                                "(the reference callers do, val.py:95 / demo.py:80)")
 
-    def _loader_args(self, frames, det_boxes, frame_idx, rule, mean, pixel_format):
-        """The loader's argument check and the rule's default mean, for the three loader calls (behind _inference_only and the
-        checks of their own arguments): -> (rule number, pixel format, number of boxes, mean)."""
-        rule_n, fmt, m = crops.check_device_loader_args(frames, det_boxes, frame_idx, rule, pixel_format)
-        if mean is None:
-            mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
-        return rule_n, fmt, m, mean
-
     OUTPUTS = ("heatmaps", "keypoints", "keypoints+index")
 
     def forward(self, x0: torch.Tensor, output: str = "heatmaps", refine: str = "get_final"):
@@ -200,7 +188,9 @@ class HighResolutionNet(nn.Module):
         (crops.MEAN_VAL / crops.MEAN_TRAIN).  -> (kp f32 [m,K,3], crop_boxes int32 [m,4], rates f64 [m], valid int32 [m]),
         all on the device; kp equals crops.crop_batch -> net(x, output="keypoints", refine=refine) bit for bit, except that
         the rows of an invalid crop (empty box, frame index out of range: valid == 0) are NaN."""
-        return self._frames_to_keypoints(frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format)[:4]
+        self._inference_only()
+        r = self._loader(LoaderRequest(refine), frames, det_boxes, frame_idx, scale, rule, mean, std, pixel_format)
+        return r["kp"], r["boxes"], r["rates"], r["valid"]
 
     def frames_to_correspondences(self, frames: torch.Tensor, det_boxes, frame_idx=None, scale: int = 256, rule: str = "val",
                                   refine: str = "get_final", thresh: float = 0.8, min_k: int = 24, weights: str = "peak",
@@ -216,21 +206,10 @@ class HighResolutionNet(nn.Module):
         (refine="gaussfit" only): esahrnet_frames_keypoints_gaussfit_cov, then esahrnet_correspondences(mode 1) with its info
         output: w = rate cov^(-1/2), the covariance of the fitted centre (inference.gaussfit_keypoints return_cov=True), zero
         where cov[0] < cov_floor."""
-        return self._frames_to_correspondences(frames, det_boxes, frame_idx, scale, rule, refine, thresh, min_k, weights, mean, std,
-                                               pixel_format, cov_floor)[:8]
-
-    def _frames_to_correspondences(self, frames, det_boxes, frame_idx, scale, rule, refine, thresh, min_k, weights, mean, std,
-                                   pixel_format, cov_floor=1e-6):
-        """frames_to_correspondences, plus (cpacked, packed): count, order, pts and w are views of `cpacked` (one uint8 buffer,
-        inference.pack_correspondences), which a caller that needs them on the host fetches with one copy; kp, crop_boxes, rates
-        and valid are views of `packed`, the keypoint record (inference.packed_layout), as _frames_to_keypoints returns it."""
         self._inference_only()
-        check_refine(refine)
-        mode = check_weights(weights, refine)
-        cov = check_cov_floor(cov_floor) if weights == "covariance" else None
-        rule_n, fmt, m, mean = self._loader_args(frames, det_boxes, frame_idx, rule, mean, pixel_format)
-        return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
-                                         REFINE_DECODER[refine], corr=(float(thresh), int(min_k), mode), cov=cov)
+        request = LoaderRequest(refine, None, cov_floor if weights == "covariance" else None, (thresh, min_k, weights))
+        r = self._loader(request, frames, det_boxes, frame_idx, scale, rule, mean, std, pixel_format)
+        return r["count"], r["order"], r["pts"], r["w"], r["kp"], r["boxes"], r["rates"], r["valid"]
 
     def keypoints_hessian(self, x0: torch.Tensor):
         """net(x, output="keypoints+index", refine="get_final2") with the Hessian of each step: -> (kp f32 [N,K,3], idx int32
@@ -288,28 +267,11 @@ class HighResolutionNet(nn.Module):
         the outputs asked for follow in net.candidates' order, [fit f64 [m,K,M,8], status int32 [m,K,M]], [hess f64 [m,K,M,3]],
         [cov, info f64 [m,K,M,3]], equal to crops.crop_batch -> net.candidates(x, ..., refine=...) bit for bit; in the rows of an
         invalid crop the f64 outputs are NaN and status is -1."""
-        out = self._frames_to_candidates(frames, det_boxes, frame_idx, scale, rule, candidates, nms_radius, mean, std, pixel_format,
-                                         refine, return_hessian, return_fit, return_cov, cov_floor)
-        if refine == "get_final":
-            return out[:4]
-        rest = list(out[6:])            # record_outputs' order: [cand_fit, cand_status,] cand_hess[, cand_cov, cand_info]
-        fit = (rest.pop(0), rest.pop(0)) if refine == "gaussfit" else ()
-        return (*out[:4], *(fit if return_fit else ()), *(rest[:1] if return_hessian else ()), *(rest[1:] if return_cov else ()))
-
-    def _frames_to_candidates(self, frames, det_boxes, frame_idx, scale, rule, candidates, nms_radius, mean, std, pixel_format,
-                              refine="get_final", return_hessian=False, return_fit=False, return_cov=False, cov_floor=1e-6):
-        """frames_to_candidates, plus (cidx int32 [m,K,M], packed): every output is a view of `packed` (one uint8 buffer,
-        inference.packed_layout(m, K, candidates=M)), so a caller that needs them on the host fetches them with one copy; cidx is
-        -1 in the rows of an invalid crop.  refine="get_final2" / "gaussfit": `packed` is the refined candidates' record
-        (inference.record_fields(K, "candidates_refined", refine == "gaussfit", return_cov, M)) and its decoder outputs follow it as
-        inference.record_outputs orders them: ([cand_fit, cand_status,] cand_hess[, cand_cov, cand_info]); the record holds the
-        Hessians (and a fit's parameters and status) whether or not the caller asked for them."""
         self._inference_only()
-        decoder, cov_floor = _check_at_outputs(refine, return_hessian, return_fit, return_cov, cov_floor)
-        rule_n, fmt, m, mean = self._loader_args(frames, det_boxes, frame_idx, rule, mean, pixel_format)
-        refined = None if decoder == 0 else (decoder, cov_floor if return_cov else None)
-        return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
-                                         0, cand=(int(candidates), int(nms_radius)), refined=refined)
+        _check_at_outputs(refine, return_hessian, return_fit, return_cov, cov_floor)
+        request = LoaderRequest(refine, (candidates, nms_radius), cov_floor if return_cov else None)
+        r = self._loader(request, frames, det_boxes, frame_idx, scale, rule, mean, std, pixel_format)
+        return candidate_returns(r, return_hessian, return_fit, return_cov)
 
     def frames_to_candidate_correspondences(self, frames: torch.Tensor, det_boxes, frame_idx=None, scale: int = 256,
                                             rule: str = "val", refine: str = "get_final", candidates: int = 3, nms_radius: int = 6,
@@ -325,34 +287,26 @@ class HighResolutionNet(nn.Module):
         calls on one stream (esahrnet_frames_keypoints_candidates[_refined], then esahrnet_correspondences_cand on its outputs);
         equal, bit for bit, to frames_to_candidates(refine=...) followed by inference.candidates_to_correspondences; capturable
         into a graph.  An invalid crop has count 0."""
-        return self._frames_to_candidate_correspondences(frames, det_boxes, frame_idx, scale, rule, refine, candidates, nms_radius,
-                                                         thresh, min_k, weights, mean, std, pixel_format, cov_floor)[:9]
-
-    def _frames_to_candidate_correspondences(self, frames, det_boxes, frame_idx, scale, rule, refine, candidates, nms_radius, thresh,
-                                             min_k, weights, mean, std, pixel_format, cov_floor=1e-6):
-        """frames_to_candidate_correspondences, plus (ccpacked, packed): the first five returns are views of `ccpacked` (one uint8
-        buffer, inference.pack_candidate_correspondences), which a caller that needs them on the host fetches with one copy;
-        cand, crop_boxes, rates and valid are views of `packed`, the candidates record as _frames_to_candidates returns it."""
         self._inference_only()
-        mode = check_weights(weights, refine)
-        decoder, cov_floor = _check_at_outputs(refine, weights == "hessian", False, weights == "covariance", cov_floor)
-        rule_n, fmt, m, mean = self._loader_args(frames, det_boxes, frame_idx, rule, mean, pixel_format)
-        refined = None if decoder == 0 else (decoder, cov_floor if weights == "covariance" else None)
-        return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
-                                         0, cand=(int(candidates), int(nms_radius)), refined=refined,
-                                         ccorr=(float(thresh), int(min_k), mode))
+        check_weights(weights, refine)
+        _check_at_outputs(refine, weights == "hessian", False, weights == "covariance", cov_floor)
+        request = LoaderRequest(refine, (candidates, nms_radius), cov_floor if weights == "covariance" else None,
+                                (thresh, min_k, weights))
+        r = self._loader(request, frames, det_boxes, frame_idx, scale, rule, mean, std, pixel_format)
+        return r["cpts"], r["cw"], r["cpeak"], r["count"], r["order"], r["cand"], r["boxes"], r["rates"], r["valid"]
 
-    def _frames_to_keypoints(self, frames, det_boxes, frame_idx, scale, rule, refine, mean, std, pixel_format, cov_floor=None):
-        """frames_to_keypoints, plus (idx int32 [m,K], packed): every output is a view of `packed` (one uint8 buffer), so a
-        caller that needs them on the host fetches them with one copy (pipeline.estimate_poses).  refine="gaussfit": plus (fit
-        f64 [m,K,8], status int32 [m,K], hess f64 [m,K,3]), views of `packed` too (inference.packed_layout); with cov_floor
-        (refine="gaussfit" only) plus (cov, info) f64 [m,K,3] behind them (esahrnet_frames_keypoints_gaussfit_cov)."""
+    def _loader(self, request: LoaderRequest, frames, det_boxes, frame_idx, scale, rule, mean, std, pixel_format) -> LoaderResult:
+        """The one loader call behind the four public ones (and parallel._sharded_loader, pipeline): the records `request` asks
+        for, every field a view of its record's one uint8 buffer (r["kp"], r["cidx"], r["count"], ...), so a caller that needs a
+        record on the host fetches it with one copy (LoaderResult.host).  The main record holds everything its decoder writes
+        (idx / cidx, a fit's parameters and status, the candidates' Hessians) whether or not a public call returns it; the rows
+        of an invalid crop are NaN, its cidx and status -1, its count 0."""
         self._inference_only()
-        check_refine(refine)
-        rule_n, fmt, m, mean = self._loader_args(frames, det_boxes, frame_idx, rule, mean, pixel_format)
-        cov = None if cov_floor is None else check_cov_floor(cov_floor)
-        return self._rt.frames_keypoints(self, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean), float(std),
-                                         REFINE_DECODER[refine], cov=cov)
+        rule_n, fmt, m = crops.check_device_loader_args(frames, det_boxes, frame_idx, rule, pixel_format)
+        if mean is None:                    # the rule's loader
+            mean = crops.MEAN_TRAIN if rule == "train" else crops.MEAN_VAL
+        return self._rt.frames_keypoints(self, request, frames, det_boxes, frame_idx, m, int(scale), rule_n, fmt, float(mean),
+                                         float(std))
 
     # ---- extras of the MI355X path ---------------------------------------------------------------
     @property
@@ -843,33 +797,50 @@ class _Runtime:
             module, x0, "candidates_refined", "esahrnet_forward_keypoints_candidates_refined", outputs, ws_key=("refined", decoder))
         return cand, cidx, {"fit": fit, "status": status, "hess": hess, "cov": cov, "info": info}
 
-    def frames_keypoints(self, module, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std, decoder, corr=None, cov=None,
-                         cand=None, refined=None, ccorr=None):
-        """esahrnet_frames_keypoints (arguments already checked by crops.check_device_loader_args).  The outputs are views
-        of one packed buffer (inference.record_fields / record_views), returned as inference.record_outputs orders them: rates f64
-        [m] | kp f32 [m,K,3] | crop_boxes int32 [m,4] | valid int32 [m] | idx int32 [m,K]; decoder 2, the Gaussian fit, also fit,
-        hess and status, returned behind `packed`.
-        Same device lock, weight-staleness key, workspace contract (graph capture included) and record_stream handling as
-        forward().  corr = (thresh, min_k, mode): esahrnet_frames_correspondences instead -> (count, order, pts, w, kp, boxes,
-        rates, valid, cpacked, packed), the first four views of `cpacked` (inference.pack_correspondences), the next four of
-        `packed`.  cov = cov_floor (decoder 2 only): esahrnet_frames_keypoints_gaussfit_cov; cov and info ride in `packed` behind
-        hess and are returned last, and the correspondences, if asked for with mode 1, take info in hess' place.  cand = (M,
-        nms_radius) (decoder 0, no corr): esahrnet_frames_keypoints_candidates instead -> (cand f32 [m,K,M,3], boxes, rates, valid,
-        cidx int32 [m,K,M], packed), views of the candidates record (inference.record_fields(K, "candidates", candidates=M)).
-        refined = (decoder 1 or 2 of esahrnet_keypoints_at, cov_floor or None) beside cand:
-        esahrnet_frames_keypoints_candidates_refined instead, on the record of kind "candidates_refined"; its decoder outputs follow
-        `packed` (inference.record_outputs).  ccorr = (thresh, min_k, mode) beside cand: esahrnet_correspondences_cand behind the
-        candidates' call on the same stream, mode 1 on the record's cand_info (refined with a cov_floor) or cand_hess -> (cpts, cw,
-        cpeak, count, order, cand, boxes, rates, valid, ccpacked, packed), the first five views of `ccpacked`
-        (inference.pack_candidate_correspondences)."""
-        if ccorr is not None and (cand is None or (ccorr[2] and refined is None)):
-            raise ValueError("the candidate correspondences belong to the candidates, their Hessian weights to a refined decoder")
-        if cand is not None and (decoder != 0 or corr is not None or cov is not None):
-            raise ValueError("the candidates belong to the get_final decoder, without correspondences")
-        if refined is not None and cand is None:
-            raise ValueError("a refined decoder belongs to the candidates")
-        if cov is not None and decoder != 2:
-            raise ValueError("the covariance of the fitted centre belongs to the Gaussian-fit decoder")
+    # The loader's library entries.  form -> (entry, workspace kind, that workspace's cache key, the entry's arguments between the
+    # loader's own and the workspace): a name is the pointer of that field of the result (None where no record has it), a callable
+    # takes the request.  ("candidates" / "gaussfit" as a cache key only keep that workspace apart from the other loader kinds.)
+    _PLACED = ("boxes", "rates", "valid")
+    _SELECTED = ("count", "order", "pts", "w")
+    _FITTED = ("kp", "idx", "fit", "status", "hess")
+    _SELECT = (lambda q: q.select[0], lambda q: q.select[1], lambda q: q.mode)
+    LOADER_ENTRIES = {
+        "keypoints": ("esahrnet_frames_keypoints", lambda q: "frames_final2" if q.decoder else "frames", lambda q: bool(q.decoder),
+                      (lambda q: q.decoder, "kp", "idx", *_PLACED)),
+        "correspondences": ("esahrnet_frames_correspondences", lambda q: "corr", lambda q: (q.decoder, q.mode),
+                            (lambda q: q.decoder, *_SELECT, "kp", "idx", *_PLACED, *_SELECTED)),
+        "gaussfit": ("esahrnet_frames_keypoints_gaussfit", lambda q: "frames_gaussfit", lambda q: "gaussfit", (*_FITTED, *_PLACED)),
+        "gaussfit_cov": ("esahrnet_frames_keypoints_gaussfit_cov", lambda q: "frames_gaussfit", lambda q: "gaussfit",
+                         (*_FITTED, *_PLACED, "cov", "info", lambda q: q.cov_floor)),
+        "candidates": ("esahrnet_frames_keypoints_candidates", lambda q: "frames_candidates", lambda q: "candidates",
+                       (lambda q: q.candidates[0], lambda q: q.candidates[1], "cand", "cidx", *_PLACED)),
+        "candidates_refined": ("esahrnet_frames_keypoints_candidates_refined", lambda q: "frames_candidates_refined",
+                               lambda q: ("refined", q.decoder),
+                               (lambda q: q.candidates[0], lambda q: q.candidates[1], lambda q: q.decoder, "cand", "cidx", "cand_hess",
+                                "cand_fit", "cand_status", "cand_cov", "cand_info", lambda q: float(q.cov_floor or 0.0), *_PLACED)),
+    }
+    # the correspondence stage of the two-call forms, behind the main entry on the same stream, on its outputs: second record ->
+    # (entry, its arguments behind the Hessian's pointer: m, k and M are the result's)
+    SECOND_ENTRIES = {
+        "correspondences": ("esahrnet_correspondences", "kp", (*_PLACED, "m", "k", *_SELECT, *_SELECTED)),
+        "candidate_correspondences": ("esahrnet_correspondences_cand", "cand",
+                                      (*_PLACED, "m", "k", "M", *_SELECT, "count", "order", "cpts", "cw", "cpeak")),
+    }
+
+    @staticmethod
+    def _loader_form(q):
+        if q.candidates is not None:
+            return q.main[0]                                        # "candidates" / "candidates_refined"
+        if q.refine == "gaussfit":                                  # its own entry points; the correspondences behind them
+            return "gaussfit" if q.cov_floor is None else "gaussfit_cov"
+        return "keypoints" if q.select is None else "correspondences"      # (one call does both for get_final / get_final2)
+
+    def frames_keypoints(self, module, request, frames, det_boxes, frame_idx, m, scale, rule, fmt, mean, std):
+        """The loader's library call for `request` (LOADER_ENTRIES; arguments already checked by crops.check_device_loader_args)
+        and, for the Gaussian fit and the candidates with a select, the correspondence stage behind it (SECOND_ENTRIES), which
+        takes the request's Hessian field, if any, where the entry takes a Hessian -> LoaderResult: the records of
+        inference.record_fields, the library's outputs written straight into them.  Same device lock, weight-staleness key,
+        workspace contract (graph capture included) and record_stream handling as forward()."""
         if module._cin != 1:
             raise ValueError(f"the loader makes 1-channel crops; this network takes {module._cin} channels")
         if "_master" not in module.__dict__:
@@ -879,73 +850,27 @@ class _Runtime:
         frames = frames.contiguous()
         dev = frames.device
         nframes, fh, fw = frames.shape[:3]
-        k = module._k
         ts = torch.cuda.current_stream(dev)
         stream = C.c_void_p(ts.cuda_stream)
+        form = self._loader_form(request)
+        entry, ws_kind, ws_key, spec = self.LOADER_ENTRIES[form]
         with torch.cuda.device(dev):
             det = crops.to_device_int32(det_boxes, dev)
             fidx = None if frame_idx is None else crops.to_device_int32(frame_idx, dev)
-            if refined is not None:
-                fields = record_fields(k, "candidates_refined", refined[0] == 2, refined[1] is not None, cand[0])
-            else:
-                fields = record_fields(k, "keypoints" if cand is None else "candidates", decoder == 2, cov is not None,
-                                       None if cand is None else cand[0])
-            packed = torch.empty(m * sum(b for _, b in fields), dtype=torch.uint8, device=dev)
-            views = record_views(packed, m, k, fields)
-            out = record_outputs(views, packed)
-            p = {name: t.data_ptr() for name, t in views.items()}
-            if corr is not None:
-                thresh, min_k, mode = corr
-                count, order, pts, w, cpacked = pack_correspondences(m, k, dev)
-                out = (count, order, pts, w, *out[:4], cpacked, packed)
-                selected = (count.data_ptr(), order.data_ptr(), pts.data_ptr(), w.data_ptr())
-            if ccorr is not None:       # (M as the candidates record has it: record_fields has refused a bad one)
-                cc = pack_candidate_correspondences(m, k, views["cand"].shape[2], dev)
-                out = (*cc[:5], *out[:4], cc[5], packed)
+            out = LoaderResult.empty(request, m, module._k, dev)
+            p = {name: t.data_ptr() for name, t in out.views.items()}
+            p.update(m=m, k=module._k, M=request.main[3])
+            args = lambda names: [a(request) if callable(a) else p.get(a) for a in names]        # noqa: E731
             with self._device_lock(dev.index):
                 h = self._handle_for(module, dev)
                 _lib.check(self.lib.esahrnet_set_debug_keep(h, 0))
-                loader = (h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m,
-                          scale, rule, mean, std)
-                placed = (p["boxes"], p["rates"], p["valid"])
-                if refined is not None:
-                    ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, ("refined", refined[0]),
-                                                           kind="frames_candidates_refined")
-                    _lib.check(self.lib.esahrnet_frames_keypoints_candidates_refined(
-                        *loader, int(cand[0]), int(cand[1]), refined[0], p["cand"], p["cidx"], p["cand_hess"], p.get("cand_fit"),
-                        p.get("cand_status"), p.get("cand_cov"), p.get("cand_info"), float(refined[1] or 0.0), *placed, ws_ptr,
-                        ws_bytes, stream))
-                elif cand is not None:
-                    # ("candidates" as the cache key's `keep`: it only keeps this workspace apart from the other loader kinds)
-                    ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, "candidates", kind="frames_candidates")
-                    _lib.check(self.lib.esahrnet_frames_keypoints_candidates(*loader, int(cand[0]), int(cand[1]), p["cand"],
-                                                                             p["cidx"], *placed, ws_ptr, ws_bytes, stream))
-                elif decoder == 2:                  # its own entry points; the correspondences, if asked for, behind them
-                    ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, "gaussfit", kind="frames_gaussfit")
-                    fitted = (p["kp"], p["idx"], p["fit"], p["status"], p["hess"])
-                    if cov is not None:
-                        _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit_cov(
-                            *loader, *fitted, *placed, p["cov"], p["info"], float(cov), ws_ptr, ws_bytes, stream))
-                    else:
-                        _lib.check(self.lib.esahrnet_frames_keypoints_gaussfit(*loader, *fitted, *placed, ws_ptr, ws_bytes, stream))
-                    if corr is not None:
-                        wsrc = p["info"] if cov is not None else p["hess"]   # weights="covariance": -cov^-1 in the Hessian's place
-                        _lib.check(self.lib.esahrnet_correspondences(
-                            p["kp"], wsrc if mode else None, *placed, m, k, thresh, min_k, mode, *selected, stream))
-                elif corr is not None:
-                    ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, (decoder, mode), kind="corr")
-                    _lib.check(self.lib.esahrnet_frames_correspondences(
-                        *loader, decoder, thresh, min_k, mode, p["kp"], p["idx"], *placed, *selected, ws_ptr, ws_bytes, stream))
-                else:
-                    ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, bool(decoder),
-                                                           kind="frames_final2" if decoder else "frames")
-                    _lib.check(self.lib.esahrnet_frames_keypoints(*loader, decoder, p["kp"], p["idx"], *placed, ws_ptr, ws_bytes,
-                                                                  stream))
-                if ccorr is not None:               # behind the candidates' call, on its outputs
-                    wsrc = p.get("cand_info", p.get("cand_hess")) if ccorr[2] else None    # "covariance": -cov^-1 as the Hessian
-                    _lib.check(self.lib.esahrnet_correspondences_cand(
-                        p["cand"], wsrc, *placed, m, k, views["cand"].shape[2], ccorr[0], ccorr[1], ccorr[2], cc[3].data_ptr(),
-                        cc[4].data_ptr(), cc[0].data_ptr(), cc[1].data_ptr(), cc[2].data_ptr(), stream))
+                ws, ws_ptr, ws_bytes = self._workspace(h, dev, ts, m, scale, scale, ws_key(request), kind=ws_kind(request))
+                _lib.check(getattr(self.lib, entry)(
+                    h, frames.data_ptr(), nframes, fh, fw, fmt, det.data_ptr(), None if fidx is None else fidx.data_ptr(), m, scale,
+                    rule, mean, std, *args(spec), ws_ptr, ws_bytes, stream))
+                if request.second is not None and form != "correspondences":
+                    second, rows, spec2 = self.SECOND_ENTRIES[request.second]
+                    _lib.check(getattr(self.lib, second)(p[rows], p.get(request.hessian), *args(spec2), stream))
         for t in (ws, frames, det, fidx):
             if t is not None:
                 t.record_stream(ts)

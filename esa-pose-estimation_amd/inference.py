@@ -14,6 +14,7 @@ and numpy-in/numpy-out contract for callers that are not rewritten, but run the 
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import heapq
 import math
 
@@ -382,13 +383,13 @@ def _field_bytes(name, k, mm=1):
 
 
 def record_fields(k: int, kind: str, gaussfit: bool = False, cov: bool = False, candidates=None):
-    """The fields of a packed record in memory order, as ((name, bytes per crop), ...): kind="keypoints" the buffer of
-    net._frames_to_keypoints (rates | [fit | hess | [cov | info]] | kp | boxes | valid | idx | [status]), kind="correspondences"
-    the buffer of pack_correspondences (pts | w | count | order), kind="candidates" the buffer of net._frames_to_candidates with
-    candidates=M (rates | cand | boxes | valid | cidx), kind="candidates_refined" the buffer of net._frames_to_candidates with a
+    """The fields of a packed record in memory order, as ((name, bytes per crop), ...): kind="keypoints" the main record of
+    net._loader (rates | [fit | hess | [cov | info]] | kp | boxes | valid | idx | [status]), kind="correspondences"
+    the buffer of pack_correspondences (pts | w | count | order), kind="candidates" net._loader's main record of a request with
+    candidates=(M, r) (rates | cand | boxes | valid | cidx), kind="candidates_refined" that of a request with candidates and a
     refine other than "get_final" (rates | [cand_fit] | cand_hess | [cand_cov | cand_info] | cand | boxes | valid | cidx |
     [cand_status]: the decoder's outputs for every candidate, f64 first; gaussfit=True is refine="gaussfit", False "get_final2"),
-    kind="candidate_correspondences" the buffer of net._frames_to_candidate_correspondences with candidates=M (cpts | cw | cpeak |
+    kind="candidate_correspondences" net._loader's second record of a request with candidates and select (cpts | cw | cpeak |
     count | order: what pnp.candidate_correspondences_to_pose_batch consumes; whatever the decoder, no gaussfit / cov switch).
     A record is field-major, so field f of m crops takes m * bytes and
     starts at m * (the bytes of the fields in front of it); every size is a multiple of 4.  This is the description the views
@@ -434,15 +435,114 @@ def record_views(packed, m: int, k: int, fields):
     return out
 
 
-def record_outputs(views, packed):
-    """The views of a keypoint record (or of a candidates record: cand and cidx in kp's and idx' places) -> what
-    net._frames_to_keypoints returns: (kp, boxes, rates, valid, idx, packed[, fit, status, hess[, cov, info]]); of a refined
-    candidates' record (cand, boxes, rates, valid, cidx, packed, [cand_fit, cand_status,] cand_hess[, cand_cov, cand_info])."""
-    v = views
-    rows, index = ("kp", "idx") if "kp" in v else ("cand", "cidx")
-    return (v[rows], v["boxes"], v["rates"], v["valid"], v[index], packed,
-            *(v[n] for n in ("fit", "status", "hess", "cov", "info", "cand_fit", "cand_status", "cand_hess", "cand_cov", "cand_info")
-              if n in v))
+@dataclasses.dataclass(frozen=True)
+class LoaderRequest:
+    """What a caller asks of the device loader (net._loader, parallel._sharded_loader), in its four independent parts.  refine:
+    the decoder.  candidates: None, or (M, nms_radius), the M best peaks of every heat-map.  cov_floor: None, or the floor of the
+    covariance outputs, which the main record then carries.  select: None, or (thresh, min_k, weights), the solver-ready second
+    record.  The constructor refuses what the public entries refuse, with their texts; everything the loader, the exchange and the
+    solve need to know of the records is derived here, once."""
+    refine: str = "get_final"
+    candidates: tuple = None
+    cov_floor: float = None
+    select: tuple = None
+
+    def __post_init__(self):
+        check_refine(self.refine)
+        if self.select is not None:
+            thresh, min_k, weights = self.select
+            check_weights(weights, self.refine)
+            object.__setattr__(self, "select", (float(thresh), int(min_k), weights))
+        if self.cov_floor is not None:
+            if self.candidates is not None:
+                _check_at_outputs(self.refine, False, False, True, self.cov_floor)
+            elif self.refine != "gaussfit":
+                raise ValueError("the covariance of the fitted centre belongs to the Gaussian-fit decoder")
+            object.__setattr__(self, "cov_floor", check_cov_floor(self.cov_floor))
+        if self.candidates is not None:
+            mm, radius = self.candidates
+            record_fields(1, "candidates", candidates=mm)                   # its range of M, with its text
+            object.__setattr__(self, "candidates", (int(mm), int(radius)))
+
+    @property
+    def decoder(self) -> int:
+        """The decoder's number in the ABI (include/esahrnet.h)."""
+        return REFINES.index(self.refine)
+
+    @property
+    def main(self):
+        """The main record, as record_fields takes it behind k: (kind, gaussfit, cov, candidates)."""
+        gaussfit, cov = self.refine == "gaussfit", self.cov_floor is not None
+        if self.candidates is None:
+            return "keypoints", gaussfit, cov, None
+        return "candidates" if self.refine == "get_final" else "candidates_refined", gaussfit, cov, self.candidates[0]
+
+    @property
+    def second(self):
+        """The kind of the solver-ready record, None without select."""
+        if self.select is None:
+            return None
+        return "correspondences" if self.candidates is None else "candidate_correspondences"
+
+    @property
+    def kinds(self):
+        """The records of a result, in the order of their exchange: the second record, if any, first."""
+        return tuple(kind for kind in (self.second, self.main[0]) if kind is not None)
+
+    @property
+    def mode(self) -> int:
+        """The mode of esahrnet_correspondences[_cand]: 1 with a 2x2 weight from the decoder, 0 with the peak (or no select)."""
+        return int(self.select is not None and self.select[2] != "peak")
+
+    @property
+    def hessian(self):
+        """The field of the main record that the correspondence stage takes as the Hessian: hess, or info where the record carries
+        the covariance outputs (weights="covariance": -cov^-1 in the Hessian's place); cand_hess or cand_info for the candidates;
+        None with mode 0, and for get_final2 without candidates, where esahrnet_frames_correspondences forms the Hessian itself."""
+        if not self.mode or (self.candidates is None and self.refine != "gaussfit"):
+            return None
+        return ("cand_" if self.candidates is not None else "") + ("info" if self.cov_floor is not None else "hess")
+
+    def fields(self, k: int) -> dict:
+        """kind -> record_fields(k, kind, ...) of every record of the result, in the order of `kinds`."""
+        main = self.main
+        return {kind: record_fields(k, *main) if kind == main[0] else record_fields(k, kind, candidates=main[3])
+                for kind in self.kinds}
+
+
+class LoaderResult:
+    """What the loader answers: m crops of k keypoints, `records`: kind -> (packed uint8 buffer, fields), and r[name] the typed
+    view (record_views) of a field, e.g. r["kp"], r["cand_hess"], r["count"]; the field names of a call's main and second record
+    are disjoint, so one namespace (`views`: name -> tensor) holds both."""
+
+    def __init__(self, m: int, k: int, records: dict):
+        self.m, self.k, self.records = m, k, records
+        self.views = {name: t for packed, fields in records.values() for name, t in record_views(packed, m, k, fields).items()}
+
+    @classmethod
+    def empty(cls, request: LoaderRequest, m: int, k: int, device):
+        """The records of `request` for m crops, allocated on `device` and not initialised."""
+        return cls(m, k, {kind: (torch.empty(m * sum(b for _, b in fields), dtype=torch.uint8, device=device), fields)
+                          for kind, fields in request.fields(k).items()})
+
+    def __getitem__(self, name):
+        return self.views[name]
+
+    def __contains__(self, name):
+        return name in self.views
+
+    def host(self, kind: str) -> dict:
+        """A path's only device->host copy: ONE .cpu() of the record of `kind`, -> its numpy views (record_views)."""
+        packed, fields = self.records[kind]
+        return record_views(packed.cpu().numpy(), self.m, self.k, fields)
+
+
+def candidate_returns(r: LoaderResult, return_hessian, return_fit, return_cov):
+    """What net.frames_to_candidates returns, out of the loader's result: (cand, crop_boxes, rates, valid) and the decoder outputs
+    asked for, in net.candidates' order."""
+    names = ("cand", "boxes", "rates", "valid", *(("cand_fit", "cand_status") if return_fit else ()),
+             *(("cand_hess",) if return_hessian else ()), *(("cand_cov", "cand_info") if return_cov else ()))
+    return tuple(r[n] for n in names)
 
 
 def packed_layout(m: int, k: int, gaussfit: bool = False, cov: bool = False, candidates=None, kind=None):

@@ -214,30 +214,28 @@ def _shard_args(det_boxes, frame_idx, lo, hi, n_total, frame_base):
     return det_boxes[lo:hi], idx
 
 
-def _sharded_frames_to_keypoints(net, frames, det_boxes, frame_idx, group, frame_base, scale, rule, refine, mean, std, pixel_format,
-                                 cov_floor=None):
-    """sharded_frames_to_keypoints with the returns of net._frames_to_keypoints: (kp, crop_boxes, rates, valid, idx, packed),
-    refine="gaussfit" plus (fit, status, hess), with cov_floor plus (cov, info); all views of `packed`."""
-    from . import inference
-    inference.check_refine(refine)
-    gauss, cov = refine == "gaussfit", cov_floor is not None
+def _sharded_loader(net, request, frames, det_boxes, frame_idx, group, frame_base, scale, rule, mean, std, pixel_format, gather=None):
+    """net._loader over the ranks of `group` -> the LoaderResult of the whole batch on every rank: rank r runs boxes [lo_r, hi_r)
+    through net._loader, one call (none on an empty shard), and each record named in `gather` (default: every record of the
+    request) is exchanged by one gather_records.  The request has made its checks before any shard work starts."""
+    from .inference import LoaderResult
     k, n_total = net.num_keypoints, len(det_boxes)
-    fields = inference.record_fields(k, "keypoints", gauss, cov)
+    fields = request.fields(k)
     lo, hi = _shard_of(n_total, group)
     local = None
     if hi > lo:
         boxes, idx = _shard_args(det_boxes, frame_idx, lo, hi, n_total, frame_base)
-        local = net._frames_to_keypoints(frames, boxes, idx, scale, rule, refine, mean, std, pixel_format,
-                                         *((cov_floor,) if cov else ()))[5]
-    packed = gather_records(local, hi - lo, n_total, fields, group, device=frames.device)
-    return inference.record_outputs(inference.record_views(packed, n_total, k, fields), packed)
+        local = net._loader(request, frames, boxes, idx, scale, rule, mean, std, pixel_format)
+    return LoaderResult(n_total, k, {kind: (gather_records(None if local is None else local.records[kind][0], hi - lo, n_total,
+                                                           fields[kind], group, device=frames.device), fields[kind])
+                                     for kind in (request.kinds if gather is None else gather)})
 
 
 def sharded_frames_to_keypoints(net, frames, det_boxes, frame_idx=None, *, group=None, frame_base: int = 0, scale: int = 256,
                                 rule: str = "val", refine: str = "get_final", mean=None, std: float = STD, pixel_format=None,
                                 return_cov: bool = False, cov_floor: float = 1e-6):
     """net.frames_to_keypoints over the ranks of `group`: EVERY rank passes the full list of boxes (and frame indices); rank r
-    runs boxes [lo_r, hi_r) (shard_bounds) through net._frames_to_keypoints, one library call, and the packed records are
+    runs boxes [lo_r, hi_r) (shard_bounds) through net._loader, one library call, and the packed records are
     gathered (gather_records: one all-gather, one kernel).  Every rank returns the whole batch's (kp f32 [m,K,3], crop_boxes
     int32 [m,4], rates f64 [m], valid int32 [m]) as views of one packed buffer, the bits the single-device call gives;
     refine="gaussfit" appends (fit f64 [m,K,8], status int32 [m,K], hess f64 [m,K,3]) and return_cov=True (gaussfit only)
@@ -245,35 +243,12 @@ def sharded_frames_to_keypoints(net, frames, det_boxes, frame_idx=None, *, group
     frames, or only the frames this rank holds with frame_base = b: frames[0] is batch frame b and the indices are rebased by
     -b; an index that falls outside gives valid = 0 and NaN rows, as it does on one device.  Other keywords as
     net.frames_to_keypoints.  An empty shard makes no library call."""
+    from .inference import LoaderRequest
     if return_cov and refine != "gaussfit":
         raise ValueError("return_cov=True needs refine='gaussfit': only the Gaussian fit has a parameter covariance")
-    out = _sharded_frames_to_keypoints(net, frames, det_boxes, frame_idx, group, int(frame_base), scale, rule, refine, mean, std,
-                                       pixel_format, cov_floor if return_cov else None)
-    return out[:4] + out[6:]
-
-
-def _sharded_frames_to_correspondences(net, frames, det_boxes, frame_idx, group, frame_base, scale, rule, refine, thresh, min_k,
-                                       weights, mean, std, pixel_format, cov_floor=1e-6):
-    """sharded_frames_to_correspondences with the returns of net._frames_to_correspondences: plus (cpacked, packed), the
-    correspondence record and the keypoint record of the whole batch."""
-    from . import inference
-    inference.check_refine(refine)
-    inference.check_weights(weights, refine)
-    gauss, cov = refine == "gaussfit", weights == "covariance"
-    k, n_total = net.num_keypoints, len(det_boxes)
-    cfields = inference.record_fields(k, "correspondences")
-    kfields = inference.record_fields(k, "keypoints", gauss, cov)
-    lo, hi = _shard_of(n_total, group)
-    clocal = klocal = None
-    if hi > lo:
-        boxes, idx = _shard_args(det_boxes, frame_idx, lo, hi, n_total, frame_base)
-        clocal, klocal = net._frames_to_correspondences(frames, boxes, idx, scale, rule, refine, thresh, min_k, weights, mean, std,
-                                                        pixel_format, cov_floor)[8:10]
-    cpacked = gather_records(clocal, hi - lo, n_total, cfields, group, device=frames.device)
-    packed = gather_records(klocal, hi - lo, n_total, kfields, group, device=frames.device)
-    c = inference.record_views(cpacked, n_total, k, cfields)
-    out = inference.record_outputs(inference.record_views(packed, n_total, k, kfields), packed)
-    return (c["count"], c["order"], c["pts"], c["w"], *out[:4], cpacked, packed)
+    request = LoaderRequest(refine, None, cov_floor if return_cov else None)
+    r = _sharded_loader(net, request, frames, det_boxes, frame_idx, group, int(frame_base), scale, rule, mean, std, pixel_format)
+    return tuple(r[n] for n in ("kp", "boxes", "rates", "valid", "fit", "status", "hess", "cov", "info") if n in r)
 
 
 def sharded_frames_to_correspondences(net, frames, det_boxes, frame_idx=None, *, group=None, frame_base: int = 0,
@@ -285,28 +260,10 @@ def sharded_frames_to_correspondences(net, frames, det_boxes, frame_idx=None, *,
     int32 [m,K], pts f64 [m,K,2], w f64 [m,K,3], kp, crop_boxes, rates, valid) of the whole batch on every rank, the bits of the
     single-device call.  TWO records are gathered, the correspondence record (the first four) and the keypoint record (the
     last four): two all-gathers and two kernel launches per step."""
-    return _sharded_frames_to_correspondences(net, frames, det_boxes, frame_idx, group, int(frame_base), scale, rule, refine,
-                                              thresh, min_k, weights, mean, std, pixel_format, cov_floor)[:8]
-
-
-def _sharded_frames_to_candidates(net, frames, det_boxes, frame_idx, group, frame_base, scale, rule, candidates, nms_radius, mean,
-                                  std, pixel_format, refine="get_final", return_hessian=False, return_fit=False, return_cov=False,
-                                  cov_floor=1e-6):
-    """sharded_frames_to_candidates with the returns of net._frames_to_candidates: (cand, crop_boxes, rates, valid, cidx, packed)
-    and, with a refine other than "get_final", the decoder outputs behind `packed` as inference.record_outputs orders them."""
-    from . import inference
-    inference._check_at_outputs(refine, return_hessian, return_fit, return_cov, cov_floor)
-    k, n_total = net.num_keypoints, len(det_boxes)
-    kind = "candidates" if refine == "get_final" else "candidates_refined"
-    fields = inference.record_fields(k, kind, refine == "gaussfit", bool(return_cov), candidates)
-    lo, hi = _shard_of(n_total, group)
-    local = None
-    if hi > lo:
-        boxes, idx = _shard_args(det_boxes, frame_idx, lo, hi, n_total, frame_base)
-        local = net._frames_to_candidates(frames, boxes, idx, scale, rule, candidates, nms_radius, mean, std, pixel_format, refine,
-                                          return_hessian, return_fit, return_cov, cov_floor)[5]
-    packed = gather_records(local, hi - lo, n_total, fields, group, device=frames.device)
-    return inference.record_outputs(inference.record_views(packed, n_total, k, fields), packed)
+    from .inference import LoaderRequest
+    request = LoaderRequest(refine, None, cov_floor if weights == "covariance" else None, (thresh, min_k, weights))
+    r = _sharded_loader(net, request, frames, det_boxes, frame_idx, group, int(frame_base), scale, rule, mean, std, pixel_format)
+    return r["count"], r["order"], r["pts"], r["w"], r["kp"], r["boxes"], r["rates"], r["valid"]
 
 
 def sharded_frames_to_candidates(net, frames, det_boxes, frame_idx=None, *, group=None, frame_base: int = 0, scale: int = 256,
@@ -317,33 +274,11 @@ def sharded_frames_to_candidates(net, frames, det_boxes, frame_idx=None, *, grou
     every rank, rank r runs boxes [lo_r, hi_r), frame_idx=None and frame_base as there, no library call on an empty shard): the
     "candidates" record, or with a refine other than "get_final" the "candidates_refined" record, is gathered (one all-gather, one
     kernel) and every rank returns what net.frames_to_candidates returns for the whole batch, the bits of the single-device call."""
-    out = _sharded_frames_to_candidates(net, frames, det_boxes, frame_idx, group, int(frame_base), scale, rule, candidates,
-                                        nms_radius, mean, std, pixel_format, refine, return_hessian, return_fit, return_cov, cov_floor)
-    if refine == "get_final":
-        return out[:4]
-    rest = list(out[6:])                # record_outputs' order: [cand_fit, cand_status,] cand_hess[, cand_cov, cand_info]
-    fit = (rest.pop(0), rest.pop(0)) if refine == "gaussfit" else ()
-    return (*out[:4], *(fit if return_fit else ()), *(rest[:1] if return_hessian else ()), *(rest[1:] if return_cov else ()))
-
-
-def _sharded_frames_to_candidate_correspondences(net, frames, det_boxes, frame_idx, group, frame_base, scale, rule, refine,
-                                                 candidates, nms_radius, thresh, min_k, weights, mean, std, pixel_format,
-                                                 cov_floor=1e-6):
-    """sharded_frames_to_candidate_correspondences, plus ccpacked, the record of the whole batch its returns are views of."""
     from . import inference
-    inference.check_refine(refine)
-    inference.check_weights(weights, refine)
-    k, n_total = net.num_keypoints, len(det_boxes)
-    fields = inference.record_fields(k, "candidate_correspondences", candidates=candidates)
-    lo, hi = _shard_of(n_total, group)
-    local = None
-    if hi > lo:
-        boxes, idx = _shard_args(det_boxes, frame_idx, lo, hi, n_total, frame_base)
-        local = net._frames_to_candidate_correspondences(frames, boxes, idx, scale, rule, refine, candidates, nms_radius, thresh,
-                                                         min_k, weights, mean, std, pixel_format, cov_floor)[9]
-    ccpacked = gather_records(local, hi - lo, n_total, fields, group, device=frames.device)
-    c = inference.record_views(ccpacked, n_total, k, fields)
-    return (c["cpts"], c["cw"], c["cpeak"], c["count"], c["order"], ccpacked)
+    inference._check_at_outputs(refine, return_hessian, return_fit, return_cov, cov_floor)
+    request = inference.LoaderRequest(refine, (candidates, nms_radius), cov_floor if return_cov else None)
+    r = _sharded_loader(net, request, frames, det_boxes, frame_idx, group, int(frame_base), scale, rule, mean, std, pixel_format)
+    return inference.candidate_returns(r, return_hessian, return_fit, return_cov)
 
 
 def sharded_frames_to_candidate_correspondences(net, frames, det_boxes, frame_idx=None, *, group=None, frame_base: int = 0,
@@ -355,9 +290,13 @@ def sharded_frames_to_candidate_correspondences(net, frames, det_boxes, frame_id
     (cpts f64 [m,K,M,2], cw f64 [m,K,M,3], cpeak f32 [m,K,M], count int32 [m], order int32 [m,K]) of the whole batch on every rank,
     the bits of the single-device call.  ONE record is gathered, the one pnp.candidate_correspondences_to_pose_batch consumes: one
     all-gather and one kernel launch per step; the candidates record stays on the rank that decoded it."""
-    return _sharded_frames_to_candidate_correspondences(net, frames, det_boxes, frame_idx, group, int(frame_base), scale, rule,
-                                                        refine, candidates, nms_radius, thresh, min_k, weights, mean, std,
-                                                        pixel_format, cov_floor)[:5]
+    from .inference import LoaderRequest, check_cov_floor
+    request = LoaderRequest(refine, (candidates, nms_radius), cov_floor if weights == "covariance" else None,
+                            (thresh, min_k, weights))
+    check_cov_floor(cov_floor)              # (refused whatever the weights, as on one device)
+    r = _sharded_loader(net, request, frames, det_boxes, frame_idx, group, int(frame_base), scale, rule, mean, std, pixel_format,
+                        gather=("candidate_correspondences",))
+    return r["cpts"], r["cw"], r["cpeak"], r["count"], r["order"]
 
 
 # ---- the measurement protocol of bench.py, importable so that the N > 1 branch runs under gloo on the CPU too ----

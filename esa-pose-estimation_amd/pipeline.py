@@ -162,7 +162,7 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
     device_loader, device_select, distributed, native=False and any other refine; candidates=1 leaves every path as it is.
     candidates_path (with candidates > 1 only) says where the runner-ups are decoded: "heatmaps" (default) as above; "fused":
     host crops, then net.candidates(x, M, nms_radius), the decoder in the forward, no heat-map tensor in caller memory; "loader":
-    net._frames_to_candidates does the box rule, the crops, the forward and the decoder in one library call and ONE device->host
+    net._loader does the box rule, the crops, the forward and the candidate decoder in one library call and ONE device->host
     copy of its packed buffer feeds the solve — bboxes are integers, frame_idx and rule are accepted and an invalid crop has no
     pose, as with device_loader=True.  The poses, .used and .rescued are those of "heatmaps", bit for bit."""
     inference.check_refine(refine)
@@ -202,7 +202,8 @@ def estimate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, scale: int = 256,
     elif device_loader:
         poses, rep = _device_loader_poses(net, frames, bboxes, frame_idx, distributed, scale, rule, refine, solve)
     elif candidates != 1 and candidates_path == "loader":
-        poses, rep = _loader_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, solve)
+        poses, rep = _loader_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, "get_final", "peak",
+                                              None, lambda rows, boxes, rates, hess: solve(rows, boxes, rates))
     else:
         poses, rep = _host_crops_poses(net, frames, bboxes, frame_idx, scale, rule, refine, distributed, keypoints_only,
                                        candidates, nms_radius, candidates_path, solve)
@@ -229,12 +230,12 @@ def candidate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, candidates: int 
     estimate_poses(..., candidates=M), bit for bit.
     candidates_path says where the candidates are decoded, as in estimate_poses: "heatmaps" (default) as above; "fused": host
     crops, then net.candidates(x, candidates, nms_radius, refine=refine, ...), search and refinement inside the forward's one
-    library call, no heat-map tensor in caller memory; "loader": net._frames_to_candidates(..., refine=refine) does the box rule,
+    library call, no heat-map tensor in caller memory; "loader": net._loader (candidates=(M, nms_radius), refine=refine) does the box rule,
     the crops, the forward and the refined candidates in one library call and ONE device->host copy of its packed record
     (inference.record_fields(K, "candidates_refined", ...)) feeds the same solve with the loader's boxes and rates -- bboxes are
     integers, frame_idx and rule are accepted, and a crop the loader could not make has the NaN pose: on_fail applies, its report
     row is that of "fewer than 4" with n = 0.  The poses, the report, .used and .rescued are those of "heatmaps", bit for bit.
-    device_select=True (implies the loader; candidates_path stays at its default): net._frames_to_candidate_correspondences also
+    device_select=True (implies the loader; candidates_path stays at its default): net._loader, asked for a select, also
     does the top-k rule, the ordering, the back-projection and the 2x2 weight of EVERY candidate on the device
     (esahrnet_correspondences_cand behind the loader's call), ONE device->host copy of that one record
     (inference.record_fields(K, "candidate_correspondences", candidates=M)), then pnp.candidate_correspondences_to_pose_batch: the
@@ -269,8 +270,8 @@ def candidate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, candidates: int 
         poses, rep = _device_select_candidate_poses(net, frames, bboxes, frame_idx, distributed, scale, rule, refine, candidates,
                                                     nms_radius, thresh, min_k, weights, cov_floor, kp3d, K, min_ratio, threads, want)
     elif candidates_path == "loader":
-        poses, rep = _loader_refined_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, refine,
-                                                      weights, ask, solve, distributed)
+        poses, rep = _loader_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, refine, weights,
+                                              cov_floor, solve, distributed)
     else:
         x, boxes, rates = crops.crop_batch(frames, bboxes, scale)
         with torch.no_grad():
@@ -293,9 +294,14 @@ def candidate_poses(net, frames: torch.Tensor, bboxes, kp3d, K, candidates: int 
     return (poses, rep) if return_report else poses
 
 
-def _fetch(packed, m, k, fields):
-    """A path's only device->host copy: the packed record of m crops, and its numpy views (inference.record_views)."""
-    return inference.record_views(packed.cpu().numpy(), m, k, fields)
+def _load(net, request, frames, bboxes, frame_idx, distributed, scale, rule, gather=None):
+    """The loader's result for `request`: the net's own call, or with distributed=True every rank its shard of the boxes and the
+    records of `gather` (default: all of the request's) gathered, all crops on all ranks."""
+    with torch.no_grad():
+        if distributed:
+            return parallel._sharded_loader(net, request, frames, bboxes, frame_idx, None, 0, scale, rule, None, crops.STD, None,
+                                            gather=gather)
+        return net._loader(request, frames, bboxes, frame_idx, scale, rule, None, crops.STD, None)
 
 
 def _solve_valid_crops(rows, v, solve):
@@ -320,75 +326,38 @@ def _solve_valid_crops(rows, v, solve):
 
 def _device_select_poses(net, frames, bboxes, frame_idx, distributed, scale, rule, refine, thresh, min_k, weights, cov_floor, kp3d, K,
                          threads, want):
-    """device_select=True."""
-    with torch.no_grad():
-        if distributed:                     # every rank its shard of the boxes, then the two records gathered: all poses on all ranks
-            out = parallel._sharded_frames_to_correspondences(net, frames, bboxes, frame_idx, None, 0, scale, rule, refine, thresh,
-                                                              min_k, weights, None, crops.STD, None, cov_floor)
-        else:
-            out = net._frames_to_correspondences(frames, bboxes, frame_idx, scale, rule, refine, thresh, min_k, weights, None,
-                                                 crops.STD, None, cov_floor)
-    m, k = out[4].shape[:2]
-    v = _fetch(out[8], m, k, inference.record_fields(k, "correspondences"))
+    """device_select=True: the correspondence record's one copy, then the solve on it."""
+    request = inference.LoaderRequest(refine, None, cov_floor if weights == "covariance" else None, (thresh, min_k, weights))
+    r = _load(net, request, frames, bboxes, frame_idx, distributed, scale, rule)
+    v = r.host("correspondences")
     q, t, *rep = pnp.correspondences_to_pose_batch(v["pts"], v["w"], v["count"], v["order"], kp3d, np.asarray(K, np.float64), threads,
                                                    report=want)
-    return [(q[i], t[i]) for i in range(m)], rep[0] if want else None
+    return [(q[i], t[i]) for i in range(r.m)], rep[0] if want else None
 
 
 def _device_loader_poses(net, frames, bboxes, frame_idx, distributed, scale, rule, refine, solve):
     """device_loader=True."""
-    with torch.no_grad():
-        if distributed:
-            out = parallel._sharded_frames_to_keypoints(net, frames, bboxes, frame_idx, None, 0, scale, rule, refine, None,
-                                                        crops.STD, None)
-        else:
-            out = net._frames_to_keypoints(frames, bboxes, frame_idx, scale, rule, refine, None, crops.STD, None)
-    m, k = out[0].shape[:2]
-    v = _fetch(out[5], m, k, inference.record_fields(k, "keypoints", refine == "gaussfit"))
+    v = _load(net, inference.LoaderRequest(refine), frames, bboxes, frame_idx, distributed, scale, rule).host("keypoints")
     return _solve_valid_crops(v["kp"], v, solve)
-
-
-def _loader_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, solve):
-    """candidates > 1 with candidates_path="loader"."""
-    with torch.no_grad():
-        out = net._frames_to_candidates(frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, None, crops.STD, None)
-    m, k, mm = out[0].shape[:3]
-    v = _fetch(out[5], m, k, inference.record_fields(k, "candidates", candidates=mm))
-    return _solve_valid_crops(v["cand"], v, solve)
 
 
 def _device_select_candidate_poses(net, frames, bboxes, frame_idx, distributed, scale, rule, refine, candidates, nms_radius, thresh,
                                    min_k, weights, cov_floor, kp3d, K, min_ratio, threads, want):
     """candidate_poses with device_select=True: the record's one copy, then the solve on it."""
-    with torch.no_grad():
-        if distributed:                     # every rank its shard of the boxes, then the one record gathered
-            ccpacked = parallel._sharded_frames_to_candidate_correspondences(
-                net, frames, bboxes, frame_idx, None, 0, scale, rule, refine, candidates, nms_radius, thresh, min_k, weights, None,
-                crops.STD, None, cov_floor)[5]
-        else:
-            ccpacked = net._frames_to_candidate_correspondences(frames, bboxes, frame_idx, scale, rule, refine, candidates,
-                                                                nms_radius, thresh, min_k, weights, None, crops.STD, None,
-                                                                cov_floor)[9]
-    m, k = len(bboxes), net.num_keypoints
-    v = _fetch(ccpacked, m, k, inference.record_fields(k, "candidate_correspondences", candidates=candidates))
+    request = inference.LoaderRequest(refine, (candidates, nms_radius), cov_floor if weights == "covariance" else None,
+                                      (thresh, min_k, weights))
+    r = _load(net, request, frames, bboxes, frame_idx, distributed, scale, rule, gather=(request.second,))
+    v = r.host(request.second)
     q, t, _, *rep = pnp.candidate_correspondences_to_pose_batch(v["cpts"], v["cw"], v["cpeak"], v["count"], v["order"], kp3d,
                                                                 np.asarray(K, np.float64), min_ratio, threads, report=want)
-    return [(q[i], t[i]) for i in range(m)], rep[0] if want else None
+    return [(q[i], t[i]) for i in range(r.m)], rep[0] if want else None
 
 
-def _loader_refined_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, refine, weights, ask, solve,
-                                     distributed=False):
-    """candidate_poses with candidates_path="loader": solve(cand, boxes, rates, hess or None) on the fetched record."""
-    with torch.no_grad():
-        if distributed:
-            out = parallel._sharded_frames_to_candidates(net, frames, bboxes, frame_idx, None, 0, scale, rule, candidates, nms_radius,
-                                                         None, crops.STD, None, refine=refine, **ask)
-        else:
-            out = net._frames_to_candidates(frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, None, crops.STD, None,
-                                            refine=refine, **ask)
-    m, k, mm = out[0].shape[:3]
-    kind = "candidates" if refine == "get_final" else "candidates_refined"
-    v = _fetch(out[5], m, k, inference.record_fields(k, kind, refine == "gaussfit", weights == "covariance", mm))
+def _loader_candidates_poses(net, frames, bboxes, frame_idx, scale, rule, candidates, nms_radius, refine, weights, cov_floor, solve,
+                             distributed=False):
+    """candidates_path="loader": solve(cand, boxes, rates, hess or None) on the fetched record of the (refined) candidates."""
+    request = inference.LoaderRequest(refine, (candidates, nms_radius), cov_floor if weights == "covariance" else None)
+    v = _load(net, request, frames, bboxes, frame_idx, distributed, scale, rule).host(request.main[0])
     hess = {"peak": None, "hessian": v.get("cand_hess"), "covariance": v.get("cand_info")}[weights]
     if hess is not None:                # (the rows of an invalid crop are NaN: zeros go in, like its candidates)
         hess = np.where((v["valid"] == 0).reshape(-1, 1, 1, 1), 0.0, hess)

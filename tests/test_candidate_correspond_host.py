@@ -322,29 +322,28 @@ class StubNet:
         hess[valid == 0] = np.nan
         return ids, valid, cand, hess
 
-    def _frames_to_candidate_correspondences(self, frames, boxes, idx, scale, rule, refine, candidates, nms_radius, thresh, min_k,
-                                             weights, mean, std, pixel_format, cov_floor=1e-6):
-        self.calls.append(("ccorr", len(boxes)))
-        ids, valid, cand, hess = self._rows(boxes)
-        r = R.record(cand, hess, self.sc["crop_boxes"][ids], self.sc["rates"][ids], valid, thresh, min_k, int(weights != "peak"))
-        out = inference.pack_candidate_correspondences(len(ids), self.num_keypoints, cand.shape[2], "cpu")
-        for t, name in zip(out, R.FIELDS):
-            t.copy_(torch.from_numpy(r[name]))
-        return (*out[:5], None, None, None, None, out[5], None)
-
-    def _frames_to_candidates(self, frames, boxes, idx, scale, rule, candidates, nms_radius, mean, std, pixel_format,
-                              refine="get_final", return_hessian=False, return_fit=False, return_cov=False, cov_floor=1e-6):
-        self.calls.append(("cand", len(boxes)))
-        assert refine == "get_final2" and not return_cov
+    def _loader(self, request, frames, boxes, idx, scale, rule, mean, std, pixel_format):
+        """The one record the caller goes on with: the candidate correspondences of a request with a select, else the candidates."""
         ids, valid, cand, hess = self._rows(boxes)
         m, k = len(ids), self.num_keypoints
+        if request.select is not None:
+            self.calls.append(("ccorr", len(boxes)))
+            thresh, min_k, _ = request.select
+            r = R.record(cand, hess, self.sc["crop_boxes"][ids], self.sc["rates"][ids], valid, thresh, min_k, request.mode)
+            out = inference.pack_candidate_correspondences(m, k, cand.shape[2], "cpu")
+            for t, name in zip(out, R.FIELDS):
+                t.copy_(torch.from_numpy(r[name]))
+            fields = inference.record_fields(k, "candidate_correspondences", candidates=cand.shape[2])
+            return inference.LoaderResult(m, k, {"candidate_correspondences": (out[5], fields)})
+        self.calls.append(("cand", len(boxes)))
+        assert request.refine == "get_final2" and request.cov_floor is None
         fields = inference.record_fields(k, "candidates_refined", False, False, cand.shape[2])
         packed = torch.zeros(m * sum(b for _, b in fields), dtype=torch.uint8)
         v = inference.record_views(packed, m, k, fields)
         for name, a in (("rates", self.sc["rates"][ids]), ("cand_hess", hess), ("cand", cand), ("boxes", self.sc["crop_boxes"][ids]),
                         ("valid", valid)):
             v[name].copy_(torch.from_numpy(np.ascontiguousarray(a)))
-        return inference.record_outputs(v, packed)
+        return inference.LoaderResult(m, k, {"candidates_refined": (packed, fields)})
 
 
 def _stub_poses(n_total, **kw):
@@ -395,17 +394,17 @@ def _worker(rank, world, port, n_total, q):
         net = StubNet(n_total)
         boxes = [(i, 0, i + 10, 10) for i in range(n_total)]
         frames = torch.zeros((n_total, 2, 2), dtype=torch.uint8)
-        a = (64, "val", "get_final2", 3, 6, 0.45, 6, "hessian", None, 0.229, None)
-        want = StubNet(n_total)._frames_to_candidate_correspondences(frames, boxes, None, *a)
+        a = (frames, boxes, None, 64, "val", None, 0.229, None)
+        want = StubNet(n_total)._loader(inference.LoaderRequest("get_final2", (3, 6), None, (0.45, 6, "hessian")), *a)
         got = parallel.sharded_frames_to_candidate_correspondences(net, frames, boxes, scale=64, refine="get_final2", candidates=3,
                                                                    thresh=0.45, min_k=6, weights="hessian")
         ok = ok and len(got) == 5 and all(torch.equal(x.view(torch.uint8), y.view(torch.uint8)) and x.shape == y.shape
-                                          for x, y in zip(got, want[:5]))
-        wantc = StubNet(n_total)._frames_to_candidates(frames, boxes, None, 64, "val", 3, 6, None, 0.229, None, "get_final2", True)
+                                          for x, y in zip(got, [want[n] for n in R.FIELDS]))
+        wantc = StubNet(n_total)._loader(inference.LoaderRequest("get_final2", (3, 6)), *a)
         gotc = parallel.sharded_frames_to_candidates(StubNet(n_total), frames, boxes, scale=64, candidates=3, refine="get_final2",
                                                      return_hessian=True)
         ok = ok and len(gotc) == 5 and all(torch.equal(x.view(torch.uint8), y.view(torch.uint8)) and x.shape == y.shape
-                                           for x, y in zip(gotc, (*wantc[:4], wantc[6])))
+                                           for x, y in zip(gotc, [wantc[n] for n in ("cand", "boxes", "rates", "valid", "cand_hess")]))
         q.put((rank, bool(ok)))
     finally:
         dist.destroy_process_group()

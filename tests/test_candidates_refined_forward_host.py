@@ -231,10 +231,12 @@ def test_the_record_of_the_refined_candidates(gaussfit, cov):
                     assert hv[n].ctypes.data - host.ctypes.data == lay[n][0] and np.shares_memory(hv[n], host), n
                     assert hv[n].dtype == (np.float64 if n in F64 else np.float32 if n == "cand" else np.int32), n
                     assert hv[n].tobytes() == tv[n].numpy().tobytes() == host[lay[n][0]:lay[n][0] + lay[n][1]].tobytes(), n
-                out = inference.record_outputs(tv, torch.from_numpy(host))
-                assert [t.data_ptr() for t in out[:5]] == [tv[n].data_ptr() for n in ("cand", "boxes", "rates", "valid", "cidx")]
+                # the loader's result gives the same places under the same names; the public return picks them in net.candidates' order
+                out = inference.LoaderResult(m, k, {"candidates_refined": (torch.from_numpy(host), fields)})
+                assert list(out.views) == want and [out[n].data_ptr() for n in want] == [tv[n].data_ptr() for n in want]
                 rest = (["cand_fit", "cand_status"] if gaussfit else []) + ["cand_hess"] + (["cand_cov", "cand_info"] if cov else [])
-                assert [t.data_ptr() for t in out[6:]] == [tv[n].data_ptr() for n in rest]
+                assert [t.data_ptr() for t in inference.candidate_returns(out, True, gaussfit, cov)] == \
+                    [tv[n].data_ptr() for n in ["cand", "boxes", "rates", "valid"] + rest]
                 with pytest.raises(ValueError, match="a record of"):
                     inference.record_views(host[:-4], m, k, fields)
     for bad in (None, 0, 5):

@@ -264,18 +264,19 @@ def test_loader_equals_frames_to_candidates_then_the_stage(env, frames3, name):
             want = inf.candidates_to_correspondences(cand, boxes, rates, valid, weights=weights, hess=hess, **sel)
             got = net.frames_to_candidate_correspondences(frames3, NET_BOXES, frame_idx=NET_FIDX, scale=64, refine=refine, candidates=M,
                                                           nms_radius=6, weights=weights, **sel, **more)
-            priv = net._frames_to_candidate_correspondences(frames3, NET_BOXES, NET_FIDX, 64, "val", refine, M, 6, sel["thresh"],
-                                                            sel["min_k"], weights, None, 0.229, None, more.get("cov_floor", 1e-6))
+            request = inf.LoaderRequest(refine, (M, 6), more.get("cov_floor", 1e-6) if weights == "covariance" else None,
+                                        (sel["thresh"], sel["min_k"], weights))
+            priv = net._loader(request, frames3, NET_BOXES, NET_FIDX, 64, "val", None, 0.229, None)
             # the good boxes alone: their rows must not feel the bad ones beside them
             alone = net.frames_to_candidate_correspondences(frames3, [NET_BOXES[i] for i in good], frame_idx=[NET_FIDX[i] for i in good],
                                                             scale=64, refine=refine, candidates=M, nms_radius=6, weights=weights, **sel,
                                                             **more)
         torch.cuda.synchronize()
         what = (name, refine, weights)
-        assert len(got) == 9 and len(priv) == 11
+        assert len(got) == 9 and list(priv.records) == [request.second, request.main[0]]
         TRF._same(got[:5], want, what)
         TRF._same(got[5:], parts[:4], what)
-        TRF._same(priv[:9], got, what)
+        TRF._same([priv[n] for n in R.FIELDS + ("cand", "boxes", "rates", "valid")], got, what)
         cpts, cw, cpeak, count, order = got[:5]
         assert cpts.shape == (5, k, M, 2) and cw.shape == (5, k, M, 3) and cpeak.shape == (5, k, M) and order.shape == (5, k)
         assert count[bad].tolist() == [0, 0] and bool((order[bad] == -1).all())
@@ -289,9 +290,9 @@ def test_loader_equals_frames_to_candidates_then_the_stage(env, frames3, name):
             assert bool((cw[..., 0] > 0)[live.expand_as(cw[..., 0])].any()), what     # some point carries a Hessian weight
         # the packed record: the five views where the description says
         lay = inf.packed_layout(5, k, candidates=M, kind="candidate_correspondences")
-        ccpacked = priv[9]
+        ccpacked = priv.records["candidate_correspondences"][0]
         assert ccpacked.dtype == torch.uint8 and ccpacked.numel() == lay["total"][1]
-        for n, t in zip(R.FIELDS, priv[:5]):
+        for n, t in ((n, priv[n]) for n in R.FIELDS):
             assert t.data_ptr() == ccpacked.data_ptr() + lay[n][0] and t.numel() * t.element_size() == lay[n][1], n
 
 

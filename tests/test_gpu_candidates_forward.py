@@ -197,7 +197,8 @@ def test_loader_equals_crop_batch_then_candidates(env, name):
         x, rboxes, rrates = env["crops"].crop_batch(frames, boxes_in, 64)
         want = net.candidates(x, 3, 6, return_index=True)
         cand, boxes, rates, valid = net.frames_to_candidates(frames, boxes_in, scale=64, candidates=3, nms_radius=6)
-        cand2, _, _, _, cidx, _ = net._frames_to_candidates(frames, boxes_in, None, 64, "val", 3, 6, None, 0.229, None)
+        r = net._loader(env["inference"].LoaderRequest("get_final", (3, 6)), frames, boxes_in, None, 64, "val", None, 0.229, None)
+        cand2, cidx = r["cand"], r["cidx"]
     torch.cuda.synchronize()
     assert valid.tolist() == [1, 1, 1] and _bits(cand, want[0]) and _bits(cand2, want[0]) and torch.equal(cidx, want[1])
     assert boxes.tolist() == [[int(v) for v in b] for b in rboxes] and rates.tolist() == [float(r) for r in rrates]
@@ -212,8 +213,9 @@ def test_loader_with_a_frame_index_and_invalid_crops(env, name):
     with torch.no_grad():
         x, rboxes, rrates, rvalid = crops.crop_batch_device(frames, SCENE_BOXES, frame_idx=SCENE_FIDX, scale=64)
         rcand, rcidx = net.candidates(x, M, 6, return_index=True)
-        cand, boxes, rates, valid, cidx, packed = net._frames_to_candidates(frames, SCENE_BOXES, SCENE_FIDX, 64, "val", M, 6, None,
-                                                                            0.229, None)
+        r = net._loader(inf.LoaderRequest("get_final", (M, 6)), frames, SCENE_BOXES, SCENE_FIDX, 64, "val", None, 0.229, None)
+        cand, boxes, rates, valid, cidx = (r[n] for n in ("cand", "boxes", "rates", "valid", "cidx"))
+        (packed, _), = r.records.values()
         four = net.frames_to_candidates(frames, SCENE_BOXES, frame_idx=SCENE_FIDX, scale=64, candidates=M, nms_radius=6)
     torch.cuda.synchronize()
     assert len(four) == 4 and _bits(four[0], cand) and _bits(four[1], boxes) and _bits(four[2].view(torch.int32), rates.view(torch.int32))

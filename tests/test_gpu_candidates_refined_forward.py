@@ -360,16 +360,18 @@ def test_loader_with_a_frame_index_and_invalid_crops(env, name, refine, cov):
     with torch.no_grad():
         x, rboxes, rrates, rvalid = crops.crop_batch_device(frames, TCF.SCENE_BOXES, frame_idx=TCF.SCENE_FIDX, scale=64)
         want = net.candidates(x, M, 6, return_index=True, refine=refine, **ask)
-        out = net._frames_to_candidates(frames, TCF.SCENE_BOXES, TCF.SCENE_FIDX, 64, "val", M, 6, None, 0.229, None, refine=refine, **ask)
+        out = net._loader(inf.LoaderRequest(refine, (M, 6), 1e-6 if cov else None), frames, TCF.SCENE_BOXES, TCF.SCENE_FIDX, 64, "val",
+                          None, 0.229, None)
     torch.cuda.synchronize()
-    cand, boxes, rates, valid, cidx, packed = out[:6]
+    cand, boxes, rates, valid, cidx = (out[n] for n in ("cand", "boxes", "rates", "valid", "cidx"))
+    (packed, _), = out.records.values()
     assert valid.tolist() == TCF.SCENE_VALID == rvalid.tolist() and _bits(boxes, rboxes) and torch.equal(rates, rrates)
     good, bad = [i for i, v in enumerate(TCF.SCENE_VALID) if v], [i for i, v in enumerate(TCF.SCENE_VALID) if not v]
     gauss = refine == "gaussfit"
     fields = inf.record_fields(k, "candidates_refined", gauss, cov, M)
     names = (["cand_fit", "cand_status"] if gauss else []) + ["cand_hess"] + (["cand_cov", "cand_info"] if cov else [])
-    assert len(out) == 6 + len(names)
-    got = dict(zip(names, out[6:]), cand=cand, cidx=cidx)
+    assert len(out.views) == 5 + len(names) and list(out.records) == ["candidates_refined"]
+    got = dict({n: out[n] for n in names}, cand=cand, cidx=cidx)
     ref = dict(zip(("cand", "cidx") + tuple({"fit": "cand_fit", "status": "cand_status", "hess": "cand_hess", "cov": "cand_cov",
                                              "info": "cand_info"}[n] for n in OUTS[refine] if cov or n not in ("cov", "info")), want))
     assert set(ref) == set(got)

@@ -268,7 +268,9 @@ def test_one_call_equals_crop_batch_then_keypoints_above_256(env):
     assert rboxes[1][2] - rboxes[1][0] != rboxes[1][3] - rboxes[1][1]
     with torch.no_grad():
         rkp, ridx = net(x, output="keypoints+index", refine="get_final")
-        kp, cboxes, rates, valid, idx, _ = net._frames_to_keypoints(frames, boxes, None, scale, "val", "get_final", None, 0.229, None)
+        from esa_pose_estimation_amd.inference import LoaderRequest
+        r = net._loader(LoaderRequest("get_final"), frames, boxes, None, scale, "val", None, 0.229, None)
+        kp, cboxes, rates, valid, idx = (r[n] for n in ("kp", "boxes", "rates", "valid", "idx"))
         kp2, cboxes2, rates2, valid2 = net.frames_to_keypoints(frames, boxes, scale=scale, refine="get_final")
     torch.cuda.synchronize()
     assert kp.shape == (2, net.num_keypoints, 3) and bool(torch.isfinite(rkp).all())

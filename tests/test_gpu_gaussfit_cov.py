@@ -365,14 +365,16 @@ def _loader_equals_its_parts(env, name, precision, scale):
     with torch.no_grad():
         x, _, _, _ = crops.crop_batch_device(frames, F.SCENE_BOXES, frame_idx=F.SCENE_FIDX, scale=scale)
         rkp, rfit, rstatus, rhess, rcov, rinfo = net.keypoints_gaussfit(x, return_fit=True, return_cov=True)
-        old = net._frames_to_keypoints(frames, F.SCENE_BOXES, F.SCENE_FIDX, scale, "val", "gaussfit", None, 0.229, None)
-        rt = net._rt.frames_keypoints(net, frames, F.SCENE_BOXES, F.SCENE_FIDX, 5, scale, 0, 0, float(crops.MEAN_VAL), 0.229, 2,
-                                      cov=V.COV_FLOOR)
+        old = net._loader(inf.LoaderRequest("gaussfit"), frames, F.SCENE_BOXES, F.SCENE_FIDX, scale, "val", None, 0.229, None)
+        rt = net._rt.frames_keypoints(net, inf.LoaderRequest("gaussfit", None, V.COV_FLOOR), frames, F.SCENE_BOXES, F.SCENE_FIDX, 5,
+                                      scale, 0, 0, float(crops.MEAN_VAL), 0.229)
     torch.cuda.synchronize()
-    kp, boxes, rates, valid, idx, packed, fit, status, hess, cov, info = rt
+    names = ("kp", "boxes", "rates", "valid", "idx", "fit", "status", "hess")
+    kp, boxes, rates, valid, idx, fit, status, hess, cov, info = (rt[n] for n in names + ("cov", "info"))
+    (packed, _), = rt.records.values()
     assert valid.tolist() == F.SCENE_VALID
-    for a, b in zip((kp, boxes, rates, valid, idx, fit, status, hess), (old[0], old[1], old[2], old[3], old[4], old[6], old[7], old[8])):
-        assert _bits(a, b)
+    for n in names:
+        assert _bits(rt[n], old[n]), n
     good, bad = [i for i, v in enumerate(F.SCENE_VALID) if v], [i for i, v in enumerate(F.SCENE_VALID) if not v]
     assert _bits(kp[good], rkp[good]) and _bits(fit[good], rfit[good]) and torch.equal(status[good], rstatus[good])
     assert _bits(cov[good], rcov[good]) and _bits(info[good], rinfo[good])
@@ -417,15 +419,16 @@ def test_estimate_poses_with_covariance_weights(env):
     got = pipeline.estimate_poses(*args, weights="covariance", **kw)
     assert len(got) == n and all(np.isfinite(q).all() and np.isfinite(t).all() for q, t in got)
     with torch.no_grad():
-        kp, boxes, rates, valid, _, _, _, status, _, cov, info = net._rt.frames_keypoints(
-            net, frames, scene["bboxes"], None, n, 64, 0, 0, float(env["crops"].MEAN_VAL), 0.229, 2, cov=V.COV_FLOOR)
+        rt = net._rt.frames_keypoints(net, inf.LoaderRequest("gaussfit", None, V.COV_FLOOR), frames, scene["bboxes"], None, n, 64, 0, 0,
+                                      float(env["crops"].MEAN_VAL), 0.229)
+        kp, boxes, rates, valid, status, cov, info = (rt[n_] for n_ in ("kp", "boxes", "rates", "valid", "status", "cov", "info"))
     want, w = solve(kp, boxes, rates, valid, info, "covariance")
     assert F._same_poses(got, want)
     print("statuses 0..3", F._counts(status), "finite info", int(torch.isfinite(info).all(-1).sum()), "points with a weight",
           int((np.abs(w).sum(-1) > 0).sum()))
     with torch.no_grad():
-        okp, oboxes, orates, ovalid, _, _, _, _, ohess = net._frames_to_keypoints(frames, scene["bboxes"], None, 64, "val", "gaussfit",
-                                                                                   None, 0.229, None)
+        old = net._loader(inf.LoaderRequest("gaussfit"), frames, scene["bboxes"], None, 64, "val", None, 0.229, None)
+        okp, oboxes, orates, ovalid, ohess = (old[n] for n in ("kp", "boxes", "rates", "valid", "hess"))
     assert _bits(okp, kp) and _bits(oboxes, boxes) and _bits(orates, rates)
     for wname, hess in (("peak", None), ("hessian", ohess)):
         assert F._same_poses(pipeline.estimate_poses(*args, weights=wname, **kw), solve(okp, oboxes, orates, ovalid, hess, wname)[0]), wname

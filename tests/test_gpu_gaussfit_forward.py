@@ -319,8 +319,9 @@ def test_loader_equals_its_parts(env, name):
         x, rboxes, rrates, rvalid = crops.crop_batch_device(frames, SCENE_BOXES, frame_idx=SCENE_FIDX, scale=scale)
         rkp, ridx = net(x, output="keypoints+index", refine="gaussfit")
         _, rfit, rstatus, rhess = net.keypoints_gaussfit(x, return_fit=True)
-        kp, boxes, rates, valid, idx, packed, fit, status, hess = net._frames_to_keypoints(
-            frames, SCENE_BOXES, SCENE_FIDX, scale, "val", "gaussfit", None, 0.229, None)
+        r = net._loader(inf.LoaderRequest("gaussfit"), frames, SCENE_BOXES, SCENE_FIDX, scale, "val", None, 0.229, None)
+        kp, boxes, rates, valid, idx, fit, status, hess = (r[n] for n in ("kp", "boxes", "rates", "valid", "idx", "fit", "status", "hess"))
+        (packed, _), = r.records.values()
         four = net.frames_to_keypoints(frames, SCENE_BOXES, **kw)
     torch.cuda.synchronize()
     assert len(four) == 4 and _bits(four[0], kp) and _bits(four[1], boxes) and _bits(four[2], rates) and _bits(four[3], valid)
@@ -389,8 +390,8 @@ def test_estimate_poses_with_the_gaussfit_decoder(env):
     # the Hessian weights: the native solver on the record the host path builds from the loader's own outputs
     got = pipeline.estimate_poses(*args, device_select=True, weights="hessian", **kw)
     with torch.no_grad():
-        kp, boxes, rates, valid, _, _, _, status, hess = net._frames_to_keypoints(frames, scene["bboxes"], None, 64, "val", "gaussfit",
-                                                                                 None, 0.229, None)
+        r = net._loader(inf.LoaderRequest("gaussfit"), frames, scene["bboxes"], None, 64, "val", None, 0.229, None)
+        kp, boxes, rates, valid, status, hess = (r[n] for n in ("kp", "boxes", "rates", "valid", "status", "hess"))
         count, order, pts, w = (t.cpu().numpy() for t in inf.keypoints_to_correspondences(kp, boxes, rates, valid, hess=hess,
                                                                                           weights="hessian", **sel))
     q, t = pnp.correspondences_to_pose_batch(pts, w, count, order, scene["kp3d"], np.asarray(synth.ESA_CAMERA, np.float64), 0)

@@ -87,27 +87,29 @@ def test_shards_give_the_single_call_record(env, world, refine, weights, own_fra
     inf, par, net, frames = env["inference"], env["parallel"], env["net"], env["frames"]
     k, n = net.num_keypoints, len(BOXES)
     n_max = -(-n // world)
-    rest = (SCALE, "val", refine, SEL["thresh"], SEL["min_k"], weights, None, 0.229, None, 1e-6)
+    request = inf.LoaderRequest(refine, None, 1e-6 if weights == "covariance" else None, (SEL["thresh"], SEL["min_k"], weights))
+    rest = (SCALE, "val", None, 0.229, None)
     cfields = inf.record_fields(k, "correspondences")
     kfields = inf.record_fields(k, "keypoints", refine == "gaussfit", weights == "covariance")
     with torch.no_grad():
-        whole = net._frames_to_correspondences(frames, BOXES, FIDX, *rest)
-        blocks = {8: [], 9: []}
+        whole = net._loader(request, frames, BOXES, FIDX, *rest)
+        blocks = {"correspondences": [], "keypoints": []}
         for r in range(world):
             lo, hi = par.shard_bounds(n, world, r)
             base = min(FIDX[lo:hi]) if own_frames else 0
             fr = frames[base:max(FIDX[lo:hi]) + 1] if own_frames else frames
             boxes, idx = par._shard_args(BOXES, FIDX, lo, hi, n, base)
             assert list(idx) == [f - base for f in FIDX[lo:hi]] and list(boxes) == BOXES[lo:hi]
-            out = net._frames_to_correspondences(fr, boxes, idx, *rest)
-            for pos, fields in ((8, cfields), (9, kfields)):
-                blocks[pos].append(_to_block(out[pos].cpu().numpy(), hi - lo, n_max, [b for _, b in fields]))
-        for pos, fields in ((8, cfields), (9, kfields)):
+            out = net._loader(request, fr, boxes, idx, *rest)
+            for pos, fields in (("correspondences", cfields), ("keypoints", kfields)):
+                assert out.records[pos][1] == fields
+                blocks[pos].append(_to_block(out.records[pos][0].cpu().numpy(), hi - lo, n_max, [b for _, b in fields]))
+        for pos, fields in (("correspondences", cfields), ("keypoints", kfields)):
             gathered = torch.from_numpy(np.concatenate(blocks[pos])).cuda()
             got = par.gather_records_device(gathered, world, n, fields)
             torch.cuda.synchronize()
-            assert torch.equal(got, whole[pos]), (pos, refine, weights)
-    assert whole[7].tolist() == [1, 1, 0, 1, 1] and int(whole[0].sum()) > 0          # the scene selects points
+            assert torch.equal(got, whole.records[pos][0]), (pos, refine, weights)
+    assert whole["valid"].tolist() == [1, 1, 0, 1, 1] and int(whole["count"].sum()) > 0          # the scene selects points
 
 
 # ---- 3. nccl (RCCL), world size 1 --------------------------------------------------------------------------------------------
@@ -132,8 +134,11 @@ def test_rccl_world_size_1_drives_the_sharded_device_path(env, monkeypatch):
     args = (net, frames, BOXES, kp3d, synth.ESA_CAMERA)
     pkw = dict(scale=SCALE, on_fail="nan", frame_idx=FIDX, thresh=0.0, min_k=8)
     with torch.no_grad():
-        want_kp = {r: net._frames_to_keypoints(frames, BOXES, FIDX, SCALE, "val", r, None, 0.229, None) for r, _ in FORMS}
-        want_cov = net._frames_to_keypoints(frames, BOXES, FIDX, SCALE, "val", "gaussfit", None, 0.229, None, 1e-6)
+        inf, extra = env["inference"], ("fit", "status", "hess", "cov", "info")      # the keypoint call's returns behind `valid`, by name
+        want_kp = {r: net._loader(inf.LoaderRequest(r), frames, BOXES, FIDX, SCALE, "val", None, 0.229, None) for r, _ in FORMS}
+        want_kp = {r: tuple(v[n] for n in KP[:4] + extra if n in v) for r, v in want_kp.items()}
+        want_cov = net._loader(inf.LoaderRequest("gaussfit", None, 1e-6), frames, BOXES, FIDX, SCALE, "val", None, 0.229, None)
+        want_cov = tuple(want_cov[n] for n in KP[:4] + extra)
         want_c = {(r, w): net.frames_to_correspondences(frames, BOXES, FIDX, scale=SCALE, refine=r, weights=w, **SEL) for r, w in FORMS}
     want_poses = pipeline.estimate_poses(*args, device_select=True, refine="get_final2", weights="hessian", **pkw)
     want_loader = pipeline.estimate_poses(*args, device_loader=True, **pkw)
@@ -143,11 +148,11 @@ def test_rccl_world_size_1_drives_the_sharded_device_path(env, monkeypatch):
         with torch.no_grad():
             for r, w in FORMS:
                 got = par.sharded_frames_to_keypoints(net, frames, BOXES, FIDX, scale=SCALE, refine=r)
-                assert all(t.is_cuda for t in got) and _same_bytes(got, want_kp[r][:4] + want_kp[r][6:]), r
+                assert all(t.is_cuda for t in got) and _same_bytes(got, want_kp[r]), r
                 got = par.sharded_frames_to_correspondences(net, frames, BOXES, FIDX, scale=SCALE, refine=r, weights=w, **SEL)
                 assert all(t.is_cuda for t in got) and _same_bytes(got, want_c[r, w]), (r, w)
             got = par.sharded_frames_to_keypoints(net, frames, BOXES, FIDX, scale=SCALE, refine="gaussfit", return_cov=True)
-            assert len(got) == 9 and _same_bytes(got, want_cov[:4] + want_cov[6:])
+            assert len(got) == 9 and _same_bytes(got, want_cov)
         got = pipeline.estimate_poses(*args, distributed=True, device_select=True, refine="get_final2", weights="hessian", **pkw)
         assert _same_poses(got, want_poses)
         assert _same_poses(pipeline.estimate_poses(*args, distributed=True, device_loader=True, **pkw), want_loader)
@@ -170,16 +175,16 @@ def _keypoint_record(m, k, gauss=False, cov=False):
 
 
 KP = ("kp", "boxes", "rates", "valid", "idx")
-# form -> (the net's call, its arguments behind (frames, BOXES, FIDX, SCALE, "val"), the record, record_fields' arguments behind k,
-# which packed_layout takes behind (m, k), the fields in the order the call returns them, `packed` left out)
+# form -> (the request's arguments, the record, record_fields' arguments behind k, which packed_layout takes behind (m, k), the names
+# the result answers to)
 VIEW_FORMS = {
-    "get_final": ("_frames_to_keypoints", ("get_final", None, 0.229, None), _keypoint_record, ("keypoints", False, False, None), KP),
-    "get_final2": ("_frames_to_keypoints", ("get_final2", None, 0.229, None), _keypoint_record, ("keypoints", False, False, None), KP),
-    "gaussfit": ("_frames_to_keypoints", ("gaussfit", None, 0.229, None), lambda m, k: _keypoint_record(m, k, True),
+    "get_final": (("get_final",), _keypoint_record, ("keypoints", False, False, None), KP),
+    "get_final2": (("get_final2",), _keypoint_record, ("keypoints", False, False, None), KP),
+    "gaussfit": (("gaussfit",), lambda m, k: _keypoint_record(m, k, True),
                  ("keypoints", True, False, None), KP + ("fit", "status", "hess")),
-    "gaussfit+cov": ("_frames_to_keypoints", ("gaussfit", None, 0.229, None, 1e-6), lambda m, k: _keypoint_record(m, k, True, True),
+    "gaussfit+cov": (("gaussfit", None, 1e-6), lambda m, k: _keypoint_record(m, k, True, True),
                      ("keypoints", True, True, None), KP + ("fit", "status", "hess", "cov", "info")),
-    "candidates=3": ("_frames_to_candidates", (3, 6, None, 0.229, None),
+    "candidates=3": (("get_final", (3, 6)),
                      lambda m, k: [("rates", F64, (m,)), ("cand", F32, (m, k, 3, 3)), ("boxes", I32, (m, 4)), ("valid", I32, (m,)),
                                    ("cidx", I32, (m, k, 3))],
                      ("candidates", False, False, 3), ("cand", "boxes", "rates", "valid", "cidx")),
@@ -189,13 +194,14 @@ VIEW_FORMS = {
 @pytest.mark.parametrize("form", list(VIEW_FORMS))
 def test_loader_outputs_are_the_views_of_the_field_table(env, form):
     inf, net, frames = env["inference"], env["net"], env["frames"]
-    call, rest, record, desc, names = VIEW_FORMS[form]
+    ask, record, desc, names = VIEW_FORMS[form]
     m, k = len(BOXES), net.num_keypoints
     with torch.no_grad():
-        out = getattr(net, call)(frames, BOXES, FIDX, SCALE, "val", *rest)
+        out = net._loader(inf.LoaderRequest(*ask), frames, BOXES, FIDX, SCALE, "val", None, 0.229, None)
     torch.cuda.synchronize()
-    packed, returned = out[5], dict(zip(names, out[:5] + out[6:]))
-    assert len(out) == len(names) + 1 and packed.dtype == torch.uint8 and packed.dim() == 1
+    (packed, _), returned = out.records[desc[0]], dict(out.views)
+    assert list(out.records) == [desc[0]] and sorted(returned) == sorted(names) and packed.dtype == torch.uint8 and packed.dim() == 1
+    assert (out.m, out.k) == (m, k)
     fields = inf.record_fields(k, *desc)
     views = inf.record_views(packed, m, k, fields)
     host = inf.record_views(packed.cpu().numpy(), m, k, fields)
@@ -209,4 +215,4 @@ def test_loader_outputs_are_the_views_of_the_field_table(env, form):
         off += t.nbytes
     assert not returned and not views and not host                      # every field, and nothing else
     assert off == packed.numel() == inf.packed_layout(m, k, *desc[1:])["total"][1]
-    assert out[3].tolist() == [1, 1, 0, 1, 1]                           # position 2: the empty box
+    assert out["valid"].tolist() == [1, 1, 0, 1, 1]                     # position 2: the empty box

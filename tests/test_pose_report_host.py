@@ -278,13 +278,12 @@ class StandInNet:
     def __init__(self, pts, w, count, order):
         self.rec = [torch.as_tensor(np.ascontiguousarray(a)) for a in (count, order, pts, w)]
 
-    def _frames_to_correspondences(self, frames, boxes, idx, scale, rule, refine, thresh, min_k, weights, mean, std, pixel_format,
-                                   cov_floor=1e-6):
+    def _loader(self, request, frames, boxes, idx, scale, rule, mean, std, pixel_format):
         m, k = self.rec[2].shape[:2]
         *views, cpacked = inference.pack_correspondences(m, k, "cpu")
         for v, a in zip(views, self.rec):
             v.copy_(a)
-        return (*views, torch.zeros(m, k, 3), None, None, None, cpacked, None)
+        return inference.LoaderResult(m, k, {"correspondences": (cpacked, inference.record_fields(k, "correspondences"))})
 
 
 @pytest.fixture(scope="module")
@@ -349,7 +348,7 @@ class StandInLoader:
     def __init__(self, kp):
         self.kp = kp
 
-    def _frames_to_keypoints(self, frames, boxes, idx, scale, rule, refine, mean, std, pixel_format, cov_floor=None):
+    def _loader(self, request, frames, boxes, idx, scale, rule, mean, std, pixel_format):
         m, k = self.kp.shape[:2]
         lay = inference.packed_layout(m, k, False)
         packed = torch.zeros(lay["total"][1], dtype=torch.uint8)
@@ -357,7 +356,7 @@ class StandInLoader:
         part("rates", torch.float64, m).fill_(1.0)
         part("kp", torch.float32, m, k, 3).copy_(torch.as_tensor(self.kp))
         part("valid", torch.int32, m).copy_(torch.tensor([1, 0, 1], dtype=torch.int32))
-        return (torch.zeros(m, k, 3), None, None, None, None, packed)
+        return inference.LoaderResult(m, k, {"keypoints": (packed, inference.record_fields(k, "keypoints"))})
 
 
 def test_report_on_the_device_loader_path():

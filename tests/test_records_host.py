@@ -136,7 +136,7 @@ def test_gather_records_without_a_group():
 
 # ---- 3. the sharded calls with a stub net -----------------------------------------------------------------------------------
 class StubNet:
-    """Stands in for the GPU model: its _frames_to_* fill the two records from the box values, the frame each box lies on
+    """Stands in for the GPU model: its _loader fills the two records from the box values, the frame each box lies on
     (read THROUGH the frame index it was given, so a wrong index shows) and the keypoint number; CPU tensors."""
 
     def __init__(self, k):
@@ -178,21 +178,43 @@ class StubNet:
             extra += (cv, info)
         return (kp, cb, rates, valid, ix, packed) + extra, v
 
-    def _frames_to_keypoints(self, frames, boxes, idx, scale, rule, refine, mean, std, pixel_format, cov_floor=None):
-        self.calls.append(("kp", len(boxes)))
-        return self._keypoint_record(frames, boxes, idx, refine == "gaussfit", cov_floor is not None)[0]
-
-    def _frames_to_correspondences(self, frames, boxes, idx, scale, rule, refine, thresh, min_k, weights, mean, std, pixel_format,
-                                   cov_floor=1e-6):
-        self.calls.append(("corr", len(boxes)))
+    def _loader(self, request, frames, boxes, idx, scale, rule, mean, std, pixel_format):
+        self.calls.append(("kp" if request.select is None else "corr", len(boxes)))
         m, k = len(boxes), self.num_keypoints
-        out, v = self._keypoint_record(frames, boxes, idx, refine == "gaussfit", weights == "covariance")
-        count, order, pts, w, cpacked = inference.pack_correspondences(m, k, "cpu")
-        count.copy_(v[:, 0] % (k + 1))
-        order.copy_((v + 3) % k)
-        pts.copy_(torch.stack([v + 0.125, v + 0.375], 2))
-        w.copy_(torch.stack([v, -v, v * 2], 2))
-        return (count, order, pts, w) + out[:4] + (cpacked, out[5])
+        _, gaussfit, cov, _ = request.main
+        out, v = self._keypoint_record(frames, boxes, idx, gaussfit, cov)
+        records = {"keypoints": (out[5], inference.record_fields(k, "keypoints", gaussfit, cov))}
+        if request.select is not None:
+            count, order, pts, w, cpacked = inference.pack_correspondences(m, k, "cpu")
+            count.copy_(v[:, 0] % (k + 1))
+            order.copy_((v + 3) % k)
+            pts.copy_(torch.stack([v + 0.125, v + 0.375], 2))
+            w.copy_(torch.stack([v, -v, v * 2], 2))
+            records["correspondences"] = (cpacked, inference.record_fields(k, "correspondences"))
+        return inference.LoaderResult(m, k, records)
+
+
+CORR = ("count", "order", "pts", "w", "kp", "boxes", "rates", "valid")       # sharded_frames_to_correspondences' returns, by name
+
+
+def _request(refine, weights=None, cov_floor=None):
+    """The request of the correspondences (weights given) or of the keypoints, as the public calls build it."""
+    if weights is None:
+        return inference.LoaderRequest(refine, None, cov_floor)
+    return inference.LoaderRequest(refine, None, 1e-6 if weights == "covariance" else None, (0.8, 24, weights))
+
+
+def _named(r, names):
+    return tuple(r[n] for n in names)
+
+
+def _same_result(a, b):
+    """Two loader results: the same records, byte for byte, and the same typed views of them under the same names."""
+    kinds, names = sorted(a.records), sorted(a.views)
+    return (a.m, a.k, kinds, names) == (b.m, b.k, sorted(b.records), sorted(b.views)) and \
+        all(a.records[kind][1] == b.records[kind][1] for kind in kinds) and \
+        _same([a.records[kind][0] for kind in kinds], [b.records[kind][0] for kind in kinds]) and \
+        _same([a[n] for n in names], [b[n] for n in names])
 
 
 def _batch(n_total):
@@ -223,29 +245,28 @@ def _worker(rank, world, port, n_total, k, q):
         frames, boxes = _batch(n_total)
         ok = True
         for refine, weights in (("get_final", "peak"), ("get_final2", "hessian"), ("gaussfit", "covariance")):
-            want = StubNet(k)._frames_to_correspondences(frames, boxes, None, 64, "val", refine, 0.8, 24, weights, None, 0.229, None)
+            want = StubNet(k)._loader(_request(refine, weights), frames, boxes, None, 64, "val", None, 0.229, None)
             kw = dict(scale=64, refine=refine, weights=weights)
             # (a) every rank holds the whole batch's frames
             net = StubNet(k)
-            got = parallel._sharded_frames_to_correspondences(net, frames, boxes, None, None, 0, 64, "val", refine, 0.8, 24, weights,
-                                                              None, 0.229, None)
-            ok = ok and _same(got, want) and net.calls == ([("corr", hi - lo)] if hi > lo else [])
-            ok = ok and _same(parallel.sharded_frames_to_correspondences(StubNet(k), frames, boxes, **kw), want[:8])
+            got = parallel._sharded_loader(net, _request(refine, weights), frames, boxes, None, None, 0, 64, "val", None, 0.229, None)
+            ok = ok and _same_result(got, want) and net.calls == ([("corr", hi - lo)] if hi > lo else [])
+            ok = ok and _same(parallel.sharded_frames_to_correspondences(StubNet(k), frames, boxes, **kw), _named(want, CORR))
             # (b) a rank holds only its own frames: frame_base = lo, indices rebased
             ok = ok and _same(parallel.sharded_frames_to_correspondences(StubNet(k), frames[lo:hi], boxes, frame_base=lo, **kw),
-                              want[:8])
+                              _named(want, CORR))
             # (c) explicit frame indices, several boxes on one frame
             fidx = [i // 2 for i in range(n_total)]
-            want_f = StubNet(k)._frames_to_correspondences(frames, boxes, fidx, 64, "val", refine, 0.8, 24, weights, None, 0.229, None)
-            ok = ok and _same(parallel.sharded_frames_to_correspondences(StubNet(k), frames, boxes, fidx, **kw), want_f[:8])
+            want_f = StubNet(k)._loader(_request(refine, weights), frames, boxes, fidx, 64, "val", None, 0.229, None)
+            ok = ok and _same(parallel.sharded_frames_to_correspondences(StubNet(k), frames, boxes, fidx, **kw), _named(want_f, CORR))
             ok = ok and _same(parallel.sharded_frames_to_correspondences(StubNet(k), frames, boxes,
-                                                                         torch.tensor(fidx, dtype=torch.int32), **kw), want_f[:8])
+                                                                         torch.tensor(fidx, dtype=torch.int32), **kw), _named(want_f, CORR))
         # the keypoint form, with every extra output
-        want = StubNet(k)._frames_to_keypoints(frames, boxes, None, 64, "val", "gaussfit", None, 0.229, None, 1e-6)
+        want = StubNet(k)._loader(_request("gaussfit", cov_floor=1e-6), frames, boxes, None, 64, "val", None, 0.229, None)
         got = parallel.sharded_frames_to_keypoints(StubNet(k), frames, boxes, scale=64, refine="gaussfit", return_cov=True)
-        ok = ok and _same(got, want[:4] + want[6:])
-        want = StubNet(k)._frames_to_keypoints(frames, boxes, None, 64, "val", "get_final", None, 0.229, None)
-        ok = ok and _same(parallel.sharded_frames_to_keypoints(StubNet(k), frames, boxes, scale=64), want[:4])
+        ok = ok and _same(got, _named(want, CORR[4:] + ("fit", "status", "hess", "cov", "info")))
+        want = StubNet(k)._loader(_request("get_final"), frames, boxes, None, 64, "val", None, 0.229, None)
+        ok = ok and _same(parallel.sharded_frames_to_keypoints(StubNet(k), frames, boxes, scale=64), _named(want, CORR[4:]))
         # a wrong shard size: gather_keypoints' message
         try:
             parallel.gather_records(torch.zeros(4 * (hi - lo + 1), dtype=torch.uint8), hi - lo + 1, n_total, [4])

@@ -54,15 +54,10 @@ def main():
         scene = synth.make_scene(n, net.num_keypoints, seed=0)
         frames = torch.from_numpy(np.random.default_rng(0).integers(0, 256, size=(n, 1200, 1920), dtype=np.uint8)).cuda()
         det = torch.tensor(scene["bboxes"], dtype=torch.int32, device="cuda")
-        k = net.num_keypoints
 
         def host_select():
-            out = net._frames_to_keypoints(frames, det, None, 256, "val", a.refine, None, 0.229, None)
-            host = out[5].cpu().numpy()
-            offs = np.cumsum([0, 8 * n, 12 * n * k, 16 * n, 4 * n])
-            rates = host[offs[0]:offs[1]].view(np.float64)
-            kp = host[offs[1]:offs[2]].view(np.float32).reshape(n, k, 3)
-            boxes = host[offs[2]:offs[3]].view(np.int32).reshape(n, 4)
+            v = net._loader(inference.LoaderRequest(a.refine), frames, det, None, 256, "val", None, 0.229, None).host("keypoints")
+            rates, kp, boxes = v["rates"], v["kp"], v["boxes"]
             rec = []
             for i in range(n):
                 idxs = inference.select_keypoints(kp[i, :, 2], thresh, min_k)
@@ -71,8 +66,9 @@ def main():
             return rec
 
         def device_select():
-            out = net._frames_to_correspondences(frames, det, None, 256, "val", a.refine, thresh, min_k, "peak", None, 0.229, None)
-            return inference.unpack_correspondences(out[8].cpu().numpy(), n, k)
+            request = inference.LoaderRequest(a.refine, None, None, (thresh, min_k, "peak"))
+            v = net._loader(request, frames, det, None, 256, "val", None, 0.229, None).host("correspondences")
+            return v["count"], v["order"], v["pts"], v["w"]
 
         def keypoints_only(m=net):
             return m.frames_to_keypoints(frames, det, scale=256, refine=a.refine)[0]

@@ -58,8 +58,10 @@ def main():
             frames = torch.from_numpy(np.random.default_rng(0).integers(0, 256, size=(n, 1200, 1920), dtype=np.uint8)).cuda()
             det = torch.tensor(scene["bboxes"], dtype=torch.int32, device="cuda")
             with torch.no_grad():
-                whole = net._frames_to_correspondences(frames, det, None, 256, "val", a.refine, 0.8, 8, weights, None, 0.229, None)
-            blocks = (whole[8].clone(), whole[9].clone())           # world size 1: a block is the record
+                whole = net._loader(inference.LoaderRequest(a.refine, None, None, (0.8, 8, weights)), frames, det, None, 256, "val",
+                                    None, 0.229, None)
+            whole = (whole.records["correspondences"][0], whole.records["keypoints"][0])
+            blocks = (whole[0].clone(), whole[1].clone())           # world size 1: a block is the record
 
             def gather_only():
                 return (parallel.gather_records_device(blocks[0], 1, n, cfields), parallel.gather_records_device(blocks[1], 1, n, kfields))
@@ -73,7 +75,7 @@ def main():
                         f()
                 torch.cuda.synchronize()
                 same = all(torch.equal(x.view(torch.uint8), y.view(torch.uint8)) for x, y in zip(forms["n"](), forms["s"]()))
-                same = same and torch.equal(gather_only()[0], whole[8]) and torch.equal(gather_only()[1], whole[9])
+                same = same and torch.equal(gather_only()[0], whole[0]) and torch.equal(gather_only()[1], whole[1])
                 ms = {f: [] for f in forms}
                 wall = {f: [] for f in forms}
                 for _ in range(a.reps):
