@@ -13,13 +13,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libesahrnet.so")
 USAGE = os.path.join(HERE, "build", "resource_usage.json")      # per kernel: VGPRs, scratch bytes, spills, waves per SIMD (hipcc's remarks)
-SOURCES = ["abi_decode.hip", "conv_mfma.hip", "conv_s2c32.hip", "conv_x6.hip", "conv1x1.hip", "correspond.hip", "diff.hip", "stem.hip", "stem_fused.hip", "bblock32.hip", "cbam.hip", "crops.hip", "frontend.hip", "fuse.hip", "head.hip", "head_fused.hip", "head_fused2.hip", "head_fused_bf.hip", "head_gather.hip", "head_t.hip", "head_x6.hip", "keypoints.hip", "keypoints_at.hip", "keypoints_candidates.hip", "keypoints_candidates_onepass.hip", "keypoints_final2.hip", "keypoints_final2_hess.hip", "keypoints_gaussfit.hip", "keypoints_gaussfit_cov.hip", "layout.hip", "op_abi.hip", "plan.hip", "pnp_host.hip", "records.hip", "stats.hip"]
+SOURCES = ["abi_decode.hip", "conv_mfma.hip", "conv_s2c32.hip", "conv_x6.hip", "conv1x1.hip", "correspond.hip", "diff.hip", "stem.hip", "stem_fused.hip", "bblock32.hip", "cbam.hip", "crops.hip", "forward.hip", "frontend.hip", "fuse.hip", "head.hip", "head_fused.hip", "head_fused2.hip", "head_fused_bf.hip", "head_gather.hip", "head_t.hip", "head_x6.hip", "keypoints.hip", "keypoints_at.hip", "keypoints_candidates.hip", "keypoints_candidates_onepass.hip", "keypoints_final2.hip", "keypoints_final2_hess.hip", "keypoints_gaussfit.hip", "keypoints_gaussfit_cov.hip", "layout.hip", "loader.hip", "op_abi.hip", "plan.hip", "plan_build.hip", "pnp_host.hip", "records.hip", "report.hip", "stats.hip"]
 # conv_x6.hip: MFMA results that a VALU instruction reads next (the per-row fresh sums) are allocated in VGPRs — with
 # AGPR destinations hipcc copies them out right behind the chain's last MFMA and pads the hazard with s_nop (csrc/conv_x6.hip)
 PER_FILE_FLAGS = {"conv_x6.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                   # frontend.hip restates Python's box arithmetic: int(c0 - 1.05 * size) must see the rounded product
                   "frontend.hip": ["-ffp-contract=off"]}
-HEADERS = ["kernels.h", "correspond.h", "final2.h", "gaussfit.h", "refine.h", "sb.h", "conv_cfg.h", "devstate.h", "host_util.h", os.path.join("..", "..", "include", "esahrnet.h")]
+HEADERS = ["kernels.h", "correspond.h", "final2.h", "gaussfit.h", "refine.h", "sb.h", "conv_cfg.h", "devstate.h", "host_util.h", "plan.h", os.path.join("..", "..", "include", "esahrnet.h")]
 
 
 def _hipcc() -> str:

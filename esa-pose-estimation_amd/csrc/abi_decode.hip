@@ -1,14 +1,16 @@
 // abi_decode.hip — the entries of include/esahrnet.h that take no handle: the stand-alone decoders (get_final, get_final2, the
 // Gaussian fit), the loader's two steps (boxes, crops) and the correspondences.  Each checks its arguments, reports through
-// esa::set_error and makes one launch; nothing here knows esahrnet_ctx (plan.hip keeps every entry that does).
+// esa::set_error and makes one launch; nothing here knows esahrnet_ctx (the units of plan.h keep every entry that does).  The
+// test hooks on the launchers' process-wide state (esahrnet_debug_*) sit at the end.
 //
-// The argument checks that the handle-taking loader entries of plan.hip repeat word for word (esahrnet_frames_keypoints*,
-// esahrnet_frames_correspondences) are defined here, in namespace esa, and declared at the top of plan.hip: `who` names the
+// The argument checks that the handle-taking loader entries of loader.hip repeat word for word (esahrnet_frames_keypoints*,
+// esahrnet_frames_correspondences) are defined here, in namespace esa, and declared in host_util.h: `who` names the
 // entry in the message.
 #include <cstdint>
 
 #include "../../include/esahrnet.h"
-#include "kernels.h"
+#include "devstate.h"
+#include "host_util.h"
 
 namespace esa {
 
@@ -224,6 +226,27 @@ int esahrnet_correspondences_cand(const void* cand_dev, const void* hess_dev, co
                                                static_cast<double*>(cw_dev), static_cast<float*>(cpeak_dev),
                                                static_cast<hipStream_t>(stream));
     if (rc) return set_error("correspondences_cand: kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
+// ---- the test hooks on the launchers' process-wide state (devstate.h, conv_s2c32.hip, conv_x6.hip) ------------------------
+int esahrnet_debug_devstate(int* kernel_device_entries, int* devices) {
+    esa::dev_state_counts(kernel_device_entries, devices);
+    return 0;
+}
+
+int esahrnet_debug_set_launch_limit(long long bytes) {
+    esa::set_stream_launch_limit(bytes);
+    return 0;
+}
+
+int esahrnet_debug_set_x6_grid_limit(int workgroups) {
+    esa::set_x6_grid_limit(workgroups);
+    return 0;
+}
+
+int esahrnet_debug_set_cu_limit(int cus) {
+    esa::set_cu_limit(cus);
     return 0;
 }
 

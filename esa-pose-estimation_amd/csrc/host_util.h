@@ -1,5 +1,5 @@
-// host_util.h — what the host files behind the C-ABI share (plan.hip: the entries that take a handle; op_abi.hip: the stand-alone
-// operator entries): the rule from a precision code to a tensor format, the plan switches' reading of the environment, uploads,
+// host_util.h — what the host files behind the C-ABI share (plan.h's units: the entries that take a handle; op_abi.hip: the
+// stand-alone operator entries): the rule from a precision code to a tensor format, the plan switches' reading of the environment, uploads,
 // and the scoped owner of a stand-alone entry's device memory.  Private to csrc; nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@ namespace esa {
 
 inline int pad32(int c) { return (c + 31) & ~31; }
 inline int pad64(int c) { return (c + 63) & ~63; }
+inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }      // byte counts inside a workspace
 
 static constexpr int POOL_SLABS = 64;              // CBAM's pooled partials: slabs per image (fewer where the image has fewer pixels)
 static constexpr int STEM_POOL_SLABS_MAX = 1024;   // pooled partials of the raw stem tensor: slabs reserved per image
@@ -65,6 +66,20 @@ int upload(const std::vector<T>& host, void** dev) {
     HIP_OK(hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
+
+// what an entry refuses about its workspace of at least `need` bytes (`who` names the entry)
+inline int check_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    if (ws_bytes < need) return set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return set_error("%s: workspace must be 256-byte aligned", who);
+    return 0;
+}
+
+// abi_decode.hip: the argument checks its handle-free entries share with the loader entries (`who` names the entry)
+extern const int kFrontendMaxRows;
+int check_boxes_args(const char* who, int m, int frame_h, int frame_w, int scale, int rule);
+int check_crops_args(const char* who, int nframes, int pixel_format, float stdv);
+int check_cov_args(const char* who, const void* cov_dev, const void* info_dev, double cov_floor);
+int check_corr_args(const char* who, int m, int k, int mode);
 
 // plan.hip: what esahrnet_commit and the plan share with the stand-alone entries
 std::vector<float> pack_stem_w(const float* w, int cout, int cin, int coutp);

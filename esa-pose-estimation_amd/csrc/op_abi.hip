@@ -1,6 +1,6 @@
 // op_abi.hip — the stand-alone operator entries of include/esahrnet.h (esahrnet_op_conv .. esahrnet_op_tile_max, test use only):
 // one kernel or one launcher on f32 NCHW tensors of the caller.  None takes a handle or knows esahrnet_ctx (esahrnet_op_desc_get
-// does, and stays in plan.hip).  Each checks its arguments before its first HIP call, reports through esa::set_error, keeps its
+// does, and is in forward.hip).  Each checks its arguments before its first HIP call, reports through esa::set_error, keeps its
 // device memory in a DevScope and ends in DevScope::finish (host_util.h); the format of a precision code is esa::Format.
 #include <algorithm>
 #include <cstdint>

@@ -255,7 +255,7 @@ def test_odd_geometry_head_carries_lo_weights(env):
 
 def test_multistream_executor_matches_single_stream(env, monkeypatch):
     """ESAHRNET_STREAMS=4: the launches a wave schedule finds independent run on side streams that fork from and join
-    into the caller's stream (plan.hip schedule_waves).  Must be bit-identical to the one-stream run, eagerly and
+    into the caller's stream (plan_build.hip schedule_waves).  Must be bit-identical to the one-stream run, eagerly and
     captured into a HIP graph (the capture gets parallel branches), at two shapes, for both variants."""
     for variant, widths, shape in (("seg_hrnet2", (32, 64, 128, 256), (8, 1, 128, 128)),
                                    ("seg_hrnet2", (32, 64, 128, 256), (3, 1, 96, 160)),

@@ -37,6 +37,18 @@ def test_library_exports_every_declared_symbol():
     assert lib.esahrnet_abi_version() == _lib.ABI_VERSION
 
 
+def test_build_lists_every_source_and_header():
+    """build.py compiles SOURCES and rebuilds when a file of SOURCES + HEADERS is newer than the library: a csrc file left out
+    of its list is never compiled, or lets a stale library load silently after an edit."""
+    from esa_pose_estimation_amd import build
+    files = sorted(os.listdir(build.CSRC))
+    assert [f for f in files if f.endswith(".hip")] == sorted(build.SOURCES)
+    assert set(f for f in files if f.endswith(".h")) <= set(build.HEADERS)
+    assert len(set(build.SOURCES + build.HEADERS)) == len(build.SOURCES + build.HEADERS)
+    for f in build.SOURCES + build.HEADERS:
+        assert os.path.isfile(os.path.join(build.CSRC, f)), f
+
+
 def test_no_oracle_or_reference_import_in_product():
     """The product package must not import oracle/ nor read /root/reference."""
     pdir = os.path.join(ROOT, "esa-pose-estimation_amd")

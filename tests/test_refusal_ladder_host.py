@@ -1,4 +1,4 @@
-"""The refusals of the entries that share a body (csrc/plan.hip frames_keypoints, csrc/abi_decode.hip keypoints_gaussfit): the
+"""The refusals of the entries that share a body (csrc/loader.hip frames_keypoints, csrc/abi_decode.hip keypoints_gaussfit): the
 three esahrnet_frames_keypoints* entries and the two stand-alone Gaussian-fit entries, one bad argument at a time and a few
 pairs.  Every call must return, byte for byte, the message recorded in tests/golden/refusal_messages.json from the library
 built before the bodies were shared (tests/golden/make_refusal_golden.py wrote it): equality with a record, not with a

@@ -30,7 +30,7 @@ def shapes(key):
     return [(2, 64, 64), (2, 48, 80), (1, 34, 18) if NETS[key][3] == 1 else (1, 18, 34)]
 
 
-# plan switch -> [(network, precisions it changes the plan of)]: the rule is plan_options() in csrc/plan.hip
+# plan switch -> [(network, precisions it changes the plan of)]: the rule is plan_options() in csrc/plan_build.hip
 _SB, _X6, _H16 = ["bf16x3"], ["fp32"], ["bf16", "fp16"]
 SWITCHES = {
     "UNFUSED": [("hrnet2_w32", _SB)],                        # split format: stem, bblock32 and the fused head
